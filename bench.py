@@ -11,8 +11,15 @@ charged at the reference's cadence: `ms_per_step` = K-step time / K + refresh ti
 
   value  = minibatch transitions consumed per second by the K timed train() steps, summed over ranks (weak scaling:
            every rank draws its own minibatch; gradients and the two actor statistics are all-reduced over RCCL)
-  also   = grad_steps_per_sec (train() calls/s, the north_star's target quantity), rollout_transitions_per_sec
-           (actor + fused ensemble step, rows produced per second), per-kernel-family roofline, CPU baseline.
+  also   = grad_steps_per_sec (train() calls/s, the north_star's target quantity).
+  --full = everything else, in runs of its own after the headline: rollout_transitions_per_sec (actor + fused ensemble
+           step, rows produced per second), per-kernel-family roofline, the other MFMA modes, CPU baseline, and with
+           N > 1 ranks the bit-for-bit replica check (exit 3 if it fails).  Off by default: a plain run sets up, warms up,
+           times the K steps and the refresh, and prints its line.
+
+`--dump-outputs DIR` writes what the last timed step computed (the weights of the critic, its target and the actor, and the
+step's losses; for `--config pretrain` the dynamics model's state_dict and the mean losses) as DIR/<name>.npy in float32 /
+float64.  Every input is seeded, so two builds run with the same arguments can be compared output for output.
 
 `--gpus N` without a torch.distributed launcher starts its N ranks itself (children are spawned before the parent
 touches the GPU); under `python -m torch.distributed.run` the ranks come from the environment.
@@ -184,6 +191,32 @@ def full_refresh(pol, src, tar, bs):
     return n_s * pol.config["src_rollout_length"] + n_t * pol.config["trg_rollout_length"] + n_s
 
 
+def step_outputs(pol):
+    """Device copies of what one train() step hands its caller: the updated critic, target critic and actor, and the
+    step's (q_loss, pi_loss, bc_loss)."""
+    return dict(critic=(pol.q_funcs, pol.q_funcs.blob.clone()), target_critic=(pol.target_q_funcs, pol.target_q_funcs.blob.clone()),
+                actor=(pol.policy, pol.policy.blob.clone()), losses=pol._loss[:3].clone())
+
+
+def dump_outputs(d, arrays):
+    """DIR/<name>.npy for every array (float32, or float64 for integer and float64 data)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(os.path.join(d, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+
+
+def train_step_arrays(snap):
+    from mobody_amd import packing
+    out = {"losses": snap["losses"]}
+    for tag in ("critic", "target_critic", "actor"):
+        net, blob = snap[tag]
+        for p, m in zip(net.prefixes, packing.unpack_mlp(blob, net.in_dim, net.out_dim, net.members)):
+            out.update({f"{tag}.{p}{k}": v for k, v in m.items()})
+    return out
+
+
 def prof_pass(pol, src, tar, bs, steps):
     """Instrumented pass: HIP event pairs around every launch of the heavy kernel families (library hook).
     Runs eagerly (event records are not part of a captured graph); the kernels are the same."""
@@ -220,6 +253,55 @@ def rollout_rate(pol, src, H, reps=5, B=50000):
     _lib.check(lib.mobody_prof_end(ms, cnt, 8), "prof_end")
     total_ms = e0.elapsed_time(e1) / reps
     return B * H / (total_ms * 1e-3), total_ms, ms[3] / (reps * H)
+
+
+def roofline_report(args, fam, dynfwd_ms, S, A, N, Nt, bs):
+    """--full: per-family times of the instrumented pass -> `kernels` and the dominant family's MFMA roofline."""
+    fl = train_flops(S, A, N, Nt)
+    kern = {}
+    for k in ("k_mlp3_fwd", "k_mlp3_bwd", "k_wgrad"):
+        ms, cnt = fam[k]
+        kern[k] = dict(launches_per_step=cnt, ms_per_step=ms, tflops=fl[k] / (ms * 1e-3) / 1e12 if ms > 0 else 0.0)
+    _, _, dyn, rw = macs(S, A)
+    kern["k_dyn_fwd"] = dict(launches_per_step=1, ms_per_step=dynfwd_ms,
+                             tflops=2.0 * (dyn - rw) * 50000 / (dynfwd_ms * 1e-3) / 1e12 if dynfwd_ms > 0 else 0.0)
+    dom = max(("k_mlp3_fwd", "k_mlp3_bwd", "k_wgrad"), key=lambda k: kern[k]["ms_per_step"])
+    d = kern[dom]
+    per_launch_flops = fl[dom] / d["launches_per_step"]
+    avg_ms = d["ms_per_step"] / d["launches_per_step"]
+    peak = effective_peak(fl[dom], wide_flops(S, A, N, Nt)[dom], args.mfma)
+    roofline = dict(kernel=dom, bound="mfma", achieved=per_launch_flops / (avg_ms * 1e-3) / 1e12, peak=peak,
+                    unit="TFLOP/s", traffic=None, avg_launch_ms=avg_ms, launches_per_step=d["launches_per_step"],
+                    flops_per_launch=per_launch_flops,
+                    peak_note="fp32-equivalent TFLOP/s of the kernel's algorithmic flops if its fp32-MFMA part ran at 157.3 TF and "
+                              f"its 256x256 GEMMs ({NPROD[args.mfma]} 16-bit MFMAs per fp32 product) at 2.5 PF" if args.mfma != "f32"
+                              else "dense fp32-input MFMA peak")
+    roofline["frac"] = roofline["achieved"] / roofline["peak"]
+    # HBM bytes of one launch of the dominant kernel: PMC counters need their own rocprofv3 passes (FETCH_SIZE and
+    # WRITE_SIZE cannot share one, and not with a timing run), so the figure can only come from a summary of those
+    # passes over this same command.  It is used ONLY when that summary was measured on exactly this build (source
+    # fingerprint recorded by tools/pmc_traffic.py); anything else is reported as null with the reason.
+    fp = src_fingerprint()
+    roofline["traffic_note"] = f"null: no PMC summary for this build (source fingerprint {fp}) under profiles/"
+    import glob
+    for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_traffic*.json")), reverse=True):
+        try:
+            pm = json.load(open(path))
+        except (OSError, ValueError):
+            continue
+        if not isinstance(pm, dict) or pm.get("src_fingerprint") != fp or pm.get("config") != args.config or pm.get("mfma") != args.mfma:
+            continue
+        sel = [e for e in pm["kernels"] if dom in e["kernel"] and e["fetch_kb_raw"] and e["write_kb"]]
+        if sel and bs == CONFIGS[args.config]["bs"]:
+            top = max(e["launches"] for e in sel)
+            sel = [e for e in sel if 2 * e["launches"] >= top]          # the train() step's launches of this family
+            n = sum(e["launches"] for e in sel)
+            roofline["traffic"] = sum((2.0 * e["fetch_kb_raw"] + e["write_kb"]) * 1024.0 * e["launches"] for e in sel) / n
+            roofline["traffic_note"] = (f"{os.path.relpath(path, ROOT)} (same source fingerprint; FETCH_SIZE doubled: gfx950 "
+                                        "tallies 128-byte read requests at 64 bytes), launch-weighted mean over " + "; ".join(
+                                            f"{e['launches']} x {e['kernel'].strip()} grid {e['grid']}" for e in sel))
+            break
+    return roofline, kern
 
 
 # ------------------------------------------------------------------------------------------------ CPU baseline
@@ -352,6 +434,7 @@ def bench_pretrain(args, dev, world, rank):
     steps, warm = args.steps, max(args.warmup, 3)
     cfg = engine.default_config(S, A, no_vae=0, inverse_sep_reward_loss=0, train_together=0, train_with_src_threshold=1, dynamics_lr=1e-3,
                                 mfma=args.mfma)
+    torch.manual_seed(0); np.random.seed(0)              # the module draws its initial weights from torch's default generators
     m = MOBODYModule(S, A, 256, 7, 5, device=dev, config=cfg)
     dyn = MOBODYEnsembleDynamics(cfg, m, None, None, get_termination_fn(task), penalty_coef=0.1, rng="device", seed=1)
     f16 = dyn.train_precision == 4                      # pre-training follows --mfma when it is f16x2, else exact fp32 MFMA
@@ -369,7 +452,25 @@ def bench_pretrain(args, dev, world, rank):
     stats = dyn._learn_indexed(True, data, idx, b)        # K optimizer steps
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    # per-family times of the same step, eager (event pairs are not part of a captured graph)
+    if args.dump_outputs:                                 # the model after the last timed optimizer step, and its losses
+        dump_outputs(args.dump_outputs, {**{"dynamics." + k_: v for k_, v in m.state_dict().items()},
+                                         "mean_losses": np.asarray(list(stats), np.float64)})
+    fl = pretrain_flops(S, A, b)
+    out = {"metric": "dynamics pre-training optimizer steps/sec (MOBODYEnsembleDynamics.learn, the step before the hot path)",
+           "value": steps / dt, "unit": "optimizer steps/s", "n_gpus": 1, "steps": steps, "warmup": warm,
+           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f16x2 split (fp32-grade), fp32 accumulate" if f16 else "f32", "mfma": "f16x2" if f16 else "f32", "data": "synthetic",
+           "config": {"workload": f"pretrain: walker2d shapes (S={S} A={A}), {b} rows x 7 members per optimizer step, target-domain batches, "
+                                  "device-Philox reparameterisation noise, " + ("HIP-graph replay" if graph else "eager launches (two streams)"),
+                      "name": "pretrain", "rows_per_step": 7 * b, "parallelism": "dp1", "hip_graph": graph},
+           "samples_per_sec": steps * b * 7 / dt, "useful_tflops": fl * steps / dt / 1e12,
+           "frac_f32_mfma_peak_whole_step": fl * steps / dt / (PEAK_F32_TFLOPS * 1e12),
+           "mean_losses": list(stats)}
+    if not args.full:
+        print(json.dumps(out))
+        sys.stdout.flush()
+        return
+    # --full: per-family times of the same step, eager (event pairs are not part of a captured graph)
     lib = _lib.load()
     dyn.train_graph = 0
     k = min(steps, 50)
@@ -378,7 +479,6 @@ def bench_pretrain(args, dev, world, rank):
     ms = (C.c_double * 8)(); cnt = (C.c_int64 * 8)()
     _lib.check(lib.mobody_prof_end(ms, cnt, 8), "prof_end")
     fam = {FAMILIES[i]: dict(ms_per_step=ms[i] / k, launches_per_step=cnt[i] / k) for i in range(3)}
-    fl = pretrain_flops(S, A, b)
     dom = max(fam, key=lambda f: fam[f]["ms_per_step"])
     share = {"k_mlp3_fwd": 1.0 / 3.0, "k_mlp3_bwd": 1.0 / 3.0, "k_wgrad": 1.0 / 3.0}[dom]     # fwd : dX : dW = 1 : 1 : 1
     d = fam[dom]
@@ -392,16 +492,7 @@ def bench_pretrain(args, dev, world, rank):
                                                               " (the pre-training kernels run exact fp32 MFMA)"),
                     traffic_note="null: no PMC pass for this configuration")
     roofline["frac"] = roofline["achieved"] / roofline["peak"]
-    out = {"metric": "dynamics pre-training optimizer steps/sec (MOBODYEnsembleDynamics.learn, the step before the hot path)",
-           "value": steps / dt, "unit": "optimizer steps/s", "n_gpus": 1, "steps": steps, "warmup": warm,
-           "ms_per_step": dt / steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f16x2 split (fp32-grade), fp32 accumulate" if f16 else "f32", "mfma": "f16x2" if f16 else "f32", "data": "synthetic",
-           "config": {"workload": f"pretrain: walker2d shapes (S={S} A={A}), {b} rows x 7 members per optimizer step, target-domain batches, "
-                                  "device-Philox reparameterisation noise, " + ("HIP-graph replay" if graph else "eager launches (two streams)"),
-                      "name": "pretrain", "rows_per_step": 7 * b, "parallelism": "dp1", "hip_graph": graph},
-           "samples_per_sec": steps * b * 7 / dt, "useful_tflops": fl * steps / dt / 1e12,
-           "frac_f32_mfma_peak_whole_step": fl * steps / dt / (PEAK_F32_TFLOPS * 1e12),
-           "roofline": roofline, "kernels": fam, "mean_losses": list(stats)}
+    out["roofline"], out["kernels"] = roofline, fam
     if not args.no_cpu_baseline:
         from oracle import mobody_oracle as O
         threads = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
@@ -437,7 +528,14 @@ def main():
                          "tolerances), bf16x3 (three bf16 terms, six products, same grade), exact fp32, bf16x2 (~6e-6) or plain bf16 (~3e-3)")
     ap.add_argument("--no_mode_sweep", action="store_true", help="skip the short runs of the other MFMA modes")
     ap.add_argument("--graph", type=int, default=1, help="HIP-graph replay of the steady-state step: 0 never, 1 always, 2 auto (minibatches under 4096 rows); with N > 1 ranks the segments between the three all-reduces are replayed")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline: per-kernel "
+                    "roofline, rollout rate, the other MFMA modes, CPU baseline (--no_cpu_baseline / --no_mode_sweep skip "
+                    "those two), replica check with N > 1 ranks")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
 
@@ -484,19 +582,27 @@ def main():
         pol.train(src, tar, bs, None, None)
     barrier()
     t1 = time.perf_counter()
+    snap = None
+    if args.dump_outputs and rank == 0:                   # the last timed step's outputs, before anything else runs
+        snap = step_outputs(pol)
+        torch.cuda.synchronize()
+    t1r = time.perf_counter()
     # one refresh at the reference's full size, timed on its own and charged at its cadence (once per 5000 steps)
     rolled = full_refresh(pol, src, tar, bs)
     barrier()
     t2 = time.perf_counter()
     gc.enable()
-    t = torch.tensor([t1 - t0, t2 - t1], dtype=torch.float64, device=dev)
+    t = torch.tensor([t1 - t0, t2 - t1r], dtype=torch.float64, device=dev)
     if world > 1:
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     dt_steps, dt_refresh = float(t[0]), float(t[1])
     ms_step = dt_steps / args.steps * 1e3 + dt_refresh * 1e3 / REFRESH_EVERY
     losses = pol.losses()
+    if snap is not None:
+        dump_outputs(args.dump_outputs, train_step_arrays(snap))
+        del snap
     replicas_identical = None
-    if world > 1:                                         # data-parallel replicas must still be bit-identical
+    if world > 1 and args.full:                           # data-parallel replicas must still be bit-identical
         h = torch.stack([b.double().sum() for b in (pol.q_funcs.blob, pol.target_q_funcs.blob, pol.policy.blob)])
         hs = [torch.zeros_like(h) for _ in range(world)]
         torch.distributed.all_gather(hs, h)
@@ -504,7 +610,7 @@ def main():
 
     # the other MFMA modes, 100 steps each on the same buffers (extra information; the headline is args.mfma)
     sweep = {}
-    if not args.no_mode_sweep and world == 1:             # single GPU only: the scaling runs time the headline mode alone
+    if args.full and not args.no_mode_sweep and world == 1:   # single GPU only: the scaling runs time the headline mode alone
         for mode in ("f32", "f16x2", "bf16x3", "bf16x2", "bf16"):
             if mode == args.mfma:
                 continue
@@ -522,54 +628,11 @@ def main():
             sweep[mode] = dict(ms_per_step_refresh_excluded=float(tq[0]) / 100 * 1e3, grad_steps_per_sec=100 / float(tq[0]))
             del p2
     # the instrumented passes call train() (collectives when world > 1): every rank runs them, rank 0 reports
-    fam = prof_pass(pol, src, tar, bs, 20)
-    roll_rate, roll_ms, dynfwd_ms = rollout_rate(pol, src, c["H"])
+    if args.full:
+        fam = prof_pass(pol, src, tar, bs, 20)
+        roll_rate, roll_ms, dynfwd_ms = rollout_rate(pol, src, c["H"])
     out = None
     if rank == 0:
-        fl = train_flops(S, A, N, Nt)
-        kern = {}
-        for k in ("k_mlp3_fwd", "k_mlp3_bwd", "k_wgrad"):
-            ms, cnt = fam[k]
-            kern[k] = dict(launches_per_step=cnt, ms_per_step=ms, tflops=fl[k] / (ms * 1e-3) / 1e12 if ms > 0 else 0.0)
-        _, _, dyn, rw = macs(S, A)
-        kern["k_dyn_fwd"] = dict(launches_per_step=1, ms_per_step=dynfwd_ms,
-                                 tflops=2.0 * (dyn - rw) * 50000 / (dynfwd_ms * 1e-3) / 1e12 if dynfwd_ms > 0 else 0.0)
-        dom = max(("k_mlp3_fwd", "k_mlp3_bwd", "k_wgrad"), key=lambda k: kern[k]["ms_per_step"])
-        d = kern[dom]
-        per_launch_flops = fl[dom] / d["launches_per_step"]
-        avg_ms = d["ms_per_step"] / d["launches_per_step"]
-        peak = effective_peak(fl[dom], wide_flops(S, A, N, Nt)[dom], args.mfma)
-        roofline = dict(kernel=dom, bound="mfma", achieved=per_launch_flops / (avg_ms * 1e-3) / 1e12, peak=peak,
-                        unit="TFLOP/s", traffic=None, avg_launch_ms=avg_ms, launches_per_step=d["launches_per_step"],
-                        flops_per_launch=per_launch_flops,
-                        peak_note="fp32-equivalent TFLOP/s of the kernel's algorithmic flops if its fp32-MFMA part ran at 157.3 TF and "
-                                  f"its 256x256 GEMMs ({NPROD[args.mfma]} 16-bit MFMAs per fp32 product) at 2.5 PF" if args.mfma != "f32"
-                                  else "dense fp32-input MFMA peak")
-        roofline["frac"] = roofline["achieved"] / roofline["peak"]
-        # HBM bytes of one launch of the dominant kernel: PMC counters need their own rocprofv3 passes (FETCH_SIZE and
-        # WRITE_SIZE cannot share one, and not with a timing run), so the figure can only come from a summary of those
-        # passes over this same command.  It is used ONLY when that summary was measured on exactly this build (source
-        # fingerprint recorded by tools/pmc_traffic.py); anything else is reported as null with the reason.
-        fp = src_fingerprint()
-        roofline["traffic_note"] = f"null: no PMC summary for this build (source fingerprint {fp}) under profiles/"
-        import glob
-        for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "*pmc_traffic*.json")), reverse=True):
-            try:
-                pm = json.load(open(path))
-            except (OSError, ValueError):
-                continue
-            if not isinstance(pm, dict) or pm.get("src_fingerprint") != fp or pm.get("config") != args.config or pm.get("mfma") != args.mfma:
-                continue
-            sel = [e for e in pm["kernels"] if dom in e["kernel"] and e["fetch_kb_raw"] and e["write_kb"]]
-            if sel and bs == CONFIGS[args.config]["bs"]:
-                top = max(e["launches"] for e in sel)
-                sel = [e for e in sel if 2 * e["launches"] >= top]          # the train() step's launches of this family
-                n = sum(e["launches"] for e in sel)
-                roofline["traffic"] = sum((2.0 * e["fetch_kb_raw"] + e["write_kb"]) * 1024.0 * e["launches"] for e in sel) / n
-                roofline["traffic_note"] = (f"{os.path.relpath(path, ROOT)} (same source fingerprint; FETCH_SIZE doubled per "
-                                            "MI355X_MICROARCH.md), launch-weighted mean over " + "; ".join(
-                                                f"{e['launches']} x {e['kernel'].strip()} grid {e['grid']}" for e in sel))
-                break
         graph_on = bool(args.graph == 1 or (args.graph == 2 and N < 4096))
         out = {
             "metric": "transitions/sec (minibatch rows through train(), refresh amortised at 1/5000) + grad-steps/sec",
@@ -583,8 +646,8 @@ def main():
                            "f16x2": "fp32 operands as two fp16 terms (22 significand bits) with exact power-of-two tile scales, three "
                                     "fp16 MFMAs per fp32 product, fp32 accumulate: fp32-grade (~3e-7 of max|out| from the fp32 kernels); "
                                     "every golden-vector suite of `pytest -m gpu` runs in this mode AND in exact fp32 (tests/conftest.py "
-                                    "`mfma` fixture) at the same tolerances; the exact-fp32 step time of the same run is under "
-                                    "other_mfma_modes.f32",
+                                    "`mfma` fixture) at the same tolerances; with --full the exact-fp32 step time of the same run "
+                                    "is under other_mfma_modes.f32",
                            "bf16x2": "two bf16 terms, three products (~6e-6): throughput mode, not parity grade",
                            "bf16": "plain bf16 MFMA inputs (~3e-3): throughput mode, not parity grade"}[args.mfma],
             "config": {"workload": f"{args.config}: {c['label']} (S={S} A={A}, ensemble 7, rollout_len {c['H']}, N={N} rows per "
@@ -598,11 +661,13 @@ def main():
                              "note": "ms_per_step = steps_ms / steps + refresh.ms / 5000 (one full-size refresh timed after the K steps)"},
             "refresh": {"rows_per_rank": rolled, "ms": dt_refresh * 1e3, "ms_per_step_share": dt_refresh * 1e3 / REFRESH_EVERY,
                         "transitions_per_sec": rolled * world / dt_refresh},
-            "rollout_transitions_per_sec": roll_rate, "rollout_ms_per_call": roll_ms,
-            "roofline": roofline, "kernels": kern, "final_losses": losses, "replicas_identical": replicas_identical,
-            "other_mfma_modes": sweep,
+            "final_losses": losses,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            roofline, kern = roofline_report(args, fam, dynfwd_ms, S, A, N, Nt, bs)
+            out.update({"rollout_transitions_per_sec": roll_rate, "rollout_ms_per_call": roll_ms, "roofline": roofline,
+                        "kernels": kern, "replicas_identical": replicas_identical, "other_mfma_modes": sweep})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(c, cfg)
             out["gpu_over_cpu_grad_steps"] = out["grad_steps_per_sec"] / out["cpu_baseline"]["grad_steps_per_sec"]
     if world > 1:

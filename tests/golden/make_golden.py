@@ -999,7 +999,38 @@ def g18():
         save(f"g18_mopo_{tag}", **out)
 
 
+def g19():
+    """Layout of the dynamics checkpoint the REFERENCE's MOBODYEnsembleDynamics.save writes (mobody_dynamics.py:1158-1161)
+    for the G2 walker model -> g19_dynamics_pth.json: the state_dict's keys in order with shape and dtype, its `_metadata`
+    prefixes, the values of the constant buffers (logvar bounds, elites) and the scaler files.  The 13 MB file itself is too
+    large to commit; tests/test_ckpt_dynamics.py rebuilds one of this layout from the G2 weights."""
+    import json
+    import tempfile
+    g = np.load(os.path.join(HERE, "g234_dynamics_walker.npz"))
+    S, A = int(g["S"]), int(g["A"])
+    m = MOBODYModule(S, A, 256, 7, 5, device="cpu", config=dict(DYN_CFG))
+    m.set_elites([6, 2, 3, 5, 4])
+    dyn = MOBODYEnsembleDynamics(dict(DYN_CFG), m, None, None, get_termination_fn("walker2d-medium-v2"), penalty_coef=0.1)
+    with tempfile.TemporaryDirectory() as d:
+        dyn.save(d)
+        sd = torch.load(os.path.join(d, "dynamics.pth"), weights_only=True)
+        files = sorted(os.listdir(d))
+        scaler = {}
+        for f in files:
+            if f.endswith(".npy"):
+                x = np.load(os.path.join(d, f), allow_pickle=True)
+                scaler[f] = dict(dtype=str(x.dtype), shape=list(x.shape), value=x.tolist() if x.dtype != object else repr(x.item()))
+    const = ("max_logvar", "min_logvar", "max_logvar_latent", "min_logvar_latent", "elites")
+    out = dict(S=S, A=A, files=files, scaler=scaler, metadata=list(getattr(sd, "_metadata", {}).keys()),
+               keys=[dict(name=k, shape=list(v.shape), dtype=str(v.dtype).replace("torch.", "")) for k, v in sd.items()],
+               constants={k: sd[k].tolist() for k in const})
+    path = os.path.join(HERE, "g19_dynamics_pth.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote g19_dynamics_pth", "%.1f KB" % (os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g234", "g5", "g6", "g7", "g8", "g9", "g9b", "g11", "g12", "g13", "g14", "g16", "g17", "g18"]
+    which = sys.argv[1:] or ["g1", "g234", "g5", "g6", "g7", "g8", "g9", "g9b", "g11", "g12", "g13", "g14", "g16", "g17", "g18", "g19"]
     for w in which:
         globals()[w]()

@@ -208,7 +208,7 @@ def test_bench_two_rank_path_keeps_replicas_identical(tmp_path):
     env = dict(os.environ, MOBODY_BENCH_BACKEND="gloo", MASTER_PORT=str(29900 + os.getpid() % 90))
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "c1", "--steps", "6", "--warmup", "2",
-                        "--no_cpu_baseline", "--no_mode_sweep"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no_cpu_baseline", "--no_mode_sweep"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)

@@ -8,7 +8,7 @@ cb = u.get('cpu_baseline') or {}
 o = u['other_mfma_modes']
 out = ["# Round 2, profile C (final round-2 build): unmasked scalar-addressed weight-gradient loop (split precision in every bf16 mode), "
        "row-interleaved replay ring, K-split wide transition heads, counter-free captured step", "",
-       "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 100 --warmup 10 --no_cpu_baseline --no_mode_sweep --graph 0`",
+       "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 100 --warmup 10 --no_cpu_baseline --no_mode_sweep --graph 0`",
        "(bench default `--mfma bf16x3`; 130 train() steps at bs=4096 -> N = 10 240 rows, 7 rollout steps of 50 000 rows and the step-1 refresh).",
        f"Un-profiled default run (`profiles/r02_c_bench_c2.json`): **{u['ms_per_step']:.3f} ms/step** incl. the refresh amortised at 1/5000 ({u['grad_steps_per_sec']:.0f} grad-steps/s), "
        f"{u['value']/1e6:.1f} M minibatch transitions/s, rollout {u['rollout_transitions_per_sec']/1e6:.1f} M transitions/s; same run, other modes (100 steps each, refresh excluded): "

@@ -6,7 +6,7 @@ rows = list(csv.DictReader(open(stats)))
 d, u = json.load(open(prof_json)), json.load(open(bench_json))
 c = u.get("cpu_baseline") or {}
 out = [f"# {title}", "",
-       "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 100 --warmup 10 --no_cpu_baseline --graph 0`",
+       "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 100 --warmup 10 --no_cpu_baseline --graph 0`",
        "(130 train() steps at bs=4096 -> N=10240 rows, plus 7 rollout steps of 50 000 rows and the step-1 refresh).",
        f"bench line of the same run (under the profiler, eager): {d['ms_per_step']:.3f} ms/step; un-profiled default run: "
        f"profiles/{tag}_bench_bs4096.json ({u['ms_per_step']:.3f} ms/step, {u['value']/1e6:.1f} M transitions/s, "

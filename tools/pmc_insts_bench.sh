@@ -1,11 +1,11 @@
 # per-kernel instruction counts of the c2 train step (eager bench under rocprofv3 --pmc): bash tools/pmc_insts_bench.sh
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-O=gpurun_out/pmc_insts_bench; mkdir -p $O
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $O/a -- python3 bench.py --steps 40 --warmup 3 --no_cpu_baseline --no_mode_sweep --graph 0 > /dev/null 2> $O/a.err
+export O=${OUT:-bench_out}/pmc_insts_bench; mkdir -p $O
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --output-format csv -d $O/a -- python3 bench.py --full --steps 40 --warmup 3 --no_cpu_baseline --no_mode_sweep --graph 0 > /dev/null 2> $O/a.err
 python - <<'PY'
-import csv, glob, collections
+import csv, glob, collections, os
 acc=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.defaultdict(set)
-for f in glob.glob("gpurun_out/pmc_insts_bench/a/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(os.environ["O"] + "/a/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k=(r["Kernel_Name"].split("(")[0][:46], r["Grid_Size"]); acc[k][r["Counter_Name"]]+=float(r["Counter_Value"]); n[k].add(r["Dispatch_Id"])
 for k,c in sorted(acc.items(), key=lambda kv:-kv[1].get("SQ_INSTS_VALU",0)):

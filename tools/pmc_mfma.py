@@ -1,6 +1,6 @@
 """MFMA-pipe utilisation per kernel from one rocprofv3 counter pass:
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_COEXEC_CYCLES --output-format csv -d gpurun_out/pmc_m -- python3 bench.py ...
-    python tools/pmc_mfma.py gpurun_out/pmc_m profiles/<tag>_pmc_mfma.json
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_COEXEC_CYCLES --output-format csv -d OUT/pmc_m -- python3 bench.py --full ...
+    python tools/pmc_mfma.py OUT/pmc_m profiles/<tag>_pmc_mfma.json
 SQ_VALU_MFMA_BUSY_CYCLES counts, summed over the chip's 1024 SIMDs, the cycles a SIMD's matrix pipe is busy (32 per
 v_mfma_f32_32x32x16_bf16, 64 per v_mfma_f32_32x32x2_f32: MI355X guide, cycle constants); GRBM_GUI_ACTIVE is the dispatch's
 cycles summed over the 8 XCDs.  Two denominators:

@@ -1,10 +1,10 @@
 """HBM-side traffic per kernel launch from two rocprofv3 counter passes (FETCH_SIZE and WRITE_SIZE cannot share a pass:
 MI355X_MICROARCH.md "rocprofv3 PMC slots").  Collect with
 
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -- python3 bench.py --steps 40 --warmup 3 --no_cpu_baseline --graph 0
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_w -- python3 bench.py --steps 40 --warmup 3 --no_cpu_baseline --graph 0
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d OUT/pmc_f -- python3 bench.py --full --steps 40 --warmup 3 --no_cpu_baseline --graph 0
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d OUT/pmc_w -- python3 bench.py --full --steps 40 --warmup 3 --no_cpu_baseline --graph 0
 
-then  python tools/pmc_traffic.py gpurun_out/pmc_f gpurun_out/pmc_w profiles/<tag>_pmc_traffic.json [config] [mfma]
+then  python tools/pmc_traffic.py OUT/pmc_f OUT/pmc_w profiles/<tag>_pmc_traffic.json [config] [mfma]
 The summary records the source fingerprint of the build (bench.src_fingerprint): bench.py only quotes it for the same build.
 Values are KiB as rocprofv3 reports them (fetch_kb_raw is NOT yet doubled; gfx950 tallies 128-B read requests at 64 B)."""
 import collections, csv, glob, json, os, sys
