@@ -452,6 +452,44 @@ int64_t mobody_dyn_validate_workspace(int S, int A, int64_t B);
 int mobody_dyn_validate(const float* dyn_blob, int S, int A, const float* obs, const float* act, const float* next_obs,
                         const float* rew, int64_t B, int use_trg, float* out, float* workspace, void* stream);
 
+/* ---- dynamics pre-training of the MOPO ablation (config mopo = 1: mean_e = s + MLP_e([s, a]), mobody_module.py:114-118,
+ *      133-137,218-219,251-254,264-266; learn() / validate() as above) ----------------------------------------------------
+ * ONE parameter blob: the 7-member MLP za_src1-3 (S+A -> 256 -> 256 -> S) in mobody_mlp_layout(S + A, S, 7) format at off_dyn
+ * (the format of the inference path's mopo blob), then the reward head reward_model1-3 (2S+A -> 256 -> 256 -> 2) at off_rw.
+ * Both domains train the same MLP (encode_trg_action delegates to encode_src_action); za_trg*, zs*, transition* and za_de_*
+ * take no part.  Gradients and both Adam moments use the same layout, the T blob holds the two regions' transposes. */
+typedef struct MobodyPretrainMopoLayout {
+  int32_t S, A, _pad0, _pad1;
+  MobodyMlpLayout dyn, rw;
+  int64_t off_dyn, off_rw, total_floats;          /* float offsets inside the parameter blob */
+  int64_t t_off_dyn, t_off_rw, t_total_floats;    /* T blob */
+} MobodyPretrainMopoLayout;
+int mobody_pretrain_mopo_layout(int S, int A, MobodyPretrainMopoLayout* out);
+/* precision 0 (exact fp32) or 4 (f16x2), as for the latent entry points above */
+int mobody_pretrain_mopo_transpose(int S, int A, const float* blob, float* blob_T, int precision, void* stream);
+int64_t mobody_pretrain_mopo_workspace(int S, int A, int64_t b);
+/* Loss and gradients of one learn() batch: xenc[7][2b][S] / act[7][b][A] / rew[7][b] as mobody_pretrain_gather writes them,
+ * noise [7][b][S] = the fake-next-state draw (NULL -> device Philox stream 22 at (seed, call)).  b_global as for
+ * mobody_pretrain_grads.  loss_out[5] = (loss, transition_loss, encoder_loss, recon_loss = 0, kl_loss). */
+int mobody_pretrain_mopo_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
+                               const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
+                               const float* noise, uint32_t seed, uint32_t call, float* grad, float* loss_out,
+                               float* workspace, int precision, void* stream);
+/* Single-GPU fused form (the reductions apply Adam): t = the 1-based step count shared by both regions; t_dev (nullable):
+ * DEVICE int64 read instead of t; call_dev (nullable): DEVICE int64 added to `call`; loss_acc (nullable): DEVICE float[5]
+ * += loss_out -- as mobody_pretrain_update, for graph replay. */
+int mobody_pretrain_mopo_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
+                                const float* xenc, const float* act, const float* rew, const float* noise, uint32_t seed,
+                                uint32_t call, const int64_t* call_dev, float* m, float* v, int64_t t, const int64_t* t_dev,
+                                float lr, float* loss_out, float* loss_acc, float* workspace, int precision, void* stream);
+/* torch.optim.Adam step of both regions with the one step count t (every learn() step gives both a gradient). */
+int mobody_pretrain_mopo_adam(int S, int A, float* blob, float* blob_T, const float* grad, float* m, float* v, int64_t t,
+                              float lr, float grad_scale, int precision, void* stream);
+/* validate() of a mopo model: the reward head from the inference blob (mobody_dyn_layout), the MLP from the mopo blob
+ * (mobody_mlp_layout(S + A, S, 7)); outputs and workspace as mobody_dyn_validate. */
+int mobody_dyn_validate_mopo(const float* dyn_blob, const float* mopo_blob, int S, int A, const float* obs, const float* act,
+                             const float* next_obs, const float* rew, int64_t B, float* out, float* workspace, void* stream);
+
 /* (Re)build the transposed blob from a parameter blob (after loading a checkpoint); `precision` selects the format of
  * the W2 / W2^T planes it writes (the mode the net will be evaluated in). */
 int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,

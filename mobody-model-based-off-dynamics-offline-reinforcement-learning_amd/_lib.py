@@ -41,6 +41,12 @@ class MobodyPretrainLayout(C.Structure):
                 ("t_off_rw", i64), ("t_total_floats", i64)]
 
 
+class MobodyPretrainMopoLayout(C.Structure):
+    _fields_ = [("S", i32), ("A", i32), ("_pad0", i32), ("_pad1", i32), ("dyn", MobodyMlpLayout), ("rw", MobodyMlpLayout),
+                ("off_dyn", i64), ("off_rw", i64), ("total_floats", i64), ("t_off_dyn", i64), ("t_off_rw", i64),
+                ("t_total_floats", i64)]
+
+
 class MobodyBufferView(C.Structure):
     _fields_ = [("state", vp), ("action", vp), ("next_state", vp), ("reward", vp), ("not_done", vp), ("pitch", i64)]
 
@@ -127,6 +133,15 @@ PROTOTYPES = {
                                         vp, vp, vp, C.c_int, f32, f32, vp]),
     "mobody_pretrain_adam": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, i64, f32, f32, C.c_int, C.c_int, i64, vp]),
     "mobody_pretrain_za_adam": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, f32, f32, vp]),
+    "mobody_pretrain_mopo_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(MobodyPretrainMopoLayout)]),
+    "mobody_pretrain_mopo_transpose": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, vp]),
+    "mobody_pretrain_mopo_workspace": (i64, [C.c_int, C.c_int, i64]),
+    "mobody_pretrain_mopo_grads": (C.c_int, [C.c_int, C.c_int, i64, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp,
+                                             vp, C.c_int, vp]),
+    "mobody_pretrain_mopo_update": (C.c_int, [C.c_int, C.c_int, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp,
+                                              i64, vp, f32, vp, vp, vp, C.c_int, vp]),
+    "mobody_pretrain_mopo_adam": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, f32, f32, C.c_int, vp]),
+    "mobody_dyn_validate_mopo": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp]),
     "mobody_dyn_validate_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_dyn_validate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, C.c_int, vp, vp, vp]),
 }
@@ -203,4 +218,10 @@ def mlp_layout(in_dim, out_dim, members):
 def pretrain_layout(S, A):
     L = MobodyPretrainLayout()
     check(load().mobody_pretrain_layout(S, A, C.byref(L)), "mobody_pretrain_layout")
+    return L
+
+
+def pretrain_mopo_layout(S, A):
+    L = MobodyPretrainMopoLayout()
+    check(load().mobody_pretrain_mopo_layout(S, A, C.byref(L)), "mobody_pretrain_mopo_layout")
     return L

@@ -64,7 +64,8 @@ class MOBODYEnsembleDynamics(object):
         self.train_precision = 4 if self.precision == 4 else 0
         self._calls = 0
         self.noise_fn = None          # optional hook: noise_fn((7, B, S)) -> unit normals (tests)
-        self.train_noise_fn = None    # optional hook: b -> (noise6[6,7,b,16], noise7[7,b,S]) device tensors (tests)
+        self.train_noise_fn = None    # optional hook: b -> (noise6[6,7,b,16], noise7[7,b,S]) device tensors (tests); mopo
+                                      # model: b -> noise[7,b,S], the fake-next-state draw (its only noise)
         self._ws = None
         self._pre_ws_by_b, self._pre_bufs_by_b, self._train_calls = {}, {}, 0
         # 1: replay full pre-training batches as one HIP graph (1 GPU, device noise).  Off by default since round 3: the step is
@@ -130,6 +131,16 @@ class MOBODYEnsembleDynamics(object):
     # ------------------------------------------------------------------ pre-training (mobody_dynamics.py:594-653,731-978,1113-1156)
     def _check_pretrain_config(self):
         cfg = self.config
+        if getattr(self.model, "mopo", False):
+            for k, bad in (("train_together", bool(cfg.get("train_together"))),
+                           ("inverse_sep_reward_loss", bool(cfg.get("inverse_sep_reward_loss"))),
+                           ("train_with_src_threshold", cfg.get("train_with_src_threshold", 1) != 1),
+                           ("latent_reward", bool(cfg.get("latent_reward")))):
+                if bad:
+                    raise NotImplementedError(f"pre-training of the mopo = 1 model is built for the reference's default learn() "
+                                              f"only: {k} = {cfg.get(k)} together with mopo is not supported")
+            if self._world()[0] > 1:
+                raise NotImplementedError("pre-training of the mopo = 1 model runs on one GPU (data parallel is not built for it)")
         if cfg.get("latent_reward"):
             raise NotImplementedError("latent_reward = 1 is outside the accelerated pre-training path (reference default 0; the "
                                       "reference's own learn() raises TypeError with it: reward_loss_with_latent calls "
@@ -171,6 +182,8 @@ class MOBODYEnsembleDynamics(object):
         """One optimizer step on the rows already laid out as the kernels want them (zero_grad, backward, Adam.step).
         Data parallel: this rank holds rows [lo_rel, lo_rel + b) of the batch's b_global rows."""
         m = self.model
+        if m.mopo:
+            return self._learn_batch_mopo(use_trg, xenc, act, rew, b)
         st = m.train_state(self.train_precision)
         S, A = m.obs_dim, m.action_dim
         ws = self._ws_for(max(b, 1))
@@ -200,6 +213,22 @@ class MOBODYEnsembleDynamics(object):
         m.mark_trained()
         return self._pre_loss
 
+    def _learn_batch_mopo(self, use_trg, xenc, act, rew, b):
+        """_learn_batch of the mopo model (one GPU): gradients, then one Adam step of the MLP and the reward head."""
+        m = self.model
+        st = m.mopo_train_state(self.train_precision)
+        S, A = m.obs_dim, m.action_dim
+        self._train_calls += 1
+        noise = self.train_noise_fn(b) if self.train_noise_fn is not None else None
+        ops.pretrain_mopo_grads(S, A, b, use_trg, self._enc_coef(), st["blob"], st["blob_T"], xenc, act, rew, st["grad"],
+                                self._pre_loss, self._ws_for(b), noise=noise, seed=(self.seed + 77) & 0xFFFFFFFF,
+                                call=self._train_calls, precision=self.train_precision)
+        st["t"] += 1
+        ops.pretrain_mopo_adam(S, A, st["blob"], st["blob_T"], st["grad"], st["m"], st["v"], st["t"], self._lr(),
+                               precision=self.train_precision)
+        m.mark_trained()
+        return self._pre_loss
+
     def _gather_bufs(self, b):
         """The batch tensors of the bootstrap gather, kept per batch size (an eager pass would allocate three per step)."""
         if b not in self._pre_bufs_by_b:
@@ -211,16 +240,27 @@ class MOBODYEnsembleDynamics(object):
 
     def _ws_for(self, b):
         if b not in self._pre_ws_by_b:
-            self._pre_ws_by_b[b] = ops.pretrain_workspace(self.model.obs_dim, self.model.action_dim, b, self.model.device)
+            ws = ops.pretrain_mopo_workspace if self.model.mopo else ops.pretrain_workspace
+            self._pre_ws_by_b[b] = ws(self.model.obs_dim, self.model.action_dim, b, self.model.device)
         return self._pre_ws_by_b[b]
 
     def _learn_batch_fused(self, use_trg, xenc, act, rew, b, acc=None):
         """Single-GPU form of _learn_batch: the gradient reductions apply Adam themselves (mobody_pretrain_update); `acc`
         (device float[5]): the step's last launch adds the loss vector onto it (no launch of its own for learn()'s sums)."""
         m = self.model
-        st = m.train_state(self.train_precision)
         S, A = m.obs_dim, m.action_dim
         ws = self._ws_for(b)
+        if m.mopo:
+            st = m.mopo_train_state(self.train_precision)
+            self._train_calls += 1
+            noise = self.train_noise_fn(b) if self.train_noise_fn is not None else None
+            st["t"] += 1
+            ops.pretrain_mopo_update(S, A, b, use_trg, self._enc_coef(), st["blob"], st["blob_T"], xenc, act, rew, st["m"], st["v"],
+                                     st["t"], self._lr(), self._pre_loss, ws, noise=noise, seed=(self.seed + 77) & 0xFFFFFFFF,
+                                     call=self._train_calls, precision=self.train_precision, loss_acc=acc)
+            m.mark_trained()
+            return None if acc is not None else self._pre_loss
+        st = m.train_state(self.train_precision)
         self._train_calls += 1
         n6 = n7 = None
         if self.train_noise_fn is not None:
@@ -238,7 +278,7 @@ class MOBODYEnsembleDynamics(object):
         ~22 launches): the batch offset into the bootstrap matrix, the noise call id and the Adam step counts live in
         device words that the graph advances itself.  Device-RNG noise only.  Returns the summed loss vector."""
         m = self.model
-        st = m.train_state(self.train_precision)
+        st = m.mopo_train_state(self.train_precision) if m.mopo else m.train_state(self.train_precision)
         S, A, b, dev = m.obs_dim, m.action_dim, batch_size, m.device
         d = bool(use_trg)
         ws = self._ws_for(b)
@@ -248,7 +288,8 @@ class MOBODYEnsembleDynamics(object):
                self._pre_loss.data_ptr(), float(self._lr()), float(self._enc_coef()), int(self.seed), self.train_precision) \
             + tuple(t.data_ptr() for t in data) + tuple(st[k].data_ptr() for k in ("blob", "blob_T", "m", "v"))
         c = self._pre_ctr                                  # [batch index, call, t_main, t_za]: one launch advances all four
-        c.copy_(torch.tensor([-1, self._train_calls, st["t_main"], st["t_za"][d]], dtype=torch.int64), non_blocking=False)
+        t_now = [st["t"], 0] if m.mopo else [st["t_main"], st["t_za"][d]]        # (mopo: [batch index, call, t, unused])
+        c.copy_(torch.tensor([-1, self._train_calls] + t_now, dtype=torch.int64), non_blocking=False)
         self._pre_acc.zero_()
         if key not in self._pre_graphs:
             bufs = (torch.empty(7, 2 * b, S, dtype=torch.float32, device=dev), torch.empty(7, b, A, dtype=torch.float32, device=dev),
@@ -257,6 +298,12 @@ class MOBODYEnsembleDynamics(object):
             def body():
                 ops.counter_add(c, 1)
                 ops.pretrain_gather(data[0], data[1], data[2], data[3], idx, 0, b, out=bufs, start_dev=c[0:1])
+                if m.mopo:
+                    ops.pretrain_mopo_update(S, A, b, d, self._enc_coef(), st["blob"], st["blob_T"], bufs[0], bufs[1], bufs[2],
+                                             st["m"], st["v"], 1, self._lr(), self._pre_loss, ws, seed=(self.seed + 77) & 0xFFFFFFFF,
+                                             call=0, call_dev=c[1:2], t_dev=c[2:3], precision=self.train_precision,
+                                             loss_acc=self._pre_acc)
+                    return
                 ops.pretrain_update(S, A, b, d, self._enc_coef(), st["blob"], st["blob_T"], bufs[0], bufs[1], bufs[2],
                                     st["m"], st["v"], 1, 1, self._lr(), self._pre_loss, ws,
                                     seed=(self.seed + 77) & 0xFFFFFFFF, call=0, call_dev=c[1:2], t_dev=c[2:4],
@@ -277,7 +324,10 @@ class MOBODYEnsembleDynamics(object):
         for _ in range(n_full - first):
             g.replay()
         self._train_calls += n_full
-        st["t_main"] += n_full; st["t_za"][d] += n_full
+        if m.mopo:
+            st["t"] += n_full
+        else:
+            st["t_main"] += n_full; st["t_za"][d] += n_full
         self.total_steps = getattr(self, "total_steps", 0) + n_full
         m.mark_trained()
         return self._pre_acc
@@ -541,8 +591,12 @@ class MOBODYEnsembleDynamics(object):
         m.training = False
         m.inference()
         f = lambda x: torch.as_tensor(x, dtype=torch.float32).to(m.device).contiguous()
-        out = ops.dyn_validate(m.packed(), m.obs_dim, m.action_dim, f(holdout_obss), f(holdout_actions), f(holdout_next_obss),
-                               f(holdout_rewards), use_trg_data).cpu().numpy()
+        if m.mopo:                                        # mean = s + MLP(s, a) for both domains (:1124-1129 via :264-266)
+            out = ops.dyn_validate_mopo(m.packed(), m.packed_mopo()[0], m.obs_dim, m.action_dim, f(holdout_obss),
+                                        f(holdout_actions), f(holdout_next_obss), f(holdout_rewards)).cpu().numpy()
+        else:
+            out = ops.dyn_validate(m.packed(), m.obs_dim, m.action_dim, f(holdout_obss), f(holdout_actions), f(holdout_next_obss),
+                                   f(holdout_rewards), use_trg_data).cpu().numpy()
         m.uninference()
         return list(out[:7]), list(out[7:])
 

@@ -6,7 +6,8 @@ Keeps the reference constructor signature (:50-64), the parameter names/shapes o
 `random_elite_idxs` :355-357) and `inference()/uninference()`.  The forward passes run in the HIP
 library on a packed copy of the weights (`packed()`, refreshed whenever the tensors change).
 Pre-training (`MOBODYEnsembleDynamics.train/learn`) works on a second packed copy, the TRAINING blob
-(`train_state()`: csrc/pretrain.hip's MobodyPretrainLayout with its transposes, gradient and Adam moments);
+(`train_state()`: csrc/pretrain.hip's MobodyPretrainLayout with its transposes, gradient and Adam moments; a
+config['mopo'] = 1 model uses `mopo_train_state()`, MobodyPretrainMopoLayout: za_src1-3 + the reward head);
 while it is ahead of the reference-layout tensors `_p` it is the master, and every reader of `_p`
 (`state_dict`, `packed`, `update_save`) first pulls it back (`_sync_from_train`).  The action decoders
 `za_de_*` take no part in any loss (their .grad is None in the reference) and are only carried in the state_dict.
@@ -157,8 +158,8 @@ class MOBODYModule(object):
         """dict(blob, blob_T, grad, m, v, t_main, t_za={False: .., True: ..}, prec) of the packed training copy; `precision`
         (0 exact fp32 | 4 f16x2; None = leave as is) = the mode of the coming optimizer steps: the T blob carries that mode's W2 planes."""
         if self.mopo:
-            raise NotImplementedError("pre-training with config['mopo'] = 1 is outside the accelerated path "
-                                      "(inference / rollouts / checkpoints of such a model are supported)")
+            raise NotImplementedError("train_state() is the latent model's training copy; a config['mopo'] = 1 model "
+                                      "trains through mopo_train_state()")
         if self._train is None:
             blob = packing.pack_pretrain(self._p, self.obs_dim, self.action_dim, self.device)
             z = lambda: torch.zeros_like(blob)
@@ -170,6 +171,24 @@ class MOBODYModule(object):
             self._train["prec"] = precision
         return self._train
 
+    def mopo_train_state(self, precision=None):
+        """The MOPO ablation's training copy: dict(blob, blob_T, grad, m, v, t, prec) in csrc/pretrain.hip's
+        MobodyPretrainMopoLayout (za_src1-3 and the reward head in one blob; both take a gradient every learn() step, so
+        one Adam step count t).  Same life cycle as train_state(): the master copy while it is ahead of `_p`."""
+        if not self.mopo:
+            raise RuntimeError("mopo_train_state() is the training copy of a config['mopo'] = 1 model; use train_state()")
+        if self._train is None:
+            blob = packing.pack_pretrain_mopo(self._p, self.obs_dim, self.action_dim, self.device)
+            z = lambda: torch.zeros_like(blob)
+            precision = precision or 0
+            self._train = dict(blob=blob, blob_T=ops.pretrain_mopo_transpose(blob, self.obs_dim, self.action_dim, precision=precision),
+                               grad=z(), m=z(), v=z(), t=0, prec=precision)
+        elif precision is not None and self._train["prec"] != precision:
+            ops.pretrain_mopo_transpose(self._train["blob"], self.obs_dim, self.action_dim, out=self._train["blob_T"],
+                                        precision=precision)
+            self._train["prec"] = precision
+        return self._train
+
     def mark_trained(self):
         """The training blob moved (an optimizer step ran): `_p` and the inference blob are stale until pulled."""
         self._train_ahead = True
@@ -177,16 +196,19 @@ class MOBODYModule(object):
 
     def _sync_from_train(self):
         if self._train is not None and self._train_ahead:
-            packing.unpack_pretrain(self._train["blob"], self.obs_dim, self.action_dim, into=self._p)
+            unpack = packing.unpack_pretrain_mopo if self.mopo else packing.unpack_pretrain
+            unpack(self._train["blob"], self.obs_dim, self.action_dim, into=self._p)
             self._train_ahead = False
             self._blob = None
 
     def _push_to_train(self):
         """`_p` changed under a live training blob (load_save): re-pack the weights, keep the Adam state."""
         if self._train is not None:
-            self._train["blob"].copy_(packing.pack_pretrain(self._p, self.obs_dim, self.action_dim, self.device))
-            ops.pretrain_transpose(self._train["blob"], self.obs_dim, self.action_dim, out=self._train["blob_T"],
-                                   precision=self._train["prec"])
+            S, A = self.obs_dim, self.action_dim
+            pack, transpose = ((packing.pack_pretrain_mopo, ops.pretrain_mopo_transpose) if self.mopo
+                               else (packing.pack_pretrain, ops.pretrain_transpose))
+            self._train["blob"].copy_(pack(self._p, S, A, self.device))
+            transpose(self._train["blob"], S, A, out=self._train["blob_T"], precision=self._train["prec"])
             self._train_ahead = False
 
     # ---- HIP side ----

@@ -967,18 +967,12 @@ extern "C" int64_t mobody_dyn_validate_workspace(int S, int A, int64_t B) {
   return (int64_t)NENS * B * S + (int64_t)NENS * B;
 }
 
-extern "C" int mobody_dyn_validate(const float* dyn_blob, int S, int A, const float* obs, const float* act,
-                                   const float* next_obs, const float* rew, int64_t B, int use_trg, float* out,
-                                   float* workspace, void* stream) {
-  MobodyDynLayout L;
-  int rc = mobody_dyn_layout(S, A, &L);
-  if (rc) return rc;
-  MB_REQUIRE(B >= 1, "mobody_dyn_validate: B < 1");
-  MB_REQUIRE(dyn_blob && obs && act && next_obs && rew && out && workspace, "mobody_dyn_validate: null pointer");
+// validate()'s reward head on [s, a, mean_e] and the per-member losses, once the means are in workspace[0 .. 7 B S)
+static int dyn_validate_tail(const float* dyn_blob, const MobodyDynLayout& L, int S, int A, const float* obs, const float* act,
+                             const float* next_obs, const float* rew, int64_t B, float* out, float* workspace, void* stream) {
+  int rc = 0;
   float* mean = workspace;
   float* r_mu = workspace + (int64_t)NENS * B * S;
-  rc = mobody_dyn_forward(dyn_blob, nullptr, 0, S, A, obs, act, B, use_trg, mean, stream);       // inference mode: z = mu (:1126-1129), exact fp32
-  if (rc) return rc;
   // reward head of member e on [s, a, mean_e]   (:1137: encode_reward(obs.repeat(7), act.repeat(7), mean))
   Mlp3FwdArgs m{};
   m.src[0] = obs; m.ld[0] = S; m.n[0] = S;
@@ -996,4 +990,410 @@ extern "C" int mobody_dyn_validate(const float* dyn_blob, int S, int A, const fl
   hipLaunchKernelGGL(k_pre_validate, dim3(NENS), dim3(256), 0, as_stream(stream), mean, next_obs, r_mu, rew, (long long)B, S, out);
   MB_LAUNCH_OK("k_pre_validate");
   return 0;
+}
+
+extern "C" int mobody_dyn_validate(const float* dyn_blob, int S, int A, const float* obs, const float* act,
+                                   const float* next_obs, const float* rew, int64_t B, int use_trg, float* out,
+                                   float* workspace, void* stream) {
+  MobodyDynLayout L;
+  int rc = mobody_dyn_layout(S, A, &L);
+  if (rc) return rc;
+  MB_REQUIRE(B >= 1, "mobody_dyn_validate: B < 1");
+  MB_REQUIRE(dyn_blob && obs && act && next_obs && rew && out && workspace, "mobody_dyn_validate: null pointer");
+  rc = mobody_dyn_forward(dyn_blob, nullptr, 0, S, A, obs, act, B, use_trg, workspace, stream);  // inference mode: z = mu (:1126-1129), exact fp32
+  if (rc) return rc;
+  return dyn_validate_tail(dyn_blob, L, S, A, obs, act, next_obs, rew, B, out, workspace, stream);
+}
+
+// ================================================================================================================
+// MOPO ablation (config['mopo'] = 1): one optimizer step of learn() for the plain ensemble MLP  mu_e = s + f_e([s, a])
+// (mobody_module.py:114-118,218-219,251-254,264-266,288-289).  encode_state and encode_transition are identities, so in
+// the terms of the latent step above (mobody_dynamics.py:300-384):
+//
+//   T       = transition_loss = sum_e mean_{b,S} (mu_e - s'_e)^2
+//   encoder = 100 * 0 (recon) + KL + T (latent consistency),  KL = 0.05 sum_e -1/2 mean(1 + x - x^2 - e^x), x = s and x = s'
+//   R       = sum_e mean (r_e(s, a, fake) - r)^2 + sum_e mean (r_e(s, a, s') - r)^2,   fake = mu + eps * std_e(mu)
+//   loss    = T + c_e * encoder + c_r * R
+//
+// KL has no parameter; both domains train the one MLP za_src1-3 (encode_trg_action delegates to encode_src_action), so the
+// parameters are ONE blob: the MLP region (mobody_mlp_layout(S + A, S, 7)) then the reward head's region.  Per step: the MLP
+// forward on b rows per member, k_mopo_rows (mu, T / KL partials, ensemble std, fake, the reward head's [s,a,fake | s,a,s']
+// rows), the reward head forward + k_pre_reward_seed + backward (its input gradient is d loss / d fake), k_mopo_dmu (d mu
+// with the chain rule through the std across members = the MLP's dz3), the MLP backward, weight gradients (+ fused Adam)
+// and the loss.  The reward head's weight gradients run on the side stream next to the MLP's backward.
+// ================================================================================================================
+namespace mobody {
+
+struct MopoRow {
+  int S, A, Np3;
+  long long b;
+  float inv_bg, ce;
+  const float* xenc;         // [E][2b][S]   s rows, then s' rows
+  const float* act;          // [E][b][A]
+  const float* noise;        // [E][b][S] or null -> Philox stream STREAM_PRE + 6 at (seed, call + call_dev[0])
+  uint32_t seed, call;
+  const long long* call_dev;
+  const float* f;            // [E][b][S]    MLP output (mu = s + f)
+  float* xrw;                // [E][2b][2S+A]
+  float* fnz;                // [E][b][S]    the noise draws of this step (k_mopo_rows -> k_mopo_dmu)
+  const float* dfake;        // [E][2b][S]   reward head input gradient, rows < b
+  float* dz3;                // [E][b][Np3]
+  float* lossp;              // [n_rt][2] (T, KL) partials
+};
+
+__device__ __forceinline__ float mopo_noise(const MopoRow& a, long long i) {
+  if (a.noise) return a.noise[i];
+  const uint32_t call = a.call + (a.call_dev ? (uint32_t)a.call_dev[0] : 0u);
+  return rng_normal_at(a.seed, STREAM_PRE + 6, call, (uint64_t)i);
+}
+
+// one thread per (member, row, state dim): mu over the seven members -> std, fake, the reward head's rows, T / KL partials
+__global__ __launch_bounds__(256) void k_mopo_rows(MopoRow a) {
+  __shared__ float sm[8];
+  const int S = a.S, A = a.A, W = 2 * S + A;
+  const long long b = a.b;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool ok = i < NENS * b * S;
+  const long long ic = ok ? i : 0;
+  const int e = (int)(ic / (b * S));
+  const long long row = (ic - (long long)e * b * S) / S;
+  const int d = (int)(ic - ((long long)e * b + row) * S);
+  float mu[NENS], avg = 0.f;
+#pragma unroll
+  for (int k = 0; k < NENS; ++k) {
+    mu[k] = a.xenc[((long long)k * 2 * b + row) * S + d] + a.f[((long long)k * b + row) * S + d];
+    avg += mu[k];
+  }
+  avg *= (1.f / NENS);
+  float var = 0.f, mine = 0.f;
+#pragma unroll
+  for (int k = 0; k < NENS; ++k) { const float t = mu[k] - avg; var += t * t; mine = k == e ? mu[k] : mine; }
+  const float sd = sqrtf(var * (1.f / (NENS - 1)));                         // torch.std over the ensemble axis, unbiased (:353)
+  const float s = a.xenc[((long long)e * 2 * b + row) * S + d], s2 = a.xenc[((long long)e * 2 * b + b + row) * S + d];
+  const float aj0 = a.act[((long long)e * b + row) * A + (d < A ? d : 0)];
+  const float nz = mopo_noise(a, ic);
+  float tr = 0.f, kl = 0.f;
+  if (ok) {
+    const float r = mine - s2;
+    tr = r * r;
+    kl = -0.5f * (1.f + s - s * s - expf(s)) + -0.5f * (1.f + s2 - s2 * s2 - expf(s2));    // get_kl_loss(s, s) + get_kl_loss(s', s')
+    float* x = a.xrw + (long long)e * 2 * b * W;
+    x[row * W + d] = s; x[(b + row) * W + d] = s;
+    x[row * W + S + A + d] = mine + nz * sd;                                // fake next state (:353)
+    x[(b + row) * W + S + A + d] = s2;
+    a.fnz[ic] = nz;
+    if (d < A) { x[row * W + S + d] = aj0; x[(b + row) * W + S + d] = aj0; }
+    for (int j = d + S; j < A; j += S) { const float aj = a.act[((long long)e * b + row) * A + j]; x[row * W + S + j] = aj; x[(b + row) * W + S + j] = aj; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { tr += __shfl_xor(tr, o); kl += __shfl_xor(kl, o); }
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = tr; sm[4 + (threadIdx.x >> 6)] = kl; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* p = a.lossp + (long long)blockIdx.x * 2;
+    p[0] = (sm[0] + sm[1]) + (sm[2] + sm[3]); p[1] = (sm[4] + sm[5]) + (sm[6] + sm[7]);
+  }
+}
+
+// one thread per (row, state dim), all seven members: d mu_e = (1 + c_e) 2 (mu_e - s'_e) / (b_global S)   (T and the latent
+// consistency term, which is T again) + g_e + (sum_j g_j eps_j) (mu_e - avg) / (6 std),   g = d loss / d fake
+__global__ __launch_bounds__(256) void k_mopo_dmu(MopoRow a) {
+  const int S = a.S, Np3 = a.Np3;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.b * S) return;
+  const long long row = i / S, b = a.b;
+  const int d = (int)(i - row * S);
+  const float ct = (1.f + a.ce) * 2.f * a.inv_bg / (float)S;
+  float mu[NENS], g[NENS], avg = 0.f, G = 0.f;
+#pragma unroll
+  for (int e = 0; e < NENS; ++e) {
+    mu[e] = a.xenc[((long long)e * 2 * b + row) * S + d] + a.f[((long long)e * b + row) * S + d];
+    g[e] = a.dfake[((long long)e * 2 * b + row) * S + d];
+    avg += mu[e];
+    G += g[e] * a.fnz[((long long)e * b + row) * S + d];
+  }
+  avg *= (1.f / NENS);
+  float var = 0.f;
+#pragma unroll
+  for (int e = 0; e < NENS; ++e) { const float t = mu[e] - avg; var += t * t; }
+  const float k = G / ((NENS - 1) * sqrtf(var * (1.f / (NENS - 1))));
+#pragma unroll
+  for (int e = 0; e < NENS; ++e) {
+    const float s2 = a.xenc[((long long)e * 2 * b + b + row) * S + d];
+    float* o = a.dz3 + ((long long)e * b + row) * Np3;
+    o[d] = ct * (mu[e] - s2) + g[e] + k * (mu[e] - avg);
+    for (int c = S + d; c < Np3; c += S) o[c] = 0.f;
+  }
+}
+
+// out[5] = (loss, transition_loss, encoder_loss, recon_loss = 0, kl_loss); acc (nullable) += out
+__global__ __launch_bounds__(256) void k_mopo_loss_final(const float* lossp, PreLossOff lo, float inv_bg, int S, float ce,
+                                                         float cr, float* out, float* acc) {
+  __shared__ float sm[3][4];
+  float v[3] = {0.f, 0.f, 0.f};                          // trans, kl, reward
+  for (int k = threadIdx.x; k < lo.n_rt; k += 256) { v[0] += lossp[lo.rt + 2 * k]; v[1] += lossp[lo.rt + 2 * k + 1]; }
+  for (int k = threadIdx.x; k < lo.n_rw; k += 256) v[2] += lossp[lo.rw + k];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o);
+    if ((threadIdx.x & 63) == 0) sm[q][threadIdx.x >> 6] = v[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t[3];
+    for (int q = 0; q < 3; ++q) t[q] = (sm[q][0] + sm[q][1]) + (sm[q][2] + sm[q][3]);
+    const float trans = t[0] * inv_bg / S, kl = 0.05f * t[1] * inv_bg / S, rl = cr * t[2] * inv_bg;
+    const float enc = kl + trans;
+    out[0] = trans + ce * enc + rl; out[1] = trans; out[2] = enc; out[3] = 0.f; out[4] = kl;
+    if (acc != nullptr) { acc[0] += out[0]; acc[1] += trans; acc[2] += enc; acc[4] += kl; }
+  }
+}
+
+struct MopoWs {
+  float *sx_d, *h1d, *h2d, *d1d, *d2d, *f;
+  float *xrw, *sx_rw, *h1r, *h2r, *d1r, *d2r, *rw_out;
+  float *dz3rw, *dz3d, *dfake, *fnz, *lossp;
+  float *dz2[2], *dz1[2], *dbp[2], *slabs[2];   // 0 reward head (2b rows), 1 MLP (b rows)
+  int *eh1d, *eh1r, *edz2[2];
+  PreLossOff lo;
+  int nsplit1, nsplit2, ntiles1, ntiles2;
+  long long total;
+};
+
+static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* base, MopoWs& w) {
+  const long long E = NENS, R1 = b, R2 = 2 * b;
+  const long long R1p = (R1 + 31) & ~31LL, R2p = (R2 + 31) & ~31LL;
+  const int S = L.S, A = L.A;
+  long long off = 0;
+  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  w.sx_d = take(E * R1 * L.dyn.Kp1);
+  w.h1d = take(E * R1p * HID); w.h2d = take(E * R1 * HID); w.d1d = take(E * R1 * HID); w.d2d = take(E * R1 * HID);
+  w.f = take(E * R1 * S);
+  w.xrw = take(E * R2 * (2 * S + A)); w.sx_rw = take(E * R2 * L.rw.Kp1);
+  w.h1r = take(E * R2p * HID); w.h2r = take(E * R2 * HID); w.d1r = take(E * R2 * HID); w.d2r = take(E * R2 * HID);
+  w.rw_out = take(E * R2 * 2);
+  w.dz3rw = take(E * R2 * 16); w.dz3d = take(E * R1 * L.dyn.Np3); w.dfake = take(E * R2 * S); w.fnz = take(E * R1 * S);
+  w.dz2[0] = take(E * R2p * HID); w.dz1[0] = take(E * R2 * HID);
+  w.dz2[1] = take(E * R1p * HID); w.dz1[1] = take(E * R1 * HID);
+  w.ntiles1 = (int)cdiv(R1, 32); w.ntiles2 = (int)cdiv(R2, 32);
+  w.eh1d = reinterpret_cast<int*>(take(E * w.ntiles1)); w.eh1r = reinterpret_cast<int*>(take(E * w.ntiles2));
+  w.edz2[0] = reinterpret_cast<int*>(take(E * w.ntiles2)); w.edz2[1] = reinterpret_cast<int*>(take(E * w.ntiles1));
+  w.dbp[0] = take((long long)w.ntiles2 * E * (2 * HID + (L.rw.Np3 > 32 ? L.rw.Np3 : 32)));
+  w.dbp[1] = take((long long)w.ntiles1 * E * (2 * HID + (L.dyn.Np3 > 32 ? L.dyn.Np3 : 32)));
+  w.nsplit1 = wgrad_nsplit(R1, NENS); w.nsplit2 = wgrad_nsplit(R2, NENS);
+  w.slabs[0] = take(((L.rw.total_floats + 3) & ~3LL) * w.nsplit2);
+  w.slabs[1] = take(((L.dyn.total_floats + 3) & ~3LL) * w.nsplit1);
+  w.lo.n_lat = 0; w.lo.lat = 0;
+  w.lo.n_rt = (int)cdiv(E * R1 * S, 256); w.lo.n_rw = (int)cdiv(E * R2, 256);
+  w.lo.rt = 0; w.lo.rw = 2LL * w.lo.n_rt;
+  w.lossp = take(w.lo.rw + w.lo.n_rw);
+  w.total = off;
+  return 0;
+}
+}  // namespace mobody
+
+extern "C" int mobody_pretrain_mopo_layout(int S, int A, MobodyPretrainMopoLayout* out) {
+  MB_REQUIRE(out != nullptr, "mobody_pretrain_mopo_layout: out is null");
+  MB_REQUIRE(S >= 2 && S <= 128 && A >= 1 && A <= 64, "mobody_pretrain_mopo_layout: unsupported S=%d A=%d (S in [2,128], A in [1,64])", S, A);
+  memset(out, 0, sizeof(*out));
+  out->S = S; out->A = A;
+  int rc = mobody_mlp_layout(S + A, S, NENS, &out->dyn);                            // za_src1-3: S+A -> 256 -> 256 -> S
+  if (!rc) rc = mobody_mlp_layout(2 * S + A, 2, NENS, &out->rw);                    // reward_model1-3: 2S+A -> 256 -> 256 -> 2
+  if (rc) return rc;
+  int64_t p = 0;
+  out->off_dyn = p; p += (out->dyn.total_floats + 3) & ~(int64_t)3;
+  out->off_rw = p; p += (out->rw.total_floats + 3) & ~(int64_t)3;
+  out->total_floats = p;
+  int64_t t = 0;
+  out->t_off_dyn = t; t += (out->dyn.t_total_floats + 3) & ~(int64_t)3;
+  out->t_off_rw = t; t += (out->rw.t_total_floats + 3) & ~(int64_t)3;
+  out->t_total_floats = t;
+  return 0;
+}
+
+extern "C" int mobody_pretrain_mopo_transpose(int S, int A, const float* blob, float* blob_T, int precision, void* stream) {
+  MobodyPretrainMopoLayout L;
+  int rc = mobody_pretrain_mopo_layout(S, A, &L);
+  if (rc) return rc;
+  MB_REQUIRE(blob && blob_T, "mobody_pretrain_mopo_transpose: null pointer");
+  rc = pre_check_prec(precision, "mobody_pretrain_mopo_transpose");
+  if (rc) return rc;
+  rc = mobody_mlp_transpose(S + A, S, NENS, blob + L.off_dyn, blob_T + L.t_off_dyn, precision, stream);
+  if (!rc) rc = mobody_mlp_transpose(2 * S + A, 2, NENS, blob + L.off_rw, blob_T + L.t_off_rw, precision, stream);
+  return rc;
+}
+
+extern "C" int64_t mobody_pretrain_mopo_workspace(int S, int A, int64_t b) {
+  MobodyPretrainMopoLayout L;
+  if (mobody_pretrain_mopo_layout(S, A, &L) || b < 1) return -1;
+  MopoWs w;
+  mopo_carve(L, b, nullptr, w);
+  return w.total;
+}
+
+static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
+                              const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
+                              const float* noise, uint32_t seed, uint32_t call, const int64_t* call_dev, float* grad,
+                              const PreOpt& opt, float* loss_out, float* loss_acc, float* workspace, int precision, void* stream) {
+  MobodyPretrainMopoLayout L;
+  int rc = mobody_pretrain_mopo_layout(S, A, &L);
+  if (rc) return rc;
+  rc = pre_check_prec(precision, "mobody_pretrain_mopo");
+  if (rc) return rc;
+  const bool f16 = precision == 4;
+  MB_REQUIRE(b >= 1 && b_global >= b, "mobody_pretrain_mopo: need 1 <= b <= b_global");
+  MB_REQUIRE(blob && blob_T && xenc && act && rew && (grad || opt.on) && loss_out && workspace, "mobody_pretrain_mopo: null pointer");
+  auto region_adam = [&](int64_t off, int64_t toff) {
+    if (!opt.on) return AdamTarget{};
+    return pre_adam_target(opt.blob + off, opt.blob_T + toff, opt.m + off, opt.v + off, opt.t_main, opt.t_dev, opt.lr, 1.f, precision);
+  };
+  auto gptr = [&](int64_t off) { return grad ? grad + off : nullptr; };
+  MopoWs w;
+  mopo_carve(L, b, workspace, w);
+  hipStream_t st = as_stream(stream);
+  const long long R2 = 2 * b;
+  static bool once = false;
+  if (!once) {
+    rc = allow_big_lds(k_mlp3_fwd_train<0>, 160 * 1024);
+    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<1>, 160 * 1024);
+    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<2>, 160 * 1024);
+    if (rc) return rc;
+    once = true;
+  }
+  const float ce = (use_trg ? 5.f : 1.f) * encoder_loss_coef, cr = use_trg ? 1.f : 0.01f, inv_bg = 1.f / (float)b_global;
+  MopoRow r{};
+  r.S = S; r.A = A; r.Np3 = L.dyn.Np3; r.b = b; r.inv_bg = inv_bg; r.ce = ce;
+  r.xenc = xenc; r.act = act; r.noise = noise; r.seed = seed; r.call = call; r.call_dev = (const long long*)call_dev;
+  r.f = w.f; r.xrw = w.xrw; r.fnz = w.fnz; r.dfake = w.dfake; r.dz3 = w.dz3d; r.lossp = w.lossp + w.lo.rt;
+  PreRow pr{};                                         // what k_pre_reward_seed reads
+  pr.S = S; pr.A = A; pr.b = b; pr.inv_bg = inv_bg; pr.cr = cr; pr.rew = rew; pr.rw_out = w.rw_out; pr.dz3rw = w.dz3rw;
+  pr.lossp = w.lossp;
+  const float *Pd = blob + L.off_dyn, *Prw = blob + L.off_rw;
+  const float *Td = blob_T + L.t_off_dyn, *Trw = blob_T + L.t_off_rw;
+  auto forward = [&](const Mlp3FwdArgs& fa) {
+    return f16 ? launch_mlp3_fwd_bf(fa, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, 4, st) : launch_fwd_train(fa, NENS, st);
+  };
+  // ---- forward: the MLP on [s, a] (b rows per member), the row kernel, the reward head on 2b rows ----
+  {
+    Mlp3FwdArgs fa = pre_fwd_args(Pd, L.dyn, xenc, S, b, w.f, w.sx_d, w.h1d, w.h2d, w.d1d, w.d2d, Td, f16 ? w.eh1d : nullptr);
+    fa.src_ms[0] = 2 * b * S;                          // the s rows of xenc (its s' rows follow in each member's block)
+    fa.src[1] = act; fa.ld[1] = A; fa.n[1] = A; fa.src_ms[1] = b * A;
+    rc = forward(fa);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_mopo_rows, dim3((unsigned)w.lo.n_rt), dim3(256), 0, st, r);
+  MB_LAUNCH_OK("k_mopo_rows");
+  rc = forward(pre_fwd_args(Prw, L.rw, w.xrw, 2 * S + A, R2, w.rw_out, w.sx_rw, w.h1r, w.h2r, w.d1r, w.d2r, Trw, f16 ? w.eh1r : nullptr));
+  if (rc) return rc;
+  // ---- backward: reward head (input gradient = d loss / d fake) ----
+  hipLaunchKernelGGL(k_pre_reward_seed, dim3((unsigned)w.lo.n_rw), dim3(256), 0, st, pr, w.lo);
+  MB_LAUNCH_OK("k_pre_reward_seed");
+  {
+    Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.d1r, w.d2r, R2, w.dz2[0], w.dz1[0], w.dbp[0], f16 ? w.edz2[0] : nullptr);
+    bw.dx = w.dfake; bw.dx_c0 = S + A; bw.dx_n = S;
+    rc = launch_mlp3_bwd(bw, NENS, true, 32, st);
+    if (rc) return rc;
+  }
+  PreSide* side = nullptr;
+  hipStream_t st2 = st;
+  if (PRE_SIDE_STREAM) {
+    rc = pre_side(&side);
+    if (rc) return rc;
+    st2 = side->s;
+    if (hipEventRecord(side->fork[0], st) != hipSuccess || hipStreamWaitEvent(st2, side->fork[0], 0) != hipSuccess)
+      return fail(MOBODY_E_LAUNCH, "mopo pre-training: fork onto the side stream failed");
+  }
+  // from here on every exit goes through the join below, error or not
+  auto after_fork = [&]() -> int {
+    int rc2 = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0],
+                                w.dbp[0], w.ntiles2, gptr(L.off_rw), LossFinal{}, region_adam(L.off_rw, L.t_off_rw), st2, precision,
+                                f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr);
+    if (rc2) return rc2;
+    hipLaunchKernelGGL(k_mopo_dmu, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
+    MB_LAUNCH_OK("k_mopo_dmu");
+    Mlp3BwdArgs bw = pre_bwd_args(L.dyn, Td, w.dz3d, w.d1d, w.d2d, b, w.dz2[1], w.dz1[1], w.dbp[1], f16 ? w.edz2[1] : nullptr);
+    rc2 = launch_mlp3_bwd(bw, NENS, false, 32, st);
+    if (rc2) return rc2;
+    return mlp3_weight_grads(L.dyn, w.sx_d, b * L.dyn.Kp1, w.h1d, w.h2d, w.dz3d, w.dz2[1], w.dz1[1], b, w.nsplit1, w.slabs[1],
+                             w.dbp[1], w.ntiles1, gptr(L.off_dyn), LossFinal{}, region_adam(L.off_dyn, L.t_off_dyn), st, precision,
+                             f16 ? w.eh1d : nullptr, f16 ? w.edz2[1] : nullptr);
+  };
+  rc = after_fork();
+  if (PRE_SIDE_STREAM) {
+    if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
+      return rc ? rc : fail(MOBODY_E_LAUNCH, "mopo pre-training: join of the side stream failed");
+  }
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_mopo_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, inv_bg, S, ce, cr, loss_out, loss_acc);
+  MB_LAUNCH_OK("k_mopo_loss_final");
+  return 0;
+}
+
+extern "C" int mobody_pretrain_mopo_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
+                                          const float* blob, const float* blob_T, const float* xenc, const float* act,
+                                          const float* rew, const float* noise, uint32_t seed, uint32_t call, float* grad,
+                                          float* loss_out, float* workspace, int precision, void* stream) {
+  MB_REQUIRE(grad, "mobody_pretrain_mopo_grads: grad is null");
+  return pretrain_mopo_impl(S, A, b, b_global, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise, seed, call, nullptr,
+                            grad, PreOpt{}, loss_out, nullptr, workspace, precision, stream);
+}
+
+extern "C" int mobody_pretrain_mopo_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
+                                           const float* xenc, const float* act, const float* rew, const float* noise, uint32_t seed,
+                                           uint32_t call, const int64_t* call_dev, float* m, float* v, int64_t t,
+                                           const int64_t* t_dev, float lr, float* loss_out, float* loss_acc, float* workspace,
+                                           int precision, void* stream) {
+  MB_REQUIRE(m && v, "mobody_pretrain_mopo_update: null pointer");
+  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_pretrain_mopo_update: the step count is 1-based");
+  PreOpt o{1, blob, blob_T, m, v, t, 0, t_dev, lr};
+  return pretrain_mopo_impl(S, A, b, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise, seed, call, call_dev,
+                            nullptr, o, loss_out, loss_acc, workspace, precision, stream);
+}
+
+extern "C" int mobody_pretrain_mopo_adam(int S, int A, float* blob, float* blob_T, const float* grad, float* m, float* v,
+                                         int64_t t, float lr, float grad_scale, int precision, void* stream) {
+  MobodyPretrainMopoLayout L;
+  int rc = mobody_pretrain_mopo_layout(S, A, &L);
+  if (rc) return rc;
+  rc = pre_check_prec(precision, "mobody_pretrain_mopo_adam");
+  if (rc) return rc;
+  MB_REQUIRE(blob && blob_T && grad && m && v, "mobody_pretrain_mopo_adam: null pointer");
+  MB_REQUIRE(t >= 1, "mobody_pretrain_mopo_adam: the step count is 1-based");
+  hipStream_t st = as_stream(stream);
+  const MobodyMlpLayout* nets[2] = {&L.dyn, &L.rw};
+  const int64_t offs[2] = {L.off_dyn, L.off_rw}, toffs[2] = {L.t_off_dyn, L.t_off_rw};
+  for (int k = 0; k < 2; ++k) {                        // both regions get a gradient every step: one step count
+    const AdamTarget a = pre_adam_target(blob + offs[k], blob_T + toffs[k], m + offs[k], v + offs[k], t, nullptr, lr, grad_scale,
+                                         precision);
+    rc = launch_adam(a, grad + offs[k], *nets[k], st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mobody_dyn_validate_mopo(const float* dyn_blob, const float* mopo_blob, int S, int A, const float* obs,
+                                        const float* act, const float* next_obs, const float* rew, int64_t B, float* out,
+                                        float* workspace, void* stream) {
+  MobodyDynLayout L;
+  int rc = mobody_dyn_layout(S, A, &L);
+  if (rc) return rc;
+  MobodyMlpLayout ML;
+  rc = mobody_mlp_layout(S + A, S, NENS, &ML);
+  if (rc) return rc;
+  MB_REQUIRE(B >= 1, "mobody_dyn_validate_mopo: B < 1");
+  MB_REQUIRE(dyn_blob && mopo_blob && obs && act && next_obs && rew && out && workspace, "mobody_dyn_validate_mopo: null pointer");
+  Mlp3FwdArgs f{};                                     // mean_e = s + f_e(s, a), exact fp32 (forward_trg == forward_src, :264-266)
+  f.src[0] = obs; f.ld[0] = S; f.n[0] = S;
+  f.src[1] = act; f.ld[1] = A; f.n[1] = A;
+  f.w1 = mopo_blob + ML.w1; f.b1 = mopo_blob + ML.b1; f.w2 = mopo_blob + ML.w2; f.b2 = mopo_blob + ML.b2;
+  f.w3 = mopo_blob + ML.w3; f.b3 = mopo_blob + ML.b3;
+  f.sw1 = f.sb1 = f.sw2 = f.sb2 = f.sw3 = f.sb3 = ML.member_floats;
+  f.Kp1 = ML.Kp1; f.Np3 = ML.Np3; f.nout = S; f.rows = B;
+  f.out = workspace; f.out_mstride = B * S; f.out_ld = S;
+  f.out_mode = 0; f.max_action = 1.f;
+  f.resid = obs; f.resid_ld = S;
+  rc = launch_mlp3_fwd(f, NENS, ACT_SWISH, as_stream(stream));
+  if (rc) return rc;
+  return dyn_validate_tail(dyn_blob, L, S, A, obs, act, next_obs, rew, B, out, workspace, stream);
 }

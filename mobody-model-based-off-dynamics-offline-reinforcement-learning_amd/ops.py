@@ -460,6 +460,58 @@ def pretrain_za_adam(S, A, use_trg, blob, grad, m, v, t_za, lr, grad_scale=1.0):
                                          float(grad_scale), cur_stream()), "mobody_pretrain_za_adam")
 
 
+# ---- MOPO ablation pre-training (MobodyPretrainMopoLayout) ----
+def pretrain_mopo_transpose(blob, S, A, out=None, precision=0):
+    L = _lib.pretrain_mopo_layout(S, A)
+    bt = out if out is not None else torch.zeros(L.t_total_floats, dtype=torch.float32, device=blob.device)
+    check(load().mobody_pretrain_mopo_transpose(S, A, ptr(blob), ptr(bt), prec_id(precision), cur_stream()),
+          "mobody_pretrain_mopo_transpose")
+    return bt
+
+
+def pretrain_mopo_workspace(S, A, b, device):
+    n = load().mobody_pretrain_mopo_workspace(S, A, b)
+    if n < 0:
+        raise _lib.MobodyError("mobody_pretrain_mopo_workspace: " + load().mobody_last_error().decode())
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def pretrain_mopo_grads(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, grad, loss_out, ws, noise=None,
+                        seed=0, call=0, b_global=None, precision=0):
+    """noise: [7, b, S] fake-next-state draw (None: device Philox at (seed, call))."""
+    check(load().mobody_pretrain_mopo_grads(S, A, b, b if b_global is None else b_global, int(bool(use_trg)),
+                                            float(encoder_loss_coef), ptr(blob), ptr(blob_T), ptr(xenc), ptr(act), ptr(rew),
+                                            ptr(noise), seed, call, ptr(grad), ptr(loss_out), ptr(ws), prec_id(precision),
+                                            cur_stream()), "mobody_pretrain_mopo_grads")
+
+
+def pretrain_mopo_update(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, m, v, t, lr, loss_out, ws,
+                         noise=None, seed=0, call=0, call_dev=None, t_dev=None, precision=0, loss_acc=None):
+    check(load().mobody_pretrain_mopo_update(S, A, b, int(bool(use_trg)), float(encoder_loss_coef), ptr(blob), ptr(blob_T),
+                                             ptr(xenc), ptr(act), ptr(rew), ptr(noise), seed, call, ptr(call_dev), ptr(m),
+                                             ptr(v), t, ptr(t_dev), float(lr), ptr(loss_out), ptr(loss_acc), ptr(ws),
+                                             prec_id(precision), cur_stream()), "mobody_pretrain_mopo_update")
+
+
+def pretrain_mopo_adam(S, A, blob, blob_T, grad, m, v, t, lr, grad_scale=1.0, precision=0):
+    check(load().mobody_pretrain_mopo_adam(S, A, ptr(blob), ptr(blob_T), ptr(grad), ptr(m), ptr(v), t, float(lr),
+                                           float(grad_scale), prec_id(precision), cur_stream()), "mobody_pretrain_mopo_adam")
+
+
+def dyn_validate_mopo(blob, mopo_blob, S, A, obs, act, next_obs, rew, ws=None):
+    """validate() of a mopo model: mean_e = s + MLP_e([s, a]) from `mopo_blob` (mobody_mlp_layout(S + A, S, 7)), the reward
+    head from the inference blob.  out[0:7] transition MSE, out[7:14] reward MSE (device tensor)."""
+    B = obs.shape[0]
+    need = load().mobody_dyn_validate_workspace(S, A, B)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.float32, device=obs.device)
+    out = torch.empty(14, dtype=torch.float32, device=obs.device)
+    check(load().mobody_dyn_validate_mopo(ptr(blob), ptr(mopo_blob), S, A, ptr(_f32(obs)), ptr(_f32(act)), ptr(_f32(next_obs)),
+                                          ptr(_f32(rew).reshape(-1).contiguous()), B, ptr(out), ptr(ws), cur_stream()),
+          "mobody_dyn_validate_mopo")
+    return out
+
+
 def dyn_validate(blob, S, A, obs, act, next_obs, rew, use_trg, ws=None):
     """validate(): out[0:7] per-member transition MSE, out[7:14] per-member reward MSE (device tensor)."""
     B = obs.shape[0]

@@ -152,3 +152,43 @@ def unpack_pretrain(blob, S, A, into=None):
         for k, v in out.items():
             into[k] = v
     return out
+
+
+# ---- MOPO ablation pre-training blob (MobodyPretrainMopoLayout) ----------------------------------------------------
+PRETRAIN_MOPO_NETS = (("dyn", ("za_src1", "za_src2", "za_src3")), ("rw", ("reward_model1", "reward_model2", "reward_model3")))
+
+
+def _ens_members(g, names):
+    """EnsembleLinear `[7, in, out]` / `[7, 1, out]` tensors of a 3-layer net -> pack_mlp's per-member nn.Linear dicts."""
+    l1, l2, l3 = names
+    return [{"network.0.weight": g(l1 + ".weight")[e].t(), "network.0.bias": g(l1 + ".bias")[e, 0],
+             "network.2.weight": g(l2 + ".weight")[e].t(), "network.2.bias": g(l2 + ".bias")[e, 0],
+             "network.4.weight": g(l3 + ".weight")[e].t(), "network.4.bias": g(l3 + ".bias")[e, 0]} for e in range(7)]
+
+
+def pack_pretrain_mopo(params, S, A, device):
+    """Reference state_dict tensors of a mopo model (za_src1-3, reward_model1-3) -> the mopo training blob."""
+    L = _lib.pretrain_mopo_layout(S, A)
+    g = lambda k: torch.as_tensor(params[k], dtype=torch.float32).to(device)
+    blob = torch.zeros(L.total_floats, dtype=torch.float32, device=device)
+    for nm, names in PRETRAIN_MOPO_NETS:
+        ml, off = getattr(L, nm), getattr(L, "off_" + nm)
+        blob[off:off + ml.total_floats] = pack_mlp(_ens_members(g, names), ml.in_dim, ml.out_dim, device)
+    return blob
+
+
+def unpack_pretrain_mopo(blob, S, A, into=None):
+    """Inverse of pack_pretrain_mopo: {name: tensor} in the reference layout; `into` (a state-dict-like mapping) is updated
+    in place when given."""
+    L = _lib.pretrain_mopo_layout(S, A)
+    out = {}
+    for nm, names in PRETRAIN_MOPO_NETS:
+        ml, off = getattr(L, nm), getattr(L, "off_" + nm)
+        ms = unpack_mlp(blob[off:off + ml.total_floats], ml.in_dim, ml.out_dim, 7)
+        for li, lname in zip((0, 2, 4), names):
+            out[lname + ".weight"] = torch.stack([m[f"network.{li}.weight"].t() for m in ms]).contiguous()
+            out[lname + ".bias"] = torch.stack([m[f"network.{li}.bias"] for m in ms]).unsqueeze(1).contiguous()
+    if into is not None:
+        for k, v in out.items():
+            into[k] = v
+    return out
