@@ -158,7 +158,7 @@ __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* 
         for (int r = 0; r < 16; ++r)
           if (32 * (MT * wave_rg() + mt) + (r & 3) + 8 * (r >> 2) + 4 * (lane_id() >> 5) >= rows_here) acc[mt][nt][r] = 0.f;
   }
-  if constexpr (Split<PM>::F16) f16_tile_max_put(mx, scr);
+  if constexpr (Split<PM>::F16) f16_tile_max_put(finite_tile_max<MT>(acc, mx), scr);
   lds_barrier();                                   // every wave has read the old image (and posted its maximum)
   int e = 0;
   if constexpr (Split<PM>::F16) e = f16_scale_exp(f16_tile_max_get(scr));

@@ -105,7 +105,7 @@ __device__ __forceinline__ float wide_mask_apply(f32x16 (&acc)[MT][2], const Mas
   };
   if (rows_here == 32 * MT) sweep(std::false_type{});
   else sweep(std::true_type{});
-  return mx;
+  return finite_tile_max<MT>(acc, mx);
 }
 
 // wide_store_colsum (after the barrier): dz -> LDS (the fp32 image, or -- PM > 0 -- the 16-bit planes the next GEMM
@@ -643,8 +643,10 @@ __device__ __forceinline__ void wgrad_tile_bf(const WgradJob& jb, const WgradArg
 // the row loop has no conversion work at all: per 16-row block 8 loads and 12 MFMAs (three products on four 32 x 32 tiles).
 // Every 32-row tile carries its own power-of-two scales (planes hold h1 * 2^eA[t], dz2 * 2^eB[t]); a wave brings its
 // blocks to one common scale U = min_t (eA[t] + eB[t]) over its rows by multiplying the B fragments with the exact factor
-// 2^(U - eA[t] - eB[t]) <= 1 (v_pk_mul_f16; a tile far below the wave's largest one underflows gracefully, its contribution
-// to the sum is below fp32 resolution anyway) and un-scales its accumulators once at the end.
+// 2^(U - eA[t] - eB[t]) <= 1 (v_pk_mul_f16, exact down to 2^-24, the smallest fp16 subnormal) and un-scales its accumulators
+// once at the end.  A tile more than 2^24 below the slice's dominant one (U - eA - eB < -24) is dropped -- its factor is
+// 0: its terms are below 2^-24 of the dominant tile's and so below fp32 resolution of the sum (a factor clamped to
+// 2^-24 instead would overweight it by 2^(-24 - sh), which is all there is of an element the dominant tiles do not reach).
 __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradArgs& a, int tile, int slice, int m, float* red) {
   constexpr int MT = 2, NT = 2, TK = 64, TN = 64, RB = 16;
   const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
@@ -691,9 +693,9 @@ __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradAr
       k.sh = U - __builtin_amdgcn_readlane(Ev, t - t0);                         // <= 0
     };
     auto mma = [&](Blk& k) {
-      // 2^sh as a packed fp16 pair (sh >= -24 stays exact down to the smallest subnormal; below that the tile is noise)
-      const int shc = max(k.sh, -24);
-      const _Float16 f = (_Float16)__int_as_float((shc + 127) << 23);
+      // 2^sh as a packed fp16 pair, exact for -24 <= sh <= 0; 0 below (the tile is dropped, see above: a select rather than a
+      // branch around the MFMAs, which would break the straight-line body the loop relies on)
+      const _Float16 f = k.sh < -24 ? (_Float16)0.f : (_Float16)__int_as_float((max(k.sh, -24) + 127) << 23);
       s16x8 bs[2][NT];
 #pragma unroll
       for (int p = 0; p < 2; ++p)

@@ -37,7 +37,10 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(8))) short s16x8;       // one MFMA A/B fragment as raw 16-bit lanes (either format)
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 constexpr long long BF_PLANE = 32LL * HID;     // s16x8 units per weight plane ([K/8 = 32][256])
-constexpr int F16_WSHIFT = 8;                  // "f16x2" weight planes hold w * 2^8 (|w| < 255; residual terms stay normal down to |w| ~ 5e-4)
+// "f16x2" weight planes hold w * 2^8: |w| must stay below 65504 / 2^8 ~ 255.9 (residual terms stay normal down to |w| ~ 5e-4).
+// The host-side plane builders (ops.mlp_transpose / dyn_planes / pretrain_transpose / pretrain_mopo_transpose) refuse a W2
+// block at or above that bound; the fused Adam plane writers do not check, so a weight trained past it becomes Inf in its plane.
+constexpr int F16_WSHIFT = 8;
 
 #ifndef SPLIT_RING
 #define SPLIT_RING 3
@@ -102,13 +105,32 @@ __device__ __forceinline__ f32x16 split_mfma(s16x8 a, s16x8 b, f32x16 c) {
 // 2^-3 of the tile maximum stays a normal fp16 number, smaller values degrade gracefully to an absolute error of 2^-39 of
 // the maximum).  An all-zero (or denormal) tile gets the LARGEST exponent, 100: its planes are zero whatever the scale, and
 // the weight-gradient GEMM, which brings the tiles of a row slice to their smallest exponent, must not let an empty tile
-// set that common scale.  Inf / NaN: 0 (a non-finite tile is garbage either way and NaNs propagate through the MFMA).
+// set that common scale.  Inf / NaN: 0 (unreachable from the epilogues, whose maxima run over finite values: finite_tile_max).
 __device__ __forceinline__ int f16_scale_exp(float m) {
   const int eb = (__float_as_int(m) >> 23) & 0xff;
   if (eb == 0) return 100;
   if (eb == 255) return 0;
   const int e = 13 - (eb - 127);
   return e > 100 ? 100 : e;
+}
+// |v|, or NaN for Inf / NaN (v * 0 + |v|: one v_fma), which fmaxf drops
+__device__ __forceinline__ float finite_abs(float v) { return __builtin_fmaf(v, 0.f, fabsf(v)); }
+// A lane's largest |v| over the values it holds, `mx` = fmaxf over |v| (NaN is dropped already, Inf is not): where that is
+// Inf, the maximum over the finite values only.  A non-finite value so stays confined to its own row instead of setting the
+// whole tile's scale to 2^0, which would push the other rows' residual terms into fp16 subnormals and make anything above
+// 65504 Inf.  The common case costs one compare per epilogue instead of a filter per element.
+template <int MT>
+__device__ __forceinline__ float finite_tile_max(const f32x16 (&v)[MT][2], float mx) {
+  if (__builtin_expect(mx == __builtin_inff(), 0)) {
+    mx = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, finite_abs(v[mt][nt][r]));
+  }
+  return mx;
 }
 __device__ __forceinline__ float exp2i(int e) { return __int_as_float((e + 127) << 23); }      // 2^e, -126 <= e <= 127
 __device__ __forceinline__ float wave_max(float v) {

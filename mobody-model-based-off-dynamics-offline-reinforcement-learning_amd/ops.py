@@ -42,9 +42,32 @@ def default_mfma():
     return os.environ.get("MOBODY_MFMA", "f32")
 
 
+F16_W_LIMIT = 65504.0 / 2 ** 8      # 'f16x2' weight planes hold w * 2^8 (csrc/tile_bf.h F16_WSHIFT): |w| at or above this is Inf
+
+
+def _check_f16_weights(blocks, what):
+    """Refuse to build 'f16x2' planes of 256 x 256 weights that fp16 cannot hold after the 2^8 pre-scale (they would silently
+    poison every output of the layer).  Runs where planes are (re)built -- set-up, checkpoint load, change of mode -- not per
+    step; skipped inside a stream capture, where the host cannot read the device (the capture's builder was checked eagerly)."""
+    if torch.cuda.is_current_stream_capturing():
+        return
+    m = max(float(b.abs().max()) for b in blocks)
+    if m >= F16_W_LIMIT:
+        raise ValueError(f"{what}: a 256 x 256 weight of magnitude {m:g} does not fit the f16x2 planes "
+                         f"(|w| < 65504 / 2^8 = {F16_W_LIMIT}); use precision 'f32' or 'bf16x3'")
+
+
+def _mlp_w2(blob, L, members):
+    return blob[:members * L.member_floats].view(members, L.member_floats)[:, L.w2:L.w2 + 65536]
+
+
 def dyn_planes(blob, S, A, out=None, precision=3):
     """16-bit planes of zs2 / transition2 / reward_model2 in the format of the split-precision mode `precision`
     (modes 1-3 share the three bf16 planes; 'f16x2' has its own two fp16 planes)."""
+    if prec_id(precision) == 4:
+        L = _lib.dyn_layout(S, A)
+        lays = [L.layer[_lib.DL_NAMES.index(n)] for n in ("zs2", "transition2", "reward_model2")]
+        _check_f16_weights([blob[y.w_off:y.w_off + L.E * y.Kp * y.Np] for y in lays], "dyn_planes")
     pl = out if out is not None else torch.empty(load().mobody_dyn_planes_floats(), dtype=torch.float32, device=blob.device)
     check(load().mobody_dyn_planes(ptr(blob), S, A, ptr(pl), prec_id(precision), cur_stream()), "mobody_dyn_planes")
     return pl
@@ -150,6 +173,8 @@ def train_workspace(dims, device):
 def mlp_transpose(blob, in_dim, out_dim, members, out=None, precision=0):
     """T blob of a packed MLP; `precision` = the MFMA mode whose W2 plane format it carries."""
     L = _lib.mlp_layout(in_dim, out_dim, members)
+    if prec_id(precision) == 4:
+        _check_f16_weights([_mlp_w2(blob, L, members)], "mlp_transpose")
     bt = out if out is not None else torch.empty(L.t_total_floats, dtype=torch.float32, device=blob.device)
     assert bt.numel() == L.t_total_floats
     check(load().mobody_mlp_transpose(in_dim, out_dim, members, ptr(blob), ptr(bt), prec_id(precision), cur_stream()),
@@ -404,6 +429,9 @@ def dara_penalty(z_sas, z_sa, coef, reward=None, want_delta=False):
 def pretrain_transpose(blob, S, A, out=None, precision=0):
     """T blob of the pre-training parameter blob; `precision` (0 / "f32" or 4 / "f16x2") = the mode it will be trained in."""
     L = _lib.pretrain_layout(S, A)
+    if prec_id(precision) == 4:
+        _check_f16_weights([_mlp_w2(blob[L.off_enc:], L.enc, 7), _mlp_w2(blob[L.off_tr:], L.tr, 7),
+                            _mlp_w2(blob[L.off_rw:], L.rw, 7)], "pretrain_transpose")
     bt = out if out is not None else torch.zeros(L.t_total_floats, dtype=torch.float32, device=blob.device)
     check(load().mobody_pretrain_transpose(S, A, ptr(blob), ptr(bt), prec_id(precision), cur_stream()), "mobody_pretrain_transpose")
     return bt
@@ -463,6 +491,8 @@ def pretrain_za_adam(S, A, use_trg, blob, grad, m, v, t_za, lr, grad_scale=1.0):
 # ---- MOPO ablation pre-training (MobodyPretrainMopoLayout) ----
 def pretrain_mopo_transpose(blob, S, A, out=None, precision=0):
     L = _lib.pretrain_mopo_layout(S, A)
+    if prec_id(precision) == 4:
+        _check_f16_weights([_mlp_w2(blob[L.off_dyn:], L.dyn, 7), _mlp_w2(blob[L.off_rw:], L.rw, 7)], "pretrain_mopo_transpose")
     bt = out if out is not None else torch.zeros(L.t_total_floats, dtype=torch.float32, device=blob.device)
     check(load().mobody_pretrain_mopo_transpose(S, A, ptr(blob), ptr(bt), prec_id(precision), cur_stream()),
           "mobody_pretrain_mopo_transpose")

@@ -18,6 +18,7 @@ Dynamics parameters are a dict with the reference's state_dict key names
 `network.{0,2,4}.{weight,bias}` (nn.Linear layout [out,in]).
 """
 import math
+import types
 
 import numpy as np
 import torch
@@ -35,8 +36,33 @@ def T(x, dtype=torch.float32):
     return torch.as_tensor(np.asarray(x), dtype=dtype)
 
 
-def to_torch(params):
-    return {k: T(v) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(np.asarray(v)) for k, v in params.items()}
+def to_torch(params, dtype=torch.float32):
+    return {k: T(v, dtype) if np.asarray(v).dtype.kind == "f" else torch.as_tensor(np.asarray(v)) for k, v in params.items()}
+
+
+# Optional record of every linear layer a differentiated loss passes through (the fp64 error bounds of tests/f64_bounds.py):
+# inside `with linear_tape() as tape:`, each call of a layer whose weight requires grad appends {"x": input, "z": output,
+# "dz": d loss / d output} to tape[layer name] (dz through an autograd hook, so torch.autograd.grad fills it too).
+_TAPE = None
+
+
+class linear_tape:
+    def __enter__(self):
+        global _TAPE
+        _TAPE = {}
+        return _TAPE
+
+    def __exit__(self, *exc):
+        global _TAPE
+        _TAPE = None
+
+
+def _rec(name, W, x, z):
+    if _TAPE is None or not W.requires_grad or not z.requires_grad:
+        return
+    rec = {"x": x.detach(), "z": z.detach()}
+    _TAPE.setdefault(name, []).append(rec)
+    z.register_hook(lambda g: rec.__setitem__("dz", g.detach()))
 
 
 def swish(x):
@@ -54,7 +80,9 @@ def ensemble_linear(x, W, b):
 
 
 def _el(p, name, x):
-    return ensemble_linear(x, p[name + ".weight"], p[name + ".bias"])
+    z = ensemble_linear(x, p[name + ".weight"], p[name + ".bias"])
+    _rec(name, p[name + ".weight"], x, z)
+    return z
 
 
 def soft_clamp(x, lo, hi):
@@ -107,8 +135,12 @@ def is_mopo(p):
     return "za_src3.weight" in p
 
 
-def dyn_forward(p, obs, act, use_trg=True):
-    """forward_trg / forward_src, mobody_module.py:315-330 -> (mean[E,B,S], zs_mu, zs_logvar)."""
+def dyn_forward(p, obs, act, use_trg=True, dtype=torch.float32):
+    """forward_trg / forward_src, mobody_module.py:315-330 -> (mean[E,B,S], zs_mu, zs_logvar).
+    dtype: the precision of the restatement (float64: reference for the error bounds of the split-precision kernels)."""
+    if dtype != torch.float32:
+        p = {k: T(v, dtype) if k.split(".")[-1] in ("weight", "bias") else v for k, v in p.items()}
+        obs, act = T(obs, dtype), T(act, dtype)
     if is_mopo(p):
         return dyn_forward_mopo(p, obs, act)
     zs, zs_logvar = dyn_encode_state(p, obs)
@@ -211,18 +243,29 @@ def dyn_step(p, obs, act, eps, elite_idx, task, penalty_coef=0.0, use_penalty=Tr
 
 def mlp3(p, x, prefix=""):
     """MLPNetwork, mobody.py:35-48: Linear-ReLU-Linear-ReLU-Linear."""
-    h = torch.relu(torch.nn.functional.linear(x, p[prefix + "network.0.weight"], p[prefix + "network.0.bias"]))
-    h = torch.relu(torch.nn.functional.linear(h, p[prefix + "network.2.weight"], p[prefix + "network.2.bias"]))
-    return torch.nn.functional.linear(h, p[prefix + "network.4.weight"], p[prefix + "network.4.bias"])
+    def lin(i, h):
+        W = p[prefix + f"network.{i}.weight"]
+        z = torch.nn.functional.linear(h, W, p[prefix + f"network.{i}.bias"])
+        _rec(prefix + f"network.{i}", W, h, z)
+        return z
+    h = torch.relu(lin(0, x))
+    h = torch.relu(lin(2, h))
+    return lin(4, h)
 
 
-def actor(p, s, max_action=1.0):
+def _cast(p, dtype):
+    return p if dtype == torch.float32 else {k: T(v, dtype) for k, v in p.items()}
+
+
+def actor(p, s, max_action=1.0, dtype=torch.float32):
     """Policy.forward, mobody.py:60-72; keys `network.network.{0,2,4}.*`."""
-    return torch.tanh(mlp3(p, s, "network.")) * max_action
+    return torch.tanh(mlp3(_cast(p, dtype), T(s, dtype) if dtype != torch.float32 else s, "network.")) * max_action
 
 
-def twin_q(p, s, a):
+def twin_q(p, s, a, dtype=torch.float32):
     """DoubleQFunc.forward, mobody.py:74-83; keys `network{1,2}.network.{0,2,4}.*`."""
+    if dtype != torch.float32:
+        p, s, a = _cast(p, dtype), T(s, dtype), T(a, dtype)
     x = torch.cat([s, a], 1)
     return mlp3(p, x, "network1."), mlp3(p, x, "network2.")
 
@@ -406,17 +449,21 @@ def _grads(loss, params):
     return {k: (g if g is not None else torch.zeros_like(params[k])) for k, g in zip(names, gs)}
 
 
-def train_step(st, batch, n_true, cfg, apply=True):
+def train_step(st, batch, n_true, cfg, apply=True, dtype=torch.float32):
     """MOBODY.train body after the minibatch is assembled, mobody.py:516-578.
+    dtype: precision of the restatement; float64 (only with apply=False) is the reference of the fp64 error bounds.
 
     batch = (state[N,S], action[N,A], next_state[N,S], reward[N,1], not_done[N,1]) in the
     reference's concat order src|tar|fake (:525-529); the "true" BC batch is the first
     n_true rows (src|tar, :561-563).  Returns a dict of losses / grads / BC weights.
     cfg keys: gamma tau max_action critic_lr actor_lr weight bc_coef q_weighted advantage scale_Q.
     """
-    s, a, s2, r, nd = [T(x) for x in batch]
+    assert dtype == torch.float32 or not apply, "the fp64 restatement computes gradients only (apply=False)"
+    s, a, s2, r, nd = [T(x, dtype) for x in batch]
     out = {}
-    req = lambda d: {k: v.detach().clone().requires_grad_(True) for k, v in d.items()}
+    req = lambda d: {k: T(v, dtype).detach().clone().requires_grad_(True) for k, v in d.items()}
+    if dtype != torch.float32:
+        st = types.SimpleNamespace(**{k: _cast(getattr(st, k), dtype) for k in ("actor", "q", "q_targ", "v")})
 
     if cfg.get("advantage", 0):                                   # :533-537, update_v_function :231-242
         vp = req(st.v)
@@ -491,7 +538,8 @@ TRAINED_LAYERS = ("zs1", "zs2", "zs3", "za_src1", "za_src2", "za_trg1", "za_trg2
                   "transition3", "reward_model1", "reward_model2", "reward_model3")
 
 
-def dyn_learn_losses(p, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef=1.0, transition_coef=1.0, reward_coef=1.0):
+def dyn_learn_losses(p, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef=1.0, transition_coef=1.0, reward_coef=1.0,
+                     dtype=torch.float32):
     """The loss of one `learn()` batch, mobody_dynamics.py:594-653 (no_vae=0, latent_reward=0, inverse_sep_reward_loss=0):
 
       encoder_loss (:300-330)   100 * [sum_e mean_{b,d}(dec(z1) - s)^2 + ... (dec(z2) - s')^2]
@@ -506,8 +554,8 @@ def dyn_learn_losses(p, obs, act, next_obs, rew, noise, use_trg, encoder_loss_co
     in the reference's order: z1(s), z2(s'), z3(s), z4(s'), z5(s), z6(s) as [E,b,16] and eps7 [E,b,S]
     (reparameterize, mobody_module.py:237-243: z = mu + eps * exp(0.5 * logvar) in training mode).
     Returns (loss, transition_loss, encoder_loss, recon_loss, kl_loss)."""
-    s, a, s2, r = T(obs), T(act), T(next_obs), T(rew)
-    n = [T(x) for x in noise]
+    s, a, s2, r = T(obs, dtype), T(act, dtype), T(next_obs, dtype), T(rew, dtype)
+    n = [T(x, dtype) for x in noise]
     pre = "za_trg" if use_trg else "za_src"
 
     def enc(x, eps):                                                  # encode_state :217-225
@@ -554,13 +602,17 @@ class DynTrainState:
         self.lr = lr
 
 
-def dyn_learn_step(st, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef=1.0, apply=True, with_reward=True):
+def dyn_learn_step(st, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef=1.0, apply=True, with_reward=True,
+                   dtype=torch.float32):
     """zero_grad -> loss.backward -> Adam.step of one learn() batch (mobody_dynamics.py:641-643).
+    dtype: precision of the restatement; float64 (only with apply=False) is the reference of the fp64 error bounds.
     with_reward=False: config inverse_sep_reward_loss = 1 (:637-641) -- reward_loss is neither evaluated nor added, so the reward
     head's parameters have no gradient (Adam skips them, their step counts stay).
     Returns dict(losses=(5 floats), grads={name: tensor or None})."""
-    pr = {k: v.detach().clone().requires_grad_(True) for k, v in st.p.items()}
-    losses = dyn_learn_losses(pr, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef, 1.0, 1.0 if with_reward else 0.0)
+    assert dtype == torch.float32 or not apply, "the fp64 restatement computes gradients only (apply=False)"
+    pr = {k: T(v, dtype).detach().clone().requires_grad_(True) for k, v in st.p.items()}
+    losses = dyn_learn_losses(pr, obs, act, next_obs, rew, noise, use_trg, encoder_loss_coef, 1.0, 1.0 if with_reward else 0.0,
+                              dtype=dtype)
     names = list(pr)
     gs = torch.autograd.grad(losses[0], [pr[k] for k in names], allow_unused=True)
     grads = dict(zip(names, gs))
