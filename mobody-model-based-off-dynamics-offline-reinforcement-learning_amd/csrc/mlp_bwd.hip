@@ -407,9 +407,11 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, int tile_ro
 // 4 consecutive row slices of the same output tile and reduce through LDS; workgroups along the row dimension
 // write separate slabs (deterministic, summed by k_grad_reduce).  Operands of the next 8 rows are prefetched
 // into a second register set while the current 8 rows feed the MFMAs (see wgrad_tile for what makes that overlap real).
-// Block -> work mapping is XCD aware (blocks b and b+8 share an XCD and its L2): all output tiles of one
-// (row slice, member) run on the same XCD back to back, so the slice's activations are fetched from
-// HBM/Infinity Cache once and re-read 4x from that XCD's L2.
+// Block -> work mapping is XCD aware (blocks b and b+8 share an XCD and its L2): every (row slice, member) lives on one
+// XCD, so its activations are fetched from HBM/Infinity Cache once and re-read by its output tiles from that XCD's L2.
+// Along the block index the output TILE varies slowest: the tiles of the heavy 256 x 256 job are dispatched first, all
+// their slices side by side (the tiles resident on an XCD at one time share its few slices' activations), and the cheap
+// narrow jobs fill the one-and-a-half-generation launch's tail.  Which block computes what changes no slab value.
 // ------------------------------------------------------------------------------------------------
 // Buffer descriptor over `nrows` rows of a row-major fp32 matrix (pitch ld floats) starting at the wave-uniform pointer p, and a
 // dword load through it: the per-lane byte offset rides in voffset, the wave-uniform row offset in soffset (a scalar register).
@@ -447,6 +449,20 @@ __device__ __forceinline__ void wgrad_store(const WgradJob& jb, const WgradArgs&
   if (w >= 2) sweep(true);
   lds_barrier();
   float* slab = a.slabs + (long long)slice * a.slab_stride + jb.out_off + m * a.out_mstride;
+  // Wide storage and W3's transposed [n][Np3] rows keep four consecutive k adjacent: the tile leaves in 16-byte stores (a wave
+  // instruction = 1 KB contiguous for the wide jobs instead of 64 dwords at a 16-byte stride); same sums, same destinations.
+  if ((jb.wide || jb.transposed) && (jb.out_k & 3) == 0 && (!jb.transposed || (jb.out_ld & 3) == 0)) {
+    for (int g = threadIdx.x; g < (TK / 4) * TN; g += NTHREADS) {
+      const int kg = g / TN, nn = g - kg * TN;
+      f32x4 s;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { const int idx = (4 * kg + c) * TN + nn; s[c] = red[idx] + red[TK * TN + idx]; }
+      const int gk = k0 + 4 * kg, gn = n0 + nn;
+      if (gk < jb.out_k && gn < jb.out_n)
+        *reinterpret_cast<f32x4*>(slab + (jb.transposed ? (long long)gn * jb.out_ld + gk : wide_idx(gk, gn))) = s;
+    }
+    return;
+  }
   for (int idx = threadIdx.x; idx < TK * TN; idx += NTHREADS) {
     const int kk = idx / TN, nn = idx - kk * TN;
     const float s = red[idx] + red[TK * TN + idx];
@@ -737,8 +753,9 @@ __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradAr
 __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_f16(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  const int sm = xcd + 8 * (j / a.tiles_total);
-  const int t = j % a.tiles_total;
+  const int groups = (a.nsplit * a.members + 7) / 8;
+  const int t = j / groups;
+  const int sm = xcd + 8 * (j - t * groups);
   if (sm >= a.nsplit * a.members) return;
   const int slice = sm / a.members, m = sm - slice * a.members;
   if (t < a.job[0].ntiles) wgrad_tile_f16(a.job[0], a, t, slice, m, red);
@@ -750,8 +767,9 @@ template <int NPL>
 __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_bf(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  const int sm = xcd + 8 * (j / a.tiles_total);
-  const int t = j % a.tiles_total;
+  const int groups = (a.nsplit * a.members + 7) / 8;
+  const int t = j / groups;
+  const int sm = xcd + 8 * (j - t * groups);
   if (sm >= a.nsplit * a.members) return;
   const int slice = sm / a.members, m = sm - slice * a.members;
   if (t < a.job[0].ntiles) wgrad_tile_bf<NPL>(a.job[0], a, t, slice, m, red);
@@ -761,10 +779,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_bf(WgradArgs a) {
 
 __global__ __launch_bounds__(NTHREADS, 4) void k_wgrad(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
-  // XCD-aware decode: blocks with equal (id % 8) share an XCD; consecutive ones walk the tiles of one (slice, member)
+  // XCD-aware decode: blocks with equal (id % 8) share an XCD; the output tile varies slowest (block comment above)
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  const int sm = xcd + 8 * (j / a.tiles_total);
-  const int t = j % a.tiles_total;
+  const int groups = (a.nsplit * a.members + 7) / 8;
+  const int t = j / groups;
+  const int sm = xcd + 8 * (j - t * groups);
   if (sm >= a.nsplit * a.members) return;
   const int slice = sm / a.members, m = sm - slice * a.members;
   if (t < a.job[0].ntiles) wgrad_tile<2>(a.job[0], a, t, slice, m, red);
