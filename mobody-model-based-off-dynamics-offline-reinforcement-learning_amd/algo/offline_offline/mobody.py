@@ -193,7 +193,11 @@ class MOBODY(object):
         self.precision = ops.prec_id(self.mfma)
         self.rng = config.get("rng", "numpy")               # 'numpy' = reference index/elite streams; 'device' = Philox
         self.seed = int(config.get("seed", 0))
-        self.fake_replay_buffer = utils.ReplayBuffer(S, A, self.device, rng=self.rng, seed=self.seed + 17)
+        # config['fake_buffer_size']: rows of the fake buffer's ring (default: the reference's 1e6).  With a sharded refresh a
+        # rank appends 1 / world of the reference's rows, so a driver that wants the reference's retention (how many refreshes
+        # a rollout survives) gives every rank ceil(1e6 / world) rows, as the CLI does.
+        self.fake_replay_buffer = utils.ReplayBuffer(S, A, self.device, max_size=int(config.get("fake_buffer_size", int(1e6))),
+                                                     rng=self.rng, seed=self.seed + 17)
         self.total_it = 0
         self.q_funcs = _PackedNet(S + A, 1, 2, ("network1.", "network2."), self.device, precision=self.precision)
         self.target_q_funcs = self.q_funcs.clone().eval()                         # deepcopy, mobody.py:116

@@ -15,6 +15,12 @@ dynamics follows the reference's load-or-train branches (`build_dynamics`, train
 `--dynamics_path` / the default `pretrained_dynamics/<env>/srcdatatype-...` tree when present and `--train_dynamics 0`,
 otherwise `MOBODYEnsembleDynamics.train` on the two buffers, then save in the reference's directory scheme.  A random
 "alive" ensemble is kept only under an explicit `--synthetic 1` with nothing to load.
+
+Several GPUs: started once per GPU (`python -m mobody_amd.dp --gpus N -- <arguments>`, or `python -m torch.distributed.run
+--nproc-per-node N train_mobody.py <arguments>`) every process becomes one data-parallel rank (`dp.init_from_env`): same
+arguments and seed everywhere, replicated buffers and weights, sharded minibatches / refresh / pre-training batches, and ONE
+set of outputs (log, prints, checkpoints, saved dynamics) written by rank 0.  There is no flag for it: the rank count comes
+from the launcher's environment, and without WORLD_SIZE nothing below differs from the single-process run.
 """
 import argparse
 import json
@@ -96,6 +102,17 @@ class ScalarLog:
 
     def close(self):
         self.f.close()
+
+
+class NullLog:
+    """The writer of every rank but 0: same surface, drops what it is given.  It must not be `None` -- MOBODY.train runs its
+    logging steps eagerly and only when it has a writer, and all ranks have to take the same eager-or-replay decision on
+    every step (the two paths issue their collectives differently)."""
+
+    def add_scalar(self, *_, **__):
+        pass
+
+    flush = close = add_scalar
 
 
 def load_datasets(args):
@@ -186,7 +203,7 @@ def dynamics_save_path(args, root):
     return os.path.join(root, args.env, f"srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}")
 
 
-def build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic):
+def build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic, rank=0, world=1):
     """The reference's load-or-train logic for the ensemble dynamics (train_mobody.py:817-877), branch for branch:
 
     * `--dynamics_path P --train_dynamics 0`: load `P/<env>/srcdatatype-...` when that directory exists, otherwise train on
@@ -198,8 +215,36 @@ def build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit
 
     The one addition of this build: with an EXPLICIT `--synthetic 1`, no `--dynamics_path` and nothing in the default tree,
     `--train_dynamics 0` keeps a random-initialised ensemble whose transition head is shifted into the task's alive box (benchmarks and smoke runs on
-    synthetic buffers; there is nothing to learn from them).  Returns 'loaded' / 'trained' / 'random'."""
+    synthetic buffers; there is nothing to learn from them).  Returns 'loaded' / 'trained' / 'random'.
+
+    Data parallel (`world` > 1): every rank takes the SAME branch.  What the branch depends on the filesystem for (does the
+    directory exist, does the load succeed) is evaluated by rank 0 alone and broadcast; a branch the flags alone decide
+    (`--train_dynamics 1`) needs no exchange, so `dynamics.train` -- sharded over the ranks, and the first thing it does is refuse
+    what data parallel does not support -- is reached before any collective.  Rank 0 writes; the others wait at a barrier
+    until the files are there."""
     from mobody_amd import synthetic
+
+    def agree(decide):
+        """rank 0's decide() -> True / False on every rank."""
+        if world == 1:
+            return decide()
+        flag = torch.tensor([int(decide()) if rank == 0 else 0], dtype=torch.int64, device=model.device)
+        torch.distributed.broadcast(flag, 0)
+        return bool(flag.item())
+
+    def try_load(save_path):
+        try:
+            dynamics.load(save_path)
+            return True
+        except Exception:                                                      # the reference's bare `except:` (:851)
+            return False
+
+    def loaded(save_path, rank0_has_it=False):
+        if rank != 0 or not rank0_has_it:
+            dynamics.load(save_path)
+        if rank == 0:
+            print("----------pretrained dynamics loaded----------")
+        return "loaded"
 
     def train_and_save(save_path):
         if explicit_synthetic:
@@ -209,29 +254,28 @@ def build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit
                        max_epochs=args.dynamics_max_epochs)
         if args.dynamics_path is not None:                                     # :831-836, 855-860, 867-872
             save_path = dynamics_save_path(args, args.dynamics_path)
-        os.makedirs(save_path, exist_ok=True)
-        dynamics.save(save_path)
-        print(f"----------dynamics trained and saved to {save_path}----------")
+        if rank == 0:
+            os.makedirs(save_path, exist_ok=True)
+            dynamics.save(save_path)
+            print(f"----------dynamics trained and saved to {save_path}----------")
+        if world > 1:
+            torch.distributed.barrier()
         return "trained"
 
     if args.dynamics_path is not None and args.train_dynamics == 0:            # :819-840
         save_path = dynamics_save_path(args, args.dynamics_path)
-        if os.path.exists(save_path):
-            dynamics.load(save_path)
-            print("----------pretrained dynamics loaded----------")
-            return "loaded"
+        if agree(lambda: os.path.exists(save_path)):
+            return loaded(save_path)
         return train_and_save(save_path)
     save_path = dynamics_save_path(args, "pretrained_dynamics")                # :842-846
-    if os.path.exists(save_path) and args.train_dynamics == 0:
-        try:
-            dynamics.load(save_path)
-            print("----------pretrained dynamics loaded----------")
-            return "loaded"
-        except Exception:                                                      # the reference's bare `except:` (:851)
-            return train_and_save(save_path)
+    if args.train_dynamics == 0 and agree(lambda: os.path.exists(save_path)):
+        if agree(lambda: try_load(save_path)):                                 # a failing load falls through to training
+            return loaded(save_path, rank0_has_it=True)
+        return train_and_save(save_path)
     if explicit_synthetic and args.train_dynamics == 0:
         synthetic.alive_dynamics(model, task)
-        print("--synthetic 1: nothing to load, random-initialised ensemble dynamics (pass --train_dynamics 1 to pre-train it)")
+        if rank == 0:
+            print("--synthetic 1: nothing to load, random-initialised ensemble dynamics (pass --train_dynamics 1 to pre-train it)")
         return "random"
     return train_and_save(save_path)
 
@@ -242,6 +286,15 @@ def main(argv=None):
         args.env = args.env.replace("_", "-")
     if args.mode != 3:
         raise NotImplementedError("only mode 3 (offline-offline, MOBODY) is built on the MI355X path")
+    from mobody_amd import dp
+    rank, world, device = dp.init_from_env()          # one data-parallel rank per process when a launcher set WORLD_SIZE
+    try:
+        return _run(args, rank, world, device)
+    finally:
+        dp.shutdown()
+
+
+def _run(args, rank, world, device):
     from mobody_amd import synthetic
     from mobody_amd.algo import utils
     from mobody_amd.algo.call_algo import call_algo
@@ -249,6 +302,7 @@ def main(argv=None):
     from mobody_amd.algo.dynamics.mobody_module import MOBODYModule
     from mobody_amd.algo.mb_utils.terminal_funs import get_termination_fn
 
+    say = print if rank == 0 else (lambda *a, **k: None)           # one set of prints
     synthetic_mode = args.synthetic
     if synthetic_mode is None:
         try:
@@ -265,12 +319,17 @@ def main(argv=None):
             raise ValueError(f"--src_data has shapes {src_ds['observations'].shape[1]}/{src_ds['actions'].shape[1]}, "
                              f"env {args.env} expects {state_dim}/{action_dim}")
     max_action = 1.0
+    # the same seed on every rank: the mirror folds the rank into its device-RNG seeds (dp.rank_salt) and broadcasts rank 0's
+    # replica before the first step (sync_replicas), and every rank builds the same buffers
     torch.manual_seed(args.seed); np.random.seed(args.seed); random.seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
-    device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     config = build_config(args, state_dim, action_dim, max_action)
+    if world > 1 and int(config.get("shard_refresh", 1)):
+        # each rank appends 1 / world of the refresh's rows: a ring of 1 / world of the reference's capacity keeps rollouts
+        # as long as the reference does
+        config["fake_buffer_size"] = -(-int(1e6) // world)
     env_penalty_coef = 0.0 if args.mobile == 1 else args.env_penalty_coef
-    print("-" * 60 + f"\nPolicy: {args.policy}, Env: {args.env}, Seed: {args.seed}\n" + "-" * 60)
+    say("-" * 60 + f"\nPolicy: {args.policy}, Env: {args.env}, Seed: {args.seed}\n" + "-" * 60)
 
     terminal_fn = get_termination_fn(task)
     policy = call_algo(args.policy, config, args.mode, device, terminal_fn=terminal_fn)
@@ -282,7 +341,7 @@ def main(argv=None):
     else:                                             # train_mobody.py:548-557: both buffers adopt their datasets
         src_rb.convert_D4RL(src_ds)
         tar_rb.convert_D4RL(tar_ds)
-        print(f"datasets: {src_rb.size} source / {tar_rb.size} target transitions")
+        say(f"datasets: {src_rb.size} source / {tar_rb.size} target transitions")
 
     model = MOBODYModule(obs_dim=state_dim, action_dim=action_dim, hidden_dims=256, num_ensemble=7, num_elites=5,
                          weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=device,
@@ -290,22 +349,30 @@ def main(argv=None):
     dynamics = MOBODYEnsembleDynamics(config, model, None, None, terminal_fn, penalty_coef=env_penalty_coef,
                                       rng=args.rng, seed=args.seed + 3)
     outdir = f"{args.dir}/{args.policy}/{args.env}-srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}/r{args.seed}{args.out_dir_remark}"
-    writer = ScalarLog(f"{outdir}/tb/scalars.csv") if args.scalars else None          # train_mobody.py:455-458
-    build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic=args.synthetic == 1)
+    writer = None
+    if args.scalars:                                                                   # train_mobody.py:455-458
+        writer = ScalarLog(f"{outdir}/tb/scalars.csv") if rank == 0 else NullLog()
+    build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic=args.synthetic == 1,
+                   rank=rank, world=world)
     config.update({"dynamics": dynamics})
     policy.dynamics = dynamics
 
-    if args.save_model:
+    if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
     start = time.time()
     for t in range(int(config["max_step"])):
         policy.train(src_rb, tar_rb, config["batch_size"], writer, None)
         if (t + 1) % args.log_every == 0:
-            q, pi, bc = policy.losses()
+            if world > 1:                             # losses() is this rank's share of the global means (kernels scale by
+                share = policy._loss[:3].clone()      # 1 / N_global): summed on log steps only
+                torch.distributed.all_reduce(share)
+                q, pi, bc = (float(x) for x in share.tolist())
+            else:
+                q, pi, bc = policy.losses()
             dt = time.time() - start
-            print(f"step {t + 1}: q_loss {q:.4f} pi_loss {pi:.4f} bc_loss {bc:.4f}  {args.log_every / dt:.1f} grad-steps/s")
+            say(f"step {t + 1}: q_loss {q:.4f} pi_loss {pi:.4f} bc_loss {bc:.4f}  {args.log_every / dt:.1f} grad-steps/s")
             start = time.time()
-        if (t + 1) % config["eval_freq"] == 0:
+        if (t + 1) % config["eval_freq"] == 0 and rank == 0:           # rank 0 alone: no collective in this block
             # The reference's evaluation block (train_mobody.py:928-975) rolls the policy out in the simulators; of it, what
             # does not need a simulator is kept on the same cadence: the transition model's error on TARGET transitions
             # (eval_policy_batch's obs-RMSE / reward-MSE, :100-133, here on a target-buffer batch) and the model checkpoint.
