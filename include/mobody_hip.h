@@ -7,6 +7,8 @@
  *   mobody_dyn_forward   <- MOBODYModule.forward_trg/forward_src  algo/dynamics/mobody_module.py:315-330
  *   mobody_dyn_step      <- MOBODYEnsembleDynamics.step           algo/dynamics/mobody_dynamics.py:193-265
  *                           (+ termination predicates             algo/mb_utils/terminal_funs.py:10-149)
+ *   mobody_ens_step      <- the same step() for either model and every uncertainty_mode   mobody_dynamics.py:193-265 (:241-252)
+ *   mobody_ens_rollout   <- MOBODY.rollout + add_batch, likewise  mobody.py:596-657, utils.py:43-92
  *   mobody_mlp3_forward  <- Policy / DoubleQFunc / ValueFunc fwd  algo/offline_offline/mobody.py:35-83
  *   mobody_rollout       <- MOBODY.rollout + add_batch            algo/offline_offline/mobody.py:596-657, algo/utils.py:43-92
  *   mobody_gather_batch  <- ReplayBuffer.sample x3 + torch.cat    algo/utils.py:127-148, mobody.py:399-400,516-529
@@ -161,6 +163,36 @@ int mobody_mopo_step(const float* dyn_blob, const float* dyn_planes, const float
                      float* reward, uint8_t* terminal, float* penalty, float* raw_reward, float* mean_out,
                      float* workspace, void* stream);
 
+/* uncertainty_mode of MOBODYEnsembleDynamics (mobody_dynamics.py:241-252): which penalty the sample kernel forms from the
+ * ensemble means (avg = their mean over the 7 members, var_d = the unbiased variance over the members of state dim d) */
+enum { MOBODY_UNC_PAIRWISE = 0,    /* 'pairwise-diff' amax_e ||mean_e - avg||_2 over d < S-1              (:246-249) */
+       MOBODY_UNC_ALEATORIC = 1,   /* 'aleatoric'     amax_e ||std_e||_2 = sqrt(sum_{d < S} var_d): ALL S dims (:241-243) */
+       MOBODY_UNC_ENS_STD = 2 };   /* 'ensemble_std'  sqrt(mean_{d < S-1} var_d)                           (:250-252) */
+
+/* MOBODYEnsembleDynamics.step (mobody_dynamics.py:193-265) in every runnable variant, arguments by name: what
+ * mobody_dyn_step takes (same meanings), plus
+ *   mopo_blob / mopo_blob_T  NULL = the latent model; else the MOPO ablation's 7-member MLP as in mobody_mopo_step
+ *                            (use_trg is ignored: forward_trg == forward_src, mobody_module.py:264-266)
+ *   uncertainty_mode         MOBODY_UNC_* (:241-252); any other value is MOBODY_E_ARG (the reference raises ValueError)
+ *   call_dev                 for both models
+ * struct_bytes = sizeof(MobodyEnsStep) (a binding built against another header is refused).  A NaN / Inf member mean
+ * makes the row's penalty NaN in every mode, as torch's amax / norm / var / sqrt do.  mobody_dyn_step and mobody_mopo_step
+ * are this call with MOBODY_UNC_PAIRWISE.  workspace: mobody_dyn_step_workspace(S, A, B) floats. */
+typedef struct MobodyEnsStep {
+  int32_t struct_bytes, uncertainty_mode;
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T;
+  int32_t precision, S, A, task;
+  const float *obs, *act;
+  int64_t B;
+  const float* noise; const int32_t* elite_idx; const uint8_t* alive;
+  const int32_t* elites;            /* HOST array */
+  int32_t n_elites; uint32_t seed, call; int32_t use_penalty;
+  const int64_t* call_dev;
+  float penalty_coef; int32_t use_trg;
+  float *next_obs, *reward; uint8_t* terminal; float *penalty, *raw_reward, *mean_out, *workspace;
+} MobodyEnsStep;
+int mobody_ens_step(const MobodyEnsStep* a, void* stream);
+
 /* ---- replay buffer views (used by the rollout below and by the gather / append entry points) ---- */
 typedef struct MobodyBufferView {   /* ReplayBuffer fields, algo/utils.py:19-23 */
   const float* state; const float* action; const float* next_state; const float* reward; const float* not_done;
@@ -189,6 +221,31 @@ int mobody_rollout(const float* dyn_blob, const float* dyn_planes, const float* 
                    const float* init_obs, int64_t B, int H, const int32_t* elites, int n_elites, uint32_t seed, uint32_t call0,
                    float penalty_coef, int use_penalty, int use_trg, float env_filter, int filter_bad_rollout,
                    const MobodyBufferView* ring, int64_t cap, int64_t* ptr_size, float* workspace, void* stream);
+
+/* MOBODY.rollout + add_batch (mobody.py:596-657, utils.py:43-92) for either model and every uncertainty_mode, arguments by
+ * name: what mobody_rollout takes (same meanings), plus mopo_blob / mopo_blob_T, uncertainty_mode and call_dev as in
+ * MobodyEnsStep (step t draws at call id call0 + t + call_dev[0]).  The mopo form has the latent form's 7 launches per
+ * horizon step -- policy forward, member MLP with the observation added in its output stage, sample with filter / alive
+ * update, reward head, finalize, the two-launch append -- and no host work between steps.  mobody_rollout is this call
+ * with the latent model and MOBODY_UNC_PAIRWISE.  workspace: mobody_ens_rollout_workspace(a) floats (reads S, A, B). */
+typedef struct MobodyEnsRollout {
+  int32_t struct_bytes, uncertainty_mode;
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T, *actor_blob, *actor_blob_T;
+  int32_t precision, S, A, task;
+  const float* init_obs;
+  int64_t B;
+  int32_t H, n_elites;
+  const int32_t* elites;            /* HOST array */
+  uint32_t seed, call0;
+  const int64_t* call_dev;
+  float max_action, penalty_coef, env_filter; int32_t use_penalty, use_trg, filter_bad_rollout;
+  const MobodyBufferView* ring;
+  int64_t cap;
+  int64_t* ptr_size;
+  float* workspace;
+} MobodyEnsRollout;
+int64_t mobody_ens_rollout_workspace(const MobodyEnsRollout* a);
+int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream);
 
 /* Termination predicate alone: done[B] (uint8) = terminal_fn(next_obs[B][S])  (terminal_funs.py:10-121). */
 int mobody_termination(int task, const float* next_obs, int64_t B, int S, uint8_t* done, void* stream);

@@ -60,8 +60,29 @@ class MobodyHyper(C.Structure):
                 ("q_weighted", i32), ("scale_q", i32), ("precision", i32)]
 
 
+class MobodyEnsStep(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
+                ("mopo_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32), ("task", i32), ("obs", vp), ("act", vp),
+                ("B", i64), ("noise", vp), ("elite_idx", vp), ("alive", vp), ("elites", C.POINTER(i32)), ("n_elites", i32),
+                ("seed", u32), ("call", u32), ("use_penalty", i32), ("call_dev", vp), ("penalty_coef", f32), ("use_trg", i32),
+                ("next_obs", vp), ("reward", vp), ("terminal", vp), ("penalty", vp), ("raw_reward", vp), ("mean_out", vp),
+                ("workspace", vp)]
+
+
+class MobodyEnsRollout(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
+                ("mopo_blob_T", vp), ("actor_blob", vp), ("actor_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32),
+                ("task", i32), ("init_obs", vp), ("B", i64), ("H", i32), ("n_elites", i32), ("elites", C.POINTER(i32)),
+                ("seed", u32), ("call0", u32), ("call_dev", vp), ("max_action", f32), ("penalty_coef", f32),
+                ("env_filter", f32), ("use_penalty", i32), ("use_trg", i32), ("filter_bad_rollout", i32),
+                ("ring", C.POINTER(MobodyBufferView)), ("cap", i64), ("ptr_size", vp), ("workspace", vp)]
+
+
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
 
+
+# MOBODYEnsembleDynamics(uncertainty_mode=...) -> MOBODY_UNC_* (mobody_dynamics.py:241-252)
+UNCERTAINTY_MODES = {"pairwise-diff": 0, "aleatoric": 1, "ensemble_std": 2}
 
 TERM_IDS = {"never": 0, "halfcheetah": 1, "hopper": 2, "ant": 3, "walker2d": 4, "humanoid": 5, "pen": 6}
 
@@ -83,6 +104,9 @@ PROTOTYPES = {
                                   u32, u32, vp, f32, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
     "mobody_mopo_step": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, vp, vp, C.POINTER(i32), C.c_int,
                                    u32, u32, f32, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "mobody_ens_step": (C.c_int, [C.POINTER(MobodyEnsStep), vp]),
+    "mobody_ens_rollout_workspace": (i64, [C.POINTER(MobodyEnsRollout)]),
+    "mobody_ens_rollout": (C.c_int, [C.POINTER(MobodyEnsRollout), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_rollout": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp, i64, C.c_int, C.POINTER(i32), C.c_int, u32, u32, f32,
                                  C.c_int, C.c_int, f32, C.c_int, C.POINTER(MobodyBufferView), i64, vp, vp, vp]),

@@ -46,8 +46,9 @@ class StandardScaler(object):
 class MOBODYEnsembleDynamics(object):
     def __init__(self, config, model, optim, scaler, terminal_fn, penalty_coef=0.0, uncertainty_mode="pairwise-diff",
                  rng="numpy", seed=0):
-        if uncertainty_mode != "pairwise-diff":
-            raise NotImplementedError("only the reference's default 'pairwise-diff' penalty is accelerated")
+        # the three penalties of the reference's step() (:241-252), formed in the sample kernel.  The reference raises a bare
+        # ValueError inside step() for any other string; here the constructor does, naming the accepted ones
+        self._unc_id = ops.unc_id(str(uncertainty_mode))
         self.model, self.optim = model, optim
         self.terminal_fn = terminal_fn
         self._penalty_coef = penalty_coef
@@ -106,7 +107,7 @@ class MOBODYEnsembleDynamics(object):
                             penalty_coef=float(self._penalty_coef or 0.0),
                             use_penalty=bool(use_penalty), use_trg=bool(use_trg), want_mean=want_mean,
                             workspace=self._ws, planes=m.planes() if self.precision else None, precision=self.precision,
-                            mopo=m.packed_mopo() if getattr(m, "mopo", False) else None)
+                            mopo=m.packed_mopo() if getattr(m, "mopo", False) else None, uncertainty_mode=self._unc_id)
 
     @torch.no_grad()
     def step(self, obs, action, use_penalty=True, use_trg=True):

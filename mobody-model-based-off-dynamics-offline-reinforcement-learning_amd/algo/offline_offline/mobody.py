@@ -366,9 +366,10 @@ class MOBODY(object):
         return res, {"num_transitions": n_tr, "reward_mean": rew_mean}
 
     def _rollout_into_fake(self, init_obss, rollout_length, use_trg=True):
-        """Same transitions as rollout()+add_batch, entirely on the device (`mobody_rollout`): rows keep their index, an
+        """Same transitions as rollout()+add_batch, entirely on the device (`mobody_ens_rollout`): rows keep their index, an
         alive mask replaces the shrinking batch, the penalty filter and the alive update are formed in the sample kernel and
-        the kept rows are stream-compacted into the ring -- 7 launches per horizon step, no host work between steps."""
+        the kept rows are stream-compacted into the ring -- 7 launches per horizon step, no host work between steps.  Latent
+        and mopo model alike, with the dynamics' uncertainty mode."""
         if rollout_length == 0:
             return 0
         dyn, m, fb = self.dynamics, self.dynamics.model, self.fake_replay_buffer
@@ -381,7 +382,8 @@ class MOBODY(object):
                                     use_trg, True, self.config["env_filter"], self.config["filter_bad_rollout"],   # quirk Q1
                                     fb._fields(), fb.max_size, fb.ptr_size, getattr(self, "_roll_ws", None),
                                     dyn_planes=m.planes() if dyn.precision else None, actor_blob_T=self.policy.blob_T,
-                                    precision=dyn.precision)
+                                    precision=dyn.precision, mopo=m.packed_mopo() if getattr(m, "mopo", False) else None,
+                                    uncertainty_mode=dyn._unc_id)
         dyn._calls += rollout_length
         fb._pull()
         return B * rollout_length
@@ -401,10 +403,10 @@ class MOBODY(object):
         t_idx = tar_rb.draw_indices(n_tar)
         src = ops.gather_batch([src_rb._fields()], [s_idx], self.S, self.A)
         tar = ops.gather_batch([tar_rb._fields()], [t_idx], self.S, self.A)
-        if self.rng == "device" and not getattr(getattr(self.dynamics, "model", None), "mopo", False):
+        if self.rng == "device":
             self._rollout_into_fake(src[0], cfg["src_rollout_length"])
             self._rollout_into_fake(tar[0], cfg["trg_rollout_length"])
-        else:                                  # NumPy-RNG parity mode, and the mopo ablation (host loop over mobody_mopo_step)
+        else:                                  # NumPy-RNG parity mode: the reference's host loop
             tr, _ = self.rollout(src[0], cfg["src_rollout_length"])
             self.fake_replay_buffer.add_batch(tr)
             tr, _ = self.rollout(tar[0], cfg["trg_rollout_length"])
@@ -435,8 +437,9 @@ class MOBODY(object):
         # the step, the noise call id read from the device counter.  The V phase of `advantage` is captured on one GPU (its
         # gradient all-reduce belongs to the eager exchange protocol).
         dyn = self.dynamics
+        # (latent or mopo model: the ensemble step takes the device call word for both)
         par_ok = self.penalty_type != "par" or (dyn is not None and getattr(dyn, "noise_fn", None) is None
-                                                and dyn.rng == "device" and not getattr(dyn.model, "mopo", False))
+                                                and dyn.rng == "device")
         adv_ok = not self.config["advantage"] or (self._world() == 1 and self.fused_update and self._v_ws is not None)
         # logging steps run eagerly: every 5000th (losses / value scalars) and, under 'par', every 100th (mobody.py:432-433)
         logs = writer is not None and (self.total_it % 5000 == 0 or (self.penalty_type == "par" and self.total_it % 100 == 0))
@@ -551,7 +554,8 @@ class MOBODY(object):
         if self.penalty_type == "par":                  # the captured ensemble step reads these
             m = self.dynamics.model
             dyn_key = (m.packed().data_ptr(), m.planes().data_ptr() if self.dynamics.precision else 0, self.dynamics.precision,
-                       m.elites_host(), float(self.dynamics._penalty_coef or 0.0))
+                       m.elites_host(), float(self.dynamics._penalty_coef or 0.0), self.dynamics._unc_id,
+                       tuple(t.data_ptr() for t in m.packed_mopo()) if getattr(m, "mopo", False) else None)
         key = (batch_size, id(src), id(tar), src.state.data_ptr(), tar.state.data_ptr(), world, segmented,
                id(fb), fb.state.data_ptr(), fb.ptr_size.data_ptr(), tuple(t.data_ptr() for t in self._batch),
                tuple((n.blob.data_ptr(), n.blob_T.data_ptr()) for n in nets), self.precision,

@@ -4,8 +4,9 @@
 //                  one workgroup = 64 rows x ONE member, the 9 ensemble layers
 //                  (zs1-3, za1-2, transition1-3) chained through one LDS image;
 //                  grid = (ceil(B/64), 7) so even B = 4096 fills the chip (448 WGs).
-//   k_dyn_sample   ensemble std, Gaussian sample of the elite member, pairwise-diff
-//                  penalty, termination predicate (one thread per (row, state dim), whole rows per
+//   k_dyn_sample   ensemble std, Gaussian sample of the elite member, the penalty of the
+//                  uncertainty mode (pairwise-diff | aleatoric | ensemble_std), termination predicate
+//                  (one thread per (row, state dim), whole rows per
 //                  workgroup)                                       mobody_dynamics.py:218-256,
 //                                                                    terminal_funs.py:10-113
 //   reward head    generic fused MLP forward (Swish) on [s,a,s']     mobody_module.py:295-302
@@ -202,6 +203,15 @@ __device__ __forceinline__ bool term_predicate(int task, const float* n, int S) 
 // row walking its S floats: every store instruction scattered 64 dwords over 64 rows and WRITE_SIZE showed 10x the
 // algorithmic bytes.)  The per-row sums over d (penalty) go through LDS and are added in increasing d by one thread
 // per (row, member): same order as a serial loop, no atomics.
+//
+// MODE = uncertainty_mode of the reference's step() (mobody_dynamics.py:241-252); all three are built from the squared
+// deviations t^2 = (mean_e - avg)^2 the sample already holds in LDS, so no mode reads or writes anything more than the default:
+//   MOBODY_UNC_PAIRWISE   amax_e ||mean_e - avg||_2 over d < S-1                                        (:246-249)
+//   MOBODY_UNC_ALEATORIC  amax_e ||std_e||_2 with std = torch.std(mean, 0) repeated over the members: seven equal norms,
+//                         sqrt(sum_{d < S} var_d), var_d = sum_e t^2 / 6 -- the last state dim is NOT dropped  (:241-243)
+//   MOBODY_UNC_ENS_STD    sqrt(mean_{d < S-1} var_d)                                                     (:250-252)
+// The two barriers order LDS traffic only (nothing global is handed between threads).
+template <int MODE>
 __global__ __launch_bounds__(256) void k_dyn_sample(DynSampleArgs a, int rpb) {
   __shared__ float s_nxt[256];
   __shared__ float s_t2[256 * NENS];
@@ -235,23 +245,34 @@ __global__ __launch_bounds__(256) void k_dyn_sample(DynSampleArgs a, int rpb) {
     a.next_obs[b * S + d] = v;
     s_nxt[tid] = v;
   }
-  __syncthreads();
-  for (int t = tid; t < rpb * NENS; t += 256) {                            // (row, member): sum over d < S-1, in order
+  lds_barrier();
+  const int nd = MODE == MOBODY_UNC_ALEATORIC ? S : S - 1;                 // state dims under the sum
+  for (int t = tid; t < rpb * NENS; t += 256) {                            // (row, member): sum over d < nd, in order
     const int rr = t / NENS, e = t - rr * NENS;
     float sq = 0.f;
-    for (int dd = 0; dd < S - 1; ++dd) sq += s_t2[(rr * S + dd) * NENS + e];
+    for (int dd = 0; dd < nd; ++dd) sq += s_t2[(rr * S + dd) * NENS + e];
     s_sq[t] = sq;
   }
-  __syncthreads();
+  lds_barrier();
   if (tid < rpb && row0 + tid < a.B) {
     const long long bb = row0 + tid;
-    // torch.amax propagates NaN (one non-finite member makes every norm of the row NaN); fmaxf would drop it and
-    // the row would pass `penalty <= env_filter` with NaN next_obs, where the reference's comparisons are all False
-    float pmax = 0.f;
-    bool bad = false;
+    if constexpr (MODE == MOBODY_UNC_PAIRWISE) {
+      // torch.amax propagates NaN (one non-finite member makes every norm of the row NaN); fmaxf would drop it and
+      // the row would pass `penalty <= env_filter` with NaN next_obs, where the reference's comparisons are all False
+      float pmax = 0.f;
+      bool bad = false;
 #pragma unroll
-    for (int e = 0; e < NENS; ++e) { const float q = s_sq[tid * NENS + e]; bad = bad || (q != q); pmax = fmaxf(pmax, q); }
-    a.penalty[bb] = bad ? __builtin_nanf("") : sqrtf(pmax);                // :246-249 (last state dim dropped)
+      for (int e = 0; e < NENS; ++e) { const float q = s_sq[tid * NENS + e]; bad = bad || (q != q); pmax = fmaxf(pmax, q); }
+      a.penalty[bb] = bad ? __builtin_nanf("") : sqrtf(pmax);              // :246-249 (last state dim dropped)
+    } else {
+      // sum_d var_d = (sum_e sum_d t^2) / 6: plain adds, so a non-finite member mean (t = NaN for every member of that
+      // dim, through the average) makes the row's penalty NaN as torch.var / norm / sqrt do
+      float tot = 0.f;
+#pragma unroll
+      for (int e = 0; e < NENS; ++e) tot += s_sq[tid * NENS + e];
+      const float den = MODE == MOBODY_UNC_ALEATORIC ? (float)(NENS - 1) : (float)(NENS - 1) * (float)(S - 1);
+      a.penalty[bb] = sqrtf(tot / den);                                    // :241-243 | :250-252
+    }
     bool done = term_predicate(a.task, s_nxt + tid * S, S);
     const bool was_alive = a.alive ? a.alive[bb] != 0 : true;
     if (!was_alive) done = true;
@@ -386,74 +407,78 @@ extern "C" int64_t mobody_dyn_step_workspace(int S, int A, int64_t B) {
   return (int64_t)NENS * B * S + (int64_t)NENS * B;    // ensemble means + per-member reward means
 }
 
-// mopo_blob != null: the MOPO ablation (config['mopo'], mobody_module.py:114-118,218-219,251-254,264-266,288-289) --
+// a.mopo_blob != null: the MOPO ablation (config['mopo'], mobody_module.py:114-118,218-219,251-254,264-266,288-289) --
 // mean[e] = obs + MLP_e([obs, act]) with the 7-member Swish MLP (S+A -> 256 -> 256 -> S) za_src1..3 packed as
 // mobody_mlp_layout(S + A, S, 7); encoders and decoder are bypassed, forward_trg == forward_src.  Everything after the means
 // (std, sample, reward head, penalty, termination) is the same code.
-static int dyn_step_impl(const float* dyn_blob, const float* dyn_planes, const float* mopo_blob, const float* mopo_blob_T,
-                         int precision, int S, int A, int task, const float* obs, const float* act,
-                         int64_t B, const float* noise, const int32_t* elite_idx, const uint8_t* alive,
-                         const int32_t* elites, int n_elites, uint32_t seed, uint32_t call, const int64_t* call_dev, float penalty_coef, int use_penalty,
-                         int use_trg, float* next_obs, float* reward, uint8_t* terminal, float* penalty,
-                         float* raw_reward, float* mean_out, float* workspace, uint8_t* keep, uint8_t* alive_out,
-                         float env_filter, int use_filter, void* stream) {
+// `who`: the public entry point named in error texts.  keep / alive_out / env_filter / use_filter: the rollout's bookkeeping.
+static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep, uint8_t* alive_out, float env_filter,
+                         int use_filter, void* stream) {
+  const int S = a.S, A = a.A, precision = a.precision;
+  const int64_t B = a.B;
   MobodyDynLayout L;
   int rc = mobody_dyn_layout(S, A, &L);
   if (rc) return rc;
-  MB_REQUIRE(B >= 0, "mobody_dyn_step: B < 0");
+  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
+             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
+  MB_REQUIRE(B >= 0, "%s: B < 0", who);
   if (B == 0) return 0;                      // empty batch: nothing to do (pointers may be null)
-  MB_REQUIRE(dyn_blob && obs && act && next_obs && reward && terminal && penalty && workspace, "mobody_dyn_step: null pointer");
-  MB_REQUIRE(task >= MOBODY_TERM_NEVER && task <= MOBODY_TERM_PEN, "mobody_dyn_step: unknown termination id %d", task);
-  MB_REQUIRE(task != MOBODY_TERM_PEN || S > 26, "mobody_dyn_step: pen predicate needs S > 26");
-  MB_REQUIRE(elite_idx != nullptr || (elites != nullptr && n_elites >= 1 && n_elites <= NENS),
-             "mobody_dyn_step: need elite_idx or 1..7 elites");
+  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && a.reward && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d", who, a.task);
+  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
+  MB_REQUIRE(a.elite_idx != nullptr || (a.elites != nullptr && a.n_elites >= 1 && a.n_elites <= NENS),
+             "%s: need elite_idx or 1..7 elites", who);
   hipStream_t st = as_stream(stream);
-  float* mean = mean_out ? mean_out : workspace;
-  float* r_mu = workspace + (int64_t)NENS * B * S;
-  rc = check_dyn_prec("mobody_dyn_step", precision, dyn_planes);
+  float* mean = a.mean_out ? a.mean_out : a.workspace;
+  float* r_mu = a.workspace + (int64_t)NENS * B * S;
+  rc = check_dyn_prec(who, precision, a.dyn_planes);
   if (rc) return rc;
-  if (mopo_blob != nullptr) {
+  if (a.mopo_blob != nullptr) {
     MobodyMlpLayout ML;
     rc = mobody_mlp_layout(S + A, S, NENS, &ML);
     if (rc) return rc;
-    MB_REQUIRE(precision == 0 || mopo_blob_T != nullptr, "mobody_mopo_step: the split-precision modes need the T blob of the MLP");
+    MB_REQUIRE(precision == 0 || a.mopo_blob_T != nullptr, "%s: the split-precision modes need the T blob of the MLP", who);
     Mlp3FwdArgs f{};
-    f.src[0] = obs; f.ld[0] = S; f.n[0] = S;
-    f.src[1] = act; f.ld[1] = A; f.n[1] = A;
-    f.w1 = mopo_blob + ML.w1; f.b1 = mopo_blob + ML.b1; f.w2 = mopo_blob + ML.w2; f.b2 = mopo_blob + ML.b2;
-    f.w3 = mopo_blob + ML.w3; f.b3 = mopo_blob + ML.b3;
+    f.src[0] = a.obs; f.ld[0] = S; f.n[0] = S;
+    f.src[1] = a.act; f.ld[1] = A; f.n[1] = A;
+    f.w1 = a.mopo_blob + ML.w1; f.b1 = a.mopo_blob + ML.b1; f.w2 = a.mopo_blob + ML.w2; f.b2 = a.mopo_blob + ML.b2;
+    f.w3 = a.mopo_blob + ML.w3; f.b3 = a.mopo_blob + ML.b3;
     f.sw1 = f.sb1 = f.sw2 = f.sb2 = f.sw3 = f.sb3 = ML.member_floats;
     f.Kp1 = ML.Kp1; f.Np3 = ML.Np3; f.nout = S; f.rows = B;
     f.out = mean; f.out_mstride = B * S; f.out_ld = S;
     f.out_mode = 0; f.max_action = 1.f;
-    f.resid = obs; f.resid_ld = S;
+    f.resid = a.obs; f.resid_ld = S;
     if (precision == 0) {
       rc = launch_mlp3_fwd(f, NENS, ACT_SWISH, st);
     } else {
-      f.w2_planes = reinterpret_cast<const unsigned short*>(mopo_blob_T + ML.w2p);
+      f.w2_planes = reinterpret_cast<const unsigned short*>(a.mopo_blob_T + ML.w2p);
       f.planes_ms = 2 * ML.t_member_floats;
       rc = launch_mlp3_fwd_bf(f, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, precision, st);
     }
   } else {
-    rc = launch_dyn_fwd(dyn_blob, L, obs, act, B, use_trg, mean, dyn_planes, precision, st);
+    rc = launch_dyn_fwd(a.dyn_blob, L, a.obs, a.act, B, a.use_trg, mean, a.dyn_planes, precision, st);
   }
   if (rc) return rc;
 
   DynSampleArgs sa{};
-  sa.mean = mean; sa.noise = noise; sa.elite_idx = elite_idx; sa.alive = alive;
-  for (int k = 0; k < NENS; ++k) sa.elites[k] = (elites && k < n_elites) ? elites[k] : 0;
-  sa.n_elites = n_elites; sa.seed = seed; sa.call = call; sa.call_dev = (const long long*)call_dev; sa.B = B; sa.S = S; sa.task = task;
-  sa.next_obs = next_obs; sa.penalty = penalty; sa.terminal = terminal;
+  sa.mean = mean; sa.noise = a.noise; sa.elite_idx = a.elite_idx; sa.alive = a.alive;
+  for (int k = 0; k < NENS; ++k) sa.elites[k] = (a.elites && k < a.n_elites) ? a.elites[k] : 0;
+  sa.n_elites = a.n_elites; sa.seed = a.seed; sa.call = a.call; sa.call_dev = (const long long*)a.call_dev; sa.B = B; sa.S = S; sa.task = a.task;
+  sa.next_obs = a.next_obs; sa.penalty = a.penalty; sa.terminal = a.terminal;
   sa.keep = keep; sa.alive_out = alive_out; sa.env_filter = env_filter; sa.use_filter = use_filter;
   const int rpb = 256 / S < 64 ? 256 / S : 64;         // whole rows per workgroup (S <= 256 is checked by the layout)
-  hipLaunchKernelGGL(k_dyn_sample, dim3((unsigned)cdiv(B, rpb)), dim3(256), 0, st, sa, rpb);
+  const dim3 grid((unsigned)cdiv(B, rpb));
+  if (a.uncertainty_mode == MOBODY_UNC_ALEATORIC) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ALEATORIC>, grid, dim3(256), 0, st, sa, rpb);
+  else if (a.uncertainty_mode == MOBODY_UNC_ENS_STD) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ENS_STD>, grid, dim3(256), 0, st, sa, rpb);
+  else hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_PAIRWISE>, grid, dim3(256), 0, st, sa, rpb);
   MB_LAUNCH_OK("k_dyn_sample");
 
   // reward head on [s, a, s'] shared by the 7 members  (mobody_dynamics.py:235)
+  const float* dyn_blob = a.dyn_blob;
   Mlp3FwdArgs m{};
-  m.src[0] = obs; m.ld[0] = S; m.n[0] = S;
-  m.src[1] = act; m.ld[1] = A; m.n[1] = A;
-  m.src[2] = next_obs; m.ld[2] = S; m.n[2] = S;
+  m.src[0] = a.obs; m.ld[0] = S; m.n[0] = S;
+  m.src[1] = a.act; m.ld[1] = A; m.n[1] = A;
+  m.src[2] = a.next_obs; m.ld[2] = S; m.n[2] = S;
   const MobodyLayer &l1 = L.layer[MOBODY_DL_RW1], &l2 = L.layer[MOBODY_DL_RW2], &l3 = L.layer[MOBODY_DL_RW3];
   m.w1 = dyn_blob + l1.w_off; m.b1 = dyn_blob + l1.b_off; m.sw1 = (long long)l1.Kp * l1.Np; m.sb1 = l1.Np;
   m.w2 = dyn_blob + l2.w_off; m.b2 = dyn_blob + l2.b_off; m.sw2 = (long long)l2.Kp * l2.Np; m.sb2 = l2.Np;
@@ -464,16 +489,23 @@ static int dyn_step_impl(const float* dyn_blob, const float* dyn_planes, const f
   if (precision == 0) {
     rc = launch_mlp3_fwd(m, NENS, ACT_SWISH, st);
   } else {
-    m.w2_planes = reinterpret_cast<const unsigned short*>(dyn_planes) + dyn_planes_off(2, 0);
+    m.w2_planes = reinterpret_cast<const unsigned short*>(a.dyn_planes) + dyn_planes_off(2, 0);
     m.planes_ms = DYN_PLANE_MEMBER;
     rc = launch_mlp3_fwd_bf(m, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, precision, st);
   }
   if (rc) return rc;
 
-  DynFinalArgs fa{r_mu, penalty, reward, raw_reward, B, (penalty_coef != 0.f && use_penalty) ? penalty_coef : 0.f};
+  DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
   hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, fa);
   MB_LAUNCH_OK("k_dyn_finalize");
   return 0;
+}
+
+extern "C" int mobody_ens_step(const MobodyEnsStep* a, void* stream) {
+  MB_REQUIRE(a != nullptr, "mobody_ens_step: null argument struct");
+  MB_REQUIRE(a->struct_bytes == (int32_t)sizeof(MobodyEnsStep), "mobody_ens_step: struct_bytes %d != sizeof(MobodyEnsStep) %d",
+             a->struct_bytes, (int)sizeof(MobodyEnsStep));
+  return dyn_step_impl("mobody_ens_step", *a, nullptr, nullptr, 0.f, 0, stream);
 }
 
 extern "C" int mobody_dyn_step(const float* dyn_blob, const float* dyn_planes, int precision, int S, int A, int task,
@@ -483,9 +515,14 @@ extern "C" int mobody_dyn_step(const float* dyn_blob, const float* dyn_planes, i
                                float penalty_coef, int use_penalty,
                                int use_trg, float* next_obs, float* reward, uint8_t* terminal, float* penalty,
                                float* raw_reward, float* mean_out, float* workspace, void* stream) {
-  return dyn_step_impl(dyn_blob, dyn_planes, nullptr, nullptr, precision, S, A, task, obs, act, B, noise, elite_idx, alive, elites, n_elites, seed,
-                       call, call_dev, penalty_coef, use_penalty, use_trg, next_obs, reward, terminal, penalty, raw_reward, mean_out, workspace,
-                       nullptr, nullptr, 0.f, 0, stream);
+  MobodyEnsStep a{};
+  a.dyn_blob = dyn_blob; a.dyn_planes = dyn_planes; a.precision = precision; a.S = S; a.A = A; a.task = task;
+  a.obs = obs; a.act = act; a.B = B; a.noise = noise; a.elite_idx = elite_idx; a.alive = alive; a.elites = elites;
+  a.n_elites = n_elites; a.seed = seed; a.call = call; a.call_dev = call_dev; a.penalty_coef = penalty_coef;
+  a.use_penalty = use_penalty; a.use_trg = use_trg; a.uncertainty_mode = MOBODY_UNC_PAIRWISE;
+  a.next_obs = next_obs; a.reward = reward; a.terminal = terminal; a.penalty = penalty; a.raw_reward = raw_reward;
+  a.mean_out = mean_out; a.workspace = workspace;
+  return dyn_step_impl("mobody_dyn_step", a, nullptr, nullptr, 0.f, 0, stream);
 }
 
 extern "C" int mobody_mopo_step(const float* dyn_blob, const float* dyn_planes, const float* mopo_blob, const float* mopo_blob_T,
@@ -495,9 +532,15 @@ extern "C" int mobody_mopo_step(const float* dyn_blob, const float* dyn_planes, 
                                 float* reward, uint8_t* terminal, float* penalty, float* raw_reward, float* mean_out,
                                 float* workspace, void* stream) {
   MB_REQUIRE(B == 0 || mopo_blob != nullptr, "mobody_mopo_step: null MLP blob");
-  return dyn_step_impl(dyn_blob, dyn_planes, mopo_blob, mopo_blob_T, precision, S, A, task, obs, act, B, noise, elite_idx, alive, elites,
-                       n_elites, seed, call, nullptr, penalty_coef, use_penalty, 1, next_obs, reward, terminal, penalty, raw_reward, mean_out,
-                       workspace, nullptr, nullptr, 0.f, 0, stream);
+  MobodyEnsStep a{};
+  a.dyn_blob = dyn_blob; a.dyn_planes = dyn_planes; a.mopo_blob = mopo_blob; a.mopo_blob_T = mopo_blob_T;
+  a.precision = precision; a.S = S; a.A = A; a.task = task;
+  a.obs = obs; a.act = act; a.B = B; a.noise = noise; a.elite_idx = elite_idx; a.alive = alive; a.elites = elites;
+  a.n_elites = n_elites; a.seed = seed; a.call = call; a.penalty_coef = penalty_coef;
+  a.use_penalty = use_penalty; a.use_trg = 1; a.uncertainty_mode = MOBODY_UNC_PAIRWISE;
+  a.next_obs = next_obs; a.reward = reward; a.terminal = terminal; a.penalty = penalty; a.raw_reward = raw_reward;
+  a.mean_out = mean_out; a.workspace = workspace;
+  return dyn_step_impl("mobody_mopo_step", a, nullptr, nullptr, 0.f, 0, stream);
 }
 
 // ---- whole H-step imagined rollout on the device (MOBODY.rollout + add_batch, mobody.py:596-657, utils.py:43-92) ----
@@ -525,57 +568,91 @@ extern "C" int64_t mobody_rollout_workspace(int S, int A, int64_t B) {
   return w.total;
 }
 
-extern "C" int mobody_rollout(const float* dyn_blob, const float* dyn_planes, const float* actor_blob, const float* actor_blob_T,
-                              int precision, int S, int A, int task, float max_action,
-                              const float* init_obs, int64_t B, int H, const int32_t* elites, int n_elites, uint32_t seed,
-                              uint32_t call0, float penalty_coef, int use_penalty, int use_trg, float env_filter,
-                              int filter_bad_rollout, const MobodyBufferView* ring, int64_t cap, int64_t* ptr_size, float* workspace,
-                              void* stream) {
-  MB_REQUIRE(B >= 0 && H >= 0, "mobody_rollout: bad sizes");
-  if (B == 0 || H == 0) return 0;
-  MB_REQUIRE(B <= cap, "mobody_rollout: %lld rows per step overflow the ring of %lld twice", (long long)B, (long long)cap);
-  MB_REQUIRE(dyn_blob && actor_blob && init_obs && elites && ring && ring->state && ring->action && ring->next_state && ring->reward && ring->not_done &&
-                 ptr_size && workspace, "mobody_rollout: null pointer");
+// H steps of policy forward -> ensemble step (latent or mopo means) -> two-launch append: 7 launches per step for both models
+static int rollout_impl(const char* who, const MobodyEnsRollout& a, void* stream) {
+  const int S = a.S, A = a.A, precision = a.precision;
+  const int64_t B = a.B;
+  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
+             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
+  MB_REQUIRE(B >= 0 && a.H >= 0, "%s: bad sizes", who);
+  if (B == 0 || a.H == 0) return 0;
+  MB_REQUIRE(B <= a.cap, "%s: %lld rows per step overflow the ring of %lld twice", who, (long long)B, (long long)a.cap);
+  const MobodyBufferView* ring = a.ring;
+  MB_REQUIRE(a.dyn_blob && a.actor_blob && a.init_obs && a.elites && ring && ring->state && ring->action && ring->next_state && ring->reward &&
+                 ring->not_done && a.ptr_size && a.workspace, "%s: null pointer", who);
   MobodyMlpLayout La;
   int rc = mobody_mlp_layout(S, A, 1, &La);
   if (rc) return rc;
   RolloutWs w;
-  rollout_carve(S, A, B, workspace, w);
+  rollout_carve(S, A, B, a.workspace, w);
   hipStream_t st = as_stream(stream);
   // the appends' arrival ticket (first words of the scan region) has to start at zero; every append leaves it at zero
-  if (hipMemsetAsync(w.scan, 0, 8 * sizeof(int32_t), st) != hipSuccess) return fail(MOBODY_E_LAUNCH, "mobody_rollout: memset failed");
-  const float* obs = init_obs;
-  for (int t = 0; t < H; ++t) {
+  if (hipMemsetAsync(w.scan, 0, 8 * sizeof(int32_t), st) != hipSuccess) return fail(MOBODY_E_LAUNCH, "%s: memset failed", who);
+  const float* obs = a.init_obs;
+  for (int t = 0; t < a.H; ++t) {
     float* nxt = w.obs[t & 1];
     // a = pi(s)  (select_action, mobody.py:612)
     Mlp3FwdArgs p{};
     p.src[0] = obs; p.ld[0] = S; p.n[0] = S;
-    p.w1 = actor_blob + La.w1; p.b1 = actor_blob + La.b1; p.w2 = actor_blob + La.w2; p.b2 = actor_blob + La.b2;
-    p.w3 = actor_blob + La.w3; p.b3 = actor_blob + La.b3;
+    p.w1 = a.actor_blob + La.w1; p.b1 = a.actor_blob + La.b1; p.w2 = a.actor_blob + La.w2; p.b2 = a.actor_blob + La.b2;
+    p.w3 = a.actor_blob + La.w3; p.b3 = a.actor_blob + La.b3;
     p.sw1 = p.sb1 = p.sw2 = p.sb2 = p.sw3 = p.sb3 = La.member_floats;
     p.Kp1 = La.Kp1; p.Np3 = La.Np3; p.nout = A; p.rows = B; p.out = w.act; p.out_mstride = B * A; p.out_ld = A;
-    p.out_mode = 1; p.max_action = max_action;
+    p.out_mode = 1; p.max_action = a.max_action;
     if (precision == 0) {
       rc = launch_mlp3_fwd(p, 1, ACT_RELU, st);
     } else {
-      MB_REQUIRE(actor_blob_T, "mobody_rollout: the split-precision modes need the actor's T blob");
-      p.w2_planes = reinterpret_cast<const unsigned short*>(actor_blob_T + La.w2p);
+      MB_REQUIRE(a.actor_blob_T, "%s: the split-precision modes need the actor's T blob", who);
+      p.w2_planes = reinterpret_cast<const unsigned short*>(a.actor_blob_T + La.w2p);
       p.planes_ms = 2 * La.t_member_floats;
       rc = launch_mlp3_fwd_bf(p, 1, Mlp3FwdArgs{}, 0, ACT_RELU, precision, st);
     }
     if (rc) return rc;
     // one imagined transition for every row; rows that terminated earlier keep their index and are flagged (alive mask);
     // the penalty filter and the alive update are formed in the sample kernel
-    rc = dyn_step_impl(dyn_blob, dyn_planes, nullptr, nullptr, precision, S, A, task, obs, w.act, B, nullptr, nullptr, t == 0 ? nullptr : w.alive, elites, n_elites, seed,
-                       call0 + (uint32_t)t, nullptr, penalty_coef, use_penalty, use_trg, nxt, w.reward, w.terminal, w.penalty, nullptr, nullptr,
-                       w.dyn, w.keep, w.alive, env_filter, filter_bad_rollout, stream);
+    MobodyEnsStep s{};
+    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
+    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = obs; s.act = w.act; s.B = B;
+    s.alive = t == 0 ? nullptr : w.alive; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
+    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.penalty_coef = a.penalty_coef; s.use_penalty = a.use_penalty;
+    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    s.next_obs = nxt; s.reward = w.reward; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
+    rc = dyn_step_impl(who, s, w.keep, w.alive, a.env_filter, a.filter_bad_rollout, stream);
     if (rc) return rc;
-    rc = launch_ring_append(*ring, cap, (long long*)ptr_size, S, A, obs, w.act, nxt,
+    rc = launch_ring_append(*ring, a.cap, (long long*)a.ptr_size, S, A, obs, w.act, nxt,
                             w.reward, w.terminal, w.keep, B, w.scan, st);
     if (rc) return rc;
     obs = nxt;
   }
   return 0;
+}
+
+extern "C" int64_t mobody_ens_rollout_workspace(const MobodyEnsRollout* a) {
+  if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyEnsRollout) || a->B < 0)
+    return fail(MOBODY_E_ARG, "mobody_ens_rollout_workspace: null struct, wrong struct_bytes or B < 0");
+  return mobody_rollout_workspace(a->S, a->A, a->B);
+}
+
+extern "C" int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream) {
+  MB_REQUIRE(a != nullptr, "mobody_ens_rollout: null argument struct");
+  MB_REQUIRE(a->struct_bytes == (int32_t)sizeof(MobodyEnsRollout), "mobody_ens_rollout: struct_bytes %d != sizeof(MobodyEnsRollout) %d",
+             a->struct_bytes, (int)sizeof(MobodyEnsRollout));
+  return rollout_impl("mobody_ens_rollout", *a, stream);
+}
+
+extern "C" int mobody_rollout(const float* dyn_blob, const float* dyn_planes, const float* actor_blob, const float* actor_blob_T,
+                              int precision, int S, int A, int task, float max_action,
+                              const float* init_obs, int64_t B, int H, const int32_t* elites, int n_elites, uint32_t seed,
+                              uint32_t call0, float penalty_coef, int use_penalty, int use_trg, float env_filter,
+                              int filter_bad_rollout, const MobodyBufferView* ring, int64_t cap, int64_t* ptr_size, float* workspace,
+                              void* stream) {
+  MobodyEnsRollout a{};
+  a.dyn_blob = dyn_blob; a.dyn_planes = dyn_planes; a.actor_blob = actor_blob; a.actor_blob_T = actor_blob_T;
+  a.precision = precision; a.S = S; a.A = A; a.task = task; a.max_action = max_action; a.init_obs = init_obs; a.B = B; a.H = H;
+  a.elites = elites; a.n_elites = n_elites; a.seed = seed; a.call0 = call0; a.penalty_coef = penalty_coef;
+  a.use_penalty = use_penalty; a.use_trg = use_trg; a.uncertainty_mode = MOBODY_UNC_PAIRWISE; a.env_filter = env_filter;
+  a.filter_bad_rollout = filter_bad_rollout; a.ring = ring; a.cap = cap; a.ptr_size = ptr_size; a.workspace = workspace;
+  return rollout_impl("mobody_rollout", a, stream);
 }
 
 // ---- stand-alone predicate / rollout bookkeeping -------------------------------------------------

@@ -35,6 +35,15 @@ def prec_id(mfma):
     return mfma if isinstance(mfma, int) else _lib.PRECISIONS[mfma]
 
 
+def unc_id(mode):
+    """'pairwise-diff' | 'aleatoric' | 'ensemble_std' (or the integer id) -> MOBODY_UNC_* (mobody_dynamics.py:241-252)."""
+    if isinstance(mode, int):
+        return mode
+    if mode not in _lib.UNCERTAINTY_MODES:
+        raise ValueError(f"uncertainty_mode {mode!r}: expected one of {sorted(_lib.UNCERTAINTY_MODES)}")
+    return _lib.UNCERTAINTY_MODES[mode]
+
+
 def default_mfma():
     """MFMA mode when a config does not name one: exact fp32, unless MOBODY_MFMA says otherwise (how the whole parity
     suite is re-run in a split-precision mode: `MOBODY_MFMA=bf16x3 pytest -m gpu`)."""
@@ -84,10 +93,10 @@ def dyn_forward(blob, S, A, obs, act, use_trg=True, planes=None, precision=0):
 
 def dyn_step(blob, S, A, task_id, obs, act, noise=None, elite_idx=None, alive=None, elites=(0, 1, 2, 3, 4), seed=0,
              call=0, penalty_coef=0.0, use_penalty=True, use_trg=True, want_mean=False, workspace=None, out=None,
-             planes=None, precision=0, mopo=None, call_dev=None):
+             planes=None, precision=0, mopo=None, call_dev=None, uncertainty_mode=0):
     """Returns dict(next_obs[B,S], reward[B,1], terminal uint8[B,1], penalty[B,1], raw_reward[B,1], mean?).
-    mopo = (blob, blob_T) of the 7-member MLP za_src1..3: the MOPO ablation's step (mobody_mopo_step).
-    call_dev: device int64[1] added to `call` (graph replay)."""
+    mopo = (blob, blob_T) of the 7-member MLP za_src1..3: the MOPO ablation's step.
+    call_dev: device int64[1] added to `call` (graph replay).  uncertainty_mode: name or MOBODY_UNC_* id (mobody_ens_step)."""
     obs, act = _f32(obs), _f32(act)
     dev, B = obs.device, obs.shape[0]
     if noise is not None:
@@ -108,19 +117,12 @@ def dyn_step(blob, S, A, task_id, obs, act, noise=None, elite_idx=None, alive=No
     raw = o["raw_reward"] if "raw_reward" in o else torch.empty(B, 1, dtype=torch.float32, device=dev)
     mean = torch.empty(7, B, S, dtype=torch.float32, device=dev) if want_mean else None
     el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
-    if mopo is not None:
-        check(load().mobody_mopo_step(ptr(blob), ptr(planes), ptr(mopo[0]), ptr(mopo[1]), prec_id(precision), S, A, task_id, ptr(obs),
-                                      ptr(act), B, ptr(noise), ptr(elite_idx), ptr(alive), el, len(elites), seed, call,
-                                      float(penalty_coef), int(bool(use_penalty)), ptr(nxt), ptr(rew), ptr(term), ptr(pen), ptr(raw),
-                                      ptr(mean), ptr(workspace), cur_stream()), "mobody_mopo_step")
-        res = dict(next_obs=nxt, reward=rew, terminal=term, penalty=pen, raw_reward=raw)
-        if want_mean:
-            res["mean"] = mean
-        return res
-    check(load().mobody_dyn_step(ptr(blob), ptr(planes), prec_id(precision), S, A, task_id, ptr(obs), ptr(act), B, ptr(noise), ptr(elite_idx),
-                                 ptr(alive), el, len(elites), seed, call, ptr(call_dev), float(penalty_coef), int(bool(use_penalty)),
-                                 int(bool(use_trg)), ptr(nxt), ptr(rew), ptr(term), ptr(pen), ptr(raw), ptr(mean),
-                                 ptr(workspace), cur_stream()), "mobody_dyn_step")
+    mb, mbt = mopo if mopo is not None else (None, None)
+    a = _lib.MobodyEnsStep(C.sizeof(_lib.MobodyEnsStep), unc_id(uncertainty_mode), ptr(blob), ptr(planes), ptr(mb), ptr(mbt),
+                           prec_id(precision), S, A, task_id, ptr(obs), ptr(act), B, ptr(noise), ptr(elite_idx), ptr(alive),
+                           el, len(elites), seed, call, int(bool(use_penalty)), ptr(call_dev), float(penalty_coef),
+                           int(bool(use_trg)), ptr(nxt), ptr(rew), ptr(term), ptr(pen), ptr(raw), ptr(mean), ptr(workspace))
+    check(load().mobody_ens_step(C.byref(a), cur_stream()), "mobody_ens_step")
     res = dict(next_obs=nxt, reward=rew, terminal=term, penalty=pen, raw_reward=raw)
     if want_mean:
         res["mean"] = mean
@@ -557,16 +559,24 @@ def dyn_validate(blob, S, A, obs, act, next_obs, rew, use_trg, ws=None):
 
 def rollout(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, elites, seed, call0, penalty_coef, use_penalty,
             use_trg, env_filter, filter_bad_rollout, buf, cap, ptr_size, ws=None, dyn_planes=None, actor_blob_T=None,
-            precision=0):
-    """H-step on-device rollout of `init_obs` appended to the ring `buf` (mobody_rollout).  Returns the workspace."""
+            precision=0, mopo=None, uncertainty_mode=0, call_dev=None):
+    """H-step on-device rollout of `init_obs` appended to the ring `buf` (mobody_ens_rollout).  mopo = (blob, blob_T) of the
+    MOPO ablation's MLP; uncertainty_mode: name or MOBODY_UNC_* id.  Returns the workspace."""
+    init_obs = _f32(init_obs)
     B = init_obs.shape[0]
-    need = load().mobody_rollout_workspace(S, A, B)
+    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
+    view = buffer_view(buf)
+    mb, mbt = mopo if mopo is not None else (None, None)
+    a = _lib.MobodyEnsRollout(C.sizeof(_lib.MobodyEnsRollout), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
+                              ptr(mbt), ptr(actor_blob), ptr(actor_blob_T), prec_id(precision), S, A, task_id, ptr(init_obs), B,
+                              int(H), len(elites), el, seed, call0, ptr(call_dev), float(max_action), float(penalty_coef),
+                              float(env_filter), int(bool(use_penalty)), int(bool(use_trg)), int(bool(filter_bad_rollout)),
+                              C.pointer(view), cap, ptr(ptr_size), None)
+    need = load().mobody_ens_rollout_workspace(C.byref(a))
+    if need < 0:
+        raise _lib.MobodyError("mobody_ens_rollout_workspace: " + load().mobody_last_error().decode())
     if ws is None or ws.numel() < need:
         ws = torch.empty(max(need, 1), dtype=torch.float32, device=init_obs.device)
-    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
-    check(load().mobody_rollout(ptr(dyn_blob), ptr(dyn_planes), ptr(actor_blob), ptr(actor_blob_T), prec_id(precision), S, A,
-                                task_id, float(max_action), ptr(_f32(init_obs)), B, int(H),
-                                el, len(elites), seed, call0, float(penalty_coef), int(bool(use_penalty)), int(bool(use_trg)),
-                                float(env_filter), int(bool(filter_bad_rollout)), C.byref(buffer_view(buf)), cap, ptr(ptr_size),
-                                ptr(ws), cur_stream()), "mobody_rollout")
+    a.workspace = ptr(ws)
+    check(load().mobody_ens_rollout(C.byref(a), cur_stream()), "mobody_ens_rollout")
     return ws

@@ -346,7 +346,9 @@ def _run(args, rank, world, device):
     model = MOBODYModule(obs_dim=state_dim, action_dim=action_dim, hidden_dims=256, num_ensemble=7, num_elites=5,
                          weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=device,
                          reward_relu=args.relu_reward, config=config)
+    # no CLI flag (the reference's driver never passes one, train_mobody.py:805-812): an optional key of the merged config
     dynamics = MOBODYEnsembleDynamics(config, model, None, None, terminal_fn, penalty_coef=env_penalty_coef,
+                                      uncertainty_mode=config.get("uncertainty_mode", "pairwise-diff"),
                                       rng=args.rng, seed=args.seed + 3)
     outdir = f"{args.dir}/{args.policy}/{args.env}-srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}/r{args.seed}{args.out_dir_remark}"
     writer = None
