@@ -129,15 +129,14 @@ __global__ __launch_bounds__(256) void k_dara_penalty(const float* z_sas, const 
 }
 
 // ---- generic MLP gradient (dz3 + saved activations -> gradient blob) ----
-struct BwdWs { float *dz2, *dz1, *dbp, *slabs; long long slab_stride, total; int nsplit, ntiles, tile_rows; };
+struct BwdWs { float *dz2, *dz1, *dbp, *slabs; long long slab_stride, total; int nsplit, ntiles; };
 
 static void carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, BwdWs& w) {
   long long off = 0;
   auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
   w.dz2 = take((long long)L.members * rows * HID);
   w.dz1 = take((long long)L.members * rows * HID);
-  w.tile_rows = pick_tile_rows(rows, L.members);
-  w.ntiles = (int)cdiv(rows, w.tile_rows);
+  w.ntiles = (int)cdiv(rows, MLP_TILE_ROWS);
   w.nsplit = wgrad_nsplit(rows, L.members);
   w.dbp = take((long long)w.ntiles * L.members * (2 * HID + L.Np3));
   w.slab_stride = (L.total_floats + 3) & ~3LL;
@@ -171,7 +170,7 @@ extern "C" int mobody_mlp3_backward(const float* blob_T, int in_dim, int out_dim
   b.dz3 = dz3; b.h1 = h1; b.h2 = h2; b.wt = blob_T; b.t_mstride = L.t_member_floats;
   b.w3t = L.w3t; b.w2t = L.w2t; b.w1t = L.w1t; b.Np3 = L.Np3; b.Np1t = L.Np1t; b.rows = rows;
   b.dz2 = w.dz2; b.dz1 = w.dz1; b.dbp = w.dbp;
-  rc = launch_mlp3_bwd(b, members, false, w.tile_rows, st);
+  rc = launch_mlp3_bwd(b, members, false, st);
   if (rc) return rc;
   WgradArgs g{};
   g.rows = rows; g.slabs = w.slabs; g.slab_stride = w.slab_stride; g.out_mstride = L.member_floats;

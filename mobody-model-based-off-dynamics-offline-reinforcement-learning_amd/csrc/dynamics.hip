@@ -326,19 +326,17 @@ static int launch_dyn_fwd_nt(const DynFwdArgs& a, int nt3, hipStream_t st) {
 static int launch_dyn_fwd(const float* blob, const MobodyDynLayout& L, const float* obs, const float* act, long long B,
                           int use_trg, float* mean, const float* planes, int prec, hipStream_t st) {
   DynFwdArgs a{blob, L, obs, act, mean, B, use_trg, reinterpret_cast<const unsigned short*>(planes)};
-  // 64-row tiles for fp32: the nine-layer chain has a wave-local narrow section in which a 32-row tile idles half of
-  // the waves (measured 102 vs 88 TFLOP/s at 50 000 rows); MOBODY_DYN_TILE_ROWS=32 selects the short tile.
-  static const int forced = tune_int("MOBODY_DYN_TILE_ROWS", 0);
+  // 64-row tiles (MT = 2) for fp32: the nine-layer chain has a wave-local narrow section in which a 32-row tile idles
+  // half of the waves (measured 102 vs 88 TFLOP/s at 50 000 rows).
   const int np = L.layer[MOBODY_DL_TR3].Np;
   const int nt3 = np == 16 ? 1 : np == 32 ? 2 : np == 48 ? 3 : np == 112 ? 7 : 0;      // walker/hopper/cheetah, pen, ant heads; else generic
-  if (prec == 0) return forced == 32 ? launch_dyn_fwd_nt<1, 0>(a, nt3, st) : launch_dyn_fwd_nt<2, 0>(a, nt3, st);
+  if (prec == 0) return launch_dyn_fwd_nt<2, 0>(a, nt3, st);
   // split-precision modes: the planes of a 64-row tile are 32 / 64 / 96 KB for 1 / 2 / 3 terms -> the three-term mode
-  // runs 32-row tiles (48 KB, three workgroups per CU)
-  const bool tall = forced == 64 || (forced != 32 && prec != 3);
-  if (prec == 1) return tall ? launch_dyn_fwd_nt<2, 1>(a, nt3, st) : launch_dyn_fwd_nt<1, 1>(a, nt3, st);
-  if (prec == 2) return tall ? launch_dyn_fwd_nt<2, 2>(a, nt3, st) : launch_dyn_fwd_nt<1, 2>(a, nt3, st);
-  if (prec == 4) return tall ? launch_dyn_fwd_nt<2, 4>(a, nt3, st) : launch_dyn_fwd_nt<1, 4>(a, nt3, st);
-  return tall ? launch_dyn_fwd_nt<2, 3>(a, nt3, st) : launch_dyn_fwd_nt<1, 3>(a, nt3, st);
+  // runs 32-row tiles (MT = 1: 48 KB, three workgroups per CU), the others 64-row tiles
+  if (prec == 1) return launch_dyn_fwd_nt<2, 1>(a, nt3, st);
+  if (prec == 2) return launch_dyn_fwd_nt<2, 2>(a, nt3, st);
+  if (prec == 4) return launch_dyn_fwd_nt<2, 4>(a, nt3, st);
+  return launch_dyn_fwd_nt<1, 3>(a, nt3, st);
 }
 
 // zs2 / transition2 / reward_model2 of every member -> their three bf16 planes (precision 0-3) or two fp16 planes of

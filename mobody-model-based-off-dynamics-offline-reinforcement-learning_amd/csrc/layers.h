@@ -20,7 +20,7 @@ namespace mobody {
 // `mask` (optional): this tile's [groups][256] words, `mask_groups` of them real; bit r of word (g, col) =
 // [y(row 32 g + r, col) > 0].  The backward
 // pass of a ReLU net needs only these signs, 32 B per row instead of the 1 KB activation row.
-template <int ACT, int MT = 2, class Extra, class Between>
+template <int ACT, int MT, class Extra, class Between>
 __device__ __forceinline__ void wide_layer(float* Xs, const float* __restrict__ W, const float* __restrict__ b, int Kp,
                                            WideRing& ring, Extra&& extra, Between&& between, uint32_t* mask = nullptr,
                                            bool full = false, int mask_groups = 1 << 30) {
@@ -60,14 +60,13 @@ __device__ __forceinline__ void wide_layer(float* Xs, const float* __restrict__ 
           word |= (uint32_t)(activate<ACT>(acc[mt][nt][r] + bias) > 0.f) << ((r & 3) + 8 * (r >> 2) + 4 * hh);
         word |= (uint32_t)__shfl_xor((int)word, 32);        // the other lane half holds the other 16 rows
         // 32-row groups past the end of the batch have no words (a taller tile's last groups would land in the next member)
-        const int grp = MT * wave_rg() + mt;
-        if (hh == 0 && grp < mask_groups) mask[grp * HID + 64 * wave_col() + 32 * nt + i] = word;
+        if (hh == 0 && mt < mask_groups) mask[mt * HID + 64 * wave_col() + 32 * nt + i] = word;
       }
   }
   lds_barrier();
 }
 
-template <int ACT, int MT = 2, class Extra>
+template <int ACT, int MT, class Extra>
 __device__ __forceinline__ void wide_layer(float* Xs, const float* __restrict__ W, const float* __restrict__ b, int Kp,
                                            Extra&& extra) {
   WideRing ring;
@@ -143,14 +142,59 @@ int launch_mlp3_fwd_pair(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs&
 // split-precision forward (mlp_fwd_bf.hip): prec 1 bf16 / 2 bf16x2 / 3 bf16x3; needs a.w2_planes (and b.w2_planes)
 int launch_mlp3_fwd_bf(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st);
 
-// Row-tile height of the fused MLP kernels.  Measured on MI355X (bench.py, S=17/A=6): 32-row tiles (33 KB LDS,
-// ~124 VGPRs -> 4 workgroups = 16 waves per CU) beat 64-row tiles (2 workgroups per CU) at every batch size from
-// 2.5 k to 41 k rows (forward 84 vs 73 TFLOP/s at 41 k rows, 60 vs 51 at 10 k): occupancy hides the weight-fetch
-// latency better than the 2x weight reuse of the taller tile.  MOBODY_TILE_ROWS=64 selects the tall tile (tuning aid).
-inline int pick_tile_rows(long long rows, int members) {
-  static const int forced = tune_int("MOBODY_TILE_ROWS", 0);
-  (void)rows; (void)members;
-  return forced == 64 ? 64 : 32;
+// Row-tile height of the fused 3-layer MLP kernels (forward and backward; the callers size the bias partials and the sign
+// words by it).  Measured on MI355X (bench.py, S=17/A=6): 32-row tiles (33 KB LDS, ~124 VGPRs -> 4 workgroups = 16 waves
+// per CU) beat 64-row tiles (2 workgroups per CU) at every batch size from 2.5 k to 41 k rows (forward 84 vs 73 TFLOP/s at
+// 41 k rows, 60 vs 51 at 10 k): occupancy hides the weight-fetch latency better than the 2x weight reuse of the taller tile.
+constexpr int MLP_TILE_ROWS = 32;
+constexpr int MLP_MT = MLP_TILE_ROWS / 32;       // 32 x 32 MFMA row tiles per wave (the MT of the tile helpers)
+
+// ---- pieces the fp32 and the split-precision forward tiles share (mlp_fwd.hip, mlp_fwd_bf.hip) ----
+// Input tile of member m: concat(src0, src1, src2) into columns [0, return value); the caller zero-pads up to Kp1.
+__device__ __forceinline__ int fwd_load_sources(const Mlp3FwdArgs& a, int m, float* Xs, long long row0, int rows_here) {
+  int c0 = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (a.n[k] > 0) {
+      tile_load(Xs, c0, a.src[k] + m * a.src_ms[k] + row0 * a.ld[k], a.ld[k], a.n[k], 0, rows_here, MLP_TILE_ROWS);
+      c0 += a.n[k];
+    }
+  }
+  return c0;
+}
+
+// Optional copy of the padded input tile for the weight gradients: same thread <-> element map as tile_load (no division).
+__device__ __forceinline__ void fwd_save_x(const Mlp3FwdArgs& a, int m, const float* Xs, long long row0, int rows_here) {
+  if (a.save_x != nullptr && (m == 0 || a.x_ms != 0)) {
+    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    float* sx = a.save_x + m * a.x_ms;
+    for (int col = c; col < a.Kp1; col += 32)
+      for (int r = r0; r < rows_here; r += NTHREADS >> 5) sx[(row0 + r) * a.Kp1 + col] = Xs[r * LDX + col];
+  }
+}
+
+// This tile's slices of the optional activation copies and sign words, and of the output.
+struct FwdTileOut { float *h1, *h2; uint32_t *mask1, *mask2; float* out; };
+__device__ __forceinline__ FwdTileOut fwd_tile_out(const Mlp3FwdArgs& a, int m, long long row0) {
+  FwdTileOut t;
+  t.h1 = a.save_h1 ? a.save_h1 + ((long long)m * a.rows + row0) * HID : nullptr;
+  t.h2 = a.save_h2 ? a.save_h2 + ((long long)m * a.rows + row0) * HID : nullptr;
+  const long long mtile = ((long long)m * ((a.rows + 31) / 32) + row0 / 32) * HID;      // this tile's first mask word
+  t.mask1 = a.mask1 ? a.mask1 + mtile : nullptr;
+  t.mask2 = a.mask2 ? a.mask2 + mtile : nullptr;
+  t.out = a.out + m * a.out_mstride + row0 * a.out_ld;
+  return t;
+}
+
+// One element of the output layer: bias, tanh * max_action, residual, guarded store.
+__device__ __forceinline__ void fwd_emit(const Mlp3FwdArgs& a, float* out, long long row0, int rows_here, int row, int col,
+                                         float v, float bias) {
+  if (row < rows_here && col < a.nout) {
+    float y = v + bias;
+    if (a.out_mode == 1) y = a.max_action * tanhf(y);
+    if (a.resid != nullptr) y += a.resid[(row0 + row) * a.resid_ld + col];
+    out[row * a.out_ld + col] = y;
+  }
 }
 
 }  // namespace mobody

@@ -22,8 +22,7 @@ __device__ __forceinline__ void relu_mask_words(f32x16 (&y)[MT][2], uint32_t* ma
       for (int r = 0; r < 16; ++r)                      // y is a ReLU output (>= +0, never -0): y > 0 <=> its bit pattern is non-zero --
         word |= min(__float_as_uint(y[mt][nt][r]), 1u) << ((r & 3) + 8 * (r >> 2) + 4 * hh);   // v_min_u32 + v_lshl_or instead of cmp + cndmask + lshl_or
       word |= (uint32_t)__shfl_xor((int)word, 32);
-      const int grp = MT * wave_rg() + mt;
-      if (hh == 0 && grp < mask_groups) mask[grp * HID + 64 * wave_col() + 32 * nt + i] = word;
+      if (hh == 0 && mt < mask_groups) mask[mt * HID + 64 * wave_col() + 32 * nt + i] = word;
     }
 }
 
@@ -38,21 +37,15 @@ struct PlaneSave {
 };
 
 // Row-major fp32 copy of a wide result held in accumulators to global memory (tile base dst, leading dimension 256): 32
-// coalesced dword stores per lane as ONE branch-free burst when the tile is full; the per-element row guard (v_cmp + exec
-// save / restore around every store) only on the batch's last, ragged tile.
-#ifndef ROWS_BUFFER_STORES
-#define ROWS_BUFFER_STORES 1
-#endif
+// coalesced dword stores per lane as ONE branch-free burst, full tile or ragged.
 template <int MT>
-__device__ __forceinline__ void wide_store_rows(f32x16 (&acc)[MT][2], float* dst, bool full, int rows_here) {
-#if ROWS_BUFFER_STORES
+__device__ __forceinline__ void wide_store_rows(f32x16 (&acc)[MT][2], float* dst, int rows_here) {
   // through a descriptor over the tile's REAL rows: a row past the end of the batch is out of range and the hardware drops
   // its store (one code path for full and ragged tiles), and an address is one per-lane offset + a scalar row offset -- no
   // 64-bit vector add per store (row offsets reach 31 KB, beyond the instruction's immediate field)
-  (void)full;
   const int lane = lane_id();
   const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(dst, (unsigned)min(rows_here, 1024) * (unsigned)(HID * 4));   // (tiles hold <= 64 rows)
-  const int voff = ((32 * MT * wave_rg() + 4 * (lane >> 5)) * HID + 64 * wave_col() + (lane & 31)) * 4;
+  const int voff = (4 * (lane >> 5) * HID + 64 * wave_col() + (lane & 31)) * 4;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -61,10 +54,6 @@ __device__ __forceinline__ void wide_store_rows(f32x16 (&acc)[MT][2], float* dst
       for (int r = 0; r < 16; ++r)
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[mt][nt][r]), rs, voff,
                                               ((32 * mt + (r & 3) + 8 * (r >> 2)) * HID + 32 * nt) * 4, 0);
-#else
-  if (full) wide_foreach<MT>(acc, [&](int row, int col, float y) { dst[row * HID + col] = y; });
-  else wide_foreach<MT>(acc, [&](int row, int col, float y) { if (row < rows_here) dst[row * HID + col] = y; });
-#endif
 }
 
 // Write the planes of a wide result held in accumulators (values y, scaled by 2^e in the f16 mode): four consecutive rows
@@ -89,7 +78,7 @@ __device__ __forceinline__ void planes_from_acc(f32x16 (&acc)[MT][2], char* Ps, 
           float y4[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) y4[j] = ys[4 * g + j];
-          planes_store4<PM, TB>(Ps, col, 8 * (MT * wave_rg() + mt) + 2 * g + h, y4, (MT * wave_rg() + mt) < groups ? gbase : nullptr,
+          planes_store4<PM, TB>(Ps, col, 8 * mt + 2 * g + h, y4, mt < groups ? gbase : nullptr,
                                 gs.plane_stride);
         }
       }
@@ -132,7 +121,7 @@ __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* 
           dv[mt][nt][r] = sig * (1.f + z * (1.f - sig));
           if constexpr (Split<PM>::F16) mx = fmaxf(mx, fabsf(y));
         }
-    wide_store_rows<MT>(dv, dsave, full, rows_here);
+    wide_store_rows<MT>(dv, dsave, rows_here);
   } else {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -156,14 +145,14 @@ __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* 
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (32 * (MT * wave_rg() + mt) + (r & 3) + 8 * (r >> 2) + 4 * (lane_id() >> 5) >= rows_here) acc[mt][nt][r] = 0.f;
+          if (32 * mt + (r & 3) + 8 * (r >> 2) + 4 * (lane_id() >> 5) >= rows_here) acc[mt][nt][r] = 0.f;
   }
   if constexpr (Split<PM>::F16) f16_tile_max_put(finite_tile_max<MT>(acc, mx), scr);
   lds_barrier();                                   // every wave has read the old image (and posted its maximum)
   int e = 0;
   if constexpr (Split<PM>::F16) e = f16_scale_exp(f16_tile_max_get(scr));
   planes_from_acc<MT, PM, TB>(acc, Ps, e, gs, (min(rows_here, TB) + 31) / 32);
-  if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, full, rows_here);
+  if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, rows_here);
   TR(7);
   if (mask != nullptr) relu_mask_words<MT>(acc, mask, mask_groups);
   lds_barrier();
@@ -174,8 +163,8 @@ __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* 
 template <int ACT, int MT, int PM, int TB, bool DS = false, class Between>
 __device__ __forceinline__ void bf_layer(float* Xs, const char* Ps, int e_in, const s16x8* __restrict__ Wb,
                                          const float* __restrict__ b, BfRing<PM>& ring, Between&& between,
-                                         uint32_t* mask = nullptr, bool full = true, int mask_groups = 0,
-                                         int rows_here = 1 << 30, float* gsave = nullptr, float* dsave = nullptr) {
+                                         uint32_t* mask = nullptr, int mask_groups = 0, int rows_here = 1 << 30,
+                                         float* gsave = nullptr, float* dsave = nullptr) {
   const float bias0 = b[64 * wave_col() + (lane_id() & 31)], bias1 = b[64 * wave_col() + 32 + (lane_id() & 31)];
   f32x16 acc[MT][2];
   wide_zero<MT>(acc);
@@ -197,7 +186,7 @@ __device__ __forceinline__ void bf_layer(float* Xs, const char* Ps, int e_in, co
           acc[mt][nt][r] = z * sig;
           dv[mt][nt][r] = sig * (1.f + z * (1.f - sig));
         }
-    wide_store_rows<MT>(dv, dsave, full, rows_here);
+    wide_store_rows<MT>(dv, dsave, rows_here);
   } else {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -213,7 +202,7 @@ __device__ __forceinline__ void bf_layer(float* Xs, const char* Ps, int e_in, co
   }
   lds_barrier();                                   // every wave has read the planes
   wide_foreach<MT>(acc, [&](int row, int col, float y) { Xs[row * LDX + col] = y; });
-  if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, full, rows_here);
+  if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, rows_here);
   if (mask != nullptr) relu_mask_words<MT>(acc, mask, mask_groups);
   lds_barrier();
 }

@@ -21,10 +21,6 @@
 #include "layers_bf.h"
 #include "train.h"
 
-#ifndef BWD_MASK_PREFETCH
-#define BWD_MASK_PREFETCH 1     // 0: fetch a layer's mask operand inside its epilogue (A/B aid)
-#endif
-
 namespace mobody {
 
 // Masked epilogue of a backward wide layer, in two parts around the barrier that separates the GEMM's LDS reads from the
@@ -145,7 +141,7 @@ __device__ __forceinline__ void wide_store_colsum(f32x16 (&acc)[MT][2], float* X
         if constexpr (PM == 0) Xs[(32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hh) * LDX + 64 * w + 32 * nt + i] = dz;
         cs[nt] += dz;
       }
-  if (gdst != nullptr) wide_store_rows<MT>(acc, gdst, rows_here == 32 * MT, rows_here);      // one branch-free burst on full tiles
+  if (gdst != nullptr) wide_store_rows<MT>(acc, gdst, rows_here);
   cs[0] += __shfl_xor(cs[0], 32);
   cs[1] += __shfl_xor(cs[1], 32);
 }
@@ -229,15 +225,15 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
 // or 0 = any Np1t through the row-split path.
 // MASK: see wide_mask_apply (1: sign words m1, m2; 0: saved activations h1, h2; 2: Swish derivatives in h1, h2).
 // PM: 0 = exact fp32 MFMA; 1..4 = the 256 x 256 GEMM (dz2 W2^T) on the split-precision core, streaming W2^T's planes.
-template <bool DX, int MT, int NT, int MASK, int PM = 0>
+template <bool DX, int NT, int MASK, int PM = 0>
 // (three workgroups per CU only for the sign-word variants: the variants that hold 32 mask / derivative values per lane next to
 //  the accumulators spilled ~26 VGPRs at the 168-register budget; they serve the small generic launches -- V function, DARA
 //  classifier, dynamics pre-training -- where a third resident workgroup buys nothing)
-__global__ __launch_bounds__(NTHREADS, (MT == 1 && MASK == 1) ? 3 : 2) void k_mlp3_bwd(Mlp3BwdArgs a) {
+__global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3BwdArgs a) {
   constexpr bool BITS = MASK == 1;
   __shared__ float red[8];
   extern __shared__ __attribute__((aligned(16))) float Xs[];
-  constexpr int TB = 32 * MT;
+  constexpr int TB = MLP_TILE_ROWS, MT = MLP_MT;
   constexpr int PMX = PM > 0 ? PM : 1;
   const int m = blockIdx.y;
   const long long row0 = (long long)blockIdx.x * TB;
@@ -258,10 +254,8 @@ __global__ __launch_bounds__(NTHREADS, (MT == 1 && MASK == 1) ? 3 : 2) void k_ml
 
   TR(0);
   MaskPre<MT, MASK> mk1, mk2;                       // layer 2's operand now; layer 1's too when it is two words, else before its GEMM
-  if (BWD_MASK_PREFETCH) {
-    mask_fetch<MT, MASK>(mk2, h2, m2, rows_here);
-    if constexpr (BITS) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here);
-  }
+  mask_fetch<MT, MASK>(mk2, h2, m2, rows_here);
+  if constexpr (BITS) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here);
   // (split modes: the ring only serves the K = Np3 GEMM, two to four chunks -- three stages keep the kernel at 128 registers)
   WideRingT<(PM > 0 ? 3 : WIDE_RING)> ring;
   wide_prefetch(w3t, a.Np3, ring);                // weight fragments travel while the seed rows are fetched
@@ -287,7 +281,6 @@ __global__ __launch_bounds__(NTHREADS, (MT == 1 && MASK == 1) ? 3 : 2) void k_ml
   else wide_prefetch(w2t, HID, ring);             // next layer's first fragments overlap the mask epilogue
   int e2 = 0;
   {
-    if (!BWD_MASK_PREFETCH) mask_fetch<MT, MASK>(mk2, h2, m2, rows_here);
     const float mx = wide_mask_apply<MT, MASK>(acc, mk2, rows_here, 1.f);
     if constexpr (PM == 4) f16_tile_max_put(mx, scr);
   }
@@ -304,14 +297,13 @@ __global__ __launch_bounds__(NTHREADS, (MT == 1 && MASK == 1) ? 3 : 2) void k_ml
   lds_barrier();
   TR(3);
   // dh1 = dz2 * W2^T ; dz1 = dh1 * [h1 > 0]
-  if constexpr (!BITS) { if (BWD_MASK_PREFETCH) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here); }
+  if constexpr (!BITS) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here);
   wide_zero<MT>(acc);
   if constexpr (PM > 0) bf_gemm<MT, PMX, TB>(reinterpret_cast<const char*>(Xs), w2tp, acc, bring);
   else wide_gemm<MT>(Xs, w2t, HID, acc, ring);
   TR(4);
   NarrowRegs<(NT > 0 ? NT : 1)> br;
   if constexpr (DX && NT > 0) narrow_prefetch<NT>(w1t, 16 * NT, br);
-  if (!BWD_MASK_PREFETCH) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here);
   wide_mask_apply<MT, MASK>(acc, mk1, rows_here, PM == 4 ? exp2i(-(e2 + F16_WSHIFT)) : 1.f);
   lds_barrier();
   wide_store_colsum<MT, 0>(acc, Xs, dz1, rows_here, 0, cs);
@@ -330,69 +322,61 @@ __global__ __launch_bounds__(NTHREADS, (MT == 1 && MASK == 1) ? 3 : 2) void k_ml
   TR(6);
 }
 
-template <bool DX, int MT, int NT, int BITS, int NPL = 0>
+template <bool DX, int NT, int BITS, int NPL = 0>
 static int launch_bwd_t(const Mlp3BwdArgs& a, int members, hipStream_t st) {
-  constexpr size_t lds = split_lds_bytes<(NPL > 0 ? NPL : 1), 32 * MT>();
+  constexpr size_t lds = split_lds_bytes<(NPL > 0 ? NPL : 1), MLP_TILE_ROWS>();
   static bool once = false;
   if (!once) {
-    int rc = allow_big_lds(k_mlp3_bwd<DX, MT, NT, BITS, NPL>, lds);
+    int rc = allow_big_lds(k_mlp3_bwd<DX, NT, BITS, NPL>, lds);
     if (rc) return rc;
     once = true;
   }
-  dim3 grid((unsigned)cdiv(a.rows, 32 * MT), (unsigned)members);
+  dim3 grid((unsigned)cdiv(a.rows, MLP_TILE_ROWS), (unsigned)members);
   ProfScope prof(PROF_MLP_BWD, st);
-  hipLaunchKernelGGL((k_mlp3_bwd<DX, MT, NT, BITS, NPL>), grid, dim3(NTHREADS), lds, st, a);
+  hipLaunchKernelGGL((k_mlp3_bwd<DX, NT, BITS, NPL>), grid, dim3(NTHREADS), lds, st, a);
   MB_LAUNCH_OK("k_mlp3_bwd");
   return 0;
 }
 
-// split-precision backward: sign-word masks, 32-row tiles (the train step's three backward launches)
+// split-precision backward: sign-word masks (the train step's three backward launches)
 template <int NPL>
 static int launch_bwd_bf(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (!with_dx) return launch_bwd_t<false, 1, 0, 1, NPL>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 1, 1, 1, NPL>(a, members, st) : nt == 2 ? launch_bwd_t<true, 1, 2, 1, NPL>(a, members, st)
-                                                                             : launch_bwd_t<true, 1, 0, 1, NPL>(a, members, st);
+  if (!with_dx) return launch_bwd_t<false, 0, 1, NPL>(a, members, st);
+  return nt == 1 ? launch_bwd_t<true, 1, 1, NPL>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 1, NPL>(a, members, st)
+                                                                             : launch_bwd_t<true, 0, 1, NPL>(a, members, st);
 }
 
-// tile_rows (32 or 64) must be the value the caller sized `dbp` / the bias reduction with
+// fp32 ReLU backward (the callers size `dbp` / the bias reduction by MLP_TILE_ROWS)
 template <int BITS>
-static int launch_bwd_masks(const Mlp3BwdArgs& a, int members, bool with_dx, int tile_rows, hipStream_t st) {
+static int launch_bwd_masks(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (tile_rows == 32) {
-    if (!with_dx) return launch_bwd_t<false, 1, 0, BITS>(a, members, st);
-    return nt == 1 ? launch_bwd_t<true, 1, 1, BITS>(a, members, st) : nt == 2 ? launch_bwd_t<true, 1, 2, BITS>(a, members, st)
-                                                                               : launch_bwd_t<true, 1, 0, BITS>(a, members, st);
-  }
-  if (!with_dx) return launch_bwd_t<false, 2, 0, BITS>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 2, 1, BITS>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2, BITS>(a, members, st)
-                                                                             : launch_bwd_t<true, 2, 0, BITS>(a, members, st);
+  if (!with_dx) return launch_bwd_t<false, 0, BITS>(a, members, st);
+  return nt == 1 ? launch_bwd_t<true, 1, BITS>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, BITS>(a, members, st)
+                                                                          : launch_bwd_t<true, 0, BITS>(a, members, st);
 }
 
-// Swish nets (the ensemble dynamics, pre-training): 32-row tiles only, derivative multipliers in h1 / h2
+// Swish nets (the ensemble dynamics, pre-training): derivative multipliers in h1 / h2
 static int launch_bwd_swish(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
   if (a.prec == 4 && a.w2t_planes != nullptr) {     // f16x2: the 256 x 256 GEMM on the split core, dz2 as planes for the weight gradients
-    if (!with_dx) return launch_bwd_t<false, 1, 0, 2, 4>(a, members, st);
-    return nt == 1 ? launch_bwd_t<true, 1, 1, 2, 4>(a, members, st) : nt == 2 ? launch_bwd_t<true, 1, 2, 2, 4>(a, members, st)
-                                                                             : launch_bwd_t<true, 1, 0, 2, 4>(a, members, st);
+    if (!with_dx) return launch_bwd_t<false, 0, 2, 4>(a, members, st);
+    return nt == 1 ? launch_bwd_t<true, 1, 2, 4>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2, 4>(a, members, st)
+                                                                             : launch_bwd_t<true, 0, 2, 4>(a, members, st);
   }
-  if (!with_dx) return launch_bwd_t<false, 1, 0, 2>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 1, 1, 2>(a, members, st) : nt == 2 ? launch_bwd_t<true, 1, 2, 2>(a, members, st)
-                                                                         : launch_bwd_t<true, 1, 0, 2>(a, members, st);
+  if (!with_dx) return launch_bwd_t<false, 0, 2>(a, members, st);
+  return nt == 1 ? launch_bwd_t<true, 1, 2>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2>(a, members, st)
+                                                                         : launch_bwd_t<true, 0, 2>(a, members, st);
 }
 
-int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, int tile_rows, hipStream_t st) {
+int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   if (a.rows <= 0) return 0;
-  if (a.swish) {
-    if (tile_rows != 32) return fail(MOBODY_E_ARG, "launch_mlp3_bwd: the Swish backward uses 32-row tiles");
-    return launch_bwd_swish(a, members, with_dx, st);
-  }
-  if (a.prec != 0 && a.w2t_planes != nullptr && a.m1 != nullptr && a.m2 != nullptr && tile_rows == 32)
+  if (a.swish) return launch_bwd_swish(a, members, with_dx, st);
+  if (a.prec != 0 && a.w2t_planes != nullptr && a.m1 != nullptr && a.m2 != nullptr)
     return a.prec == 1 ? launch_bwd_bf<1>(a, members, with_dx, st) : a.prec == 2 ? launch_bwd_bf<2>(a, members, with_dx, st)
          : a.prec == 3 ? launch_bwd_bf<3>(a, members, with_dx, st) : launch_bwd_bf<4>(a, members, with_dx, st);
-  return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_masks<1>(a, members, with_dx, tile_rows, st)
-                                            : launch_bwd_masks<0>(a, members, with_dx, tile_rows, st);
+  return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_masks<1>(a, members, with_dx, st)
+                                            : launch_bwd_masks<0>(a, members, with_dx, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -813,7 +797,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
   ProfScope prof(PROF_WGRAD, st);
   // Split-precision job 0 in every bf16 mode (the operand split costs ~6 VALU instructions per value and term; with the
   // unmasked scalar-addressed row loop that still leaves a gain: per step at c2 0.058 ms fp32 job -> 0.052 bf16x3,
-  // 0.044 bf16x2); MOBODY_WGRAD_BF=0 keeps the job in fp32 (tuning aid).
+  // 0.044 bf16x2).
   if (a.prec == 4 && a.eA != nullptr) {               // "f16x2": job 0 on the pre-split fp16 planes
     if (a.rows_per_wave > 2048) return fail(MOBODY_E_ARG, "launch_wgrad: more than 64 row tiles per wave slice (raise nsplit)");
     static bool once_h = false;
@@ -826,9 +810,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
     MB_LAUNCH_OK("k_wgrad_f16");
     return 0;
   }
-  static const int bf_force = tune_int("MOBODY_WGRAD_BF", -1);
-  const bool use_bf = bf_force == 0 ? false : a.prec != 0;
-  if (use_bf && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide) {
+  if (a.prec != 0 && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide) {
     static bool once_bf = false;
     if (!once_bf) {
       int rc = allow_big_lds(k_wgrad_bf<1>, lds);

@@ -1,4 +1,4 @@
-// Fused 3-layer MLP forward: one workgroup = one 32-row tile (64 with MOBODY_TILE_ROWS=64) x one member, all three
+// Fused 3-layer MLP forward: one workgroup = one 32-row tile (MLP_TILE_ROWS, layers.h) x one member, all three
 // GEMMs on fp32 MFMA with the activations resident in LDS (written to HBM only when the backward pass asks for
 // them: x / h1 / h2 for the weight gradients, 32 B/row of ReLU sign words for the masks).  k_mlp3_fwd2 runs two
 // independent networks in one launch.  Roofline: MFMA f32 (2*(Kp1+256+Np3)*256 FLOP per row against (in+out)*4
@@ -10,48 +10,40 @@
 
 namespace mobody {
 
+constexpr int TB = MLP_TILE_ROWS;               // rows of a workgroup's tile
+
 // Output layer of the forward (256 -> nout <= 16*NT) through the K-split narrow layer; NT = 0: generic row-split path.
-template <int ACT, int MT, int RG, int NT>
+template <int ACT, int NT>
 __device__ __forceinline__ void mlp3_fwd_tail(const Mlp3FwdArgs& a, int m, float* Xs, WideRing& ring, float* h2,
-                                              uint32_t* mask2, long long row0, int rows_here) {
-  constexpr int TB = 32 * MT * RG;
+                                              uint32_t* mask2, float* out, long long row0, int rows_here) {
   const float* w3 = a.w3 + m * a.sw3;
   const float* b3 = a.b3 + m * a.sb3;
-  float* out = a.out + m * a.out_mstride + row0 * a.out_ld;
   const bool full = rows_here == TB;
   auto save_h2 = [=](auto guarded, int row, int col, float y) {
     if (h2 != nullptr && (!decltype(guarded)::value || row < rows_here)) h2[row * HID + col] = y;
   };
-  auto emit = [&](int row, int col, float v, float bias) {
-    if (row < rows_here && col < a.nout) {
-      float y = v + bias;
-      if (a.out_mode == 1) y = a.max_action * tanhf(y);
-      if (a.resid != nullptr) y += a.resid[(row0 + row) * a.resid_ld + col];
-      out[row * a.out_ld + col] = y;
-    }
-  };
+  auto emit = [&](int row, int col, float v, float bias) { fwd_emit(a, out, row0, rows_here, row, col, v, bias); };
   if constexpr (NT > 0) {
     NarrowRegs<NT> br;
     // b3 of this thread's output columns: element e = threadIdx.x + 256 k has column e % (16 NT), the same for all k
     const int mycol = threadIdx.x % (16 * NT);
     float bias;
-    wide_layer<ACT, MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [&] {
+    wide_layer<ACT, MLP_MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [&] {
       narrow_prefetch<NT>(w3, 16 * NT, br);
       bias = b3[mycol < a.nout ? mycol : 0];
     }, mask2, full, (rows_here + 31) / 32);
     TR(4);
     narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
   } else {
-    wide_layer<ACT, MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [] {}, mask2, full, (rows_here + 31) / 32);
+    wide_layer<ACT, MLP_MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [] {}, mask2, full, (rows_here + 31) / 32);
     TR(4);
     narrow_layer(Xs, w3, HID, a.Np3, [&](int row, int col, float v) { emit(row, col, v, b3[col < a.nout ? col : 0]); }, TB);
   }
 }
 
 // NT: 16-column tiles of the output layer handled by the K-split narrow layer (Np3 == 16*NT), or 0 = any Np3.
-template <int ACT, int MT, int RG, int NT>
+template <int ACT, int NT>
 __device__ __forceinline__ void mlp3_fwd_tile(const Mlp3FwdArgs& a, int m, float* Xs) {
-  constexpr int TB = 32 * MT * RG;                // rows of this workgroup's tile
   const long long row0 = (long long)blockIdx.x * TB;
   const int rows_here = (int)min((long long)TB, a.rows - row0);
   const float* w1 = a.w1 + m * a.sw1;
@@ -59,45 +51,26 @@ __device__ __forceinline__ void mlp3_fwd_tile(const Mlp3FwdArgs& a, int m, float
   TR(0);
   WideRing ring;
   wide_prefetch(w1, a.Kp1, ring);                 // W1 fragments travel while the input tile is fetched
-
-  // ---- input tile: concat(src0, src1, src2), zero padded to Kp1 columns ----
-  int c0 = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (a.n[k] > 0) {
-      tile_load(Xs, c0, a.src[k] + m * a.src_ms[k] + row0 * a.ld[k], a.ld[k], a.n[k], 0, rows_here, TB);
-      c0 += a.n[k];
-    }
-  }
-  tile_zero_cols(Xs, c0, a.Kp1, TB);
+  tile_zero_cols(Xs, fwd_load_sources(a, m, Xs, row0, rows_here), a.Kp1, TB);
   lds_barrier();
   TR(1);
-  if (a.save_x != nullptr && (m == 0 || a.x_ms != 0)) {   // same thread <-> element map as tile_load (no division)
-    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-    float* sx = a.save_x + m * a.x_ms;
-    for (int col = c; col < a.Kp1; col += 32)
-      for (int r = r0; r < rows_here; r += (NTHREADS * RG) >> 5) sx[(row0 + r) * a.Kp1 + col] = Xs[r * LDX + col];
-  }
-
-  float* h1 = a.save_h1 ? a.save_h1 + ((long long)m * a.rows + row0) * HID : nullptr;
-  float* h2 = a.save_h2 ? a.save_h2 + ((long long)m * a.rows + row0) * HID : nullptr;
-  const long long mtile = ((long long)m * cdiv(a.rows, 32) + row0 / 32) * HID;      // this tile's first mask word
-  uint32_t* mask1 = a.mask1 ? a.mask1 + mtile : nullptr;
-  uint32_t* mask2 = a.mask2 ? a.mask2 + mtile : nullptr;
-  wide_layer<ACT, MT>(Xs, w1, a.b1 + m * a.sb1, a.Kp1, ring,
+  fwd_save_x(a, m, Xs, row0, rows_here);
+  const FwdTileOut t = fwd_tile_out(a, m, row0);
+  float* h1 = t.h1;
+  wide_layer<ACT, MLP_MT>(Xs, w1, a.b1 + m * a.sb1, a.Kp1, ring,
                       [=](auto guarded, int row, int col, float y) {
                         if (h1 != nullptr && (!decltype(guarded)::value || row < rows_here)) h1[row * HID + col] = y;
                       },
-                      [&] { wide_prefetch(w2, HID, ring); }, mask1, rows_here == TB, (rows_here + 31) / 32);
+                      [&] { wide_prefetch(w2, HID, ring); }, t.mask1, rows_here == TB, (rows_here + 31) / 32);
   TR(2);
-  mlp3_fwd_tail<ACT, MT, RG, NT>(a, m, Xs, ring, h2, mask2, row0, rows_here);
+  mlp3_fwd_tail<ACT, NT>(a, m, Xs, ring, t.h2, t.mask2, t.out, row0, rows_here);
   TR(5);
 }
 
-template <int ACT, int MT, int RG, int NT>
-__global__ __launch_bounds__(NTHREADS * RG, 2) void k_mlp3_fwd(Mlp3FwdArgs a) {
+template <int ACT, int NT>
+__global__ __launch_bounds__(NTHREADS, 2) void k_mlp3_fwd(Mlp3FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float Xs[];
-  mlp3_fwd_tile<ACT, MT, RG, NT>(a, blockIdx.y, Xs);
+  mlp3_fwd_tile<ACT, NT>(a, blockIdx.y, Xs);
 }
 
 // Two independent networks in ONE launch (blockIdx.y < members_a -> net a, else net b): Q(s,a) with pi(s') in the
@@ -105,44 +78,44 @@ __global__ __launch_bounds__(NTHREADS * RG, 2) void k_mlp3_fwd(Mlp3FwdArgs a) {
 // (1.25 per CU: half the chip idles through the second round); merged with the twin-Q launch the grid is ~3.5
 // workgroups per CU and one generation shorter.  The argument block is SELECTED (scalar selects), not branched on:
 // two inlined copies of the tile body in an if/else made hipcc keep both live (190 VGPRs, half the occupancy).
-template <int ACT, int MT, int NT>
+template <int ACT, int NT>
 __global__ __launch_bounds__(NTHREADS, 2) void k_mlp3_fwd2(Mlp3FwdArgs a, Mlp3FwdArgs b, int members_a) {
   extern __shared__ __attribute__((aligned(16))) float Xs[];
   const bool second = (int)blockIdx.y >= members_a;
   const Mlp3FwdArgs s = second ? b : a;
-  if ((long long)blockIdx.x * (32 * MT) >= s.rows) return;       // the two nets may differ in rows (grid.x = max)
-  mlp3_fwd_tile<ACT, MT, 1, NT>(s, second ? (int)blockIdx.y - members_a : (int)blockIdx.y, Xs);
+  if ((long long)blockIdx.x * TB >= s.rows) return;              // the two nets may differ in rows (grid.x = max)
+  mlp3_fwd_tile<ACT, NT>(s, second ? (int)blockIdx.y - members_a : (int)blockIdx.y, Xs);
 }
 
-template <int ACT, int MT, int RG, int NT>
+template <int ACT, int NT>
 static int launch_fwd_t(const Mlp3FwdArgs& a, int members, hipStream_t stream) {
-  size_t lds = (size_t)32 * MT * RG * LDX * sizeof(float);
+  size_t lds = (size_t)TB * LDX * sizeof(float);
   static bool once = false;
   if (!once) {
-    int rc = allow_big_lds(k_mlp3_fwd<ACT, MT, RG, NT>, 160 * 1024);
+    int rc = allow_big_lds(k_mlp3_fwd<ACT, NT>, 160 * 1024);
     if (rc) return rc;
     once = true;
   }
-  dim3 grid((unsigned)cdiv(a.rows, 32 * MT * RG), (unsigned)members);
+  dim3 grid((unsigned)cdiv(a.rows, TB), (unsigned)members);
   ProfScope prof(PROF_MLP_FWD, stream);
-  hipLaunchKernelGGL((k_mlp3_fwd<ACT, MT, RG, NT>), grid, dim3(NTHREADS * RG), lds, stream, a);
+  hipLaunchKernelGGL((k_mlp3_fwd<ACT, NT>), grid, dim3(NTHREADS), lds, stream, a);
   MB_LAUNCH_OK("k_mlp3_fwd");
   return 0;
 }
 
-template <int MT, int NT>
+template <int NT>
 static int launch_fwd2_t(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, hipStream_t stream) {
-  size_t lds = (size_t)32 * MT * LDX * sizeof(float);
+  size_t lds = (size_t)TB * LDX * sizeof(float);
   static bool once = false;
   if (!once) {
-    int rc = allow_big_lds(k_mlp3_fwd2<ACT_RELU, MT, NT>, 160 * 1024);
+    int rc = allow_big_lds(k_mlp3_fwd2<ACT_RELU, NT>, 160 * 1024);
     if (rc) return rc;
     once = true;
   }
   const long long rows = a.rows > b.rows ? a.rows : b.rows;
-  dim3 grid((unsigned)cdiv(rows, 32 * MT), (unsigned)(members_a + members_b));
+  dim3 grid((unsigned)cdiv(rows, TB), (unsigned)(members_a + members_b));
   ProfScope prof(PROF_MLP_FWD, stream);
-  hipLaunchKernelGGL((k_mlp3_fwd2<ACT_RELU, MT, NT>), grid, dim3(NTHREADS), lds, stream, a, b, members_a);
+  hipLaunchKernelGGL((k_mlp3_fwd2<ACT_RELU, NT>), grid, dim3(NTHREADS), lds, stream, a, b, members_a);
   MB_LAUNCH_OK("k_mlp3_fwd2");
   return 0;
 }
@@ -153,33 +126,22 @@ static int narrow_tiles(int Np3) { return Np3 == 16 ? 1 : Np3 == 32 ? 2 : 0; }
 int launch_mlp3_fwd_pair(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, hipStream_t stream) {
   if (a.rows <= 0) return launch_mlp3_fwd(b, members_b, ACT_RELU, stream);
   if (b.rows <= 0) return launch_mlp3_fwd(a, members_a, ACT_RELU, stream);
-  static const bool split = tune_int("MOBODY_NO_FWD_PAIR", 0) != 0;   // tuning aid (diagnostic build)
-  if (split || a.Np3 != b.Np3) {                  // the merged kernel is specialised on one output-layer width
+  if (a.Np3 != b.Np3) {                           // the merged kernel is specialised on one output-layer width
     int rc = launch_mlp3_fwd(a, members_a, ACT_RELU, stream);
     return rc ? rc : launch_mlp3_fwd(b, members_b, ACT_RELU, stream);
   }
-  const bool tall = pick_tile_rows(a.rows, members_a) == 64;
   const int nt = narrow_tiles(a.Np3);
-  if (tall) return nt == 1 ? launch_fwd2_t<2, 1>(a, members_a, b, members_b, stream)
-                 : nt == 2 ? launch_fwd2_t<2, 2>(a, members_a, b, members_b, stream)
-                           : launch_fwd2_t<2, 0>(a, members_a, b, members_b, stream);
-  return nt == 1 ? launch_fwd2_t<1, 1>(a, members_a, b, members_b, stream)
-       : nt == 2 ? launch_fwd2_t<1, 2>(a, members_a, b, members_b, stream)
-                 : launch_fwd2_t<1, 0>(a, members_a, b, members_b, stream);
+  return nt == 1 ? launch_fwd2_t<1>(a, members_a, b, members_b, stream)
+       : nt == 2 ? launch_fwd2_t<2>(a, members_a, b, members_b, stream)
+                 : launch_fwd2_t<0>(a, members_a, b, members_b, stream);
 }
 
 template <int ACT>
 static int launch_fwd_act(const Mlp3FwdArgs& a, int members, hipStream_t stream) {
-  static const int shape = tune_int("MOBODY_FWD_SHAPE", 0);   // tuning aid (diagnostic build)
-  if (shape == 8) return launch_fwd_t<ACT, 1, 2, 0>(a, members, stream);
-  const bool tall = pick_tile_rows(a.rows, members) == 64;
   const int nt = narrow_tiles(a.Np3);
-  if (tall) return nt == 1 ? launch_fwd_t<ACT, 2, 1, 1>(a, members, stream)
-                 : nt == 2 ? launch_fwd_t<ACT, 2, 1, 2>(a, members, stream)
-                           : launch_fwd_t<ACT, 2, 1, 0>(a, members, stream);
-  return nt == 1 ? launch_fwd_t<ACT, 1, 1, 1>(a, members, stream)
-       : nt == 2 ? launch_fwd_t<ACT, 1, 1, 2>(a, members, stream)
-                 : launch_fwd_t<ACT, 1, 1, 0>(a, members, stream);
+  return nt == 1 ? launch_fwd_t<ACT, 1>(a, members, stream)
+       : nt == 2 ? launch_fwd_t<ACT, 2>(a, members, stream)
+                 : launch_fwd_t<ACT, 0>(a, members, stream);
 }
 
 int launch_mlp3_fwd(const Mlp3FwdArgs& a, int members, int act, hipStream_t stream) {

@@ -734,10 +734,7 @@ static AdamTarget pre_adam_target(float* p, float* pT, float* m, float* v, int64
 // Adam step) feed nothing later in the step, while the main chain -- 13 dependent launches of 17 .. 224 workgroups that leave
 // most of the 256 CUs idle -- still has the next net's backward to run: the reward head's and the decoder's (~26 us each) go to
 // a library-owned second stream between two events and rejoin before the loss is finalised.  Under stream capture the event
-// pair pulls the side stream into the caller's graph as a parallel branch.  PRE_SIDE_STREAM=0 builds the single-stream order.
-#ifndef PRE_SIDE_STREAM
-#define PRE_SIDE_STREAM 1
-#endif
+// pair pulls the side stream into the caller's graph as a parallel branch.
 struct PreSide { hipStream_t s; hipEvent_t fork[3], join; };
 static int pre_side(PreSide** out) {
   static PreSide side[16];
@@ -826,14 +823,10 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   rc = forward(pre_fwd_args(Prw, L.rw, w.xrw, 2 * S + A, R2, w.rw_out, w.sx_rw, w.h1r, w.h2r, w.d1r, w.d2r, Trw, f16 ? w.eh1r : nullptr));
   if (rc) return rc;
   PreSide* side = nullptr;
-  hipStream_t st2 = st;                              // where the off-chain weight-gradient work goes
-  if (PRE_SIDE_STREAM) {
-    rc = pre_side(&side);
-    if (rc) return rc;
-    st2 = side->s;
-  }
+  rc = pre_side(&side);
+  if (rc) return rc;
+  hipStream_t st2 = side->s;                         // where the off-chain weight-gradient work goes
   auto fork = [&](int k) {                           // side stream: wait for everything enqueued on the main stream so far
-    if (!PRE_SIDE_STREAM) return 0;
     if (hipEventRecord(side->fork[k], st) != hipSuccess || hipStreamWaitEvent(st2, side->fork[k], 0) != hipSuccess)
       return fail(MOBODY_E_LAUNCH, "pre-training: fork onto the side stream failed");
     return 0;
@@ -844,7 +837,7 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   {
     Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.d1r, w.d2r, R2, w.dz2[0], w.dz1[0], w.dbp[0], f16 ? w.edz2[0] : nullptr);
     bw.dx = w.dfake; bw.dx_c0 = S + A; bw.dx_n = S;
-    rc = launch_mlp3_bwd(bw, NENS, true, 32, st);
+    rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (!rc) rc = fork(0);
     if (rc) return rc;
     rc = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0], w.dbp[0],
@@ -858,7 +851,7 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   {
     Mlp3BwdArgs bw = pre_bwd_args(L.tr, Ttr, w.dz3tr, w.d1t, w.d2t, R4, w.dz2[1], w.dz1[1], w.dbp[1], f16 ? w.edz2[1] : nullptr);
     bw.dx = w.dzt; bw.dx_c0 = 0; bw.dx_n = LATENT;
-    rc = launch_mlp3_bwd(bw, NENS, true, 32, st);
+    rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (!rc) rc = fork(1);
     if (rc) return rc;
     rc = mlp3_weight_grads(L.tr, w.zt, R4 * LATENT, w.h1t, w.h2t, w.dz3tr, w.dz2[1], w.dz1[1], R4, w.nsplit4, w.slabs[1], w.dbp[1],
@@ -882,17 +875,16 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   // ---- state encoder ----
   {
     Mlp3BwdArgs bw = pre_bwd_args(L.enc, Tenc, w.dz3enc, w.d1e, w.d2e, R2, w.dz2[2], w.dz1[2], w.dbp[2], f16 ? w.edz2[2] : nullptr);
-    rc = launch_mlp3_bwd(bw, NENS, false, 32, st);
+    rc = launch_mlp3_bwd(bw, NENS, false, st);
     if (rc) return rc;
     rc = mlp3_weight_grads(L.enc, w.sx_enc, R2 * L.enc.Kp1, w.h1e, w.h2e, w.dz3enc, w.dz2[2], w.dz1[2], R2, w.nsplit2, w.slabs[2], w.dbp[2],
                            w.ntiles2, gptr(L.off_enc), LossFinal{}, region_adam(L.off_enc, L.t_off_enc), st, precision,
                            f16 ? w.eh1e : nullptr, f16 ? w.edz2[2] : nullptr);
     if (rc) return rc;
   }
-  if (PRE_SIDE_STREAM) {                             // the step ends when both streams have: the main one waits for the side one
-    if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
-      return fail(MOBODY_E_LAUNCH, "pre-training: join of the side stream failed");
-  }
+  // the step ends when both streams have: the main one waits for the side one
+  if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
+    return fail(MOBODY_E_LAUNCH, "pre-training: join of the side stream failed");
   hipLaunchKernelGGL(k_pre_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, r.inv_bg, S, r.ce, r.cr, r.ct, loss_out, loss_acc);
   MB_LAUNCH_OK("k_pre_loss_final");
   return 0;
@@ -1292,18 +1284,15 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
   {
     Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.d1r, w.d2r, R2, w.dz2[0], w.dz1[0], w.dbp[0], f16 ? w.edz2[0] : nullptr);
     bw.dx = w.dfake; bw.dx_c0 = S + A; bw.dx_n = S;
-    rc = launch_mlp3_bwd(bw, NENS, true, 32, st);
+    rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (rc) return rc;
   }
   PreSide* side = nullptr;
-  hipStream_t st2 = st;
-  if (PRE_SIDE_STREAM) {
-    rc = pre_side(&side);
-    if (rc) return rc;
-    st2 = side->s;
-    if (hipEventRecord(side->fork[0], st) != hipSuccess || hipStreamWaitEvent(st2, side->fork[0], 0) != hipSuccess)
-      return fail(MOBODY_E_LAUNCH, "mopo pre-training: fork onto the side stream failed");
-  }
+  rc = pre_side(&side);
+  if (rc) return rc;
+  hipStream_t st2 = side->s;
+  if (hipEventRecord(side->fork[0], st) != hipSuccess || hipStreamWaitEvent(st2, side->fork[0], 0) != hipSuccess)
+    return fail(MOBODY_E_LAUNCH, "mopo pre-training: fork onto the side stream failed");
   // from here on every exit goes through the join below, error or not
   auto after_fork = [&]() -> int {
     int rc2 = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0],
@@ -1313,17 +1302,15 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
     hipLaunchKernelGGL(k_mopo_dmu, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
     MB_LAUNCH_OK("k_mopo_dmu");
     Mlp3BwdArgs bw = pre_bwd_args(L.dyn, Td, w.dz3d, w.d1d, w.d2d, b, w.dz2[1], w.dz1[1], w.dbp[1], f16 ? w.edz2[1] : nullptr);
-    rc2 = launch_mlp3_bwd(bw, NENS, false, 32, st);
+    rc2 = launch_mlp3_bwd(bw, NENS, false, st);
     if (rc2) return rc2;
     return mlp3_weight_grads(L.dyn, w.sx_d, b * L.dyn.Kp1, w.h1d, w.h2d, w.dz3d, w.dz2[1], w.dz1[1], b, w.nsplit1, w.slabs[1],
                              w.dbp[1], w.ntiles1, gptr(L.off_dyn), LossFinal{}, region_adam(L.off_dyn, L.t_off_dyn), st, precision,
                              f16 ? w.eh1d : nullptr, f16 ? w.edz2[1] : nullptr);
   };
   rc = after_fork();
-  if (PRE_SIDE_STREAM) {
-    if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
-      return rc ? rc : fail(MOBODY_E_LAUNCH, "mopo pre-training: join of the side stream failed");
-  }
+  if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
+    return rc ? rc : fail(MOBODY_E_LAUNCH, "mopo pre-training: join of the side stream failed");
   if (rc) return rc;
   hipLaunchKernelGGL(k_mopo_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, inv_bg, S, ce, cr, loss_out, loss_acc);
   MB_LAUNCH_OK("k_mopo_loss_final");

@@ -39,11 +39,10 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
-// Workgroups have 4*RG waves: wave w owns output columns [64*(w&3), +64) of the row group w>>2 (rows
-// [32*MT*(w>>2), +32*MT) of the tile).  RG = 2 puts two waves on every weight-column slice: their B-fragment
-// requests are identical and merge in the CU's L1, so a 64-row tile streams the weights once instead of twice.
+// Workgroups have four waves: wave w owns output columns [64*w, +64) of every row of the tile.  (Eight-wave workgroups, two
+// waves per weight-column slice sharing their B-fragment requests in the CU's L1, were measured and lost: twin-Q forward at
+// 10 240 rows 41.5 us against 28.8 us in bf16x3.)
 __device__ __forceinline__ int wave_col() { return (threadIdx.x >> 6) & 3; }
-__device__ __forceinline__ int wave_rg() { return threadIdx.x >> 8; }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also emits s_waitcnt vmcnt(0), which parks
 // every wave until its outstanding GLOBAL loads/stores (activation saves, prefetched masks) have retired;
@@ -55,16 +54,7 @@ enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2 };
 // 1 / x as ONE v_rcp_f32 (1 ulp) instead of the IEEE division sequence (v_div_scale x 2, v_rcp, four fma, v_div_fmas, v_div_fixup):
 // a Swish is exp + reciprocal + two multiplies, and the ensemble step evaluates ~500 of them per wave and 64-row tile in a kernel
 // whose vector ALU is as busy as its matrix pipe.  The results move by ~1e-7 relative, two orders inside the parity tolerance.
-#ifndef SWISH_FAST_RCP
-#define SWISH_FAST_RCP 1
-#endif
-__device__ __forceinline__ float fast_rcp(float x) {
-#if SWISH_FAST_RCP
-  return __builtin_amdgcn_rcpf(x);
-#else
-  return 1.f / x;
-#endif
-}
+__device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 template <int ACT>
 __device__ __forceinline__ float activate(float x) {
@@ -99,9 +89,6 @@ __host__ __device__ inline long long wide_idx(int k, int n) { return ((long long
 // ~0.9 us (~2000 cycles): throughput per wave = bytes in flight / latency, so 4 chunks (2 KB per wave) are
 // kept in flight.  (With 2 chunks of 4-byte loads the 640-workgroup twin-Q forward ran at 35 % MFMA busy.)
 constexpr int WIDE_RING = 5;
-#ifndef GEMM_PEEL
-#define GEMM_PEEL 1              // 0: accumulate onto the caller's zero-filled registers (A/B aid)
-#endif
 template <int R>
 struct WideRingT { f32x4 r[R][2]; };
 using WideRing = WideRingT<WIDE_RING>;
@@ -148,12 +135,12 @@ __device__ __forceinline__ void wide_gemm(const float* __restrict__ Xs, const fl
   const int i = lane & 31, h = lane >> 5;
   const int kh = Kp >> 1;                       // K range of this lane half, multiple of 4
   const int nch = kh >> 2;                      // chunks of four k-steps
-  const float* xa = Xs + (32 * MT * wave_rg() + i) * LDX + h * kh;
+  const float* xa = Xs + i * LDX + h * kh;
   // FIRST (chunk 0): the first MFMA of each accumulator takes a literal zero C operand -- acc is WRITTEN by this GEMM, a
   // caller's wide_zero is dead code (the chunk loop is a runtime loop: the compiler cannot fold the zero fill itself, and it
   // costs 32 * MT v_mov per GEMM and wave in kernels whose vector ALU is a third of their busy time)
   auto mma = [&](auto first_c, int c, f32x4 (&b)[2]) {
-    constexpr bool FIRST = GEMM_PEEL && decltype(first_c)::value;
+    constexpr bool FIRST = decltype(first_c)::value;
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x4 av[MT];
 #pragma unroll
@@ -206,14 +193,13 @@ template <int MT, class F>
 __device__ __forceinline__ void wide_foreach(f32x16 (&acc)[MT][2], F&& f) {
   const int lane = lane_id(), w = wave_col();
   const int i = lane & 31, h = lane >> 5;
-  const int rbase = 32 * MT * wave_rg();
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = rbase + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;   // C/D map of 32x32 MFMA
+        const int row = 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * h;   // C/D map of 32x32 MFMA
         const int col = 64 * w + 32 * nt + i;
         f(row, col, acc[mt][nt][r]);
       }

@@ -42,15 +42,12 @@ constexpr long long BF_PLANE = 32LL * HID;     // s16x8 units per weight plane (
 // block at or above that bound; the fused Adam plane writers do not check, so a weight trained past it becomes Inf in its plane.
 constexpr int F16_WSHIFT = 8;
 
-#ifndef SPLIT_RING
-#define SPLIT_RING 3
-#endif
 template <int PM>
 struct Split {
   static_assert(PM >= 1 && PM <= 4, "precision mode 1..4");
   static constexpr int NPL = PM == 4 ? 2 : PM;
   static constexpr bool F16 = PM == 4;
-  static constexpr int RING = SPLIT_RING;        // k16 steps of weight fragments in flight
+  static constexpr int RING = 3;                 // k16 steps of weight fragments in flight
 };
 constexpr int split_planes(int pm) { return pm == 4 ? 2 : pm; }
 
@@ -139,15 +136,13 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 // Tile maximum of per-thread maxima through four LDS words: call f16_tile_max_put BEFORE the barrier that separates the GEMM
-// from its epilogue, f16_tile_max_get after it.  `scr` = 4 * waves floats of LDS no other phase touches before the next barrier.
+// from its epilogue, f16_tile_max_get after it.  `scr` = four floats of LDS (one per wave) no other phase touches before the next barrier.
 __device__ __forceinline__ void f16_tile_max_put(float v, float* scr) {
   v = wave_max(v);
   if (lane_id() == 0) scr[threadIdx.x >> 6] = v;
 }
 __device__ __forceinline__ float f16_tile_max_get(const float* scr) {
-  float m = fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
-  if (blockDim.x > 256) m = fmaxf(m, fmaxf(fmaxf(scr[4], scr[5]), fmaxf(scr[6], scr[7])));
-  return m;
+  return fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));
 }
 
 // ---- activation planes in LDS ---------------------------------------------------------------------------------------------
@@ -180,17 +175,13 @@ __device__ __forceinline__ void planes_store4(char* Ps, int k, int c, const floa
   }
 }
 
-// Weight fragments come through a buffer descriptor (BF_BUFFER_LOADS): the per-lane part of the address is ONE 32-bit offset
+// Weight fragments come through a buffer descriptor: the per-lane part of the address is ONE 32-bit offset
 // computed once, the (plane, k-step, column tile) part a scalar / immediate offset -- no vector address arithmetic per load.
 // With plain pointers every 16-byte load cost a 64-bit vector add (~100 of the ~720 non-MFMA vector instructions a wave
 // executes per forward tile, in a kernel whose vector ALU is active a third of its busy time).
-#ifndef BF_BUFFER_LOADS
-#define BF_BUFFER_LOADS 1
-#endif
 template <int PM>
 __device__ __forceinline__ void bf_ldb(const s16x8* __restrict__ Wb, int s, s16x8 (&b)[Split<PM>::NPL][2]) {
   const int lane = lane_id(), r = lane & 31, h = lane >> 5;
-#if BF_BUFFER_LOADS
   // (the member's plane block: NPL planes of 128 KB; wave-uniform base -> scalar registers)
   const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(Wb, (unsigned)(Split<PM>::NPL * BF_PLANE * 16));
   const int voff = (h * HID + 64 * wave_col() + r) * 16;
@@ -199,12 +190,6 @@ __device__ __forceinline__ void bf_ldb(const s16x8* __restrict__ Wb, int s, s16x
 #pragma unroll
     for (int n = 0; n < 2; ++n)
       b[p][n] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (int)((p * BF_PLANE + (long long)2 * s * HID + 32 * n) * 16), 0));
-#else
-#pragma unroll
-  for (int p = 0; p < Split<PM>::NPL; ++p)
-#pragma unroll
-    for (int n = 0; n < 2; ++n) b[p][n] = Wb[p * BF_PLANE + (long long)(2 * s + h) * HID + 64 * wave_col() + 32 * n + r];
-#endif
 }
 
 template <int PM>
@@ -223,19 +208,19 @@ __device__ __forceinline__ void bf_gemm(const char* __restrict__ Ps, const s16x8
   using lds_s16x4 = __attribute__((address_space(3))) s16x4;
   const int lane = lane_id(), g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3, h = lane >> 5;
   // transposed read of k-step s, half j, tile m: lane 4q + pp of a 16-lane group supplies the address of k-row
-  // 16 s + 8 h + 4 j + q, rows 4 c .. 4 c + 3 with c = 8 (MT rg + m) + 4 (g & 1) + pp; it receives its row (lane & 31 of the
+  // 16 s + 8 h + 4 j + q, rows 4 c .. 4 c + 3 with c = 8 m + 4 (g & 1) + pp; it receives its row (lane & 31 of the
   // tile) of the four k-rows: elements 4 j .. 4 j + 3 of the A fragment.  The swizzle depends on k bits 1-3 only: s moves nothing.
   int base[MT][2];
 #pragma unroll
   for (int m = 0; m < MT; ++m)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) base[m][j] = plane_off<TB>(8 * h + 4 * j + q, 8 * (MT * wave_rg() + m) + 4 * (g & 1) + pp);
+    for (int j = 0; j < 2; ++j) base[m][j] = plane_off<TB>(8 * h + 4 * j + q, 8 * m + 4 * (g & 1) + pp);
   // one k-step: weight fragments of step s + R - 1 requested into slot (SL + R - 1) % R, A fragments read, the NPL (NPL + 1) / 2
   // products of every accumulator issued smallest terms first.  FIRST (step 0): the first product of each accumulator takes a
   // literal zero as its C operand -- the accumulators are never zero-initialised (32 v_mov per GEMM and wave otherwise: the
   // loop is a runtime loop, so the compiler cannot fold the caller's zero fill into the first MFMA itself).
   auto step = [&](auto first_c, int s, auto slot_c) {
-    constexpr bool FIRST = GEMM_PEEL && decltype(first_c)::value;
+    constexpr bool FIRST = decltype(first_c)::value;
     constexpr int SL = decltype(slot_c)::value;
     if (s + R - 1 < 16) bf_ldb<PM>(Wb, s + R - 1, ring.r[(SL + R - 1) % R]);
     __builtin_amdgcn_sched_barrier(0);

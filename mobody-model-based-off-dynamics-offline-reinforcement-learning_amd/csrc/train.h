@@ -73,7 +73,7 @@ struct Mlp3BwdArgs {
   float* dx;               // [members][rows][dx_n] input gradient columns [dx_c0, dx_c0 + dx_n)  (DX only)
   int dx_c0, dx_n;
 };
-int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, int tile_rows, hipStream_t st);
+int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st);
 
 struct WgradJob {
   const float* A; long long a_mstride; int lda, ka;    // A[rows][lda], columns < ka contribute (output rows)

@@ -22,7 +22,7 @@ struct TrainWs {
   float *pin;            // pi(s') of the critic phase (pi holds pi(s) for the actor phase)
   float *pi, *qt, *q, *qb, *xq, *h1q, *h2q, *xa, *h1a, *h2a, *dz3q, *dz2, *dz1, *dz3a, *dxa, *bcw, *dbp, *slabs, *lossp;
   long long total;
-  int nsplit_q, nsplit_a, ntiles, tile_rows;
+  int nsplit_q, nsplit_a, ntiles;
   MobodyMlpLayout Lq, La;
 };
 
@@ -57,8 +57,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   w.dxa = take(2 * N * d.A);
   w.bcw = take(Nt > 0 ? Nt : 1);
   w.lossp = take(2 * cdiv(N, 32));                // per (row tile, member) / per-tile pairs, tiles of >= 32 rows
-  w.tile_rows = pick_tile_rows(N, 1);             // one value for both nets: the bias partials are per row tile
-  w.ntiles = (int)cdiv(N, w.tile_rows);
+  w.ntiles = (int)cdiv(N, MLP_TILE_ROWS);         // the bias partials are per row tile
   w.nsplit_q = wgrad_nsplit(N, 2);
   w.nsplit_a = wgrad_nsplit(N, 1);
   const long long per_q = 2 * HID + w.Lq.Np3, per_a = 2 * HID + w.La.Np3;
@@ -333,7 +332,7 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
   Mlp3BwdArgs bq = bwd_args(w.Lq, q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
   bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = reward; bq.seed.nd = not_done;
   bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
-  rc = launch_mlp3_bwd(bq, 2, false, w.tile_rows, st);
+  rc = launch_mlp3_bwd(bq, 2, false, st);
   if (rc) return rc;
   LossFinal lf{};                                  // q_loss = mse(q1,y)+mse(q2,y), local share of the global mean
   lf.kind = 1; lf.nparts = 2 * w.ntiles; lf.scale = invNg; lf.parts = w.lossp; lf.out = loss_out;
@@ -406,15 +405,11 @@ extern "C" int mobody_actor_forward(const MobodyTrainDims* d, const MobodyHyper*
   const Mlp3FwdArgs fb = fwd_args(q_blob, w.Lq, state, S, action, A, Nt, w.qb, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, qT);
   // Q(s, pi(s)) with the freshly updated critic (:316); dQ/da through the frozen net needs only the ReLU signs
   const Mlp3FwdArgs fp = fwd_args(q_blob, w.Lq, state, S, w.pi, A, N, w.q, 0, 1.f, nullptr, nullptr, nullptr, w.mq1, w.mq2, qT);
-  static const bool split_q = tune_int("MOBODY_MERGE_ACTOR_Q", 1) == 0;   // tuning aid (diagnostic build)
-  if (policy_ready && !split_q) {
+  if (policy_ready) {
     rc = fwd_pair(fb, 2, fp, 2, prec, st);                 // both on the same critic: one launch of N + Nt rows (0.384 -> 0.380 ms/step)
   } else {
-    if (policy_ready)
-      rc = fwd_one(fb, 2, prec, st);
-    else
-      rc = fwd_pair(fb, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
-                                    prec == 4 ? w.eh1a : nullptr), 1, prec, st);
+    rc = fwd_pair(fb, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                                  prec == 4 ? w.eh1a : nullptr), 1, prec, st);
     if (!rc) rc = fwd_one(fp, 2, prec, st);
   }
   if (rc) return rc;
@@ -447,12 +442,12 @@ static int actor_backward_impl(const MobodyTrainDims* d, const MobodyHyper* h, c
   Mlp3BwdArgs bq = bwd_args(w.Lq, q_blob_T, nullptr, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, h->precision);
   bq.seed.mode = 2; bq.seed.ar = ra;
   bq.dx = w.dxa; bq.dx_c0 = d->S; bq.dx_n = d->A;
-  rc = launch_mlp3_bwd(bq, 2, true, w.tile_rows, st);
+  rc = launch_mlp3_bwd(bq, 2, true, st);
   if (rc) return rc;
   // actor: d(pre-tanh) from both members' dx and the BC term in the prologue, then the actor's own backward
   Mlp3BwdArgs ba = bwd_args(w.La, actor_blob_T, w.dz3a, w.h1a, w.h2a, N, w.dz2, w.dz1, w.dbp, w.ma1, w.ma2, h->precision, w.edz2);
   ba.seed.mode = 3; ba.seed.ar = ra; ba.seed.dz3_out = w.dz3a; ba.seed.lossp = w.lossp;
-  rc = launch_mlp3_bwd(ba, 1, false, w.tile_rows, st);
+  rc = launch_mlp3_bwd(ba, 1, false, st);
   if (rc) return rc;
   LossFinal lf{};                                  // loss_out[0] = p_w*mean(-q) + bc_coef*L_BC, [1] = L_BC (local shares)
   lf.kind = 2; lf.nparts = w.ntiles; lf.scale_q = h->scale_q; lf.weight = h->weight; lf.bc_coef = h->bc_coef;

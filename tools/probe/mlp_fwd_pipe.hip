@@ -1,6 +1,6 @@
 // EXPERIMENT, NOT BUILT (round 3; measured slower than k_mlp3_fwd_bf).  To try it again: copy this file into
 // csrc/, declare try_launch_mlp3_fwd_pipe in layers.h and call it at the top of launch_mlp3_fwd_bf for prec == 4;
-// tools/probe/ab_pipe.sh and trace_pipe.sh then A/B and phase-trace it (tools/trace_mlp.py fwd with PIPE_MT set).
+// tools/probe/ab_pipe.sh then A/Bs it; tools/trace_mlp.py fwd with PIPE_MT set phase-traces it.
 //
 // Software-pipelined fused 3-layer MLP forward of the "f16x2" mode (ReLU nets of the train step: actor / twin-Q and their
 // targets).  In k_mlp3_fwd_bf (mlp_fwd_bf.hip) every workgroup of a launch walks the same phases at the same time -- the
