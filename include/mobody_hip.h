@@ -24,7 +24,8 @@
  * Conventions
  *   - every pointer is a DEVICE pointer (hipMalloc / torch `tensor.data_ptr()`), fp32
  *     row-major contiguous unless stated; the caller owns every buffer; the library
- *     allocates nothing and keeps no state between calls (no context object needed);
+ *     allocates nothing and needs no context object.  Between calls it keeps, per device, the
+ *     pre-training side stream and the pointer to the caller's health words (mobody_health_bind);
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*); no call
  *     synchronises; calls are graph-capturable;
  *   - every function returns 0 on success, a negative MOBODY_E* code otherwise and
@@ -105,13 +106,47 @@ int mobody_abi_version(void);
 int mobody_dyn_layout(int S, int A, MobodyDynLayout* out);
 int mobody_mlp_layout(int in_dim, int out_dim, int members, MobodyMlpLayout* out);
 
-/* ---- optional per-kernel timing (measurement only; the one piece of process-global state) ----
+/* ---- optional per-kernel timing (measurement only; process-global state) ----
  * Between prof_begin and prof_end every launch of the heavy kernel families is bracketed by a HIP
  * event pair on its launch stream.  prof_end SYNCHRONISES, then returns the summed milliseconds
  * and launch counts per family id: 0 mlp3_fwd, 1 mlp3_bwd, 2 wgrad, 3 dyn_fwd (4..7 reserved). */
 #define MOBODY_PROF_IDS 8
 int mobody_prof_begin(int max_events);
 int mobody_prof_end(double* ms_by_id, int64_t* count_by_id, int n_ids);
+
+/* ---- device health words ------------------------------------------------------------------
+ * A caller-owned block of MOBODY_HEALTH_WORDS int32 in device memory that the kernels writing weights report into, so
+ * that a fault is seen where it happens and not when NaN reaches the host:
+ *   words[0]  bit mask.  MOBODY_HEALTH_F16_RANGE: a value w with !(|w| < MOBODY_F16_W_LIMIT) was written into a
+ *             precision-4 ("f16x2") weight plane, whose fp16 terms of w * 2^8 then hold Inf (online and target planes, W2
+ *             and W2^T; the optimizer entry points, mobody_mlp_transpose, mobody_dyn_planes and the pre-training
+ *             transposes).  MOBODY_HEALTH_NONFINITE: an optimizer step produced a non-finite parameter (every mode).
+ *   words[1]  Adam step count of the first optimizer launch that raised a bit (0: none, or a plane builder did)
+ *   words[2..3] internal (one 64-bit key of that launch; the block must be 8-byte aligned); words[4..] reserved
+ * Lanes write (atomically) only when they see a violation; a clean run costs one compare per parameter.
+ * FREEZE: every entry point that applies an optimizer step (mobody_adam_polyak[_dev], mobody_critic_update[_phase],
+ * mobody_actor_update, mobody_pretrain[_mopo]_update / _adam, mobody_pretrain_za_adam) reads words[0] on entry; when an
+ * EARLIER launch has set a bit it applies nothing -- parameters, moments, target, T blob, planes and `bump` stay as they
+ * are (gradient and loss outputs are still written).  The launch in which the fault happens completes: its fp32 results
+ * are exact, only the plane holds Inf.  So the state stops at the last update computed from healthy planes, however many
+ * replayed steps pass before the host looks.  A captured optimizer launch must read a device step count that advances
+ * between replays (as the `_dev` forms require anyway): that is how a replay tells itself from the faulting one.
+ * CONSEQUENCE for callers of the `_dev` forms: whatever advances those step words keeps advancing them while the updates are
+ * frozen (only `bump` stops), so after a fault they run ahead of the steps that were applied: words[1] holds the faulting
+ * launch's own count, and the caller re-seeds its step words from it before it goes on (the host mirror does).
+ * OVERLAP: the verdict is taken per workgroup when it starts.  It is one verdict per launch as long as no other optimizer
+ * launch raises a fault while the launch runs; an optimizer launch that overlaps the faulting one on another stream (the
+ * pre-training step runs its nets' optimizer launches on two streams) may be applied in part -- each element it applied is a
+ * complete, finite step computed from healthy planes.
+ * With no block bound, or a bound block that stays zero, every output is bit-identical to a library without the guard.
+ * mobody_health_bind stores the pointer for the CURRENT device (NULL unbinds); launches pass it to their kernels as an
+ * argument, so a graph captured after the bind carries it.  mobody_health_clear zeroes the block on `stream`. */
+#define MOBODY_HEALTH_WORDS 8
+#define MOBODY_HEALTH_F16_RANGE 1
+#define MOBODY_HEALTH_NONFINITE 2
+#define MOBODY_F16_W_LIMIT 255.875f   /* 65504 / 2^8 */
+int mobody_health_bind(int32_t* words_dev);
+int mobody_health_clear(void* stream);
 
 /* ---- counter based RNG (Philox4x32-10; CPU twin: oracle/mobody_oracle.py rng_*) ---------- */
 int mobody_rng_normal(uint32_t seed, uint32_t stream_id, uint32_t call, int64_t n, float* out, void* stream);

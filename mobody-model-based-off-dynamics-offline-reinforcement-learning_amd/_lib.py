@@ -86,6 +86,9 @@ UNCERTAINTY_MODES = {"pairwise-diff": 0, "aleatoric": 1, "ensemble_std": 2}
 
 TERM_IDS = {"never": 0, "halfcheetah": 1, "hopper": 2, "ant": 3, "walker2d": 4, "humanoid": 5, "pen": 6}
 
+# device health words (include/mobody_hip.h)
+HEALTH_WORDS, HEALTH_F16_RANGE, HEALTH_NONFINITE = 8, 1, 2
+
 # name -> (restype, argtypes); must list every symbol include/mobody_hip.h declares
 PROTOTYPES = {
     "mobody_last_error": (C.c_char_p, []),
@@ -94,6 +97,8 @@ PROTOTYPES = {
     "mobody_mlp_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MobodyMlpLayout)]),
     "mobody_prof_begin": (C.c_int, [C.c_int]),
     "mobody_prof_end": (C.c_int, [C.POINTER(C.c_double), C.POINTER(i64), C.c_int]),
+    "mobody_health_bind": (C.c_int, [vp]),
+    "mobody_health_clear": (C.c_int, [vp]),
     "mobody_rng_normal": (C.c_int, [u32, u32, u32, i64, vp, vp]),
     "mobody_rng_index": (C.c_int, [u32, u32, u32, i64, u32, vp, vp]),
     "mobody_dyn_forward": (C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, i64, C.c_int, vp, vp]),

@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from ... import dp, ops
+from ... import _lib, dp, ops
 
 
 class StandardScaler(object):
@@ -63,6 +63,20 @@ class MOBODYEnsembleDynamics(object):
         self.precision = ops.prec_id(str(config.get("mfma", ops.default_mfma())))     # MFMA mode of step(): 0 exact fp32 | bf16 / bf16x2 / bf16x3
         # pre-training follows the mode when it is the fp32-grade "f16x2", and stays on exact fp32 MFMA under the bf16 modes
         self.train_precision = 4 if self.precision == 4 else 0
+        # config['f16_guard'] ('raise' | 'fallback' | 'off'): the device health words are read after every validate() and in
+        # save().  Pre-training does not change its mode mid-run: 'fallback' (one config serves the policy and the dynamics
+        # object) is taken as 'raise' here, with a warning.
+        d = torch.distributed
+        self.f16_guard = ops.check_f16_guard(config.get("f16_guard", "raise"), d.is_available() and d.is_initialized())
+        if self.f16_guard == "fallback":
+            import warnings
+            warnings.warn("f16_guard='fallback' applies to the policy object; the dynamics object raises on a fault (as 'raise')")
+            self.f16_guard = "raise"
+        self._health = None
+        if self.f16_guard != "off" and torch.device(model.device).type == "cuda":   # (a CPU-side model only converts checkpoints)
+            with torch.cuda.device(model.device):
+                self._health = ops.health_block(model.device)
+        self._fault = None
         self._calls = 0
         self.noise_fn = None          # optional hook: noise_fn((7, B, S)) -> unit normals (tests)
         self.train_noise_fn = None    # optional hook: b -> (noise6[6,7,b,16], noise7[7,b,S]) device tensors (tests); mopo
@@ -130,6 +144,42 @@ class MOBODYEnsembleDynamics(object):
                 "reward_mse": torch.mean((rew - r["reward"].reshape(-1)) ** 2), "penalty": r["penalty"]}
 
     # ------------------------------------------------------------------ pre-training (mobody_dynamics.py:594-653,731-978,1113-1156)
+    def _health_check(self):
+        """Raise FloatingPointError (once) when a kernel has reported an f16x2 range fault or a non-finite optimizer result:
+        every optimizer launch since was frozen, so the training copy holds the last update computed from healthy planes.
+        (The host step counts of the frozen launches are not taken back.)"""
+        words = ops.health_bound(self.model.device) if torch.device(self.model.device).type == "cuda" else None
+        if words is None or self._fault is not None:
+            return
+        mask, step = ops.health_read(words)
+        if mask == 0:
+            return
+        m, found = self.model, []
+        st = getattr(m, "_train", None)
+        if st is not None:
+            S, A = m.obs_dim, m.action_dim
+            if m.mopo:
+                L = _lib.pretrain_mopo_layout(S, A)
+                nets = (("dynamics MLP (za_src2)", L.off_dyn, L.dyn), ("reward head (reward_model2)", L.off_rw, L.rw))
+            else:
+                L = _lib.pretrain_layout(S, A)
+                nets = (("state encoder (zs2)", L.off_enc, L.enc), ("decoder (transition2)", L.off_tr, L.tr),
+                        ("reward head (reward_model2)", L.off_rw, L.rw))
+            for name, off, lay in nets:
+                w = float(ops._mlp_w2(st["blob"][off:], lay, 7).abs().max())
+                if not (w < ops.F16_W_LIMIT):
+                    found.append(f"{name} (max |W2| = {w:g})")
+            if not bool(torch.isfinite(st["blob"]).all()):
+                found.append("non-finite parameters in the training copy")
+        self._pre_graphs = {}
+        self._fault = (f"device health word {'|'.join(ops.health_bits(mask))}" + (f" at Adam step {step}" if step else "") + ": "
+                       + (", ".join(found) or "no pre-training network (another object on this device)")
+                       + "; optimizer steps since are frozen at the last healthy update (a net whose optimizer launch ran next to the "
+                       "faulting one on the step's second stream may hold that step in part; the host step counts include the frozen "
+                       f"steps). f16x2 planes hold |w| < {ops.F16_W_LIMIT}: "
+                       "pre-train with mfma='bf16x3' (exact fp32 pre-training)")
+        raise FloatingPointError(self._fault)
+
     def _check_pretrain_config(self):
         cfg = self.config
         if getattr(self.model, "mopo", False):
@@ -599,6 +649,7 @@ class MOBODYEnsembleDynamics(object):
             out = ops.dyn_validate(m.packed(), m.obs_dim, m.action_dim, f(holdout_obss), f(holdout_actions), f(holdout_next_obss),
                                    f(holdout_rewards), use_trg_data).cpu().numpy()
         m.uninference()
+        self._health_check()                              # (the .cpu() above has synchronised)
         return list(out[:7]), list(out[7:])
 
     def select_elites(self, metrics):
@@ -712,6 +763,7 @@ class MOBODYEnsembleDynamics(object):
         print("elites:{} , holdout loss: {}".format(indexes, (np.sort(trg_holdout_losses)[:m.num_elites]).mean()))
 
     def save(self, save_path):
+        self._health_check()
         torch.save(self.model.state_dict(), os.path.join(save_path, "dynamics.pth"))        # :1158-1161
         self.obs_scaler.save_scaler(save_path)
 

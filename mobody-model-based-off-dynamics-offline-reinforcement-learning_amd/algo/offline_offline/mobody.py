@@ -191,6 +191,17 @@ class MOBODY(object):
         # MFMA mode of the 256 x 256 layers: 'f32' exact | 'f16x2' | 'bf16x3' (both fp32-grade) | 'bf16x2' | 'bf16'
         self.mfma = str(config.get("mfma", ops.default_mfma()))
         self.precision = ops.prec_id(self.mfma)
+        # config['f16_guard']: what a fault in the device health words does ('raise' | 'fallback' to bf16x3 | 'off').  The
+        # block is ONE per device, shared by every object there: constructing an object never clears it (a fault another object
+        # has not reported yet stays), and 'off' only means that this object binds none -- if something else on the device did,
+        # its kernels report and freeze all the same, so the check points below still read the word and raise.
+        d = torch.distributed
+        self.f16_guard = ops.check_f16_guard(config.get("f16_guard", "raise"), d.is_available() and d.is_initialized())
+        self._health = None
+        if self.f16_guard != "off":
+            with torch.cuda.device(self.device):
+                self._health = ops.health_block(self.device)
+        self._fault = None                                  # message of a fault already reported ('raise' leaves the object frozen)
         self.rng = config.get("rng", "numpy")               # 'numpy' = reference index/elite streams; 'device' = Philox
         self.seed = int(config.get("seed", 0))
         # config['fake_buffer_size']: rows of the fake buffer's ring (default: the reference's 1e6).  With a sharded refresh a
@@ -428,6 +439,64 @@ class MOBODY(object):
                                  tr["rewards"], cfg["penalty_coef"])
                 self.fake_replay_buffer.add_batch(tr)
 
+    # ------------------------------------------------------------------ device health words
+    def _health_check(self):
+        """Read the health words (a device sync: called before a refresh, on logging steps, in save() and at the end of the
+        CLI's run, never per step).  A fault has frozen every optimizer launch since, so the fp32 state is the last one computed
+        from healthy planes: 'raise' reports it once and leaves the object saveable, 'fallback' moves an F16_RANGE fault to
+        bf16x3 and goes on."""
+        words = ops.health_bound(self.device)              # whoever bound it: the kernels of this object report there too
+        if words is None or self._fault is not None:
+            return
+        mask, step = ops.health_read(words)
+        if mask == 0:
+            return
+        cls = self.classifier
+        nets = (("q_funcs", self.q_funcs, self.q_optimizer), ("target_q_funcs", self.target_q_funcs, self.q_optimizer),
+                ("policy", self.policy, self.policy_optimizer), ("v_func", self.v_func, self.v_optimizer),
+                ("classifier.sa_classifier", cls.sa_classifier, cls.opt_sa), ("classifier.sas_classifier", cls.sas_classifier, cls.opt_sas))
+        found = []
+        for name, n, opt in nets:
+            w2 = ops._mlp_w2(n.blob, n.layout, n.members)
+            m = float(w2.abs().max())
+            if (n.precision == 4 and not (m < ops.F16_W_LIMIT)) or not bool(torch.isfinite(n.blob).all()):
+                found.append((name, m, opt))
+        frozen = self._health_rewind(step, found[0][2] if found else None)
+        self._graph = None                                  # the device step counts are re-seeded from the host's
+        bits = "|".join(ops.health_bits(mask))
+        where = ", ".join(f"{name} (max |W2| = {m:g})" for name, m, _ in found) or "no policy network (another object on this device)"
+        msg = (f"device health word {bits}" + (f" at Adam step {step}" if step else "") + f": {where}; "
+               f"{frozen} optimizer step(s) were frozen, the parameters are those of the last healthy update (an optimizer launch "
+               f"that ran next to the faulting one on another stream, if there was one, may hold that step in part). "
+               f"f16x2 planes hold |w| < {ops.F16_W_LIMIT}: use mfma='bf16x3' (or f16_guard='fallback')")
+        if self.f16_guard == "fallback" and mask == _lib.HEALTH_F16_RANGE and found:
+            import warnings
+            warnings.warn("falling back to mfma='bf16x3': " + msg)
+            self.mfma, self.precision = "bf16x3", ops.prec_id("bf16x3")
+            self.config["mfma"] = "bf16x3"
+            for n in (self.q_funcs, self.target_q_funcs, self.policy):   # T blobs and planes again, from the intact fp32 weights
+                n.precision = self.precision
+                ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
+                n.version += 1
+            self._ws, self._ws_key = None, None             # re-made by _dims(), as after construction
+            ops.health_clear()
+            return
+        self._fault = msg
+        raise FloatingPointError(msg)
+
+    def _health_rewind(self, step, opt):
+        """Host step counts back to the updates that were applied.  `step` is the faulting optimizer's own count; within a
+        train() call the order is V, critic, actor, so the launches after the faulting one were frozen one call earlier."""
+        order = [self.v_optimizer, self.q_optimizer, self.policy_optimizer]      # (the classifier's counts are left as they are)
+        if opt not in order or step <= 0 or opt.t < step:
+            return 0
+        n = opt.t - step
+        k = order.index(opt)
+        for j, o in enumerate(order):
+            if o.t > 0:
+                o.t = max(0, o.t - n - (1 if j > k else 0))
+        return n
+
     # ------------------------------------------------------------------ training
     # ------------------------------------------------------------------ HIP-graph fast path
     def _graph_ok(self, writer):
@@ -618,6 +687,8 @@ class MOBODY(object):
         ns, nt = int(cfg["src_ratio"] * batch_size), int(cfg["trg_ratio"] * batch_size)
         nf = int(cfg["fake_batch_scale"] * batch_size) if cfg["fake_batch_scale"] != 0 else 0
         N, Nt = ns + nt + nf, ns + nt
+        if (self.total_it - 1) % REFRESH_EVERY == 0 or (writer is not None and self.total_it % 5000 == 0):
+            self._health_check()                          # no NaN rows into the fake buffer, no NaN scalars into the log
         # graph replay only once the minibatch tensors of THIS batch size exist (an eager step allocates them)
         if (self._batch is not None and self._batch_key == (N,) and self._graph_ok(writer)
                 and self._graph_step(src_replay_buffer, tar_replay_buffer, batch_size)):
@@ -810,6 +881,7 @@ class MOBODY(object):
 
     # ------------------------------------------------------------------ checkpoints (mobody.py:584-594)
     def save(self, filename):
+        self._health_check()
         torch.save(self.q_funcs.state_dict(), filename + "_critic")
         torch.save(self.q_optimizer.state_dict(), filename + "_critic_optimizer")
         torch.save(self.policy.state_dict(), filename + "_actor")

@@ -3,9 +3,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "common.h"
+#include "health.h"
 
 namespace mobody {
 
@@ -24,7 +26,7 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// ---- profiling state (the only process-global state of the library; off by default) ----
+// ---- profiling state (process-global, off by default) ----
 struct ProfEvent { int id; hipEvent_t a, b; };
 static std::vector<ProfEvent>& prof_pool() { static std::vector<ProfEvent> p; return p; }
 static bool g_prof_on = false;
@@ -40,9 +42,40 @@ ProfScope::~ProfScope() {
   if (slot >= 0) (void)hipEventRecord(prof_pool()[slot].b, st);
 }
 
+
+// ---- health words: the caller's block, kept per device (health.h) ----
+static int* g_health[16] = {nullptr};
+static std::atomic<int> g_health_tag{0};            // host threads driving different devices share the count
+int* health_words() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
+  return g_health[dev];
+}
+int health_next_tag() {
+  int t = g_health_tag.fetch_add(1, std::memory_order_relaxed) + 1;
+  return (t & 0x7fffffff) ? (t & 0x7fffffff) : 1;                        // never 0: that is "no launch" in the key
+}
+
 }  // namespace mobody
 
 using namespace mobody;
+
+extern "C" int mobody_health_bind(int32_t* words_dev) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return fail(MOBODY_E_LAUNCH, "mobody_health_bind: hipGetDevice failed");
+  MB_REQUIRE(dev >= 0 && dev < 16, "mobody_health_bind: device index %d is outside the 16 the library keeps a pointer for", dev);
+  MB_REQUIRE((reinterpret_cast<uintptr_t>(words_dev) & 7) == 0, "mobody_health_bind: the block must be 8-byte aligned");
+  g_health[dev] = words_dev;
+  return 0;
+}
+
+extern "C" int mobody_health_clear(void* stream) {
+  int* w = health_words();
+  MB_REQUIRE(w != nullptr, "mobody_health_clear: no health words bound on this device");
+  if (hipMemsetAsync(w, 0, sizeof(int32_t) * MOBODY_HEALTH_WORDS, reinterpret_cast<hipStream_t>(stream)) != hipSuccess)
+    return fail(MOBODY_E_LAUNCH, "mobody_health_clear: hipMemsetAsync failed");
+  return 0;
+}
 
 #ifdef MOBODY_TRACE
 namespace mobody { __device__ unsigned long long g_trace[TRACE_BLOCKS * TRACE_SLOTS]; }

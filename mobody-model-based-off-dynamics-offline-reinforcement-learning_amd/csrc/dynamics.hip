@@ -16,6 +16,7 @@
 // S=17,A=6 against 240 algorithmic bytes); k_dyn_sample / k_dyn_finalize are HBM-bound
 // streaming kernels over [E,B,S] floats.
 #include "common.h"
+#include "health.h"
 #include "layers_bf.h"
 #include "rng.h"
 
@@ -341,7 +342,7 @@ static int launch_dyn_fwd(const float* blob, const MobodyDynLayout& L, const flo
 
 // zs2 / transition2 / reward_model2 of every member -> their three bf16 planes (precision 0-3) or two fp16 planes of
 // w * 2^F16_WSHIFT (precision 4)
-__global__ __launch_bounds__(256) void k_dyn_planes(const float* blob, MobodyDynLayout L, short* planes, int precision) {
+__global__ __launch_bounds__(256) void k_dyn_planes(const float* blob, MobodyDynLayout L, short* planes, int precision, int* health) {
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= 3LL * NENS * HID * HID) return;
   const int layer = (int)(gid / ((long long)NENS * HID * HID));
@@ -355,6 +356,7 @@ __global__ __launch_bounds__(256) void k_dyn_planes(const float* blob, MobodyDyn
     split_terms<4>(w * exp2i(F16_WSHIFT), t);
 #pragma unroll
     for (int p = 0; p < 2; ++p) pl[bf_plane_idx(p, k, n)] = t[p];
+    health_check_f16(health, w);
   } else {
     short t[3];
     split_terms<3>(w, t);
@@ -376,7 +378,7 @@ extern "C" int mobody_dyn_planes(const float* dyn_blob, int S, int A, float* pla
   MB_REQUIRE(dyn_blob && planes, "mobody_dyn_planes: null pointer");
   MB_REQUIRE(precision >= 0 && precision <= 4, "mobody_dyn_planes: precision must be 0..4");
   hipLaunchKernelGGL(k_dyn_planes, dim3((unsigned)cdiv(3LL * NENS * HID * HID, 256)), dim3(256), 0, as_stream(stream), dyn_blob, L,
-                     reinterpret_cast<short*>(planes), precision);
+                     reinterpret_cast<short*>(planes), precision, health_words());
   MB_LAUNCH_OK("k_dyn_planes");
   return 0;
 }

@@ -839,9 +839,10 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
 __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
   __shared__ float adam_sm[2];
   adam_block_consts(a.adam, adam_sm);
+  const int hmask = health_mask(a.adam);                         // an earlier fault: the gradient and the loss are still written
   const long long nW = a.L.total_floats;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid == 0 && a.adam.bump != nullptr) a.adam.bump[0] += 1;      // graph replay: advance a counter no block of this launch reads
+  if (gid == 0 && a.adam.on && a.adam.bump != nullptr && !(hmask != 0 && health_foreign(a.adam))) a.adam.bump[0] += 1;      // graph replay: advance a counter no block of this launch reads
   if (gid < nW) {
     const long long j = gid;
     const long long o = j % a.L.member_floats;
@@ -858,7 +859,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
     }
     for (; k < a.nsplit; ++k) s += a.slabs[(long long)k * a.slab_stride + j];
     if (a.grad != nullptr) a.grad[j] = s;
-    if (a.adam.on) adam_element(a.adam, a.L, j, s, adam_sm);
+    if (a.adam.on) adam_element(a.adam, a.L, j, s, adam_sm, hmask);
     return;
   }
   // ---- bias part: wave index -> (member, bias element) ----
@@ -898,7 +899,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
   if (lane == 0) {
     const long long dst = (long long)m * a.L.member_floats + (off < HID ? a.L.b1 + off : off < 2 * HID ? a.L.b2 + (off - HID) : a.L.b3 + (off - 2 * HID));
     if (a.grad != nullptr) a.grad[dst] = s;
-    if (a.adam.on) adam_element(a.adam, a.L, dst, s, adam_sm);
+    if (a.adam.on) adam_element(a.adam, a.L, dst, s, adam_sm, hmask);
   }
 }
 

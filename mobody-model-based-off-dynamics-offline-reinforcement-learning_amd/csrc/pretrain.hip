@@ -449,20 +449,24 @@ __global__ __launch_bounds__(256) void k_pre_latent_bwd(PreRow a, LatentLds o, i
 }
 
 // action-encoder gradient: sum of the workgroup partials in chunk order (deterministic)
-__device__ __forceinline__ void za_adam_element(const AdamTarget& a, long long j, float g, const float* sm2) {
+__device__ __forceinline__ void za_adam_element(const AdamTarget& a, long long j, float g, const float* sm2, int hmask) {
   AdamConsts c = a.c;
   if (a.t_dev != nullptr) { c.step_size = sm2[0]; c.bc2_sqrt = sm2[1]; }      // adam_block_consts (train.h)
   const float gj = g * c.gscale;
   const float m0 = a.m[j];
-  const float mj = m0 + c.w1 * (gj - m0);
-  const float vj = c.b2 * a.v[j] + c.w2 * (gj * gj);
+  const float mj = m0 + ADAM_W1 * (gj - m0);
+  const float vj = ADAM_B2 * a.v[j] + ADAM_W2 * (gj * gj);
+  const float pj = a.p[j] - c.step_size * (mj / (sqrtf(vj) / c.bc2_sqrt + ADAM_EPS));
+  if (hmask != 0 && health_foreign(a)) return;
   a.m[j] = mj; a.v[j] = vj;
-  a.p[j] = a.p[j] - c.step_size * (mj / (sqrtf(vj) / c.bc2_sqrt + c.eps));
+  a.p[j] = pj;
+  health_after_update(a, pj, false, 0.f, false);
 }
 
 __global__ __launch_bounds__(256) void k_pre_za_reduce(const float* zap, int nch, long long n, float* grad, AdamTarget adam) {
   __shared__ float adam_sm[2];
   adam_block_consts(adam, adam_sm);
+  const int hmask = health_mask(adam);
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float s = 0.f;
@@ -474,7 +478,7 @@ __global__ __launch_bounds__(256) void k_pre_za_reduce(const float* zap, int nch
   }
   for (; c < nch; ++c) s += zap[(long long)c * n + i];
   if (grad != nullptr) grad[i] = s;
-  if (adam.on) za_adam_element(adam, i, s, adam_sm);       // single-GPU form: the reduction applies the optimizer step itself
+  if (adam.on) za_adam_element(adam, i, s, adam_sm, hmask);       // single-GPU form: the reduction applies the optimizer step itself
 }
 
 // out[5] = (loss, transition_loss, encoder_loss, recon_loss, kl_loss) as learn() reports them (:630-650); local shares
@@ -509,9 +513,10 @@ __global__ __launch_bounds__(256) void k_pre_loss_final(const float* lossp, PreL
 __global__ __launch_bounds__(256) void k_pre_za_adam(AdamTarget a, const float* g, long long n) {
   __shared__ float adam_sm[2];
   adam_block_consts(a, adam_sm);
+  const int hmask = health_mask(a);
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  za_adam_element(a, j, g[j], adam_sm);
+  za_adam_element(a, j, g[j], adam_sm, hmask);
 }
 
 // bootstrap gather of one batch: member e takes dataset rows idx[e][start + r]   (mobody_dynamics.py:604-612, the
@@ -723,11 +728,11 @@ static AdamTarget pre_adam_target(float* p, float* pT, float* m, float* v, int64
   const double bc1 = 1.0 - pow(0.9, tt), bc2 = 1.0 - pow(0.999, tt);
   AdamTarget a{};
   a.p = p; a.m = m; a.v = v; a.blob_T = pT; a.target = nullptr;
-  a.c.w1 = (float)(1.0 - 0.9); a.c.b2 = (float)0.999; a.c.w2 = (float)(1.0 - 0.999);
-  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2); a.c.eps = 1e-8f;
+  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
   a.c.tau = -1.f; a.c.one_minus_tau = 0.f; a.c.gscale = grad_scale;
   a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1;
   a.precision = precision == 4 ? 4 : -1;          // exact fp32 never reads the W2 planes of its T blob; f16x2 keeps them current
+  a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
   return a;
 }
 // Side stream of the step.  After a net's backward kernel its weight-gradient GEMM and the gradient reduction (with the fused

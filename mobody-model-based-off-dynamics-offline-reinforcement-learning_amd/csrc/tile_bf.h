@@ -39,7 +39,8 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 constexpr long long BF_PLANE = 32LL * HID;     // s16x8 units per weight plane ([K/8 = 32][256])
 // "f16x2" weight planes hold w * 2^8: |w| must stay below 65504 / 2^8 ~ 255.9 (residual terms stay normal down to |w| ~ 5e-4).
 // The host-side plane builders (ops.mlp_transpose / dyn_planes / pretrain_transpose / pretrain_mopo_transpose) refuse a W2
-// block at or above that bound; the fused Adam plane writers do not check, so a weight trained past it becomes Inf in its plane.
+// block at or above that bound; a weight TRAINED past it becomes Inf in its plane, which the writers report into the device
+// health words (health.h: MOBODY_HEALTH_F16_RANGE) -- later optimizer launches then leave the fp32 state as it is.
 constexpr int F16_WSHIFT = 8;
 
 template <int PM>

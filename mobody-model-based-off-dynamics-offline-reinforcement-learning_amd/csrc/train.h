@@ -6,6 +6,7 @@
 #include "common.h"
 #include "tile.h"
 #include "tile_bf.h"
+#include "health.h"
 
 namespace mobody {
 
@@ -100,7 +101,9 @@ int launch_wgrad(WgradArgs a, hipStream_t st);
 // Same op forms as torch's single-tensor Adam: exp_avg.lerp_(g, 1-b1); exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2);
 // denom = sqrt(v)/sqrt(bc2) + eps; p.addcdiv_(m, denom, -lr/bc1).  The scalar constants are formed in double
 // on the host and rounded to fp32 once, as torch does when it multiplies a fp32 tensor by a Python float.
-struct AdamConsts { float w1, b2, w2, step_size, bc2_sqrt, eps, tau, one_minus_tau, gscale; };
+// beta1 = 0.9, beta2 = 0.999, eps = 1e-8 (torch's defaults, what every caller uses) are constants of the element functions.
+struct AdamConsts { float step_size, bc2_sqrt, tau, one_minus_tau, gscale; };
+constexpr float ADAM_W1 = (float)(1.0 - 0.9), ADAM_B2 = (float)0.999, ADAM_W2 = (float)(1.0 - 0.999), ADAM_EPS = 1e-8f;
 
 // W2[k][n] = w -> its terms in the planes of W2 (as B[k][n]) and of W2^T (as B[n][k]) of a member's T blob: the three bf16
 // terms (precision modes 0-3 share them), or -- precision 4, "f16x2" -- the two fp16 terms of w * 2^F16_WSHIFT in planes 0, 1
@@ -153,7 +156,19 @@ struct AdamTarget {
   long long* bump;                          // k_grad_reduce only: device word incremented by one thread (not t_dev), or null
   int precision;                            // format of the W2 planes kept in blob_T / target_T (write_w2_planes); < 0: no planes
                                             // (dynamics pre-training runs exact fp32: six scattered 2-byte stores per W2 element saved)
+  int* health;                              // health words of the device or null; this launch's tag and host step count
+  int health_tag, t_host;
 };
+__device__ __forceinline__ int adam_step_count(const AdamTarget& a) { return a.t_dev != nullptr ? (int)a.t_dev[0] : a.t_host; }
+
+// after an element's update: a non-finite parameter in any mode, an online / target W2 value past the fp16 planes' range
+__device__ __forceinline__ void health_after_update(const AdamTarget& a, float pj, bool w2_plane, float tj, bool w2t_plane) {
+  if (a.health == nullptr) return;
+  int bits = 0;
+  if (!(fabsf(pj) < INFINITY)) bits |= MOBODY_HEALTH_NONFINITE;
+  if (a.precision == 4 && ((w2_plane && !(fabsf(pj) < F16_W_LIMIT)) || (w2t_plane && !(fabsf(tj) < F16_W_LIMIT)))) bits |= MOBODY_HEALTH_F16_RANGE;
+  if (bits != 0) health_flag(a.health, bits, a.health_tag, adam_step_count(a));
+}
 
 // Bias corrections of a device-side step count (graph replay), formed ONCE per workgroup in double: thread 0 computes,
 // everybody reads after the barrier.  (Every thread evaluating two double pow() per element made the fused
@@ -169,8 +184,22 @@ __device__ __forceinline__ void adam_block_consts(const AdamTarget& a, float* sm
   }
 }
 
+// The health mask as an optimizer kernel reads it on entry: a uniform load (one scalar load per wave, no barrier, no LDS --
+// a per-workgroup read behind a barrier put a memory round trip in front of every workgroup's first loads and cost 3 % of
+// the c2 step and 27 % of the pre-training step).  The element functions test it only in front of their stores,
+// so the load overlaps their own loads.  A stale 0 can only be seen inside the faulting launch, where 0 is the right answer.
+__device__ __forceinline__ int health_mask(const AdamTarget& a) { return a.health != nullptr ? a.health[0] : 0; }
+// mask != 0: was the fault raised by ANOTHER launch?  (slow path: acquire fence, then the key the faulting lane published)
+__device__ __forceinline__ bool health_foreign(const AdamTarget& a) {
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  const unsigned long long key = __atomic_load_n(reinterpret_cast<const unsigned long long*>(a.health + 2), __ATOMIC_RELAXED);
+  // (a host-count launch has a tag of its own; a captured one shares its tag with its replays and differs in the step count)
+  return !((int)(key >> 32) == a.health_tag && (a.t_dev == nullptr || (int)(unsigned)key == (int)a.t_dev[0]));
+}
+
+// hmask: health_mask(a) of the launch; when an earlier launch has raised a fault nothing is stored
 __device__ __forceinline__ void adam_element(const AdamTarget& a, const MobodyMlpLayout& L, long long j, float g,
-                                             const float* sm2 = nullptr) {
+                                             const float* sm2 = nullptr, int hmask = 0) {
   AdamConsts c = a.c;
   if (a.t_dev != nullptr) {                         // graph replay: the step count lives in device memory
     if (sm2 != nullptr) {
@@ -183,10 +212,11 @@ __device__ __forceinline__ void adam_element(const AdamTarget& a, const MobodyMl
   }
   const float gj = g * c.gscale;
   const float m0 = a.m[j];
-  const float mj = m0 + c.w1 * (gj - m0);
-  const float vj = c.b2 * a.v[j] + c.w2 * (gj * gj);
+  const float mj = m0 + ADAM_W1 * (gj - m0);
+  const float vj = ADAM_B2 * a.v[j] + ADAM_W2 * (gj * gj);
+  const float pj = a.p[j] - c.step_size * (mj / (sqrtf(vj) / c.bc2_sqrt + ADAM_EPS));
+  if (hmask != 0 && health_foreign(a)) return;
   a.m[j] = mj; a.v[j] = vj;
-  const float pj = a.p[j] - c.step_size * (mj / (sqrtf(vj) / c.bc2_sqrt + c.eps));
   a.p[j] = pj;
   float tj = 0.f;
   if (a.target != nullptr) { tj = c.tau * pj + c.one_minus_tau * a.target[j]; a.target[j] = tj; }      // update_target :183-187
@@ -200,8 +230,11 @@ __device__ __forceinline__ void adam_element(const AdamTarget& a, const MobodyMl
       const int k = (int)(g / HID) * 4 + (int)(oo & 3), n = (int)(g % HID);
       if (a.blob_T != nullptr) write_w2_planes(a.blob_T + (long long)mem * L.t_member_floats, L, k, n, pj, a.precision);
       if (a.target_T != nullptr && a.target != nullptr) write_w2_planes(a.target_T + (long long)mem * L.t_member_floats, L, k, n, tj, a.precision);
+      health_after_update(a, pj, a.blob_T != nullptr, tj, a.target_T != nullptr && a.target != nullptr);
+      return;
     }
   }
+  health_after_update(a, pj, false, 0.f, false);
 }
 
 int launch_adam(const AdamTarget& a, const float* g, const MobodyMlpLayout& L, hipStream_t st);      // k_adam over one packed MLP

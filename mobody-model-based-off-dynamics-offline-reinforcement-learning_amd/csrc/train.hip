@@ -151,7 +151,9 @@ __global__ __launch_bounds__(256) void k_adam(AdamTarget a, const float* g, long
   __shared__ float adam_sm[2];
   adam_block_consts(a, adam_sm);
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
+  // (tested on entry here, not in front of the stores as in the fused kernels: this launch is off the step's critical chain,
+  //  and the early form keeps the kernel at 8 waves per SIMD -- 97 scalar registers against 103)
+  if (j >= n || (health_mask(a) != 0 && health_foreign(a))) return;
   adam_element(a, L, j, g[j], adam_sm);
 }
 
@@ -163,7 +165,7 @@ int launch_adam(const AdamTarget& a, const float* g, const MobodyMlpLayout& L, h
 
 // W1 and W2 (and W3T, W2T of the T blob) are 256 columns wide and stored K-interleaved (tile.h wide_idx);
 // W3 and W1T are narrow and row major.
-__global__ __launch_bounds__(256) void k_mlp_transpose(MobodyMlpLayout L, const float* blob, float* bt, int precision) {
+__global__ __launch_bounds__(256) void k_mlp_transpose(MobodyMlpLayout L, const float* blob, float* bt, int precision, int* health) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= L.t_total_floats) return;
   const int m = (int)(j / L.t_member_floats);
@@ -172,10 +174,12 @@ __global__ __launch_bounds__(256) void k_mlp_transpose(MobodyMlpLayout L, const 
   if (o >= L.w2p) {                                // bf16 planes of W2 / W2^T: one thread per float slot writes nothing here;
     if (o >= L.w2p + HID * HID) return;            // the first 65536 threads of the region each split one weight
     const int e = (int)(o - L.w2p), k = e / HID, n = e % HID;
-    write_w2_planes(bt + (long long)m * L.t_member_floats, L, k, n, src[L.w2 + wide_idx(k, n)], precision);
+    const float w = src[L.w2 + wide_idx(k, n)];
+    write_w2_planes(bt + (long long)m * L.t_member_floats, L, k, n, w, precision);
     if (precision == 4) {                          // the unused third plane slot: defined contents (a rebuilt T blob compares equal)
       short* tm = reinterpret_cast<short*>(bt + (long long)m * L.t_member_floats);
       tm[2 * L.w2p + bf_plane_idx(2, k, n)] = 0; tm[2 * L.w2tp + bf_plane_idx(2, n, k)] = 0;
+      health_check_f16(health, w);
     }
     return;
   }
@@ -483,7 +487,7 @@ extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const 
   MB_REQUIRE(blob && blob_T, "mobody_mlp_transpose: null pointer");
   MB_REQUIRE(precision >= 0 && precision <= 4, "mobody_mlp_transpose: precision must be 0..4");
   hipLaunchKernelGGL(k_mlp_transpose, dim3((unsigned)cdiv(L.t_total_floats, 256)), dim3(256), 0, as_stream(stream), L, blob, blob_T,
-                     precision);
+                     precision, health_words());
   MB_LAUNCH_OK("k_mlp_transpose");
   return 0;
 }
@@ -496,10 +500,10 @@ static AdamTarget adam_target(float* blob, float* blob_T, float* m, float* v, fl
   AdamTarget a{};
   a.p = blob; a.m = m; a.v = v; a.blob_T = blob_T;
   a.target = (target != nullptr && tau >= 0.f) ? target : nullptr;
-  a.c.w1 = (float)(1.0 - 0.9); a.c.b2 = (float)0.999; a.c.w2 = (float)(1.0 - 0.999);
-  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2); a.c.eps = 1e-8f;
+  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
   a.c.tau = tau; a.c.one_minus_tau = (float)(1.0 - (double)tau); a.c.gscale = grad_scale;
   a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1; a.precision = precision;
+  a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
   return a;
 }
 

@@ -66,6 +66,70 @@ def _check_f16_weights(blocks, what):
                          f"(|w| < 65504 / 2^8 = {F16_W_LIMIT}); use precision 'f32' or 'bf16x3'")
 
 
+# ------------------------------------------------------------------------------------------------
+# device health words (include/mobody_hip.h): f16x2 range faults and non-finite optimizer results
+# ------------------------------------------------------------------------------------------------
+F16_GUARDS = ("raise", "fallback", "off")
+_health_blocks = {}                 # device index -> the int32[HEALTH_WORDS] block bound there
+
+
+def check_f16_guard(value, distributed=False):
+    """Validate config['f16_guard'] ('raise' | 'fallback' | 'off'); needs no GPU.  'fallback' re-builds one replica's planes in
+    another mode, which data-parallel replicas cannot do independently: refused under a process group."""
+    if value not in F16_GUARDS:
+        raise ValueError(f"f16_guard {value!r}: expected one of {F16_GUARDS}")
+    if value == "fallback" and distributed:
+        raise ValueError("f16_guard='fallback' is not supported under a process group (replicas raise together under 'raise')")
+    return value
+
+
+def health_bind(words):
+    """Bind an int32[>= HEALTH_WORDS] device tensor as the current device's health words (None unbinds).  Launches enqueued
+    -- or captured -- afterwards report into it and freeze their optimizer steps once a bit is set."""
+    if words is not None:
+        assert words.dtype == torch.int32 and words.is_cuda and words.is_contiguous() and words.numel() >= _lib.HEALTH_WORDS
+        with torch.cuda.device(words.device):
+            check(load().mobody_health_bind(ptr(words)), "mobody_health_bind")
+        _health_blocks[words.device.index] = words
+    else:
+        check(load().mobody_health_bind(None), "mobody_health_bind")
+        _health_blocks.pop(torch.cuda.current_device(), None)
+
+
+def health_block(device):
+    """The block bound on `device`, allocated (zeroed) and bound on first use: one per device, shared by every object there."""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _health_blocks:
+        health_bind(torch.zeros(_lib.HEALTH_WORDS, dtype=torch.int32, device=torch.device("cuda", idx)))
+    return _health_blocks[idx]
+
+
+def health_bound(device=None):
+    """The block bound on `device` (default: the current one) through this module, or None."""
+    idx = torch.cuda.current_device() if device is None or torch.device(device).index is None else torch.device(device).index
+    return _health_blocks.get(idx)
+
+
+def health_clear():
+    """Zero the bound block on the current stream (updates apply again)."""
+    check(load().mobody_health_clear(cur_stream()), "mobody_health_clear")
+
+
+def health_read(words=None):
+    """(mask, step) of the bound block -- the fault bits and the Adam step count of the first faulting optimizer launch (0:
+    none recorded).  The only health call that synchronises."""
+    w = words if words is not None else _health_blocks.get(torch.cuda.current_device())
+    if w is None:
+        return 0, 0
+    h = w[:2].tolist()
+    return int(h[0]), int(h[1])
+
+
+def health_bits(mask):
+    return [n for n, b in (("F16_RANGE", _lib.HEALTH_F16_RANGE), ("NONFINITE", _lib.HEALTH_NONFINITE)) if mask & b]
+
+
 def _mlp_w2(blob, L, members):
     return blob[:members * L.member_floats].view(members, L.member_floats)[:, L.w2:L.w2 + 65536]
 

@@ -389,6 +389,7 @@ def _run(args, rank, world, device):
     if writer is not None:
         writer.close()
     torch.cuda.synchronize()
+    policy._health_check()                   # a fault after the last check point must not end the run silently
     return policy
 
 
