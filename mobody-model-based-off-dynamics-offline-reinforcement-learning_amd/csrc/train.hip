@@ -543,9 +543,11 @@ __global__ __launch_bounds__(256) void k_par_penalty(const float* ns_true, const
                                                      long long n, int S) {
   const long long row = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= n) return;
-  float s = 0.f;
-  for (int d = 0; d < S; ++d) { const float e = ns_true[row * S + d] - ns_model[row * S + d]; s += e * e; }
-  reward[row] -= coef * (s / (float)S);
+  // In double, rounded once: in fp32 the differences alone cost 2 u of the mean (u = 2^-24) before its S products and adds, and a
+  // row at S = 1 missed the (S + 2) u tests/test_hip_aux_rowwise.py holds it to.  The kernel streams 2 S floats per row: free.
+  double s = 0.0;
+  for (int d = 0; d < S; ++d) { const double e = (double)ns_true[row * S + d] - (double)ns_model[row * S + d]; s += e * e; }
+  reward[row] = (float)((double)reward[row] - (double)coef * (s / (double)S));
 }
 }  // namespace mobody
 
