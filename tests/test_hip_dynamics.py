@@ -138,7 +138,7 @@ def test_dyn_step_device_rng_mode(dev):
         close(got[k], want[k])
 
 
-@pytest.mark.parametrize("S,A", [(17, 6), (111, 8), (45, 24)])
+@pytest.mark.parametrize("S,A", [(17, 6), (111, 8), (45, 24), (11, 3)])
 def test_mlp3_forward_actor_and_twin_q(S, A, dev):
     from mobody_amd import ops, packing
     pa, pq, _ = gu.policy_params(401, S, A)

@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import actor_ref as AR
 import f64_bounds as fb
+from f64_bounds import e2e_bound, grad_bounds, net_weights, robust_rows
 import golden_util as gu
 from oracle import mobody_oracle as O
 
@@ -55,21 +57,6 @@ def rows_pattern(name, rng):
 
 FWD_PATTERNS = ["outlier", "tile_scales", "zero_tile", "dead_tile", "ragged_1", "ragged_31", "ragged_33", "ragged_65",
                 "ragged_4097"]
-
-
-def net_weights(p, pre):
-    return [(p[pre + f"network.{i}.weight"].T.astype(np.float64), p[pre + f"network.{i}.bias"].astype(np.float64)) for i in (0, 2, 4)]
-
-
-def e2e_bound(x, layers, c, split_mode, pad1, lip=1.0, act=lambda z: np.maximum(z, 0.0), E0=None):
-    """fp64 forward of a 3-layer net and a bound on the error of its pre-output, propagated layer by layer:
-    E_l = lip |W_l|^T E_(l-1) + c (|h||W_l| + |b_l|) (+ subnormal floor of the split layer 2); E0: error of the input."""
-    h, E = fb.f64(x), (0.0 if E0 is None else E0)
-    for li, (W, b) in enumerate(layers):
-        z, bnd = fb.layer_bound(h, W, b, c, split=split_mode and li == 1, pad=pad1 if li == 1 else 0.0)
-        E = (lip if li else 1.0) * (E @ np.abs(W) if (li or E0 is not None) else 0.0) + bnd
-        h = act(z) if li < 2 else z
-    return h, E
 
 
 @pytest.mark.parametrize("pattern", FWD_PATTERNS)
@@ -269,62 +256,6 @@ def test_plane_builders_refuse_weights_fp16_cannot_hold(dev):
 
 
 # ---- critic / actor gradients of Engine.step -----------------------------------------------------------------------------
-def grad_bounds(tape, c, split, which, edz3=None, ex=None):
-    """Per-element bounds of every gradient tensor of the nets whose layers were recorded under the prefix `which` (nn.Linear
-    layout): c (sum_calls |dz|^T |x| + the error the split GEMM dz_(l+1) W_(l+1)^T passes into dz_l) + the floors of the
-    plane-fed layer-2 weight gradient (+ |x|^T Edz, edz3 = a bound on the error of the output gradient that the forward's
-    error carries in: a TD error q - y far below |q| amplifies it; + |dz|^T Ex, ex = the forward error of each layer's input,
-    which a large dz amplifies where the input itself is small)."""
-    out = {}
-    E = {4: edz3}
-    if edz3 is not None:
-        for i in (2, 0):
-            W = tape["_W"][which + f"network.{i + 2}.weight"]
-            E[i] = (E[i + 2] @ np.abs(W)) * (fb.f64(tape[which + f"network.{i}"][0]["z"]) > 0)
-    for i in (0, 2, 4):
-        name = which + f"network.{i}"
-        recs = tape[name]
-        gW = sum(np.abs(fb.f64(r["dz"])).T @ np.abs(fb.f64(r["x"])) for r in recs)
-        gb = sum(np.abs(fb.f64(r["dz"])).sum(0) for r in recs)
-        if i < 4:                                              # dz_l = (dz_(l+1) W_(l+1)^T) [z_l > 0] carries c |dz_(l+1)| |W_(l+1)|
-            W = tape["_W"][which + f"network.{i + 2}.weight"]
-            for r, rn in zip(recs, tape[which + f"network.{i + 2}"]):
-                prop = (np.abs(fb.f64(rn["dz"])) @ np.abs(W)) * (fb.f64(r["z"]) > 0)
-                gW = gW + prop.T @ np.abs(fb.f64(r["x"]))
-                gb = gb + prop.sum(0)
-        bW, bb = c * gW, c * gb
-        if edz3 is not None:
-            bW = bW + E[i].T @ np.abs(fb.f64(recs[0]["x"]))
-            bb = bb + E[i].sum(0)
-        if ex is not None and i in ex:
-            bW = bW + (np.abs(fb.f64(recs[0]["dz"])) + (E[i] if edz3 is not None else 0.0)).T @ ex[i]
-        if split and i == 2:
-            bW = bW + sum(fb.wgrad_floor(r["x"], r["dz"]).T for r in recs)
-        out[name + ".weight"], out[name + ".bias"] = bW, bb
-    return out
-
-
-def robust_rows(pa, pq, s, a, thr=2.0 ** -18):
-    """Rows whose fp64 hidden pre-activations (both Q nets at (s, a) and (s, pi(s)), the actor at s) all keep |z| above thr of
-    their own rounding scale |W||h| + |b|: a ReLU mask there cannot flip under the kernels' error."""
-    ok = np.ones(len(s), bool)
-
-    def scan(layers, x):
-        nonlocal ok
-        h = x
-        for (W, b) in layers[:2]:
-            z = h @ W + b
-            ok &= (np.abs(z) >= thr * (np.abs(h) @ np.abs(W) + np.abs(b))).all(1)
-            h = np.maximum(z, 0)
-        return h @ layers[2][0] + layers[2][1]
-    s64, a64 = s.astype(np.float64), a.astype(np.float64)
-    pi = np.tanh(scan(net_weights(pa, "network."), s64))
-    for pre in ("network1.", "network2."):
-        scan(net_weights(pq, pre), np.concatenate([s64, a64], 1))
-        scan(net_weights(pq, pre), np.concatenate([s64, pi], 1))
-    return ok
-
-
 def engine_grads_check(mode, pa, pq, batch, n_true, dev):
     from mobody_amd.engine import Engine
     cfg = gu.policy_cfg(S, A, mfma=mode)
@@ -358,6 +289,17 @@ def engine_grads_check(mode, pa, pq, batch, n_true, dev):
         bd = grad_bounds(tape, fb.C_E2E, split, pre, edz3=2.0 / N * (Eq + Ey), ex={2: e1, 4: e1 @ np.abs(W2) + e2})
         for k, v in bd.items():
             fb.check(got_q[k], want["q_grads"][k], v, f"{mode} critic {k}")
+    # the actor half: eng.ga against the same fp64 step with the derived bound of tests/actor_ref.py (apply=False: the critic the
+    # actor phase sees is the one the step started with)
+    h = dict(cfg, advantage=0)
+    fw = AR.forward_ref(pa, pq, batch[0], batch[1], n_true, cfg["max_action"])
+    cf = AR.closed_forms(fw["pi"], fw["qp"], fw["qb"], fw["dqda"], batch[1], h, N, n_true, N, n_true)
+    ref_a, tape_a = AR.actor_grads_ref(pa, batch[0], fw, cf["dz3"])
+    bd = AR.actor_bounds(pa, pq, batch[0], batch[1], h, N, n_true, N, n_true, fw, cf, tape_a, split)
+    got_a = eng.unpack(eng.ga, "actor")
+    for k, v in want["actor_grads"].items():
+        np.testing.assert_allclose(ref_a[k], fb.f64(v), rtol=1e-9, atol=1e-9 * np.abs(fb.f64(v)).max(), err_msg=k)   # one reference
+        fb.check(got_a[k], v, bd["grads"][k], f"{mode} actor {k}")
     return got_q, want
 
 

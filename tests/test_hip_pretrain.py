@@ -366,7 +366,7 @@ def test_mirror_dynamics_train_together_vs_reference_golden(dev, mfma):
     assert sorted(int(x) for x in m.elites.tolist()) == sorted(int(x) for x in g["elites"])
 
 
-@pytest.mark.parametrize("S,A,b", [(17, 6, 1), (17, 6, 33), (17, 6, 256), (111, 8, 40), (45, 24, 65)])
+@pytest.mark.parametrize("S,A,b", [(17, 6, 1), (17, 6, 33), (17, 6, 256), (111, 8, 40), (45, 24, 65), (11, 3, 40)])
 def test_pretrain_grads_vs_oracle_shapes(S, A, b, dev, mfma):
     """Ragged / full batches and the ant / pen shapes against the oracle's autograd (same noise), source and target step."""
     p = gu.gi.dyn_params(5, S, A)

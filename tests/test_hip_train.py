@@ -70,7 +70,7 @@ def test_train_step_vs_reference_golden(tag, mfma, dev):
                 params_close(gu.sub(v.cpu().numpy()), g[f"s{step}_{nm}_p::{k}"], cfg["critic_lr"])
 
 
-@pytest.mark.parametrize("S,A,N,Nt", [(17, 6, 640, 512), (17, 6, 333, 200), (111, 8, 192, 128), (45, 24, 130, 65)])
+@pytest.mark.parametrize("S,A,N,Nt", [(17, 6, 640, 512), (17, 6, 333, 200), (111, 8, 192, 128), (45, 24, 130, 65), (11, 3, 130, 65)])
 def test_train_step_vs_oracle_shapes(S, A, N, Nt, mfma, dev):
     cfg = gu.policy_cfg(S, A)
     pa, pq, pv = gu.policy_params(77, S, A)
