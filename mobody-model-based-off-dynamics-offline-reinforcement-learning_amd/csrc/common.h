@@ -24,6 +24,25 @@ int fail(int code, const char* fmt, ...);
     if (e_ != hipSuccess) return ::mobody::fail(MOBODY_E_LAUNCH, "%s: %s", what, hipGetErrorString(e_)); \
   } while (0)
 
+// Precision ids of the C ABI (MobodyHyper.precision and the `precision` arguments; names as _lib.PRECISIONS).  Host code
+// compares against these; the kernels' template arguments PM / NPL carry the same numbers.
+enum Precision { PREC_F32 = 0, PREC_BF16 = 1, PREC_BF16X2 = 2, PREC_BF16X3 = 3, PREC_F16X2 = 4 };
+constexpr unsigned PREC_ALL = 0x1f, PREC_F32_OR_F16X2 = 1u << PREC_F32 | 1u << PREC_F16X2;   // `allowed` sets of check_precision
+
+// The one range check of a precision argument: a known id, one of `allowed` (bit k = id k), and -- for every id but f32 --
+// the 16-bit weight planes the split-precision kernels stream (T blobs / the ensemble's plane blob).
+inline int check_precision(const char* who, int precision, bool have_planes, unsigned allowed = PREC_ALL) {
+  static const char* const names[] = {"0 (f32)", "1 (bf16)", "2 (bf16x2)", "3 (bf16x3)", "4 (f16x2)"};
+  if (precision < PREC_F32 || precision > PREC_F16X2 || !((allowed >> precision) & 1)) {
+    std::string list;
+    for (int k = PREC_F32; k <= PREC_F16X2; ++k)
+      if ((allowed >> k) & 1) list += (list.empty() ? "" : ", ") + std::string(names[k]);
+    return fail(MOBODY_E_ARG, "%s: precision %d: must be one of %s", who, precision, list.c_str());
+  }
+  MB_REQUIRE(precision == PREC_F32 || have_planes, "%s: the split-precision modes need the T blobs / plane blob (16-bit planes) of every net", who);
+  return 0;
+}
+
 constexpr size_t TILE_LDS_BYTES = (size_t)BM * LDX * sizeof(float);   // 66,560 B: one activation image
 
 // Opt a kernel into > 64 KiB of dynamic LDS once per process.

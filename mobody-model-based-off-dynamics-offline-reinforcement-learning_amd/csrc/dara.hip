@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void k_dara_penalty(const float* z_sas, const 
 }
 
 // ---- generic MLP gradient (dz3 + saved activations -> gradient blob) ----
-struct BwdWs { float *dz2, *dz1, *dbp, *slabs; long long slab_stride, total; int nsplit, ntiles; };
+struct BwdWs { float *dz2, *dz1, *dbp, *slabs; long long total; int nsplit, ntiles; };
 
 static void carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, BwdWs& w) {
   long long off = 0;
@@ -139,8 +139,7 @@ static void carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, Bwd
   w.ntiles = (int)cdiv(rows, MLP_TILE_ROWS);
   w.nsplit = wgrad_nsplit(rows, L.members);
   w.dbp = take((long long)w.ntiles * L.members * (2 * HID + L.Np3));
-  w.slab_stride = (L.total_floats + 3) & ~3LL;
-  w.slabs = take(w.slab_stride * w.nsplit);
+  w.slabs = take(((L.total_floats + 3) & ~3LL) * w.nsplit);
   w.total = off;
 }
 
@@ -166,23 +165,13 @@ extern "C" int mobody_mlp3_backward(const float* blob_T, int in_dim, int out_dim
   BwdWs w;
   carve_bwd(L, rows, workspace, w);
   hipStream_t st = as_stream(stream);
-  Mlp3BwdArgs b{};
-  b.dz3 = dz3; b.h1 = h1; b.h2 = h2; b.wt = blob_T; b.t_mstride = L.t_member_floats;
-  b.w3t = L.w3t; b.w2t = L.w2t; b.w1t = L.w1t; b.Np3 = L.Np3; b.Np1t = L.Np1t; b.rows = rows;
-  b.dz2 = w.dz2; b.dz1 = w.dz1; b.dbp = w.dbp;
+  Mlp3BwdArgs b = bwd_net(L, blob_T, rows);       // exact fp32 on the saved activations: no planes, no sign words
+  bwd_set_acts(b, h1, h2, nullptr, nullptr, 0);
+  bwd_set_grads(b, dz3, w.dz2, w.dz1, w.dbp);
   rc = launch_mlp3_bwd(b, members, false, st);
   if (rc) return rc;
-  WgradArgs g{};
-  g.rows = rows; g.slabs = w.slabs; g.slab_stride = w.slab_stride; g.out_mstride = L.member_floats;
-  g.nsplit = w.nsplit; g.members = L.members;
-  const long long hs = rows * HID;
-  g.job[0] = WgradJob{h1, hs, HID, HID, w.dz2, hs, HID, HID, L.w2, HID, HID, HID, 0, 1, 0, 0};
-  g.job[1] = WgradJob{x, 0, L.Kp1, L.Kp1, w.dz1, hs, HID, HID, L.w1, HID, L.Kp1, HID, 0, 1, 0, 0};
-  g.job[2] = WgradJob{dz3, rows * L.Np3, L.Np3, L.Np3, h2, hs, HID, HID, L.w3, L.Np3, L.Np3, HID, 1, 0, 0, 0};
-  rc = launch_wgrad(g, st);
-  if (rc) return rc;
-  GradReduceArgs r{L, w.slabs, w.slab_stride, w.nsplit, w.dbp, w.ntiles, grad};
-  return launch_grad_reduce(r, st);
+  return mlp3_weight_grads(L, x, 0, h1, h2, dz3, w.dz2, w.dz1, rows, w.nsplit, w.slabs, w.dbp, w.ntiles, grad, LossFinal{},
+                           AdamTarget{}, st);
 }
 
 extern "C" int mobody_dara_inputs(const float* s, const float* a, const float* s2, int64_t N, int S, int A, float std,

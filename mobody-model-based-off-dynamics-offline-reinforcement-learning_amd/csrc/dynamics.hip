@@ -33,10 +33,6 @@ struct DynFwdArgs {
   const unsigned short* planes;   // split-precision modes: 16-bit planes of zs2 | transition2 | reward_model2 (dyn_planes_off)
 };
 
-// bf16 planes of the three 256 x 256 ensemble layers: [layer 0..2 = zs2, transition2, reward_model2][member][3 planes][65536]
-constexpr long long DYN_PLANE_MEMBER = 3LL * HID * HID;                       // bf16 elements per (layer, member)
-__host__ __device__ inline long long dyn_planes_off(int layer, int member) { return ((long long)layer * NENS + member) * DYN_PLANE_MEMBER; }
-
 // NT3: 16-column tiles of the transition head handled by the K-split narrow layer (Np == 16*NT3: 1, 2, 3 or 7), 0 = any width
 // (row-split narrow_layer: half of the waves idle on a 32-row tile).
 // PM: 0 = exact fp32 MFMA; 1..4 = the two 256 x 256 layers (zs2, transition2) on the split-precision core (tile_bf.h).
@@ -331,12 +327,12 @@ static int launch_dyn_fwd(const float* blob, const MobodyDynLayout& L, const flo
   // half of the waves (measured 102 vs 88 TFLOP/s at 50 000 rows).
   const int np = L.layer[MOBODY_DL_TR3].Np;
   const int nt3 = np == 16 ? 1 : np == 32 ? 2 : np == 48 ? 3 : np == 112 ? 7 : 0;      // walker/hopper/cheetah, pen, ant heads; else generic
-  if (prec == 0) return launch_dyn_fwd_nt<2, 0>(a, nt3, st);
+  if (prec == PREC_F32) return launch_dyn_fwd_nt<2, 0>(a, nt3, st);
   // split-precision modes: the planes of a 64-row tile are 32 / 64 / 96 KB for 1 / 2 / 3 terms -> the three-term mode
   // runs 32-row tiles (MT = 1: 48 KB, three workgroups per CU), the others 64-row tiles
-  if (prec == 1) return launch_dyn_fwd_nt<2, 1>(a, nt3, st);
-  if (prec == 2) return launch_dyn_fwd_nt<2, 2>(a, nt3, st);
-  if (prec == 4) return launch_dyn_fwd_nt<2, 4>(a, nt3, st);
+  if (prec == PREC_BF16) return launch_dyn_fwd_nt<2, 1>(a, nt3, st);
+  if (prec == PREC_BF16X2) return launch_dyn_fwd_nt<2, 2>(a, nt3, st);
+  if (prec == PREC_F16X2) return launch_dyn_fwd_nt<2, 4>(a, nt3, st);
   return launch_dyn_fwd_nt<1, 3>(a, nt3, st);
 }
 
@@ -376,16 +372,11 @@ extern "C" int mobody_dyn_planes(const float* dyn_blob, int S, int A, float* pla
   int rc = mobody_dyn_layout(S, A, &L);
   if (rc) return rc;
   MB_REQUIRE(dyn_blob && planes, "mobody_dyn_planes: null pointer");
-  MB_REQUIRE(precision >= 0 && precision <= 4, "mobody_dyn_planes: precision must be 0..4");
+  rc = check_precision("mobody_dyn_planes", precision, true);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_dyn_planes, dim3((unsigned)cdiv(3LL * NENS * HID * HID, 256)), dim3(256), 0, as_stream(stream), dyn_blob, L,
                      reinterpret_cast<short*>(planes), precision, health_words());
   MB_LAUNCH_OK("k_dyn_planes");
-  return 0;
-}
-
-static int check_dyn_prec(const char* who, int precision, const float* planes) {
-  MB_REQUIRE(precision >= 0 && precision <= 4, "%s: precision must be 0 (f32), 1 (bf16), 2 (bf16x2), 3 (bf16x3) or 4 (f16x2)", who);
-  MB_REQUIRE(precision == 0 || planes, "%s: the split-precision modes need the plane blob (mobody_dyn_planes)", who);
   return 0;
 }
 
@@ -397,7 +388,7 @@ extern "C" int mobody_dyn_forward(const float* dyn_blob, const float* dyn_planes
   MB_REQUIRE(B >= 0, "mobody_dyn_forward: B < 0");
   if (B == 0) return 0;                      // empty batch: nothing to do (pointers may be null)
   MB_REQUIRE(dyn_blob && obs && act && mean, "mobody_dyn_forward: null pointer");
-  rc = check_dyn_prec("mobody_dyn_forward", precision, dyn_planes);
+  rc = check_precision("mobody_dyn_forward", precision, dyn_planes != nullptr);
   if (rc) return rc;
   return launch_dyn_fwd(dyn_blob, L, obs, act, B, use_trg, mean, dyn_planes, precision, as_stream(stream));
 }
@@ -431,30 +422,19 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
   hipStream_t st = as_stream(stream);
   float* mean = a.mean_out ? a.mean_out : a.workspace;
   float* r_mu = a.workspace + (int64_t)NENS * B * S;
-  rc = check_dyn_prec(who, precision, a.dyn_planes);
+  rc = check_precision(who, precision, a.dyn_planes != nullptr);
   if (rc) return rc;
   if (a.mopo_blob != nullptr) {
     MobodyMlpLayout ML;
     rc = mobody_mlp_layout(S + A, S, NENS, &ML);
     if (rc) return rc;
-    MB_REQUIRE(precision == 0 || a.mopo_blob_T != nullptr, "%s: the split-precision modes need the T blob of the MLP", who);
-    Mlp3FwdArgs f{};
-    f.src[0] = a.obs; f.ld[0] = S; f.n[0] = S;
-    f.src[1] = a.act; f.ld[1] = A; f.n[1] = A;
-    f.w1 = a.mopo_blob + ML.w1; f.b1 = a.mopo_blob + ML.b1; f.w2 = a.mopo_blob + ML.w2; f.b2 = a.mopo_blob + ML.b2;
-    f.w3 = a.mopo_blob + ML.w3; f.b3 = a.mopo_blob + ML.b3;
-    f.sw1 = f.sb1 = f.sw2 = f.sb2 = f.sw3 = f.sb3 = ML.member_floats;
-    f.Kp1 = ML.Kp1; f.Np3 = ML.Np3; f.nout = S; f.rows = B;
-    f.out = mean; f.out_mstride = B * S; f.out_ld = S;
-    f.out_mode = 0; f.max_action = 1.f;
-    f.resid = a.obs; f.resid_ld = S;
-    if (precision == 0) {
-      rc = launch_mlp3_fwd(f, NENS, ACT_SWISH, st);
-    } else {
-      f.w2_planes = reinterpret_cast<const unsigned short*>(a.mopo_blob_T + ML.w2p);
-      f.planes_ms = 2 * ML.t_member_floats;
-      rc = launch_mlp3_fwd_bf(f, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, precision, st);
-    }
+    MB_REQUIRE(precision == PREC_F32 || a.mopo_blob_T != nullptr, "%s: the split-precision modes need the T blob of the MLP", who);
+    Mlp3FwdArgs f = fwd_net(a.mopo_blob, ML, B);
+    fwd_set_src(f, 0, a.obs, S, S);
+    fwd_set_src(f, 1, a.act, A, A);
+    fwd_set_out(f, mean, 0, 1.f, a.obs, S);
+    if (precision != PREC_F32) fwd_set_planes(f, a.mopo_blob_T, ML);
+    rc = launch_mlp3_forward(f, NENS, ACT_SWISH, precision, st);
   } else {
     rc = launch_dyn_fwd(a.dyn_blob, L, a.obs, a.act, B, a.use_trg, mean, a.dyn_planes, precision, st);
   }
@@ -474,25 +454,12 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
   MB_LAUNCH_OK("k_dyn_sample");
 
   // reward head on [s, a, s'] shared by the 7 members  (mobody_dynamics.py:235)
-  const float* dyn_blob = a.dyn_blob;
-  Mlp3FwdArgs m{};
-  m.src[0] = a.obs; m.ld[0] = S; m.n[0] = S;
-  m.src[1] = a.act; m.ld[1] = A; m.n[1] = A;
-  m.src[2] = a.next_obs; m.ld[2] = S; m.n[2] = S;
-  const MobodyLayer &l1 = L.layer[MOBODY_DL_RW1], &l2 = L.layer[MOBODY_DL_RW2], &l3 = L.layer[MOBODY_DL_RW3];
-  m.w1 = dyn_blob + l1.w_off; m.b1 = dyn_blob + l1.b_off; m.sw1 = (long long)l1.Kp * l1.Np; m.sb1 = l1.Np;
-  m.w2 = dyn_blob + l2.w_off; m.b2 = dyn_blob + l2.b_off; m.sw2 = (long long)l2.Kp * l2.Np; m.sb2 = l2.Np;
-  m.w3 = dyn_blob + l3.w_off; m.b3 = dyn_blob + l3.b_off; m.sw3 = (long long)l3.Kp * l3.Np; m.sb3 = l3.Np;
-  m.Kp1 = l1.Kp; m.Np3 = l3.Np; m.nout = 1; m.rows = B;
-  m.out = r_mu; m.out_mstride = B; m.out_ld = 1;
-  m.out_mode = 0; m.max_action = 1.f;
-  if (precision == 0) {
-    rc = launch_mlp3_fwd(m, NENS, ACT_SWISH, st);
-  } else {
-    m.w2_planes = reinterpret_cast<const unsigned short*>(a.dyn_planes) + dyn_planes_off(2, 0);
-    m.planes_ms = DYN_PLANE_MEMBER;
-    rc = launch_mlp3_fwd_bf(m, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, precision, st);
-  }
+  Mlp3FwdArgs m = fwd_reward_head(a.dyn_blob, L, precision != PREC_F32 ? a.dyn_planes : nullptr, B);
+  fwd_set_src(m, 0, a.obs, S, S);
+  fwd_set_src(m, 1, a.act, A, A);
+  fwd_set_src(m, 2, a.next_obs, S, S);
+  fwd_set_out(m, r_mu, 0, 1.f);
+  rc = launch_mlp3_forward(m, NENS, ACT_SWISH, precision, st);
   if (rc) return rc;
 
   DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
@@ -580,8 +547,11 @@ static int rollout_impl(const char* who, const MobodyEnsRollout& a, void* stream
   const MobodyBufferView* ring = a.ring;
   MB_REQUIRE(a.dyn_blob && a.actor_blob && a.init_obs && a.elites && ring && ring->state && ring->action && ring->next_state && ring->reward &&
                  ring->not_done && a.ptr_size && a.workspace, "%s: null pointer", who);
+  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
+  if (rc) return rc;
+  MB_REQUIRE(precision == PREC_F32 || a.actor_blob_T, "%s: the split-precision modes need the actor's T blob", who);
   MobodyMlpLayout La;
-  int rc = mobody_mlp_layout(S, A, 1, &La);
+  rc = mobody_mlp_layout(S, A, 1, &La);
   if (rc) return rc;
   RolloutWs w;
   rollout_carve(S, A, B, a.workspace, w);
@@ -592,21 +562,11 @@ static int rollout_impl(const char* who, const MobodyEnsRollout& a, void* stream
   for (int t = 0; t < a.H; ++t) {
     float* nxt = w.obs[t & 1];
     // a = pi(s)  (select_action, mobody.py:612)
-    Mlp3FwdArgs p{};
-    p.src[0] = obs; p.ld[0] = S; p.n[0] = S;
-    p.w1 = a.actor_blob + La.w1; p.b1 = a.actor_blob + La.b1; p.w2 = a.actor_blob + La.w2; p.b2 = a.actor_blob + La.b2;
-    p.w3 = a.actor_blob + La.w3; p.b3 = a.actor_blob + La.b3;
-    p.sw1 = p.sb1 = p.sw2 = p.sb2 = p.sw3 = p.sb3 = La.member_floats;
-    p.Kp1 = La.Kp1; p.Np3 = La.Np3; p.nout = A; p.rows = B; p.out = w.act; p.out_mstride = B * A; p.out_ld = A;
-    p.out_mode = 1; p.max_action = a.max_action;
-    if (precision == 0) {
-      rc = launch_mlp3_fwd(p, 1, ACT_RELU, st);
-    } else {
-      MB_REQUIRE(a.actor_blob_T, "%s: the split-precision modes need the actor's T blob", who);
-      p.w2_planes = reinterpret_cast<const unsigned short*>(a.actor_blob_T + La.w2p);
-      p.planes_ms = 2 * La.t_member_floats;
-      rc = launch_mlp3_fwd_bf(p, 1, Mlp3FwdArgs{}, 0, ACT_RELU, precision, st);
-    }
+    Mlp3FwdArgs p = fwd_net(a.actor_blob, La, B);
+    fwd_set_src(p, 0, obs, S, S);
+    fwd_set_out(p, w.act, 1, a.max_action);
+    if (precision != PREC_F32) fwd_set_planes(p, a.actor_blob_T, La);
+    rc = launch_mlp3_forward(p, 1, ACT_RELU, precision, st);
     if (rc) return rc;
     // one imagined transition for every row; rows that terminated earlier keep their index and are flagged (alive mask);
     // the penalty filter and the alive update are formed in the sample kernel

@@ -9,6 +9,7 @@
 
 #include <type_traits>
 
+#include "../../include/mobody_hip.h"
 #include "tile.h"
 
 namespace mobody {
@@ -137,10 +138,75 @@ struct Mlp3FwdArgs {
   float max_action;
 };
 
-int launch_mlp3_fwd(const Mlp3FwdArgs& a, int members, int act, hipStream_t stream);
-int launch_mlp3_fwd_pair(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, hipStream_t stream);
-// split-precision forward (mlp_fwd_bf.hip): prec 1 bf16 / 2 bf16x2 / 3 bf16x3; needs a.w2_planes (and b.w2_planes)
-int launch_mlp3_fwd_bf(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st);
+// ---- host side: the one place an Mlp3FwdArgs is filled; each helper owns one group of fields ----
+// 16-bit planes of the three 256 x 256 ensemble layers (mobody_dyn_planes): [layer 0..2 = zs2, transition2, reward_model2][member]
+// [3 planes][65536]; elements per (layer, member) and the offset of one
+constexpr long long DYN_PLANE_MEMBER = 3LL * HID * HID;
+__host__ __device__ inline long long dyn_planes_off(int layer, int member) { return ((long long)layer * NENS + member) * DYN_PLANE_MEMBER; }
+
+// weights, member strides and dims of a packed MLP (mobody_mlp_layout) on `rows` rows; everything else zero
+inline Mlp3FwdArgs fwd_net(const float* blob, const MobodyMlpLayout& L, long long rows) {
+  Mlp3FwdArgs a{};
+  a.w1 = blob + L.w1; a.b1 = blob + L.b1; a.w2 = blob + L.w2; a.b2 = blob + L.b2; a.w3 = blob + L.w3; a.b3 = blob + L.b3;
+  a.sw1 = a.sb1 = a.sw2 = a.sb2 = a.sw3 = a.sb3 = L.member_floats;
+  a.Kp1 = L.Kp1; a.Np3 = L.Np3; a.nout = L.out_dim; a.rows = rows;
+  return a;
+}
+// W2's planes in the net's T blob (what the split-precision forward streams)
+inline void fwd_set_planes(Mlp3FwdArgs& a, const float* blob_T, const MobodyMlpLayout& L) {
+  a.w2_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2p);
+  a.planes_ms = 2 * L.t_member_floats;
+}
+// the ensemble's reward head (reward_model1-3 of the dynamics blob, one output); dyn_planes: the plane blob or null (exact fp32)
+inline Mlp3FwdArgs fwd_reward_head(const float* dyn_blob, const MobodyDynLayout& L, const float* dyn_planes, long long rows) {
+  Mlp3FwdArgs a{};
+  const MobodyLayer &l1 = L.layer[MOBODY_DL_RW1], &l2 = L.layer[MOBODY_DL_RW2], &l3 = L.layer[MOBODY_DL_RW3];
+  a.w1 = dyn_blob + l1.w_off; a.b1 = dyn_blob + l1.b_off; a.sw1 = (long long)l1.Kp * l1.Np; a.sb1 = l1.Np;
+  a.w2 = dyn_blob + l2.w_off; a.b2 = dyn_blob + l2.b_off; a.sw2 = (long long)l2.Kp * l2.Np; a.sb2 = l2.Np;
+  a.w3 = dyn_blob + l3.w_off; a.b3 = dyn_blob + l3.b_off; a.sw3 = (long long)l3.Kp * l3.Np; a.sb3 = l3.Np;
+  a.Kp1 = l1.Kp; a.Np3 = l3.Np; a.nout = 1; a.rows = rows;
+  if (dyn_planes != nullptr) {
+    a.w2_planes = reinterpret_cast<const unsigned short*>(dyn_planes) + dyn_planes_off(2, 0);
+    a.planes_ms = DYN_PLANE_MEMBER;
+  }
+  return a;
+}
+// input k: [rows][ld] of which n columns are read; ms = 0: shared by the members, else the member stride in floats
+inline void fwd_set_src(Mlp3FwdArgs& a, int k, const float* src, int ld, int n, long long ms = 0) {
+  a.src[k] = src; a.ld[k] = ld; a.n[k] = n; a.src_ms[k] = ms;
+}
+// dense output [members][rows][nout], optionally max_action * tanh (out_mode 1) and + resid[row][c]
+inline void fwd_set_out(Mlp3FwdArgs& a, float* out, int out_mode, float max_action, const float* resid = nullptr, int resid_ld = 0) {
+  a.out = out; a.out_mstride = a.rows * a.nout; a.out_ld = a.nout;
+  a.out_mode = out_mode; a.max_action = max_action; a.resid = resid; a.resid_ld = resid_ld;
+}
+// what the backward pass wants kept.  x_ms: 0 = x saved once by member 0, else per member.  e1 != null (f16x2) and h1: h1 leaves
+// as the two fp16 planes + tile exponents the weight-gradient GEMM reads, not as fp32 rows
+inline void fwd_set_saves(Mlp3FwdArgs& a, float* x, long long x_ms, float* h1, int* e1, float* h2, uint32_t* m1 = nullptr,
+                          uint32_t* m2 = nullptr, float* d1 = nullptr, float* d2 = nullptr) {
+  if (e1 != nullptr && h1 != nullptr) {
+    const long long r32 = (a.rows + 31) & ~31LL;
+    a.save_h1p = reinterpret_cast<unsigned short*>(h1); a.h1p_plane = r32 * HID; a.h1p_ms = 2 * r32 * HID; a.save_e1 = e1;
+    h1 = nullptr;
+  }
+  a.save_x = x; a.x_ms = x_ms; a.save_h1 = h1; a.save_h2 = h2; a.mask1 = m1; a.mask2 = m2; a.save_d1 = d1; a.save_d2 = d2;
+}
+
+// Output-layer width -> the NT of the kernel instantiations (16-column tiles of the K-split narrow layer; 0 = any width):
+// f(std::integral_constant<int, NT>)
+template <class F>
+inline int dispatch_out_width(int Np3, F&& f) {
+  return Np3 == 16 ? f(std::integral_constant<int, 1>{}) : Np3 == 32 ? f(std::integral_constant<int, 2>{})
+                                                                     : f(std::integral_constant<int, 0>{});
+}
+
+// THE forward launch: net a, optionally net b (members_b = 0: none; either may be empty, rows <= 0), activation `act`, precision id
+// (common.h).  It alone decides which kernel runs -- exact fp32 (mlp_fwd.hip), split precision (mlp_fwd_bf.hip), or the fp32
+// training forward of a Swish net with derivative saves (pretrain.hip) -- and whether two nets share a launch.
+int launch_mlp3_forward(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st);
+inline int launch_mlp3_forward(const Mlp3FwdArgs& a, int members, int act, int prec, hipStream_t st) {
+  return launch_mlp3_forward(a, members, Mlp3FwdArgs{}, 0, act, prec, st);
+}
 
 // Row-tile height of the fused 3-layer MLP kernels (forward and backward; the callers size the bias partials and the sign
 // words by it).  Measured on MI355X (bench.py, S=17/A=6): 32-row tiles (33 KB LDS, ~124 VGPRs -> 4 workgroups = 16 waves

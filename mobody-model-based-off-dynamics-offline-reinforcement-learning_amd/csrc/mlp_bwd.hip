@@ -359,7 +359,7 @@ static int launch_bwd_masks(const Mlp3BwdArgs& a, int members, bool with_dx, hip
 // Swish nets (the ensemble dynamics, pre-training): derivative multipliers in h1 / h2
 static int launch_bwd_swish(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (a.prec == 4 && a.w2t_planes != nullptr) {     // f16x2: the 256 x 256 GEMM on the split core, dz2 as planes for the weight gradients
+  if (a.prec == PREC_F16X2 && a.w2t_planes != nullptr) {     // f16x2: the 256 x 256 GEMM on the split core, dz2 as planes for the weight gradients
     if (!with_dx) return launch_bwd_t<false, 0, 2, 4>(a, members, st);
     return nt == 1 ? launch_bwd_t<true, 1, 2, 4>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2, 4>(a, members, st)
                                                                              : launch_bwd_t<true, 0, 2, 4>(a, members, st);
@@ -372,9 +372,9 @@ static int launch_bwd_swish(const Mlp3BwdArgs& a, int members, bool with_dx, hip
 int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
   if (a.rows <= 0) return 0;
   if (a.swish) return launch_bwd_swish(a, members, with_dx, st);
-  if (a.prec != 0 && a.w2t_planes != nullptr && a.m1 != nullptr && a.m2 != nullptr)
-    return a.prec == 1 ? launch_bwd_bf<1>(a, members, with_dx, st) : a.prec == 2 ? launch_bwd_bf<2>(a, members, with_dx, st)
-         : a.prec == 3 ? launch_bwd_bf<3>(a, members, with_dx, st) : launch_bwd_bf<4>(a, members, with_dx, st);
+  if (a.prec != PREC_F32 && a.w2t_planes != nullptr && a.m1 != nullptr && a.m2 != nullptr)
+    return a.prec == PREC_BF16 ? launch_bwd_bf<1>(a, members, with_dx, st) : a.prec == PREC_BF16X2 ? launch_bwd_bf<2>(a, members, with_dx, st)
+         : a.prec == PREC_BF16X3 ? launch_bwd_bf<3>(a, members, with_dx, st) : launch_bwd_bf<4>(a, members, with_dx, st);
   return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_masks<1>(a, members, with_dx, st)
                                             : launch_bwd_masks<0>(a, members, with_dx, st);
 }
@@ -786,7 +786,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
   }
   long long rpw = cdiv(a.rows, (long long)4 * a.nsplit);
   a.rows_per_wave = (rpw + 15) & ~15LL;               // whole 8- / 16-row blocks for every wave but the last one with work
-  for (int k = (a.prec == 4 && a.eA != nullptr) ? 1 : 0; k < 3; ++k)     // a wave addresses its row slice through 32-bit buffer offsets
+  for (int k = (a.prec == PREC_F16X2 && a.eA != nullptr) ? 1 : 0; k < 3; ++k)     // a wave addresses its row slice through 32-bit buffer offsets
     if (a.rows_per_wave * (long long)std::max(a.job[k].lda, a.job[k].ldb) * 4 >= (1LL << 31))
       return fail(MOBODY_E_ARG, "launch_wgrad: row slice too large for 32-bit offsets (raise nsplit)");
   a.job[0].tiles_n = (a.job[0].nb + 63) / 64; a.job[0].ntiles = ((a.job[0].ka + 63) / 64) * a.job[0].tiles_n;
@@ -798,7 +798,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
   // Split-precision job 0 in every bf16 mode (the operand split costs ~6 VALU instructions per value and term; with the
   // unmasked scalar-addressed row loop that still leaves a gain: per step at c2 0.058 ms fp32 job -> 0.052 bf16x3,
   // 0.044 bf16x2).
-  if (a.prec == 4 && a.eA != nullptr) {               // "f16x2": job 0 on the pre-split fp16 planes
+  if (a.prec == PREC_F16X2 && a.eA != nullptr) {               // "f16x2": job 0 on the pre-split fp16 planes
     if (a.rows_per_wave > 2048) return fail(MOBODY_E_ARG, "launch_wgrad: more than 64 row tiles per wave slice (raise nsplit)");
     static bool once_h = false;
     if (!once_h) {
@@ -810,7 +810,7 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
     MB_LAUNCH_OK("k_wgrad_f16");
     return 0;
   }
-  if (a.prec != 0 && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide) {
+  if (a.prec != PREC_F32 && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide) {
     static bool once_bf = false;
     if (!once_bf) {
       int rc = allow_big_lds(k_wgrad_bf<1>, lds);
@@ -819,8 +819,8 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
       if (rc) return rc;
       once_bf = true;
     }
-    if (a.prec == 1) hipLaunchKernelGGL(k_wgrad_bf<1>, dim3(blocks), dim3(NTHREADS), lds, st, a);
-    else if (a.prec == 2) hipLaunchKernelGGL(k_wgrad_bf<2>, dim3(blocks), dim3(NTHREADS), lds, st, a);
+    if (a.prec == PREC_BF16) hipLaunchKernelGGL(k_wgrad_bf<1>, dim3(blocks), dim3(NTHREADS), lds, st, a);
+    else if (a.prec == PREC_BF16X2) hipLaunchKernelGGL(k_wgrad_bf<2>, dim3(blocks), dim3(NTHREADS), lds, st, a);
     else hipLaunchKernelGGL(k_wgrad_bf<3>, dim3(blocks), dim3(NTHREADS), lds, st, a);
     MB_LAUNCH_OK("k_wgrad_bf");
     return 0;
@@ -919,7 +919,7 @@ int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstr
   const long long hs = rows * HID;
   // dW2 = h1^T dz2
   g.job[0] = WgradJob{h1, hs, HID, HID, dz2, hs, HID, HID, L.w2, HID, HID, HID, 0, 1, 0, 0};
-  if (prec == 4 && e_h1 != nullptr) g.job[0].a_mstride = g.job[0].b_mstride = 2 * rows32 * HID;   // planes: 16-bit elements per member
+  if (prec == PREC_F16X2 && e_h1 != nullptr) g.job[0].a_mstride = g.job[0].b_mstride = 2 * rows32 * HID;   // planes: 16-bit elements per member
   // dW1 = x^T dz1
   g.job[1] = WgradJob{x, x_mstride, L.Kp1, L.Kp1, dz1, hs, HID, HID, L.w1, HID, L.Kp1, HID, 0, 1, 0, 0};
   // dW3^T = dz3^T h2, stored transposed into W3[256][Np3]

@@ -120,33 +120,44 @@ static int launch_fwd2_t(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs&
   return 0;
 }
 
-static int narrow_tiles(int Np3) { return Np3 == 16 ? 1 : Np3 == 32 ? 2 : 0; }
-
-// ReLU nets a and b in one launch (either may be empty)
-int launch_mlp3_fwd_pair(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, hipStream_t stream) {
-  if (a.rows <= 0) return launch_mlp3_fwd(b, members_b, ACT_RELU, stream);
-  if (b.rows <= 0) return launch_mlp3_fwd(a, members_a, ACT_RELU, stream);
-  if (a.Np3 != b.Np3) {                           // the merged kernel is specialised on one output-layer width
-    int rc = launch_mlp3_fwd(a, members_a, ACT_RELU, stream);
-    return rc ? rc : launch_mlp3_fwd(b, members_b, ACT_RELU, stream);
-  }
-  const int nt = narrow_tiles(a.Np3);
-  return nt == 1 ? launch_fwd2_t<1>(a, members_a, b, members_b, stream)
-       : nt == 2 ? launch_fwd2_t<2>(a, members_a, b, members_b, stream)
-                 : launch_fwd2_t<0>(a, members_a, b, members_b, stream);
+// ReLU nets a and b, both non-empty and of one output width, in one launch
+static int launch_fwd_pair(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, hipStream_t stream) {
+  return dispatch_out_width(a.Np3, [&](auto nt) { return launch_fwd2_t<decltype(nt)::value>(a, members_a, b, members_b, stream); });
 }
 
 template <int ACT>
 static int launch_fwd_act(const Mlp3FwdArgs& a, int members, hipStream_t stream) {
-  const int nt = narrow_tiles(a.Np3);
-  return nt == 1 ? launch_fwd_t<ACT, 1>(a, members, stream)
-       : nt == 2 ? launch_fwd_t<ACT, 2>(a, members, stream)
-                 : launch_fwd_t<ACT, 0>(a, members, stream);
+  return dispatch_out_width(a.Np3, [&](auto nt) { return launch_fwd_t<ACT, decltype(nt)::value>(a, members, stream); });
 }
 
-int launch_mlp3_fwd(const Mlp3FwdArgs& a, int members, int act, hipStream_t stream) {
-  if (a.rows <= 0) return 0;
+static int launch_mlp3_fwd(const Mlp3FwdArgs& a, int members, int act, hipStream_t stream) {
   return act == ACT_SWISH ? launch_fwd_act<ACT_SWISH>(a, members, stream) : launch_fwd_act<ACT_RELU>(a, members, stream);
+}
+
+// the other two back ends: split precision (mlp_fwd_bf.hip: a non-empty with w2_planes; b a ReLU net that shares the launch, or
+// members_b = 0) and the fp32 training forward of a Swish net, which also saves the derivatives (pretrain.hip)
+int launch_mlp3_fwd_bf(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st);
+int launch_fwd_train(const Mlp3FwdArgs& a, int members, hipStream_t st);
+
+// Two nets share a launch when both are ReLU nets of one output-layer width (the merged kernels are specialised on it), or --
+// f16x2 only, which has the two mixed instantiations -- of widths 16 and 32: a twin-Q next to an actor of more than 16 actions.
+static bool nets_share_launch(const Mlp3FwdArgs& a, const Mlp3FwdArgs& b, int act, int prec) {
+  if (act != ACT_RELU) return false;
+  return a.Np3 == b.Np3 || (prec == PREC_F16X2 && ((a.Np3 == 16 && b.Np3 == 32) || (a.Np3 == 32 && b.Np3 == 16)));
+}
+
+int launch_mlp3_forward(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st) {
+  auto one = [&](const Mlp3FwdArgs& x, int members) {
+    if (prec != PREC_F32) return launch_mlp3_fwd_bf(x, members, Mlp3FwdArgs{}, 0, act, prec, st);
+    return x.save_d1 != nullptr ? launch_fwd_train(x, members, st) : launch_mlp3_fwd(x, members, act, st);
+  };
+  const bool has_a = members_a > 0 && a.rows > 0, has_b = members_b > 0 && b.rows > 0;
+  if (!has_a || !has_b) return has_a ? one(a, members_a) : has_b ? one(b, members_b) : 0;
+  if (!nets_share_launch(a, b, act, prec)) {
+    int rc = one(a, members_a);
+    return rc ? rc : one(b, members_b);
+  }
+  return prec == PREC_F32 ? launch_fwd_pair(a, members_a, b, members_b, st) : launch_mlp3_fwd_bf(a, members_a, b, members_b, act, prec, st);
 }
 
 }  // namespace mobody
@@ -164,19 +175,13 @@ extern "C" int mobody_mlp3_forward(const float* blob, const float* blob_T, int p
   if (rows == 0) return 0;
   MB_REQUIRE(blob && src0 && out, "mobody_mlp3_forward: null pointer");
   MB_REQUIRE(n0 + n1 == in_dim && n0 > 0 && n1 >= 0 && (n1 == 0 || src1), "mobody_mlp3_forward: n0+n1=%d != in_dim=%d", n0 + n1, in_dim);
-  Mlp3FwdArgs a{};
-  a.src[0] = src0; a.ld[0] = n0; a.n[0] = n0;
-  a.src[1] = src1; a.ld[1] = n1; a.n[1] = n1;
-  a.src[2] = nullptr; a.ld[2] = 0; a.n[2] = 0;
-  a.w1 = blob + L.w1; a.b1 = blob + L.b1; a.w2 = blob + L.w2; a.b2 = blob + L.b2; a.w3 = blob + L.w3; a.b3 = blob + L.b3;
-  a.sw1 = a.sb1 = a.sw2 = a.sb2 = a.sw3 = a.sb3 = L.member_floats;
-  a.Kp1 = L.Kp1; a.Np3 = L.Np3; a.nout = out_dim; a.rows = rows;
-  a.out = out; a.out_mstride = rows * out_dim; a.out_ld = out_dim;
-  a.save_x = save_x; a.save_h1 = save_h1; a.save_h2 = save_h2;
-  a.out_mode = out_mode; a.max_action = max_action;
-  MB_REQUIRE(precision >= 0 && precision <= 4 && (precision == 0 || blob_T), "mobody_mlp3_forward: precision %d needs the T blob", precision);
-  if (precision == 0) return launch_mlp3_fwd(a, members, ACT_RELU, as_stream(stream));
-  a.w2_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2p);
-  a.planes_ms = 2 * L.t_member_floats;
-  return launch_mlp3_fwd_bf(a, members, Mlp3FwdArgs{}, 0, ACT_RELU, precision, as_stream(stream));
+  rc = check_precision("mobody_mlp3_forward", precision, blob_T != nullptr);
+  if (rc) return rc;
+  Mlp3FwdArgs a = fwd_net(blob, L, rows);
+  fwd_set_src(a, 0, src0, n0, n0);
+  fwd_set_src(a, 1, src1, n1, n1);
+  fwd_set_out(a, out, out_mode, max_action);
+  fwd_set_saves(a, save_x, 0, save_h1, nullptr, save_h2);
+  if (precision != PREC_F32) fwd_set_planes(a, blob_T, L);
+  return launch_mlp3_forward(a, members, ACT_RELU, precision, as_stream(stream));
 }

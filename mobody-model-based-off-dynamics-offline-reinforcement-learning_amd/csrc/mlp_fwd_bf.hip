@@ -109,21 +109,15 @@ static int launch_bf_t(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b
 
 template <int ACT, int PM>
 static int launch_bf_nt(const Mlp3FwdArgs& a, int ma, const Mlp3FwdArgs& b, int mb, hipStream_t st) {
-  if constexpr (PM == 4) {                          // f16x2: two nets, two output widths (16 | 32); pairs are ReLU nets
-    if (mb > 0 && b.rows > 0 && a.rows > 0 && a.Np3 != b.Np3) {
-      if constexpr (ACT == ACT_RELU) {
-        if (a.Np3 == 16 && b.Np3 == 32) return launch_bf_t<ACT, PM, 1, false, 2>(a, ma, b, mb, st);
-        if (a.Np3 == 32 && b.Np3 == 16) return launch_bf_t<ACT, PM, 2, false, 1>(a, ma, b, mb, st);
-      }
-      return fail(MOBODY_E_ARG, "launch_mlp3_fwd_bf: nets of output widths %d and %d do not share a launch", a.Np3, b.Np3);
-    }
+  if constexpr (PM == 4 && ACT == ACT_RELU) {       // f16x2: the mixed pair launch_mlp3_forward lets through, widths 16 | 32
+    if (mb > 0 && a.Np3 != b.Np3)
+      return a.Np3 == 16 ? launch_bf_t<ACT, PM, 1, false, 2>(a, ma, b, mb, st) : launch_bf_t<ACT, PM, 2, false, 1>(a, ma, b, mb, st);
   }
-  const int np3 = a.rows > 0 ? a.Np3 : b.Np3;
-  return np3 == 16 ? launch_bf_t<ACT, PM, 1>(a, ma, b, mb, st) : np3 == 32 ? launch_bf_t<ACT, PM, 2>(a, ma, b, mb, st)
-                                                                          : launch_bf_t<ACT, PM, 0>(a, ma, b, mb, st);
+  return dispatch_out_width(a.Np3, [&](auto nt) { return launch_bf_t<ACT, PM, decltype(nt)::value>(a, ma, b, mb, st); });
 }
 
-// prec: 1 bf16, 2 bf16x2, 3 bf16x3, 4 f16x2.  Two ReLU nets (either may be empty: rows <= 0) or one Swish net.
+// prec: 1 bf16, 2 bf16x2, 3 bf16x3, 4 f16x2.  Net a (non-empty) alone, or with a ReLU net b that launch_mlp3_forward found to share
+// the launch.
 // Workgroup shape: 32-row tiles of four waves.  Measured alternatives that lost (removed; they live in the history before
 // this shape became the only one):
 //   * two row groups (eight waves) sharing each weight fragment: twin-Q forward at 10 240 rows 41.5 us against 28.8 us in
@@ -133,20 +127,14 @@ static int launch_bf_nt(const Mlp3FwdArgs& a, int ma, const Mlp3FwdArgs& b, int 
 //     10 240 rows: 19.8 against 17.4) and lose in the train step, whose forwards also save activations: c3 forward 302
 //     against 297 us per step, c4 280 against 258.
 int launch_mlp3_fwd_bf(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, int act, int prec, hipStream_t st) {
-  if (a.rows <= 0 && b.rows <= 0) return 0;
-  Mlp3FwdArgs x = a, y = b; int mx = members_a, my = members_b;
-  if (x.rows <= 0) { x = b; mx = members_b; y.rows = 0; my = 0; }
-  if (y.rows <= 0) my = 0;
-  if (x.save_d1 != nullptr || x.save_d2 != nullptr) {  // training forward of a Swish net (dynamics pre-training): f16x2, one net
-    if (act != ACT_SWISH || prec != 4 || my != 0 || !x.save_d1 || !x.save_d2)
+  if (a.save_d1 != nullptr || a.save_d2 != nullptr) {  // training forward of a Swish net (dynamics pre-training): f16x2, one net
+    if (act != ACT_SWISH || prec != PREC_F16X2 || members_b != 0 || !a.save_d1 || !a.save_d2)
       return fail(MOBODY_E_ARG, "launch_mlp3_fwd_bf: derivative saves need one Swish net in the f16x2 mode");
-    const int np3 = x.Np3;
-    return np3 == 16 ? launch_bf_t<ACT_SWISH, 4, 1, true>(x, mx, y, 0, st) : np3 == 32 ? launch_bf_t<ACT_SWISH, 4, 2, true>(x, mx, y, 0, st)
-                                                                           : launch_bf_t<ACT_SWISH, 4, 0, true>(x, mx, y, 0, st);
+    return dispatch_out_width(a.Np3, [&](auto nt) { return launch_bf_t<ACT_SWISH, 4, decltype(nt)::value, true>(a, members_a, b, 0, st); });
   }
-#define BF_CASE(ACT, PM) launch_bf_nt<ACT, PM>(x, mx, y, my, st)
-  if (act == ACT_SWISH) return prec == 1 ? BF_CASE(ACT_SWISH, 1) : prec == 2 ? BF_CASE(ACT_SWISH, 2) : prec == 3 ? BF_CASE(ACT_SWISH, 3) : BF_CASE(ACT_SWISH, 4);
-  return prec == 1 ? BF_CASE(ACT_RELU, 1) : prec == 2 ? BF_CASE(ACT_RELU, 2) : prec == 3 ? BF_CASE(ACT_RELU, 3) : BF_CASE(ACT_RELU, 4);
+#define BF_CASE(ACT, PM) launch_bf_nt<ACT, PM>(a, members_a, b, members_b, st)
+  if (act == ACT_SWISH) return prec == PREC_BF16 ? BF_CASE(ACT_SWISH, 1) : prec == PREC_BF16X2 ? BF_CASE(ACT_SWISH, 2) : prec == PREC_BF16X3 ? BF_CASE(ACT_SWISH, 3) : BF_CASE(ACT_SWISH, 4);
+  return prec == PREC_BF16 ? BF_CASE(ACT_RELU, 1) : prec == PREC_BF16X2 ? BF_CASE(ACT_RELU, 2) : prec == PREC_BF16X3 ? BF_CASE(ACT_RELU, 3) : BF_CASE(ACT_RELU, 4);
 #undef BF_CASE
 }
 

@@ -103,10 +103,17 @@ static int launch_fwd_train_t(const Mlp3FwdArgs& a, int members, hipStream_t st)
   MB_LAUNCH_OK("k_mlp3_fwd_train");
   return 0;
 }
-static int launch_fwd_train(const Mlp3FwdArgs& a, int members, hipStream_t st) {
-  if (a.rows <= 0) return 0;
-  return a.Np3 == 16 ? launch_fwd_train_t<1>(a, members, st) : a.Np3 == 32 ? launch_fwd_train_t<2>(a, members, st)
-                                                                            : launch_fwd_train_t<0>(a, members, st);
+// reached through launch_mlp3_forward (mlp_fwd.hip): precision f32, a net with derivative saves
+int launch_fwd_train(const Mlp3FwdArgs& a, int members, hipStream_t st) {
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_fwd_train<0>, 160 * 1024);
+    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<1>, 160 * 1024);
+    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<2>, 160 * 1024);
+    if (rc) return rc;
+    once = true;
+  }
+  return dispatch_out_width(a.Np3, [&](auto nt) { return launch_fwd_train_t<decltype(nt)::value>(a, members, st); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -611,38 +618,27 @@ static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, Pr
   return 0;
 }
 
-// blob_T / e1 (f16x2): W2's fp16 planes from the T blob; h1 receives planes + tile exponents instead of fp32 rows
+// per-member input rows [E][rows][n] and a per-member x save.  e1 != null (f16x2, and only then): W2's fp16 planes from the T
+// blob; h1 receives planes + tile exponents instead of fp32 rows
 static Mlp3FwdArgs pre_fwd_args(const float* blob, const MobodyMlpLayout& L, const float* src, int n, long long rows, float* out,
                                 float* sx, float* h1, float* h2, float* d1, float* d2, const float* blob_T = nullptr,
                                 int* e1 = nullptr) {
-  Mlp3FwdArgs a{};
-  if (e1 != nullptr) {
-    const long long r32 = (rows + 31) & ~31LL;
-    a.save_h1p = reinterpret_cast<unsigned short*>(h1); a.h1p_plane = r32 * HID; a.h1p_ms = 2 * r32 * HID; a.save_e1 = e1;
-    a.w2_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2p); a.planes_ms = 2 * L.t_member_floats;
-    h1 = nullptr;
-  }
-  a.src[0] = src; a.ld[0] = n; a.n[0] = n; a.src_ms[0] = rows * n;
-  a.w1 = blob + L.w1; a.b1 = blob + L.b1; a.w2 = blob + L.w2; a.b2 = blob + L.b2; a.w3 = blob + L.w3; a.b3 = blob + L.b3;
-  a.sw1 = a.sb1 = a.sw2 = a.sb2 = a.sw3 = a.sb3 = L.member_floats;
-  a.Kp1 = L.Kp1; a.Np3 = L.Np3; a.nout = L.out_dim; a.rows = rows;
-  a.out = out; a.out_mstride = rows * L.out_dim; a.out_ld = L.out_dim;
-  a.save_x = sx; a.x_ms = rows * L.Kp1; a.save_h1 = h1; a.save_h2 = h2; a.save_d1 = d1; a.save_d2 = d2;
+  Mlp3FwdArgs a = fwd_net(blob, L, rows);
+  if (e1 != nullptr) fwd_set_planes(a, blob_T, L);
+  fwd_set_src(a, 0, src, n, n, rows * n);
+  fwd_set_out(a, out, 0, 0.f);
+  fwd_set_saves(a, sx, rows * L.Kp1, h1, e1, h2, nullptr, nullptr, d1, d2);
   return a;
 }
 
+// Swish nets: d1 / d2 are the saved derivatives.  e2 != null (f16x2, and only then): prec and W2^T's planes from the T blob; dz2
+// leaves as planes + tile exponents
 static Mlp3BwdArgs pre_bwd_args(const MobodyMlpLayout& L, const float* blob_T, const float* dz3, const float* d1, const float* d2,
                                 long long rows, float* dz2, float* dz1, float* dbp, int* e2 = nullptr) {
-  Mlp3BwdArgs b{};
-  if (e2 != nullptr) {                              // f16x2: dz2 leaves as planes + tile exponents, W2^T's planes from the T blob
-    const long long r32 = (rows + 31) & ~31LL;
-    b.dz2p = reinterpret_cast<unsigned short*>(dz2); b.dz2p_plane = r32 * HID; b.dz2p_ms = 2 * r32 * HID; b.e2_out = e2;
-    b.prec = 4; b.w2t_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2tp); b.planes_ms = 2 * L.t_member_floats;
-    dz2 = nullptr;
-  }
-  b.dz3 = dz3; b.h1 = d1; b.h2 = d2; b.swish = 1; b.wt = blob_T; b.t_mstride = L.t_member_floats;
-  b.w3t = L.w3t; b.w2t = L.w2t; b.w1t = L.w1t; b.Np3 = L.Np3; b.Np1t = L.Np1t; b.rows = rows;
-  b.dz2 = dz2; b.dz1 = dz1; b.dbp = dbp;
+  Mlp3BwdArgs b = bwd_net(L, blob_T, rows);
+  if (e2 != nullptr) bwd_set_planes(b, L, PREC_F16X2);
+  bwd_set_acts(b, d1, d2, nullptr, nullptr, 1);
+  bwd_set_grads(b, dz3, dz2, dz1, dbp, e2);
   return b;
 }
 
@@ -680,17 +676,12 @@ extern "C" int mobody_pretrain_layout(int S, int A, MobodyPretrainLayout* out) {
   return 0;
 }
 
-static int pre_check_prec(int precision, const char* who) {
-  MB_REQUIRE(precision == 0 || precision == 4, "%s: pre-training runs in precision 0 (f32) or 4 (f16x2)", who);
-  return 0;
-}
-
 extern "C" int mobody_pretrain_transpose(int S, int A, const float* blob, float* blob_T, int precision, void* stream) {
   MobodyPretrainLayout L;
   int rc = mobody_pretrain_layout(S, A, &L);
   if (rc) return rc;
   MB_REQUIRE(blob && blob_T, "mobody_pretrain_transpose: null pointer");
-  rc = pre_check_prec(precision, "mobody_pretrain_transpose");
+  rc = check_precision("mobody_pretrain_transpose", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   rc = mobody_mlp_transpose(S, 2 * LATENT, NENS, blob + L.off_enc, blob_T + L.t_off_enc, precision, stream);
   if (!rc) rc = mobody_mlp_transpose(LATENT, S, NENS, blob + L.off_tr, blob_T + L.t_off_tr, precision, stream);
@@ -731,7 +722,7 @@ static AdamTarget pre_adam_target(float* p, float* pT, float* m, float* v, int64
   a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
   a.c.tau = -1.f; a.c.one_minus_tau = 0.f; a.c.gscale = grad_scale;
   a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1;
-  a.precision = precision == 4 ? 4 : -1;          // exact fp32 never reads the W2 planes of its T blob; f16x2 keeps them current
+  a.precision = precision == PREC_F16X2 ? PREC_F16X2 : -1;         // exact fp32 never reads the W2 planes of its T blob; f16x2 keeps them current
   a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
   return a;
 }
@@ -777,9 +768,9 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   MobodyPretrainLayout L;
   int rc = mobody_pretrain_layout(S, A, &L);
   if (rc) return rc;
-  rc = pre_check_prec(precision, "mobody_pretrain");
+  rc = check_precision("mobody_pretrain", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
-  const bool f16 = precision == 4;
+  const bool f16 = precision == PREC_F16X2;
   MB_REQUIRE(b >= 1 && b_global >= b, "mobody_pretrain: need 1 <= b <= b_global");
   MB_REQUIRE(blob && blob_T && xenc && act && rew && (grad || opt.on) && loss_out && workspace, "mobody_pretrain: null pointer");
   auto region_adam = [&](int64_t off, int64_t toff) {
@@ -791,14 +782,6 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   pre_carve(L, b, workspace, w);
   hipStream_t st = as_stream(stream);
   const long long R2 = 2 * b, R4 = 4 * b;
-  static bool once = false;
-  if (!once) {
-    rc = allow_big_lds(k_mlp3_fwd_train<0>, 160 * 1024);
-    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<1>, 160 * 1024);
-    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<2>, 160 * 1024);
-    if (rc) return rc;
-    once = true;
-  }
   PreRow r{};
   r.S = S; r.A = A; r.use_trg = use_trg; r.Np3tr = L.tr.Np3; r.b = b; r.inv_bg = 1.f / (float)b_global;
   r.ce = (use_trg ? 5.f : 1.f) * encoder_loss_coef; r.cr = (use_trg ? 1.f : 0.01f) * reward_coef; r.ct = transition_coef;
@@ -811,10 +794,8 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   const float *Penc = blob + L.off_enc, *Ptr = blob + L.off_tr, *Prw = blob + L.off_rw;
   const float *Tenc = blob_T + L.t_off_enc, *Ttr = blob_T + L.t_off_tr, *Trw = blob_T + L.t_off_rw;
 
-  // f16x2: the 256 x 256 layers of the three nets on the split core (mlp_fwd_bf.hip with derivative saves)
-  auto forward = [&](const Mlp3FwdArgs& fa) {
-    return f16 ? launch_mlp3_fwd_bf(fa, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, 4, st) : launch_fwd_train(fa, NENS, st);
-  };
+  // f32: k_mlp3_fwd_train; f16x2: the 256 x 256 layers of the three nets on the split core (mlp_fwd_bf.hip with derivative saves)
+  auto forward = [&](const Mlp3FwdArgs& fa) { return launch_mlp3_forward(fa, NENS, ACT_SWISH, precision, st); };
   // ---- forward ----
   rc = forward(pre_fwd_args(Penc, L.enc, xenc, S, R2, w.enc_out, w.sx_enc, w.h1e, w.h2e, w.d1e, w.d2e, Tenc, f16 ? w.eh1e : nullptr));
   if (rc) return rc;
@@ -923,7 +904,7 @@ extern "C" int mobody_pretrain_adam(int S, int A, int use_trg, float* blob, floa
   MobodyPretrainLayout L;
   int rc = mobody_pretrain_layout(S, A, &L);
   if (rc) return rc;
-  rc = pre_check_prec(precision, "mobody_pretrain_adam");
+  rc = check_precision("mobody_pretrain_adam", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   MB_REQUIRE(blob && blob_T && grad && m && v, "mobody_pretrain_adam: null pointer");
   MB_REQUIRE(t_main >= 1 && t_za >= 1 && (!(net_mask & 4) || t_rw >= 1), "mobody_pretrain_adam: step counts are 1-based");
@@ -971,18 +952,12 @@ static int dyn_validate_tail(const float* dyn_blob, const MobodyDynLayout& L, in
   float* mean = workspace;
   float* r_mu = workspace + (int64_t)NENS * B * S;
   // reward head of member e on [s, a, mean_e]   (:1137: encode_reward(obs.repeat(7), act.repeat(7), mean))
-  Mlp3FwdArgs m{};
-  m.src[0] = obs; m.ld[0] = S; m.n[0] = S;
-  m.src[1] = act; m.ld[1] = A; m.n[1] = A;
-  m.src[2] = mean; m.ld[2] = S; m.n[2] = S; m.src_ms[2] = B * S;
-  const MobodyLayer &l1 = L.layer[MOBODY_DL_RW1], &l2 = L.layer[MOBODY_DL_RW2], &l3 = L.layer[MOBODY_DL_RW3];
-  m.w1 = dyn_blob + l1.w_off; m.b1 = dyn_blob + l1.b_off; m.sw1 = (long long)l1.Kp * l1.Np; m.sb1 = l1.Np;
-  m.w2 = dyn_blob + l2.w_off; m.b2 = dyn_blob + l2.b_off; m.sw2 = (long long)l2.Kp * l2.Np; m.sb2 = l2.Np;
-  m.w3 = dyn_blob + l3.w_off; m.b3 = dyn_blob + l3.b_off; m.sw3 = (long long)l3.Kp * l3.Np; m.sb3 = l3.Np;
-  m.Kp1 = l1.Kp; m.Np3 = l3.Np; m.nout = 1; m.rows = B;
-  m.out = r_mu; m.out_mstride = B; m.out_ld = 1;
-  m.out_mode = 0; m.max_action = 1.f;
-  rc = launch_mlp3_fwd(m, NENS, ACT_SWISH, as_stream(stream));
+  Mlp3FwdArgs m = fwd_reward_head(dyn_blob, L, nullptr, B);
+  fwd_set_src(m, 0, obs, S, S);
+  fwd_set_src(m, 1, act, A, A);
+  fwd_set_src(m, 2, mean, S, S, B * S);
+  fwd_set_out(m, r_mu, 0, 1.f);
+  rc = launch_mlp3_forward(m, NENS, ACT_SWISH, PREC_F32, as_stream(stream));
   if (rc) return rc;
   hipLaunchKernelGGL(k_pre_validate, dim3(NENS), dim3(256), 0, as_stream(stream), mean, next_obs, r_mu, rew, (long long)B, S, out);
   MB_LAUNCH_OK("k_pre_validate");
@@ -1214,7 +1189,7 @@ extern "C" int mobody_pretrain_mopo_transpose(int S, int A, const float* blob, f
   int rc = mobody_pretrain_mopo_layout(S, A, &L);
   if (rc) return rc;
   MB_REQUIRE(blob && blob_T, "mobody_pretrain_mopo_transpose: null pointer");
-  rc = pre_check_prec(precision, "mobody_pretrain_mopo_transpose");
+  rc = check_precision("mobody_pretrain_mopo_transpose", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   rc = mobody_mlp_transpose(S + A, S, NENS, blob + L.off_dyn, blob_T + L.t_off_dyn, precision, stream);
   if (!rc) rc = mobody_mlp_transpose(2 * S + A, 2, NENS, blob + L.off_rw, blob_T + L.t_off_rw, precision, stream);
@@ -1236,9 +1211,9 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
   MobodyPretrainMopoLayout L;
   int rc = mobody_pretrain_mopo_layout(S, A, &L);
   if (rc) return rc;
-  rc = pre_check_prec(precision, "mobody_pretrain_mopo");
+  rc = check_precision("mobody_pretrain_mopo", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
-  const bool f16 = precision == 4;
+  const bool f16 = precision == PREC_F16X2;
   MB_REQUIRE(b >= 1 && b_global >= b, "mobody_pretrain_mopo: need 1 <= b <= b_global");
   MB_REQUIRE(blob && blob_T && xenc && act && rew && (grad || opt.on) && loss_out && workspace, "mobody_pretrain_mopo: null pointer");
   auto region_adam = [&](int64_t off, int64_t toff) {
@@ -1250,14 +1225,6 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
   mopo_carve(L, b, workspace, w);
   hipStream_t st = as_stream(stream);
   const long long R2 = 2 * b;
-  static bool once = false;
-  if (!once) {
-    rc = allow_big_lds(k_mlp3_fwd_train<0>, 160 * 1024);
-    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<1>, 160 * 1024);
-    if (!rc) rc = allow_big_lds(k_mlp3_fwd_train<2>, 160 * 1024);
-    if (rc) return rc;
-    once = true;
-  }
   const float ce = (use_trg ? 5.f : 1.f) * encoder_loss_coef, cr = use_trg ? 1.f : 0.01f, inv_bg = 1.f / (float)b_global;
   MopoRow r{};
   r.S = S; r.A = A; r.Np3 = L.dyn.Np3; r.b = b; r.inv_bg = inv_bg; r.ce = ce;
@@ -1268,14 +1235,12 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
   pr.lossp = w.lossp;
   const float *Pd = blob + L.off_dyn, *Prw = blob + L.off_rw;
   const float *Td = blob_T + L.t_off_dyn, *Trw = blob_T + L.t_off_rw;
-  auto forward = [&](const Mlp3FwdArgs& fa) {
-    return f16 ? launch_mlp3_fwd_bf(fa, NENS, Mlp3FwdArgs{}, 0, ACT_SWISH, 4, st) : launch_fwd_train(fa, NENS, st);
-  };
+  auto forward = [&](const Mlp3FwdArgs& fa) { return launch_mlp3_forward(fa, NENS, ACT_SWISH, precision, st); };
   // ---- forward: the MLP on [s, a] (b rows per member), the row kernel, the reward head on 2b rows ----
   {
     Mlp3FwdArgs fa = pre_fwd_args(Pd, L.dyn, xenc, S, b, w.f, w.sx_d, w.h1d, w.h2d, w.d1d, w.d2d, Td, f16 ? w.eh1d : nullptr);
-    fa.src_ms[0] = 2 * b * S;                          // the s rows of xenc (its s' rows follow in each member's block)
-    fa.src[1] = act; fa.ld[1] = A; fa.n[1] = A; fa.src_ms[1] = b * A;
+    fwd_set_src(fa, 0, xenc, S, S, 2 * b * S);          // the s rows of xenc (its s' rows follow in each member's block)
+    fwd_set_src(fa, 1, act, A, A, b * A);
     rc = forward(fa);
     if (rc) return rc;
   }
@@ -1348,7 +1313,7 @@ extern "C" int mobody_pretrain_mopo_adam(int S, int A, float* blob, float* blob_
   MobodyPretrainMopoLayout L;
   int rc = mobody_pretrain_mopo_layout(S, A, &L);
   if (rc) return rc;
-  rc = pre_check_prec(precision, "mobody_pretrain_mopo_adam");
+  rc = check_precision("mobody_pretrain_mopo_adam", precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   MB_REQUIRE(blob && blob_T && grad && m && v, "mobody_pretrain_mopo_adam: null pointer");
   MB_REQUIRE(t >= 1, "mobody_pretrain_mopo_adam: the step count is 1-based");
@@ -1375,17 +1340,11 @@ extern "C" int mobody_dyn_validate_mopo(const float* dyn_blob, const float* mopo
   if (rc) return rc;
   MB_REQUIRE(B >= 1, "mobody_dyn_validate_mopo: B < 1");
   MB_REQUIRE(dyn_blob && mopo_blob && obs && act && next_obs && rew && out && workspace, "mobody_dyn_validate_mopo: null pointer");
-  Mlp3FwdArgs f{};                                     // mean_e = s + f_e(s, a), exact fp32 (forward_trg == forward_src, :264-266)
-  f.src[0] = obs; f.ld[0] = S; f.n[0] = S;
-  f.src[1] = act; f.ld[1] = A; f.n[1] = A;
-  f.w1 = mopo_blob + ML.w1; f.b1 = mopo_blob + ML.b1; f.w2 = mopo_blob + ML.w2; f.b2 = mopo_blob + ML.b2;
-  f.w3 = mopo_blob + ML.w3; f.b3 = mopo_blob + ML.b3;
-  f.sw1 = f.sb1 = f.sw2 = f.sb2 = f.sw3 = f.sb3 = ML.member_floats;
-  f.Kp1 = ML.Kp1; f.Np3 = ML.Np3; f.nout = S; f.rows = B;
-  f.out = workspace; f.out_mstride = B * S; f.out_ld = S;
-  f.out_mode = 0; f.max_action = 1.f;
-  f.resid = obs; f.resid_ld = S;
-  rc = launch_mlp3_fwd(f, NENS, ACT_SWISH, as_stream(stream));
+  Mlp3FwdArgs f = fwd_net(mopo_blob, ML, B);           // mean_e = s + f_e(s, a), exact fp32 (forward_trg == forward_src, :264-266)
+  fwd_set_src(f, 0, obs, S, S);
+  fwd_set_src(f, 1, act, A, A);
+  fwd_set_out(f, workspace, 0, 1.f, obs, S);
+  rc = launch_mlp3_forward(f, NENS, ACT_SWISH, PREC_F32, as_stream(stream));
   if (rc) return rc;
   return dyn_validate_tail(dyn_blob, L, S, A, obs, act, next_obs, rew, B, out, workspace, stream);
 }

@@ -76,6 +76,34 @@ struct Mlp3BwdArgs {
 };
 int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st);
 
+// ---- host side: the one place an Mlp3BwdArgs is filled; each helper owns one group of fields (the seed and dx are the caller's).
+// launch_mlp3_bwd picks its kernel from swish, prec + w2t_planes and m1 + m2, so every caller states those explicitly. ----
+// transposed weights of a packed MLP (mobody_mlp_layout) on `rows` rows; everything else zero = exact fp32, ReLU, dz3 from memory
+inline Mlp3BwdArgs bwd_net(const MobodyMlpLayout& L, const float* blob_T, long long rows) {
+  Mlp3BwdArgs b{};
+  b.wt = blob_T; b.t_mstride = L.t_member_floats;
+  b.w3t = L.w3t; b.w2t = L.w2t; b.w1t = L.w1t; b.Np3 = L.Np3; b.Np1t = L.Np1t; b.rows = rows;
+  return b;
+}
+// the precision id and W2^T's planes in the T blob (a launch without them runs the 256 x 256 GEMM on exact fp32 MFMA)
+inline void bwd_set_planes(Mlp3BwdArgs& b, const MobodyMlpLayout& L, int prec) {
+  b.prec = prec; b.w2t_planes = reinterpret_cast<const unsigned short*>(b.wt + L.w2tp); b.planes_ms = 2 * L.t_member_floats;
+}
+// what the forward saved: ReLU nets h1 / h2 or (replacing them) the sign words m1 / m2; swish = 1: the derivatives d1 / d2
+inline void bwd_set_acts(Mlp3BwdArgs& b, const float* h1, const float* h2, const uint32_t* m1, const uint32_t* m2, int swish) {
+  b.h1 = h1; b.h2 = h2; b.m1 = m1; b.m2 = m2; b.swish = swish;
+}
+// dz3 in (seed.mode 0) and dz2 / dz1 / the bias partials out.  e2 != null (f16x2, needs bwd_set_planes) and dz2: dz2 leaves as the
+// two fp16 planes + tile exponents the weight-gradient GEMM reads, not as fp32 rows
+inline void bwd_set_grads(Mlp3BwdArgs& b, const float* dz3, float* dz2, float* dz1, float* dbp, int* e2 = nullptr) {
+  if (e2 != nullptr && dz2 != nullptr) {
+    const long long r32 = (b.rows + 31) & ~31LL;
+    b.dz2p = reinterpret_cast<unsigned short*>(dz2); b.dz2p_plane = r32 * HID; b.dz2p_ms = 2 * r32 * HID; b.e2_out = e2;
+    dz2 = nullptr;
+  }
+  b.dz3 = dz3; b.dz2 = dz2; b.dz1 = dz1; b.dbp = dbp;
+}
+
 struct WgradJob {
   const float* A; long long a_mstride; int lda, ka;    // A[rows][lda], columns < ka contribute (output rows)
   const float* B; long long b_mstride; int ldb, nb;    // B[rows][ldb], columns < nb contribute (output cols)
@@ -94,7 +122,8 @@ struct WgradArgs {
   long long rows, rows_per_wave;
   float* slabs; long long slab_stride, out_mstride;    // partial slab s = slabs + s*slab_stride (gradient-blob layout)
   int nsplit, members, tiles_total;
-  int prec;                                            // 0 exact fp32; 1..3: the 256 x 256 job on the split-precision bf16 core
+  int prec;                                            // precision id (common.h): f32 exact; bf16 modes: the 256 x 256 job on the
+                                                       // split-precision core; f16x2 with eA: job 0 on the saved fp16 planes
 };
 int launch_wgrad(WgradArgs a, hipStream_t st);
 

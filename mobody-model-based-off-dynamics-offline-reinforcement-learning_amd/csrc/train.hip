@@ -202,50 +202,19 @@ __global__ __launch_bounds__(256) void k_mlp_transpose(MobodyMlpLayout L, const 
 // ------------------------------------------------------------------------------------------------
 // helpers to launch the fused MLP pieces on a packed blob
 // ------------------------------------------------------------------------------------------------
-// e1 != null (f16 mode): sh1 receives the layer-1 activations as fp16 planes + tile exponents instead of fp32 rows
+// blob_T != null: the split-precision modes stream W2's planes from the T blob.  e1 != null (f16 mode): sh1 receives the
+// layer-1 activations as fp16 planes + tile exponents instead of fp32 rows.  s1 == null: one input.
 static Mlp3FwdArgs fwd_args(const float* blob, const MobodyMlpLayout& L, const float* s0, int n0, const float* s1, int n1,
                             long long rows, float* out, int out_mode, float max_action, float* sx, float* sh1,
                             float* sh2, uint32_t* m1 = nullptr, uint32_t* m2 = nullptr, const float* blob_T = nullptr,
                             int* e1 = nullptr) {
-  Mlp3FwdArgs a{};
-  if (e1 != nullptr && sh1 != nullptr) {
-    const long long r32 = (rows + 31) & ~31LL;
-    a.save_h1p = reinterpret_cast<unsigned short*>(sh1); a.h1p_plane = r32 * HID; a.h1p_ms = 2 * r32 * HID; a.save_e1 = e1;
-    sh1 = nullptr;
-  }
-  if (blob_T != nullptr) {                          // split-precision modes stream W2's bf16 planes from the T blob
-    a.w2_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2p);
-    a.planes_ms = 2 * L.t_member_floats;
-  }
-  a.src[0] = s0; a.ld[0] = n0; a.n[0] = n0;
-  a.src[1] = s1; a.ld[1] = n1; a.n[1] = s1 ? n1 : 0;
-  a.w1 = blob + L.w1; a.b1 = blob + L.b1; a.w2 = blob + L.w2; a.b2 = blob + L.b2; a.w3 = blob + L.w3; a.b3 = blob + L.b3;
-  a.sw1 = a.sb1 = a.sw2 = a.sb2 = a.sw3 = a.sb3 = L.member_floats;
-  a.Kp1 = L.Kp1; a.Np3 = L.Np3; a.nout = L.out_dim; a.rows = rows;
-  a.out = out; a.out_mstride = rows * L.out_dim; a.out_ld = L.out_dim;
-  a.save_x = sx; a.save_h1 = sh1; a.save_h2 = sh2; a.mask1 = m1; a.mask2 = m2;
-  a.out_mode = out_mode; a.max_action = max_action;
+  Mlp3FwdArgs a = fwd_net(blob, L, rows);
+  if (blob_T != nullptr) fwd_set_planes(a, blob_T, L);
+  fwd_set_src(a, 0, s0, n0, n0);
+  fwd_set_src(a, 1, s1, n1, s1 ? n1 : 0);
+  fwd_set_out(a, out, out_mode, max_action);
+  fwd_set_saves(a, sx, 0, sh1, e1, sh2, m1, m2);
   return a;
-}
-
-// two ReLU nets in one launch at the requested precision (0 = exact fp32 MFMA)
-static int fwd_pair(const Mlp3FwdArgs& a, int ma, const Mlp3FwdArgs& b, int mb, int prec, hipStream_t st) {
-  if (prec == 0) return launch_mlp3_fwd_pair(a, ma, b, mb, st);
-  // (one launch also when the two output layers differ in width, 16 | 32 columns, in the f16x2 mode; else one launch per net)
-  const bool mixed_ok = prec == 4 && ((a.Np3 == 16 && b.Np3 == 32) || (a.Np3 == 32 && b.Np3 == 16));
-  if (a.rows > 0 && b.rows > 0 && a.Np3 != b.Np3 && !mixed_ok) {
-    int rc = launch_mlp3_fwd_bf(a, ma, Mlp3FwdArgs{}, 0, ACT_RELU, prec, st);
-    return rc ? rc : launch_mlp3_fwd_bf(b, mb, Mlp3FwdArgs{}, 0, ACT_RELU, prec, st);
-  }
-  return launch_mlp3_fwd_bf(a, ma, b, mb, ACT_RELU, prec, st);
-}
-static int fwd_one(const Mlp3FwdArgs& a, int ma, int prec, hipStream_t st) {
-  return prec == 0 ? launch_mlp3_fwd(a, ma, ACT_RELU, st) : launch_mlp3_fwd_bf(a, ma, Mlp3FwdArgs{}, 0, ACT_RELU, prec, st);
-}
-static int check_prec(const MobodyHyper* h, const char* who, bool have_planes) {
-  MB_REQUIRE(h->precision >= 0 && h->precision <= 4, "%s: precision must be 0 (f32), 1 (bf16), 2 (bf16x2), 3 (bf16x3) or 4 (f16x2)", who);
-  MB_REQUIRE(h->precision == 0 || have_planes, "%s: the split-precision modes need the T blobs (bf16 planes) of every net", who);
-  return 0;
 }
 
 // weight gradients of one packed MLP: one merged split-K launch + the deterministic reduction
@@ -253,23 +222,18 @@ static int weight_grads(const MobodyMlpLayout& L, const float* x, const float* h
                         const float* dz2, const float* dz1, long long rows, const TrainWs& w, float* grad,
                         const LossFinal& loss, const AdamTarget& adam, hipStream_t st, int prec = 0, const int* e_h1 = nullptr) {
   return mlp3_weight_grads(L, x, 0, h1, h2, dz3, dz2, dz1, rows, L.members == 1 ? w.nsplit_a : w.nsplit_q, w.slabs, w.dbp,
-                           w.ntiles, grad, loss, adam, st, prec, prec == 4 ? e_h1 : nullptr, prec == 4 ? w.edz2 : nullptr);
+                           w.ntiles, grad, loss, adam, st, prec, prec == PREC_F16X2 ? e_h1 : nullptr, prec == PREC_F16X2 ? w.edz2 : nullptr);
 }
 
-// e2 != null (f16 mode): dz2 receives fp16 planes + tile exponents instead of fp32 rows
+// the train step's ReLU nets: always the W2^T planes and `prec`; e2 != null in the f16 mode: dz2 receives fp16 planes + tile
+// exponents instead of fp32 rows
 static Mlp3BwdArgs bwd_args(const MobodyMlpLayout& L, const float* blob_T, const float* dz3, const float* h1,
                             const float* h2, long long rows, float* dz2, float* dz1, float* dbp,
-                            const uint32_t* m1 = nullptr, const uint32_t* m2 = nullptr, int prec = 0, int* e2 = nullptr) {
-  Mlp3BwdArgs b{};
-  if (prec == 4 && e2 != nullptr && dz2 != nullptr) {
-    const long long r32 = (rows + 31) & ~31LL;
-    b.dz2p = reinterpret_cast<unsigned short*>(dz2); b.dz2p_plane = r32 * HID; b.dz2p_ms = 2 * r32 * HID; b.e2_out = e2;
-    dz2 = nullptr;
-  }
-  b.prec = prec; b.w2t_planes = reinterpret_cast<const unsigned short*>(blob_T + L.w2tp); b.planes_ms = 2 * L.t_member_floats;
-  b.dz3 = dz3; b.h1 = h1; b.h2 = h2; b.m1 = m1; b.m2 = m2; b.wt = blob_T; b.t_mstride = L.t_member_floats;
-  b.w3t = L.w3t; b.w2t = L.w2t; b.w1t = L.w1t; b.Np3 = L.Np3; b.Np1t = L.Np1t; b.rows = rows;
-  b.dz2 = dz2; b.dz1 = dz1; b.dbp = dbp;
+                            const uint32_t* m1 = nullptr, const uint32_t* m2 = nullptr, int prec = PREC_F32, int* e2 = nullptr) {
+  Mlp3BwdArgs b = bwd_net(L, blob_T, rows);
+  bwd_set_planes(b, L, prec);
+  bwd_set_acts(b, h1, h2, m1, m2, 0);
+  bwd_set_grads(b, dz3, dz2, dz1, dbp, prec == PREC_F16X2 ? e2 : nullptr);
   return b;
 }
 
@@ -301,10 +265,10 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
   MB_REQUIRE(h && q_blob && q_blob_T && state && action && reward && not_done && (grad_q || adam.on) && loss_out && workspace,
              "mobody_critic_step: null pointer");
   MB_REQUIRE(q_next || (actor_blob && qtarg_blob && next_state), "mobody_critic_step: need q_next or actor/target/next_state");
-  rc = check_prec(h, "mobody_critic_step", q_next != nullptr || (actor_blob_T && qtarg_blob_T));
+  rc = check_precision("mobody_critic_step", h->precision, q_next != nullptr || (actor_blob_T && qtarg_blob_T));
   if (rc) return rc;
   const int prec = h->precision;
-  const float *aT = prec ? actor_blob_T : nullptr, *qT = prec ? q_blob_T : nullptr, *tT = prec ? qtarg_blob_T : nullptr;
+  const float *aT = prec != PREC_F32 ? actor_blob_T : nullptr, *qT = prec != PREC_F32 ? q_blob_T : nullptr, *tT = prec != PREC_F32 ? qtarg_blob_T : nullptr;
   TrainWs w;
   rc = carve(*d, workspace, w);
   if (rc) return rc;
@@ -313,22 +277,22 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
   const int S = d->S, A = d->A;
   // online twin-Q(s, a), activations kept for the backward (:196), together with a' = pi(s') (:191) in one launch
   const Mlp3FwdArgs fq = fwd_args(q_blob, w.Lq, state, S, action, A, N, w.q, 0, 1.f, w.xq, w.h1q, w.h2q, w.mq1, w.mq2, qT,
-                                  prec == 4 ? w.eh1q : nullptr);
+                                  prec == PREC_F16X2 ? w.eh1q : nullptr);
   if (phase == 2) {
     // forwards already enqueued by the phase-1 call
   } else if (q_next == nullptr) {
-    rc = fwd_pair(fq, 2, fwd_args(actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT), 1, prec, st);
+    rc = launch_mlp3_forward(fq, 2, fwd_args(actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT), 1, ACT_RELU, prec, st);
     // target twin-Q(s', a') (:192) -- and, when the caller asks for it, pi(s) of the coming actor phase in the same
     // launch: the actor is not updated in between, and a twin-Q launch alone is 2.5 workgroups per CU where the
     // merged one is 3.75 (the actor phase then opens with Q(s_t,a_t) alone: exactly 2 per CU)
     const Mlp3FwdArgs ft = fwd_args(qtarg_blob, w.Lq, next_state, S, w.pin, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
     if (!rc && policy_forward)
-      rc = fwd_pair(ft, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
-                                    prec == 4 ? w.eh1a : nullptr), 1, prec, st);
+      rc = launch_mlp3_forward(ft, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                                               prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
     else if (!rc)
-      rc = fwd_one(ft, 2, prec, st);
+      rc = launch_mlp3_forward(ft, 2, ACT_RELU, prec, st);
   } else {
-    rc = fwd_one(fq, 2, prec, st);                  // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229)
+    rc = launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);                  // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229)
   }
   if (rc || phase == 1) return rc;
   const float invNg = 1.f / (float)d->N_global;
@@ -394,10 +358,10 @@ extern "C" int mobody_actor_forward(const MobodyTrainDims* d, const MobodyHyper*
   int rc = check_dims(d, "mobody_actor_forward");
   if (rc) return rc;
   MB_REQUIRE(h && actor_blob && q_blob && state && action && stats && workspace, "mobody_actor_forward: null pointer");
-  rc = check_prec(h, "mobody_actor_forward", actor_blob_T && q_blob_T);
+  rc = check_precision("mobody_actor_forward", h->precision, actor_blob_T && q_blob_T);
   if (rc) return rc;
   const int prec = h->precision;
-  const float *aT = prec ? actor_blob_T : nullptr, *qT = prec ? q_blob_T : nullptr;
+  const float *aT = prec != PREC_F32 ? actor_blob_T : nullptr, *qT = prec != PREC_F32 ? q_blob_T : nullptr;
   TrainWs w;
   rc = carve(*d, workspace, w);
   if (rc) return rc;
@@ -410,11 +374,11 @@ extern "C" int mobody_actor_forward(const MobodyTrainDims* d, const MobodyHyper*
   // Q(s, pi(s)) with the freshly updated critic (:316); dQ/da through the frozen net needs only the ReLU signs
   const Mlp3FwdArgs fp = fwd_args(q_blob, w.Lq, state, S, w.pi, A, N, w.q, 0, 1.f, nullptr, nullptr, nullptr, w.mq1, w.mq2, qT);
   if (policy_ready) {
-    rc = fwd_pair(fb, 2, fp, 2, prec, st);                 // both on the same critic: one launch of N + Nt rows (0.384 -> 0.380 ms/step)
+    rc = launch_mlp3_forward(fb, 2, fp, 2, ACT_RELU, prec, st);                 // both on the same critic: one launch of N + Nt rows (0.384 -> 0.380 ms/step)
   } else {
-    rc = fwd_pair(fb, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
-                                  prec == 4 ? w.eh1a : nullptr), 1, prec, st);
-    if (!rc) rc = fwd_one(fp, 2, prec, st);
+    rc = launch_mlp3_forward(fb, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                                             prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
+    if (!rc) rc = launch_mlp3_forward(fp, 2, ACT_RELU, prec, st);
   }
   if (rc) return rc;
   hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, stats);
@@ -430,7 +394,7 @@ static int actor_backward_impl(const MobodyTrainDims* d, const MobodyHyper* h, c
   if (rc) return rc;
   MB_REQUIRE(h && actor_blob && actor_blob_T && q_blob && q_blob_T && state && action && stats && (grad_actor || adam.on) &&
                  loss_out && workspace, "mobody_actor_backward: null pointer");
-  rc = check_prec(h, "mobody_actor_backward", true);
+  rc = check_precision("mobody_actor_backward", h->precision, true);
   if (rc) return rc;
   TrainWs w;
   rc = carve(*d, workspace, w);
@@ -485,7 +449,8 @@ extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const 
   int rc = mobody_mlp_layout(in_dim, out_dim, members, &L);
   if (rc) return rc;
   MB_REQUIRE(blob && blob_T, "mobody_mlp_transpose: null pointer");
-  MB_REQUIRE(precision >= 0 && precision <= 4, "mobody_mlp_transpose: precision must be 0..4");
+  rc = check_precision("mobody_mlp_transpose", precision, true);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_mlp_transpose, dim3((unsigned)cdiv(L.t_total_floats, 256)), dim3(256), 0, as_stream(stream), L, blob, blob_T,
                      precision, health_words());
   MB_LAUNCH_OK("k_mlp_transpose");
@@ -515,7 +480,8 @@ static int adam_impl(int in_dim, int out_dim, int members, float* blob, float* b
   if (rc) return rc;
   MB_REQUIRE(blob && grad && m && v, "mobody_adam_polyak: null pointer");
   MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_adam_polyak: step t must be >= 1");
-  MB_REQUIRE(precision >= 0 && precision <= 4, "mobody_adam_polyak: precision must be 0..4");
+  rc = check_precision("mobody_adam_polyak", precision, true);
+  if (rc) return rc;
   AdamTarget a = adam_target(blob, blob_T, m, v, target, t, t_dev, lr, tau, grad_scale, precision);
   a.target_T = a.target ? target_T : nullptr;
   hipStream_t st = as_stream(stream);
