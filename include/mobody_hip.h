@@ -413,6 +413,30 @@ int mobody_critic_update_phase(const MobodyTrainDims* d, const MobodyHyper* h, c
                                const float* q_next, float* m, float* v, int64_t t, const int64_t* t_dev, float lr, float* loss_out,
                                float* workspace, int policy_forward, int64_t* bump, int phase, void* stream);
 
+/* mobody_gather_batch_rng + mobody_critic_update in one call and one launch fewer: the step's first forward launch (twin-Q(s,a)
+ * next to pi(s')) draws its tiles' row indices and takes the rows straight from the rings, and writes the minibatch arrays
+ * state .. not_done (outputs here) for the launches behind it and for the caller.  Same draws, same bump words, bit-identical
+ * results to the two calls.  `gr` carries mobody_gather_batch_rng's host arrays; its counts must add up to d->N.  Refused with
+ * MOBODY_E_ARG: a source with rows to draw that is not a row-interleaved ring (mobody_ring_pitch), q_next != NULL, phase != 0
+ * (the argument exists so that a caller of mobody_critic_update_phase gets a message, not a wrong step). */
+typedef struct MobodyGatherRng {
+  const MobodyBufferView* bufs;
+  const int64_t* counts;
+  int nbuf;
+  const uint32_t* seeds;
+  const int64_t* call_offsets;
+  const int64_t* counter;
+  const int64_t* const* sizes;
+  int64_t* const* bump;
+  int nbump;
+} MobodyGatherRng;
+int mobody_critic_update_gather(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
+                                float* q_blob, float* q_blob_T, float* qtarg_blob, float* qtarg_blob_T, float* state,
+                                float* action, float* next_state, float* reward, float* not_done, const float* q_next,
+                                float* m, float* v, int64_t t, const int64_t* t_dev, float lr, float* loss_out,
+                                float* workspace, int policy_forward, int64_t* bump, int phase, const MobodyGatherRng* gr,
+                                void* stream);
+
 /* Single-GPU form of mobody_actor_backward + mobody_adam_polyak (mobody.py:554-578), as mobody_critic_update. */
 int mobody_actor_update(const MobodyTrainDims* d, const MobodyHyper* h, float* actor_blob, float* actor_blob_T,
                         const float* q_blob, const float* q_blob_T, const float* state, const float* action,

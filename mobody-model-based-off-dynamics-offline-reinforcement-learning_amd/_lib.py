@@ -60,6 +60,12 @@ class MobodyHyper(C.Structure):
                 ("q_weighted", i32), ("scale_q", i32), ("precision", i32)]
 
 
+class MobodyGatherRng(C.Structure):
+    _fields_ = [("bufs", C.POINTER(MobodyBufferView)), ("counts", C.POINTER(i64)), ("nbuf", C.c_int), ("seeds", C.POINTER(u32)),
+                ("call_offsets", C.POINTER(i64)), ("counter", vp), ("sizes", C.POINTER(vp)), ("bump", C.POINTER(vp)),
+                ("nbump", C.c_int)]
+
+
 class MobodyEnsStep(C.Structure):
     _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
                 ("mopo_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32), ("task", i32), ("obs", vp), ("act", vp),
@@ -134,6 +140,9 @@ PROTOTYPES = {
                                      vp, vp, vp, vp, vp, vp, C.c_int, vp]),
     "mobody_critic_update": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, vp]),
+    "mobody_critic_update_gather": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                              vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, C.c_int,
+                                              C.POINTER(MobodyGatherRng), vp]),
     "mobody_critic_update_phase": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                              vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, C.c_int, vp]),
     "mobody_actor_update": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp,

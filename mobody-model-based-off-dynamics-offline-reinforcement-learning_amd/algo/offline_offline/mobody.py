@@ -556,8 +556,16 @@ class MOBODY(object):
         def fused_step():
             # no launch of its own for the three counters: the gather draws with call id c[0] + 1 and advances the two Adam
             # step counts (it does not read them), the critic's optimizer launch advances c[0] (the gather is done with it)
-            ops.gather_batch_rng([rb._fields() for rb in bufs], cnts, seeds, [1] * len(bufs), c[0:1],
-                                 [rb.ptr_size[1:2] for rb in bufs], S, A, b, bump=(c[1:2], c[2:3], c[3:4]))
+            gather = dict(buffers=[rb._fields() for rb in bufs], counts=cnts, seeds=seeds, call_offsets=[1] * len(bufs),
+                          counter=c[0:1], sizes=[rb.ptr_size[1:2] for rb in bufs], bump=(c[1:2], c[2:3], c[3:4]))
+            if self._gather_in_forward(gather["buffers"]):
+                # nothing reads the minibatch before the critic's first forward launch: that launch draws and fetches the rows
+                # itself and leaves the minibatch arrays behind for the launches after it (one launch and one pass fewer)
+                self.critic_update(b, N, Nt, t_dev=c[1:2], bump=c[0:1], gather=gather)
+                self.actor_stats(b, N, Nt, N, Nt)
+                self.actor_update(b, N, Nt, t_dev=c[2:3])
+                return
+            ops.gather_batch_rng(S=S, A=A, out=b, **gather)
             if par and not cfg["advantage"] and int(cfg.get("par_overlap", 1)):
                 # The ensemble step that relabels the source rewards (mobody.py:428-434) runs on a side stream NEXT TO the
                 # critic's forwards -- none of them reads the rewards, the TD error in the backward's prologue is the first
@@ -607,6 +615,15 @@ class MOBODY(object):
                 actor_apply()
             return [whole_step]
         return [critic, critic_apply_actor_stats, actor, actor_apply]
+
+    def _gather_in_forward(self, views):
+        """The captured single-GPU step lets the critic's first forward launch gather the minibatch (config['fused_gather'],
+        default 1) when nothing needs the rows before it: 'par' relabels the source rewards from them, `advantage` runs the V
+        update on them and 'dara' rewrites rewards through its classifier inputs; the draw has to be the device generator's and
+        every source a row-interleaved ring."""
+        return bool(int(self.config.get("fused_gather", 1)) and self.penalty_type not in ("par", "dara")
+                    and not self.config["advantage"] and self.rng == "device"
+                    and all(isinstance(v, ops.RingView) for v in views))
 
     def _graph_step(self, src, tar, batch_size):
         world = self._world()
@@ -820,9 +837,9 @@ class MOBODY(object):
         between); not in the advantage variant, whose critic call has no target-Q launch."""
         return not self.config["advantage"]
 
-    def critic_update(self, b, N, Nt, t_dev=None, bump=None, phase=0):
+    def critic_update(self, b, N, Nt, t_dev=None, bump=None, phase=0, gather=None):
         """critic_grad + critic_apply in the fused single-GPU form (same arithmetic, no gradient blob).  phase 1 / 2: only its
-        forwards / only the backward + update (ops.critic_update)."""
+        forwards / only the backward + update; gather: the first forward launch fills `b` itself (ops.critic_update)."""
         dims, hyp = self._dims(N, Nt, N, Nt)
         q_next = None
         if self.config["advantage"]:
@@ -834,7 +851,7 @@ class MOBODY(object):
         ops.critic_update(dims, hyp, self.policy.blob, self.q_funcs.blob, self.q_funcs.blob_T, self.target_q_funcs.blob, b,
                           o.m, o.v, o.t, o.lr, self._loss[0:1], self._ws, q_next=q_next, t_dev=t_dev,
                           policy_forward=self._policy_rides_along(), actor_blob_T=self.policy.blob_T,
-                          qtarg_blob_T=self.target_q_funcs.blob_T, bump=bump, phase=phase)
+                          qtarg_blob_T=self.target_q_funcs.blob_T, bump=bump, phase=phase, gather=gather)
 
     def actor_update(self, b, N, Nt, t_dev=None):
         dims, hyp = self._dims(N, Nt, N, Nt)

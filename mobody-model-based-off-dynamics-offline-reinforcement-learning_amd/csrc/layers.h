@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "../../include/mobody_hip.h"
+#include "gather.h"
 #include "tile.h"
 
 namespace mobody {
@@ -192,6 +193,20 @@ inline void fwd_set_saves(Mlp3FwdArgs& a, float* x, long long x_ms, float* h1, i
   a.save_x = x; a.x_ms = x_ms; a.save_h1 = h1; a.save_h2 = h2; a.mask1 = m1; a.mask2 = m2; a.save_d1 = d1; a.save_d2 = d2;
 }
 
+// The gathering input stage of a paired launch (the train step's first forward, twin-Q(s,a) next to pi(s')): the tiles draw
+// and fetch their own ring rows (gather.h) instead of reading a minibatch another launch assembled.  Net k's input tile is
+// columns [off[k], off[k] + n[k]) of the packed ring row; `g` also names the minibatch arrays the launch still writes for the
+// launches behind it.  Travels as a kernel argument of its own: Mlp3FwdArgs keeps its layout.
+struct FwdGather {
+  GatherArgs g;
+  int off[2], n[2];
+};
+// net k (0 = a, 1 = b) of the paired launch reads the columns from `off` of the ring row where it read its sources
+inline void fwd_set_gather(FwdGather& fg, int k, const Mlp3FwdArgs& a, int off) {
+  fg.off[k] = off; fg.n[k] = a.n[0] + a.n[1] + a.n[2];
+}
+constexpr int FWD_GATHER_NQ = 2;                 // 16-byte chunks a lane holds per row: a tile's part of a ring row is <= 32 chunks
+
 // Output-layer width -> the NT of the kernel instantiations (16-column tiles of the K-split narrow layer; 0 = any width):
 // f(std::integral_constant<int, NT>)
 template <class F>
@@ -207,6 +222,14 @@ int launch_mlp3_forward(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& 
 inline int launch_mlp3_forward(const Mlp3FwdArgs& a, int members, int act, int prec, hipStream_t st) {
   return launch_mlp3_forward(a, members, Mlp3FwdArgs{}, 0, act, prec, st);
 }
+
+// The same pair of ReLU nets with the gathering input stage: a = twin-Q on state | action, b = the actor on next_state, of
+// one minibatch of fg.g (every source a packed ring).  Pairs the gathering kernels do not cover (nets that cannot share a
+// launch, ring rows longer than the stage holds) run the stand-alone gather and then the plain launch: same results.
+int launch_mlp3_forward_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg,
+                               int prec, hipStream_t st);
+int launch_mlp3_fwd_bf_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg,
+                              int prec, hipStream_t st);
 
 // Row-tile height of the fused 3-layer MLP kernels (forward and backward; the callers size the bias partials and the sign
 // words by it).  Measured on MI355X (bench.py, S=17/A=6): 32-row tiles (33 KB LDS, ~124 VGPRs -> 4 workgroups = 16 waves
@@ -227,6 +250,82 @@ __device__ __forceinline__ int fwd_load_sources(const Mlp3FwdArgs& a, int m, flo
     }
   }
   return c0;
+}
+
+// ---- gathering input stage (FwdGather): what replaces the tile load, and the minibatch arrays the tile owes ----
+// The tile's 32 rows, two per 16-lane group as k_gather_rows<2, .> takes them: lanes 0 and 1 of a group form the source
+// pointers of rows g and g + 16 (buffer by start[], then an explicit index or one Philox draw: gather_src) and hand them over
+// by shuffle; every lane requests its 16-byte chunks of both rows -- unconditional, from a clamped row and chunk -- before
+// the first LDS store.  Only the chunks that hold the tile's own columns travel: [off, off + n) for the twin-Q tiles,
+// [off, off + n + 2) for the pi(s') tile, which also owes reward and not_done (they follow next_state in the ring row) and
+// stores them straight from the registers.  Xs ends up as tile_load2 / tile_load leave it: rows past the batch are zero.
+template <int NQ>
+__device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here) {
+  const GatherArgs& g = fg.g;
+  const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4;
+  const long long N = g.start[g.nbuf];
+  const float* mine = nullptr;
+  if (lane < 2) {
+    const long long r = min(row0 + 16 * lane + grp, N - 1);
+    int k;
+    const long long src = gather_src(g, r, k);
+    mine = g.bufs[k].state + src * g.bufs[k].pitch;
+  }
+  const int off = second ? fg.off[1] : fg.off[0], n = second ? fg.n[1] : fg.n[0];
+  const int q0 = off >> 2, q1 = (off + n + (second ? 2 : 0) + 3) >> 2;      // this tile's chunks of the row
+  v4f v[2][NQ];
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const gather_ptr_t rp = gather_group_row(mine, p);
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) v[p][j] = rp[min(q0 + lane + 16 * j, q1 - 1)];
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int r = 16 * p + grp;
+    const bool ok = r < rows_here;
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      const int q = q0 + lane + 16 * j;
+      if (q >= q1) continue;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = 4 * q + e - off;
+        if (c >= 0 && c < n) Xs[r * LDX + c] = ok ? v[p][j][e] : 0.f;
+        if (second && ok && c == n) g.reward[row0 + r] = v[p][j][e];
+        if (second && ok && c == n + 1) g.not_done[row0 + r] = v[p][j][e];
+      }
+    }
+  }
+}
+
+// Returns the width of the input tile, as fwd_load_sources.  One thread of the launch advances the bump words.
+__device__ __forceinline__ int fwd_gather_tile(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here) {
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
+    for (int k = 0; k < fg.g.nbump; ++k) fg.g.bump[k][0] += 1;
+  const int off = second ? fg.off[1] : fg.off[0], n = second ? fg.n[1] : fg.n[0];
+  if (((off + n + (second ? 2 : 0) + 3) >> 2) - (off >> 2) <= 16) fwd_gather_rows<1>(fg, second, Xs, row0, rows_here);
+  else fwd_gather_rows<FWD_GATHER_NQ>(fg, second, Xs, row0, rows_here);
+  return n;
+}
+
+// After the input barrier: the contiguous minibatch arrays, every element written once per launch -- state and action by
+// the member-0 twin-Q tile of a row block, next_state by the pi(s') tile (all 256 threads, consecutive addresses).
+__device__ __forceinline__ void fwd_gather_save(const FwdGather& fg, bool second, int m, const float* Xs, long long row0, int rows_here) {
+  const GatherArgs& g = fg.g;
+  auto put = [&](float* out, int col0, int n) {
+    const uint32_t magic = div_magic(n);
+    for (int e = threadIdx.x; e < rows_here * n; e += NTHREADS) {
+      const int r = fast_div(e, magic, n);
+      out[row0 * n + e] = Xs[r * LDX + col0 + (e - r * n)];
+    }
+  };
+  if (second) {
+    put(g.next_state, 0, g.S);
+  } else if (m == 0) {
+    put(g.state, 0, g.S);
+    put(g.action, g.S, g.A);
+  }
 }
 
 // Optional copy of the padded input tile for the weight gradients: same thread <-> element map as tile_load (no division).

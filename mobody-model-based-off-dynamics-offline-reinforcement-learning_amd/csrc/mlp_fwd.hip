@@ -42,8 +42,10 @@ __device__ __forceinline__ void mlp3_fwd_tail(const Mlp3FwdArgs& a, int m, float
 }
 
 // NT: 16-column tiles of the output layer handled by the K-split narrow layer (Np3 == 16*NT), or 0 = any Np3.
-template <int ACT, int NT>
-__device__ __forceinline__ void mlp3_fwd_tile(const Mlp3FwdArgs& a, int m, float* Xs) {
+// GATHER: the input tile comes straight from the replay rings (layers.h fwd_gather_tile); fg / second: the stage's arguments and
+// which net of the pair this tile belongs to
+template <int ACT, int NT, bool GATHER = false>
+__device__ __forceinline__ void mlp3_fwd_tile(const Mlp3FwdArgs& a, int m, float* Xs, const FwdGather* fg = nullptr, bool second = false) {
   const long long row0 = (long long)blockIdx.x * TB;
   const int rows_here = (int)min((long long)TB, a.rows - row0);
   const float* w1 = a.w1 + m * a.sw1;
@@ -51,10 +53,12 @@ __device__ __forceinline__ void mlp3_fwd_tile(const Mlp3FwdArgs& a, int m, float
   TR(0);
   WideRing ring;
   wide_prefetch(w1, a.Kp1, ring);                 // W1 fragments travel while the input tile is fetched
-  tile_zero_cols(Xs, fwd_load_sources(a, m, Xs, row0, rows_here), a.Kp1, TB);
+  if constexpr (GATHER) tile_zero_cols(Xs, fwd_gather_tile(*fg, second, Xs, row0, rows_here), a.Kp1, TB);
+  else tile_zero_cols(Xs, fwd_load_sources(a, m, Xs, row0, rows_here), a.Kp1, TB);
   lds_barrier();
   TR(1);
   fwd_save_x(a, m, Xs, row0, rows_here);
+  if constexpr (GATHER) fwd_gather_save(*fg, second, m, Xs, row0, rows_here);
   const FwdTileOut t = fwd_tile_out(a, m, row0);
   float* h1 = t.h1;
   wide_layer<ACT, MLP_MT>(Xs, w1, a.b1 + m * a.sb1, a.Kp1, ring,
@@ -87,6 +91,16 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_mlp3_fwd2(Mlp3FwdArgs a, Mlp3Fw
   mlp3_fwd_tile<ACT, NT>(s, second ? (int)blockIdx.y - members_a : (int)blockIdx.y, Xs);
 }
 
+// k_mlp3_fwd2 with the gathering input stage (a kernel of its own: the stage's arguments are a fourth kernel argument)
+template <int NT>
+__global__ __launch_bounds__(NTHREADS, 2) void k_mlp3_fwd2_gather(Mlp3FwdArgs a, Mlp3FwdArgs b, int members_a, FwdGather fg) {
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  const bool second = (int)blockIdx.y >= members_a;
+  const Mlp3FwdArgs s = second ? b : a;
+  if ((long long)blockIdx.x * TB >= s.rows) return;
+  mlp3_fwd_tile<ACT_RELU, NT, true>(s, second ? (int)blockIdx.y - members_a : (int)blockIdx.y, Xs, &fg, second);
+}
+
 template <int ACT, int NT>
 static int launch_fwd_t(const Mlp3FwdArgs& a, int members, hipStream_t stream) {
   size_t lds = (size_t)TB * LDX * sizeof(float);
@@ -117,6 +131,21 @@ static int launch_fwd2_t(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs&
   ProfScope prof(PROF_MLP_FWD, stream);
   hipLaunchKernelGGL((k_mlp3_fwd2<ACT_RELU, NT>), grid, dim3(NTHREADS), lds, stream, a, b, members_a);
   MB_LAUNCH_OK("k_mlp3_fwd2");
+  return 0;
+}
+
+static int launch_fwd2_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg, hipStream_t stream) {
+  size_t lds = (size_t)TB * LDX * sizeof(float);
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_fwd2_gather<1>, 160 * 1024);
+    if (rc) return rc;
+    once = true;
+  }
+  dim3 grid((unsigned)cdiv(a.rows, TB), (unsigned)(members_a + members_b));
+  ProfScope prof(PROF_MLP_FWD, stream);
+  hipLaunchKernelGGL(k_mlp3_fwd2_gather<1>, grid, dim3(NTHREADS), lds, stream, a, b, members_a, fg);
+  MB_LAUNCH_OK("k_mlp3_fwd2_gather");
   return 0;
 }
 
@@ -158,6 +187,27 @@ int launch_mlp3_forward(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& 
     return rc ? rc : one(b, members_b);
   }
   return prec == PREC_F32 ? launch_fwd_pair(a, members_a, b, members_b, st) : launch_mlp3_fwd_bf(a, members_a, b, members_b, act, prec, st);
+}
+
+int launch_mlp3_forward_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg,
+                               int prec, hipStream_t st) {
+  const GatherArgs& g = fg.g;
+  const long long N = g.start[g.nbuf];
+  if (N <= 0 || members_a <= 0 || members_b <= 0) return fail(MOBODY_E_ARG, "launch_mlp3_forward_gather: needs both nets and a non-empty minibatch");
+  if (a.rows != N || b.rows != N) return fail(MOBODY_E_ARG, "launch_mlp3_forward_gather: the nets run on %lld / %lld rows, the minibatch has %lld", a.rows, b.rows, N);
+  for (int k = 0; k < g.nbuf; ++k)
+    if (!g.packed[k] && g.start[k + 1] > g.start[k]) return fail(MOBODY_E_ARG, "launch_mlp3_forward_gather: source %d is not a packed ring", k);
+  if (fg.off[0] != 0 || fg.n[0] != g.S + g.A || fg.off[1] != g.S + g.A || fg.n[1] != g.S)
+    return fail(MOBODY_E_ARG, "launch_mlp3_forward_gather: net a reads state | action, net b next_state");
+  auto chunks = [](int off, int n) { return ((off + n + 3) >> 2) - (off >> 2); };
+  // the instances that exist: a one-output twin-Q (NT = 1) next to an actor of the same output-layer width, or -- f16x2 -- of width 32
+  const bool built = a.Np3 == 16 && (b.Np3 == 16 || (prec == PREC_F16X2 && b.Np3 == 32)) && nets_share_launch(a, b, ACT_RELU, prec) &&
+                     chunks(fg.off[0], fg.n[0]) <= 16 * FWD_GATHER_NQ && chunks(fg.off[1], fg.n[1] + 2) <= 16 * FWD_GATHER_NQ;
+  if (!built) {
+    int rc = launch_gather(g, N, st);
+    return rc ? rc : launch_mlp3_forward(a, members_a, b, members_b, ACT_RELU, prec, st);
+  }
+  return prec == PREC_F32 ? launch_fwd2_gather(a, members_a, b, members_b, fg, st) : launch_mlp3_fwd_bf_gather(a, members_a, b, members_b, fg, prec, st);
 }
 
 }  // namespace mobody

@@ -15,8 +15,10 @@ constexpr int FWD_L1_RING = 3;                  // layer 1 is K = 24 .. 120: a s
 constexpr int FWD_F16_WAVES = 4;                // waves per SIMD the f16x2 inference forward is compiled for (launch bounds)
 
 // DS: training forward of a Swish net -- save_d1 / save_d2 receive the derivatives next to h1 (planes or rows) / h2
-template <int ACT, int PM, int NT, bool DS = false>
-__device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, float* Xs) {
+// GATHER: the input tile comes straight from the replay rings (layers.h fwd_gather_tile); fg / second: the stage's arguments and
+// which net of the pair this tile belongs to
+template <int ACT, int PM, int NT, bool DS = false, bool GATHER = false>
+__device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, float* Xs, const FwdGather* fg = nullptr, bool second = false) {
   char* Ps = reinterpret_cast<char*>(Xs);
   float* scr = reinterpret_cast<float*>(Ps + split_scr_offset<PM, TB>());
   const long long row0 = (long long)blockIdx.x * TB;
@@ -30,7 +32,9 @@ __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, fl
   WideRingT<FWD_L1_RING> ring;
   wide_prefetch(w1, a.Kp1, ring);
   int c0;
-  if (a.n[0] <= 32 && a.n[1] <= 32 && a.n[2] == 0) {       // state | action: both sources in one round trip
+  if constexpr (GATHER) {
+    c0 = fwd_gather_tile(*fg, second, Xs, row0, rows_here);
+  } else if (a.n[0] <= 32 && a.n[1] <= 32 && a.n[2] == 0) {       // state | action: both sources in one round trip
     tile_load2<TB>(Xs, a.src[0] + m * a.src_ms[0] + row0 * a.ld[0], a.ld[0], a.n[0],
                    a.n[1] > 0 ? a.src[1] + m * a.src_ms[1] + row0 * a.ld[1] : nullptr, a.ld[1], a.n[1], rows_here);
     c0 = a.n[0] + a.n[1];
@@ -41,6 +45,7 @@ __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, fl
   lds_barrier();
   TR(1);
   fwd_save_x(a, m, Xs, row0, rows_here);
+  if constexpr (GATHER) fwd_gather_save(*fg, second, m, Xs, row0, rows_here);
   const FwdTileOut t = fwd_tile_out(a, m, row0);
   float* d1 = DS ? a.save_d1 + ((long long)m * a.rows + row0) * HID : nullptr;
   float* d2 = DS ? a.save_d2 + ((long long)m * a.rows + row0) * HID : nullptr;
@@ -87,6 +92,51 @@ __global__ __launch_bounds__(NTHREADS, (PM == 4 && !DS) ? FWD_F16_WAVES : 2) voi
   } else {
     if (second) mlp3_fwd_bf_tile<ACT, PM, NT2, DS>(s, (int)blockIdx.y - members_a, Xs);
     else mlp3_fwd_bf_tile<ACT, PM, NT, DS>(s, (int)blockIdx.y, Xs);
+  }
+}
+
+// The paired ReLU launch with the gathering input stage (a kernel of its own: the stage's arguments are a fourth kernel
+// argument, and every other instance keeps its signature and its code).  Same occupancy target as its plain twin.
+template <int PM, int NT, int NT2 = NT>
+__global__ __launch_bounds__(NTHREADS, PM == 4 ? FWD_F16_WAVES : 2) void k_mlp3_fwd_bf_gather(Mlp3FwdArgs a, Mlp3FwdArgs b, int members_a, FwdGather fg) {
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  const bool second = (int)blockIdx.y >= members_a;
+  const Mlp3FwdArgs s = second ? b : a;
+  if ((long long)blockIdx.x * TB >= s.rows) return;
+  if constexpr (NT2 == NT) {
+    mlp3_fwd_bf_tile<ACT_RELU, PM, NT, false, true>(s, second ? (int)blockIdx.y - members_a : (int)blockIdx.y, Xs, &fg, second);
+  } else {
+    if (second) mlp3_fwd_bf_tile<ACT_RELU, PM, NT2, false, true>(s, (int)blockIdx.y - members_a, Xs, &fg, true);
+    else mlp3_fwd_bf_tile<ACT_RELU, PM, NT, false, true>(s, (int)blockIdx.y, Xs, &fg, false);
+  }
+}
+
+template <int PM, int NT, int NT2 = NT>
+static int launch_bf_gather_t(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg, hipStream_t st) {
+  constexpr size_t lds = split_lds_bytes<PM, TB>();
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_fwd_bf_gather<PM, NT, NT2>, 160 * 1024);
+    if (rc) return rc;
+    once = true;
+  }
+  ProfScope prof(PROF_MLP_FWD, st);
+  hipLaunchKernelGGL((k_mlp3_fwd_bf_gather<PM, NT, NT2>), dim3((unsigned)cdiv(a.rows, TB), (unsigned)(members_a + members_b)),
+                     dim3(NTHREADS), lds, st, a, b, members_a, fg);
+  MB_LAUNCH_OK("k_mlp3_fwd_bf_gather");
+  return 0;
+}
+
+// the pairs the gathering kernels are built for (launch_mlp3_forward_gather has checked them): a one-output twin-Q next to
+// an actor of up to 16 actions in every split mode, of up to 32 in f16x2
+int launch_mlp3_fwd_bf_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg,
+                              int prec, hipStream_t st) {
+  if (prec == PREC_F16X2 && b.Np3 == 32) return launch_bf_gather_t<4, 1, 2>(a, members_a, b, members_b, fg, st);
+  switch (prec) {
+    case PREC_BF16: return launch_bf_gather_t<1, 1>(a, members_a, b, members_b, fg, st);
+    case PREC_BF16X2: return launch_bf_gather_t<2, 1>(a, members_a, b, members_b, fg, st);
+    case PREC_BF16X3: return launch_bf_gather_t<3, 1>(a, members_a, b, members_b, fg, st);
+    default: return launch_bf_gather_t<4, 1>(a, members_a, b, members_b, fg, st);
   }
 }
 

@@ -13,38 +13,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gather.h"
 #include "rng.h"
 
 namespace mobody {
 
 constexpr int ROWS_WG = 16;
-
-__host__ __device__ inline bool view_packed(const MobodyBufferView& b, int S, int A) {
-  return b.pitch > 0 && b.pitch % 16 == 0 && b.pitch >= 2LL * S + A + 2 && (reinterpret_cast<uintptr_t>(b.state) & 15) == 0 &&
-         b.action == b.state + S && b.next_state == b.action + A && b.reward == b.next_state + S && b.not_done == b.reward + 1;
-}
-
-struct GatherArgs {
-  MobodyBufferView bufs[3];
-  int packed[3];            // view_packed(bufs[k])
-  const int32_t* idx[3];    // explicit row indices, or null -> drawn on the fly from the device generator
-  long long start[4];       // row offsets of each source inside the output, start[nbuf] = N
-  int nbuf, S, A, WS;       // WS = staged floats per row (2S+A+2 rounded up to 4)
-  float *state, *action, *next_state, *reward, *not_done;
-  // device-RNG mode (idx[k] == null): index i of source k = philox(seed[k], STREAM_SAMPLE, call)[i] * size >> 32,
-  // call = (counter ? counter[0] : 0) + call_offset[k], size read from the device word size[k][0]
-  uint32_t seed[3];
-  long long call_offset[3];
-  const long long* counter;
-  const long long* size[3];
-  long long* bump[4];       // device words incremented by one thread (never `counter`): graph replay advances its step counts here
-  int nbump;
-};
-
-// e / n for 0 <= e < 2^16 and 1 <= n <= 2^16 through one multiply-high with ceil(2^32 / n) (exact in that range; a runtime
-// integer division costs ~20 vector instructions per element of the staging loops)
-__host__ __device__ inline uint32_t div_magic(int n) { return (uint32_t)((0x100000000ULL + (uint32_t)n - 1) / (uint32_t)n); }
-__device__ __forceinline__ int fast_div(int e, uint32_t magic, int n) { return n == 1 ? e : (int)__umulhi((uint32_t)e, magic); }
 
 // field block f of `rows` staged rows -> contiguous output rows (all 256 threads, consecutive addresses)
 __device__ __forceinline__ void stage_to_batch(const float* stage, int WS, int off, int n, int rows, float* out) {
@@ -53,17 +27,6 @@ __device__ __forceinline__ void stage_to_batch(const float* stage, int WS, int o
     const int r = fast_div(e, magic, n), c = e - r * n;
     out[e] = stage[r * WS + off + c];
   }
-}
-
-// Source row of output row r (and which buffer it comes from): an explicit index, or one Philox draw.
-__device__ __forceinline__ long long gather_src(const GatherArgs& a, long long r, int& k) {
-  k = 0;
-  if (a.nbuf > 1 && r >= a.start[1]) k = 1;
-  if (a.nbuf > 2 && r >= a.start[2]) k = 2;
-  if (a.idx[k] != nullptr) return a.idx[k][r - a.start[k]];
-  const uint32_t call = (uint32_t)((a.counter ? a.counter[0] : 0) + a.call_offset[k]);
-  const long long sz = a.size[k][0];
-  return rng_index_at(a.seed[k], STREAM_SAMPLE, call, (uint64_t)(r - a.start[k]), (uint32_t)(sz > 0 ? sz : 1));
 }
 
 // Row-interleaved sources (every buffer a packed ring): 16 * P rows per workgroup, P rows per 16-lane group.
@@ -93,16 +56,10 @@ __global__ __launch_bounds__(256) void k_gather_rows(GatherArgs a) {
     const long long src = gather_src(a, r, k);
     mine = a.bufs[k].state + src * a.bufs[k].pitch;
   }
-  // (plain vector types and global-address-space pointers: with HIP's float4 struct and a pointer rebuilt from two shuffled
-  //  words the compiler emitted flat loads and kept the rows in SCRATCH memory -- 131 us per million rows instead of 85)
-  typedef float v4f __attribute__((ext_vector_type(4)));
-  typedef const __attribute__((address_space(1))) v4f* gptr_t;
-  v4f v[P][NQ];
+  v4f v[P][NQ];                                      // (gather.h on why these types)
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-    const unsigned long long up = (unsigned long long)mine;
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)up, (threadIdx.x & 48) + p, 64), hi = (unsigned)__shfl((int)(unsigned)(up >> 32), (threadIdx.x & 48) + p, 64);
-    gptr_t rp = (gptr_t)(((unsigned long long)hi << 32) | lo);
+    const gather_ptr_t rp = gather_group_row(mine, p);
 #pragma unroll
     for (int j = 0; j < NQ; ++j) v[p][j] = rp[min(lane + 16 * j, nq - 1)];
   }
@@ -173,7 +130,7 @@ static void launch_gather_rows(const GatherArgs& a, long long N, hipStream_t st)
   hipLaunchKernelGGL((k_gather_rows<P, NQ>), dim3((unsigned)cdiv(N, ROWS_WG * P)), dim3(256), lds, st, a);
 }
 
-static int launch_gather(const GatherArgs& a, long long N, hipStream_t st) {
+int launch_gather(const GatherArgs& a, long long N, hipStream_t st) {
   const size_t lds = (size_t)ROWS_WG * a.WS * sizeof(float);
   if (lds > 64 * 1024) return fail(MOBODY_E_ARG, "gather: rows of %d floats do not fit the LDS stage", a.WS);
   bool all_packed = true;
@@ -455,6 +412,28 @@ static int gather_common(const char* who, GatherArgs& a, const MobodyBufferView*
   return 0;
 }
 
+int mobody::gather_args_rng(const char* who, GatherArgs& a, const MobodyBufferView* bufs, const int64_t* counts, int nbuf, int S, int A,
+                            const uint32_t* seeds, const int64_t* call_offsets, const int64_t* counter, const int64_t* const* sizes,
+                            float* state, float* action, float* next_state, float* reward, float* not_done, int64_t* const* bump,
+                            int nbump, long long& N) {
+  N = 0;
+  MB_REQUIRE(bufs && counts && seeds && call_offsets && sizes && nbuf >= 1 && nbuf <= 3, "%s: need 1..3 source buffers", who);
+  MB_REQUIRE(nbump >= 0 && nbump <= 4 && (nbump == 0 || bump), "%s: at most 4 words to advance", who);
+  int rc = gather_common(who, a, bufs, counts, nbuf, S, A, state, action, next_state, reward, not_done, N);
+  if (rc || N == 0) return rc;
+  for (int k = 0; k < nbuf; ++k) {
+    MB_REQUIRE(counts[k] == 0 || sizes[k], "%s: null size word of source %d", who, k);
+    a.idx[k] = nullptr; a.seed[k] = seeds[k]; a.call_offset[k] = call_offsets[k]; a.size[k] = (const long long*)sizes[k];
+  }
+  a.counter = (const long long*)counter;
+  for (int k = 0; k < nbump; ++k) {
+    MB_REQUIRE(bump[k] && bump[k] != counter, "%s: bump word %d is null or the call counter itself", who, k);
+    a.bump[k] = (long long*)bump[k];
+  }
+  a.nbump = nbump;
+  return 0;
+}
+
 extern "C" int mobody_gather_batch(const MobodyBufferView* bufs, const int32_t* const* idx, const int64_t* counts,
                                    int nbuf, int S, int A, float* state, float* action, float* next_state,
                                    float* reward, float* not_done, void* stream) {
@@ -490,21 +469,10 @@ extern "C" int mobody_gather_batch_rng(const MobodyBufferView* bufs, const int64
                                        const uint32_t* seeds, const int64_t* call_offsets, const int64_t* counter,
                                        const int64_t* const* sizes, float* state, float* action, float* next_state,
                                        float* reward, float* not_done, int64_t* const* bump, int nbump, void* stream) {
-  MB_REQUIRE(bufs && counts && seeds && call_offsets && sizes && nbuf >= 1 && nbuf <= 3, "mobody_gather_batch_rng: need 1..3 source buffers");
-  MB_REQUIRE(nbump >= 0 && nbump <= 4 && (nbump == 0 || bump), "mobody_gather_batch_rng: at most 4 words to advance");
   GatherArgs a{};
   long long N;
-  int rc = gather_common("mobody_gather_batch_rng", a, bufs, counts, nbuf, S, A, state, action, next_state, reward, not_done, N);
+  int rc = gather_args_rng("mobody_gather_batch_rng", a, bufs, counts, nbuf, S, A, seeds, call_offsets, counter, sizes, state, action,
+                           next_state, reward, not_done, bump, nbump, N);
   if (rc || N == 0) return rc;
-  for (int k = 0; k < nbuf; ++k) {
-    MB_REQUIRE(counts[k] == 0 || sizes[k], "mobody_gather_batch_rng: null size word of source %d", k);
-    a.idx[k] = nullptr; a.seed[k] = seeds[k]; a.call_offset[k] = call_offsets[k]; a.size[k] = (const long long*)sizes[k];
-  }
-  a.counter = (const long long*)counter;
-  for (int k = 0; k < nbump; ++k) {
-    MB_REQUIRE(bump[k] && bump[k] != counter, "mobody_gather_batch_rng: bump word %d is null or the call counter itself", k);
-    a.bump[k] = (long long*)bump[k];
-  }
-  a.nbump = nbump;
   return launch_gather(a, N, as_stream(stream));
 }

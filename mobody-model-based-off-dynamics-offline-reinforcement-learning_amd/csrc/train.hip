@@ -256,7 +256,9 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
                        const float* state, const float* action,
                        const float* next_state, const float* reward, const float* not_done, const float* q_next,
                        float* grad_q, const AdamTarget& adam, float* loss_out, float* workspace, int policy_forward,
-                       void* stream, int phase = 0) {
+                       void* stream, int phase = 0, const FwdGather* gather = nullptr) {
+  // gather != null (phase 0, q_next == null): state .. not_done are not read by the first forward launch but WRITTEN by it --
+  // its tiles draw and fetch the minibatch rows themselves (layers.h FwdGather; the block arrives with `g` filled)
   // phase: 0 the whole step; 1 only its forwards (nothing of them reads `reward`); 2 only the backward, weight gradients and
   // reduction / optimizer step -- the caller may let another stream finish rewriting `reward` (penalty_type 'par': an ensemble
   // step on the source rows) between the two
@@ -281,7 +283,15 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
   if (phase == 2) {
     // forwards already enqueued by the phase-1 call
   } else if (q_next == nullptr) {
-    rc = launch_mlp3_forward(fq, 2, fwd_args(actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT), 1, ACT_RELU, prec, st);
+    const Mlp3FwdArgs fpn = fwd_args(actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT);
+    if (gather != nullptr) {
+      FwdGather fg = *gather;
+      fwd_set_gather(fg, 0, fq, 0);                // state | action open the ring row, next_state follows them
+      fwd_set_gather(fg, 1, fpn, S + A);
+      rc = launch_mlp3_forward_gather(fq, 2, fpn, 1, fg, prec, st);
+    } else {
+      rc = launch_mlp3_forward(fq, 2, fpn, 1, ACT_RELU, prec, st);
+    }
     // target twin-Q(s', a') (:192) -- and, when the caller asks for it, pi(s) of the coming actor phase in the same
     // launch: the actor is not updated in between, and a twin-Q launch alone is 2.5 workgroups per CU where the
     // merged one is 3.75 (the actor phase then opens with Q(s_t,a_t) alone: exactly 2 per CU)
@@ -332,6 +342,33 @@ extern "C" int mobody_critic_update(const MobodyTrainDims* d, const MobodyHyper*
   at.bump = (long long*)bump;
   return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
                      not_done, q_next, nullptr, at, loss_out, workspace, policy_forward, stream);
+}
+
+extern "C" int mobody_critic_update_gather(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
+                                           const float* actor_blob_T, float* q_blob, float* q_blob_T, float* qtarg_blob,
+                                           float* qtarg_blob_T, float* state, float* action, float* next_state, float* reward,
+                                           float* not_done, const float* q_next, float* m, float* v, int64_t t,
+                                           const int64_t* t_dev, float lr, float* loss_out, float* workspace, int policy_forward,
+                                           int64_t* bump, int phase, const MobodyGatherRng* gr, void* stream) {
+  const char* who = "mobody_critic_update_gather";
+  MB_REQUIRE(h && q_blob && q_blob_T && qtarg_blob && m && v && d && gr, "%s: null pointer", who);
+  MB_REQUIRE(phase == 0, "%s: the step cannot be split (phase %d): the first forward launch writes the minibatch the backward reads", who, phase);
+  MB_REQUIRE(q_next == nullptr, "%s: q_next given: the launch that gathers is the one that evaluates pi(s')", who);
+  MB_REQUIRE(t_dev != nullptr || t >= 1, "%s: step t must be >= 1", who);
+  MB_REQUIRE(bump == nullptr || bump != t_dev, "%s: bump must not be the step word the launch reads", who);
+  FwdGather fg{};
+  long long N;
+  int rc = gather_args_rng(who, fg.g, gr->bufs, gr->counts, gr->nbuf, d->S, d->A, gr->seeds, gr->call_offsets, gr->counter, gr->sizes,
+                           state, action, next_state, reward, not_done, gr->bump, gr->nbump, N);
+  if (rc) return rc;
+  MB_REQUIRE(N == d->N, "%s: the counts add up to %lld rows, the step runs on %lld", who, N, (long long)d->N);
+  for (int k = 0; k < gr->nbuf; ++k)
+    MB_REQUIRE(gr->counts[k] == 0 || fg.g.packed[k], "%s: source %d is not a row-interleaved ring (mobody_ring_pitch)", who, k);
+  AdamTarget at = adam_target(q_blob, q_blob_T, m, v, qtarg_blob, t, t_dev, lr, h->tau, 1.f, h->precision);
+  at.target_T = qtarg_blob_T;
+  at.bump = (long long*)bump;
+  return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
+                     not_done, nullptr, nullptr, at, loss_out, workspace, policy_forward, stream, 0, &fg);
 }
 
 extern "C" int mobody_critic_update_phase(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,

@@ -16,7 +16,7 @@ def default_config(S, A, **over):
                use_src_sa_to_get_target_next_state=1, env_filter=10.0, rollout_from_src=0, fake_batch_scale=0.5,
                advantage=0, scale_Q=1, weight=2.5, bc_coef=1.0, q_weighted=1, filter_bad_rollout=1,
                penalty_coef=0.1, mopo=0, latent_reward=0, encoder_loss_coef=1, domain_loss_coef=0.0,
-               cycle_loss_coef=0.3)
+               cycle_loss_coef=0.3, fused_gather=1)
     cfg.update(over)
     return cfg
 

@@ -270,15 +270,20 @@ def actor_backward(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state,
 
 
 def critic_update(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, m, v, t, lr, loss_out, ws, q_next=None,
-                  t_dev=None, policy_forward=False, actor_blob_T=None, qtarg_blob_T=None, bump=None, phase=0):
+                  t_dev=None, policy_forward=False, actor_blob_T=None, qtarg_blob_T=None, bump=None, phase=0, gather=None):
     """critic_step + Adam + Polyak in the fused single-GPU form (t: host step count, or t_dev: device int64[1]);
     bump: device int64[1] word (not t_dev) the optimizer launch increments by one.  phase 1 / 2: only the forwards / only the
-    backward + update (mobody_critic_update_phase: the caller joins whatever rewrites `reward` in between)."""
+    backward + update (mobody_critic_update_phase: the caller joins whatever rewrites `reward` in between).
+    gather: the arguments of gather_batch_rng up to `sizes`, plus its `bump`, as a dict -- the step's first forward launch then
+    draws and fetches the minibatch itself and WRITES `batch` (mobody_critic_update_gather: packed rings, no q_next, phase 0)."""
     s, a, s2, r, nd = batch
     args = (C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob), ptr(q_blob_T),
             ptr(qtarg_blob), ptr(qtarg_blob_T), ptr(s), ptr(a), ptr(s2), ptr(r), ptr(nd), ptr(q_next), ptr(m),
             ptr(v), int(t), ptr(t_dev), float(lr), ptr(loss_out), ptr(ws), int(bool(policy_forward)), ptr(bump))
-    if phase:
+    if gather is not None:
+        gr, keep = _gather_rng_args(**gather)
+        check(load().mobody_critic_update_gather(*args, int(phase), C.byref(gr), cur_stream()), "mobody_critic_update_gather")
+    elif phase:
         check(load().mobody_critic_update_phase(*args, int(phase), cur_stream()), "mobody_critic_update_phase")
     else:
         check(load().mobody_critic_update(*args, cur_stream()), "mobody_critic_update")
@@ -425,6 +430,18 @@ def adam_polyak_dev(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, 
     check(load().mobody_adam_polyak_dev(in_dim, out_dim, members, ptr(blob), ptr(blob_T), ptr(grad), ptr(m), ptr(v),
                                         ptr(target), ptr(target_T), ptr(t_dev), float(lr), float(tau), float(grad_scale),
                                         prec_id(precision), cur_stream()), "mobody_adam_polyak_dev")
+
+
+def _gather_rng_args(buffers, counts, seeds, call_offsets, counter, sizes, bump=()):
+    """MobodyGatherRng of gather_batch_rng's arguments, and the host arrays it points into (keep them until the call returns)."""
+    n = len(buffers)
+    views = (_lib.MobodyBufferView * n)(*[buffer_view(b) for b in buffers])
+    cnt = (C.c_int64 * n)(*[int(c) for c in counts])
+    sd = (C.c_uint32 * n)(*[int(s) & 0xFFFFFFFF for s in seeds])
+    off = (C.c_int64 * n)(*[int(o) for o in call_offsets])
+    sz = (C.c_void_p * n)(*[ptr(s) for s in sizes])
+    bp = (C.c_void_p * max(1, len(bump)))(*[ptr(t) for t in bump])
+    return _lib.MobodyGatherRng(views, cnt, n, sd, off, ptr(counter), sz, bp, len(bump)), (views, cnt, sd, off, sz, bp)
 
 
 def gather_batch_rng(buffers, counts, seeds, call_offsets, counter, sizes, S, A, out, bump=()):
