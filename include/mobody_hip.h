@@ -527,7 +527,9 @@ int mobody_pretrain_gather(const float* state, const float* action, const float*
  * SUM all-reduce `grad` before mobody_pretrain_adam).  noise6 [6][7][b][16] = the six reparameterisation draws in the
  * reference's order z1(s) z2(s') z3(s) z4(s') z5(s) z6(s), noise7 [7][b][S] = the fake-next-state draw; NULL -> device
  * Philox streams 16..22 at (seed, call).  grad: blob layout; the action encoder that is not used this step
- * (za_trg* on source batches, za_src* on target ones) is left untouched.
+ * (za_trg* on source batches, za_src* on target ones) is left untouched; every other float of `grad` is written, layout
+ * padding (W1 rows >= in_dim, W3 / b3 columns >= out_dim of the three regions) as exactly 0.  The workspace needs no
+ * initialisation: the results do not depend on what it held.
  * loss_out[5] = (loss, transition_loss, encoder_loss, recon_loss, kl_loss). */
 int mobody_pretrain_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
                           const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
