@@ -146,8 +146,9 @@ __device__ __forceinline__ void wide_store_colsum(f32x16 (&acc)[MT][2], float* X
   cs[1] += __shfl_xor(cs[1], 32);
 }
 
-// Seed prologue (BwdSeed modes 1-3): fills Xs[r][0..Np3) for the TB rows of this tile.  All global loads of a pass
-// are independent (one round trip); the loss partials are reduced through `red` (static LDS, 8 floats).
+// Seed prologue (BwdSeed modes 1-3).  Modes 1 and 2 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) --
+// the kernel forms the rank-1 product dz3 W3^T from them; mode 3 fills Xs[r][0..Np3).  All global loads of a pass are
+// independent (one round trip); the loss partials are reduced through `red` (static LDS, 8 floats).
 __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float* red, int m, long long row0, int rows_here,
                                          int TB) {
   const BwdSeed& sd = a.seed;
@@ -173,9 +174,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
         v = ok ? c * (m == 0 ? g0 : 1.f - g0) : 0.f;
         if (m == 0 && ok && row < r.Nt) r.bcw[row] = bc_weight(r, row);
       }
-      float* o = Xs + t * LDX;
-      o[0] = v;
-      for (int c = 1; c < Np3; ++c) o[c] = 0.f;
+      Xs[t] = v;
       if (sd.dz3_out != nullptr && ok) {
         float* g = sd.dz3_out + ((long long)m * a.rows + row) * Np3;
         g[0] = v;
@@ -258,22 +257,42 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
   if constexpr (BITS) mask_fetch<MT, MASK>(mk1, h1, m1, rows_here);
   // (split modes: the ring only serves the K = Np3 GEMM, two to four chunks -- three stages keep the kernel at 128 registers)
   WideRingT<(PM > 0 ? 3 : WIDE_RING)> ring;
-  wide_prefetch(w3t, a.Np3, ring);                // weight fragments travel while the seed rows are fetched
-  if (a.seed.mode == 0) tile_load(Xs, 0, a.dz3 + ((long long)m * a.rows + row0) * a.Np3, a.Np3, a.Np3, 0, rows_here, TB);
+  // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
+  // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
+  // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
+  const int mode = a.seed.mode;
+  const bool rank1 = mode == 1 || mode == 2, with_db = mode != 2;
+  const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
+  const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
+  if (!rank1) wide_prefetch(w3t, a.Np3, ring);    // weight fragments travel while the seed rows are fetched
+  if (mode == 0) tile_load(Xs, 0, a.dz3 + ((long long)m * a.rows + row0) * a.Np3, a.Np3, a.Np3, 0, rows_here, TB);
   else bwd_seed(a, Xs, red, m, row0, rows_here, TB);
   lds_barrier();
   TR(1);
-  if ((int)threadIdx.x < a.Np3) {                 // db3 partial of this tile
+  if (with_db && (int)threadIdx.x < a.Np3) {      // db3 partial of this tile (rank-1: column 0 alone is non-zero)
     float s = 0.f;
-    for (int r = 0; r < TB; ++r) s += Xs[r * LDX + threadIdx.x];
+    if (!rank1) for (int r = 0; r < TB; ++r) s += Xs[r * LDX + threadIdx.x];
+    else if (threadIdx.x == 0) for (int r = 0; r < TB; ++r) s += Xs[r];
     dbp[2 * HID + threadIdx.x] = s;
   }
 
   f32x16 acc[MT][2];
   float cs[2];
   // dh2 = dz3 * W3^T ; dz2 = dh2 * [h2 > 0]
-  wide_zero<MT>(acc);
-  wide_gemm<MT>(Xs, w3t, a.Np3, acc, ring);
+  if (rank1) {
+    const int hh = lane >> 5;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const f32x4 sv = *reinterpret_cast<const f32x4*>(Xs + 32 * mt + 8 * g + 4 * hh);     // rows (r & 3) + 8 (r >> 2) + 4 hh, r = 4 g + j
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { acc[mt][0][4 * g + j] = sv[j] * w3c[0]; acc[mt][1][4 * g + j] = sv[j] * w3c[1]; }
+      }
+  } else {
+    wide_zero<MT>(acc);
+    wide_gemm<MT>(Xs, w3t, a.Np3, acc, ring);
+  }
   TR(2);
   BfRing<PMX> bring;
   const s16x8* w2tp = PM > 0 ? reinterpret_cast<const s16x8*>(a.w2t_planes + m * a.planes_ms) : nullptr;
@@ -293,7 +312,7 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
     gs.e_out = a.e2_out + (long long)m * cdiv(a.rows, 32) + row0 / 32;
   }
   wide_store_colsum<MT, PM>(acc, Xs, dz2, rows_here, e2, cs, gs);
-  if (lane < 32) { dbp[HID + 64 * w + lane] = cs[0]; dbp[HID + 64 * w + 32 + lane] = cs[1]; }
+  if (with_db && lane < 32) { dbp[HID + 64 * w + lane] = cs[0]; dbp[HID + 64 * w + 32 + lane] = cs[1]; }
   lds_barrier();
   TR(3);
   // dh1 = dz2 * W2^T ; dz1 = dh1 * [h1 > 0]
@@ -307,7 +326,7 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
   wide_mask_apply<MT, MASK>(acc, mk1, rows_here, PM == 4 ? exp2i(-(e2 + F16_WSHIFT)) : 1.f);
   lds_barrier();
   wide_store_colsum<MT, 0>(acc, Xs, dz1, rows_here, 0, cs);
-  if (lane < 32) { dbp[64 * w + lane] = cs[0]; dbp[64 * w + 32 + lane] = cs[1]; }
+  if (with_db && lane < 32) { dbp[64 * w + lane] = cs[0]; dbp[64 * w + 32 + lane] = cs[1]; }
   TR(5);
   if constexpr (DX) {
     lds_barrier();

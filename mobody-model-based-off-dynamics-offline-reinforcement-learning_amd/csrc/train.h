@@ -36,10 +36,12 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //   1  critic: y = r + nd*gamma*min(Qt1,Qt2) (or q_next); dz3[m][row][0] = 2 (q_m - y) / N_global   (mobody.py:190-207)
 //      lossp[tile*2 + m] = sum_rows (q_m - y)^2
 //   2  frozen twin-Q of the actor update: dz3[m][row][0] = -p_w/N_global * d min(q0,q1)/dq_m (ties split 1/2, as
-//      torch.min's backward); member 0 also writes the BC weights bcw[row < Nt]
+//      torch.min's backward); member 0 also writes the BC weights bcw[row < Nt].  The net takes no parameter gradient:
+//      this mode stores no bias-gradient partials (`dbp` is not written).
 //   3  actor: d(pre-tanh) = (dxa[0]+dxa[1] + bc_coef*2*w*(pi-a)/(Ntg*A)) * max_action*(1-tanh^2);
 //      lossp[2*tile] = sum -min q, lossp[2*tile+1] = sum w*(pi-a)^2
-// Modes 1 and 3 also store dz3 to `dz3_out` (the weight-gradient GEMM reads it).
+// Modes 1 and 3 also store dz3 to `dz3_out` (the weight-gradient GEMM reads it).  Modes 1 and 2 seed column 0 of a
+// one-output net only: the kernel forms dz3 W3^T as the rank-1 product it is instead of running the K = Np3 GEMM.
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
