@@ -13,10 +13,12 @@
  *   mobody_rollout       <- MOBODY.rollout + add_batch            algo/offline_offline/mobody.py:596-657, algo/utils.py:43-92
  *   mobody_gather_batch  <- ReplayBuffer.sample x3 + torch.cat    algo/utils.py:127-148, mobody.py:399-400,516-529
  *   mobody_ring_append   <- ReplayBuffer.add_batch (+ filter)     algo/utils.py:43-92, mobody.py:468,648-653
- *   mobody_critic_step   <- update_q_functions + backward         mobody.py:189-208,544-547
+ *   mobody_critic        <- update_q_functions + backward (+ Adam.step + update_target)   mobody.py:189-208,544-552
  *   mobody_actor_forward / mobody_actor_backward
- *                        <- update_policy + bc_loss + backward    mobody.py:246-276,314-345,555-572
+ *                        <- update_policy + bc_loss + backward (+ Adam.step)   mobody.py:246-276,314-345,555-573
  *   mobody_adam_polyak   <- Adam.step + update_target             mobody.py:127-131,183-187,548,552,573
+ *   mobody_pretrain / mobody_pretrain_mopo
+ *                        <- one learn() batch: zero_grad + loss.backward (+ Adam.step)   algo/dynamics/mobody_dynamics.py:594-642
  *   mobody_pretrain_*    <- MOBODYEnsembleDynamics.learn / validate  algo/dynamics/mobody_dynamics.py:300-384,594-653,1113-1140
  *   mobody_rng_*         <- torch.normal / np.random.choice / np.random.randint draws
  *                           (mobody_dynamics.py:220, mobody_module.py:355-357, utils.py:128)
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define MOBODY_ABI_VERSION 6
+#define MOBODY_ABI_VERSION 7
 #define MOBODY_E_ARG (-1)      /* bad argument (dims, null pointer, unsupported size) */
 #define MOBODY_E_LAUNCH (-2)   /* hipLaunch / runtime error */
 #define MOBODY_E_UNSUPPORTED (-3)
@@ -124,14 +126,15 @@ int mobody_prof_end(double* ms_by_id, int64_t* count_by_id, int n_ids);
  *   words[1]  Adam step count of the first optimizer launch that raised a bit (0: none, or a plane builder did)
  *   words[2..3] internal (one 64-bit key of that launch; the block must be 8-byte aligned); words[4..] reserved
  * Lanes write (atomically) only when they see a violation; a clean run costs one compare per parameter.
- * FREEZE: every entry point that applies an optimizer step (mobody_adam_polyak[_dev], mobody_critic_update[_phase],
- * mobody_actor_update, mobody_pretrain[_mopo]_update / _adam, mobody_pretrain_za_adam) reads words[0] on entry; when an
+ * FREEZE: every entry point that applies an optimizer step (mobody_adam_polyak, the fused forms -- m, v given -- of mobody_critic,
+ * mobody_actor_backward, mobody_pretrain and mobody_pretrain_mopo, mobody_pretrain[_mopo]_adam, mobody_pretrain_za_adam) reads
+ * words[0] on entry; when an
  * EARLIER launch has set a bit it applies nothing -- parameters, moments, target, T blob, planes and `bump` stay as they
  * are (gradient and loss outputs are still written).  The launch in which the fault happens completes: its fp32 results
  * are exact, only the plane holds Inf.  So the state stops at the last update computed from healthy planes, however many
  * replayed steps pass before the host looks.  A captured optimizer launch must read a device step count that advances
- * between replays (as the `_dev` forms require anyway): that is how a replay tells itself from the faulting one.
- * CONSEQUENCE for callers of the `_dev` forms: whatever advances those step words keeps advancing them while the updates are
+ * between replays (a `t_dev` word, as replay requires anyway): that is how a replay tells itself from the faulting one.
+ * CONSEQUENCE for callers that pass `t_dev`: whatever advances those step words keeps advancing them while the updates are
  * frozen (only `bump` stops), so after a fault they run ahead of the steps that were applied: words[1] holds the faulting
  * launch's own count, and the caller re-seeds its step words from it before it goes on (the host mirror does).
  * OVERLAP: the verdict is taken per workgroup when it starts.  It is one verdict per launch as long as no other optimizer
@@ -360,66 +363,23 @@ typedef struct MobodyHyper {
 
 /* floats of scratch the training calls need.  The SAME workspace has to be handed to mobody_actor_forward and the
  * following mobody_actor_backward: it carries pi(s), the Q values, the saved activations and the ReLU sign words
- * between the two calls (the data-parallel caller all-reduces `stats` in between). */
+ * between the two calls (the data-parallel caller all-reduces `stats` in between); one MobodyActor block serves both. */
 int64_t mobody_train_workspace(const MobodyTrainDims* d);
 
-/* Critic loss + gradients (A.2): grad_q (MobodyMlpLayout(S+A,1,2) layout) and loss_out[0] = L_Q of
- * the LOCAL rows scaled by 1/N_global (sum over ranks == global loss). */
-int mobody_critic_step(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                       const float* q_blob, const float* q_blob_T, const float* qtarg_blob, const float* qtarg_blob_T,
-                       const float* state, const float* action, const float* next_state, const float* reward,
-                       const float* not_done, const float* q_next, float* grad_q, float* loss_out, float* workspace,
-                       int policy_forward, void* stream);
-/* actor_blob_T / qtarg_blob_T are only read when h->precision != 0 (their W2 planes); NULL is fine at precision 0. */
-/* policy_forward != 0 (needs q_next == NULL): the target-Q launch also evaluates pi(s) with its saves for the coming
- * mobody_actor_forward(..., policy_ready = 1) on the same workspace -- the actor does not change in between, and
- * the merged launch fills the chip better than the two it replaces.
- * q_next: NULL -> min target-Q(s', pi(s')) is computed here (update_q_functions, mobody.py:189-208); non-NULL ->
- * [N] bootstrap values supplied by the caller, V(s') in the advantage variant (update_q_functions_1, :210-229;
- * actor_blob / qtarg_blob / next_state may then be NULL). */
+/* ---- argument blocks of the train step: every field named, as MobodyEnsStep ----------------------------------------
+ * struct_bytes = sizeof(the block) (a binding built against another header is refused before anything else is read);
+ * MobodyTrainDims and MobodyHyper are embedded by value.  GRADIENT-ONLY OR FUSED is chosen by the fields: exactly one of the
+ * gradient blob (grad_q / grad_actor / grad) and the optimizer state m, v is non-NULL; both or neither is MOBODY_E_ARG.
+ *   gradient blob given   the data-parallel form: the gradient is written (SUM all-reduce it, then mobody_adam_polyak)
+ *   m, v given            the single-GPU form: the gradient reduction applies the Adam step (1-based t, or the device word
+ *                         t_dev[0] when t_dev != NULL) itself, so the gradient blob is never written -- one launch and one
+ *                         gradient round trip fewer.  Bit-identical to the gradient form followed by mobody_adam_polyak.
+ * Every argument check runs before the first HIP runtime call. */
 
-/* Single-GPU form of mobody_critic_step + mobody_adam_polyak (mobody.py:540-552): the gradient reduction applies the
- * Adam step (1-based t, or a device word t_dev) and the Polyak update of qtarg_blob (tau from `h`) itself, so the
- * gradient blob is never written -- one launch and one gradient round trip fewer.  Bit-identical to the two calls. */
-int mobody_critic_update(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                         float* q_blob, float* q_blob_T, float* qtarg_blob, float* qtarg_blob_T, const float* state,
-                         const float* action, const float* next_state, const float* reward, const float* not_done,
-                         const float* q_next, float* m, float* v, int64_t t, const int64_t* t_dev, float lr,
-                         float* loss_out, float* workspace, int policy_forward, int64_t* bump, void* stream);
-/* qtarg_blob_T (nullable): the target net's T blob; when given, the W2 planes of the target follow the Polyak update.
- * bump (nullable, != t_dev): a device int64 word the optimizer launch increments by one -- a captured step advances the
- * RNG call id it has already consumed here instead of in a launch of its own. */
-
-/* Actor phase, part 1: forwards + the two batch statistics stats[0]=sum|min Q(s,pi(s))|,
- * stats[1]=sum|min Q(s_t,a_t)| over LOCAL rows (all-reduce them across ranks before part 2). */
-int mobody_actor_forward(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                         const float* q_blob, const float* q_blob_T, const float* state, const float* action, float* stats,
-                         float* workspace, int policy_ready, void* stream);
-/* policy_ready != 0: pi(s) and its saves are already in the workspace (mobody_critic_step(..., policy_forward = 1)). */
-
-/* Actor phase, part 2: grad_actor (MobodyMlpLayout(S,A,1)) and loss_out[0]=L_pi, [1]=L_BC (local share). */
-int mobody_actor_backward(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                          const float* actor_blob_T, const float* q_blob, const float* q_blob_T, const float* state,
-                          const float* action, const float* stats, const float* v_true, float* grad_actor,
-                          float* loss_out, float* workspace, void* stream);
-/* v_true: NULL -> BC weights exp(3*q_b/mean|q_b|); [Nt] V(s_true) -> exp(3*(q_b - V)) (config['advantage'], :255-256). */
-
-/* mobody_critic_update in two calls: phase 1 enqueues its forwards (none of them reads `reward`), phase 2 the backward, the
- * weight gradients and the reduction / optimizer step.  Between the two the caller may join a stream that rewrites `reward`
- * (penalty_type 'par', mobody.py:428-434: an ensemble step on the source rows that otherwise sits in front of the critic). */
-int mobody_critic_update_phase(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                               float* q_blob, float* q_blob_T, float* qtarg_blob, float* qtarg_blob_T, const float* state,
-                               const float* action, const float* next_state, const float* reward, const float* not_done,
-                               const float* q_next, float* m, float* v, int64_t t, const int64_t* t_dev, float lr, float* loss_out,
-                               float* workspace, int policy_forward, int64_t* bump, int phase, void* stream);
-
-/* mobody_gather_batch_rng + mobody_critic_update in one call and one launch fewer: the step's first forward launch (twin-Q(s,a)
- * next to pi(s')) draws its tiles' row indices and takes the rows straight from the rings, and writes the minibatch arrays
- * state .. not_done (outputs here) for the launches behind it and for the caller.  Same draws, same bump words, bit-identical
- * results to the two calls.  `gr` carries mobody_gather_batch_rng's host arrays; its counts must add up to d->N.  Refused with
- * MOBODY_E_ARG: a source with rows to draw that is not a row-interleaved ring (mobody_ring_pitch), q_next != NULL, phase != 0
- * (the argument exists so that a caller of mobody_critic_update_phase gets a message, not a wrong step). */
-typedef struct MobodyGatherRng {
+/* Critic update (A.2; update_q_functions + backward, mobody.py:189-208,540-552): grad_q (MobodyMlpLayout(S+A,1,2) layout) or,
+ * fused, the Adam step of q_blob and the Polyak update of qtarg_blob (tau from `h`); loss_out[0] = L_Q of the LOCAL rows
+ * scaled by 1/N_global (sum over ranks == global loss). */
+typedef struct MobodyGatherRng {   /* mobody_gather_batch_rng's host arrays */
   const MobodyBufferView* bufs;
   const int64_t* counts;
   int nbuf;
@@ -430,39 +390,95 @@ typedef struct MobodyGatherRng {
   int64_t* const* bump;
   int nbump;
 } MobodyGatherRng;
-int mobody_critic_update_gather(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                                float* q_blob, float* q_blob_T, float* qtarg_blob, float* qtarg_blob_T, float* state,
-                                float* action, float* next_state, float* reward, float* not_done, const float* q_next,
-                                float* m, float* v, int64_t t, const int64_t* t_dev, float lr, float* loss_out,
-                                float* workspace, int policy_forward, int64_t* bump, int phase, const MobodyGatherRng* gr,
-                                void* stream);
+typedef struct MobodyCritic {
+  int32_t struct_bytes;
+  int32_t phase;            /* 0 the whole step.  1 / 2: the step in two calls -- phase 1 enqueues its forwards (none of them
+                               reads `reward`), phase 2 the backward, the weight gradients and the reduction / optimizer step.
+                               Between the two the caller may join a stream that rewrites `reward` (penalty_type 'par',
+                               mobody.py:428-434: an ensemble step on the source rows that otherwise sits in front of the critic) */
+  MobodyTrainDims d;
+  MobodyHyper h;
+  const float *actor_blob, *actor_blob_T;   /* actor_blob_T / qtarg_blob_T are only read when h.precision != 0 (their W2
+                                               planes); NULL is fine at precision 0 */
+  float *q_blob, *q_blob_T;                 /* written by the fused form only */
+  float *qtarg_blob;
+  float *qtarg_blob_T;      /* nullable: the target net's T blob; when given, the W2 planes of the target follow the Polyak update */
+  float *state, *action, *next_state, *reward, *not_done;   /* the minibatch: read -- or, with `gather`, WRITTEN */
+  const float* q_next;      /* NULL -> min target-Q(s', pi(s')) is computed here (update_q_functions, mobody.py:189-208);
+                               non-NULL -> [N] bootstrap values supplied by the caller, V(s') in the advantage variant
+                               (update_q_functions_1, :210-229; actor_blob / qtarg_blob / next_state may then be NULL) */
+  float* grad_q;
+  float *m, *v;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  int32_t policy_forward;   /* != 0 (needs q_next == NULL): the target-Q launch also evaluates pi(s) with its saves for the coming
+                               mobody_actor_forward (policy_ready = 1) on the same workspace -- the actor does not change in
+                               between, and the merged launch fills the chip better than the two it replaces */
+  float *loss_out, *workspace;
+  int64_t* bump;            /* nullable, != t_dev, fused form only: a device int64 word the optimizer launch increments by one -- a
+                               captured step advances the RNG call id it has already consumed here instead of in a launch of
+                               its own */
+  const MobodyGatherRng* gather;
+                            /* NULL: none.  Else mobody_gather_batch_rng + this call in one call and one launch fewer: the
+                               step's first forward launch (twin-Q(s,a) next to pi(s')) draws its tiles' row indices and takes
+                               the rows straight from the rings, and writes the minibatch arrays state .. not_done for the
+                               launches behind it and for the caller.  Same draws, same bump words, bit-identical results to
+                               the two calls.  Its counts must add up to d.N.  Refused with MOBODY_E_ARG: a source with rows
+                               to draw that is not a row-interleaved ring (mobody_ring_pitch), q_next != NULL, phase != 0 (the
+                               first forward launch writes the minibatch the backward reads) */
+} MobodyCritic;
+int mobody_critic(const MobodyCritic* a, void* stream);
 
-/* Single-GPU form of mobody_actor_backward + mobody_adam_polyak (mobody.py:554-578), as mobody_critic_update. */
-int mobody_actor_update(const MobodyTrainDims* d, const MobodyHyper* h, float* actor_blob, float* actor_blob_T,
-                        const float* q_blob, const float* q_blob_T, const float* state, const float* action,
-                        const float* stats, const float* v_true, float* m, float* v, int64_t t, const int64_t* t_dev,
-                        float lr, float* loss_out, float* workspace, void* stream);
+/* Actor phase (update_policy + bc_loss + backward, mobody.py:246-276,314-345,554-578): ONE block for its two calls, filled
+ * once; mobody_actor_forward reads the fields up to `workspace` and policy_ready, mobody_actor_backward all but policy_ready.
+ *   mobody_actor_forward   part 1: forwards + the two batch statistics stats[0]=sum|min Q(s,pi(s))|,
+ *                          stats[1]=sum|min Q(s_t,a_t)| over LOCAL rows (all-reduce them across ranks before part 2)
+ *   mobody_actor_backward  part 2: grad_actor (MobodyMlpLayout(S,A,1)) or, fused, the Adam step of actor_blob (no target);
+ *                          loss_out[0]=L_pi, [1]=L_BC (local share) */
+typedef struct MobodyActor {
+  int32_t struct_bytes;
+  int32_t policy_ready;     /* != 0: pi(s) and its saves are already in the workspace (mobody_critic with policy_forward = 1) */
+  MobodyTrainDims d;
+  MobodyHyper h;
+  float *actor_blob, *actor_blob_T;         /* written by the fused form only */
+  const float *q_blob, *q_blob_T, *state, *action;
+  float* stats;
+  float* workspace;
+  const float* v_true;      /* NULL -> BC weights exp(3*q_b/mean|q_b|); [Nt] V(s_true) -> exp(3*(q_b - V)) (config['advantage'],
+                               :255-256) */
+  float* grad_actor;
+  float *m, *v;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  float* loss_out;
+} MobodyActor;
+int mobody_actor_forward(const MobodyActor* a, void* stream);
+int mobody_actor_backward(const MobodyActor* a, void* stream);
 
 /* Expectile loss of the V function (update_v_function, mobody.py:231-242): adv = min(qt[0],qt[1]) - v;
  * dz3[N][16] column 0 = dL_V/dV (1/N_global scaling), loss_out[0] = local share of L_V; lossp_ws: ceil(N/256) floats. */
 int mobody_value_loss_grad(const float* qt, const float* v, int64_t N, int64_t N_global, float* dz3, float* loss_out,
                            float* lossp_ws, void* stream);
 
-/* Adam (torch defaults b1=.9 b2=.999 eps=1e-8) on a packed blob, 1-based step t; optional Polyak
- * target update target = tau*p + (1-tau)*target (tau < 0 or target == NULL: skip); refreshes the
- * transposed blob used by the backward kernels (blob_T may be NULL). grad_scale multiplies the
- * gradient first (1/world for an all-reduced SUM). */
-int mobody_adam_polyak(int in_dim, int out_dim, int members, float* blob, float* blob_T, const float* grad, float* m,
-                       float* v, float* target, float* target_T, int64_t t, float lr, float tau, float grad_scale,
-                       int precision, void* stream);
-/* target_T (nullable): T blob of the target net, whose W2 planes then follow the Polyak update (split-precision modes).
- * precision: format of the W2 planes written into blob_T / target_T (the mode the nets are evaluated in). */
-
-/* Same, with the 1-based step count read from DEVICE memory (t_dev[0]) so that a captured HIP graph advances
- * without new kernel arguments (bias corrections are formed in double on the device). */
-int mobody_adam_polyak_dev(int in_dim, int out_dim, int members, float* blob, float* blob_T, const float* grad,
-                           float* m, float* v, float* target, float* target_T, const int64_t* t_dev, float lr, float tau,
-                           float grad_scale, int precision, void* stream);
+/* Adam (torch defaults b1=.9 b2=.999 eps=1e-8) on a packed blob (mobody_mlp_layout(in_dim, out_dim, members)); refreshes the
+ * transposed blob used by the backward kernels. */
+typedef struct MobodyAdam {
+  int32_t struct_bytes, in_dim, out_dim, members;
+  float *blob, *blob_T;     /* blob_T may be NULL */
+  const float* grad;
+  float *m, *v;
+  float *target;            /* optional Polyak update target = tau*p + (1-tau)*target (tau < 0 or target == NULL: skip) */
+  float *target_T;          /* nullable: T blob of the target net, whose W2 planes then follow the Polyak update */
+  int64_t t;                /* 1-based step count */
+  const int64_t* t_dev;     /* nullable: the step count is read from DEVICE memory (t_dev[0]) instead, so that a captured HIP
+                               graph advances without new kernel arguments (bias corrections are formed in double on the device) */
+  float lr, tau;
+  float grad_scale;         /* multiplies the gradient first (1/world for an all-reduced SUM) */
+  int32_t precision;        /* format of the W2 planes written into blob_T / target_T (the mode the nets are evaluated in) */
+} MobodyAdam;
+int mobody_adam_polyak(const MobodyAdam* a, void* stream);
 
 /* PAR reward shaping: reward[i] -= coef * mean_d (next_state_true[i][d] - next_state_model[i][d])^2  (mobody.py:428-434) */
 int mobody_par_penalty(const float* next_state_true, const float* next_state_model, float* reward, float coef,
@@ -507,7 +523,7 @@ typedef struct MobodyPretrainLayout {
   int64_t t_off_enc, t_off_tr, t_off_rw, t_total_floats;      /* T blob */
 } MobodyPretrainLayout;
 int mobody_pretrain_layout(int S, int A, MobodyPretrainLayout* out);
-/* `precision` of the four pre-training entry points: 0 = exact fp32 MFMA, 4 = "f16x2" (the 256 x 256 layers of the three
+/* `precision` of the pre-training entry points: 0 = exact fp32 MFMA, 4 = "f16x2" (the 256 x 256 layers of the three
  * 7-member nets on the split core, h1 / dz2 handed to the weight-gradient GEMM as fp16 planes; other modes are refused).
  * The T blob carries the W2 / W2^T planes of the mode it was built for; Adam keeps them current. */
 int mobody_pretrain_transpose(int S, int A, const float* blob, float* blob_T, int precision, void* stream);
@@ -522,33 +538,43 @@ int mobody_pretrain_gather(const float* state, const float* action, const float*
 /* start_dev (nullable): DEVICE int64 batch counter, start += start_dev[0] * b, so a captured graph walks the index matrix
  * batch by batch (advance it with mobody_counter_add); reads are clamped to the matrix. */
 
-/* Loss and gradients of one learn() batch (zero_grad + loss.backward, :594-642).  b rows per member on this rank,
- * b_global = rows per member over all data-parallel ranks (gradients / losses are local shares of the global means:
- * SUM all-reduce `grad` before mobody_pretrain_adam).  noise6 [6][7][b][16] = the six reparameterisation draws in the
- * reference's order z1(s) z2(s') z3(s) z4(s') z5(s) z6(s), noise7 [7][b][S] = the fake-next-state draw; NULL -> device
- * Philox streams 16..22 at (seed, call).  grad: blob layout; the action encoder that is not used this step
- * (za_trg* on source batches, za_src* on target ones) is left untouched; every other float of `grad` is written, layout
- * padding (W1 rows >= in_dim, W3 / b3 columns >= out_dim of the three regions) as exactly 0.  The workspace needs no
- * initialisation: the results do not depend on what it held.
- * loss_out[5] = (loss, transition_loss, encoder_loss, recon_loss, kl_loss). */
-int mobody_pretrain_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                          const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
-                          const float* noise6, const float* noise7, uint32_t seed, uint32_t call, float* grad,
-                          float* loss_out, float* workspace, int precision, float transition_coef, float reward_coef,
-                          void* stream);
-/* transition_coef / reward_coef: weights of transition_loss and reward_loss in this call's loss (1, 1 = learn()).
- * inverse_sep_reward_loss = 1 runs learn() with reward_coef 0 and learn_sep_reward (:482-519) with encoder_loss_coef 0,
- * transition_coef 0, reward_coef 1. */
-
-/* Single-GPU form of mobody_pretrain_grads + mobody_pretrain_adam: every gradient reduction applies the Adam step of the
- * elements it has just reduced (no gradient blob, four launches fewer).  t_dev (nullable): DEVICE int64[2] = {t_main,
- * t_za} read instead of the host counts; call_dev (nullable): DEVICE int64 word added to `call` -- both for graph replay.
- * loss_acc (nullable): DEVICE float[5], loss_acc += loss_out in the step's last launch (learn()'s running sums, :630-650). */
-int mobody_pretrain_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
-                           const float* xenc, const float* act, const float* rew, const float* noise6, const float* noise7,
-                           uint32_t seed, uint32_t call, const int64_t* call_dev, float* m, float* v, int64_t t_main,
-                           int64_t t_za, const int64_t* t_dev, float lr, float* loss_out, float* loss_acc, float* workspace,
-                           int precision, void* stream);
+/* Loss and gradients of one learn() batch (zero_grad + loss.backward, :594-642), arguments by name; gradient-only or fused by
+ * the fields, as the train-step blocks above (exactly one of `grad` and m, v).
+ *   grad given   every float of `grad` (blob layout) is written, layout padding (W1 rows >= in_dim, W3 / b3 columns >= out_dim
+ *                of the three regions) as exactly 0 -- except the action encoder that is not used this step (za_trg* on source
+ *                batches, za_src* on target ones), which is left untouched.  SUM all-reduce it before mobody_pretrain_adam.
+ *   m, v given   single-GPU form of this call + mobody_pretrain_adam: every gradient reduction applies the Adam step of the
+ *                elements it has just reduced (no gradient blob, four launches fewer).  Needs b_global == b.
+ * The workspace needs no initialisation: the results do not depend on what it held. */
+typedef struct MobodyPretrain {
+  int32_t struct_bytes, S, A, use_trg;
+  int64_t b;                /* rows per member on this rank */
+  int64_t b_global;         /* rows per member over all data-parallel ranks (gradients / losses are local shares of the global
+                               means) */
+  float encoder_loss_coef;
+  float transition_coef, reward_coef;
+                            /* weights of transition_loss and reward_loss in this call's loss (1, 1 = learn()).
+                               inverse_sep_reward_loss = 1 runs learn() with reward_coef 0 and learn_sep_reward (:482-519) with
+                               encoder_loss_coef 0, transition_coef 0, reward_coef 1 */
+  int32_t precision;
+  float *blob, *blob_T;     /* written by the fused form only */
+  const float *xenc, *act, *rew;   /* as mobody_pretrain_gather writes them */
+  const float *noise6;      /* [6][7][b][16] = the six reparameterisation draws in the reference's order z1(s) z2(s') z3(s) z4(s')
+                               z5(s) z6(s) */
+  const float *noise7;      /* [7][b][S] = the fake-next-state draw; NULL (either) -> device Philox streams 16..22 at (seed, call) */
+  uint32_t seed, call;
+  const int64_t* call_dev;  /* nullable: DEVICE int64 word added to `call` (graph replay) */
+  float* grad;
+  float *m, *v;
+  int64_t t_main, t_za;     /* 1-based step counts of the three MLP regions / of this step's action encoder */
+  const int64_t* t_dev;     /* nullable: DEVICE int64[2] = {t_main, t_za} read instead of the host counts (graph replay) */
+  float lr;
+  float *loss_out;          /* [5] = (loss, transition_loss, encoder_loss, recon_loss, kl_loss) */
+  float *loss_acc;          /* nullable: DEVICE float[5], loss_acc += loss_out in the step's last launch (learn()'s running sums,
+                               :630-650) */
+  float *workspace;
+} MobodyPretrain;
+int mobody_pretrain(const MobodyPretrain* a, void* stream);
 
 /* torch.optim.Adam step on the blob (and its T blob): the three MLP regions use the 1-based step count t_main, the
  * action encoder of this step's domain t_za; the other action encoder is skipped (its .grad is None in the reference,
@@ -586,20 +612,28 @@ int mobody_pretrain_mopo_layout(int S, int A, MobodyPretrainMopoLayout* out);
 /* precision 0 (exact fp32) or 4 (f16x2), as for the latent entry points above */
 int mobody_pretrain_mopo_transpose(int S, int A, const float* blob, float* blob_T, int precision, void* stream);
 int64_t mobody_pretrain_mopo_workspace(int S, int A, int64_t b);
-/* Loss and gradients of one learn() batch: xenc[7][2b][S] / act[7][b][A] / rew[7][b] as mobody_pretrain_gather writes them,
- * noise [7][b][S] = the fake-next-state draw (NULL -> device Philox stream 22 at (seed, call)).  b_global as for
- * mobody_pretrain_grads.  loss_out[5] = (loss, transition_loss, encoder_loss, recon_loss = 0, kl_loss). */
-int mobody_pretrain_mopo_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                               const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
-                               const float* noise, uint32_t seed, uint32_t call, float* grad, float* loss_out,
-                               float* workspace, int precision, void* stream);
-/* Single-GPU fused form (the reductions apply Adam): t = the 1-based step count shared by both regions; t_dev (nullable):
- * DEVICE int64 read instead of t; call_dev (nullable): DEVICE int64 added to `call`; loss_acc (nullable): DEVICE float[5]
- * += loss_out -- as mobody_pretrain_update, for graph replay. */
-int mobody_pretrain_mopo_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
-                                const float* xenc, const float* act, const float* rew, const float* noise, uint32_t seed,
-                                uint32_t call, const int64_t* call_dev, float* m, float* v, int64_t t, const int64_t* t_dev,
-                                float lr, float* loss_out, float* loss_acc, float* workspace, int precision, void* stream);
+/* Loss and gradients of one learn() batch of the mopo model, arguments by name: the fields of MobodyPretrain with the same
+ * meanings (gradient-only or fused likewise), except
+ *   noise   [7][b][S] = the fake-next-state draw (NULL -> device Philox stream 22 at (seed, call))
+ *   t       the 1-based step count shared by both regions; t_dev (nullable): DEVICE int64 read instead of t
+ * loss_out[5] = (loss, transition_loss, encoder_loss, recon_loss = 0, kl_loss). */
+typedef struct MobodyPretrainMopo {
+  int32_t struct_bytes, S, A, use_trg;
+  int64_t b, b_global;
+  float encoder_loss_coef;
+  int32_t precision;
+  float *blob, *blob_T;
+  const float *xenc, *act, *rew, *noise;
+  uint32_t seed, call;
+  const int64_t* call_dev;
+  float* grad;
+  float *m, *v;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  float *loss_out, *loss_acc, *workspace;
+} MobodyPretrainMopo;
+int mobody_pretrain_mopo(const MobodyPretrainMopo* a, void* stream);
 /* torch.optim.Adam step of both regions with the one step count t (every learn() step gives both a gradient). */
 int mobody_pretrain_mopo_adam(int S, int A, float* blob, float* blob_T, const float* grad, float* m, float* v, int64_t t,
                               float lr, float grad_scale, int precision, void* stream);

@@ -84,6 +84,52 @@ class MobodyEnsRollout(C.Structure):
                 ("ring", C.POINTER(MobodyBufferView)), ("cap", i64), ("ptr_size", vp), ("workspace", vp)]
 
 
+# Argument blocks of the train step and of the pre-training step: one field per argument, in the header's order.  Float and
+# counter pointers are c_void_p (torch data_ptr()); what keeps two of them apart is the field NAME the caller writes.
+class MobodyCritic(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("phase", i32), ("d", MobodyTrainDims), ("h", MobodyHyper), ("actor_blob", vp),
+                ("actor_blob_T", vp), ("q_blob", vp), ("q_blob_T", vp), ("qtarg_blob", vp), ("qtarg_blob_T", vp), ("state", vp),
+                ("action", vp), ("next_state", vp), ("reward", vp), ("not_done", vp), ("q_next", vp), ("grad_q", vp), ("m", vp), ("v", vp),
+                ("t", i64), ("t_dev", vp), ("lr", f32), ("policy_forward", i32), ("loss_out", vp), ("workspace", vp),
+                ("bump", vp), ("gather", C.POINTER(MobodyGatherRng))]
+
+
+class MobodyActor(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("policy_ready", i32), ("d", MobodyTrainDims), ("h", MobodyHyper), ("actor_blob", vp),
+                ("actor_blob_T", vp), ("q_blob", vp), ("q_blob_T", vp), ("state", vp), ("action", vp), ("stats", vp),
+                ("workspace", vp), ("v_true", vp), ("grad_actor", vp), ("m", vp), ("v", vp), ("t", i64), ("t_dev", vp), ("lr", f32),
+                ("loss_out", vp)]
+
+
+class MobodyAdam(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("in_dim", i32), ("out_dim", i32), ("members", i32), ("blob", vp), ("blob_T", vp),
+                ("grad", vp), ("m", vp), ("v", vp), ("target", vp), ("target_T", vp), ("t", i64), ("t_dev", vp), ("lr", f32), ("tau", f32),
+                ("grad_scale", f32), ("precision", i32)]
+
+
+class MobodyPretrain(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("S", i32), ("A", i32), ("use_trg", i32), ("b", i64), ("b_global", i64),
+                ("encoder_loss_coef", f32), ("transition_coef", f32), ("reward_coef", f32), ("precision", i32), ("blob", vp),
+                ("blob_T", vp), ("xenc", vp), ("act", vp), ("rew", vp), ("noise6", vp), ("noise7", vp), ("seed", u32),
+                ("call", u32), ("call_dev", vp), ("grad", vp), ("m", vp), ("v", vp), ("t_main", i64), ("t_za", i64), ("t_dev", vp),
+                ("lr", f32), ("loss_out", vp), ("loss_acc", vp), ("workspace", vp)]
+
+
+class MobodyPretrainMopo(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("S", i32), ("A", i32), ("use_trg", i32), ("b", i64), ("b_global", i64),
+                ("encoder_loss_coef", f32), ("precision", i32), ("blob", vp), ("blob_T", vp), ("xenc", vp), ("act", vp),
+                ("rew", vp), ("noise", vp), ("seed", u32), ("call", u32), ("call_dev", vp), ("grad", vp), ("m", vp), ("v", vp), ("t", i64),
+                ("t_dev", vp), ("lr", f32), ("loss_out", vp), ("loss_acc", vp), ("workspace", vp)]
+
+
+def block(cls, **fields):
+    """An argument block with struct_bytes set and `fields` by name (everything else zero / NULL)."""
+    return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
+
+
+BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
+
+
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
 
 
@@ -136,24 +182,11 @@ PROTOTYPES = {
                                      vp]),
     "mobody_ring_pitch": (i64, [C.c_int, C.c_int]),
     "mobody_train_workspace": (i64, [C.POINTER(MobodyTrainDims)]),
-    "mobody_critic_step": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     vp, vp, vp, vp, vp, vp, C.c_int, vp]),
-    "mobody_critic_update": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                       vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, vp]),
-    "mobody_critic_update_gather": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                              vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, C.c_int,
-                                              C.POINTER(MobodyGatherRng), vp]),
-    "mobody_critic_update_phase": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                             vp, vp, vp, vp, vp, i64, vp, f32, vp, vp, C.c_int, vp, C.c_int, vp]),
-    "mobody_actor_update": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp,
-                                      vp, vp, vp, i64, vp, f32, vp, vp, vp]),
+    "mobody_critic": (C.c_int, [C.POINTER(MobodyCritic), vp]),
+    "mobody_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
-    "mobody_actor_forward": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp, vp, vp,
-                                       C.c_int, vp]),
-    "mobody_actor_backward": (C.c_int, [C.POINTER(MobodyTrainDims), C.POINTER(MobodyHyper), vp, vp, vp, vp, vp, vp,
-                                        vp, vp, vp, vp, vp, vp]),
-    "mobody_adam_polyak": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, C.c_int, vp]),
-    "mobody_adam_polyak_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, f32, C.c_int, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),
     "mobody_mlp3_backward_workspace": (i64, [C.c_int, C.c_int, C.c_int, i64]),
     "mobody_mlp3_backward": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp]),
@@ -165,19 +198,13 @@ PROTOTYPES = {
     "mobody_pretrain_transpose": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "mobody_pretrain_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_pretrain_gather": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp, vp]),
-    "mobody_pretrain_update": (C.c_int, [C.c_int, C.c_int, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp,
-                                         vp, i64, i64, vp, f32, vp, vp, vp, C.c_int, vp]),
-    "mobody_pretrain_grads": (C.c_int, [C.c_int, C.c_int, i64, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, vp, u32, u32,
-                                        vp, vp, vp, C.c_int, f32, f32, vp]),
+    "mobody_pretrain": (C.c_int, [C.POINTER(MobodyPretrain), vp]),
     "mobody_pretrain_adam": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, i64, f32, f32, C.c_int, C.c_int, i64, vp]),
     "mobody_pretrain_za_adam": (C.c_int, [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, f32, f32, vp]),
     "mobody_pretrain_mopo_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(MobodyPretrainMopoLayout)]),
     "mobody_pretrain_mopo_transpose": (C.c_int, [C.c_int, C.c_int, vp, vp, C.c_int, vp]),
     "mobody_pretrain_mopo_workspace": (i64, [C.c_int, C.c_int, i64]),
-    "mobody_pretrain_mopo_grads": (C.c_int, [C.c_int, C.c_int, i64, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp,
-                                             vp, C.c_int, vp]),
-    "mobody_pretrain_mopo_update": (C.c_int, [C.c_int, C.c_int, i64, C.c_int, f32, vp, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp,
-                                              i64, vp, f32, vp, vp, vp, C.c_int, vp]),
+    "mobody_pretrain_mopo": (C.c_int, [C.POINTER(MobodyPretrainMopo), vp]),
     "mobody_pretrain_mopo_adam": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, i64, f32, f32, C.c_int, vp]),
     "mobody_dyn_validate_mopo": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp]),
     "mobody_dyn_validate_workspace": (i64, [C.c_int, C.c_int, i64]),
@@ -203,7 +230,7 @@ def load():
     for name, (res, args) in PROTOTYPES.items():
         fn = getattr(lib, name)          # AttributeError if the .so lacks a declared symbol
         fn.restype, fn.argtypes = res, args
-    if lib.mobody_abi_version() != 6:
+    if lib.mobody_abi_version() != 7:
         raise ImportError("libmobody_hip.so ABI version mismatch")
     _lib = lib
     return lib

@@ -296,7 +296,7 @@ class MOBODYEnsembleDynamics(object):
         return self._pre_ws_by_b[b]
 
     def _learn_batch_fused(self, use_trg, xenc, act, rew, b, acc=None):
-        """Single-GPU form of _learn_batch: the gradient reductions apply Adam themselves (mobody_pretrain_update); `acc`
+        """Single-GPU form of _learn_batch: the gradient reductions apply Adam themselves (mobody_pretrain with m, v); `acc`
         (device float[5]): the step's last launch adds the loss vector onto it (no launch of its own for learn()'s sums)."""
         m = self.model
         S, A = m.obs_dim, m.action_dim

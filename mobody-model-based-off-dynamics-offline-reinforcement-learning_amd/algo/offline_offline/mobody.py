@@ -237,7 +237,7 @@ class MOBODY(object):
         # (measured with one RCCL rank at bs 4096: 0.385 ms/step captured vs 0.431 segments; tools/dp_capture_probe.py)
         import os
         self.dp_graph = str(config.get("dp_graph", os.environ.get("MOBODY_DP_GRAPH", "captured")))
-        # one GPU: the gradient reduction applies Adam/Polyak itself (mobody_critic_update / mobody_actor_update);
+        # one GPU: the gradient reduction applies Adam/Polyak itself (mobody_critic / mobody_actor_backward with m, v);
         # config['fused_update']=0 keeps the separate gradient blobs + optimizer launches (what N > 1 ranks use)
         self.fused_update = int(config.get("fused_update", 1))
         self._ctr = torch.zeros(4, dtype=torch.int64, device=self.device)      # [rng call, critic t, actor t, V t]

@@ -24,6 +24,14 @@ int fail(int code, const char* fmt, ...);
     if (e_ != hipSuccess) return ::mobody::fail(MOBODY_E_LAUNCH, "%s: %s", what, hipGetErrorString(e_)); \
   } while (0)
 
+// The head of every entry point that takes an argument block: the block is there and was built against this header.
+#define MB_BLOCK(who, a, Block)                                                                                  \
+  do {                                                                                                           \
+    MB_REQUIRE((a) != nullptr, "%s: null argument struct", who);                                                 \
+    MB_REQUIRE((a)->struct_bytes == (int32_t)sizeof(Block), "%s: struct_bytes %d != sizeof(" #Block ") %d", who, \
+               (a)->struct_bytes, (int)sizeof(Block));                                                           \
+  } while (0)
+
 // Precision ids of the C ABI (MobodyHyper.precision and the `precision` arguments; names as _lib.PRECISIONS).  Host code
 // compares against these; the kernels' template arguments PM / NPL carry the same numbers.
 enum Precision { PREC_F32 = 0, PREC_BF16 = 1, PREC_BF16X2 = 2, PREC_BF16X3 = 3, PREC_F16X2 = 4 };

@@ -469,9 +469,7 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
 }
 
 extern "C" int mobody_ens_step(const MobodyEnsStep* a, void* stream) {
-  MB_REQUIRE(a != nullptr, "mobody_ens_step: null argument struct");
-  MB_REQUIRE(a->struct_bytes == (int32_t)sizeof(MobodyEnsStep), "mobody_ens_step: struct_bytes %d != sizeof(MobodyEnsStep) %d",
-             a->struct_bytes, (int)sizeof(MobodyEnsStep));
+  MB_BLOCK("mobody_ens_step", a, MobodyEnsStep);
   return dyn_step_impl("mobody_ens_step", *a, nullptr, nullptr, 0.f, 0, stream);
 }
 
@@ -594,9 +592,7 @@ extern "C" int64_t mobody_ens_rollout_workspace(const MobodyEnsRollout* a) {
 }
 
 extern "C" int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream) {
-  MB_REQUIRE(a != nullptr, "mobody_ens_rollout: null argument struct");
-  MB_REQUIRE(a->struct_bytes == (int32_t)sizeof(MobodyEnsRollout), "mobody_ens_rollout: struct_bytes %d != sizeof(MobodyEnsRollout) %d",
-             a->struct_bytes, (int)sizeof(MobodyEnsRollout));
+  MB_BLOCK("mobody_ens_rollout", a, MobodyEnsRollout);
   return rollout_impl("mobody_ens_rollout", *a, stream);
 }
 

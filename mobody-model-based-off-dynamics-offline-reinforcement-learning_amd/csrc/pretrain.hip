@@ -712,19 +712,11 @@ extern "C" int mobody_pretrain_gather(const float* state, const float* action, c
 }
 
 namespace mobody {
-// torch.optim.Adam scalar bookkeeping in double (same forms as train.hip's adam_target); t_dev: device step count
+// train.h's adam_target for a pre-training net: no Polyak target (tau = -1), and no W2 planes (precision -1) unless the step runs
+// f16x2 -- exact fp32 never reads the planes of its T blob
 static AdamTarget pre_adam_target(float* p, float* pT, float* m, float* v, int64_t t, const int64_t* t_dev, float lr,
                                   float grad_scale, int precision = 0) {
-  const double tt = t_dev ? 1.0 : (double)t;
-  const double bc1 = 1.0 - pow(0.9, tt), bc2 = 1.0 - pow(0.999, tt);
-  AdamTarget a{};
-  a.p = p; a.m = m; a.v = v; a.blob_T = pT; a.target = nullptr;
-  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
-  a.c.tau = -1.f; a.c.one_minus_tau = 0.f; a.c.gscale = grad_scale;
-  a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1;
-  a.precision = precision == PREC_F16X2 ? PREC_F16X2 : -1;         // exact fp32 never reads the W2 planes of its T blob; f16x2 keeps them current
-  a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
-  return a;
+  return adam_target(p, pT, m, v, nullptr, t, t_dev, lr, -1.f, grad_scale, precision == PREC_F16X2 ? PREC_F16X2 : -1);
 }
 // Side stream of the step.  After a net's backward kernel its weight-gradient GEMM and the gradient reduction (with the fused
 // Adam step) feed nothing later in the step, while the main chain -- 13 dependent launches of 17 .. 224 workgroups that leave
@@ -750,43 +742,47 @@ static int pre_side(PreSide** out) {
   *out = &side[dev];
   return 0;
 }
-
-struct PreOpt {             // fused optimizer step (single GPU): Adam state and step counts; on = 0 -> gradients only
-  int on;
-  float *blob, *blob_T, *m, *v;
-  int64_t t_main, t_za;
-  const int64_t* t_dev;     // device {t_main, t_za} (graph replay) or null
-  float lr;
-};
 }  // namespace mobody
 
-static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                         const float* blob, const float* blob_T, const float* xenc, const float* act,
-                         const float* rew, const float* noise6, const float* noise7, uint32_t seed, uint32_t call,
-                         const int64_t* call_dev, float* grad, const PreOpt& opt, float* loss_out, float* loss_acc,
-                         float* workspace, int precision, void* stream, float transition_coef = 1.f, float reward_coef = 1.f) {
+// Both pre-training blocks: exactly one of `grad` and m, v; the fused form is the single-GPU one
+template <class Block>
+static int pre_block_check(const char* who, const Block& a) {
+  MB_REQUIRE((a.grad != nullptr) != (a.m != nullptr || a.v != nullptr), "%s: exactly one of grad and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a.grad || (a.m && a.v), "%s: null pointer", who);
+  MB_REQUIRE(a.grad || a.b_global == a.b, "%s: the fused form is the single-GPU one: b_global %lld != b %lld", who, (long long)a.b_global, (long long)a.b);
+  return 0;
+}
+
+static int pretrain_impl(const MobodyPretrain& a, void* stream) {
+  const char* who = "mobody_pretrain";
+  const int S = a.S, A = a.A, use_trg = a.use_trg, precision = a.precision;
+  const int64_t b = a.b;
+  const float *blob = a.blob, *blob_T = a.blob_T, *xenc = a.xenc;
+  float* grad = a.grad;
+  const bool fused = a.m != nullptr;
   MobodyPretrainLayout L;
   int rc = mobody_pretrain_layout(S, A, &L);
   if (rc) return rc;
-  rc = check_precision("mobody_pretrain", precision, true, PREC_F32_OR_F16X2);
+  rc = check_precision(who, precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   const bool f16 = precision == PREC_F16X2;
-  MB_REQUIRE(b >= 1 && b_global >= b, "mobody_pretrain: need 1 <= b <= b_global");
-  MB_REQUIRE(blob && blob_T && xenc && act && rew && (grad || opt.on) && loss_out && workspace, "mobody_pretrain: null pointer");
+  MB_REQUIRE(b >= 1 && a.b_global >= b, "%s: need 1 <= b <= b_global", who);
+  MB_REQUIRE(blob && blob_T && xenc && a.act && a.rew && a.loss_out && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(!fused || a.t_dev != nullptr || (a.t_main >= 1 && a.t_za >= 1), "%s: step counts are 1-based", who);
   auto region_adam = [&](int64_t off, int64_t toff) {
-    if (!opt.on) return AdamTarget{};
-    return pre_adam_target(opt.blob + off, opt.blob_T + toff, opt.m + off, opt.v + off, opt.t_main, opt.t_dev, opt.lr, 1.f, precision);
+    if (!fused) return AdamTarget{};
+    return pre_adam_target(a.blob + off, a.blob_T + toff, a.m + off, a.v + off, a.t_main, a.t_dev, a.lr, 1.f, precision);
   };
   auto gptr = [&](int64_t off) { return grad ? grad + off : nullptr; };
   PreWs w;
-  pre_carve(L, b, workspace, w);
+  pre_carve(L, b, a.workspace, w);
   hipStream_t st = as_stream(stream);
   const long long R2 = 2 * b, R4 = 4 * b;
   PreRow r{};
-  r.S = S; r.A = A; r.use_trg = use_trg; r.Np3tr = L.tr.Np3; r.b = b; r.inv_bg = 1.f / (float)b_global;
-  r.ce = (use_trg ? 5.f : 1.f) * encoder_loss_coef; r.cr = (use_trg ? 1.f : 0.01f) * reward_coef; r.ct = transition_coef;
-  r.xenc = xenc; r.act = act; r.rew = rew; r.noise6 = noise6; r.noise7 = noise7; r.seed = seed; r.call = call;
-  r.call_dev = (const long long*)call_dev;
+  r.S = S; r.A = A; r.use_trg = use_trg; r.Np3tr = L.tr.Np3; r.b = b; r.inv_bg = 1.f / (float)a.b_global;
+  r.ce = (use_trg ? 5.f : 1.f) * a.encoder_loss_coef; r.cr = (use_trg ? 1.f : 0.01f) * a.reward_coef; r.ct = a.transition_coef;
+  r.xenc = xenc; r.act = a.act; r.rew = a.rew; r.noise6 = a.noise6; r.noise7 = a.noise7; r.seed = a.seed; r.call = a.call;
+  r.call_dev = (const long long*)a.call_dev;
   r.za = blob + (use_trg ? L.off_za_trg : L.off_za_src);
   r.za_mf = L.za_member_floats; r.za_w1 = L.za_w1; r.za_b1 = L.za_b1; r.za_w2 = L.za_w2; r.za_b2 = L.za_b2;
   r.enc_out = w.enc_out; r.zt = w.zt; r.tr_out = w.tr_out; r.dz3tr = w.dz3tr; r.xrw = w.xrw; r.rw_out = w.rw_out;
@@ -852,7 +848,7 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
     const long long n = (long long)NENS * L.za_member_floats;
     const int64_t oz = use_trg ? L.off_za_trg : L.off_za_src;
     AdamTarget za{};
-    if (opt.on) za = pre_adam_target(opt.blob + oz, nullptr, opt.m + oz, opt.v + oz, opt.t_za, opt.t_dev ? opt.t_dev + 1 : nullptr, opt.lr, 1.f);
+    if (fused) za = pre_adam_target(a.blob + oz, nullptr, a.m + oz, a.v + oz, a.t_za, a.t_dev ? a.t_dev + 1 : nullptr, a.lr, 1.f);
     rc = fork(2);                                    // (the action encoder's reduction + Adam feed nothing later either)
     if (rc) return rc;
     hipLaunchKernelGGL(k_pre_za_reduce, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st2, w.zap, w.nch, n, gptr(oz), za);
@@ -871,31 +867,15 @@ static int pretrain_impl(int S, int A, int64_t b, int64_t b_global, int use_trg,
   // the step ends when both streams have: the main one waits for the side one
   if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
     return fail(MOBODY_E_LAUNCH, "pre-training: join of the side stream failed");
-  hipLaunchKernelGGL(k_pre_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, r.inv_bg, S, r.ce, r.cr, r.ct, loss_out, loss_acc);
+  hipLaunchKernelGGL(k_pre_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, r.inv_bg, S, r.ce, r.cr, r.ct, a.loss_out, a.loss_acc);
   MB_LAUNCH_OK("k_pre_loss_final");
   return 0;
 }
 
-extern "C" int mobody_pretrain_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                                     const float* blob, const float* blob_T, const float* xenc, const float* act,
-                                     const float* rew, const float* noise6, const float* noise7, uint32_t seed, uint32_t call,
-                                     float* grad, float* loss_out, float* workspace, int precision, float transition_coef,
-                                     float reward_coef, void* stream) {
-  MB_REQUIRE(grad, "mobody_pretrain_grads: grad is null");
-  return pretrain_impl(S, A, b, b_global, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise6, noise7, seed, call,
-                       nullptr, grad, PreOpt{}, loss_out, nullptr, workspace, precision, stream, transition_coef, reward_coef);
-}
-
-extern "C" int mobody_pretrain_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
-                                      const float* xenc, const float* act, const float* rew, const float* noise6,
-                                      const float* noise7, uint32_t seed, uint32_t call, const int64_t* call_dev, float* m,
-                                      float* v, int64_t t_main, int64_t t_za, const int64_t* t_dev, float lr, float* loss_out,
-                                      float* loss_acc, float* workspace, int precision, void* stream) {
-  MB_REQUIRE(m && v, "mobody_pretrain_update: null pointer");
-  MB_REQUIRE(t_dev != nullptr || (t_main >= 1 && t_za >= 1), "mobody_pretrain_update: step counts are 1-based");
-  PreOpt o{1, blob, blob_T, m, v, t_main, t_za, t_dev, lr};
-  return pretrain_impl(S, A, b, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise6, noise7, seed, call, call_dev,
-                       nullptr, o, loss_out, loss_acc, workspace, precision, stream);
+extern "C" int mobody_pretrain(const MobodyPretrain* a, void* stream) {
+  MB_BLOCK("mobody_pretrain", a, MobodyPretrain);
+  int rc = pre_block_check("mobody_pretrain", *a);
+  return rc ? rc : pretrain_impl(*a, stream);
 }
 
 extern "C" int mobody_pretrain_adam(int S, int A, int use_trg, float* blob, float* blob_T, const float* grad, float* m,
@@ -1204,34 +1184,38 @@ extern "C" int64_t mobody_pretrain_mopo_workspace(int S, int A, int64_t b) {
   return w.total;
 }
 
-static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                              const float* blob, const float* blob_T, const float* xenc, const float* act, const float* rew,
-                              const float* noise, uint32_t seed, uint32_t call, const int64_t* call_dev, float* grad,
-                              const PreOpt& opt, float* loss_out, float* loss_acc, float* workspace, int precision, void* stream) {
+static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
+  const char* who = "mobody_pretrain_mopo";
+  const int S = a.S, A = a.A, use_trg = a.use_trg, precision = a.precision;
+  const int64_t b = a.b;
+  const float *blob = a.blob, *blob_T = a.blob_T, *xenc = a.xenc, *act = a.act;
+  float* grad = a.grad;
+  const bool fused = a.m != nullptr;
   MobodyPretrainMopoLayout L;
   int rc = mobody_pretrain_mopo_layout(S, A, &L);
   if (rc) return rc;
-  rc = check_precision("mobody_pretrain_mopo", precision, true, PREC_F32_OR_F16X2);
+  rc = check_precision(who, precision, true, PREC_F32_OR_F16X2);
   if (rc) return rc;
   const bool f16 = precision == PREC_F16X2;
-  MB_REQUIRE(b >= 1 && b_global >= b, "mobody_pretrain_mopo: need 1 <= b <= b_global");
-  MB_REQUIRE(blob && blob_T && xenc && act && rew && (grad || opt.on) && loss_out && workspace, "mobody_pretrain_mopo: null pointer");
+  MB_REQUIRE(b >= 1 && a.b_global >= b, "%s: need 1 <= b <= b_global", who);
+  MB_REQUIRE(blob && blob_T && xenc && act && a.rew && a.loss_out && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(!fused || a.t_dev != nullptr || a.t >= 1, "%s: the step count is 1-based", who);
   auto region_adam = [&](int64_t off, int64_t toff) {
-    if (!opt.on) return AdamTarget{};
-    return pre_adam_target(opt.blob + off, opt.blob_T + toff, opt.m + off, opt.v + off, opt.t_main, opt.t_dev, opt.lr, 1.f, precision);
+    if (!fused) return AdamTarget{};
+    return pre_adam_target(a.blob + off, a.blob_T + toff, a.m + off, a.v + off, a.t, a.t_dev, a.lr, 1.f, precision);
   };
   auto gptr = [&](int64_t off) { return grad ? grad + off : nullptr; };
   MopoWs w;
-  mopo_carve(L, b, workspace, w);
+  mopo_carve(L, b, a.workspace, w);
   hipStream_t st = as_stream(stream);
   const long long R2 = 2 * b;
-  const float ce = (use_trg ? 5.f : 1.f) * encoder_loss_coef, cr = use_trg ? 1.f : 0.01f, inv_bg = 1.f / (float)b_global;
+  const float ce = (use_trg ? 5.f : 1.f) * a.encoder_loss_coef, cr = use_trg ? 1.f : 0.01f, inv_bg = 1.f / (float)a.b_global;
   MopoRow r{};
   r.S = S; r.A = A; r.Np3 = L.dyn.Np3; r.b = b; r.inv_bg = inv_bg; r.ce = ce;
-  r.xenc = xenc; r.act = act; r.noise = noise; r.seed = seed; r.call = call; r.call_dev = (const long long*)call_dev;
+  r.xenc = xenc; r.act = act; r.noise = a.noise; r.seed = a.seed; r.call = a.call; r.call_dev = (const long long*)a.call_dev;
   r.f = w.f; r.xrw = w.xrw; r.fnz = w.fnz; r.dfake = w.dfake; r.dz3 = w.dz3d; r.lossp = w.lossp + w.lo.rt;
   PreRow pr{};                                         // what k_pre_reward_seed reads
-  pr.S = S; pr.A = A; pr.b = b; pr.inv_bg = inv_bg; pr.cr = cr; pr.rew = rew; pr.rw_out = w.rw_out; pr.dz3rw = w.dz3rw;
+  pr.S = S; pr.A = A; pr.b = b; pr.inv_bg = inv_bg; pr.cr = cr; pr.rew = a.rew; pr.rw_out = w.rw_out; pr.dz3rw = w.dz3rw;
   pr.lossp = w.lossp;
   const float *Pd = blob + L.off_dyn, *Prw = blob + L.off_rw;
   const float *Td = blob_T + L.t_off_dyn, *Trw = blob_T + L.t_off_rw;
@@ -1282,30 +1266,15 @@ static int pretrain_mopo_impl(int S, int A, int64_t b, int64_t b_global, int use
   if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
     return rc ? rc : fail(MOBODY_E_LAUNCH, "mopo pre-training: join of the side stream failed");
   if (rc) return rc;
-  hipLaunchKernelGGL(k_mopo_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, inv_bg, S, ce, cr, loss_out, loss_acc);
+  hipLaunchKernelGGL(k_mopo_loss_final, dim3(1), dim3(256), 0, st, w.lossp, w.lo, inv_bg, S, ce, cr, a.loss_out, a.loss_acc);
   MB_LAUNCH_OK("k_mopo_loss_final");
   return 0;
 }
 
-extern "C" int mobody_pretrain_mopo_grads(int S, int A, int64_t b, int64_t b_global, int use_trg, float encoder_loss_coef,
-                                          const float* blob, const float* blob_T, const float* xenc, const float* act,
-                                          const float* rew, const float* noise, uint32_t seed, uint32_t call, float* grad,
-                                          float* loss_out, float* workspace, int precision, void* stream) {
-  MB_REQUIRE(grad, "mobody_pretrain_mopo_grads: grad is null");
-  return pretrain_mopo_impl(S, A, b, b_global, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise, seed, call, nullptr,
-                            grad, PreOpt{}, loss_out, nullptr, workspace, precision, stream);
-}
-
-extern "C" int mobody_pretrain_mopo_update(int S, int A, int64_t b, int use_trg, float encoder_loss_coef, float* blob, float* blob_T,
-                                           const float* xenc, const float* act, const float* rew, const float* noise, uint32_t seed,
-                                           uint32_t call, const int64_t* call_dev, float* m, float* v, int64_t t,
-                                           const int64_t* t_dev, float lr, float* loss_out, float* loss_acc, float* workspace,
-                                           int precision, void* stream) {
-  MB_REQUIRE(m && v, "mobody_pretrain_mopo_update: null pointer");
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_pretrain_mopo_update: the step count is 1-based");
-  PreOpt o{1, blob, blob_T, m, v, t, 0, t_dev, lr};
-  return pretrain_mopo_impl(S, A, b, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, noise, seed, call, call_dev,
-                            nullptr, o, loss_out, loss_acc, workspace, precision, stream);
+extern "C" int mobody_pretrain_mopo(const MobodyPretrainMopo* a, void* stream) {
+  MB_BLOCK("mobody_pretrain_mopo", a, MobodyPretrainMopo);
+  int rc = pre_block_check("mobody_pretrain_mopo", *a);
+  return rc ? rc : pretrain_mopo_impl(*a, stream);
 }
 
 extern "C" int mobody_pretrain_mopo_adam(int S, int A, float* blob, float* blob_T, const float* grad, float* m, float* v,

@@ -192,6 +192,22 @@ struct AdamTarget {
 };
 __device__ __forceinline__ int adam_step_count(const AdamTarget& a) { return a.t_dev != nullptr ? (int)a.t_dev[0] : a.t_host; }
 
+// torch.optim.Adam scalar bookkeeping in double, as the reference's host code does; t_dev != null: the kernel forms the bias
+// corrections itself from the device step count.  target == null or tau < 0: no Polyak update.  The caller sets target_T / bump.
+inline AdamTarget adam_target(float* blob, float* blob_T, float* m, float* v, float* target, int64_t t, const int64_t* t_dev,
+                              float lr, float tau, float grad_scale, int precision) {
+  const double tt = t_dev ? 1.0 : (double)t;
+  const double bc1 = 1.0 - pow(0.9, tt), bc2 = 1.0 - pow(0.999, tt);
+  AdamTarget a{};
+  a.p = blob; a.m = m; a.v = v; a.blob_T = blob_T;
+  a.target = (target != nullptr && tau >= 0.f) ? target : nullptr;
+  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
+  a.c.tau = tau; a.c.one_minus_tau = (float)(1.0 - (double)tau); a.c.gscale = grad_scale;
+  a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1; a.precision = precision;
+  a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
+  return a;
+}
+
 // after an element's update: a non-finite parameter in any mode, an online / target W2 value past the fp16 planes' range
 __device__ __forceinline__ void health_after_update(const AdamTarget& a, float pj, bool w2_plane, float tj, bool w2t_plane) {
   if (a.health == nullptr) return;

@@ -248,42 +248,51 @@ extern "C" int64_t mobody_train_workspace(const MobodyTrainDims* d) {
   return w.total;
 }
 
-static AdamTarget adam_target(float* blob, float* blob_T, float* m, float* v, float* target, int64_t t, const int64_t* t_dev,
-                              float lr, float tau, float grad_scale, int precision);
-
-static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob, const float* actor_blob_T,
-                       const float* q_blob, const float* q_blob_T, const float* qtarg_blob, const float* qtarg_blob_T,
-                       const float* state, const float* action,
-                       const float* next_state, const float* reward, const float* not_done, const float* q_next,
-                       float* grad_q, const AdamTarget& adam, float* loss_out, float* workspace, int policy_forward,
-                       void* stream, int phase = 0, const FwdGather* gather = nullptr) {
+static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* stream) {
   // gather != null (phase 0, q_next == null): state .. not_done are not read by the first forward launch but WRITTEN by it --
   // its tiles draw and fetch the minibatch rows themselves (layers.h FwdGather; the block arrives with `g` filled)
   // phase: 0 the whole step; 1 only its forwards (nothing of them reads `reward`); 2 only the backward, weight gradients and
   // reduction / optimizer step -- the caller may let another stream finish rewriting `reward` (penalty_type 'par': an ensemble
   // step on the source rows) between the two
-  int rc = check_dims(d, "mobody_critic_step");
+  const char* who = "mobody_critic";
+  const MobodyTrainDims* d = &a.d;
+  const MobodyHyper* h = &a.h;
+  const bool fused = a.m != nullptr;
+  int rc = check_dims(d, who);
   if (rc) return rc;
-  MB_REQUIRE(h && q_blob && q_blob_T && state && action && reward && not_done && (grad_q || adam.on) && loss_out && workspace,
-             "mobody_critic_step: null pointer");
-  MB_REQUIRE(q_next || (actor_blob && qtarg_blob && next_state), "mobody_critic_step: need q_next or actor/target/next_state");
-  rc = check_precision("mobody_critic_step", h->precision, q_next != nullptr || (actor_blob_T && qtarg_blob_T));
+  MB_REQUIRE(a.q_blob && a.q_blob_T && a.state && a.action && a.reward && a.not_done && a.loss_out && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(a.q_next || (a.actor_blob && a.qtarg_blob && a.next_state), "%s: need q_next or actor/target/next_state", who);
+  rc = check_precision(who, h->precision, a.q_next != nullptr || (a.actor_blob_T && a.qtarg_blob_T));
   if (rc) return rc;
-  const int prec = h->precision;
-  const float *aT = prec != PREC_F32 ? actor_blob_T : nullptr, *qT = prec != PREC_F32 ? q_blob_T : nullptr, *tT = prec != PREC_F32 ? qtarg_blob_T : nullptr;
+  if (fused) {
+    MB_REQUIRE(a.qtarg_blob, "%s: null pointer", who);
+    MB_REQUIRE(a.t_dev != nullptr || a.t >= 1, "%s: step t must be >= 1", who);
+    MB_REQUIRE(a.bump == nullptr || a.bump != a.t_dev, "%s: bump must not be the step word the launch reads", who);
+  } else {
+    MB_REQUIRE(a.bump == nullptr, "%s: bump is incremented by the optimizer launch: it needs m, v", who);
+  }
   TrainWs w;
-  rc = carve(*d, workspace, w);
+  rc = carve(*d, a.workspace, w);
   if (rc) return rc;
+  AdamTarget adam{};
+  if (fused) {
+    adam = adam_target(a.q_blob, a.q_blob_T, a.m, a.v, a.qtarg_blob, a.t, a.t_dev, a.lr, h->tau, 1.f, h->precision);
+    adam.target_T = a.qtarg_blob_T;
+    adam.bump = (long long*)a.bump;
+  }
+  const float *q_blob = a.q_blob, *state = a.state, *action = a.action, *next_state = a.next_state, *q_next = a.q_next;
+  const int prec = h->precision;
+  const float *aT = prec != PREC_F32 ? a.actor_blob_T : nullptr, *qT = prec != PREC_F32 ? a.q_blob_T : nullptr, *tT = prec != PREC_F32 ? a.qtarg_blob_T : nullptr;
   hipStream_t st = as_stream(stream);
   const long long N = d->N;
   const int S = d->S, A = d->A;
   // online twin-Q(s, a), activations kept for the backward (:196), together with a' = pi(s') (:191) in one launch
   const Mlp3FwdArgs fq = fwd_args(q_blob, w.Lq, state, S, action, A, N, w.q, 0, 1.f, w.xq, w.h1q, w.h2q, w.mq1, w.mq2, qT,
                                   prec == PREC_F16X2 ? w.eh1q : nullptr);
-  if (phase == 2) {
+  if (a.phase == 2) {
     // forwards already enqueued by the phase-1 call
   } else if (q_next == nullptr) {
-    const Mlp3FwdArgs fpn = fwd_args(actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT);
+    const Mlp3FwdArgs fpn = fwd_args(a.actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT);
     if (gather != nullptr) {
       FwdGather fg = *gather;
       fwd_set_gather(fg, 0, fq, 0);                // state | action open the ring row, next_state follows them
@@ -295,189 +304,132 @@ static int critic_impl(const MobodyTrainDims* d, const MobodyHyper* h, const flo
     // target twin-Q(s', a') (:192) -- and, when the caller asks for it, pi(s) of the coming actor phase in the same
     // launch: the actor is not updated in between, and a twin-Q launch alone is 2.5 workgroups per CU where the
     // merged one is 3.75 (the actor phase then opens with Q(s_t,a_t) alone: exactly 2 per CU)
-    const Mlp3FwdArgs ft = fwd_args(qtarg_blob, w.Lq, next_state, S, w.pin, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
-    if (!rc && policy_forward)
-      rc = launch_mlp3_forward(ft, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+    const Mlp3FwdArgs ft = fwd_args(a.qtarg_blob, w.Lq, next_state, S, w.pin, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
+    if (!rc && a.policy_forward)
+      rc = launch_mlp3_forward(ft, 2, fwd_args(a.actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
                                                prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
     else if (!rc)
       rc = launch_mlp3_forward(ft, 2, ACT_RELU, prec, st);
   } else {
     rc = launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);                  // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229)
   }
-  if (rc || phase == 1) return rc;
+  if (rc || a.phase == 1) return rc;
   const float invNg = 1.f / (float)d->N_global;
   // TD error -> dz3 in the backward's prologue (mobody.py:190-207), then dz2, dz1 and the bias partials
-  Mlp3BwdArgs bq = bwd_args(w.Lq, q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
-  bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = reward; bq.seed.nd = not_done;
+  Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
+  bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = a.reward; bq.seed.nd = a.not_done;
   bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
   rc = launch_mlp3_bwd(bq, 2, false, st);
   if (rc) return rc;
   LossFinal lf{};                                  // q_loss = mse(q1,y)+mse(q2,y), local share of the global mean
-  lf.kind = 1; lf.nparts = 2 * w.ntiles; lf.scale = invNg; lf.parts = w.lossp; lf.out = loss_out;
-  return weight_grads(w.Lq, w.xq, w.h1q, w.h2q, w.dz3q, w.dz2, w.dz1, N, w, grad_q, lf, adam, st, prec, w.eh1q);
+  lf.kind = 1; lf.nparts = 2 * w.ntiles; lf.scale = invNg; lf.parts = w.lossp; lf.out = a.loss_out;
+  return weight_grads(w.Lq, w.xq, w.h1q, w.h2q, w.dz3q, w.dz2, w.dz1, N, w, a.grad_q, lf, adam, st, prec, w.eh1q);
 }
 
-extern "C" int mobody_critic_step(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                  const float* actor_blob_T, const float* q_blob, const float* q_blob_T,
-                                  const float* qtarg_blob, const float* qtarg_blob_T, const float* state,
-                                  const float* action, const float* next_state, const float* reward, const float* not_done,
-                                  const float* q_next, float* grad_q, float* loss_out, float* workspace, int policy_forward,
-                                  void* stream) {
-  MB_REQUIRE(grad_q, "mobody_critic_step: grad_q is null");
-  return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
-                     not_done, q_next, grad_q, AdamTarget{}, loss_out, workspace, policy_forward, stream);
-}
-
-extern "C" int mobody_critic_update(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                    const float* actor_blob_T, float* q_blob, float* q_blob_T, float* qtarg_blob,
-                                    float* qtarg_blob_T, const float* state, const float* action, const float* next_state,
-                                    const float* reward, const float* not_done, const float* q_next, float* m, float* v,
-                                    int64_t t, const int64_t* t_dev, float lr, float* loss_out, float* workspace,
-                                    int policy_forward, int64_t* bump, void* stream) {
-  MB_REQUIRE(h && q_blob && q_blob_T && qtarg_blob && m && v, "mobody_critic_update: null pointer");
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_critic_update: step t must be >= 1");
-  MB_REQUIRE(bump == nullptr || bump != t_dev, "mobody_critic_update: bump must not be the step word the launch reads");
-  AdamTarget at = adam_target(q_blob, q_blob_T, m, v, qtarg_blob, t, t_dev, lr, h->tau, 1.f, h->precision);
-  at.target_T = qtarg_blob_T;
-  at.bump = (long long*)bump;
-  return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
-                     not_done, q_next, nullptr, at, loss_out, workspace, policy_forward, stream);
-}
-
-extern "C" int mobody_critic_update_gather(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                           const float* actor_blob_T, float* q_blob, float* q_blob_T, float* qtarg_blob,
-                                           float* qtarg_blob_T, float* state, float* action, float* next_state, float* reward,
-                                           float* not_done, const float* q_next, float* m, float* v, int64_t t,
-                                           const int64_t* t_dev, float lr, float* loss_out, float* workspace, int policy_forward,
-                                           int64_t* bump, int phase, const MobodyGatherRng* gr, void* stream) {
-  const char* who = "mobody_critic_update_gather";
-  MB_REQUIRE(h && q_blob && q_blob_T && qtarg_blob && m && v && d && gr, "%s: null pointer", who);
-  MB_REQUIRE(phase == 0, "%s: the step cannot be split (phase %d): the first forward launch writes the minibatch the backward reads", who, phase);
-  MB_REQUIRE(q_next == nullptr, "%s: q_next given: the launch that gathers is the one that evaluates pi(s')", who);
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "%s: step t must be >= 1", who);
-  MB_REQUIRE(bump == nullptr || bump != t_dev, "%s: bump must not be the step word the launch reads", who);
+extern "C" int mobody_critic(const MobodyCritic* a, void* stream) {
+  const char* who = "mobody_critic";
+  MB_BLOCK(who, a, MobodyCritic);
+  MB_REQUIRE((a->grad_q != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_q and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad_q || (a->m && a->v), "%s: null pointer", who);
+  MB_REQUIRE(a->phase >= 0 && a->phase <= 2, "%s: phase is 0 (the whole step), 1 (forwards) or 2 (backward + update)", who);
+  if (a->gather == nullptr) return critic_impl(*a, nullptr, stream);
+  const MobodyGatherRng* gr = a->gather;
+  MB_REQUIRE(a->phase == 0, "%s: the step cannot be split (phase %d): the first forward launch writes the minibatch the backward reads", who, a->phase);
+  MB_REQUIRE(a->q_next == nullptr, "%s: q_next given: the launch that gathers is the one that evaluates pi(s')", who);
   FwdGather fg{};
   long long N;
-  int rc = gather_args_rng(who, fg.g, gr->bufs, gr->counts, gr->nbuf, d->S, d->A, gr->seeds, gr->call_offsets, gr->counter, gr->sizes,
-                           state, action, next_state, reward, not_done, gr->bump, gr->nbump, N);
+  int rc = gather_args_rng(who, fg.g, gr->bufs, gr->counts, gr->nbuf, a->d.S, a->d.A, gr->seeds, gr->call_offsets, gr->counter, gr->sizes,
+                           a->state, a->action, a->next_state, a->reward, a->not_done, gr->bump, gr->nbump, N);
   if (rc) return rc;
-  MB_REQUIRE(N == d->N, "%s: the counts add up to %lld rows, the step runs on %lld", who, N, (long long)d->N);
+  MB_REQUIRE(N == a->d.N, "%s: the counts add up to %lld rows, the step runs on %lld", who, N, (long long)a->d.N);
   for (int k = 0; k < gr->nbuf; ++k)
     MB_REQUIRE(gr->counts[k] == 0 || fg.g.packed[k], "%s: source %d is not a row-interleaved ring (mobody_ring_pitch)", who, k);
-  AdamTarget at = adam_target(q_blob, q_blob_T, m, v, qtarg_blob, t, t_dev, lr, h->tau, 1.f, h->precision);
-  at.target_T = qtarg_blob_T;
-  at.bump = (long long*)bump;
-  return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
-                     not_done, nullptr, nullptr, at, loss_out, workspace, policy_forward, stream, 0, &fg);
+  return critic_impl(*a, &fg, stream);
 }
 
-extern "C" int mobody_critic_update_phase(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                          const float* actor_blob_T, float* q_blob, float* q_blob_T, float* qtarg_blob,
-                                          float* qtarg_blob_T, const float* state, const float* action, const float* next_state,
-                                          const float* reward, const float* not_done, const float* q_next, float* m, float* v,
-                                          int64_t t, const int64_t* t_dev, float lr, float* loss_out, float* workspace,
-                                          int policy_forward, int64_t* bump, int phase, void* stream) {
-  MB_REQUIRE(h && q_blob && q_blob_T && qtarg_blob && m && v, "mobody_critic_update_phase: null pointer");
-  MB_REQUIRE(phase == 1 || phase == 2, "mobody_critic_update_phase: phase is 1 (forwards) or 2 (backward + update)");
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_critic_update_phase: step t must be >= 1");
-  MB_REQUIRE(bump == nullptr || bump != t_dev, "mobody_critic_update_phase: bump must not be the step word the launch reads");
-  AdamTarget at = adam_target(q_blob, q_blob_T, m, v, qtarg_blob, t, t_dev, lr, h->tau, 1.f, h->precision);
-  at.target_T = qtarg_blob_T;
-  at.bump = (long long*)bump;
-  return critic_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, qtarg_blob, qtarg_blob_T, state, action, next_state, reward,
-                     not_done, q_next, nullptr, at, loss_out, workspace, policy_forward, stream, phase);
-}
-
-extern "C" int mobody_actor_forward(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                    const float* actor_blob_T, const float* q_blob, const float* q_blob_T,
-                                    const float* state, const float* action, float* stats, float* workspace, int policy_ready,
-                                    void* stream) {
-  int rc = check_dims(d, "mobody_actor_forward");
+extern "C" int mobody_actor_forward(const MobodyActor* a, void* stream) {
+  const char* who = "mobody_actor_forward";
+  MB_BLOCK(who, a, MobodyActor);
+  const MobodyTrainDims* d = &a->d;
+  const MobodyHyper* h = &a->h;
+  int rc = check_dims(d, who);
   if (rc) return rc;
-  MB_REQUIRE(h && actor_blob && q_blob && state && action && stats && workspace, "mobody_actor_forward: null pointer");
-  rc = check_precision("mobody_actor_forward", h->precision, actor_blob_T && q_blob_T);
+  MB_REQUIRE(a->actor_blob && a->q_blob && a->state && a->action && a->stats && a->workspace, "%s: null pointer", who);
+  rc = check_precision(who, h->precision, a->actor_blob_T && a->q_blob_T);
   if (rc) return rc;
   const int prec = h->precision;
-  const float *aT = prec != PREC_F32 ? actor_blob_T : nullptr, *qT = prec != PREC_F32 ? q_blob_T : nullptr;
+  const float *aT = prec != PREC_F32 ? a->actor_blob_T : nullptr, *qT = prec != PREC_F32 ? a->q_blob_T : nullptr;
+  const float *q_blob = a->q_blob, *state = a->state;
   TrainWs w;
-  rc = carve(*d, workspace, w);
+  rc = carve(*d, a->workspace, w);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
   const long long N = d->N, Nt = d->Nt;
   const int S = d->S, A = d->A;
   // Q(s_true, a_true) for the BC weights (:251) and pi(s) on the whole mixed batch (its first Nt rows are
   // pi(s_true), mobody.py:249,315) in one launch -- unless the critic call already left pi(s) in the workspace
-  const Mlp3FwdArgs fb = fwd_args(q_blob, w.Lq, state, S, action, A, Nt, w.qb, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, qT);
+  const Mlp3FwdArgs fb = fwd_args(q_blob, w.Lq, state, S, a->action, A, Nt, w.qb, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, qT);
   // Q(s, pi(s)) with the freshly updated critic (:316); dQ/da through the frozen net needs only the ReLU signs
   const Mlp3FwdArgs fp = fwd_args(q_blob, w.Lq, state, S, w.pi, A, N, w.q, 0, 1.f, nullptr, nullptr, nullptr, w.mq1, w.mq2, qT);
-  if (policy_ready) {
+  if (a->policy_ready) {
     rc = launch_mlp3_forward(fb, 2, fp, 2, ACT_RELU, prec, st);                 // both on the same critic: one launch of N + Nt rows (0.384 -> 0.380 ms/step)
   } else {
-    rc = launch_mlp3_forward(fb, 2, fwd_args(actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+    rc = launch_mlp3_forward(fb, 2, fwd_args(a->actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
                                              prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
     if (!rc) rc = launch_mlp3_forward(fp, 2, ACT_RELU, prec, st);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, stats);
+  hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, a->stats);
   MB_LAUNCH_OK("k_actor_stats");
   return 0;
 }
 
-static int actor_backward_impl(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                               const float* actor_blob_T, const float* q_blob, const float* q_blob_T, const float* state,
-                               const float* action, const float* stats, const float* v_true, float* grad_actor,
-                               const AdamTarget& adam, float* loss_out, float* workspace, void* stream) {
-  int rc = check_dims(d, "mobody_actor_backward");
+static int actor_backward_impl(const MobodyActor& a, void* stream) {
+  const char* who = "mobody_actor_backward";
+  const MobodyTrainDims* d = &a.d;
+  const MobodyHyper* h = &a.h;
+  const bool fused = a.m != nullptr;
+  int rc = check_dims(d, who);
   if (rc) return rc;
-  MB_REQUIRE(h && actor_blob && actor_blob_T && q_blob && q_blob_T && state && action && stats && (grad_actor || adam.on) &&
-                 loss_out && workspace, "mobody_actor_backward: null pointer");
-  rc = check_precision("mobody_actor_backward", h->precision, true);
+  MB_REQUIRE(a.actor_blob && a.actor_blob_T && a.q_blob && a.q_blob_T && a.state && a.action && a.stats && a.loss_out && a.workspace,
+             "%s: null pointer", who);
+  rc = check_precision(who, h->precision, true);
   if (rc) return rc;
+  MB_REQUIRE(!fused || a.t_dev != nullptr || a.t >= 1, "%s: step t must be >= 1", who);
   TrainWs w;
-  rc = carve(*d, workspace, w);
+  rc = carve(*d, a.workspace, w);
   if (rc) return rc;
+  const AdamTarget adam = fused ? adam_target(a.actor_blob, a.actor_blob_T, a.m, a.v, nullptr, a.t, a.t_dev, a.lr, -1.f, 1.f, h->precision) : AdamTarget{};
   hipStream_t st = as_stream(stream);
   const long long N = d->N;
   ActorRowArgs ra{};
-  ra.qp = w.q; ra.qb = w.qb; ra.stats = stats; ra.pi = w.pi; ra.act = action; ra.dxa = w.dxa; ra.v_true = v_true;
+  ra.qp = w.q; ra.qb = w.qb; ra.stats = a.stats; ra.pi = w.pi; ra.act = a.action; ra.dxa = w.dxa; ra.v_true = a.v_true;
   ra.bcw = w.bcw; ra.N = N; ra.Nt = d->Nt; ra.Ng = d->N_global; ra.Ntg = d->Nt_global > 0 ? d->Nt_global : 1;
   ra.A = d->A; ra.h = *h;
   // dq -> d(action) through the frozen twin-Q (parameters get no gradient, mobody.py:555-556); the prologue forms
   // -p_w/N d min(q1,q2) and the BC weights
-  Mlp3BwdArgs bq = bwd_args(w.Lq, q_blob_T, nullptr, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, h->precision);
+  Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, nullptr, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, h->precision);
   bq.seed.mode = 2; bq.seed.ar = ra;
   bq.dx = w.dxa; bq.dx_c0 = d->S; bq.dx_n = d->A;
   rc = launch_mlp3_bwd(bq, 2, true, st);
   if (rc) return rc;
   // actor: d(pre-tanh) from both members' dx and the BC term in the prologue, then the actor's own backward
-  Mlp3BwdArgs ba = bwd_args(w.La, actor_blob_T, w.dz3a, w.h1a, w.h2a, N, w.dz2, w.dz1, w.dbp, w.ma1, w.ma2, h->precision, w.edz2);
+  Mlp3BwdArgs ba = bwd_args(w.La, a.actor_blob_T, w.dz3a, w.h1a, w.h2a, N, w.dz2, w.dz1, w.dbp, w.ma1, w.ma2, h->precision, w.edz2);
   ba.seed.mode = 3; ba.seed.ar = ra; ba.seed.dz3_out = w.dz3a; ba.seed.lossp = w.lossp;
   rc = launch_mlp3_bwd(ba, 1, false, st);
   if (rc) return rc;
   LossFinal lf{};                                  // loss_out[0] = p_w*mean(-q) + bc_coef*L_BC, [1] = L_BC (local shares)
   lf.kind = 2; lf.nparts = w.ntiles; lf.scale_q = h->scale_q; lf.weight = h->weight; lf.bc_coef = h->bc_coef;
-  lf.ng = (float)ra.Ng; lf.ntg_a = (float)ra.Ntg * (float)ra.A; lf.parts = w.lossp; lf.stats = stats; lf.out = loss_out;
-  return weight_grads(w.La, w.xa, w.h1a, w.h2a, w.dz3a, w.dz2, w.dz1, N, w, grad_actor, lf, adam, st, h->precision, w.eh1a);
+  lf.ng = (float)ra.Ng; lf.ntg_a = (float)ra.Ntg * (float)ra.A; lf.parts = w.lossp; lf.stats = a.stats; lf.out = a.loss_out;
+  return weight_grads(w.La, w.xa, w.h1a, w.h2a, w.dz3a, w.dz2, w.dz1, N, w, a.grad_actor, lf, adam, st, h->precision, w.eh1a);
 }
 
-extern "C" int mobody_actor_backward(const MobodyTrainDims* d, const MobodyHyper* h, const float* actor_blob,
-                                     const float* actor_blob_T, const float* q_blob, const float* q_blob_T,
-                                     const float* state, const float* action, const float* stats, const float* v_true,
-                                     float* grad_actor, float* loss_out, float* workspace, void* stream) {
-  MB_REQUIRE(grad_actor, "mobody_actor_backward: grad_actor is null");
-  return actor_backward_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, v_true, grad_actor,
-                             AdamTarget{}, loss_out, workspace, stream);
-}
-
-extern "C" int mobody_actor_update(const MobodyTrainDims* d, const MobodyHyper* h, float* actor_blob, float* actor_blob_T,
-                                   const float* q_blob, const float* q_blob_T, const float* state, const float* action,
-                                   const float* stats, const float* v_true, float* m, float* v, int64_t t,
-                                   const int64_t* t_dev, float lr, float* loss_out, float* workspace, void* stream) {
-  MB_REQUIRE(actor_blob && actor_blob_T && m && v, "mobody_actor_update: null pointer");
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_actor_update: step t must be >= 1");
-  return actor_backward_impl(d, h, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, v_true, nullptr,
-                             adam_target(actor_blob, actor_blob_T, m, v, nullptr, t, t_dev, lr, -1.f, 1.f, h ? h->precision : 0), loss_out,
-                             workspace, stream);
+extern "C" int mobody_actor_backward(const MobodyActor* a, void* stream) {
+  const char* who = "mobody_actor_backward";
+  MB_BLOCK(who, a, MobodyActor);
+  MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
+  return actor_backward_impl(*a, stream);
 }
 
 extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,
@@ -494,50 +446,26 @@ extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const 
   return 0;
 }
 
-// torch.optim.Adam scalar bookkeeping in double, as the reference's host code does
-static AdamTarget adam_target(float* blob, float* blob_T, float* m, float* v, float* target, int64_t t, const int64_t* t_dev,
-                              float lr, float tau, float grad_scale, int precision) {
-  const double tt = t_dev ? 1.0 : (double)t;
-  const double bc1 = 1.0 - pow(0.9, tt), bc2 = 1.0 - pow(0.999, tt);
-  AdamTarget a{};
-  a.p = blob; a.m = m; a.v = v; a.blob_T = blob_T;
-  a.target = (target != nullptr && tau >= 0.f) ? target : nullptr;
-  a.c.step_size = (float)((double)lr / bc1); a.c.bc2_sqrt = (float)sqrt(bc2);
-  a.c.tau = tau; a.c.one_minus_tau = (float)(1.0 - (double)tau); a.c.gscale = grad_scale;
-  a.t_dev = (const long long*)t_dev; a.lr = lr; a.on = 1; a.precision = precision;
-  a.health = health_words(); a.health_tag = a.health ? health_next_tag() : 0; a.t_host = (int)t;
-  return a;
-}
-
-static int adam_impl(int in_dim, int out_dim, int members, float* blob, float* blob_T, const float* grad, float* m,
-                     float* v, float* target, float* target_T, int64_t t, const int64_t* t_dev, float lr, float tau,
-                     float grad_scale, int precision, void* stream) {
+static int adam_impl(const MobodyAdam& a, void* stream) {
+  const char* who = "mobody_adam_polyak";
   MobodyMlpLayout L;
-  int rc = mobody_mlp_layout(in_dim, out_dim, members, &L);
+  int rc = mobody_mlp_layout(a.in_dim, a.out_dim, a.members, &L);
   if (rc) return rc;
-  MB_REQUIRE(blob && grad && m && v, "mobody_adam_polyak: null pointer");
-  MB_REQUIRE(t_dev != nullptr || t >= 1, "mobody_adam_polyak: step t must be >= 1");
-  rc = check_precision("mobody_adam_polyak", precision, true);
+  MB_REQUIRE(a.blob && a.grad && a.m && a.v, "%s: null pointer", who);
+  MB_REQUIRE(a.t_dev != nullptr || a.t >= 1, "%s: step t must be >= 1", who);
+  rc = check_precision(who, a.precision, true);
   if (rc) return rc;
-  AdamTarget a = adam_target(blob, blob_T, m, v, target, t, t_dev, lr, tau, grad_scale, precision);
-  a.target_T = a.target ? target_T : nullptr;
+  AdamTarget at = adam_target(a.blob, a.blob_T, a.m, a.v, a.target, a.t, a.t_dev, a.lr, a.tau, a.grad_scale, a.precision);
+  at.target_T = at.target ? a.target_T : nullptr;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)cdiv(L.total_floats, 256)), dim3(256), 0, st, a, grad, (long long)L.total_floats, L);
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)cdiv(L.total_floats, 256)), dim3(256), 0, st, at, a.grad, (long long)L.total_floats, L);
   MB_LAUNCH_OK("k_adam");
   return 0;       // (W1T's zero padding columns k >= Kp1 are written once by mobody_mlp_transpose and never change)
 }
 
-extern "C" int mobody_adam_polyak(int in_dim, int out_dim, int members, float* blob, float* blob_T, const float* grad,
-                                  float* m, float* v, float* target, float* target_T, int64_t t, float lr, float tau,
-                                  float grad_scale, int precision, void* stream) {
-  return adam_impl(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, target_T, t, nullptr, lr, tau, grad_scale, precision, stream);
-}
-
-extern "C" int mobody_adam_polyak_dev(int in_dim, int out_dim, int members, float* blob, float* blob_T,
-                                      const float* grad, float* m, float* v, float* target, float* target_T,
-                                      const int64_t* t_dev, float lr, float tau, float grad_scale, int precision, void* stream) {
-  MB_REQUIRE(t_dev != nullptr, "mobody_adam_polyak_dev: t_dev is null");
-  return adam_impl(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, target_T, 0, t_dev, lr, tau, grad_scale, precision, stream);
+extern "C" int mobody_adam_polyak(const MobodyAdam* a, void* stream) {
+  MB_BLOCK("mobody_adam_polyak", a, MobodyAdam);
+  return adam_impl(*a, stream);
 }
 
 // ---- PAR reward penalty: r -= coef * mean_d (s'_true - s'_model)^2   (mobody.py:428-434) ----

@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import check, cur_stream, load, ptr
+from ._lib import BLOCK_BYTES as _BYTES
 
 
 def _f32(t, device=None):
@@ -248,53 +249,68 @@ def mlp_transpose(blob, in_dim, out_dim, members, out=None, precision=0):
     return bt
 
 
+# Block fillers: one per argument block, shared by the wrappers of its gradient-only and fused forms.  The shared fields are set
+# by keyword in ONE constructor call (everything else stays 0 / NULL); a wrapper then assigns the few fields of its own form.
+# Forwarding those as **kwargs through helpers doubled the host cost of a call, and so did spelling out every NULL.
+def _critic_block(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, loss_out, ws, q_next, policy_forward,
+                  actor_blob_T, qtarg_blob_T):
+    s, a, s2, r, nd = batch
+    return _lib.MobodyCritic(struct_bytes=_BYTES[_lib.MobodyCritic], d=dims, h=hyp, actor_blob=ptr(actor_blob),
+                             actor_blob_T=ptr(actor_blob_T), q_blob=ptr(q_blob), q_blob_T=ptr(q_blob_T),
+                             qtarg_blob=ptr(qtarg_blob), qtarg_blob_T=ptr(qtarg_blob_T), state=ptr(s), action=ptr(a),
+                             next_state=ptr(s2), reward=ptr(r), not_done=ptr(nd), q_next=ptr(q_next),
+                             policy_forward=int(bool(policy_forward)), loss_out=ptr(loss_out), workspace=ptr(ws))
+
+
+def _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws):
+    return _lib.MobodyActor(struct_bytes=_BYTES[_lib.MobodyActor], d=dims, h=hyp, actor_blob=ptr(actor_blob),
+                            actor_blob_T=ptr(actor_blob_T), q_blob=ptr(q_blob), q_blob_T=ptr(q_blob_T), state=ptr(state),
+                            action=ptr(action), stats=ptr(stats), workspace=ptr(ws))
+
+
 def critic_step(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, grad_q, loss_out, ws, q_next=None,
                 policy_forward=False, actor_blob_T=None, qtarg_blob_T=None):
-    s, a, s2, r, nd = batch
-    check(load().mobody_critic_step(C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob), ptr(q_blob_T),
-                                    ptr(qtarg_blob), ptr(qtarg_blob_T), ptr(s), ptr(a), ptr(s2), ptr(r), ptr(nd), ptr(q_next), ptr(grad_q),
-                                    ptr(loss_out), ptr(ws), int(bool(policy_forward)), cur_stream()), "mobody_critic_step")
+    blk = _critic_block(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, loss_out, ws, q_next, policy_forward,
+                        actor_blob_T, qtarg_blob_T)
+    blk.grad_q = ptr(grad_q)
+    check(load().mobody_critic(C.byref(blk), cur_stream()), "mobody_critic")
 
 
 def actor_forward(dims, hyp, actor_blob, q_blob, state, action, stats, ws, policy_ready=False, actor_blob_T=None, q_blob_T=None):
-    check(load().mobody_actor_forward(C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob), ptr(q_blob_T), ptr(state),
-                                      ptr(action), ptr(stats), ptr(ws), int(bool(policy_ready)), cur_stream()),
-          "mobody_actor_forward")
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.policy_ready = int(bool(policy_ready))
+    check(load().mobody_actor_forward(C.byref(blk), cur_stream()), "mobody_actor_forward")
 
 
 def actor_backward(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, grad_actor, loss_out,
                    ws, v_true=None):
-    check(load().mobody_actor_backward(C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob),
-                                       ptr(q_blob_T), ptr(state), ptr(action), ptr(stats), ptr(v_true), ptr(grad_actor),
-                                       ptr(loss_out), ptr(ws), cur_stream()), "mobody_actor_backward")
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.v_true, blk.grad_actor, blk.loss_out = ptr(v_true), ptr(grad_actor), ptr(loss_out)
+    check(load().mobody_actor_backward(C.byref(blk), cur_stream()), "mobody_actor_backward")
 
 
 def critic_update(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, m, v, t, lr, loss_out, ws, q_next=None,
                   t_dev=None, policy_forward=False, actor_blob_T=None, qtarg_blob_T=None, bump=None, phase=0, gather=None):
     """critic_step + Adam + Polyak in the fused single-GPU form (t: host step count, or t_dev: device int64[1]);
     bump: device int64[1] word (not t_dev) the optimizer launch increments by one.  phase 1 / 2: only the forwards / only the
-    backward + update (mobody_critic_update_phase: the caller joins whatever rewrites `reward` in between).
+    backward + update (MobodyCritic.phase: the caller joins whatever rewrites `reward` in between).
     gather: the arguments of gather_batch_rng up to `sizes`, plus its `bump`, as a dict -- the step's first forward launch then
-    draws and fetches the minibatch itself and WRITES `batch` (mobody_critic_update_gather: packed rings, no q_next, phase 0)."""
-    s, a, s2, r, nd = batch
-    args = (C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob), ptr(q_blob_T),
-            ptr(qtarg_blob), ptr(qtarg_blob_T), ptr(s), ptr(a), ptr(s2), ptr(r), ptr(nd), ptr(q_next), ptr(m),
-            ptr(v), int(t), ptr(t_dev), float(lr), ptr(loss_out), ptr(ws), int(bool(policy_forward)), ptr(bump))
+    draws and fetches the minibatch itself and WRITES `batch` (MobodyCritic.gather: packed rings, no q_next, phase 0)."""
+    blk = _critic_block(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, loss_out, ws, q_next, policy_forward,
+                        actor_blob_T, qtarg_blob_T)
+    blk.m, blk.v, blk.t, blk.t_dev, blk.lr, blk.bump, blk.phase = ptr(m), ptr(v), int(t), ptr(t_dev), float(lr), ptr(bump), int(phase)
     if gather is not None:
-        gr, keep = _gather_rng_args(**gather)
-        check(load().mobody_critic_update_gather(*args, int(phase), C.byref(gr), cur_stream()), "mobody_critic_update_gather")
-    elif phase:
-        check(load().mobody_critic_update_phase(*args, int(phase), cur_stream()), "mobody_critic_update_phase")
-    else:
-        check(load().mobody_critic_update(*args, cur_stream()), "mobody_critic_update")
+        gr, keep = _gather_rng_args(**gather)           # `keep`: the host arrays `gr` points into, alive until the call returns
+        blk.gather = C.pointer(gr)
+    check(load().mobody_critic(C.byref(blk), cur_stream()), "mobody_critic")
 
 
 def actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, m, v, t, lr, loss_out, ws,
                  v_true=None, t_dev=None):
-    check(load().mobody_actor_update(C.byref(dims), C.byref(hyp), ptr(actor_blob), ptr(actor_blob_T), ptr(q_blob),
-                                     ptr(q_blob_T), ptr(state), ptr(action), ptr(stats), ptr(v_true), ptr(m), ptr(v),
-                                     int(t), ptr(t_dev), float(lr), ptr(loss_out), ptr(ws), cur_stream()),
-          "mobody_actor_update")
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.v_true, blk.loss_out = ptr(v_true), ptr(loss_out)
+    blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    check(load().mobody_actor_backward(C.byref(blk), cur_stream()), "mobody_actor_backward")
 
 
 def value_loss_grad(qt, v, n_global):
@@ -308,12 +324,24 @@ def value_loss_grad(qt, v, n_global):
     return dz3, loss
 
 
+def _adam(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, t, t_dev, lr, tau, grad_scale, target_T, precision):
+    blk = _lib.MobodyAdam(struct_bytes=_BYTES[_lib.MobodyAdam], in_dim=in_dim, out_dim=out_dim, members=members, blob=ptr(blob),
+                          blob_T=ptr(blob_T), grad=ptr(grad), m=ptr(m), v=ptr(v), target=ptr(target), target_T=ptr(target_T),
+                          t=t, t_dev=ptr(t_dev), lr=float(lr), tau=float(tau), grad_scale=float(grad_scale),
+                          precision=prec_id(precision))
+    check(load().mobody_adam_polyak(C.byref(blk), cur_stream()), "mobody_adam_polyak")
+
+
 def adam_polyak(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, t, lr, tau=-1.0, grad_scale=1.0, target_T=None,
                 precision=0):
-    check(load().mobody_adam_polyak(in_dim, out_dim, members, ptr(blob), ptr(blob_T), ptr(grad), ptr(m), ptr(v),
-                                    ptr(target), ptr(target_T), int(t), float(lr), float(tau), float(grad_scale),
-                                    prec_id(precision), cur_stream()),
-          "mobody_adam_polyak")
+    _adam(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, int(t), None, lr, tau, grad_scale, target_T, precision)
+
+
+def adam_polyak_dev(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, t_dev, lr, tau=-1.0, grad_scale=1.0,
+                    target_T=None, precision=0):
+    """adam_polyak with the step count read from the device word t_dev (graph replay)."""
+    assert t_dev is not None, "adam_polyak_dev: t_dev is None"
+    _adam(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, 0, t_dev, lr, tau, grad_scale, target_T, precision)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -425,13 +453,6 @@ def par_penalty(next_state_true, next_state_model, reward, coef):
                                     cur_stream()), "mobody_par_penalty")
 
 
-def adam_polyak_dev(in_dim, out_dim, members, blob, blob_T, grad, m, v, target, t_dev, lr, tau=-1.0, grad_scale=1.0,
-                    target_T=None, precision=0):
-    check(load().mobody_adam_polyak_dev(in_dim, out_dim, members, ptr(blob), ptr(blob_T), ptr(grad), ptr(m), ptr(v),
-                                        ptr(target), ptr(target_T), ptr(t_dev), float(lr), float(tau), float(grad_scale),
-                                        prec_id(precision), cur_stream()), "mobody_adam_polyak_dev")
-
-
 def _gather_rng_args(buffers, counts, seeds, call_offsets, counter, sizes, bump=()):
     """MobodyGatherRng of gather_batch_rng's arguments, and the host arrays it points into (keep them until the call returns)."""
     n = len(buffers)
@@ -541,20 +562,31 @@ def pretrain_gather(state, action, next_state, reward, idx, start, b, out=None, 
     return xenc, act, rew
 
 
+def _pretrain_block(cls, S, A, b, b_global, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, loss_out, ws, seed, call,
+                    precision):
+    """MobodyPretrain / MobodyPretrainMopo: what the two models and the gradient and fused forms share."""
+    return cls(struct_bytes=_BYTES[cls], S=S, A=A, b=b, b_global=b_global, use_trg=int(bool(use_trg)),
+               encoder_loss_coef=float(encoder_loss_coef), blob=ptr(blob), blob_T=ptr(blob_T), xenc=ptr(xenc), act=ptr(act),
+               rew=ptr(rew), loss_out=ptr(loss_out), workspace=ptr(ws), seed=seed, call=call, precision=prec_id(precision))
+
+
 def pretrain_grads(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, grad, loss_out, ws, noise6=None,
                    noise7=None, seed=0, call=0, b_global=None, precision=0, transition_coef=1.0, reward_coef=1.0):
-    check(load().mobody_pretrain_grads(S, A, b, b if b_global is None else b_global, int(bool(use_trg)),
-                                       float(encoder_loss_coef), ptr(blob), ptr(blob_T), ptr(xenc), ptr(act), ptr(rew),
-                                       ptr(noise6), ptr(noise7), seed, call, ptr(grad), ptr(loss_out), ptr(ws),
-                                       prec_id(precision), float(transition_coef), float(reward_coef), cur_stream()), "mobody_pretrain_grads")
+    blk = _pretrain_block(_lib.MobodyPretrain, S, A, b, b if b_global is None else b_global, use_trg, encoder_loss_coef, blob,
+                          blob_T, xenc, act, rew, loss_out, ws, seed, call, precision)
+    blk.noise6, blk.noise7, blk.grad = ptr(noise6), ptr(noise7), ptr(grad)
+    blk.transition_coef, blk.reward_coef = float(transition_coef), float(reward_coef)
+    check(load().mobody_pretrain(C.byref(blk), cur_stream()), "mobody_pretrain")
 
 
 def pretrain_update(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, m, v, t_main, t_za, lr, loss_out, ws,
                     noise6=None, noise7=None, seed=0, call=0, call_dev=None, t_dev=None, precision=0, loss_acc=None):
-    check(load().mobody_pretrain_update(S, A, b, int(bool(use_trg)), float(encoder_loss_coef), ptr(blob), ptr(blob_T), ptr(xenc),
-                                        ptr(act), ptr(rew), ptr(noise6), ptr(noise7), seed, call, ptr(call_dev), ptr(m), ptr(v),
-                                        t_main, t_za, ptr(t_dev), float(lr), ptr(loss_out), ptr(loss_acc), ptr(ws), prec_id(precision), cur_stream()),
-          "mobody_pretrain_update")
+    blk = _pretrain_block(_lib.MobodyPretrain, S, A, b, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, loss_out, ws,
+                          seed, call, precision)
+    blk.noise6, blk.noise7, blk.transition_coef, blk.reward_coef = ptr(noise6), ptr(noise7), 1.0, 1.0
+    blk.m, blk.v, blk.t_main, blk.t_za, blk.t_dev, blk.lr = ptr(m), ptr(v), t_main, t_za, ptr(t_dev), float(lr)
+    blk.call_dev, blk.loss_acc = ptr(call_dev), ptr(loss_acc)
+    check(load().mobody_pretrain(C.byref(blk), cur_stream()), "mobody_pretrain")
 
 
 def pretrain_adam(S, A, use_trg, blob, blob_T, grad, m, v, t_main, t_za, lr, grad_scale=1.0, precision=0, net_mask=7, t_rw=None):
@@ -592,18 +624,19 @@ def pretrain_mopo_workspace(S, A, b, device):
 def pretrain_mopo_grads(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, grad, loss_out, ws, noise=None,
                         seed=0, call=0, b_global=None, precision=0):
     """noise: [7, b, S] fake-next-state draw (None: device Philox at (seed, call))."""
-    check(load().mobody_pretrain_mopo_grads(S, A, b, b if b_global is None else b_global, int(bool(use_trg)),
-                                            float(encoder_loss_coef), ptr(blob), ptr(blob_T), ptr(xenc), ptr(act), ptr(rew),
-                                            ptr(noise), seed, call, ptr(grad), ptr(loss_out), ptr(ws), prec_id(precision),
-                                            cur_stream()), "mobody_pretrain_mopo_grads")
+    blk = _pretrain_block(_lib.MobodyPretrainMopo, S, A, b, b if b_global is None else b_global, use_trg, encoder_loss_coef, blob,
+                          blob_T, xenc, act, rew, loss_out, ws, seed, call, precision)
+    blk.noise, blk.grad = ptr(noise), ptr(grad)
+    check(load().mobody_pretrain_mopo(C.byref(blk), cur_stream()), "mobody_pretrain_mopo")
 
 
 def pretrain_mopo_update(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, m, v, t, lr, loss_out, ws,
                          noise=None, seed=0, call=0, call_dev=None, t_dev=None, precision=0, loss_acc=None):
-    check(load().mobody_pretrain_mopo_update(S, A, b, int(bool(use_trg)), float(encoder_loss_coef), ptr(blob), ptr(blob_T),
-                                             ptr(xenc), ptr(act), ptr(rew), ptr(noise), seed, call, ptr(call_dev), ptr(m),
-                                             ptr(v), t, ptr(t_dev), float(lr), ptr(loss_out), ptr(loss_acc), ptr(ws),
-                                             prec_id(precision), cur_stream()), "mobody_pretrain_mopo_update")
+    blk = _pretrain_block(_lib.MobodyPretrainMopo, S, A, b, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, loss_out,
+                          ws, seed, call, precision)
+    blk.noise, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(noise), ptr(m), ptr(v), t, ptr(t_dev), float(lr)
+    blk.call_dev, blk.loss_acc = ptr(call_dev), ptr(loss_acc)
+    check(load().mobody_pretrain_mopo(C.byref(blk), cur_stream()), "mobody_pretrain_mopo")
 
 
 def pretrain_mopo_adam(S, A, blob, blob_T, grad, m, v, t, lr, grad_scale=1.0, precision=0):

@@ -1,4 +1,4 @@
-"""The minibatch gather inside the critic's first forward launch (mobody_critic_update_gather, config['fused_gather']).
+"""The minibatch gather inside the critic's first forward launch (MobodyCritic.gather, config['fused_gather']).
 
 Everything here is bit-for-bit against the unfused path of the same build -- mobody_gather_batch_rng followed by
 mobody_critic_update: the two perform the same draws, the same loads and the same arithmetic, so there is no tolerance."""
@@ -161,7 +161,8 @@ class _Recorder:
 
     def __getattr__(self, name):
         def fn(*args):
-            self.calls.append(name)
+            gathers = name == "mobody_critic" and bool(args[0]._obj.gather)      # args[0]: byref(MobodyCritic)
+            self.calls.append(name + ("+gather" if gathers else ""))
             return 0
         return fn
 
@@ -199,10 +200,10 @@ def _mock_step(monkeypatch, **over):
 
 
 def test_fused_step_takes_the_gathering_entry(monkeypatch):
-    assert _mock_step(monkeypatch) == ["mobody_critic_update_gather"]
+    assert _mock_step(monkeypatch) == ["mobody_critic+gather"]
 
 
 @pytest.mark.parametrize("over", [dict(penalty_type="par"), dict(advantage=1), dict(penalty_type="dara"), dict(fused_gather=0)],
                          ids=["par", "advantage", "dara", "off"])
 def test_fused_step_falls_back_to_two_calls(monkeypatch, over):
-    assert _mock_step(monkeypatch, **over) == ["mobody_gather_batch_rng", "mobody_critic_update"]
+    assert _mock_step(monkeypatch, **over) == ["mobody_gather_batch_rng", "mobody_critic"]

@@ -1,6 +1,6 @@
 """Dynamics pre-training throughput on the GPU box: optimizer steps per second of
 MOBODYEnsembleDynamics.learn at the reference's batch size (256 rows per member, 7 members), walker2d shapes by default,
-through the mirror (`_learn_indexed`: bootstrap gather + mobody_pretrain_grads + mobody_pretrain_adam), next to the CPU
+through the mirror (`_learn_indexed`: bootstrap gather + mobody_pretrain (gradient form) + mobody_pretrain_adam), next to the CPU
 oracle (`oracle.dyn_learn_step`, torch CPU fp32 autograd).  One JSON line.
 
 FLOPs per step (useful): per member and row, forward MACs of the three big nets are enc 2x, dec 4x, reward 2x

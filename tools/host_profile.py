@@ -5,7 +5,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "
 import torch
 import bench
 dev = torch.device("cuda:0")
-pol, src, tar, cfg = bench.build(dev, 0, 128, 0)
+pol, src, tar, cfg = bench.build(dev, dict(bench.CONFIGS["c2"], bs=128), 0, "f16x2")      # c2 shapes, batch 128, eager
 for _ in range(20):
     pol.train(src, tar, 128, None, None)
 torch.cuda.synchronize()

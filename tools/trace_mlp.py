@@ -1,7 +1,7 @@
 """Phase timeline of the fused MLP kernels' workgroups (diagnostic).  Needs a trace build of the library:
     MOBODY_TRACE=1 python mobody_amd/csrc/build.py --force      (rebuild without the variable afterwards)
     python tools/trace_mlp.py fwd|critic|actor [ROWS]
-fwd: twin-Q forward (2 members); critic: mobody_critic_step (the trace left behind is its backward);
+fwd: twin-Q forward (2 members); critic: mobody_critic, gradient form (the trace left behind is its backward);
 actor: mobody_actor_forward + mobody_actor_backward (workgroups >= tiles: frozen-Q dX backward, < tiles: actor backward)."""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
