@@ -413,8 +413,15 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
 // Block -> work mapping is XCD aware (blocks b and b+8 share an XCD and its L2): every (row slice, member) lives on one
 // XCD, so its activations are fetched from HBM/Infinity Cache once and re-read by its output tiles from that XCD's L2.
 // Along the block index the output TILE varies slowest: the tiles of the heavy 256 x 256 job are dispatched first, all
-// their slices side by side (the tiles resident on an XCD at one time share its few slices' activations), and the cheap
-// narrow jobs fill the one-and-a-half-generation launch's tail.  Which block computes what changes no slab value.
+// their slices side by side (the tiles resident on an XCD at one time share its few slices' activations), the narrow
+// jobs last.  k_wgrad_f16 holds 153 registers, three waves a SIMD: all 768 workgroups of a train-step launch are resident at
+// once, three per CU.  Which block computes what changes no slab value; what every form has to keep is the ORDER (tests/
+// wgrad_order_ref.py): wave (slice, w) runs one fp32 fma chain per element over its rows in increasing order, the four waves
+// of a slice meet as (w0 + w2) + (w1 + w3), k_grad_reduce adds the slabs in slab order.
+// The narrow jobs are 14 % of the FLOPs and cost 4.5 us of a 17.4 us launch, but not through the matrix pipe: 32 x 32
+// tiles (half the chain per wave), 16-row blocks (half the round trips) and a rank-1 fma form of a one-output net's dW3 (no
+// MFMA at all) each kept every bit and each measured SLOWER -- the launch moves ~11 TB/s from L2 and whatever makes the narrow
+// waves ask for more, or sooner, takes it from the 256 x 256 tiles.
 // ------------------------------------------------------------------------------------------------
 // Buffer descriptor over `nrows` rows of a row-major fp32 matrix (pitch ld floats) starting at the wave-uniform pointer p, and a
 // dword load through it: the per-lane byte offset rides in voffset, the wave-uniform row offset in soffset (a scalar register).
@@ -753,8 +760,17 @@ __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradAr
   wgrad_store<MT, NT>(jb, a, acc, k0, n0, slice, m, red);
 }
 
+// The Adam bias corrections of a device step count for the k_grad_reduce launch behind this one: one thread of the LAST
+// workgroup (a narrow tile, done long before the 256 x 256 tiles), so that no workgroup of k_grad_reduce opens with a load, two
+// double pow() and a barrier in front of its slab loads.  The step word is final before this launch (the step's first launch
+// advances it).
+__device__ __forceinline__ void wgrad_bias_corrections(const WgradArgs& a) {
+  if (a.bc_out != nullptr && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) adam_dev_consts(a.bc_t, a.bc_lr, a.bc_out);
+}
+
 __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_f16(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
+  wgrad_bias_corrections(a);
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
   const int groups = (a.nsplit * a.members + 7) / 8;
   const int t = j / groups;
@@ -769,6 +785,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_f16(WgradArgs a) {
 template <int NPL>
 __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_bf(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
+  wgrad_bias_corrections(a);
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
   const int groups = (a.nsplit * a.members + 7) / 8;
   const int t = j / groups;
@@ -783,6 +800,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_bf(WgradArgs a) {
 __global__ __launch_bounds__(NTHREADS, 4) void k_wgrad(WgradArgs a) {
   extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
   // XCD-aware decode: blocks with equal (id % 8) share an XCD; the output tile varies slowest (block comment above)
+  wgrad_bias_corrections(a);
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
   const int groups = (a.nsplit * a.members + 7) / 8;
   const int t = j / groups;
@@ -857,7 +875,13 @@ int launch_wgrad(WgradArgs a, hipStream_t st) {
 // L2 reads per thread made the first version of this kernel latency bound: 41 us instead of ~5).
 __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
   __shared__ float adam_sm[2];
-  adam_block_consts(a.adam, adam_sm);
+  // bias corrections of a device step count: a uniform load of what the weight-gradient launch left (no pow, no barrier, no
+  // LDS in front of the slab loads), else formed once per workgroup
+  const float* bc = a.bc_dev;
+  float c0 = 0.f, c1 = 0.f;
+  if (bc != nullptr) { c0 = bc[0]; c1 = bc[1]; }
+  else if (a.adam.on && a.adam.t_dev != nullptr) { adam_block_consts(a.adam, adam_sm); c0 = adam_sm[0]; c1 = adam_sm[1]; }
+  const float adam_c[2] = {c0, c1};
   const int hmask = health_mask(a.adam);                         // an earlier fault: the gradient and the loss are still written
   const long long nW = a.L.total_floats;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -878,7 +902,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
     }
     for (; k < a.nsplit; ++k) s += a.slabs[(long long)k * a.slab_stride + j];
     if (a.grad != nullptr) a.grad[j] = s;
-    if (a.adam.on) adam_element(a.adam, a.L, j, s, adam_sm, hmask);
+    if (a.adam.on) adam_element(a.adam, a.L, j, s, adam_c, hmask);
     return;
   }
   // ---- bias part: wave index -> (member, bias element) ----
@@ -918,7 +942,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
   if (lane == 0) {
     const long long dst = (long long)m * a.L.member_floats + (off < HID ? a.L.b1 + off : off < 2 * HID ? a.L.b2 + (off - HID) : a.L.b3 + (off - 2 * HID));
     if (a.grad != nullptr) a.grad[dst] = s;
-    if (a.adam.on) adam_element(a.adam, a.L, dst, s, adam_sm, hmask);
+    if (a.adam.on) adam_element(a.adam, a.L, dst, s, adam_c, hmask);
   }
 }
 
@@ -927,7 +951,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
 int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstride, const float* h1, const float* h2,
                       const float* dz3, const float* dz2, const float* dz1, long long rows, int nsplit, float* slabs,
                       const float* dbp, int ntiles, float* grad, const LossFinal& loss, const AdamTarget& adam,
-                      hipStream_t st, int prec, const int* e_h1, const int* e_dz2) {
+                      hipStream_t st, int prec, const int* e_h1, const int* e_dz2, float* bc_ws) {
   WgradArgs g{};
   g.prec = prec;
   const long long rows32 = (rows + 31) & ~31LL;
@@ -943,9 +967,13 @@ int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstr
   g.job[1] = WgradJob{x, x_mstride, L.Kp1, L.Kp1, dz1, hs, HID, HID, L.w1, HID, L.Kp1, HID, 0, 1, 0, 0};
   // dW3^T = dz3^T h2, stored transposed into W3[256][Np3]
   g.job[2] = WgradJob{dz3, rows * L.Np3, L.Np3, L.Np3, h2, hs, HID, HID, L.w3, L.Np3, L.Np3, HID, 1, 0, 0, 0};
+  GradReduceArgs r{L, slabs, slab_stride, nsplit, dbp, ntiles, grad, loss, adam, nullptr};
+  if (bc_ws != nullptr && adam.on && adam.t_dev != nullptr) {
+    g.bc_out = bc_ws; g.bc_t = adam.t_dev; g.bc_lr = adam.lr;
+    r.bc_dev = bc_ws;
+  }
   int rc = launch_wgrad(g, st);
   if (rc) return rc;
-  GradReduceArgs r{L, slabs, slab_stride, nsplit, dbp, ntiles, grad, loss, adam};
   return launch_grad_reduce(r, st);
 }
 

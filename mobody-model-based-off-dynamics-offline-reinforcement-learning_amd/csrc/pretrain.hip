@@ -575,6 +575,7 @@ struct PreWs {
   // backward operands of the three nets (0 reward head, 1 decoder, 2 state encoder): one set EACH, because the weight-gradient
   // GEMM + reduction of nets 0 and 1 run on the side stream while the main stream's backward chain moves on to the next net
   float *dz2[3], *dz1[3], *dbp[3], *slabs[3];
+  float* bc;                                    // Adam bias corrections of a device step count, two floats per net (mlp3_weight_grads)
   int *eh1e, *eh1t, *eh1r, *edz2[3];   // f16x2: scale exponents of the 32-row tiles of the h1 / dz2 planes (h1*, dz2 then hold planes)
   PreLossOff lo;
   int nch, nsplit2, nsplit4, ntiles2, ntiles4;
@@ -614,6 +615,7 @@ static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, Pr
   w.lo.n_lat = (int)(E * w.nch); w.lo.n_rt = (int)cdiv(E * b * S, 256); w.lo.n_rw = (int)cdiv(E * R2, 256);
   w.lo.lat = 0; w.lo.rt = 2LL * w.lo.n_lat; w.lo.rw = w.lo.rt + 2LL * w.lo.n_rt;
   w.lossp = take(w.lo.rw + w.lo.n_rw);
+  w.bc = take(8);
   w.total = off;
   return 0;
 }
@@ -824,7 +826,7 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
     if (rc) return rc;
     rc = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0], w.dbp[0],
                            w.ntiles2, gptr(L.off_rw), LossFinal{}, region_adam(L.off_rw, L.t_off_rw), st2, precision,
-                           f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr);
+                           f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr, w.bc);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_pre_fake_bwd, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
@@ -838,7 +840,7 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
     if (rc) return rc;
     rc = mlp3_weight_grads(L.tr, w.zt, R4 * LATENT, w.h1t, w.h2t, w.dz3tr, w.dz2[1], w.dz1[1], R4, w.nsplit4, w.slabs[1], w.dbp[1],
                            w.ntiles4, gptr(L.off_tr), LossFinal{}, region_adam(L.off_tr, L.t_off_tr), st2, precision,
-                           f16 ? w.eh1t : nullptr, f16 ? w.edz2[1] : nullptr);
+                           f16 ? w.eh1t : nullptr, f16 ? w.edz2[1] : nullptr, w.bc + 2);
     if (rc) return rc;
   }
   // ---- latent level + action encoder ----
@@ -861,7 +863,7 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
     if (rc) return rc;
     rc = mlp3_weight_grads(L.enc, w.sx_enc, R2 * L.enc.Kp1, w.h1e, w.h2e, w.dz3enc, w.dz2[2], w.dz1[2], R2, w.nsplit2, w.slabs[2], w.dbp[2],
                            w.ntiles2, gptr(L.off_enc), LossFinal{}, region_adam(L.off_enc, L.t_off_enc), st, precision,
-                           f16 ? w.eh1e : nullptr, f16 ? w.edz2[2] : nullptr);
+                           f16 ? w.eh1e : nullptr, f16 ? w.edz2[2] : nullptr, w.bc + 4);
     if (rc) return rc;
   }
   // the step ends when both streams have: the main one waits for the side one
@@ -1107,6 +1109,7 @@ struct MopoWs {
   float *xrw, *sx_rw, *h1r, *h2r, *d1r, *d2r, *rw_out;
   float *dz3rw, *dz3d, *dfake, *fnz, *lossp;
   float *dz2[2], *dz1[2], *dbp[2], *slabs[2];   // 0 reward head (2b rows), 1 MLP (b rows)
+  float* bc;                                    // Adam bias corrections of a device step count, two floats per net (mlp3_weight_grads)
   int *eh1d, *eh1r, *edz2[2];
   PreLossOff lo;
   int nsplit1, nsplit2, ntiles1, ntiles2;
@@ -1140,6 +1143,7 @@ static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* bas
   w.lo.n_rt = (int)cdiv(E * R1 * S, 256); w.lo.n_rw = (int)cdiv(E * R2, 256);
   w.lo.rt = 0; w.lo.rw = 2LL * w.lo.n_rt;
   w.lossp = take(w.lo.rw + w.lo.n_rw);
+  w.bc = take(8);
   w.total = off;
   return 0;
 }
@@ -1251,7 +1255,7 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
   auto after_fork = [&]() -> int {
     int rc2 = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0],
                                 w.dbp[0], w.ntiles2, gptr(L.off_rw), LossFinal{}, region_adam(L.off_rw, L.t_off_rw), st2, precision,
-                                f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr);
+                                f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr, w.bc);
     if (rc2) return rc2;
     hipLaunchKernelGGL(k_mopo_dmu, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
     MB_LAUNCH_OK("k_mopo_dmu");
@@ -1260,7 +1264,7 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
     if (rc2) return rc2;
     return mlp3_weight_grads(L.dyn, w.sx_d, b * L.dyn.Kp1, w.h1d, w.h2d, w.dz3d, w.dz2[1], w.dz1[1], b, w.nsplit1, w.slabs[1],
                              w.dbp[1], w.ntiles1, gptr(L.off_dyn), LossFinal{}, region_adam(L.off_dyn, L.t_off_dyn), st, precision,
-                             f16 ? w.eh1d : nullptr, f16 ? w.edz2[1] : nullptr);
+                             f16 ? w.eh1d : nullptr, f16 ? w.edz2[1] : nullptr, w.bc + 2);
   };
   rc = after_fork();
   if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)

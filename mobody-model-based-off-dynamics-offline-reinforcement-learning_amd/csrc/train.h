@@ -124,6 +124,9 @@ struct WgradArgs {
   long long rows, rows_per_wave;
   float* slabs; long long slab_stride, out_mstride;    // partial slab s = slabs + s*slab_stride (gradient-blob layout)
   int nsplit, members, tiles_total;
+  // bc_out != null: the launch's last workgroup forms the Adam bias corrections of the device step count bc_t[0] at learning
+  // rate bc_lr (adam_block_consts' expressions) for the k_grad_reduce launch that follows it on the stream
+  float* bc_out; const long long* bc_t; float bc_lr;
   int prec;                                            // precision id (common.h): f32 exact; bf16 modes: the 256 x 256 job on the
                                                        // split-precision core; f16x2 with eA: job 0 on the saved fp16 planes
 };
@@ -220,6 +223,12 @@ __device__ __forceinline__ void health_after_update(const AdamTarget& a, float p
 // Bias corrections of a device-side step count (graph replay), formed ONCE per workgroup in double: thread 0 computes,
 // everybody reads after the barrier.  (Every thread evaluating two double pow() per element made the fused
 // reduce+Adam kernel 3x slower: 5.5 -> 17 us on the 0.5 M-parameter ensemble nets.)  Call before any early return.
+// The same two values by one thread, for a launch that runs after this one (WgradArgs::bc_out).
+__device__ __forceinline__ void adam_dev_consts(const long long* t_dev, float lr, float* out) {
+  const double t = (double)t_dev[0];
+  out[0] = (float)((double)lr / (1.0 - pow(0.9, t)));
+  out[1] = (float)sqrt(1.0 - pow(0.999, t));
+}
 __device__ __forceinline__ void adam_block_consts(const AdamTarget& a, float* sm2) {
   if (a.on && a.t_dev != nullptr) {
     if (threadIdx.x == 0) {
@@ -303,13 +312,16 @@ struct GradReduceArgs {
   float* grad;          // may be null when `adam.on` (nobody reads the gradient blob on one GPU)
   LossFinal loss;       // kind 0: none
   AdamTarget adam;      // on = 0: none
+  const float* bc_dev;  // {step_size, bc2_sqrt} of adam.t_dev[0], formed by the weight-gradient launch in front, or null
 };
 int launch_grad_reduce(const GradReduceArgs& a, hipStream_t st);
 // prec 4: h1 / dz2 point at the saved fp16 planes and e_h1 / e_dz2 at their tile exponents (else null)
+// bc_ws: two floats of workspace (or null).  With a fused optimizer step on a device step count, the weight-gradient launch
+// leaves the bias corrections there and k_grad_reduce takes them as a uniform load instead of forming them behind a barrier.
 int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstride, const float* h1, const float* h2,
                       const float* dz3, const float* dz2, const float* dz1, long long rows, int nsplit, float* slabs,
                       const float* dbp, int ntiles, float* grad, const LossFinal& loss, const AdamTarget& adam,
-                      hipStream_t st, int prec = 0, const int* e_h1 = nullptr, const int* e_dz2 = nullptr);
+                      hipStream_t st, int prec = 0, const int* e_h1 = nullptr, const int* e_dz2 = nullptr, float* bc_ws = nullptr);
 
 // split-K factor (workgroups along the row dimension) used for a batch of `rows`: 24 output tiles x nsplit x members
 // workgroups should reach ~3 per CU (768), so a one-member net splits twice as fine as a twin net

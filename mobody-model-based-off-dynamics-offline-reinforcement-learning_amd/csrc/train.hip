@@ -21,6 +21,7 @@ struct TrainWs {
   int *eh1q, *eh1a, *edz2;              // f16 mode: scale exponents of the 32-row tiles of the h1 / dz2 planes
   float *pin;            // pi(s') of the critic phase (pi holds pi(s) for the actor phase)
   float *pi, *qt, *q, *qb, *xq, *h1q, *h2q, *xa, *h1a, *h2a, *dz3q, *dz2, *dz1, *dz3a, *dxa, *bcw, *dbp, *slabs, *lossp;
+  float *bc;               // Adam bias corrections of a device step count: two floats per net (critic, actor), mlp3_weight_grads
   long long total;
   int nsplit_q, nsplit_a, ntiles;
   MobodyMlpLayout Lq, La;
@@ -66,6 +67,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
     const long long sq = ((w.Lq.total_floats + 3) & ~3LL) * w.nsplit_q, sa = ((w.La.total_floats + 3) & ~3LL) * w.nsplit_a;
     w.slabs = take(sq > sa ? sq : sa);
   }
+  w.bc = take(4);
   w.total = off;
   return 0;
 }
@@ -222,7 +224,8 @@ static int weight_grads(const MobodyMlpLayout& L, const float* x, const float* h
                         const float* dz2, const float* dz1, long long rows, const TrainWs& w, float* grad,
                         const LossFinal& loss, const AdamTarget& adam, hipStream_t st, int prec = 0, const int* e_h1 = nullptr) {
   return mlp3_weight_grads(L, x, 0, h1, h2, dz3, dz2, dz1, rows, L.members == 1 ? w.nsplit_a : w.nsplit_q, w.slabs, w.dbp,
-                           w.ntiles, grad, loss, adam, st, prec, prec == PREC_F16X2 ? e_h1 : nullptr, prec == PREC_F16X2 ? w.edz2 : nullptr);
+                           w.ntiles, grad, loss, adam, st, prec, prec == PREC_F16X2 ? e_h1 : nullptr, prec == PREC_F16X2 ? w.edz2 : nullptr,
+                           w.bc + (L.members == 1 ? 2 : 0));
 }
 
 // the train step's ReLU nets: always the W2^T planes and `prec`; e2 != null in the f16 mode: dz2 receives fp16 planes + tile
