@@ -96,6 +96,7 @@ inline MlpView mlp_view(const float* blob, const MobodyMlpLayout& L) {
 
 // Phase timeline of the fused MLP kernels (diagnostic builds only: MOBODY_TRACE=1 python build.py --force).
 // TR(k) stores the 100 MHz wall clock of workgroup (blockIdx.y, blockIdx.x) at phase k; tools/trace_mlp.py reads it.
+// (k_actor_bwd_chain runs two tiles in a continuing workgroup: the actor tile's stamps overwrite the dX tile's in its slots.)
 #ifdef MOBODY_TRACE
 constexpr int TRACE_BLOCKS = 16384, TRACE_SLOTS = 8;
 extern __device__ unsigned long long g_trace[TRACE_BLOCKS * TRACE_SLOTS];

@@ -6,6 +6,8 @@
 //                partial sums of the tile.  Masks come from the forward's sign words (or the saved activations);
 //                W^T blobs are streamed as MFMA B operands exactly like the forward weights.
 //                                                                    (autograd of mobody.py:35-48)
+//   k_actor_bwd_chain  the actor update's two passes in one launch: a frozen-Q dX tile, then -- in the second of the tile's two
+//                member workgroups to finish -- the actor's tile of the same rows (ticket per row tile, no waiting)
 //   k_wgrad      dW[k][n] = sum_rows A[row][k] * dZ[row][n]: rows are the contraction index, both
 //                operands are read straight from global memory in MFMA fragment order (a wave
 //                instruction = two full 128-byte lines); split-K over row slices, the four waves of a
@@ -148,9 +150,15 @@ __device__ __forceinline__ void wide_store_colsum(f32x16 (&acc)[MT][2], float* X
 
 // Seed prologue (BwdSeed modes 1-3).  Modes 1 and 2 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) --
 // the kernel forms the rank-1 product dz3 W3^T from them; mode 3 fills Xs[r][0..Np3).  All global loads of a pass are
-// independent (one round trip); the loss partials are reduced through `red` (static LDS, 8 floats).
-__device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float* red, int m, long long row0, int rows_here,
-                                         int TB) {
+// independent (one round trip); the loss partials are reduced through `red` (static LDS, 8 floats).  `tile` is the row tile
+// (row0 / TB).  CHAIN: the tile runs inside k_actor_bwd_chain, where mode 2's bcw (and dx) are handed to the mode-3 tile of the
+// same rows within the launch: mode 2 stores them write-through (agent scope), mode 3 loads them at agent scope -- past its
+// CU's L1 -- and a row's loads stay on words its own tile has published.
+__device__ __forceinline__ void agent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float agent_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <bool CHAIN = false>
+__device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float* red, int m, int tile, long long row0,
+                                         int rows_here, int TB) {
   const BwdSeed& sd = a.seed;
   const int Np3 = a.Np3;
   const int t = threadIdx.x;
@@ -172,7 +180,10 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
         const float c = -policy_weight(r) / (float)r.Ng;
         const float g0 = q0 < q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
         v = ok ? c * (m == 0 ? g0 : 1.f - g0) : 0.f;
-        if (m == 0 && ok && row < r.Nt) r.bcw[row] = bc_weight(r, row);
+        if (m == 0 && ok && row < r.Nt) {
+          if constexpr (CHAIN) agent_store(r.bcw + row, bc_weight(r, row));
+          else r.bcw[row] = bc_weight(r, row);
+        }
       }
       Xs[t] = v;
       if (sd.dz3_out != nullptr && ok) {
@@ -184,6 +195,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   } else {                                          // mode 3: one thread per (row, column)
     const ActorRowArgs& r = sd.ar;
     const float wscale = r.h.bc_coef * 2.f / ((float)r.Ntg * (float)r.A);
+    if constexpr (!CHAIN) {
     for (int e = t; e < TB * Np3; e += NTHREADS) {
       const int rr = e / Np3, j = e - rr * Np3;
       const bool ok = rr < rows_here && j < r.A;
@@ -205,6 +217,51 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
       Xs[rr * LDX + j] = v;
       if (rr < rows_here) sd.dz3_out[(row0 + rr) * Np3 + j] = v;
     }
+    } else {
+    // The agent-scope loads of dxa / bcw pass L1, so a thread requests the operands of ALL its elements (SEED_U passes of the loop
+    // above: Np3 = 32 has four) before it uses the first: one round trip per tile, not one per pass.  The elements are then formed
+    // in the same order by the same expressions.
+    constexpr int SEED_U = 4;
+    for (int e0 = t; e0 < TB * Np3; e0 += SEED_U * NTHREADS) {
+      float pv[SEED_U], d0v[SEED_U], d1v[SEED_U], av[SEED_U], wv[SEED_U], qv[SEED_U][2];
+#pragma unroll
+      for (int u = 0; u < SEED_U; ++u) {
+        const int e = min(e0 + u * NTHREADS, TB * Np3 - 1);
+        const int rr = e / Np3, j = e - rr * Np3;
+        const long long row = row0 + (rr < rows_here ? rr : 0);
+        const int jc = j < r.A ? j : 0;
+        const float* dp = r.dxa + row * r.A + jc;
+        pv[u] = r.pi[row * r.A + jc]; av[u] = r.act[row * r.A + jc];
+        qv[u][0] = r.qp[row]; qv[u][1] = r.qp[r.N + row];
+        d0v[u] = agent_load(dp); d1v[u] = agent_load(dp + r.N * r.A);
+        // A non-BC row's weight is gated out below.  bcw[0] belongs to tile 0, which may not have run yet: such a row asks for its
+        // own dxa word again instead, so that no word is touched before its writer has published it.  (An unconditional load
+        // beside the others, same line as d0: a `bc ? load : 0` select branches around the load and waits for it.)
+        wv[u] = agent_load(row < r.Nt ? r.bcw + row : dp);
+      }
+#pragma unroll
+      for (int u = 0; u < SEED_U; ++u) {
+        const int e = e0 + u * NTHREADS;
+        if (e < TB * Np3) {
+          const int rr = e / Np3, j = e - rr * Np3;
+          const bool ok = rr < rows_here && j < r.A;
+          const long long row = row0 + (rr < rows_here ? rr : 0);
+          const bool bc = row < r.Nt;
+          const float p = pv[u], w = wv[u];
+          float v = 0.f;
+          if (ok) {
+            float d = d0v[u] + d1v[u];
+            if (bc) { const float df = p - av[u]; d += wscale * w * df; l1 += w * (df * df); }
+            const float th = p / r.h.max_action;
+            v = d * r.h.max_action * (1.f - th * th);                   // d tanh
+            if (j == 0) l0 = l0 - fminf(qv[u][0], qv[u][1]);
+          }
+          Xs[rr * LDX + j] = v;
+          if (rr < rows_here) sd.dz3_out[(row0 + rr) * Np3 + j] = v;
+        }
+      }
+    }
+    }
   }
   if (sd.mode == 2) return;
   // loss partials of this tile
@@ -215,8 +272,8 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   if (t == 0) {
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
-    if (sd.mode == 1) sd.lossp[blockIdx.x * 2 + m] = l0;
-    else { sd.lossp[2 * blockIdx.x] = l0; sd.lossp[2 * blockIdx.x + 1] = l1; }
+    if (sd.mode == 1) sd.lossp[tile * 2 + m] = l0;
+    else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
 }
 
@@ -224,18 +281,14 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
 // or 0 = any Np1t through the row-split path.
 // MASK: see wide_mask_apply (1: sign words m1, m2; 0: saved activations h1, h2; 2: Swish derivatives in h1, h2).
 // PM: 0 = exact fp32 MFMA; 1..4 = the 256 x 256 GEMM (dz2 W2^T) on the split-precision core, streaming W2^T's planes.
-template <bool DX, int NT, int MASK, int PM = 0>
-// (three workgroups per CU only for the sign-word variants: the variants that hold 32 mask / derivative values per lane next to
-//  the accumulators spilled ~26 VGPRs at the 168-register budget; they serve the small generic launches -- V function, DARA
-//  classifier, dynamics pre-training -- where a third resident workgroup buys nothing)
-__global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3BwdArgs a) {
+// The backward of one (32-row tile, member) of a launch of `members` members: Xs is the workgroup's dynamic LDS, red its eight
+// static floats.  CHAIN: see bwd_seed.
+template <bool DX, int NT, int MASK, int PM = 0, bool CHAIN = false>
+__device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int tile, int members, float* Xs, float* red) {
   constexpr bool BITS = MASK == 1;
-  __shared__ float red[8];
-  extern __shared__ __attribute__((aligned(16))) float Xs[];
   constexpr int TB = MLP_TILE_ROWS, MT = MLP_MT;
   constexpr int PMX = PM > 0 ? PM : 1;
-  const int m = blockIdx.y;
-  const long long row0 = (long long)blockIdx.x * TB;
+  const long long row0 = (long long)tile * TB;
   const int rows_here = (int)min((long long)TB, a.rows - row0);
   const int lane = lane_id(), w = wave_id();
   const float* w3t = a.wt + m * a.t_mstride + a.w3t;
@@ -248,7 +301,7 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
   const uint32_t* m2 = BITS ? a.m2 + mtile : nullptr;
   float* dz2 = a.dz2 ? a.dz2 + ((long long)m * a.rows + row0) * HID : nullptr;
   float* dz1 = a.dz1 ? a.dz1 + ((long long)m * a.rows + row0) * HID : nullptr;
-  float* dbp = a.dbp + ((long long)blockIdx.x * gridDim.y + m) * (2 * HID + a.Np3);
+  float* dbp = a.dbp + ((long long)tile * members + m) * (2 * HID + a.Np3);
   float* scr = reinterpret_cast<float*>(reinterpret_cast<char*>(Xs) + split_scr_offset<PMX, TB>());   // tile maximum (f16 mode)
 
   TR(0);
@@ -266,7 +319,7 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
   if (!rank1) wide_prefetch(w3t, a.Np3, ring);    // weight fragments travel while the seed rows are fetched
   if (mode == 0) tile_load(Xs, 0, a.dz3 + ((long long)m * a.rows + row0) * a.Np3, a.Np3, a.Np3, 0, rows_here, TB);
-  else bwd_seed(a, Xs, red, m, row0, rows_here, TB);
+  else bwd_seed<CHAIN>(a, Xs, red, m, tile, row0, rows_here, TB);
   lds_barrier();
   TR(1);
   if (with_db && (int)threadIdx.x < a.Np3) {      // db3 partial of this tile (rank-1: column 0 alone is non-zero)
@@ -333,12 +386,25 @@ __global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3Bw
     float* dx = a.dx + ((long long)m * a.rows + row0) * a.dx_n;
     auto emit = [&](int row, int col, float v) {
       const int c = col - a.dx_c0;
-      if (row < rows_here && c >= 0 && c < a.dx_n) dx[row * a.dx_n + c] = v;
+      if (row < rows_here && c >= 0 && c < a.dx_n) {
+        if constexpr (CHAIN) agent_store(dx + row * a.dx_n + c, v);
+        else dx[row * a.dx_n + c] = v;
+      }
     };
     if constexpr (NT > 0) narrow_run<TB / 16, NT>(Xs, br, emit);
     else narrow_layer(Xs, w1t, HID, a.Np1t, emit, TB);
   }
   TR(6);
+}
+
+template <bool DX, int NT, int MASK, int PM = 0>
+// (three workgroups per CU only for the sign-word variants: the variants that hold 32 mask / derivative values per lane next to
+//  the accumulators spilled ~26 VGPRs at the 168-register budget; they serve the small generic launches -- V function, DARA
+//  classifier, dynamics pre-training -- where a third resident workgroup buys nothing)
+__global__ __launch_bounds__(NTHREADS, MASK == 1 ? 3 : 2) void k_mlp3_bwd(Mlp3BwdArgs a) {
+  __shared__ float red[8];
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  mlp3_bwd_tile<DX, NT, MASK, PM>(a, blockIdx.y, blockIdx.x, gridDim.y, Xs, red);
 }
 
 template <bool DX, int NT, int BITS, int NPL = 0>
@@ -396,6 +462,89 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
          : a.prec == PREC_BF16X3 ? launch_bwd_bf<3>(a, members, with_dx, st) : launch_bwd_bf<4>(a, members, with_dx, st);
   return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_masks<1>(a, members, with_dx, st)
                                             : launch_bwd_masks<0>(a, members, with_dx, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The actor update's two backward passes in ONE launch: the frozen twin-Q input-gradient pass (seed mode 2, grid = row tiles x
+// 2 members, exactly the launch k_mlp3_bwd<true, NT, 1, PM> would be) and, chained onto it tile by tile, the actor's own backward
+// (seed mode 3).  An actor tile reads, for its 32 rows only, dxa of both members and bcw -- all written by the two member
+// workgroups of the same blockIdx.x -- so it can start the moment those two have finished: each workgroup publishes its rows at
+// device scope and draws a ticket for its tile; the second arriver runs the actor tile in the same workgroup, on the same LDS.
+// THERE IS NO WAIT LOOP: a workgroup that is not last exits, so nobody ever waits for another workgroup and the launch makes
+// progress under any dispatch order or residency.  The two passes use disjoint scratch (mode 2 writes dx and bcw only; dz2, dz1,
+// dz3a, dbp and lossp are mode 3's), so an actor tile running beside other tiles' dX workgroups conflicts with nothing.
+// Publication (correct wherever the three parties sit -- with an odd tile count a tile's members land on different XCDs): the
+// ~1 KB of dx / bcw leaves in write-through agent-scope stores -> every wave drains its vector-memory counter -> workgroup barrier ->
+// one lane's relaxed agent-scope fetch_add on tickets[tile]; the workgroup that draws 1 re-arms the ticket (a second backward on the
+// same forward finds 0 again; k_actor_stats zeroes the words in front of the first) and goes on, reading dxa / bcw -- every load
+// of them -- at agent scope, past its CU's L1.  (The fence form -- plain stores, an agent-scope release in all 640 workgroups,
+// an acquire in the 320 that go on -- is as correct and measured 10 us SLOWER per step than the two separate launches: each
+// release writes back its XCD's L2, which is full of the actor tiles' dz2 / dz1.)  "I am last" travels through
+// `red`, the one static LDS object the tile body has anyway.  Every fma and MFMA sequence per output element is the one of the two
+// separate launches: the results are the same bits.
+// ------------------------------------------------------------------------------------------------
+// PARAMETER ORDER: `q` first, `pi` directly behind it -- the body reads `pi` at offset sizeof(Mlp3BwdArgs) of the kernel-argument
+// segment (see there); a parameter put in front of `pi` moves it.
+template <int NT, int PM>
+__global__ __launch_bounds__(NTHREADS, 3) void k_actor_bwd_chain(Mlp3BwdArgs q, Mlp3BwdArgs pi, int* tickets) {
+  __shared__ float red[8];
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  const int tile = blockIdx.x;
+  mlp3_bwd_tile<true, NT, 1, PM, true>(q, blockIdx.y, tile, 2, Xs, red);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's write-through dx (and bcw) stores are done
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = __hip_atomic_fetch_add(tickets + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == 1) __hip_atomic_store(tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // both members have published
+    red[0] = __int_as_float(t);
+  }
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");         // (no instruction: the agent-scope loads below stay below the ticket)
+  const int ticket = __float_as_int(red[0]);
+  if (ticket != 1) return;                                       // (a word nobody zeroed never reads 1: the actor tile then does not run)
+  lds_barrier();                                                 // everybody has read red[0] before the seed's loss partials overwrite it
+  // `pi` is read through the kernel-argument segment behind an opaque copy of its address: read as the parameter, its fields
+  // (invariant loads) were hoisted into the frozen-Q tile and held there, up to 14 scalar registers spilled and a scratch frame
+  // in two instances.  Nothing of the first tile is live here but the tile index.
+  static_assert(sizeof(Mlp3BwdArgs) % 8 == 0 && alignof(Mlp3BwdArgs) == 8, "`pi` follows `q` in the kernel-argument segment");
+  using KernArg = const __attribute__((address_space(4))) Mlp3BwdArgs;
+  KernArg* ka = (KernArg*)__builtin_amdgcn_kernarg_segment_ptr() + 1;
+  asm volatile("" : "+s"(ka));
+  mlp3_bwd_tile<false, 0, 1, PM, true>(*(const Mlp3BwdArgs*)ka, 0, tile, 1, Xs, red);
+}
+
+template <int NT, int PM>
+static int launch_chain_t(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
+  constexpr size_t lds = split_lds_bytes<(PM > 0 ? PM : 1), MLP_TILE_ROWS>();
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_actor_bwd_chain<NT, PM>, lds);
+    if (rc) return rc;
+    once = true;
+  }
+  dim3 grid((unsigned)cdiv(q.rows, MLP_TILE_ROWS), 2u);
+  ProfScope prof(PROF_MLP_BWD, st);
+  hipLaunchKernelGGL((k_actor_bwd_chain<NT, PM>), grid, dim3(NTHREADS), lds, st, q, pi, tickets);
+  MB_LAUNCH_OK("k_actor_bwd_chain");
+  return 0;
+}
+template <int PM>
+static int launch_chain_nt(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
+  return q.Np1t == 16 ? launch_chain_t<1, PM>(q, pi, tickets, st) : q.Np1t == 32 ? launch_chain_t<2, PM>(q, pi, tickets, st)
+                                                                                   : launch_chain_t<0, PM>(q, pi, tickets, st);
+}
+
+// q: the frozen twin-Q pass (seed mode 2, dx out), pi: the actor's pass (seed mode 3) on the same rows; both with sign words and
+// the same precision.  tickets: one zeroed int per row tile.  The precision picks the instance as in launch_mlp3_bwd.
+int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
+  if (q.rows <= 0) return 0;
+  MB_REQUIRE(q.seed.mode == 2 && pi.seed.mode == 3 && q.rows == pi.rows && q.prec == pi.prec && tickets != nullptr &&
+             q.m1 && q.m2 && pi.m1 && pi.m2 && !q.swish && !pi.swish && (q.w2t_planes != nullptr) == (pi.w2t_planes != nullptr),
+             "launch_actor_bwd_chain: the two passes do not form an actor update");
+  if (q.prec != PREC_F32 && q.w2t_planes != nullptr)
+    return q.prec == PREC_BF16 ? launch_chain_nt<1>(q, pi, tickets, st) : q.prec == PREC_BF16X2 ? launch_chain_nt<2>(q, pi, tickets, st)
+         : q.prec == PREC_BF16X3 ? launch_chain_nt<3>(q, pi, tickets, st) : launch_chain_nt<4>(q, pi, tickets, st);
+  return launch_chain_nt<0>(q, pi, tickets, st);
 }
 
 // ------------------------------------------------------------------------------------------------

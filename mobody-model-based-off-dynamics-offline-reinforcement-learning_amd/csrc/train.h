@@ -77,6 +77,10 @@ struct Mlp3BwdArgs {
   int dx_c0, dx_n;
 };
 int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st);
+// the actor update's frozen-Q pass `q` (seed mode 2, 2 members, dx) and actor pass `pi` (seed mode 3) in one launch: the second of a
+// tile's two member workgroups to finish runs that tile's actor backward (mlp_bwd.hip k_actor_bwd_chain).  tickets: one int per
+// row tile, zero on entry and on exit.
+int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st);
 
 // ---- host side: the one place an Mlp3BwdArgs is filled; each helper owns one group of fields (the seed and dx are the caller's).
 // launch_mlp3_bwd picks its kernel from swish, prec + w2t_planes and m1 + m2, so every caller states those explicitly. ----

@@ -22,6 +22,7 @@ struct TrainWs {
   float *pin;            // pi(s') of the critic phase (pi holds pi(s) for the actor phase)
   float *pi, *qt, *q, *qb, *xq, *h1q, *h2q, *xa, *h1a, *h2a, *dz3q, *dz2, *dz1, *dz3a, *dxa, *bcw, *dbp, *slabs, *lossp;
   float *bc;               // Adam bias corrections of a device step count: two floats per net (critic, actor), mlp3_weight_grads
+  int *tickets;            // one per row tile: arrivals of the tile's two frozen-Q workgroups in k_actor_bwd_chain (zeroed by k_actor_stats)
   long long total;
   int nsplit_q, nsplit_a, ntiles;
   MobodyMlpLayout Lq, La;
@@ -68,6 +69,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
     w.slabs = take(sq > sa ? sq : sa);
   }
   w.bc = take(4);
+  w.tickets = (int*)take(w.ntiles);
   w.total = off;
   return 0;
 }
@@ -96,9 +98,11 @@ __device__ __forceinline__ float block_sum(float v, float* sm) {      // blockDi
 }
 
 // stats[0] = sum_rows |min(Q1,Q2)(s,pi(s))|, stats[1] = sum_{rows<Nt} |min(Q1,Q2)(s_t,a_t)|   (:318, :259)
+// Also zeroes the tile tickets of the backward launch that follows it in every caller (k_actor_bwd_chain).
 __global__ __launch_bounds__(1024) void k_actor_stats(const float* qp, const float* qb, long long N, long long Nt,
-                                                      float* stats) {
+                                                      float* stats, int* tickets, int ntickets) {
   __shared__ float sm[16];
+  for (int k = threadIdx.x; k < ntickets; k += 1024) tickets[k] = 0;
   constexpr int U = 4;                            // 2U independent loads in flight; each thread still adds its rows in
   float s0 = 0.f, s1 = 0.f;                       // increasing order, so the sums do not depend on U
   for (long long base = threadIdx.x; base < N; base += U * 1024) {
@@ -382,7 +386,7 @@ extern "C" int mobody_actor_forward(const MobodyActor* a, void* stream) {
     if (!rc) rc = launch_mlp3_forward(fp, 2, ACT_RELU, prec, st);
   }
   if (rc) return rc;
-  hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, a->stats);
+  hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, a->stats, w.tickets, w.ntiles);
   MB_LAUNCH_OK("k_actor_stats");
   return 0;
 }
@@ -414,12 +418,11 @@ static int actor_backward_impl(const MobodyActor& a, void* stream) {
   Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, nullptr, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, h->precision);
   bq.seed.mode = 2; bq.seed.ar = ra;
   bq.dx = w.dxa; bq.dx_c0 = d->S; bq.dx_n = d->A;
-  rc = launch_mlp3_bwd(bq, 2, true, st);
-  if (rc) return rc;
-  // actor: d(pre-tanh) from both members' dx and the BC term in the prologue, then the actor's own backward
+  // actor: d(pre-tanh) from both members' dx and the BC term in the prologue, then the actor's own backward -- in the same
+  // launch: a tile's actor backward runs in the second of the tile's two frozen-Q workgroups to finish
   Mlp3BwdArgs ba = bwd_args(w.La, a.actor_blob_T, w.dz3a, w.h1a, w.h2a, N, w.dz2, w.dz1, w.dbp, w.ma1, w.ma2, h->precision, w.edz2);
   ba.seed.mode = 3; ba.seed.ar = ra; ba.seed.dz3_out = w.dz3a; ba.seed.lossp = w.lossp;
-  rc = launch_mlp3_bwd(ba, 1, false, st);
+  rc = launch_actor_bwd_chain(bq, ba, w.tickets, st);
   if (rc) return rc;
   LossFinal lf{};                                  // loss_out[0] = p_w*mean(-q) + bc_coef*L_BC, [1] = L_BC (local shares)
   lf.kind = 2; lf.nparts = w.ntiles; lf.scale_q = h->scale_q; lf.weight = h->weight; lf.bc_coef = h->bc_coef;
