@@ -129,18 +129,13 @@ __global__ __launch_bounds__(256) void k_dara_penalty(const float* z_sas, const 
 }
 
 // ---- generic MLP gradient (dz3 + saved activations -> gradient blob) ----
-struct BwdWs { float *dz2, *dz1, *dbp, *slabs; long long total; int nsplit, ntiles; };
-
-static void carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, BwdWs& w) {
+// its scratch: the backward half of a net's record (the caller owns x, h1, h2)
+static NetScratch carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, long long& total) {
   long long off = 0;
   auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  w.dz2 = take((long long)L.members * rows * HID);
-  w.dz1 = take((long long)L.members * rows * HID);
-  w.ntiles = (int)cdiv(rows, MLP_TILE_ROWS);
-  w.nsplit = wgrad_nsplit(rows, L.members);
-  w.dbp = take((long long)w.ntiles * L.members * (2 * HID + L.Np3));
-  w.slabs = take(((L.total_floats + 3) & ~3LL) * w.nsplit);
-  w.total = off;
+  const NetScratch s = carve_net(L, rows, false, L.Np3, take);
+  total = off;
+  return s;
 }
 
 }  // namespace mobody
@@ -149,9 +144,9 @@ using namespace mobody;
 extern "C" int64_t mobody_mlp3_backward_workspace(int in_dim, int out_dim, int members, int64_t rows) {
   MobodyMlpLayout L;
   if (mobody_mlp_layout(in_dim, out_dim, members, &L) || rows < 1) return -1;
-  BwdWs w;
-  carve_bwd(L, rows, nullptr, w);
-  return w.total;
+  long long total = 0;
+  carve_bwd(L, rows, nullptr, total);
+  return total;
 }
 
 extern "C" int mobody_mlp3_backward(const float* blob_T, int in_dim, int out_dim, int members, const float* dz3,
@@ -162,16 +157,20 @@ extern "C" int mobody_mlp3_backward(const float* blob_T, int in_dim, int out_dim
   if (rc) return rc;
   MB_REQUIRE(rows >= 1, "mobody_mlp3_backward: rows < 1");
   MB_REQUIRE(blob_T && dz3 && x && h1 && h2 && grad && workspace, "mobody_mlp3_backward: null pointer");
-  BwdWs w;
-  carve_bwd(L, rows, workspace, w);
+  long long total = 0;
+  const NetScratch w = carve_bwd(L, rows, workspace, total);
   hipStream_t st = as_stream(stream);
   Mlp3BwdArgs b = bwd_net(L, blob_T, rows);       // exact fp32 on the saved activations: no planes, no sign words
   bwd_set_acts(b, h1, h2, nullptr, nullptr, 0);
   bwd_set_grads(b, dz3, w.dz2, w.dz1, w.dbp);
   rc = launch_mlp3_bwd(b, members, false, st);
   if (rc) return rc;
-  return mlp3_weight_grads(L, x, 0, h1, h2, dz3, w.dz2, w.dz1, rows, w.nsplit, w.slabs, w.dbp, w.ntiles, grad, LossFinal{},
-                           AdamTarget{}, st);
+  Mlp3WgradArgs g = wgrad_net(L, rows, w.nsplit);
+  wgrad_set_saves(g, x, 0, h1, h2);               // the members share the input rows
+  wgrad_set_grads(g, dz3, w.dz2, w.dz1, w.dbp, w.ntiles);
+  wgrad_set_scratch(g, w.slabs, nullptr);
+  wgrad_set_result(g, grad, LossFinal{}, AdamTarget{}, PREC_F32);
+  return mlp3_weight_grads(g, st);
 }
 
 extern "C" int mobody_dara_inputs(const float* s, const float* a, const float* s2, int64_t N, int S, int A, float std,

@@ -1,13 +1,13 @@
 // Backward kernels of the 3-layer ReLU MLP (actor / twin-Q), fp32 MFMA.
 //
-//   k_mlp3_bwd   per (32-row tile, member): dz3 (read, or formed in the prologue from the row-wise inputs: TD error,
-//                -p_w dmin(Q), actor d(pre-tanh)) -> dz2 = (dz3 W3^T) * [h2>0] -> dz1 = (dz2 W2^T) * [h1>0]
-//                (-> dx = dz1 W1^T for the frozen-Q pass of the actor update), plus the bias-gradient and loss
-//                partial sums of the tile.  Masks come from the forward's sign words (or the saved activations);
-//                W^T blobs are streamed as MFMA B operands exactly like the forward weights.
+//   k_mlp3_bwd   per (32-row tile, member): dz3 (seed mode 0: read; mode 1: formed in the prologue from the critic's TD
+//                error) -> dz2 = (dz3 W3^T) * [h2>0] -> dz1 = (dz2 W2^T) * [h1>0] (-> dx = dz1 W1^T), plus the
+//                bias-gradient and loss partial sums of the tile.  Masks come from the forward's sign words (or the saved
+//                activations); W^T blobs are streamed as MFMA B operands exactly like the forward weights.
 //                                                                    (autograd of mobody.py:35-48)
-//   k_actor_bwd_chain  the actor update's two passes in one launch: a frozen-Q dX tile, then -- in the second of the tile's two
-//                member workgroups to finish -- the actor's tile of the same rows (ticket per row tile, no waiting)
+//   k_actor_bwd_chain  the actor update's two passes in one launch, the only place seed modes 2 and 3 run: a frozen-Q dX tile
+//                (mode 2: -p_w dmin(Q)), then -- in the second of the tile's two member workgroups to finish -- the actor's
+//                tile of the same rows (mode 3: d(pre-tanh); ticket per row tile, no waiting)
 //   k_wgrad      dW[k][n] = sum_rows A[row][k] * dZ[row][n]: rows are the contraction index, both
 //                operands are read straight from global memory in MFMA fragment order (a wave
 //                instruction = two full 128-byte lines); split-K over row slices, the four waves of a
@@ -148,79 +148,56 @@ __device__ __forceinline__ void wide_store_colsum(f32x16 (&acc)[MT][2], float* X
   cs[1] += __shfl_xor(cs[1], 32);
 }
 
-// Seed prologue (BwdSeed modes 1-3).  Modes 1 and 2 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) --
-// the kernel forms the rank-1 product dz3 W3^T from them; mode 3 fills Xs[r][0..Np3).  All global loads of a pass are
-// independent (one round trip); the loss partials are reduced through `red` (static LDS, 8 floats).  `tile` is the row tile
-// (row0 / TB).  CHAIN: the tile runs inside k_actor_bwd_chain, where mode 2's bcw (and dx) are handed to the mode-3 tile of the
-// same rows within the launch: mode 2 stores them write-through (agent scope), mode 3 loads them at agent scope -- past its
-// CU's L1 -- and a row's loads stay on words its own tile has published.
+// Seed prologue (BwdSeed modes 1-3).  SEED is the seed form of the tile: SEED_RT = k_mlp3_bwd, whose launch carries mode 0 (dz3
+// from memory, no prologue) or mode 1 and chooses at run time; 2 and 3 = the two tiles of k_actor_bwd_chain, known at compile
+// time.  Modes 1 and 2 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) -- the kernel forms the rank-1
+// product dz3 W3^T from them; mode 3 fills Xs[r][0..Np3).  All global loads of a pass are independent (one round trip); the loss
+// partials are reduced through `red` (static LDS, 8 floats).  `tile` is the row tile (row0 / TB).  Mode 2's bcw (and dx) are
+// handed to the mode-3 tile of the same rows within the launch: mode 2 stores them write-through (agent scope), mode 3 loads
+// them at agent scope -- past its CU's L1 -- and a row's loads stay on words its own tile has published.
+constexpr int SEED_RT = -1;
 __device__ __forceinline__ void agent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float agent_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <bool CHAIN = false>
+template <int SEED>
 __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float* red, int m, int tile, long long row0,
                                          int rows_here, int TB) {
   const BwdSeed& sd = a.seed;
   const int Np3 = a.Np3;
   const int t = threadIdx.x;
   float l0 = 0.f, l1 = 0.f;
-  if (sd.mode == 1 || sd.mode == 2) {
+  if constexpr (SEED != 3) {                          // modes 1 and 2: one thread per row
     if (t < TB) {
       const bool ok = t < rows_here;
       const long long row = row0 + (ok ? t : 0);
       float v = 0.f;
-      if (sd.mode == 1) {
+      if constexpr (SEED == SEED_RT) {
         const float qn = sd.qnext ? sd.qnext[row] : fminf(sd.qt[row], sd.qt[a.rows + row]);
         const float y = sd.r[row] + sd.nd[row] * sd.gamma * qn;
         const float d = sd.q[(long long)m * a.rows + row] - y;
         v = ok ? 2.f * d * sd.inv_ng : 0.f;
         l0 = ok ? d * d : 0.f;
+        if (sd.dz3_out != nullptr && ok) {
+          float* g = sd.dz3_out + ((long long)m * a.rows + row) * Np3;
+          g[0] = v;
+          for (int c = 1; c < Np3; ++c) g[c] = 0.f;
+        }
       } else {
         const ActorRowArgs& r = sd.ar;
         const float q0 = r.qp[row], q1 = r.qp[r.N + row];
         const float c = -policy_weight(r) / (float)r.Ng;
         const float g0 = q0 < q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
         v = ok ? c * (m == 0 ? g0 : 1.f - g0) : 0.f;
-        if (m == 0 && ok && row < r.Nt) {
-          if constexpr (CHAIN) agent_store(r.bcw + row, bc_weight(r, row));
-          else r.bcw[row] = bc_weight(r, row);
-        }
+        if (m == 0 && ok && row < r.Nt) agent_store(r.bcw + row, bc_weight(r, row));
       }
       Xs[t] = v;
-      if (sd.dz3_out != nullptr && ok) {
-        float* g = sd.dz3_out + ((long long)m * a.rows + row) * Np3;
-        g[0] = v;
-        for (int c = 1; c < Np3; ++c) g[c] = 0.f;
-      }
     }
-  } else {                                          // mode 3: one thread per (row, column)
+    if constexpr (SEED == 2) return;                  // no loss partials
+  } else {                                            // mode 3: one thread per (row, column)
     const ActorRowArgs& r = sd.ar;
     const float wscale = r.h.bc_coef * 2.f / ((float)r.Ntg * (float)r.A);
-    if constexpr (!CHAIN) {
-    for (int e = t; e < TB * Np3; e += NTHREADS) {
-      const int rr = e / Np3, j = e - rr * Np3;
-      const bool ok = rr < rows_here && j < r.A;
-      const long long row = row0 + (rr < rows_here ? rr : 0);
-      const int jc = j < r.A ? j : 0;
-      const bool bc = row < r.Nt;
-      const float p = r.pi[row * r.A + jc];
-      const float d0 = r.dxa[row * r.A + jc], d1 = r.dxa[(r.N + row) * r.A + jc];
-      const float act = r.act[row * r.A + jc];
-      const float w = r.bcw[bc ? row : 0];
-      float v = 0.f;
-      if (ok) {
-        float d = d0 + d1;
-        if (bc) { const float df = p - act; d += wscale * w * df; l1 += w * (df * df); }
-        const float th = p / r.h.max_action;
-        v = d * r.h.max_action * (1.f - th * th);                   // d tanh
-        if (j == 0) l0 = l0 - fminf(r.qp[row], r.qp[r.N + row]);
-      }
-      Xs[rr * LDX + j] = v;
-      if (rr < rows_here) sd.dz3_out[(row0 + rr) * Np3 + j] = v;
-    }
-    } else {
-    // The agent-scope loads of dxa / bcw pass L1, so a thread requests the operands of ALL its elements (SEED_U passes of the loop
-    // above: Np3 = 32 has four) before it uses the first: one round trip per tile, not one per pass.  The elements are then formed
-    // in the same order by the same expressions.
+    // The agent-scope loads of dxa / bcw pass L1, so a thread requests the operands of ALL its elements (SEED_U passes of
+    // NTHREADS elements: Np3 = 32 has four) before it uses the first: one round trip per tile, not one per pass.  The elements
+    // are then formed in element order.
     constexpr int SEED_U = 4;
     for (int e0 = t; e0 < TB * Np3; e0 += SEED_U * NTHREADS) {
       float pv[SEED_U], d0v[SEED_U], d1v[SEED_U], av[SEED_U], wv[SEED_U], qv[SEED_U][2];
@@ -261,9 +238,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
         }
       }
     }
-    }
   }
-  if (sd.mode == 2) return;
   // loss partials of this tile
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { l0 += __shfl_xor(l0, o); l1 += __shfl_xor(l1, o); }
@@ -272,7 +247,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   if (t == 0) {
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
-    if (sd.mode == 1) sd.lossp[tile * 2 + m] = l0;
+    if constexpr (SEED == SEED_RT) sd.lossp[tile * 2 + m] = l0;
     else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
 }
@@ -282,8 +257,8 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
 // MASK: see wide_mask_apply (1: sign words m1, m2; 0: saved activations h1, h2; 2: Swish derivatives in h1, h2).
 // PM: 0 = exact fp32 MFMA; 1..4 = the 256 x 256 GEMM (dz2 W2^T) on the split-precision core, streaming W2^T's planes.
 // The backward of one (32-row tile, member) of a launch of `members` members: Xs is the workgroup's dynamic LDS, red its eight
-// static floats.  CHAIN: see bwd_seed.
-template <bool DX, int NT, int MASK, int PM = 0, bool CHAIN = false>
+// static floats.  SEED: see bwd_seed.
+template <bool DX, int NT, int MASK, int PM = 0, int SEED = SEED_RT>
 __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int tile, int members, float* Xs, float* red) {
   constexpr bool BITS = MASK == 1;
   constexpr int TB = MLP_TILE_ROWS, MT = MLP_MT;
@@ -313,13 +288,13 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
   // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
   // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
   // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
-  const int mode = a.seed.mode;
-  const bool rank1 = mode == 1 || mode == 2, with_db = mode != 2;
+  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : SEED == 2;
+  constexpr bool with_db = SEED != 2;
   const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
   if (!rank1) wide_prefetch(w3t, a.Np3, ring);    // weight fragments travel while the seed rows are fetched
-  if (mode == 0) tile_load(Xs, 0, a.dz3 + ((long long)m * a.rows + row0) * a.Np3, a.Np3, a.Np3, 0, rows_here, TB);
-  else bwd_seed<CHAIN>(a, Xs, red, m, tile, row0, rows_here, TB);
+  if (SEED == SEED_RT && !rank1) tile_load(Xs, 0, a.dz3 + ((long long)m * a.rows + row0) * a.Np3, a.Np3, a.Np3, 0, rows_here, TB);
+  else bwd_seed<SEED>(a, Xs, red, m, tile, row0, rows_here, TB);
   lds_barrier();
   TR(1);
   if (with_db && (int)threadIdx.x < a.Np3) {      // db3 partial of this tile (rank-1: column 0 alone is non-zero)
@@ -387,7 +362,7 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
     auto emit = [&](int row, int col, float v) {
       const int c = col - a.dx_c0;
       if (row < rows_here && c >= 0 && c < a.dx_n) {
-        if constexpr (CHAIN) agent_store(dx + row * a.dx_n + c, v);
+        if constexpr (SEED != SEED_RT) agent_store(dx + row * a.dx_n + c, v);
         else dx[row * a.dx_n + c] = v;
       }
     };
@@ -423,45 +398,37 @@ static int launch_bwd_t(const Mlp3BwdArgs& a, int members, hipStream_t st) {
   return 0;
 }
 
-// split-precision backward: sign-word masks (the train step's three backward launches)
-template <int NPL>
-static int launch_bwd_bf(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
-  const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (!with_dx) return launch_bwd_t<false, 0, 1, NPL>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 1, 1, NPL>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 1, NPL>(a, members, st)
-                                                                             : launch_bwd_t<true, 0, 1, NPL>(a, members, st);
+// (Np1t, with_dx) -> the <DX, NT> pair of a backward instance, handed to `f` as integral constants: no dx = <false, 0>; dx
+// through the K-split narrow layer where Np1t == 16 * NT (NT = 1, 2), else <true, 0>, the row-split path
+template <class F>
+static int dispatch_dx_nt(int Np1t, bool with_dx, F&& f) {
+  using std::integral_constant;
+  if (!with_dx) return f(std::false_type{}, integral_constant<int, 0>{});
+  return Np1t == 16 ? f(std::true_type{}, integral_constant<int, 1>{}) : Np1t == 32 ? f(std::true_type{}, integral_constant<int, 2>{})
+                                                                                      : f(std::true_type{}, integral_constant<int, 0>{});
 }
 
-// fp32 ReLU backward (the callers size `dbp` / the bias reduction by MLP_TILE_ROWS)
-template <int BITS>
-static int launch_bwd_masks(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
-  const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (!with_dx) return launch_bwd_t<false, 0, BITS>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 1, BITS>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, BITS>(a, members, st)
-                                                                          : launch_bwd_t<true, 0, BITS>(a, members, st);
-}
-
-// Swish nets (the ensemble dynamics, pre-training): derivative multipliers in h1 / h2
-static int launch_bwd_swish(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
-  const int nt = a.Np1t == 16 ? 1 : a.Np1t == 32 ? 2 : 0;
-  if (a.prec == PREC_F16X2 && a.w2t_planes != nullptr) {     // f16x2: the 256 x 256 GEMM on the split core, dz2 as planes for the weight gradients
-    if (!with_dx) return launch_bwd_t<false, 0, 2, 4>(a, members, st);
-    return nt == 1 ? launch_bwd_t<true, 1, 2, 4>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2, 4>(a, members, st)
-                                                                             : launch_bwd_t<true, 0, 2, 4>(a, members, st);
-  }
-  if (!with_dx) return launch_bwd_t<false, 0, 2>(a, members, st);
-  return nt == 1 ? launch_bwd_t<true, 1, 2>(a, members, st) : nt == 2 ? launch_bwd_t<true, 2, 2>(a, members, st)
-                                                                         : launch_bwd_t<true, 0, 2>(a, members, st);
+// MASK / NPL as in mlp3_bwd_tile (MASK, PM); the callers size `dbp` / the bias reduction by MLP_TILE_ROWS
+template <int MASK, int NPL = 0>
+static int launch_bwd_dx(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
+  return dispatch_dx_nt(a.Np1t, with_dx, [&](auto dx, auto nt) {
+    return launch_bwd_t<decltype(dx)::value, decltype(nt)::value, MASK, NPL>(a, members, st);
+  });
 }
 
 int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t st) {
+  MB_REQUIRE(a.seed.mode == 0 || a.seed.mode == 1, "launch_mlp3_bwd: seed mode %d runs in launch_actor_bwd_chain only", a.seed.mode);
   if (a.rows <= 0) return 0;
-  if (a.swish) return launch_bwd_swish(a, members, with_dx, st);
+  // Swish nets (the ensemble dynamics, pre-training): derivative multipliers in h1 / h2; f16x2: the 256 x 256 GEMM on the split
+  // core, dz2 as planes for the weight gradients
+  if (a.swish)
+    return a.prec == PREC_F16X2 && a.w2t_planes != nullptr ? launch_bwd_dx<2, 4>(a, members, with_dx, st) : launch_bwd_dx<2>(a, members, with_dx, st);
+  // split-precision backward: sign-word masks (the train step's three backward launches)
   if (a.prec != PREC_F32 && a.w2t_planes != nullptr && a.m1 != nullptr && a.m2 != nullptr)
-    return a.prec == PREC_BF16 ? launch_bwd_bf<1>(a, members, with_dx, st) : a.prec == PREC_BF16X2 ? launch_bwd_bf<2>(a, members, with_dx, st)
-         : a.prec == PREC_BF16X3 ? launch_bwd_bf<3>(a, members, with_dx, st) : launch_bwd_bf<4>(a, members, with_dx, st);
-  return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_masks<1>(a, members, with_dx, st)
-                                            : launch_bwd_masks<0>(a, members, with_dx, st);
+    return a.prec == PREC_BF16 ? launch_bwd_dx<1, 1>(a, members, with_dx, st) : a.prec == PREC_BF16X2 ? launch_bwd_dx<1, 2>(a, members, with_dx, st)
+         : a.prec == PREC_BF16X3 ? launch_bwd_dx<1, 3>(a, members, with_dx, st) : launch_bwd_dx<1, 4>(a, members, with_dx, st);
+  // fp32 ReLU backward: sign words, or the saved activations
+  return a.m1 != nullptr && a.m2 != nullptr ? launch_bwd_dx<1>(a, members, with_dx, st) : launch_bwd_dx<0>(a, members, with_dx, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -490,7 +457,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_actor_bwd_chain(Mlp3BwdArgs q, 
   __shared__ float red[8];
   extern __shared__ __attribute__((aligned(16))) float Xs[];
   const int tile = blockIdx.x;
-  mlp3_bwd_tile<true, NT, 1, PM, true>(q, blockIdx.y, tile, 2, Xs, red);
+  mlp3_bwd_tile<true, NT, 1, PM, 2>(q, blockIdx.y, tile, 2, Xs, red);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's write-through dx (and bcw) stores are done
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -510,7 +477,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_actor_bwd_chain(Mlp3BwdArgs q, 
   using KernArg = const __attribute__((address_space(4))) Mlp3BwdArgs;
   KernArg* ka = (KernArg*)__builtin_amdgcn_kernarg_segment_ptr() + 1;
   asm volatile("" : "+s"(ka));
-  mlp3_bwd_tile<false, 0, 1, PM, true>(*(const Mlp3BwdArgs*)ka, 0, tile, 1, Xs, red);
+  mlp3_bwd_tile<false, 0, 1, PM, 3>(*(const Mlp3BwdArgs*)ka, 0, tile, 1, Xs, red);
 }
 
 template <int NT, int PM>
@@ -530,8 +497,7 @@ static int launch_chain_t(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tick
 }
 template <int PM>
 static int launch_chain_nt(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
-  return q.Np1t == 16 ? launch_chain_t<1, PM>(q, pi, tickets, st) : q.Np1t == 32 ? launch_chain_t<2, PM>(q, pi, tickets, st)
-                                                                                   : launch_chain_t<0, PM>(q, pi, tickets, st);
+  return dispatch_dx_nt(q.Np1t, true, [&](auto, auto nt) { return launch_chain_t<decltype(nt)::value, PM>(q, pi, tickets, st); });
 }
 
 // q: the frozen twin-Q pass (seed mode 2, dx out), pi: the actor's pass (seed mode 3) on the same rows; both with sign words and
@@ -634,30 +600,62 @@ __device__ __forceinline__ void wgrad_store(const WgradJob& jb, const WgradArgs&
   }
 }
 
-// The row loop runs on wave-uniform row-block pointers (scalar registers) plus one per-lane 32-bit offset per operand
-// column block, so a load costs no vector arithmetic, and whole row blocks carry no masks: the loaded registers feed the
-// MFMAs directly and the loads of block n+1 stay in flight under the MFMAs of block n.  (Multiplying every loaded
-// value by a 0/1 mask, as the first version did, made the compiler wait for each block's loads BEFORE the previous
-// block's MFMAs: nothing overlapped inside a wave.)  Columns past ka / nb read column 0 instead: their products land in
-// output elements wgrad_store never writes.  Only the < RB rows left at the end of a wave's slice take masked loads.
-template <int MT>
-__device__ __forceinline__ void wgrad_tile(const WgradJob& jb, const WgradArgs& a, int tile, int slice, int m, float* red) {
-  constexpr int NT = 2, TK = 32 * MT, TN = 32 * NT, U = 4, RB = 2 * U;
-  const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
-  const int i = lane & 31, h = lane >> 5;
+// What the three tile functions open with: the tile's first output row k0 and column n0, the row range [r_begin, r_end) of this
+// wave (wave w of slice `slice` takes the slice's w-th run of rows_per_wave rows), and zeroed accumulators.
+struct WgradTile { int k0, n0; long long r_begin, r_end; };
+template <int MT, int NT>
+__device__ __forceinline__ WgradTile wgrad_tile_open(const WgradJob& jb, const WgradArgs& a, int tile, int slice, f32x16 (&acc)[MT][NT]) {
+  const int w = __builtin_amdgcn_readfirstlane(wave_id());
   const int tk = tile / jb.tiles_n, tn = tile - tk * jb.tiles_n;
-  const int k0 = tk * TK, n0 = tn * TN;
-  const long long r_begin = ((long long)slice * 4 + w) * a.rows_per_wave;
-  const long long r_end = min(a.rows, r_begin + a.rows_per_wave);
-  const int lda = jb.lda, ldb = jb.ldb;
-
-  f32x16 acc[MT][NT];
+  WgradTile g;
+  g.k0 = tk * 32 * MT; g.n0 = tn * 32 * NT;
+  g.r_begin = ((long long)slice * 4 + w) * a.rows_per_wave;
+  g.r_end = min(a.rows, g.r_begin + a.rows_per_wave);
 #pragma unroll
   for (int x = 0; x < MT; ++x)
 #pragma unroll
     for (int y = 0; y < NT; ++y)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
+  return g;
+}
+
+// The row loop runs on wave-uniform row-block pointers (scalar registers) plus one per-lane 32-bit offset per operand
+// column block, so a load costs no vector arithmetic, and whole row blocks carry no masks: the loaded registers feed the
+// MFMAs directly and the loads of block n+1 stay in flight under the MFMAs of block n.  (Multiplying every loaded
+// value by a 0/1 mask, as the first version did, made the compiler wait for each block's loads BEFORE the previous
+// block's MFMAs: nothing overlapped inside a wave.)  Columns past ka / nb read column 0 instead: their products land in
+// output elements wgrad_store never writes.  Only the < RB rows left at the end of a wave's slice take masked loads.
+// The double-buffered loop over a wave's nblk whole row blocks: load(block, buf) requests a block's operands, mma(buf) feeds
+// them to the MFMAs, so the loads of block n + 1 travel under the MFMAs of block n.  Straight-line body (no branch between a
+// block's loads and the previous block's MFMAs, or the compiler's vmcnt bookkeeping merges the two paths and waits for the NEW
+// loads): the last pass re-loads block nblk - 1, unused if nblk is even.
+template <class Buf, class Load, class Mma>
+__device__ __forceinline__ void wgrad_row_loop(int nblk, Load&& load, Mma&& mma) {
+  Buf b0, b1;
+  if (nblk > 0) load(0, b0);
+  for (int blk = 0; blk + 1 < nblk; blk += 2) {
+    load(blk + 1, b1);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(b0);
+    __builtin_amdgcn_sched_barrier(0);
+    load(min(blk + 2, nblk - 1), b0);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(b1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (nblk & 1) mma(b0);
+}
+
+template <int MT>
+__device__ __forceinline__ void wgrad_tile(const WgradJob& jb, const WgradArgs& a, int tile, int slice, int m, float* red) {
+  constexpr int NT = 2, U = 4, RB = 2 * U;
+  f32x16 acc[MT][NT];
+  const WgradTile g = wgrad_tile_open<MT, NT>(jb, a, tile, slice, acc);
+  const int k0 = g.k0, n0 = g.n0;
+  const long long r_begin = g.r_begin, r_end = g.r_end;
+  const int lane = lane_id(), i = lane & 31, h = lane >> 5;
+  const int lda = jb.lda, ldb = jb.ldb;
 
   unsigned oa[MT], ob[NT];                            // byte offsets; lane half h takes the odd row of each pair
 #pragma unroll
@@ -665,54 +663,42 @@ __device__ __forceinline__ void wgrad_tile(const WgradJob& jb, const WgradArgs& 
 #pragma unroll
   for (int y = 0; y < NT; ++y) { const int c = n0 + 32 * y + i; ob[y] = 4u * (unsigned)((c < jb.nb ? c : 0) + h * ldb); }
 
-  auto mma = [&](float (&av)[U][MT], float (&bv)[U][NT]) {
+  struct Blk { float a[U][MT], b[U][NT]; };          // the operands of one RB-row block
+  auto mma = [&](const Blk& k) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
       for (int x = 0; x < MT; ++x)
 #pragma unroll
         for (int y = 0; y < NT; ++y)
-          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][x], bv[u][y], acc[x][y], 0, 0, 0);
+          acc[x][y] = __builtin_amdgcn_mfma_f32_32x32x2f32(k.a[u][x], k.b[u][y], acc[x][y], 0, 0, 0);
   };
   if (r_begin < r_end) {
     const int nrows = (int)(r_end - r_begin), nblk = nrows / RB, tail = nrows - nblk * RB;
     const auto ra = slice_rsrc(jb.A + m * jb.a_mstride + r_begin * lda, nrows, lda);
     const auto rb = slice_rsrc(jb.B + m * jb.b_mstride + r_begin * ldb, nrows, ldb);
     const unsigned sa = 4u * lda, sb = 4u * ldb;      // row pitch in bytes
-    auto load = [&](unsigned row, float (&av)[U][MT], float (&bv)[U][NT]) {
+    wgrad_row_loop<Blk>(nblk, [&](int blk, Blk& k) {
+      const unsigned row = blk * RB;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
 #pragma unroll
-        for (int x = 0; x < MT; ++x) av[u][x] = buf_ld(ra, oa[x], (row + 2 * u) * sa);
+        for (int x = 0; x < MT; ++x) k.a[u][x] = buf_ld(ra, oa[x], (row + 2 * u) * sa);
 #pragma unroll
-        for (int y = 0; y < NT; ++y) bv[u][y] = buf_ld(rb, ob[y], (row + 2 * u) * sb);
+        for (int y = 0; y < NT; ++y) k.b[u][y] = buf_ld(rb, ob[y], (row + 2 * u) * sb);
       }
-    };
-    float a0[U][MT], b0[U][NT], a1[U][MT], b1[U][NT];
-    // Straight-line body (no branch between a block's loads and the previous block's MFMAs, or the compiler's vmcnt
-    // bookkeeping merges the two paths and waits for the NEW loads): the last pass re-loads block nblk - 1, unused if nblk is even.
-    if (nblk > 0) load(0, a0, b0);
-    for (int blk = 0; blk + 1 < nblk; blk += 2) {
-      load((blk + 1) * RB, a1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      load(min(blk + 2, nblk - 1) * RB, a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(a1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (nblk & 1) mma(a0, b0);
+    }, mma);
     if (tail > 0) {                                   // rows [nblk * RB, nrows) of the slice: masked lanes re-read its first row
+      Blk k;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const bool ok = 2 * u + h < tail;
 #pragma unroll
-        for (int x = 0; x < MT; ++x) { const float v = buf_ld(ra, ok ? oa[x] + 2 * u * sa : oa[x] - h * sa, nblk * RB * sa); a0[u][x] = ok ? v : 0.f; }
+        for (int x = 0; x < MT; ++x) { const float v = buf_ld(ra, ok ? oa[x] + 2 * u * sa : oa[x] - h * sa, nblk * RB * sa); k.a[u][x] = ok ? v : 0.f; }
 #pragma unroll
-        for (int y = 0; y < NT; ++y) { const float v = buf_ld(rb, ok ? ob[y] + 2 * u * sb : ob[y] - h * sb, nblk * RB * sb); b0[u][y] = ok ? v : 0.f; }
+        for (int y = 0; y < NT; ++y) { const float v = buf_ld(rb, ok ? ob[y] + 2 * u * sb : ob[y] - h * sb, nblk * RB * sb); k.b[u][y] = ok ? v : 0.f; }
       }
-      mma(a0, b0);
+      mma(k);
     }
   }
   wgrad_store<MT, NT>(jb, a, acc, k0, n0, slice, m, red);
@@ -724,21 +710,13 @@ __device__ __forceinline__ void wgrad_tile(const WgradJob& jb, const WgradArgs& 
 // (i + j < NPL) products.  Same work split, addressing, LDS reduction and slab output as wgrad_tile<2>; row blocks of 16.
 template <int NPL>
 __device__ __forceinline__ void wgrad_tile_bf(const WgradJob& jb, const WgradArgs& a, int tile, int slice, int m, float* red) {
-  constexpr int MT = 2, NT = 2, TK = 64, TN = 64, RB = 16;
-  const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
-  const int i = lane & 31, h = lane >> 5;
-  const int tk = tile / jb.tiles_n, tn = tile - tk * jb.tiles_n;
-  const int k0 = tk * TK, n0 = tn * TN;
-  const long long r_begin = ((long long)slice * 4 + w) * a.rows_per_wave;
-  const long long r_end = min(a.rows, r_begin + a.rows_per_wave);
-  const int lda = jb.lda, ldb = jb.ldb;
+  constexpr int MT = 2, NT = 2, RB = 16;
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int x = 0; x < MT; ++x)
-#pragma unroll
-    for (int y = 0; y < NT; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
+  const WgradTile g = wgrad_tile_open<MT, NT>(jb, a, tile, slice, acc);
+  const int k0 = g.k0, n0 = g.n0;
+  const long long r_begin = g.r_begin, r_end = g.r_end;
+  const int lane = lane_id(), i = lane & 31, h = lane >> 5;
+  const int lda = jb.lda, ldb = jb.ldb;
   unsigned oa[MT], ob[NT];                                       // byte offsets; job 0: every column is real (ka = nb = 256)
 #pragma unroll
   for (int x = 0; x < MT; ++x) oa[x] = 4u * (unsigned)(k0 + 32 * x + i + 8 * h * lda);
@@ -753,12 +731,13 @@ __device__ __forceinline__ void wgrad_tile_bf(const WgradJob& jb, const WgradArg
       for (int p = 0; p < NPL; ++p) f[p][j] = t[p];
     }
   };
-  auto mma = [&](const float (&av)[MT][8], const float (&bv)[NT][8]) {
+  struct Blk { float a[MT][8], b[NT][8]; };          // the operands of one RB-row block
+  auto mma = [&](const Blk& k) {
     bf16x8 af[MT][NPL], bfr[NT][NPL];
 #pragma unroll
-    for (int x = 0; x < MT; ++x) pack(av[x], af[x]);
+    for (int x = 0; x < MT; ++x) pack(k.a[x], af[x]);
 #pragma unroll
-    for (int y = 0; y < NT; ++y) pack(bv[y], bfr[y]);
+    for (int y = 0; y < NT; ++y) pack(k.b[y], bfr[y]);
 #pragma unroll
     for (int x = 0; x < MT; ++x)
 #pragma unroll
@@ -774,40 +753,27 @@ __device__ __forceinline__ void wgrad_tile_bf(const WgradJob& jb, const WgradArg
     const auto ra = slice_rsrc(jb.A + m * jb.a_mstride + r_begin * lda, nrows, lda);
     const auto rb = slice_rsrc(jb.B + m * jb.b_mstride + r_begin * ldb, nrows, ldb);
     const unsigned sa = 4u * lda, sb = 4u * ldb;
-    auto load = [&](unsigned row, float (&av)[MT][8], float (&bv)[NT][8]) {
+    wgrad_row_loop<Blk>(nblk, [&](int blk, Blk& k) {
+      const unsigned row = blk * RB;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
 #pragma unroll
-        for (int x = 0; x < MT; ++x) av[x][j] = buf_ld(ra, oa[x], (row + j) * sa);
+        for (int x = 0; x < MT; ++x) k.a[x][j] = buf_ld(ra, oa[x], (row + j) * sa);
 #pragma unroll
-        for (int y = 0; y < NT; ++y) bv[y][j] = buf_ld(rb, ob[y], (row + j) * sb);
+        for (int y = 0; y < NT; ++y) k.b[y][j] = buf_ld(rb, ob[y], (row + j) * sb);
       }
-    };
-    float a0[MT][8], b0[NT][8], a1[MT][8], b1[NT][8];
-    // Straight-line body (no branch between a block's loads and the previous block's MFMAs, or the compiler's vmcnt
-    // bookkeeping merges the two paths and waits for the NEW loads): the last pass re-loads block nblk - 1, unused if nblk is even.
-    if (nblk > 0) load(0, a0, b0);
-    for (int blk = 0; blk + 1 < nblk; blk += 2) {
-      load((blk + 1) * RB, a1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      load(min(blk + 2, nblk - 1) * RB, a0, b0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(a1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (nblk & 1) mma(a0, b0);
-    if (tail > 0) {
+    }, mma);
+    if (tail > 0) {                                   // as in wgrad_tile
+      Blk k;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool ok = 8 * h + j < tail;
 #pragma unroll
-        for (int x = 0; x < MT; ++x) { const float v = buf_ld(ra, ok ? oa[x] + j * sa : oa[x] - 8 * h * sa, nblk * RB * sa); a0[x][j] = ok ? v : 0.f; }
+        for (int x = 0; x < MT; ++x) { const float v = buf_ld(ra, ok ? oa[x] + j * sa : oa[x] - 8 * h * sa, nblk * RB * sa); k.a[x][j] = ok ? v : 0.f; }
 #pragma unroll
-        for (int y = 0; y < NT; ++y) { const float v = buf_ld(rb, ok ? ob[y] + j * sb : ob[y] - 8 * h * sb, nblk * RB * sb); b0[y][j] = ok ? v : 0.f; }
+        for (int y = 0; y < NT; ++y) { const float v = buf_ld(rb, ok ? ob[y] + j * sb : ob[y] - 8 * h * sb, nblk * RB * sb); k.b[y][j] = ok ? v : 0.f; }
       }
-      mma(a0, b0);
+      mma(k);
     }
   }
   wgrad_store<MT, NT>(jb, a, acc, k0, n0, slice, m, red);
@@ -823,20 +789,12 @@ __device__ __forceinline__ void wgrad_tile_bf(const WgradJob& jb, const WgradArg
 // 0: its terms are below 2^-24 of the dominant tile's and so below fp32 resolution of the sum (a factor clamped to
 // 2^-24 instead would overweight it by 2^(-24 - sh), which is all there is of an element the dominant tiles do not reach).
 __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradArgs& a, int tile, int slice, int m, float* red) {
-  constexpr int MT = 2, NT = 2, TK = 64, TN = 64, RB = 16;
-  const int lane = lane_id(), w = __builtin_amdgcn_readfirstlane(wave_id());
-  const int i = lane & 31, h = lane >> 5;
-  const int tk = tile / jb.tiles_n, tn = tile - tk * jb.tiles_n;
-  const int k0 = tk * TK, n0 = tn * TN;
-  const long long r_begin = ((long long)slice * 4 + w) * a.rows_per_wave;      // multiple of 16
-  const long long r_end = min(a.rows, r_begin + a.rows_per_wave);
+  constexpr int MT = 2, NT = 2, RB = 16;
   f32x16 acc[MT][NT];
-#pragma unroll
-  for (int x = 0; x < MT; ++x)
-#pragma unroll
-    for (int y = 0; y < NT; ++y)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
+  const WgradTile g = wgrad_tile_open<MT, NT>(jb, a, tile, slice, acc);
+  const int k0 = g.k0, n0 = g.n0;
+  const long long r_begin = g.r_begin, r_end = g.r_end;
+  const int lane = lane_id(), i = lane & 31, h = lane >> 5;      // r_begin: multiple of 16
   int U = 0;
   if (r_begin < r_end) {
     const int nblk = (int)((r_end - r_begin + RB - 1) / RB);                   // the planes are zero beyond the batch (rows32)
@@ -867,7 +825,7 @@ __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradAr
       const int t = (int)((r_begin + (long long)b * RB) >> 5);
       k.sh = U - __builtin_amdgcn_readlane(Ev, t - t0);                         // <= 0
     };
-    auto mma = [&](Blk& k) {
+    auto mma = [&](const Blk& k) {
       // 2^sh as a packed fp16 pair, exact for -24 <= sh <= 0; 0 below (the tile is dropped, see above: a select rather than a
       // branch around the MFMAs, which would break the straight-line body the loop relies on)
       const _Float16 f = k.sh < -24 ? (_Float16)0.f : (_Float16)__int_as_float((max(k.sh, -24) + 127) << 23);
@@ -885,20 +843,7 @@ __device__ __forceinline__ void wgrad_tile_f16(const WgradJob& jb, const WgradAr
           acc[x][y] = split_mfma<4>(k.a[0][x], bs[0][y], acc[x][y]);
         }
     };
-    Blk b0, b1;
-    // straight-line body as in wgrad_tile: the last pass re-loads block nblk - 1, unused if nblk is even
-    load(0, b0);
-    for (int blk = 0; blk + 1 < nblk; blk += 2) {
-      load(blk + 1, b1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(b0);
-      __builtin_amdgcn_sched_barrier(0);
-      load(min(blk + 2, nblk - 1), b0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(b1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (nblk & 1) mma(b0);
+    wgrad_row_loop<Blk>(nblk, load, mma);
   }
 #pragma unroll
   for (int x = 0; x < MT; ++x)
@@ -917,103 +862,77 @@ __device__ __forceinline__ void wgrad_bias_corrections(const WgradArgs& a) {
   if (a.bc_out != nullptr && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) adam_dev_consts(a.bc_t, a.bc_lr, a.bc_out);
 }
 
-__global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_f16(WgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
+// The body of the three weight-gradient kernels, which differ in the tile function of job 0 (TILE0) alone.  red: the workgroup's
+// dynamic LDS, [2][64][64] floats.
+template <void (*TILE0)(const WgradJob&, const WgradArgs&, int, int, int, float*)>
+__device__ __forceinline__ void wgrad_body(const WgradArgs& a, float* red) {
   wgrad_bias_corrections(a);
+  // XCD-aware decode: blocks with equal (id % 8) share an XCD; the output tile varies slowest (block comment above)
   const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
   const int groups = (a.nsplit * a.members + 7) / 8;
   const int t = j / groups;
   const int sm = xcd + 8 * (j - t * groups);
   if (sm >= a.nsplit * a.members) return;
   const int slice = sm / a.members, m = sm - slice * a.members;
-  if (t < a.job[0].ntiles) wgrad_tile_f16(a.job[0], a, t, slice, m, red);
+  if (t < a.job[0].ntiles) TILE0(a.job[0], a, t, slice, m, red);
   else if (t < a.job[0].ntiles + a.job[1].ntiles) wgrad_tile<1>(a.job[1], a, t - a.job[0].ntiles, slice, m, red);
   else wgrad_tile<1>(a.job[2], a, t - a.job[0].ntiles - a.job[1].ntiles, slice, m, red);
+}
+
+__global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_f16(WgradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float red[];
+  wgrad_body<wgrad_tile_f16>(a, red);
 }
 
 template <int NPL>
 __global__ __launch_bounds__(NTHREADS, 2) void k_wgrad_bf(WgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
-  wgrad_bias_corrections(a);
-  const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  const int groups = (a.nsplit * a.members + 7) / 8;
-  const int t = j / groups;
-  const int sm = xcd + 8 * (j - t * groups);
-  if (sm >= a.nsplit * a.members) return;
-  const int slice = sm / a.members, m = sm - slice * a.members;
-  if (t < a.job[0].ntiles) wgrad_tile_bf<NPL>(a.job[0], a, t, slice, m, red);
-  else if (t < a.job[0].ntiles + a.job[1].ntiles) wgrad_tile<1>(a.job[1], a, t - a.job[0].ntiles, slice, m, red);
-  else wgrad_tile<1>(a.job[2], a, t - a.job[0].ntiles - a.job[1].ntiles, slice, m, red);
+  extern __shared__ __attribute__((aligned(16))) float red[];
+  wgrad_body<wgrad_tile_bf<NPL>>(a, red);
 }
 
 __global__ __launch_bounds__(NTHREADS, 4) void k_wgrad(WgradArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float red[];     // [2][64][64]
-  // XCD-aware decode: blocks with equal (id % 8) share an XCD; the output tile varies slowest (block comment above)
-  wgrad_bias_corrections(a);
-  const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-  const int groups = (a.nsplit * a.members + 7) / 8;
-  const int t = j / groups;
-  const int sm = xcd + 8 * (j - t * groups);
-  if (sm >= a.nsplit * a.members) return;
-  const int slice = sm / a.members, m = sm - slice * a.members;
-  if (t < a.job[0].ntiles) wgrad_tile<2>(a.job[0], a, t, slice, m, red);
-  else if (t < a.job[0].ntiles + a.job[1].ntiles) wgrad_tile<1>(a.job[1], a, t - a.job[0].ntiles, slice, m, red);
-  else wgrad_tile<1>(a.job[2], a, t - a.job[0].ntiles - a.job[1].ntiles, slice, m, red);
+  extern __shared__ __attribute__((aligned(16))) float red[];
+  wgrad_body<wgrad_tile<2>>(a, red);
+}
+
+// one weight-gradient kernel: allow its 32 KB of dynamic LDS once, then launch
+template <void (*K)(WgradArgs)>
+static int launch_wgrad_k(const char* name, const WgradArgs& a, int blocks, hipStream_t st) {
+  constexpr size_t lds = (size_t)2 * 64 * 64 * sizeof(float);
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(K, lds);
+    if (rc) return rc;
+    once = true;
+  }
+  hipLaunchKernelGGL(K, dim3(blocks), dim3(NTHREADS), lds, st, a);
+  MB_LAUNCH_OK(name);
+  return 0;
 }
 
 int launch_wgrad(WgradArgs a, hipStream_t st) {
   if (a.rows <= 0) return 0;
-  constexpr size_t lds = (size_t)2 * 64 * 64 * sizeof(float);
-  static bool once = false;
-  if (!once) {
-    int rc = allow_big_lds(k_wgrad, lds);
-    if (rc) return rc;
-    once = true;
-  }
+  const bool planes = a.prec == PREC_F16X2 && a.eA != nullptr;     // "f16x2": job 0 on the pre-split fp16 planes
   long long rpw = cdiv(a.rows, (long long)4 * a.nsplit);
   a.rows_per_wave = (rpw + 15) & ~15LL;               // whole 8- / 16-row blocks for every wave but the last one with work
-  for (int k = (a.prec == PREC_F16X2 && a.eA != nullptr) ? 1 : 0; k < 3; ++k)     // a wave addresses its row slice through 32-bit buffer offsets
+  for (int k = planes ? 1 : 0; k < 3; ++k)            // a wave addresses its row slice through 32-bit buffer offsets
     if (a.rows_per_wave * (long long)std::max(a.job[k].lda, a.job[k].ldb) * 4 >= (1LL << 31))
       return fail(MOBODY_E_ARG, "launch_wgrad: row slice too large for 32-bit offsets (raise nsplit)");
+  if (planes && a.rows_per_wave > 2048) return fail(MOBODY_E_ARG, "launch_wgrad: more than 64 row tiles per wave slice (raise nsplit)");
   a.job[0].tiles_n = (a.job[0].nb + 63) / 64; a.job[0].ntiles = ((a.job[0].ka + 63) / 64) * a.job[0].tiles_n;
   for (int k = 1; k < 3; ++k) { a.job[k].tiles_n = (a.job[k].nb + 63) / 64; a.job[k].ntiles = ((a.job[k].ka + 31) / 32) * a.job[k].tiles_n; }
   a.tiles_total = a.job[0].ntiles + a.job[1].ntiles + a.job[2].ntiles;
   const int sm = a.nsplit * a.members;
   const int blocks = 8 * ((sm + 7) / 8) * a.tiles_total;
   ProfScope prof(PROF_WGRAD, st);
+  if (planes) return launch_wgrad_k<k_wgrad_f16>("k_wgrad_f16", a, blocks, st);
   // Split-precision job 0 in every bf16 mode (the operand split costs ~6 VALU instructions per value and term; with the
   // unmasked scalar-addressed row loop that still leaves a gain: per step at c2 0.058 ms fp32 job -> 0.052 bf16x3,
   // 0.044 bf16x2).
-  if (a.prec == PREC_F16X2 && a.eA != nullptr) {               // "f16x2": job 0 on the pre-split fp16 planes
-    if (a.rows_per_wave > 2048) return fail(MOBODY_E_ARG, "launch_wgrad: more than 64 row tiles per wave slice (raise nsplit)");
-    static bool once_h = false;
-    if (!once_h) {
-      int rc = allow_big_lds(k_wgrad_f16, lds);
-      if (rc) return rc;
-      once_h = true;
-    }
-    hipLaunchKernelGGL(k_wgrad_f16, dim3(blocks), dim3(NTHREADS), lds, st, a);
-    MB_LAUNCH_OK("k_wgrad_f16");
-    return 0;
-  }
-  if (a.prec != PREC_F32 && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide) {
-    static bool once_bf = false;
-    if (!once_bf) {
-      int rc = allow_big_lds(k_wgrad_bf<1>, lds);
-      if (!rc) rc = allow_big_lds(k_wgrad_bf<2>, lds);
-      if (!rc) rc = allow_big_lds(k_wgrad_bf<3>, lds);
-      if (rc) return rc;
-      once_bf = true;
-    }
-    if (a.prec == PREC_BF16) hipLaunchKernelGGL(k_wgrad_bf<1>, dim3(blocks), dim3(NTHREADS), lds, st, a);
-    else if (a.prec == PREC_BF16X2) hipLaunchKernelGGL(k_wgrad_bf<2>, dim3(blocks), dim3(NTHREADS), lds, st, a);
-    else hipLaunchKernelGGL(k_wgrad_bf<3>, dim3(blocks), dim3(NTHREADS), lds, st, a);
-    MB_LAUNCH_OK("k_wgrad_bf");
-    return 0;
-  }
-  hipLaunchKernelGGL(k_wgrad, dim3(blocks), dim3(NTHREADS), lds, st, a);
-  MB_LAUNCH_OK("k_wgrad");
-  return 0;
+  if (a.prec != PREC_F32 && a.job[0].ka == HID && a.job[0].nb == HID && a.job[0].wide)
+    return a.prec == PREC_BF16 ? launch_wgrad_k<k_wgrad_bf<1>>("k_wgrad_bf", a, blocks, st)
+         : a.prec == PREC_BF16X2 ? launch_wgrad_k<k_wgrad_bf<2>>("k_wgrad_bf", a, blocks, st) : launch_wgrad_k<k_wgrad_bf<3>>("k_wgrad_bf", a, blocks, st);
+  return launch_wgrad_k<k_wgrad>("k_wgrad", a, blocks, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1096,30 +1015,30 @@ __global__ __launch_bounds__(256) void k_grad_reduce(GradReduceArgs a) {
 }
 
 // dW1, dW2, dW3 (one merged split-K launch) + the deterministic slab / bias-partial reduction (optionally with the
-// optimizer step fused).  x_mstride: 0 = the input rows are shared by the members, rows*Kp1 = per-member inputs.
-int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstride, const float* h1, const float* h2,
-                      const float* dz3, const float* dz2, const float* dz1, long long rows, int nsplit, float* slabs,
-                      const float* dbp, int ntiles, float* grad, const LossFinal& loss, const AdamTarget& adam,
-                      hipStream_t st, int prec, const int* e_h1, const int* e_dz2, float* bc_ws) {
+// optimizer step fused).
+int mlp3_weight_grads(const Mlp3WgradArgs& a, hipStream_t st) {
+  const MobodyMlpLayout& L = a.L;
+  const long long rows = a.rows;
+  const bool planes = a.prec == PREC_F16X2 && a.e_h1 != nullptr;     // the exponents are read in the f16x2 mode alone
   WgradArgs g{};
-  g.prec = prec;
+  g.prec = a.prec;
   const long long rows32 = (rows + 31) & ~31LL;
-  g.eA = e_h1; g.eB = e_dz2; g.e_mstride = rows32 / 32; g.plane_stride = rows32 * HID;
+  g.eA = planes ? a.e_h1 : nullptr; g.eB = planes ? a.e_dz2 : nullptr; g.e_mstride = rows32 / 32; g.plane_stride = rows32 * HID;
   const long long slab_stride = (L.total_floats + 3) & ~3LL;
-  g.rows = rows; g.slabs = slabs; g.slab_stride = slab_stride; g.out_mstride = L.member_floats;
-  g.nsplit = nsplit; g.members = L.members;
+  g.rows = rows; g.slabs = a.slabs; g.slab_stride = slab_stride; g.out_mstride = L.member_floats;
+  g.nsplit = a.nsplit; g.members = L.members;
   const long long hs = rows * HID;
   // dW2 = h1^T dz2
-  g.job[0] = WgradJob{h1, hs, HID, HID, dz2, hs, HID, HID, L.w2, HID, HID, HID, 0, 1, 0, 0};
-  if (prec == PREC_F16X2 && e_h1 != nullptr) g.job[0].a_mstride = g.job[0].b_mstride = 2 * rows32 * HID;   // planes: 16-bit elements per member
+  g.job[0] = WgradJob{a.h1, hs, HID, HID, a.dz2, hs, HID, HID, L.w2, HID, HID, HID, 0, 1, 0, 0};
+  if (planes) g.job[0].a_mstride = g.job[0].b_mstride = 2 * rows32 * HID;   // planes: 16-bit elements per member
   // dW1 = x^T dz1
-  g.job[1] = WgradJob{x, x_mstride, L.Kp1, L.Kp1, dz1, hs, HID, HID, L.w1, HID, L.Kp1, HID, 0, 1, 0, 0};
+  g.job[1] = WgradJob{a.x, a.x_mstride, L.Kp1, L.Kp1, a.dz1, hs, HID, HID, L.w1, HID, L.Kp1, HID, 0, 1, 0, 0};
   // dW3^T = dz3^T h2, stored transposed into W3[256][Np3]
-  g.job[2] = WgradJob{dz3, rows * L.Np3, L.Np3, L.Np3, h2, hs, HID, HID, L.w3, L.Np3, L.Np3, HID, 1, 0, 0, 0};
-  GradReduceArgs r{L, slabs, slab_stride, nsplit, dbp, ntiles, grad, loss, adam, nullptr};
-  if (bc_ws != nullptr && adam.on && adam.t_dev != nullptr) {
-    g.bc_out = bc_ws; g.bc_t = adam.t_dev; g.bc_lr = adam.lr;
-    r.bc_dev = bc_ws;
+  g.job[2] = WgradJob{a.dz3, rows * L.Np3, L.Np3, L.Np3, a.h2, hs, HID, HID, L.w3, L.Np3, L.Np3, HID, 1, 0, 0, 0};
+  GradReduceArgs r{L, a.slabs, slab_stride, a.nsplit, a.dbp, a.ntiles, a.grad, a.loss, a.adam, nullptr};
+  if (a.bc_ws != nullptr && a.adam.on && a.adam.t_dev != nullptr) {
+    g.bc_out = a.bc_ws; g.bc_t = a.adam.t_dev; g.bc_lr = a.adam.lr;
+    r.bc_dev = a.bc_ws;
   }
   int rc = launch_wgrad(g, st);
   if (rc) return rc;

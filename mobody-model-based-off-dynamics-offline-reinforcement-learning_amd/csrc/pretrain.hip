@@ -568,48 +568,34 @@ __global__ __launch_bounds__(256) void k_pre_validate(const float* mean, const f
 // workspace carving
 // ------------------------------------------------------------------------------------------------
 struct PreWs {
-  float *enc_out, *sx_enc, *h1e, *h2e, *d1e, *d2e;
-  float *zt, *h1t, *h2t, *d1t, *d2t, *tr_out;
-  float *xrw, *sx_rw, *h1r, *h2r, *d1r, *d2r, *rw_out;
+  // 2b rows of the state encoder, 4b of the decoder (its x is the decoder's input zt, written by k_pre_latent_fwd, not a save),
+  // 2b of the reward head.  One record EACH, because the weight-gradient GEMM + reduction of the reward head and the decoder run
+  // on the side stream while the main stream's backward chain moves on to the next net
+  NetScratch enc, tr, rw;
+  float *enc_out, *tr_out, *xrw, *rw_out;
   float *dz3rw, *dz3tr, *dz3enc, *dfake, *dzt, *zap, *lossp, *fnz;
-  // backward operands of the three nets (0 reward head, 1 decoder, 2 state encoder): one set EACH, because the weight-gradient
-  // GEMM + reduction of nets 0 and 1 run on the side stream while the main stream's backward chain moves on to the next net
-  float *dz2[3], *dz1[3], *dbp[3], *slabs[3];
   float* bc;                                    // Adam bias corrections of a device step count, two floats per net (mlp3_weight_grads)
-  int *eh1e, *eh1t, *eh1r, *edz2[3];   // f16x2: scale exponents of the 32-row tiles of the h1 / dz2 planes (h1*, dz2 then hold planes)
   PreLossOff lo;
-  int nch, nsplit2, nsplit4, ntiles2, ntiles4;
+  int nch;
   long long total;
 };
 
+// a pre-training net's record: forward saves included, bias partials at least 32 outputs wide
+template <class Take>
+static NetScratch pre_net(const MobodyMlpLayout& L, long long rows, int np3, Take&& take) {
+  return carve_net(L, rows, true, np3 > 32 ? np3 : 32, take);
+}
+
 static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, PreWs& w) {
   const long long E = NENS, R2 = 2 * b, R4 = 4 * b;
-  const long long R2p = (R2 + 31) & ~31LL, R4p = (R4 + 31) & ~31LL;     // the fp16 planes of h1 / dz2 are padded to whole 32-row tiles
   const int S = L.S, A = L.A;
   long long off = 0;
   auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  w.enc_out = take(E * R2 * 32); w.sx_enc = take(E * R2 * L.enc.Kp1);
-  w.h1e = take(E * R2p * HID); w.h2e = take(E * R2 * HID); w.d1e = take(E * R2 * HID); w.d2e = take(E * R2 * HID);
-  w.zt = take(E * R4 * LATENT);
-  w.h1t = take(E * R4p * HID); w.h2t = take(E * R4 * HID); w.d1t = take(E * R4 * HID); w.d2t = take(E * R4 * HID);
-  w.tr_out = take(E * R4 * S);
-  w.xrw = take(E * R2 * (2 * S + A)); w.sx_rw = take(E * R2 * L.rw.Kp1);
-  w.h1r = take(E * R2p * HID); w.h2r = take(E * R2 * HID); w.d1r = take(E * R2 * HID); w.d2r = take(E * R2 * HID);
-  w.rw_out = take(E * R2 * 2);
+  static_assert(LATENT % 8 == 0, "the decoder's input rows zt are its weight-gradient operand x: Kp1 == LATENT");
+  w.enc = pre_net(L.enc, R2, L.tr.Np3, take); w.tr = pre_net(L.tr, R4, L.tr.Np3, take); w.rw = pre_net(L.rw, R2, L.tr.Np3, take);
+  w.enc_out = take(E * R2 * 32); w.tr_out = take(E * R4 * S); w.xrw = take(E * R2 * (2 * S + A)); w.rw_out = take(E * R2 * 2);
   w.dz3rw = take(E * R2 * 16); w.dz3tr = take(E * R4 * L.tr.Np3); w.dz3enc = take(E * R2 * 32);
-  const long long rows_of[3] = {R2, R4, R2}, rowsp_of[3] = {R2p, R4p, R2p};
-  for (int k = 0; k < 3; ++k) { w.dz2[k] = take(E * rowsp_of[k] * HID); w.dz1[k] = take(E * rows_of[k] * HID); }
   w.dfake = take(E * R2 * S); w.dzt = take(E * R4 * LATENT); w.fnz = take(E * b * S);
-  w.ntiles2 = (int)cdiv(R2, 32); w.ntiles4 = (int)cdiv(R4, 32);
-  w.eh1e = reinterpret_cast<int*>(take(E * w.ntiles2)); w.eh1r = reinterpret_cast<int*>(take(E * w.ntiles2));
-  w.eh1t = reinterpret_cast<int*>(take(E * w.ntiles4));
-  for (int k = 0; k < 3; ++k) w.edz2[k] = reinterpret_cast<int*>(take(E * (k == 1 ? w.ntiles4 : w.ntiles2)));
-  const long long per = 2 * HID + (L.tr.Np3 > 32 ? L.tr.Np3 : 32);
-  for (int k = 0; k < 3; ++k) w.dbp[k] = take((long long)(k == 1 ? w.ntiles4 : w.ntiles2) * E * per);
-  w.nsplit2 = wgrad_nsplit(R2, NENS); w.nsplit4 = wgrad_nsplit(R4, NENS);
-  w.slabs[0] = take(((L.rw.total_floats + 3) & ~3LL) * w.nsplit2);
-  w.slabs[1] = take(((L.tr.total_floats + 3) & ~3LL) * w.nsplit4);
-  w.slabs[2] = take(((L.enc.total_floats + 3) & ~3LL) * w.nsplit2);
   w.nch = (int)cdiv(b, LROWS);
   w.zap = take((long long)w.nch * E * L.za_member_floats);
   w.lo.n_lat = (int)(E * w.nch); w.lo.n_rt = (int)cdiv(E * b * S, 256); w.lo.n_rw = (int)cdiv(E * R2, 256);
@@ -620,28 +606,35 @@ static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, Pr
   return 0;
 }
 
-// per-member input rows [E][rows][n] and a per-member x save.  e1 != null (f16x2, and only then): W2's fp16 planes from the T
-// blob; h1 receives planes + tile exponents instead of fp32 rows
-static Mlp3FwdArgs pre_fwd_args(const float* blob, const MobodyMlpLayout& L, const float* src, int n, long long rows, float* out,
-                                float* sx, float* h1, float* h2, float* d1, float* d2, const float* blob_T = nullptr,
-                                int* e1 = nullptr) {
-  Mlp3FwdArgs a = fwd_net(blob, L, rows);
-  if (e1 != nullptr) fwd_set_planes(a, blob_T, L);
-  fwd_set_src(a, 0, src, n, n, rows * n);
+// The three launches of a pre-training net on its record.  f16 (the f16x2 mode, and only then): W2's / W2^T's fp16 planes from the
+// T blob; h1 and dz2 travel as planes + tile exponents instead of fp32 rows.
+// forward: per-member input rows src [E][rows][n], saved to s.x unless they are s.x
+static Mlp3FwdArgs pre_fwd_args(const float* blob, const float* blob_T, const MobodyMlpLayout& L, const float* src, int n, float* out,
+                                const NetScratch& s, bool f16) {
+  Mlp3FwdArgs a = fwd_net(blob, L, s.rows);
+  if (f16) fwd_set_planes(a, blob_T, L);
+  fwd_set_src(a, 0, src, n, n, s.rows * n);
   fwd_set_out(a, out, 0, 0.f);
-  fwd_set_saves(a, sx, rows * L.Kp1, h1, e1, h2, nullptr, nullptr, d1, d2);
+  fwd_set_saves(a, src == s.x ? nullptr : s.x, s.rows * L.Kp1, s.h1, f16 ? s.e_h1 : nullptr, s.h2, nullptr, nullptr, s.d1, s.d2);
   return a;
 }
-
-// Swish nets: d1 / d2 are the saved derivatives.  e2 != null (f16x2, and only then): prec and W2^T's planes from the T blob; dz2
-// leaves as planes + tile exponents
-static Mlp3BwdArgs pre_bwd_args(const MobodyMlpLayout& L, const float* blob_T, const float* dz3, const float* d1, const float* d2,
-                                long long rows, float* dz2, float* dz1, float* dbp, int* e2 = nullptr) {
-  Mlp3BwdArgs b = bwd_net(L, blob_T, rows);
-  if (e2 != nullptr) bwd_set_planes(b, L, PREC_F16X2);
-  bwd_set_acts(b, d1, d2, nullptr, nullptr, 1);
-  bwd_set_grads(b, dz3, dz2, dz1, dbp, e2);
+// backward (Swish nets: d1 / d2 are the saved derivatives); the caller adds dx
+static Mlp3BwdArgs pre_bwd_args(const MobodyMlpLayout& L, const float* blob_T, const float* dz3, const NetScratch& s, bool f16) {
+  Mlp3BwdArgs b = bwd_net(L, blob_T, s.rows);
+  if (f16) bwd_set_planes(b, L, PREC_F16X2);
+  bwd_set_acts(b, s.d1, s.d2, nullptr, nullptr, 1);
+  bwd_set_grads(b, dz3, s.dz2, s.dz1, s.dbp, f16 ? s.e_dz2 : nullptr);
   return b;
+}
+// weight gradients + reduction (+ the fused Adam step when adam.on)
+static Mlp3WgradArgs pre_wgrad_args(const MobodyMlpLayout& L, const float* dz3, const NetScratch& s, float* bc_ws, float* grad,
+                                    const AdamTarget& adam, int prec) {
+  Mlp3WgradArgs g = wgrad_net(L, s.rows, s.nsplit);
+  wgrad_set_saves(g, s.x, s.rows * L.Kp1, s.h1, s.h2, s.e_h1);
+  wgrad_set_grads(g, dz3, s.dz2, s.dz1, s.dbp, s.ntiles, s.e_dz2);
+  wgrad_set_scratch(g, s.slabs, bc_ws);
+  wgrad_set_result(g, grad, LossFinal{}, adam, prec);
+  return g;
 }
 
 }  // namespace mobody
@@ -779,7 +772,6 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
   PreWs w;
   pre_carve(L, b, a.workspace, w);
   hipStream_t st = as_stream(stream);
-  const long long R2 = 2 * b, R4 = 4 * b;
   PreRow r{};
   r.S = S; r.A = A; r.use_trg = use_trg; r.Np3tr = L.tr.Np3; r.b = b; r.inv_bg = 1.f / (float)a.b_global;
   r.ce = (use_trg ? 5.f : 1.f) * a.encoder_loss_coef; r.cr = (use_trg ? 1.f : 0.01f) * a.reward_coef; r.ct = a.transition_coef;
@@ -787,7 +779,7 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
   r.call_dev = (const long long*)a.call_dev;
   r.za = blob + (use_trg ? L.off_za_trg : L.off_za_src);
   r.za_mf = L.za_member_floats; r.za_w1 = L.za_w1; r.za_b1 = L.za_b1; r.za_w2 = L.za_w2; r.za_b2 = L.za_b2;
-  r.enc_out = w.enc_out; r.zt = w.zt; r.tr_out = w.tr_out; r.dz3tr = w.dz3tr; r.xrw = w.xrw; r.rw_out = w.rw_out;
+  r.enc_out = w.enc_out; r.zt = w.tr.x; r.tr_out = w.tr_out; r.dz3tr = w.dz3tr; r.xrw = w.xrw; r.rw_out = w.rw_out;
   r.dz3rw = w.dz3rw; r.dfake = w.dfake; r.dzt = w.dzt; r.dz3enc = w.dz3enc; r.zap = w.zap; r.lossp = w.lossp; r.fnz = w.fnz;
   const float *Penc = blob + L.off_enc, *Ptr = blob + L.off_tr, *Prw = blob + L.off_rw;
   const float *Tenc = blob_T + L.t_off_enc, *Ttr = blob_T + L.t_off_tr, *Trw = blob_T + L.t_off_rw;
@@ -795,16 +787,16 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
   // f32: k_mlp3_fwd_train; f16x2: the 256 x 256 layers of the three nets on the split core (mlp_fwd_bf.hip with derivative saves)
   auto forward = [&](const Mlp3FwdArgs& fa) { return launch_mlp3_forward(fa, NENS, ACT_SWISH, precision, st); };
   // ---- forward ----
-  rc = forward(pre_fwd_args(Penc, L.enc, xenc, S, R2, w.enc_out, w.sx_enc, w.h1e, w.h2e, w.d1e, w.d2e, Tenc, f16 ? w.eh1e : nullptr));
+  rc = forward(pre_fwd_args(Penc, Tenc, L.enc, xenc, S, w.enc_out, w.enc, f16));
   if (rc) return rc;
   const LatentLds ll = latent_lds(L.za_member_floats, A);
   hipLaunchKernelGGL(k_pre_latent_fwd, dim3((unsigned)w.nch, NENS), dim3(256), sizeof(float) * (size_t)ll.total, st, r, w.lo, ll);
   MB_LAUNCH_OK("k_pre_latent_fwd");
-  rc = forward(pre_fwd_args(Ptr, L.tr, w.zt, LATENT, R4, w.tr_out, nullptr, w.h1t, w.h2t, w.d1t, w.d2t, Ttr, f16 ? w.eh1t : nullptr));
+  rc = forward(pre_fwd_args(Ptr, Ttr, L.tr, w.tr.x, LATENT, w.tr_out, w.tr, f16));
   if (rc) return rc;
   hipLaunchKernelGGL(k_pre_trans_loss, dim3((unsigned)w.lo.n_rt), dim3(256), 0, st, r, w.lo);
   MB_LAUNCH_OK("k_pre_trans_loss");
-  rc = forward(pre_fwd_args(Prw, L.rw, w.xrw, 2 * S + A, R2, w.rw_out, w.sx_rw, w.h1r, w.h2r, w.d1r, w.d2r, Trw, f16 ? w.eh1r : nullptr));
+  rc = forward(pre_fwd_args(Prw, Trw, L.rw, w.xrw, 2 * S + A, w.rw_out, w.rw, f16));
   if (rc) return rc;
   PreSide* side = nullptr;
   rc = pre_side(&side);
@@ -819,28 +811,24 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
   hipLaunchKernelGGL(k_pre_reward_seed, dim3((unsigned)w.lo.n_rw), dim3(256), 0, st, r, w.lo);
   MB_LAUNCH_OK("k_pre_reward_seed");
   {
-    Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.d1r, w.d2r, R2, w.dz2[0], w.dz1[0], w.dbp[0], f16 ? w.edz2[0] : nullptr);
+    Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.rw, f16);
     bw.dx = w.dfake; bw.dx_c0 = S + A; bw.dx_n = S;
     rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (!rc) rc = fork(0);
     if (rc) return rc;
-    rc = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0], w.dbp[0],
-                           w.ntiles2, gptr(L.off_rw), LossFinal{}, region_adam(L.off_rw, L.t_off_rw), st2, precision,
-                           f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr, w.bc);
+    rc = mlp3_weight_grads(pre_wgrad_args(L.rw, w.dz3rw, w.rw, w.bc, gptr(L.off_rw), region_adam(L.off_rw, L.t_off_rw), precision), st2);
     if (rc) return rc;
   }
   hipLaunchKernelGGL(k_pre_fake_bwd, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
   MB_LAUNCH_OK("k_pre_fake_bwd");
   // ---- decoder ----
   {
-    Mlp3BwdArgs bw = pre_bwd_args(L.tr, Ttr, w.dz3tr, w.d1t, w.d2t, R4, w.dz2[1], w.dz1[1], w.dbp[1], f16 ? w.edz2[1] : nullptr);
+    Mlp3BwdArgs bw = pre_bwd_args(L.tr, Ttr, w.dz3tr, w.tr, f16);
     bw.dx = w.dzt; bw.dx_c0 = 0; bw.dx_n = LATENT;
     rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (!rc) rc = fork(1);
     if (rc) return rc;
-    rc = mlp3_weight_grads(L.tr, w.zt, R4 * LATENT, w.h1t, w.h2t, w.dz3tr, w.dz2[1], w.dz1[1], R4, w.nsplit4, w.slabs[1], w.dbp[1],
-                           w.ntiles4, gptr(L.off_tr), LossFinal{}, region_adam(L.off_tr, L.t_off_tr), st2, precision,
-                           f16 ? w.eh1t : nullptr, f16 ? w.edz2[1] : nullptr, w.bc + 2);
+    rc = mlp3_weight_grads(pre_wgrad_args(L.tr, w.dz3tr, w.tr, w.bc + 2, gptr(L.off_tr), region_adam(L.off_tr, L.t_off_tr), precision), st2);
     if (rc) return rc;
   }
   // ---- latent level + action encoder ----
@@ -858,12 +846,10 @@ static int pretrain_impl(const MobodyPretrain& a, void* stream) {
   }
   // ---- state encoder ----
   {
-    Mlp3BwdArgs bw = pre_bwd_args(L.enc, Tenc, w.dz3enc, w.d1e, w.d2e, R2, w.dz2[2], w.dz1[2], w.dbp[2], f16 ? w.edz2[2] : nullptr);
+    Mlp3BwdArgs bw = pre_bwd_args(L.enc, Tenc, w.dz3enc, w.enc, f16);
     rc = launch_mlp3_bwd(bw, NENS, false, st);
     if (rc) return rc;
-    rc = mlp3_weight_grads(L.enc, w.sx_enc, R2 * L.enc.Kp1, w.h1e, w.h2e, w.dz3enc, w.dz2[2], w.dz1[2], R2, w.nsplit2, w.slabs[2], w.dbp[2],
-                           w.ntiles2, gptr(L.off_enc), LossFinal{}, region_adam(L.off_enc, L.t_off_enc), st, precision,
-                           f16 ? w.eh1e : nullptr, f16 ? w.edz2[2] : nullptr, w.bc + 4);
+    rc = mlp3_weight_grads(pre_wgrad_args(L.enc, w.dz3enc, w.enc, w.bc + 4, gptr(L.off_enc), region_adam(L.off_enc, L.t_off_enc), precision), st);
     if (rc) return rc;
   }
   // the step ends when both streams have: the main one waits for the side one
@@ -1105,40 +1091,22 @@ __global__ __launch_bounds__(256) void k_mopo_loss_final(const float* lossp, Pre
 }
 
 struct MopoWs {
-  float *sx_d, *h1d, *h2d, *d1d, *d2d, *f;
-  float *xrw, *sx_rw, *h1r, *h2r, *d1r, *d2r, *rw_out;
+  NetScratch dyn, rw;                           // the MLP (b rows), the reward head (2b rows)
+  float *f, *xrw, *rw_out;
   float *dz3rw, *dz3d, *dfake, *fnz, *lossp;
-  float *dz2[2], *dz1[2], *dbp[2], *slabs[2];   // 0 reward head (2b rows), 1 MLP (b rows)
   float* bc;                                    // Adam bias corrections of a device step count, two floats per net (mlp3_weight_grads)
-  int *eh1d, *eh1r, *edz2[2];
   PreLossOff lo;
-  int nsplit1, nsplit2, ntiles1, ntiles2;
   long long total;
 };
 
 static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* base, MopoWs& w) {
   const long long E = NENS, R1 = b, R2 = 2 * b;
-  const long long R1p = (R1 + 31) & ~31LL, R2p = (R2 + 31) & ~31LL;
   const int S = L.S, A = L.A;
   long long off = 0;
   auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  w.sx_d = take(E * R1 * L.dyn.Kp1);
-  w.h1d = take(E * R1p * HID); w.h2d = take(E * R1 * HID); w.d1d = take(E * R1 * HID); w.d2d = take(E * R1 * HID);
-  w.f = take(E * R1 * S);
-  w.xrw = take(E * R2 * (2 * S + A)); w.sx_rw = take(E * R2 * L.rw.Kp1);
-  w.h1r = take(E * R2p * HID); w.h2r = take(E * R2 * HID); w.d1r = take(E * R2 * HID); w.d2r = take(E * R2 * HID);
-  w.rw_out = take(E * R2 * 2);
+  w.dyn = pre_net(L.dyn, R1, L.dyn.Np3, take); w.rw = pre_net(L.rw, R2, L.rw.Np3, take);
+  w.f = take(E * R1 * S); w.xrw = take(E * R2 * (2 * S + A)); w.rw_out = take(E * R2 * 2);
   w.dz3rw = take(E * R2 * 16); w.dz3d = take(E * R1 * L.dyn.Np3); w.dfake = take(E * R2 * S); w.fnz = take(E * R1 * S);
-  w.dz2[0] = take(E * R2p * HID); w.dz1[0] = take(E * R2 * HID);
-  w.dz2[1] = take(E * R1p * HID); w.dz1[1] = take(E * R1 * HID);
-  w.ntiles1 = (int)cdiv(R1, 32); w.ntiles2 = (int)cdiv(R2, 32);
-  w.eh1d = reinterpret_cast<int*>(take(E * w.ntiles1)); w.eh1r = reinterpret_cast<int*>(take(E * w.ntiles2));
-  w.edz2[0] = reinterpret_cast<int*>(take(E * w.ntiles2)); w.edz2[1] = reinterpret_cast<int*>(take(E * w.ntiles1));
-  w.dbp[0] = take((long long)w.ntiles2 * E * (2 * HID + (L.rw.Np3 > 32 ? L.rw.Np3 : 32)));
-  w.dbp[1] = take((long long)w.ntiles1 * E * (2 * HID + (L.dyn.Np3 > 32 ? L.dyn.Np3 : 32)));
-  w.nsplit1 = wgrad_nsplit(R1, NENS); w.nsplit2 = wgrad_nsplit(R2, NENS);
-  w.slabs[0] = take(((L.rw.total_floats + 3) & ~3LL) * w.nsplit2);
-  w.slabs[1] = take(((L.dyn.total_floats + 3) & ~3LL) * w.nsplit1);
   w.lo.n_lat = 0; w.lo.lat = 0;
   w.lo.n_rt = (int)cdiv(E * R1 * S, 256); w.lo.n_rw = (int)cdiv(E * R2, 256);
   w.lo.rt = 0; w.lo.rw = 2LL * w.lo.n_rt;
@@ -1212,7 +1180,6 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
   MopoWs w;
   mopo_carve(L, b, a.workspace, w);
   hipStream_t st = as_stream(stream);
-  const long long R2 = 2 * b;
   const float ce = (use_trg ? 5.f : 1.f) * a.encoder_loss_coef, cr = use_trg ? 1.f : 0.01f, inv_bg = 1.f / (float)a.b_global;
   MopoRow r{};
   r.S = S; r.A = A; r.Np3 = L.dyn.Np3; r.b = b; r.inv_bg = inv_bg; r.ce = ce;
@@ -1226,7 +1193,7 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
   auto forward = [&](const Mlp3FwdArgs& fa) { return launch_mlp3_forward(fa, NENS, ACT_SWISH, precision, st); };
   // ---- forward: the MLP on [s, a] (b rows per member), the row kernel, the reward head on 2b rows ----
   {
-    Mlp3FwdArgs fa = pre_fwd_args(Pd, L.dyn, xenc, S, b, w.f, w.sx_d, w.h1d, w.h2d, w.d1d, w.d2d, Td, f16 ? w.eh1d : nullptr);
+    Mlp3FwdArgs fa = pre_fwd_args(Pd, Td, L.dyn, xenc, S, w.f, w.dyn, f16);
     fwd_set_src(fa, 0, xenc, S, S, 2 * b * S);          // the s rows of xenc (its s' rows follow in each member's block)
     fwd_set_src(fa, 1, act, A, A, b * A);
     rc = forward(fa);
@@ -1234,13 +1201,13 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
   }
   hipLaunchKernelGGL(k_mopo_rows, dim3((unsigned)w.lo.n_rt), dim3(256), 0, st, r);
   MB_LAUNCH_OK("k_mopo_rows");
-  rc = forward(pre_fwd_args(Prw, L.rw, w.xrw, 2 * S + A, R2, w.rw_out, w.sx_rw, w.h1r, w.h2r, w.d1r, w.d2r, Trw, f16 ? w.eh1r : nullptr));
+  rc = forward(pre_fwd_args(Prw, Trw, L.rw, w.xrw, 2 * S + A, w.rw_out, w.rw, f16));
   if (rc) return rc;
   // ---- backward: reward head (input gradient = d loss / d fake) ----
   hipLaunchKernelGGL(k_pre_reward_seed, dim3((unsigned)w.lo.n_rw), dim3(256), 0, st, pr, w.lo);
   MB_LAUNCH_OK("k_pre_reward_seed");
   {
-    Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.d1r, w.d2r, R2, w.dz2[0], w.dz1[0], w.dbp[0], f16 ? w.edz2[0] : nullptr);
+    Mlp3BwdArgs bw = pre_bwd_args(L.rw, Trw, w.dz3rw, w.rw, f16);
     bw.dx = w.dfake; bw.dx_c0 = S + A; bw.dx_n = S;
     rc = launch_mlp3_bwd(bw, NENS, true, st);
     if (rc) return rc;
@@ -1253,18 +1220,14 @@ static int pretrain_mopo_impl(const MobodyPretrainMopo& a, void* stream) {
     return fail(MOBODY_E_LAUNCH, "mopo pre-training: fork onto the side stream failed");
   // from here on every exit goes through the join below, error or not
   auto after_fork = [&]() -> int {
-    int rc2 = mlp3_weight_grads(L.rw, w.sx_rw, R2 * L.rw.Kp1, w.h1r, w.h2r, w.dz3rw, w.dz2[0], w.dz1[0], R2, w.nsplit2, w.slabs[0],
-                                w.dbp[0], w.ntiles2, gptr(L.off_rw), LossFinal{}, region_adam(L.off_rw, L.t_off_rw), st2, precision,
-                                f16 ? w.eh1r : nullptr, f16 ? w.edz2[0] : nullptr, w.bc);
+    int rc2 = mlp3_weight_grads(pre_wgrad_args(L.rw, w.dz3rw, w.rw, w.bc, gptr(L.off_rw), region_adam(L.off_rw, L.t_off_rw), precision), st2);
     if (rc2) return rc2;
     hipLaunchKernelGGL(k_mopo_dmu, dim3((unsigned)cdiv(b * S, 256)), dim3(256), 0, st, r);
     MB_LAUNCH_OK("k_mopo_dmu");
-    Mlp3BwdArgs bw = pre_bwd_args(L.dyn, Td, w.dz3d, w.d1d, w.d2d, b, w.dz2[1], w.dz1[1], w.dbp[1], f16 ? w.edz2[1] : nullptr);
+    Mlp3BwdArgs bw = pre_bwd_args(L.dyn, Td, w.dz3d, w.dyn, f16);
     rc2 = launch_mlp3_bwd(bw, NENS, false, st);
     if (rc2) return rc2;
-    return mlp3_weight_grads(L.dyn, w.sx_d, b * L.dyn.Kp1, w.h1d, w.h2d, w.dz3d, w.dz2[1], w.dz1[1], b, w.nsplit1, w.slabs[1],
-                             w.dbp[1], w.ntiles1, gptr(L.off_dyn), LossFinal{}, region_adam(L.off_dyn, L.t_off_dyn), st, precision,
-                             f16 ? w.eh1d : nullptr, f16 ? w.edz2[1] : nullptr, w.bc + 2);
+    return mlp3_weight_grads(pre_wgrad_args(L.dyn, w.dz3d, w.dyn, w.bc + 2, gptr(L.off_dyn), region_adam(L.off_dyn, L.t_off_dyn), precision), st);
   };
   rc = after_fork();
   if (hipEventRecord(side->join, st2) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)

@@ -4,13 +4,14 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "layers.h"
 #include "tile.h"
 #include "tile_bf.h"
 #include "health.h"
 
 namespace mobody {
 
-// Row-wise quantities of the actor update (mobody.py:246-276, 314-345) shared by the seed prologues of k_mlp3_bwd.
+// Row-wise quantities of the actor update (mobody.py:246-276, 314-345) shared by the two seed prologues of k_actor_bwd_chain.
 struct ActorRowArgs {
   const float *qp, *qb, *stats, *pi, *act, *dxa;
   const float* v_true;       // [Nt] V(s_true) when config['advantage'] (else null)
@@ -42,6 +43,9 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //      lossp[2*tile] = sum -min q, lossp[2*tile+1] = sum w*(pi-a)^2
 // Modes 1 and 3 also store dz3 to `dz3_out` (the weight-gradient GEMM reads it).  Modes 1 and 2 seed column 0 of a
 // one-output net only: the kernel forms dz3 W3^T as the rank-1 product it is instead of running the K = Np3 GEMM.
+// Where each runs: launch_mlp3_bwd (k_mlp3_bwd) takes modes 0 and 1 and chooses between them at run time; modes 2 and 3 exist
+// only as the two tiles of launch_actor_bwd_chain (k_actor_bwd_chain), compiled in, with mode 2's dx / bcw handed to mode 3 in
+// agent-scope stores and loads.
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
@@ -319,13 +323,50 @@ struct GradReduceArgs {
   const float* bc_dev;  // {step_size, bc2_sqrt} of adam.t_dev[0], formed by the weight-gradient launch in front, or null
 };
 int launch_grad_reduce(const GradReduceArgs& a, hipStream_t st);
-// prec 4: h1 / dz2 point at the saved fp16 planes and e_h1 / e_dz2 at their tile exponents (else null)
-// bc_ws: two floats of workspace (or null).  With a fused optimizer step on a device step count, the weight-gradient launch
-// leaves the bias corrections there and k_grad_reduce takes them as a uniform load instead of forming them behind a barrier.
-int mlp3_weight_grads(const MobodyMlpLayout& L, const float* x, long long x_mstride, const float* h1, const float* h2,
-                      const float* dz3, const float* dz2, const float* dz1, long long rows, int nsplit, float* slabs,
-                      const float* dbp, int ntiles, float* grad, const LossFinal& loss, const AdamTarget& adam,
-                      hipStream_t st, int prec = 0, const int* e_h1 = nullptr, const int* e_dz2 = nullptr, float* bc_ws = nullptr);
+// dW1, dW2, dW3 of one packed MLP (one merged split-K launch) + the deterministic slab / bias-partial reduction, optionally with
+// the optimizer step fused.
+struct Mlp3WgradArgs {
+  MobodyMlpLayout L;
+  long long rows;
+  int nsplit;              // split-K factor the slabs were sized for (wgrad_nsplit)
+  const float* x;          // what the forward saved: [.][rows][Kp1] input rows; x_mstride 0 = shared by the members, rows * Kp1 = per member
+  long long x_mstride;
+  const float *h1, *h2;    // [members][rows][256]
+  const int* e_h1;         // f16x2: h1 holds the saved fp16 planes, e_h1 their 32-row tiles' exponents (read in that mode only)
+  const float *dz3, *dz2, *dz1;    // what the backward left (Mlp3BwdArgs); f16x2: dz2 holds planes, e_dz2 their exponents
+  const float* dbp;
+  int ntiles;              // row tiles of dbp
+  const int* e_dz2;
+  float* slabs;            // scratch: [nsplit] partial slabs in the gradient-blob layout
+  float* bc_ws;            // two floats of workspace (or null).  With a fused optimizer step on a device step count, the weight-gradient
+                           // launch leaves the bias corrections there and k_grad_reduce takes them as a uniform load instead of forming
+                           // them behind a barrier.
+  float* grad;             // result: the gradient blob (may be null when adam.on), the loss scalars (kind 0: none), the fused step
+  LossFinal loss;
+  AdamTarget adam;
+  int prec;
+};
+int mlp3_weight_grads(const Mlp3WgradArgs& a, hipStream_t st);
+
+// ---- host side: the one place an Mlp3WgradArgs is filled, one helper per group of fields (as for Mlp3BwdArgs above) ----
+inline Mlp3WgradArgs wgrad_net(const MobodyMlpLayout& L, long long rows, int nsplit) {
+  Mlp3WgradArgs g{};
+  g.L = L; g.rows = rows; g.nsplit = nsplit;
+  return g;
+}
+// e_h1 / e_dz2 (below): the exponent arrays of the f16x2 mode.  Callers pass them whatever the precision: mlp3_weight_grads reads
+// them in the f16x2 mode alone, every other mode takes h1 / dz2 as fp32 rows.
+inline void wgrad_set_saves(Mlp3WgradArgs& g, const float* x, long long x_mstride, const float* h1, const float* h2, const int* e_h1 = nullptr) {
+  g.x = x; g.x_mstride = x_mstride; g.h1 = h1; g.h2 = h2; g.e_h1 = e_h1;
+}
+inline void wgrad_set_grads(Mlp3WgradArgs& g, const float* dz3, const float* dz2, const float* dz1, const float* dbp, int ntiles,
+                            const int* e_dz2 = nullptr) {
+  g.dz3 = dz3; g.dz2 = dz2; g.dz1 = dz1; g.dbp = dbp; g.ntiles = ntiles; g.e_dz2 = e_dz2;
+}
+inline void wgrad_set_scratch(Mlp3WgradArgs& g, float* slabs, float* bc_ws) { g.slabs = slabs; g.bc_ws = bc_ws; }
+inline void wgrad_set_result(Mlp3WgradArgs& g, float* grad, const LossFinal& loss, const AdamTarget& adam, int prec) {
+  g.grad = grad; g.loss = loss; g.adam = adam; g.prec = prec;
+}
 
 // split-K factor (workgroups along the row dimension) used for a batch of `rows`: 24 output tiles x nsplit x members
 // workgroups should reach ~3 per CU (768), so a one-member net splits twice as fine as a twin net
@@ -336,6 +377,36 @@ inline int wgrad_nsplit(long long rows, int members) {
   if (s > cap) s = cap;
   while (rows > 2048LL * 4 * s) s *= 2;             // a wave's row slice spans at most 64 tiles of 32 rows (wgrad_tile_f16)
   return (int)s;
+}
+
+// The training scratch of one net: what its forward saves (x .. d2, e_h1: only in a record carved with them -- the pre-training
+// nets; Swish derivatives d1 / d2), what its backward leaves and what its weight-gradient launch needs.  h1 and dz2 of a record with
+// saves span rows32 rows: in the f16x2 mode they hold fp16 planes of whole 32-row tiles (same bytes) and e_h1 / e_dz2 the tiles'
+// exponents.
+struct NetScratch {
+  float *x, *h1, *h2, *d1, *d2;
+  float *dz2, *dz1, *dbp, *slabs;
+  int *e_h1, *e_dz2;
+  long long rows, rows32;
+  int nsplit, ntiles;
+};
+// take(n) hands out n floats of the workspace (or null while it is only being sized).  dbp_np3: the output width the bias partials
+// are sized for (>= L.Np3).
+template <class Take>
+inline NetScratch carve_net(const MobodyMlpLayout& L, long long rows, bool saves, int dbp_np3, Take&& take) {
+  NetScratch s{};
+  const long long M = L.members;
+  s.rows = rows; s.rows32 = (rows + 31) & ~31LL;
+  s.ntiles = (int)cdiv(rows, MLP_TILE_ROWS); s.nsplit = wgrad_nsplit(rows, L.members);
+  if (saves) {
+    s.x = take(M * rows * L.Kp1);
+    s.h1 = take(M * s.rows32 * HID); s.h2 = take(M * rows * HID); s.d1 = take(M * rows * HID); s.d2 = take(M * rows * HID);
+    s.e_h1 = reinterpret_cast<int*>(take(M * s.ntiles)); s.e_dz2 = reinterpret_cast<int*>(take(M * s.ntiles));
+  }
+  s.dz2 = take(M * (saves ? s.rows32 : rows) * HID); s.dz1 = take(M * rows * HID);
+  s.dbp = take((long long)s.ntiles * M * (2 * HID + dbp_np3));
+  s.slabs = take(((L.total_floats + 3) & ~3LL) * s.nsplit);
+  return s;
 }
 
 }  // namespace mobody

@@ -223,13 +223,18 @@ static Mlp3FwdArgs fwd_args(const float* blob, const MobodyMlpLayout& L, const f
   return a;
 }
 
-// weight gradients of one packed MLP: one merged split-K launch + the deterministic reduction
-static int weight_grads(const MobodyMlpLayout& L, const float* x, const float* h1, const float* h2, const float* dz3,
-                        const float* dz2, const float* dz1, long long rows, const TrainWs& w, float* grad,
-                        const LossFinal& loss, const AdamTarget& adam, hipStream_t st, int prec = 0, const int* e_h1 = nullptr) {
-  return mlp3_weight_grads(L, x, 0, h1, h2, dz3, dz2, dz1, rows, L.members == 1 ? w.nsplit_a : w.nsplit_q, w.slabs, w.dbp,
-                           w.ntiles, grad, loss, adam, st, prec, prec == PREC_F16X2 ? e_h1 : nullptr, prec == PREC_F16X2 ? w.edz2 : nullptr,
-                           w.bc + (L.members == 1 ? 2 : 0));
+// weight gradients of one packed MLP: one merged split-K launch + the deterministic reduction.  The critic (two members) and the
+// actor (one) take turns on the same dz2 / dz1 / dbp / slabs.
+static int weight_grads(const MobodyMlpLayout& L, const float* x, const float* h1, const float* h2, const int* e_h1, const float* dz3,
+                        long long rows, const TrainWs& w, float* grad, const LossFinal& loss, const AdamTarget& adam, int prec,
+                        hipStream_t st) {
+  const bool actor = L.members == 1;
+  Mlp3WgradArgs g = wgrad_net(L, rows, actor ? w.nsplit_a : w.nsplit_q);
+  wgrad_set_saves(g, x, 0, h1, h2, e_h1);
+  wgrad_set_grads(g, dz3, w.dz2, w.dz1, w.dbp, w.ntiles, w.edz2);
+  wgrad_set_scratch(g, w.slabs, w.bc + (actor ? 2 : 0));
+  wgrad_set_result(g, grad, loss, adam, prec);
+  return mlp3_weight_grads(g, st);
 }
 
 // the train step's ReLU nets: always the W2^T planes and `prec`; e2 != null in the f16 mode: dz2 receives fp16 planes + tile
@@ -330,7 +335,7 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   if (rc) return rc;
   LossFinal lf{};                                  // q_loss = mse(q1,y)+mse(q2,y), local share of the global mean
   lf.kind = 1; lf.nparts = 2 * w.ntiles; lf.scale = invNg; lf.parts = w.lossp; lf.out = a.loss_out;
-  return weight_grads(w.Lq, w.xq, w.h1q, w.h2q, w.dz3q, w.dz2, w.dz1, N, w, a.grad_q, lf, adam, st, prec, w.eh1q);
+  return weight_grads(w.Lq, w.xq, w.h1q, w.h2q, w.eh1q, w.dz3q, N, w, a.grad_q, lf, adam, prec, st);
 }
 
 extern "C" int mobody_critic(const MobodyCritic* a, void* stream) {
@@ -427,7 +432,7 @@ static int actor_backward_impl(const MobodyActor& a, void* stream) {
   LossFinal lf{};                                  // loss_out[0] = p_w*mean(-q) + bc_coef*L_BC, [1] = L_BC (local shares)
   lf.kind = 2; lf.nparts = w.ntiles; lf.scale_q = h->scale_q; lf.weight = h->weight; lf.bc_coef = h->bc_coef;
   lf.ng = (float)ra.Ng; lf.ntg_a = (float)ra.Ntg * (float)ra.A; lf.parts = w.lossp; lf.stats = a.stats; lf.out = a.loss_out;
-  return weight_grads(w.La, w.xa, w.h1a, w.h2a, w.dz3a, w.dz2, w.dz1, N, w, a.grad_actor, lf, adam, st, h->precision, w.eh1a);
+  return weight_grads(w.La, w.xa, w.h1a, w.h2a, w.eh1a, w.dz3a, N, w, a.grad_actor, lf, adam, h->precision, st);
 }
 
 extern "C" int mobody_actor_backward(const MobodyActor* a, void* stream) {

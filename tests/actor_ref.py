@@ -109,7 +109,7 @@ def actor_grads_ref(pa, s, fw, dz3):
     return grads, tape
 
 
-# ---- launch formulas (csrc/core.hip mobody_mlp_layout, csrc/mlp_bwd.hip launch_bwd_masks / launch_bwd_bf, train.hip) ----
+# ---- launch formulas (csrc/core.hip mobody_mlp_layout, csrc/mlp_bwd.hip dispatch_dx_nt, train.hip) ----
 def bwd_dx_nt(S, A):
     """NT of the frozen-Q backward's input-gradient instance k_mlp3_bwd<true, NT, ...>: Np1t = round_up(S + A, 16)."""
     np1t = (S + A + 15) // 16 * 16
