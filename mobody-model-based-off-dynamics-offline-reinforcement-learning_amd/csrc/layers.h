@@ -231,6 +231,17 @@ int launch_mlp3_forward_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3Fw
 int launch_mlp3_fwd_bf_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3FwdArgs& b, int members_b, const FwdGather& fg,
                               int prec, hipStream_t st);
 
+// All forwards of a gathering critic step: q = twin-Q(s,a) with saves, pn = pi(s'), qt = target twin-Q(s', pi(s')) reading pn's
+// output, pi = pi(s) with saves or null.  One launch where the merged kernel exists (f16x2, the pairs the gathering kernels
+// cover, [s' | a'] rows that fit behind the image: critic_fwd_bf.hip k_critic_fwd_bf); otherwise launch_mlp3_forward_gather(q, pn)
+// and then launch_mlp3_forward(qt, pi): same results, bit for bit.
+int launch_critic_forward_gather(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi,
+                                 const FwdGather& fg, int prec, hipStream_t st);
+int launch_critic_fwd_bf(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi, const FwdGather& fg,
+                         hipStream_t st);
+size_t critic_fwd_bf_lds(int S, int A);          // LDS bytes of a k_critic_fwd_bf workgroup
+constexpr size_t CRITIC_FWD_LDS_MAX = 40 * 1024; // four workgroups per CU
+
 // Row-tile height of the fused 3-layer MLP kernels (forward and backward; the callers size the bias partials and the sign
 // words by it).  Measured on MI355X (bench.py, S=17/A=6): 32-row tiles (33 KB LDS, ~124 VGPRs -> 4 workgroups = 16 waves
 // per CU) beat 64-row tiles (2 workgroups per CU) at every batch size from 2.5 k to 41 k rows (forward 84 vs 73 TFLOP/s at
@@ -259,8 +270,12 @@ __device__ __forceinline__ int fwd_load_sources(const Mlp3FwdArgs& a, int m, flo
 // the first LDS store.  Only the chunks that hold the tile's own columns travel: [off, off + n) for the twin-Q tiles,
 // [off, off + n + 2) for the pi(s') tile, which also owes reward and not_done (they follow next_state in the ring row) and
 // stores them straight from the registers.  Xs ends up as tile_load2 / tile_load leave it: rows past the batch are zero.
-template <int NQ>
-__device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here) {
+// The pi(s) tile of the merged critic forward (critic_fwd_bf.hip) reads the state columns alone (FWD_COLS_STATE: the first
+// g.S columns of net a's part of the row) and owes no minibatch array; where that launch evaluates pi(s') of a row block twice,
+// the second copy fetches the same chunks and leaves reward / not_done to the first (`owes` false).
+enum FwdGatherCols { FWD_COLS_NET = 0, FWD_COLS_STATE = 1 };
+template <int NQ, int COLS = FWD_COLS_NET>
+__device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here, bool owes = true) {
   const GatherArgs& g = fg.g;
   const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4;
   const long long N = g.start[g.nbuf];
@@ -271,7 +286,7 @@ __device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second
     const long long src = gather_src(g, r, k);
     mine = g.bufs[k].state + src * g.bufs[k].pitch;
   }
-  const int off = second ? fg.off[1] : fg.off[0], n = second ? fg.n[1] : fg.n[0];
+  const int off = second ? fg.off[1] : fg.off[0], n = COLS == FWD_COLS_STATE ? g.S : second ? fg.n[1] : fg.n[0];
   const int q0 = off >> 2, q1 = (off + n + (second ? 2 : 0) + 3) >> 2;      // this tile's chunks of the row
   v4f v[2][NQ];
 #pragma unroll
@@ -292,20 +307,21 @@ __device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second
       for (int e = 0; e < 4; ++e) {
         const int c = 4 * q + e - off;
         if (c >= 0 && c < n) Xs[r * LDX + c] = ok ? v[p][j][e] : 0.f;
-        if (second && ok && c == n) g.reward[row0 + r] = v[p][j][e];
-        if (second && ok && c == n + 1) g.not_done[row0 + r] = v[p][j][e];
+        if (second && ok && owes && c == n) g.reward[row0 + r] = v[p][j][e];
+        if (second && ok && owes && c == n + 1) g.not_done[row0 + r] = v[p][j][e];
       }
     }
   }
 }
 
 // Returns the width of the input tile, as fwd_load_sources.  One thread of the launch advances the bump words.
-__device__ __forceinline__ int fwd_gather_tile(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here) {
+template <int COLS = FWD_COLS_NET>
+__device__ __forceinline__ int fwd_gather_tile(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here, bool owes = true) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     for (int k = 0; k < fg.g.nbump; ++k) fg.g.bump[k][0] += 1;
-  const int off = second ? fg.off[1] : fg.off[0], n = second ? fg.n[1] : fg.n[0];
-  if (((off + n + (second ? 2 : 0) + 3) >> 2) - (off >> 2) <= 16) fwd_gather_rows<1>(fg, second, Xs, row0, rows_here);
-  else fwd_gather_rows<FWD_GATHER_NQ>(fg, second, Xs, row0, rows_here);
+  const int off = second ? fg.off[1] : fg.off[0], n = COLS == FWD_COLS_STATE ? fg.g.S : second ? fg.n[1] : fg.n[0];
+  if (((off + n + (second ? 2 : 0) + 3) >> 2) - (off >> 2) <= 16) fwd_gather_rows<1, COLS>(fg, second, Xs, row0, rows_here, owes);
+  else fwd_gather_rows<FWD_GATHER_NQ, COLS>(fg, second, Xs, row0, rows_here, owes);
   return n;
 }
 

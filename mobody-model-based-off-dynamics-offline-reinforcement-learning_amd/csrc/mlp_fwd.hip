@@ -210,6 +210,41 @@ int launch_mlp3_forward_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3Fw
   return prec == PREC_F32 ? launch_fwd2_gather(a, members_a, b, members_b, fg, st) : launch_mlp3_fwd_bf_gather(a, members_a, b, members_b, fg, prec, st);
 }
 
+// The merged launch takes what the f16x2 gathering kernel takes (launch_mlp3_forward_gather, `built`) when target-Q reads
+// exactly pi(s')'s rows and outputs and a tile's [s' | a'] rows fit behind the image at four workgroups per CU (S + A <= 59:
+// ant, 111 + 8, and pen, 45 + 24, stay on two launches).
+static bool critic_forward_merges(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi, const FwdGather& fg,
+                                  int prec) {
+#ifdef MOBODY_TWO_CRITIC_FWD
+  return false;                                    // A/B aid (build.py MOBODY_EXTRA_FLAGS): the two launches this one replaces
+#else
+  const GatherArgs& g = fg.g;
+  const long long N = g.start[g.nbuf];
+  auto chunks = [](int off, int n) { return ((off + n + 3) >> 2) - (off >> 2); };
+  if (prec != PREC_F16X2 || N <= 0 || q.rows != N || pn.rows != N || qt.rows != N || (pi != nullptr && pi->rows != N)) return false;
+  for (int k = 0; k < g.nbuf; ++k)
+    if (!g.packed[k] && g.start[k + 1] > g.start[k]) return false;
+  if (fg.off[0] != 0 || fg.n[0] != g.S + g.A || fg.off[1] != g.S + g.A || fg.n[1] != g.S) return false;
+  if (q.Np3 != 16 || qt.Np3 != 16 || (pn.Np3 != 16 && pn.Np3 != 32) || chunks(0, g.S + g.A) > 16 * FWD_GATHER_NQ ||
+      chunks(g.S + g.A, g.S + 2) > 16 * FWD_GATHER_NQ)
+    return false;
+  // target-Q is the twin-Q of [next_state | pn's output], whole rows, no saves; pi(s') is a plain tanh actor
+  if (qt.Kp1 != q.Kp1 || qt.n[0] != g.S || qt.n[1] != g.A || qt.n[2] != 0 || qt.src[1] != pn.out || pn.nout != g.A ||
+      pn.out_ld != g.A || pn.resid != nullptr || qt.save_x || qt.save_h1 || qt.save_h1p || qt.save_h2 || qt.mask1 || qt.mask2)
+    return false;
+  if (pi != nullptr && (pi->Np3 != pn.Np3 || pi->Kp1 != pn.Kp1 || pi->n[0] != g.S || pi->n[1] + pi->n[2] != 0)) return false;
+  return critic_fwd_bf_lds(g.S, g.A) <= CRITIC_FWD_LDS_MAX;
+#endif
+}
+
+int launch_critic_forward_gather(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi,
+                                 const FwdGather& fg, int prec, hipStream_t st) {
+  if (critic_forward_merges(q, pn, qt, pi, fg, prec)) return launch_critic_fwd_bf(q, pn, qt, pi, fg, st);
+  int rc = launch_mlp3_forward_gather(q, 2, pn, 1, fg, prec, st);
+  if (rc) return rc;
+  return pi != nullptr ? launch_mlp3_forward(qt, 2, *pi, 1, ACT_RELU, prec, st) : launch_mlp3_forward(qt, 2, ACT_RELU, prec, st);
+}
+
 }  // namespace mobody
 
 using namespace mobody;

@@ -5,78 +5,9 @@
 // planes kept in the T blob and writes an fp32 image for the output layer.
 #include <stdlib.h>
 
-#include "common.h"
-#include "layers_bf.h"
+#include "fwd_bf_tile.h"
 
 namespace mobody {
-
-constexpr int TB = MLP_TILE_ROWS, MT = MLP_MT;  // rows of a workgroup's tile; 32 x 32 MFMA row tiles per wave
-constexpr int FWD_L1_RING = 3;                  // layer 1 is K = 24 .. 120: a short ring keeps the kernel at 128 registers
-constexpr int FWD_F16_WAVES = 4;                // waves per SIMD the f16x2 inference forward is compiled for (launch bounds)
-
-// DS: training forward of a Swish net -- save_d1 / save_d2 receive the derivatives next to h1 (planes or rows) / h2
-// GATHER: the input tile comes straight from the replay rings (layers.h fwd_gather_tile); fg / second: the stage's arguments and
-// which net of the pair this tile belongs to
-template <int ACT, int PM, int NT, bool DS = false, bool GATHER = false>
-__device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, float* Xs, const FwdGather* fg = nullptr, bool second = false) {
-  char* Ps = reinterpret_cast<char*>(Xs);
-  float* scr = reinterpret_cast<float*>(Ps + split_scr_offset<PM, TB>());
-  const long long row0 = (long long)blockIdx.x * TB;
-  const int rows_here = (int)min((long long)TB, a.rows - row0);
-  const bool full = rows_here == TB;
-  const float* w1 = a.w1 + m * a.sw1;
-  const s16x8* w2b = reinterpret_cast<const s16x8*>(a.w2_planes + m * a.planes_ms);
-  const float* w3 = a.w3 + m * a.sw3;
-  const float* b3 = a.b3 + m * a.sb3;
-  TR(0);
-  WideRingT<FWD_L1_RING> ring;
-  wide_prefetch(w1, a.Kp1, ring);
-  int c0;
-  if constexpr (GATHER) {
-    c0 = fwd_gather_tile(*fg, second, Xs, row0, rows_here);
-  } else if (a.n[0] <= 32 && a.n[1] <= 32 && a.n[2] == 0) {       // state | action: both sources in one round trip
-    tile_load2<TB>(Xs, a.src[0] + m * a.src_ms[0] + row0 * a.ld[0], a.ld[0], a.n[0],
-                   a.n[1] > 0 ? a.src[1] + m * a.src_ms[1] + row0 * a.ld[1] : nullptr, a.ld[1], a.n[1], rows_here);
-    c0 = a.n[0] + a.n[1];
-  } else {
-    c0 = fwd_load_sources(a, m, Xs, row0, rows_here);
-  }
-  tile_zero_cols(Xs, c0, a.Kp1, TB);
-  lds_barrier();
-  TR(1);
-  fwd_save_x(a, m, Xs, row0, rows_here);
-  if constexpr (GATHER) fwd_gather_save(*fg, second, m, Xs, row0, rows_here);
-  const FwdTileOut t = fwd_tile_out(a, m, row0);
-  float* d1 = DS ? a.save_d1 + ((long long)m * a.rows + row0) * HID : nullptr;
-  float* d2 = DS ? a.save_d2 + ((long long)m * a.rows + row0) * HID : nullptr;
-  const int mg = (rows_here + 31) / 32;
-  BfRing<PM> bring;
-  PlaneSave gs{nullptr, 0, nullptr};
-  if (a.save_h1p != nullptr) {
-    gs.base = reinterpret_cast<short*>(a.save_h1p) + m * a.h1p_ms + (row0 / 8) * (HID * 8);
-    gs.plane_stride = a.h1p_plane;
-    gs.e_out = a.save_e1 + (long long)m * cdiv(a.rows, 32) + row0 / 32;
-  }
-  const int e1 = wide_layer_to_planes<ACT, MT, PM, TB, DS>(Xs, Ps, scr, w1, a.b1 + m * a.sb1, a.Kp1, ring,
-                                                           [&] { bf_prefetch<PM>(w2b, bring); }, t.mask1, full, mg, rows_here, t.h1, gs, d1);
-  TR(2);
-  auto emit = [&](int row, int col, float v, float bias) { fwd_emit(a, t.out, row0, rows_here, row, col, v, bias); };
-  if constexpr (NT > 0) {
-    NarrowRegs<NT> br;
-    const int mycol = threadIdx.x % (16 * NT);
-    float bias;
-    bf_layer<ACT, MT, PM, TB, DS>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [&] {
-      narrow_prefetch<NT>(w3, 16 * NT, br);
-      bias = b3[mycol < a.nout ? mycol : 0];
-    }, t.mask2, mg, rows_here, t.h2, d2);
-    TR(4);
-    narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
-  } else {
-    bf_layer<ACT, MT, PM, TB, DS>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [] {}, t.mask2, mg, rows_here, t.h2, d2);
-    narrow_layer(Xs, w3, HID, a.Np3, [&](int row, int col, float v) { emit(row, col, v, b3[col < a.nout ? col : 0]); }, TB);
-  }
-  TR(5);
-}
 
 // one or two independent networks per launch (blockIdx.y < members_a -> net a), as k_mlp3_fwd2
 // NT / NT2: output-layer width (16-column tiles; 0 = any) of net a / net b -- a twin-Q (one output) and an actor with more than

@@ -305,23 +305,25 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
     // forwards already enqueued by the phase-1 call
   } else if (q_next == nullptr) {
     const Mlp3FwdArgs fpn = fwd_args(a.actor_blob, w.La, next_state, S, nullptr, 0, N, w.pin, 1, h->max_action, nullptr, nullptr, nullptr, nullptr, nullptr, aT);
-    if (gather != nullptr) {
-      FwdGather fg = *gather;
-      fwd_set_gather(fg, 0, fq, 0);                // state | action open the ring row, next_state follows them
-      fwd_set_gather(fg, 1, fpn, S + A);
-      rc = launch_mlp3_forward_gather(fq, 2, fpn, 1, fg, prec, st);
-    } else {
-      rc = launch_mlp3_forward(fq, 2, fpn, 1, ACT_RELU, prec, st);
-    }
     // target twin-Q(s', a') (:192) -- and, when the caller asks for it, pi(s) of the coming actor phase in the same
     // launch: the actor is not updated in between, and a twin-Q launch alone is 2.5 workgroups per CU where the
     // merged one is 3.75 (the actor phase then opens with Q(s_t,a_t) alone: exactly 2 per CU)
     const Mlp3FwdArgs ft = fwd_args(a.qtarg_blob, w.Lq, next_state, S, w.pin, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
-    if (!rc && a.policy_forward)
-      rc = launch_mlp3_forward(ft, 2, fwd_args(a.actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
-                                               prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
-    else if (!rc)
-      rc = launch_mlp3_forward(ft, 2, ACT_RELU, prec, st);
+    Mlp3FwdArgs fpi{};
+    if (a.policy_forward)
+      fpi = fwd_args(a.actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                     prec == PREC_F16X2 ? w.eh1a : nullptr);
+    if (gather != nullptr) {
+      // all of them in one launch where target-Q's workgroups can evaluate pi(s') of their own rows (layers.h)
+      FwdGather fg = *gather;
+      fwd_set_gather(fg, 0, fq, 0);                // state | action open the ring row, next_state follows them
+      fwd_set_gather(fg, 1, fpn, S + A);
+      rc = launch_critic_forward_gather(fq, fpn, ft, a.policy_forward ? &fpi : nullptr, fg, prec, st);
+    } else {
+      rc = launch_mlp3_forward(fq, 2, fpn, 1, ACT_RELU, prec, st);
+      if (!rc && a.policy_forward) rc = launch_mlp3_forward(ft, 2, fpi, 1, ACT_RELU, prec, st);
+      else if (!rc) rc = launch_mlp3_forward(ft, 2, ACT_RELU, prec, st);
+    }
   } else {
     rc = launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);                  // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229)
   }
