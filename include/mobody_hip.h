@@ -457,6 +457,18 @@ typedef struct MobodyActor {
 int mobody_actor_forward(const MobodyActor* a, void* stream);
 int mobody_actor_backward(const MobodyActor* a, void* stream);
 
+/* TD3_BC actor phase (the reference's td3_bc.py update_policy :160-176) on the same MobodyActor block, workspace and call order as
+ * the pair above (mobody_critic serves TD3_BC's critic update as it is).  BC runs on EVERY row against the batch's own actions,
+ * weighted -- when h.q_weighted (the reference's config['advantage'] == 1) -- by w = min(exp(q/m), 100), q = min Q(s, pi(s)) the
+ * policy term uses, m = stats[0]/N_global; q is not detached inside w, so the BC loss also reaches the actor through the frozen Q.
+ *   mobody_td3bc_actor_forward    pi(s) unless policy_ready, ONE twin-Q forward Q(s, pi(s)), stats[0] = sum|q|, stats[1] = 0
+ *                                 (no Q(s_t, a_t) forward: N twin-Q rows fewer than mobody_actor_forward)
+ *   mobody_td3bc_actor_backward   grad_actor or, fused, the Adam step (same rule, t / t_dev as above); loss_out as above
+ * Refused with MOBODY_E_ARG before any runtime call: d.Nt != d.N, d.Nt_global != d.N_global, v_true != NULL, h.scale_q != 1,
+ * d.A > 24.  With h.q_weighted == 0 the results are the bits of the pair above at q_weighted = 0, scale_q = 1, Nt = N. */
+int mobody_td3bc_actor_forward(const MobodyActor* a, void* stream);
+int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream);
+
 /* Expectile loss of the V function (update_v_function, mobody.py:231-242): adv = min(qt[0],qt[1]) - v;
  * dz3[N][16] column 0 = dL_V/dV (1/N_global scaling), loss_out[0] = local share of L_V; lossp_ws: ceil(N/256) floats. */
 int mobody_value_loss_grad(const float* qt, const float* v, int64_t N, int64_t N_global, float* dz3, float* loss_out,

@@ -185,6 +185,8 @@ PROTOTYPES = {
     "mobody_critic": (C.c_int, [C.POINTER(MobodyCritic), vp]),
     "mobody_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_td3bc_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_td3bc_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),

@@ -2,19 +2,20 @@
 
 `call_algo(algo_name, config, mode, device, **kwargs)` lower-cases the name, looks the class up
 and returns `cls(config, device)`; `mode` and kwargs are accepted and ignored exactly as the
-reference does.  Unknown names raise KeyError like the reference's dict lookup.  The baseline
-algorithms (dara, bosa, iql, td3_bc, igdf) are outside the accelerated path.
+reference does.  Unknown names raise KeyError like the reference's dict lookup.  Of the baseline
+algorithms TD3_BC is built (`offline_offline/td3_bc.py`); dara, bosa, iql and igdf are outside the accelerated path.
 """
 from .offline_offline.mobody import MOBODY
+from .offline_offline.td3_bc import TD3BC
 
-_BASELINES = ("dara", "bosa", "iql", "td3_bc", "igdf")
+_BASELINES = ("dara", "bosa", "iql", "igdf")
 
 
 def call_algo(algo_name, config, mode, device, **kwargs):
     algo_name = algo_name.lower()
-    algo_to_call = {"mobody": MOBODY}
+    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC}
     if algo_name in _BASELINES:
         raise NotImplementedError(f"'{algo_name}' is a reference baseline outside the MI355X-accelerated path; "
-                                  "only 'mobody' is built here")
+                                  "only 'mobody' and 'td3_bc' are built here")
     algo = algo_to_call[algo_name]          # KeyError for unknown names, as in the reference
     return algo(config, device)

@@ -148,13 +148,14 @@ __device__ __forceinline__ void wide_store_colsum(f32x16 (&acc)[MT][2], float* X
   cs[1] += __shfl_xor(cs[1], 32);
 }
 
-// Seed prologue (BwdSeed modes 1-3).  SEED is the seed form of the tile: SEED_RT = k_mlp3_bwd, whose launch carries mode 0 (dz3
-// from memory, no prologue) or mode 1 and chooses at run time; 2 and 3 = the two tiles of k_actor_bwd_chain, known at compile
-// time.  Modes 1 and 2 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) -- the kernel forms the rank-1
-// product dz3 W3^T from them; mode 3 fills Xs[r][0..Np3).  All global loads of a pass are independent (one round trip); the loss
-// partials are reduced through `red` (static LDS, 8 floats).  `tile` is the row tile (row0 / TB).  Mode 2's bcw (and dx) are
-// handed to the mode-3 tile of the same rows within the launch: mode 2 stores them write-through (agent scope), mode 3 loads
-// them at agent scope -- past its CU's L1 -- and a row's loads stay on words its own tile has published.
+// Seed prologue (BwdSeed modes 1-4).  SEED is the seed form of the tile: SEED_RT = k_mlp3_bwd, whose launch carries mode 0 (dz3
+// from memory, no prologue) or mode 1 and chooses at run time; 2 or 4 and 3 = the two tiles of k_actor_bwd_chain, known at compile
+// time.  Modes 1, 2 and 4 (one-output nets) leave the TB seed values of column 0 in Xs[0..TB) -- the kernel forms the rank-1
+// product dz3 W3^T from them -- with one thread per row (1, 2) or eight (4, which also sums the row's (pi - a)^2); modes 2 and 4
+// return there, they have no loss partials.  Mode 3 fills Xs[r][0..Np3).  All global loads of a pass are independent (one round
+// trip); the loss partials are reduced through `red` (static LDS, 8 floats).  `tile` is the row tile (row0 / TB).  Mode 2's / 4's
+// bcw (and dx) are handed to the mode-3 tile of the same rows within the launch: they store them write-through (agent scope), mode 3
+// loads them at agent scope -- past its CU's L1 -- and a row's loads stay on words its own tile has published.
 constexpr int SEED_RT = -1;
 __device__ __forceinline__ void agent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float agent_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -165,7 +166,40 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   const int Np3 = a.Np3;
   const int t = threadIdx.x;
   float l0 = 0.f, l1 = 0.f;
-  if constexpr (SEED != 3) {                          // modes 1 and 2: one thread per row
+  if constexpr (SEED == 4) {                          // mode 4: eight threads per row (TB * 8 == NTHREADS)
+    static_assert(MLP_TILE_ROWS * 8 == NTHREADS, "mode 4 spreads a row's A <= 24 action columns over eight lanes");
+    // sq = sum_j (pi - a)^2 needs A words of pi and of act per row: lane `sub` of a row's eight takes columns sub, sub + 8,
+    // sub + 16 (A <= 24, checked by the launcher), all requested beside q0, q1 and stats[0] -- one round trip -- and the eight
+    // partial sums meet in three shuffles.  (pi is the policy forward's output of an earlier launch: plain loads.)
+    const ActorRowArgs& r = sd.ar;
+    const int rr = t >> 3, sub = t & 7;
+    const bool ok = rr < rows_here;
+    const long long row = row0 + (ok ? rr : 0);
+    const float *pp = r.pi + row * r.A, *ap = r.act + row * r.A;
+    float pv[3], av[3];
+#pragma unroll
+    for (int u = 0; u < 3; ++u) { const int j = sub + 8 * u, jc = j < r.A ? j : 0; pv[u] = pp[jc]; av[u] = ap[jc]; }
+    const float q0 = r.qp[row], q1 = r.qp[r.N + row];
+    const float c = -policy_weight(r) / (float)r.Ng;
+    float sq = 0.f;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) if (sub + 8 * u < r.A) { const float df = pv[u] - av[u]; sq += df * df; }
+    sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
+    float dq = c, w = 1.f;
+    if (r.h.q_weighted) {                             // w = min(exp(k q / m), 100) with its gradient through q (td3_bc.py:166-170)
+      const float mean = r.stats[0] / (float)r.Ng;
+      const float e = expf(sd.exp_scale * (fminf(q0, q1) / mean));
+      w = fminf(e, 100.f);
+      const float gw = r.h.bc_coef * (sd.exp_scale * e / mean) * sq / ((float)r.Ng * (float)r.A);
+      dq = e <= 100.f ? c + gw : c;                   // a select: above the clamp e may be inf, and inf * 0 would seed a NaN
+    }
+    if (sub == 0) {
+      const float g0 = q0 < q1 ? 1.f : (q0 == q1 ? 0.5f : 0.f);
+      Xs[rr] = ok ? dq * (m == 0 ? g0 : 1.f - g0) : 0.f;
+      if (m == 0 && ok) agent_store(r.bcw + row, w);  // every row is a BC row (Nt == N)
+    }
+    return;                                           // no loss partials
+  } else if constexpr (SEED != 3) {                   // modes 1 and 2: one thread per row
     if (t < TB) {
       const bool ok = t < rows_here;
       const long long row = row0 + (ok ? t : 0);
@@ -288,8 +322,8 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
   // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
   // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
   // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
-  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : SEED == 2;
-  constexpr bool with_db = SEED != 2;
+  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4);
+  constexpr bool with_db = SEED != 2 && SEED != 4;
   const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
   if (!rank1) wide_prefetch(w3t, a.Np3, ring);    // weight fragments travel while the seed rows are fetched
@@ -452,12 +486,13 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
 // ------------------------------------------------------------------------------------------------
 // PARAMETER ORDER: `q` first, `pi` directly behind it -- the body reads `pi` at offset sizeof(Mlp3BwdArgs) of the kernel-argument
 // segment (see there); a parameter put in front of `pi` moves it.
-template <int NT, int PM>
+// SQ: the seed form of the frozen-Q tile -- 2 (MOBODY) or 4 (the TD3_BC actor update, train.h BwdSeed)
+template <int NT, int PM, int SQ>
 __global__ __launch_bounds__(NTHREADS, 3) void k_actor_bwd_chain(Mlp3BwdArgs q, Mlp3BwdArgs pi, int* tickets) {
   __shared__ float red[8];
   extern __shared__ __attribute__((aligned(16))) float Xs[];
   const int tile = blockIdx.x;
-  mlp3_bwd_tile<true, NT, 1, PM, 2>(q, blockIdx.y, tile, 2, Xs, red);
+  mlp3_bwd_tile<true, NT, 1, PM, SQ>(q, blockIdx.y, tile, 2, Xs, red);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's write-through dx (and bcw) stores are done
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -480,31 +515,39 @@ __global__ __launch_bounds__(NTHREADS, 3) void k_actor_bwd_chain(Mlp3BwdArgs q, 
   mlp3_bwd_tile<false, 0, 1, PM, 3>(*(const Mlp3BwdArgs*)ka, 0, tile, 1, Xs, red);
 }
 
-template <int NT, int PM>
+template <int NT, int PM, int SQ>
 static int launch_chain_t(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
   constexpr size_t lds = split_lds_bytes<(PM > 0 ? PM : 1), MLP_TILE_ROWS>();
   static bool once = false;
   if (!once) {
-    int rc = allow_big_lds(k_actor_bwd_chain<NT, PM>, lds);
+    int rc = allow_big_lds(k_actor_bwd_chain<NT, PM, SQ>, lds);
     if (rc) return rc;
     once = true;
   }
   dim3 grid((unsigned)cdiv(q.rows, MLP_TILE_ROWS), 2u);
   ProfScope prof(PROF_MLP_BWD, st);
-  hipLaunchKernelGGL((k_actor_bwd_chain<NT, PM>), grid, dim3(NTHREADS), lds, st, q, pi, tickets);
+  hipLaunchKernelGGL((k_actor_bwd_chain<NT, PM, SQ>), grid, dim3(NTHREADS), lds, st, q, pi, tickets);
   MB_LAUNCH_OK("k_actor_bwd_chain");
   return 0;
 }
 template <int PM>
 static int launch_chain_nt(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
-  return dispatch_dx_nt(q.Np1t, true, [&](auto, auto nt) { return launch_chain_t<decltype(nt)::value, PM>(q, pi, tickets, st); });
+  return dispatch_dx_nt(q.Np1t, true, [&](auto, auto nt) {
+    // (mode 2 named first: the instances are emitted in the order they are named here, and with the mode-4 instance in front of
+    //  its mode-2 sibling the SAME machine code of k_actor_bwd_chain<2, 4, 2> ran 1.9 us per launch slower at another address:
+    //  the c2 step 0.1992 ms against 0.1966 ms this way round and 0.1978 ms before mode 4 existed)
+    return q.seed.mode != 4 ? launch_chain_t<decltype(nt)::value, PM, 2>(q, pi, tickets, st)
+                            : launch_chain_t<decltype(nt)::value, PM, 4>(q, pi, tickets, st);
+  });
 }
 
-// q: the frozen twin-Q pass (seed mode 2, dx out), pi: the actor's pass (seed mode 3) on the same rows; both with sign words and
+// q: the frozen twin-Q pass (seed mode 2, or 4 = TD3_BC; dx out), pi: the actor's pass (seed mode 3) on the same rows; both with sign words and
 // the same precision.  tickets: one zeroed int per row tile.  The precision picks the instance as in launch_mlp3_bwd.
 int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st) {
   if (q.rows <= 0) return 0;
-  MB_REQUIRE(q.seed.mode == 2 && pi.seed.mode == 3 && q.rows == pi.rows && q.prec == pi.prec && tickets != nullptr &&
+  MB_REQUIRE(q.seed.mode != 4 || (q.seed.ar.A <= 24 && q.seed.ar.Nt == q.seed.ar.N),
+             "launch_actor_bwd_chain: seed mode 4 spreads A <= 24 action columns over eight lanes and weights every row (A=%d)", q.seed.ar.A);
+  MB_REQUIRE((q.seed.mode == 2 || q.seed.mode == 4) && pi.seed.mode == 3 && q.rows == pi.rows && q.prec == pi.prec && tickets != nullptr &&
              q.m1 && q.m2 && pi.m1 && pi.m2 && !q.swish && !pi.swish && (q.w2t_planes != nullptr) == (pi.w2t_planes != nullptr),
              "launch_actor_bwd_chain: the two passes do not form an actor update");
   if (q.prec != PREC_F32 && q.w2t_planes != nullptr)

@@ -41,16 +41,22 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //      this mode stores no bias-gradient partials (`dbp` is not written).
 //   3  actor: d(pre-tanh) = (dxa[0]+dxa[1] + bc_coef*2*w*(pi-a)/(Ntg*A)) * max_action*(1-tanh^2);
 //      lossp[2*tile] = sum -min q, lossp[2*tile+1] = sum w*(pi-a)^2
+//   4  frozen twin-Q of the TD3_BC actor update (td3_bc.py:160-176), in mode 2's place: every row is a BC row (Nt == N) and the
+//      BC weight w = min(e, 100), e = exp(k q/m), q = min(q0,q1), m = stats[0]/N_global (detached), carries a gradient through q:
+//        dq = -(weight/m)/N_global + (q_weighted && e <= 100 ? bc_coef * (k e/m) * sum_j (pi-a)^2 / (N_global*A) : 0)
+//        dz3[m][row][0] = dq * d min(q0,q1)/dq_m (ties as mode 2);  member 0 writes bcw[row] = q_weighted ? w : 1
+//      k = `exp_scale`.  The clamp's gradient is a select (e overflows to inf past q/m = 88).  The actor tile behind it is mode 3.
 // Modes 1 and 3 also store dz3 to `dz3_out` (the weight-gradient GEMM reads it).  Modes 1 and 2 seed column 0 of a
 // one-output net only: the kernel forms dz3 W3^T as the rank-1 product it is instead of running the K = Np3 GEMM.
 // Where each runs: launch_mlp3_bwd (k_mlp3_bwd) takes modes 0 and 1 and chooses between them at run time; modes 2 and 3 exist
 // only as the two tiles of launch_actor_bwd_chain (k_actor_bwd_chain), compiled in, with mode 2's dx / bcw handed to mode 3 in
-// agent-scope stores and loads.
+// agent-scope stores and loads; mode 4 is mode 2's alternative as the first tile (the chain's third template argument).
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
-  float gamma, inv_ng;
-  ActorRowArgs ar;                           // modes 2, 3
+  union { float gamma; float exp_scale; };   // mode 1: the discount; mode 4: the exponent scale k of the BC weight
+  float inv_ng;
+  ActorRowArgs ar;                           // modes 2, 3, 4
   float* dz3_out;
   float* lossp;
 };

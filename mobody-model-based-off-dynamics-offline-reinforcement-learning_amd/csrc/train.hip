@@ -253,6 +253,9 @@ static Mlp3BwdArgs bwd_args(const MobodyMlpLayout& L, const float* blob_T, const
 
 using namespace mobody;
 
+// exponent scale of TD3_BC's BC weight exp(1 * q / mean|q|) (td3_bc.py:167; MOBODY's bc_weight has 3)
+static constexpr float TD3BC_EXP_SCALE = 1.f;
+
 extern "C" int64_t mobody_train_workspace(const MobodyTrainDims* d) {
   if (check_dims(d, "mobody_train_workspace")) return -1;
   TrainWs w;
@@ -361,9 +364,8 @@ extern "C" int mobody_critic(const MobodyCritic* a, void* stream) {
   return critic_impl(*a, &fg, stream);
 }
 
-extern "C" int mobody_actor_forward(const MobodyActor* a, void* stream) {
-  const char* who = "mobody_actor_forward";
-  MB_BLOCK(who, a, MobodyActor);
+// td3bc: the TD3_BC form (the entry point has checked Nt == N, no v_true, scale_q) -- no Q(s_t, a_t) forward and no second statistic
+static int actor_forward_impl(const MobodyActor* a, void* stream, const char* who, bool td3bc) {
   const MobodyTrainDims* d = &a->d;
   const MobodyHyper* h = &a->h;
   int rc = check_dims(d, who);
@@ -378,28 +380,41 @@ extern "C" int mobody_actor_forward(const MobodyActor* a, void* stream) {
   rc = carve(*d, a->workspace, w);
   if (rc) return rc;
   hipStream_t st = as_stream(stream);
-  const long long N = d->N, Nt = d->Nt;
+  const long long N = d->N, Nt = td3bc ? 0 : d->Nt;
   const int S = d->S, A = d->A;
   // Q(s_true, a_true) for the BC weights (:251) and pi(s) on the whole mixed batch (its first Nt rows are
   // pi(s_true), mobody.py:249,315) in one launch -- unless the critic call already left pi(s) in the workspace
   const Mlp3FwdArgs fb = fwd_args(q_blob, w.Lq, state, S, a->action, A, Nt, w.qb, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, qT);
   // Q(s, pi(s)) with the freshly updated critic (:316); dQ/da through the frozen net needs only the ReLU signs
   const Mlp3FwdArgs fp = fwd_args(q_blob, w.Lq, state, S, w.pi, A, N, w.q, 0, 1.f, nullptr, nullptr, nullptr, w.mq1, w.mq2, qT);
-  if (a->policy_ready) {
+  const auto policy = [&] {
+    return fwd_args(a->actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                    prec == PREC_F16X2 ? w.eh1a : nullptr);
+  };
+  if (td3bc) {                                      // TD3_BC (td3_bc.py:161-163): pi(s), then Q(s, pi(s)) alone
+    if (!a->policy_ready) rc = launch_mlp3_forward(policy(), 1, ACT_RELU, prec, st);
+    if (!rc) rc = launch_mlp3_forward(fp, 2, ACT_RELU, prec, st);
+  } else if (a->policy_ready) {
     rc = launch_mlp3_forward(fb, 2, fp, 2, ACT_RELU, prec, st);                 // both on the same critic: one launch of N + Nt rows (0.384 -> 0.380 ms/step)
   } else {
-    rc = launch_mlp3_forward(fb, 2, fwd_args(a->actor_blob, w.La, state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
-                                             prec == PREC_F16X2 ? w.eh1a : nullptr), 1, ACT_RELU, prec, st);
+    rc = launch_mlp3_forward(fb, 2, policy(), 1, ACT_RELU, prec, st);
     if (!rc) rc = launch_mlp3_forward(fp, 2, ACT_RELU, prec, st);
   }
   if (rc) return rc;
+  // (Nt = 0: stats[1] = 0 and qb is not read)
   hipLaunchKernelGGL(k_actor_stats, dim3(1), dim3(1024), 0, st, w.q, w.qb, N, Nt, a->stats, w.tickets, w.ntiles);
   MB_LAUNCH_OK("k_actor_stats");
   return 0;
 }
 
-static int actor_backward_impl(const MobodyActor& a, void* stream) {
-  const char* who = "mobody_actor_backward";
+extern "C" int mobody_actor_forward(const MobodyActor* a, void* stream) {
+  const char* who = "mobody_actor_forward";
+  MB_BLOCK(who, a, MobodyActor);
+  return actor_forward_impl(a, stream, who, false);
+}
+
+// td3bc: the TD3_BC form (seed mode 4 in the frozen-Q tile; the entry point has checked Nt == N, no v_true, scale_q)
+static int actor_backward_impl(const MobodyActor& a, void* stream, const char* who = "mobody_actor_backward", bool td3bc = false) {
   const MobodyTrainDims* d = &a.d;
   const MobodyHyper* h = &a.h;
   const bool fused = a.m != nullptr;
@@ -423,7 +438,8 @@ static int actor_backward_impl(const MobodyActor& a, void* stream) {
   // dq -> d(action) through the frozen twin-Q (parameters get no gradient, mobody.py:555-556); the prologue forms
   // -p_w/N d min(q1,q2) and the BC weights
   Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, nullptr, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, h->precision);
-  bq.seed.mode = 2; bq.seed.ar = ra;
+  bq.seed.mode = td3bc ? 4 : 2; bq.seed.ar = ra;
+  if (td3bc) bq.seed.exp_scale = TD3BC_EXP_SCALE;
   bq.dx = w.dxa; bq.dx_c0 = d->S; bq.dx_n = d->A;
   // actor: d(pre-tanh) from both members' dx and the BC term in the prologue, then the actor's own backward -- in the same
   // launch: a tile's actor backward runs in the second of the tile's two frozen-Q workgroups to finish
@@ -443,6 +459,33 @@ extern "C" int mobody_actor_backward(const MobodyActor* a, void* stream) {
   MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
   MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
   return actor_backward_impl(*a, stream);
+}
+
+// ---- TD3_BC actor phase (td3_bc.py:160-176): BC on every row, weighted by min(exp(1 * q/mean|q|), 100) of the SAME Q the policy
+// term uses, with the gradient through the weight.  One Q forward fewer than MOBODY's actor phase (no Q(s_t, a_t)). ----
+static int td3bc_check(const MobodyActor* a, const char* who) {
+  MB_BLOCK(who, a, MobodyActor);
+  MB_REQUIRE(a->d.Nt == a->d.N, "%s: d.Nt %lld != d.N %lld (the BC term runs on every row)", who, (long long)a->d.Nt, (long long)a->d.N);
+  MB_REQUIRE(a->d.Nt_global == a->d.N_global, "%s: d.Nt_global %lld != d.N_global %lld", who, (long long)a->d.Nt_global, (long long)a->d.N_global);
+  MB_REQUIRE(a->v_true == nullptr, "%s: v_true given: the weight is exp(q/mean|q|) of Q(s, pi(s)), there is no V function", who);
+  MB_REQUIRE(a->h.scale_q == 1, "%s: h.scale_q %d != 1 (the policy term is always weight / mean|Q|)", who, a->h.scale_q);
+  MB_REQUIRE(a->d.A <= 24, "%s: d.A %d > 24", who, a->d.A);
+  return 0;
+}
+
+extern "C" int mobody_td3bc_actor_forward(const MobodyActor* a, void* stream) {
+  const char* who = "mobody_td3bc_actor_forward";
+  int rc = td3bc_check(a, who);
+  return rc ? rc : actor_forward_impl(a, stream, who, true);
+}
+
+extern "C" int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream) {
+  const char* who = "mobody_td3bc_actor_backward";
+  int rc = td3bc_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
+  return actor_backward_impl(*a, stream, who, true);
 }
 
 extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,

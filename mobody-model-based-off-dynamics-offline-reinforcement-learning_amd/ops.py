@@ -313,6 +313,27 @@ def actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, a
     check(load().mobody_actor_backward(C.byref(blk), cur_stream()), "mobody_actor_backward")
 
 
+# TD3_BC actor phase: the same block and workspace, its own two entry points (no v_true; every row is a BC row)
+def td3bc_actor_forward(dims, hyp, actor_blob, q_blob, state, action, stats, ws, policy_ready=False, actor_blob_T=None, q_blob_T=None):
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.policy_ready = int(bool(policy_ready))
+    check(load().mobody_td3bc_actor_forward(C.byref(blk), cur_stream()), "mobody_td3bc_actor_forward")
+
+
+def td3bc_actor_backward(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, grad_actor, loss_out, ws):
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.grad_actor, blk.loss_out = ptr(grad_actor), ptr(loss_out)
+    check(load().mobody_td3bc_actor_backward(C.byref(blk), cur_stream()), "mobody_td3bc_actor_backward")
+
+
+def td3bc_actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, m, v, t, lr, loss_out, ws,
+                       t_dev=None):
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
+    blk.loss_out = ptr(loss_out)
+    blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    check(load().mobody_td3bc_actor_backward(C.byref(blk), cur_stream()), "mobody_td3bc_actor_backward")
+
+
 def value_loss_grad(qt, v, n_global):
     """qt [2,N] target twin-Q(s,a), v [N] -> (dz3[N,16], loss[1]) of the expectile V loss."""
     N = v.numel()

@@ -1,4 +1,5 @@
-"""CLI driver -- mirror of the reference's `train_mobody.py` for mode 3 (offline-offline = MOBODY).
+"""CLI driver -- mirror of the reference's `train_mobody.py` for mode 3 (offline-offline): `--policy MOBODY` and the model-free
+baseline `--policy TD3_BC` (no ensemble dynamics is built, loaded or trained for it, train_mobody.py:820).
 
 Accepts the reference's flags with the same names, types and defaults (train_mobody.py:210-307),
 merges configuration in the same precedence (yaml <- --params JSON <- CLI-derived keys, :407-416,
@@ -146,21 +147,35 @@ def domain_of(env):
     raise NotImplementedError
 
 
+# hyper-parameters of the reference's config/mujoco/<policy>/*.yaml, used when no config tree is present: its four files per
+# policy are identical (mobody's except for eval_freq); tests/golden/g23_td3bc_configs.json holds td3_bc's
+_BUILTIN_YAML = {
+    "mobody": dict(alpha=0.2, batch_size=128, actor_lr=0.0003, critic_lr=0.0003, gamma=0.99, state_dim=17, action_dim=3,
+                   hidden_sizes=256, max_action=1, gaussian_noise_std=1.0, eta=0.1, temperature_opt=False, tau=0.005,
+                   update_interval=2, expl_noise=0.2, eval_episode=10, eval_freq=2500, start_steps=5000, max_step=500000,
+                   device="cuda", save_freq=5000, lam=0.7, temp=3.0, weight=2.5),
+    "td3_bc": dict(batch_size=128, actor_lr=0.0003, critic_lr=0.0003, gamma=0.99, state_dim=17, action_dim=3, hidden_sizes=256,
+                   max_action=1, tau=0.005, update_interval=2, expl_noise=0.2, eval_episode=10, eval_freq=10000,
+                   start_steps=5000, max_step=500000, device="cuda", weight=2.5, save_freq=5000),
+}
+
+
+def uses_model(policy):
+    """The ensemble dynamics is built, loaded or trained only for model-based policies (train_mobody.py:820)."""
+    return "mb" in policy.lower() or "mobody" in policy.lower()
+
+
 def load_yaml(domain, policy, env_base):
-    """config/<domain>/<policy>/<env>.yaml next to the script (train_mobody.py:410-411); the four
-    mujoco MOBODY files of the reference are identical except eval_freq, so a built-in copy of the
-    hyper-parameters is used when no config tree is present."""
+    """config/<domain>/<policy>/<env>.yaml next to the script (train_mobody.py:410-411); a built-in copy of the mujoco
+    hyper-parameters of `mobody` and `td3_bc` is used when no config tree is present."""
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(here, "config", domain, policy, env_base + ".yaml")
     if os.path.exists(path):
         with open(path, "r", encoding="utf-8") as f:
             return yaml.safe_load(f)
-    if policy != "mobody" or domain != "mujoco":
+    if policy not in _BUILTIN_YAML or domain != "mujoco":
         raise FileNotFoundError(path)             # same failure as the reference for configs it does not ship
-    return dict(alpha=0.2, batch_size=128, actor_lr=0.0003, critic_lr=0.0003, gamma=0.99, state_dim=17, action_dim=3,
-                hidden_sizes=256, max_action=1, gaussian_noise_std=1.0, eta=0.1, temperature_opt=False, tau=0.005,
-                update_interval=2, expl_noise=0.2, eval_episode=10, eval_freq=2500, start_steps=5000, max_step=500000,
-                device="cuda", save_freq=5000, lam=0.7, temp=3.0, weight=2.5)
+    return dict(_BUILTIN_YAML[policy])
 
 
 def build_config(args, state_dim, action_dim, max_action):
@@ -343,21 +358,23 @@ def _run(args, rank, world, device):
         tar_rb.convert_D4RL(tar_ds)
         say(f"datasets: {src_rb.size} source / {tar_rb.size} target transitions")
 
-    model = MOBODYModule(obs_dim=state_dim, action_dim=action_dim, hidden_dims=256, num_ensemble=7, num_elites=5,
-                         weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=device,
-                         reward_relu=args.relu_reward, config=config)
-    # no CLI flag (the reference's driver never passes one, train_mobody.py:805-812): an optional key of the merged config
-    dynamics = MOBODYEnsembleDynamics(config, model, None, None, terminal_fn, penalty_coef=env_penalty_coef,
-                                      uncertainty_mode=config.get("uncertainty_mode", "pairwise-diff"),
-                                      rng=args.rng, seed=args.seed + 3)
     outdir = f"{args.dir}/{args.policy}/{args.env}-srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}/r{args.seed}{args.out_dir_remark}"
     writer = None
     if args.scalars:                                                                   # train_mobody.py:455-458
         writer = ScalarLog(f"{outdir}/tb/scalars.csv") if rank == 0 else NullLog()
-    build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic=args.synthetic == 1,
-                   rank=rank, world=world)
-    config.update({"dynamics": dynamics})
-    policy.dynamics = dynamics
+    dynamics = None
+    if uses_model(args.policy):                       # a model-free baseline (TD3_BC) has no ensemble to build, load or train
+        model = MOBODYModule(obs_dim=state_dim, action_dim=action_dim, hidden_dims=256, num_ensemble=7, num_elites=5,
+                             weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=device,
+                             reward_relu=args.relu_reward, config=config)
+        # no CLI flag (the reference's driver never passes one, train_mobody.py:805-812): an optional key of the merged config
+        dynamics = MOBODYEnsembleDynamics(config, model, None, None, terminal_fn, penalty_coef=env_penalty_coef,
+                                          uncertainty_mode=config.get("uncertainty_mode", "pairwise-diff"),
+                                          rng=args.rng, seed=args.seed + 3)
+        build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit_synthetic=args.synthetic == 1,
+                       rank=rank, world=world)
+        config.update({"dynamics": dynamics})
+        policy.dynamics = dynamics
 
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
@@ -378,11 +395,12 @@ def _run(args, rank, world, device):
             # The reference's evaluation block (train_mobody.py:928-975) rolls the policy out in the simulators; of it, what
             # does not need a simulator is kept on the same cadence: the transition model's error on TARGET transitions
             # (eval_policy_batch's obs-RMSE / reward-MSE, :100-133, here on a target-buffer batch) and the model checkpoint.
-            if writer is not None:
+            if writer is not None and dynamics is not None:
                 s_, a_, s2_, r_, _ = tar_rb.sample(min(1000, tar_rb.size))
                 err = dynamics.model_error(s_, a_, s2_, r_)
                 writer.add_scalar("test/model error next_obs", err["obs_mse"], global_step=t + 1)
                 writer.add_scalar("test/model error reward", err["reward_mse"], global_step=t + 1)
+            if writer is not None:
                 writer.flush()
             if args.save_model:
                 policy.save(f"{outdir}/models/model")
