@@ -9,6 +9,7 @@
  *                           (+ termination predicates             algo/mb_utils/terminal_funs.py:10-149)
  *   mobody_ens_step      <- the same step() for either model and every uncertainty_mode   mobody_dynamics.py:193-265 (:241-252)
  *   mobody_ens_rollout   <- MOBODY.rollout + add_batch, likewise  mobody.py:596-657, utils.py:43-92
+ *   mobody_ens_evaluate  <- eval_policy_batch, in the learned model   train_mobody.py:60-98
  *   mobody_mlp3_forward  <- Policy / DoubleQFunc / ValueFunc fwd  algo/offline_offline/mobody.py:35-83
  *   mobody_rollout       <- MOBODY.rollout + add_batch            algo/offline_offline/mobody.py:596-657, algo/utils.py:43-92
  *   mobody_gather_batch  <- ReplayBuffer.sample x3 + torch.cat    algo/utils.py:127-148, mobody.py:399-400,516-529
@@ -284,6 +285,47 @@ typedef struct MobodyEnsRollout {
 } MobodyEnsRollout;
 int64_t mobody_ens_rollout_workspace(const MobodyEnsRollout* a);
 int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream);
+
+/* The policy's return in the learned model, on the device: the stand-in for eval_policy_batch (train_mobody.py:60-98) in a
+ * build without simulators -- B episodes are rolled through the ensemble for H steps and their rewards summed per row,
+ * the terminating step's reward included (`reward_all[i, :done_index[i] + 1]`, :86-93).  Fields as MobodyEnsRollout, plus
+ * the caller-owned ROW STATE (in/out).  resume == 0 first sets, per row b, obs_state = init_obs[b], alive = 1,
+ * ret = pen_sum = 0, length = 0, disc = 1; resume == 1 continues from the state as it is.  Then for t = 0 .. H-1:
+ *   a = pi(obs_state)                       the bits of mobody_mlp3_forward(out_mode 1, max_action)
+ *   (obs', raw, term, pen) = mobody_ens_step(obs_state, a) with the current alive mask, noise = elite_idx = NULL, call id
+ *                            call0 + t + call_dev[0], use_penalty = 0 (raw = the ensemble's mean reward), this block's
+ *                            use_trg, uncertainty_mode and model
+ *   if alive:  ret = fmaf(disc, raw, ret);  pen_sum += pen;  length += 1;  disc = disc * discount
+ *   alive = alive && !term;  obs_state = obs'
+ * Rows that died keep their index and are computed but never accumulated.  H == 0 with resume == 0 only initialises.
+ * 5 launches per step (policy forward, member forward, sample, reward head, accounting), one more for the initialisation;
+ * no host work and no synchronisation between steps.  With resume = 1 and call_dev a captured chunk of C steps is replayed
+ * ceil(H / C) times (mobody_counter_add inside the graph advances the call word).  MOBODY_E_ARG, before any runtime call:
+ * struct_bytes, uncertainty_mode, B < 0, H < 0, resume not 0 / 1, discount NaN or outside (0, 1], every null pointer
+ * (init_obs only when resume == 0), precision / planes as mobody_ens_rollout.  B == 0 returns 0.
+ * workspace: mobody_ens_evaluate_workspace(a) floats (reads S, A, B).
+ * (Declared as a tagged struct plus its typedef: the layout is that of `typedef struct MobodyEnsEval { ... } MobodyEnsEval`.) */
+struct MobodyEnsEval {
+  int32_t struct_bytes, uncertainty_mode;
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T, *actor_blob, *actor_blob_T;
+  int32_t precision, S, A, task;
+  const float* init_obs;            /* [B][S]; read only when resume == 0 */
+  int64_t B;
+  int32_t H, n_elites;
+  const int32_t* elites;            /* HOST array */
+  uint32_t seed, call0;
+  const int64_t* call_dev;          /* nullable */
+  float max_action, discount;       /* discount in (0, 1] */
+  int32_t use_trg, resume;
+  float* obs_state;                 /* [B][S] current observation */
+  uint8_t* alive;                   /* [B] */
+  float *ret, *pen_sum, *disc;      /* [B] each */
+  int32_t* length;                  /* [B] */
+  float* workspace;
+};
+typedef struct MobodyEnsEval MobodyEnsEval;
+int64_t mobody_ens_evaluate_workspace(const MobodyEnsEval* a);
+int mobody_ens_evaluate(const MobodyEnsEval* a, void* stream);
 
 /* Termination predicate alone: done[B] (uint8) = terminal_fn(next_obs[B][S])  (terminal_funs.py:10-121). */
 int mobody_termination(int task, const float* next_obs, int64_t B, int S, uint8_t* done, void* stream);

@@ -84,6 +84,15 @@ class MobodyEnsRollout(C.Structure):
                 ("ring", C.POINTER(MobodyBufferView)), ("cap", i64), ("ptr_size", vp), ("workspace", vp)]
 
 
+class MobodyEnsEval(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
+                ("mopo_blob_T", vp), ("actor_blob", vp), ("actor_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32),
+                ("task", i32), ("init_obs", vp), ("B", i64), ("H", i32), ("n_elites", i32), ("elites", C.POINTER(i32)),
+                ("seed", u32), ("call0", u32), ("call_dev", vp), ("max_action", f32), ("discount", f32), ("use_trg", i32),
+                ("resume", i32), ("obs_state", vp), ("alive", vp), ("ret", vp), ("pen_sum", vp), ("disc", vp), ("length", vp),
+                ("workspace", vp)]
+
+
 # Argument blocks of the train step and of the pre-training step: one field per argument, in the header's order.  Float and
 # counter pointers are c_void_p (torch data_ptr()); what keeps two of them apart is the field NAME the caller writes.
 class MobodyCritic(C.Structure):
@@ -164,6 +173,8 @@ PROTOTYPES = {
     "mobody_ens_step": (C.c_int, [C.POINTER(MobodyEnsStep), vp]),
     "mobody_ens_rollout_workspace": (i64, [C.POINTER(MobodyEnsRollout)]),
     "mobody_ens_rollout": (C.c_int, [C.POINTER(MobodyEnsRollout), vp]),
+    "mobody_ens_evaluate_workspace": (i64, [C.POINTER(MobodyEnsEval)]),
+    "mobody_ens_evaluate": (C.c_int, [C.POINTER(MobodyEnsEval), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_rollout": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp, i64, C.c_int, C.POINTER(i32), C.c_int, u32, u32, f32,
                                  C.c_int, C.c_int, f32, C.c_int, C.POINTER(MobodyBufferView), i64, vp, vp, vp]),

@@ -19,6 +19,8 @@ import torch
 
 from ... import _lib, dp, ops
 
+MODEL_EVAL_SEED = 0xE7A1                  # seed offset of evaluate_policy's noise / elite stream (cf. mobody.GRAPH_DYN_SEED)
+
 
 class StandardScaler(object):
     """Identity scaler (the reference's fit() overwrites mu=0, std=1 and transform() returns its input,
@@ -82,6 +84,8 @@ class MOBODYEnsembleDynamics(object):
         self.train_noise_fn = None    # optional hook: b -> (noise6[6,7,b,16], noise7[7,b,S]) device tensors (tests); mopo
                                       # model: b -> noise[7,b,S], the fake-next-state draw (its only noise)
         self._ws = None
+        # evaluate_policy: its own row state / workspace / call word (per B), chunk graph, call counter, capture count
+        self._eval, self._eval_graph, self._eval_calls, self.eval_captures = None, None, 0, 0
         self._pre_ws_by_b, self._pre_bufs_by_b, self._train_calls = {}, {}, 0
         # 1: replay full pre-training batches as one HIP graph (1 GPU, device noise).  Off by default since round 3: the step is
         # ~20 launches of 5-20 us, the host's eager launches stay ahead of the GPU, and a graph replay measured SLOWER (0.260 ms
@@ -129,6 +133,85 @@ class MOBODYEnsembleDynamics(object):
         info = {"samples": r["mean"], "raw_reward": r["raw_reward"], "penalty": r["penalty"]}
         terminal = r["terminal"].cpu().numpy().astype(bool)            # the reference returns host NumPy (:237)
         return r["next_obs"], r["reward"], terminal, info
+
+    @torch.no_grad()
+    def evaluate_policy(self, actor_net, init_obs, horizon, use_trg=True, discount=1.0, chunk=50, seed_offset=MODEL_EVAL_SEED):
+        """The policy's return in this model (`mobody_ens_evaluate`): eval_policy_batch's accounting (train_mobody.py:60-98)
+        with the learned step in the simulator's place.  Every row of `init_obs` is one episode of at most `horizon` steps;
+        a row's return is the discounted sum of the ensemble's raw mean rewards up to and including its terminating step.
+        A model-based ESTIMATE: its error grows with the horizon.
+
+        Always the device Philox generator, on a seed stream (`seed_offset`) and a call counter of its own: no training RNG
+        stream, counter, ring or workspace is read or written, whatever config['rng'] says.  horizon > chunk > 0: the row
+        state is initialised, then one captured graph of `chunk` steps is replayed horizon // chunk times (the call id lives
+        in a device word the graph advances) and the remainder runs eagerly; chunk = 0: one eager call.  Returns device
+        tensors `returns`, `lengths`, `penalty_sums`, `alive` [B] and the float means `return_mean`, `length_mean`,
+        `penalty_mean`, `alive_frac` (the one synchronisation)."""
+        m = self.model
+        m.inference()
+        obs = torch.as_tensor(init_obs, dtype=torch.float32).to(m.device).reshape(-1, m.obs_dim).contiguous()
+        B, H, chunk = obs.shape[0], int(horizon), int(chunk)
+        if H < 0 or chunk < 0:
+            raise ValueError(f"evaluate_policy: horizon {H} / chunk {chunk} must be >= 0")
+        S, A = m.obs_dim, m.action_dim
+        if self._eval is None or self._eval[0] != B:
+            self._eval = (B, ops.eval_state(B, S, m.device), None, torch.zeros(1, dtype=torch.int64, device=m.device))
+            self._eval_graph = None
+        _, st, ws, ctr = self._eval
+        mopo = m.packed_mopo() if getattr(m, "mopo", False) else None
+        planes = m.planes() if self.precision else None
+        seed = (self.seed + int(seed_offset) + dp.rank_salt()) & 0xFFFFFFFF
+        call0 = self._eval_calls + 1
+        self._eval_calls += H
+
+        def run(h, call, resume, call_dev=None):
+            return ops.ens_evaluate(m.packed(), actor_net.blob, S, A, self._task_id, actor_net.max_action,
+                                    None if resume else obs, h, list(m.elites_host()), seed, call & 0xFFFFFFFF, st,
+                                    use_trg=use_trg, discount=discount, resume=resume, ws=ws, dyn_planes=planes,
+                                    actor_blob_T=actor_net.blob_T, precision=self.precision, mopo=mopo,
+                                    uncertainty_mode=self._unc_id, call_dev=call_dev)
+
+        if chunk == 0 or H <= chunk:
+            ws = run(H, call0, False)
+        else:
+            ws = run(0, call0, False)                         # initialise the row state (sizes the workspace)
+            n_full = H // chunk
+            ctr.fill_(call0)
+            # every pointer and scalar the captured launches bake in (a reloaded model re-packs its blob: a new key).  The
+            # graph keeps the tensors it reads alive, so a stale address is never handed out again while it could be replayed
+            held = [t for t in (ws, m.packed(), actor_net.blob, actor_net.blob_T, planes) + (mopo or ()) if t is not None]
+            key = (chunk, bool(use_trg), float(discount), seed, self.precision, self._unc_id, float(actor_net.max_action),
+                   tuple(m.elites_host()), mopo is not None) + tuple(t.data_ptr() for t in held)
+
+            def body():
+                run(chunk, 0, True, call_dev=ctr)
+                ops.counter_add(ctr, chunk)
+
+            first = 0
+            if self._eval_graph is None or self._eval_graph[0] != key:
+                self._eval_graph = None
+                body()                                        # the first chunk runs eagerly (capturing executes nothing)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body()
+                self._eval_graph = (key, g, held)
+                self.eval_captures += 1
+                first = 1
+            for _ in range(n_full - first):
+                self._eval_graph[1].replay()
+            if H > n_full * chunk:
+                run(H - n_full * chunk, call0 + n_full * chunk, True)
+        self._eval = (B, st, ws, ctr)
+        alive = st["alive"].clone()
+        out = dict(returns=st["ret"].clone(), lengths=st["length"].clone(), penalty_sums=st["pen_sum"].clone(), alive=alive)
+        if B > 0:
+            means = torch.stack([out["returns"].mean(), out["lengths"].to(torch.float32).mean(), out["penalty_sums"].mean(),
+                                 alive.to(torch.float32).mean()]).tolist()
+        else:
+            means = [float("nan")] * 4
+        out.update(return_mean=means[0], length_mean=means[1], penalty_mean=means[2], alive_frac=means[3])
+        return out
 
     def model_error(self, obs, action, next_obs, reward):
         """Model error on real transitions as eval_policy_batch reports it (train_mobody.py:100-133):

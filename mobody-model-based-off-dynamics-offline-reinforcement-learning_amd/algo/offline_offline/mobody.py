@@ -25,6 +25,7 @@ REFRESH_EVERY = 5000        # mobody.py:441
 REFRESH_SRC, REFRESH_TAR = 50000, 2000    # :442-443
 REFRESH_FROM_SRC_TAR = 100                # target init states of the rollout_from_src branch, :485
 GRAPH_DYN_SEED = 0x51ED                    # seed offset of the ensemble-step noise stream of captured 'par' steps
+from ..dynamics.mobody_dynamics import MODEL_EVAL_SEED   # noqa: E402,F401  seed offset of evaluate_in_model's stream (its own)
 
 
 class _PackedNet(object):
@@ -375,6 +376,11 @@ class MOBODY(object):
             keep = (res["penalty"] <= self.config["env_filter"]).squeeze(1)
             res = {k: v[keep] for k, v in res.items()}
         return res, {"num_transitions": n_tr, "reward_mean": rew_mean}
+
+    def evaluate_in_model(self, init_obs, horizon, **kw):
+        """Return of the current policy in the learned model (MOBODYEnsembleDynamics.evaluate_policy: the stand-in for
+        eval_policy_batch, train_mobody.py:60-98).  Reads the policy and the model only: no training state moves."""
+        return self.dynamics.evaluate_policy(self.policy, init_obs, horizon, **kw)
 
     def _rollout_into_fake(self, init_obss, rollout_length, use_trg=True):
         """Same transitions as rollout()+add_batch, entirely on the device (`mobody_ens_rollout`): rows keep their index, an

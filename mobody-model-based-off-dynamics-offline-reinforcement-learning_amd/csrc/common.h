@@ -81,6 +81,19 @@ int launch_ring_append(const MobodyBufferView& ring, long long cap, long long* p
                        const uint8_t* keep, long long M, int32_t* scan_ws, hipStream_t st);
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// return accounting of mobody_ens_evaluate (trajectory_return.hip): the caller's row state, which dyn_step_impl's last launch
+// updates in k_dyn_finalize's place (the step's obs / alive ARE obs_state / alive), and the two launches
+struct DynEvalHook {
+  float* obs_state;
+  uint8_t* alive;
+  float *ret, *pen_sum, *disc;
+  int32_t* length;
+  float discount;
+};
+int launch_eval_account(const float* r_mu, const float* penalty, const float* next_obs, const uint8_t* alive_next,
+                        const DynEvalHook& h, long long B, int S, hipStream_t st);
+int launch_eval_init(const float* init_obs, const DynEvalHook& h, long long B, int S, hipStream_t st);
+
 // device-side view of one packed MLP (member 0 pointers + strides), built from MobodyMlpLayout
 struct MlpView {
   const float *w1, *b1, *w2, *b2, *w3, *b3;

@@ -11,6 +11,7 @@
 //                                                                    terminal_funs.py:10-113
 //   reward head    generic fused MLP forward (Swish) on [s,a,s']     mobody_module.py:295-302
 //   k_dyn_finalize reward = mean_e r_mu - coef*penalty               mobody_dynamics.py:236,261-263
+//   k_eval_account (trajectory_return.hip) in k_dyn_finalize's place under mobody_ens_evaluate
 //
 // Roofline: k_dyn_fwd / reward head are MFMA-f32 bound (3.36 MFLOP per transition at
 // S=17,A=6 against 240 algorithmic bytes); k_dyn_sample / k_dyn_finalize are HBM-bound
@@ -403,8 +404,9 @@ extern "C" int64_t mobody_dyn_step_workspace(int S, int A, int64_t B) {
 // mobody_mlp_layout(S + A, S, 7); encoders and decoder are bypassed, forward_trg == forward_src.  Everything after the means
 // (std, sample, reward head, penalty, termination) is the same code.
 // `who`: the public entry point named in error texts.  keep / alive_out / env_filter / use_filter: the rollout's bookkeeping.
+// `eval`: the last launch is k_eval_account on the caller's row state, not k_dyn_finalize (a.reward / a.raw_reward unused).
 static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep, uint8_t* alive_out, float env_filter,
-                         int use_filter, void* stream) {
+                         int use_filter, void* stream, const DynEvalHook* eval = nullptr) {
   const int S = a.S, A = a.A, precision = a.precision;
   const int64_t B = a.B;
   MobodyDynLayout L;
@@ -414,7 +416,7 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
              "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
   MB_REQUIRE(B >= 0, "%s: B < 0", who);
   if (B == 0) return 0;                      // empty batch: nothing to do (pointers may be null)
-  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && a.reward && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && (a.reward || eval) && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
   MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d", who, a.task);
   MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
   MB_REQUIRE(a.elite_idx != nullptr || (a.elites != nullptr && a.n_elites >= 1 && a.n_elites <= NENS),
@@ -462,6 +464,9 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
   rc = launch_mlp3_forward(m, NENS, ACT_SWISH, precision, st);
   if (rc) return rc;
 
+  if (eval != nullptr) {
+    return launch_eval_account(r_mu, a.penalty, a.next_obs, alive_out, *eval, B, S, st);
+  }
   DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
   hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, fa);
   MB_LAUNCH_OK("k_dyn_finalize");
@@ -594,6 +599,99 @@ extern "C" int64_t mobody_ens_rollout_workspace(const MobodyEnsRollout* a) {
 extern "C" int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream) {
   MB_BLOCK("mobody_ens_rollout", a, MobodyEnsRollout);
   return rollout_impl("mobody_ens_rollout", *a, stream);
+}
+
+// ---- the policy's return in the model (eval_policy_batch's accounting, train_mobody.py:60-98, over the learned step) ----
+namespace mobody {
+struct EvalWs {
+  float *act, *next_obs, *penalty, *dyn;
+  uint8_t *terminal, *alive_next;
+  long long total;
+};
+static void eval_carve(int S, int A, long long B, float* base, EvalWs& w) {
+  long long off = 0;
+  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  w.act = take(B * A); w.next_obs = take(B * S); w.penalty = take(B);
+  w.dyn = take((long long)NENS * B * S + (long long)NENS * B);
+  w.terminal = (uint8_t*)take((B + 3) / 4); w.alive_next = (uint8_t*)take((B + 3) / 4);
+  w.total = off;
+}
+}  // namespace mobody
+
+extern "C" int64_t mobody_ens_evaluate_workspace(const MobodyEnsEval* a) {
+  if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyEnsEval) || a->B < 0 || a->S < 1 || a->A < 1)
+    return fail(MOBODY_E_ARG, "mobody_ens_evaluate_workspace: null struct, wrong struct_bytes, B < 0 or S, A < 1");
+  EvalWs w;
+  eval_carve(a->S, a->A, a->B, nullptr, w);
+  return w.total;
+}
+
+// H steps of 5 launches: policy forward -> member forward -> sample (alive update into the workspace) -> reward head ->
+// accounting; one launch more when the row state is initialised first
+extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
+  const char* who = "mobody_ens_evaluate";
+  MB_BLOCK(who, ap, MobodyEnsEval);
+  const MobodyEnsEval& a = *ap;
+  const int S = a.S, A = a.A, precision = a.precision;
+  const int64_t B = a.B;
+  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
+             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
+  MB_REQUIRE(B >= 0, "%s: B < 0", who);
+  MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
+  MB_REQUIRE(a.resume == 0 || a.resume == 1, "%s: resume %d is neither 0 nor 1", who, a.resume);
+  MB_REQUIRE(a.discount > 0.f && a.discount <= 1.f, "%s: discount %g outside (0, 1]", who, (double)a.discount);   // NaN fails both
+  if (B == 0) return 0;
+  MB_REQUIRE(a.dyn_blob, "%s: null pointer dyn_blob", who);
+  MB_REQUIRE(a.actor_blob, "%s: null pointer actor_blob", who);
+  MB_REQUIRE(a.resume == 1 || a.init_obs, "%s: null pointer init_obs (resume == 0)", who);
+  MB_REQUIRE(a.elites, "%s: null pointer elites", who);
+  MB_REQUIRE(a.obs_state, "%s: null pointer obs_state", who);
+  MB_REQUIRE(a.alive, "%s: null pointer alive", who);
+  MB_REQUIRE(a.ret, "%s: null pointer ret", who);
+  MB_REQUIRE(a.pen_sum, "%s: null pointer pen_sum", who);
+  MB_REQUIRE(a.disc, "%s: null pointer disc", who);
+  MB_REQUIRE(a.length, "%s: null pointer length", who);
+  MB_REQUIRE(a.workspace, "%s: null pointer workspace", who);
+  MB_REQUIRE(a.n_elites >= 1 && a.n_elites <= NENS, "%s: n_elites %d outside 1..7", who, a.n_elites);
+  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
+  if (rc) return rc;
+  MB_REQUIRE(precision == PREC_F32 || a.actor_blob_T, "%s: the split-precision modes need the actor's T blob (actor_blob_T)", who);
+  MB_REQUIRE(precision == PREC_F32 || !a.mopo_blob || a.mopo_blob_T, "%s: the split-precision modes need the T blob of the MLP (mopo_blob_T)", who);
+  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d (task)", who, a.task);
+  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
+  MobodyDynLayout L;
+  rc = mobody_dyn_layout(S, A, &L);
+  if (rc) return rc;
+  MobodyMlpLayout La;
+  rc = mobody_mlp_layout(S, A, 1, &La);
+  if (rc) return rc;
+  EvalWs w;
+  eval_carve(S, A, B, a.workspace, w);
+  hipStream_t st = as_stream(stream);
+  const DynEvalHook hook{a.obs_state, a.alive, a.ret, a.pen_sum, a.disc, a.length, a.discount};
+  if (a.resume == 0) {
+    rc = launch_eval_init(a.init_obs, hook, B, S, st);
+    if (rc) return rc;
+  }
+  for (int t = 0; t < a.H; ++t) {
+    // a = pi(s)  (eval_policy_batch's policy.select_action, train_mobody.py:76)
+    Mlp3FwdArgs p = fwd_net(a.actor_blob, La, B);
+    fwd_set_src(p, 0, a.obs_state, S, S);
+    fwd_set_out(p, w.act, 1, a.max_action);
+    if (precision != PREC_F32) fwd_set_planes(p, a.actor_blob_T, La);
+    rc = launch_mlp3_forward(p, 1, ACT_RELU, precision, st);
+    if (rc) return rc;
+    MobodyEnsStep s{};
+    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
+    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = a.obs_state; s.act = w.act; s.B = B;
+    s.alive = a.alive; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
+    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.use_penalty = 0;
+    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
+    rc = dyn_step_impl(who, s, nullptr, w.alive_next, 0.f, 0, stream, &hook);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 extern "C" int mobody_rollout(const float* dyn_blob, const float* dyn_planes, const float* actor_blob, const float* actor_blob_T,

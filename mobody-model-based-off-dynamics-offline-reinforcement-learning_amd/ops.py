@@ -715,3 +715,39 @@ def rollout(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, elites
     a.workspace = ptr(ws)
     check(load().mobody_ens_rollout(C.byref(a), cur_stream()), "mobody_ens_rollout")
     return ws
+
+
+def eval_state(B, S, device):
+    """The caller-owned row state of mobody_ens_evaluate: obs_state[B,S], alive uint8[B], ret / pen_sum / disc float[B],
+    length int32[B].  Uninitialised: the first call (resume=False) sets it."""
+    f = dict(dtype=torch.float32, device=device)
+    return dict(obs_state=torch.empty(B, S, **f), alive=torch.empty(B, dtype=torch.uint8, device=device),
+                ret=torch.empty(B, **f), pen_sum=torch.empty(B, **f), disc=torch.empty(B, **f),
+                length=torch.empty(B, dtype=torch.int32, device=device))
+
+
+def ens_evaluate(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, elites, seed, call0, state, use_trg=True,
+                 discount=1.0, resume=False, ws=None, dyn_planes=None, actor_blob_T=None, precision=0, mopo=None,
+                 uncertainty_mode=0, call_dev=None):
+    """H steps of policy evaluation in the model on the row state `state` (eval_state; mobody_ens_evaluate): per row the
+    discounted sum of the ensemble's raw mean rewards up to and including the terminating step, the penalty sum, the
+    length and the alive flag.  init_obs may be None when resume.  Returns the workspace."""
+    B = state["obs_state"].shape[0]
+    if init_obs is not None:
+        init_obs = _f32(init_obs)
+        assert init_obs.shape == (B, S)
+    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
+    mb, mbt = mopo if mopo is not None else (None, None)
+    a = _lib.MobodyEnsEval(C.sizeof(_lib.MobodyEnsEval), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
+                           ptr(mbt), ptr(actor_blob), ptr(actor_blob_T), prec_id(precision), S, A, task_id, ptr(init_obs), B,
+                           int(H), len(elites), el, seed, call0, ptr(call_dev), float(max_action), float(discount),
+                           int(bool(use_trg)), int(bool(resume)), ptr(state["obs_state"]), ptr(state["alive"]),
+                           ptr(state["ret"]), ptr(state["pen_sum"]), ptr(state["disc"]), ptr(state["length"]), None)
+    need = load().mobody_ens_evaluate_workspace(C.byref(a))
+    if need < 0:
+        raise _lib.MobodyError("mobody_ens_evaluate_workspace: " + load().mobody_last_error().decode())
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=state["obs_state"].device)
+    a.workspace = ptr(ws)
+    check(load().mobody_ens_evaluate(C.byref(a), cur_stream()), "mobody_ens_evaluate")
+    return ws

@@ -213,6 +213,31 @@ def build_config(args, state_dim, action_dim, max_action):
     return config
 
 
+def episode_starts(observations, next_observations, terminals):
+    """Row indices at which an episode of a transition dataset starts (pure NumPy): row 0, every row after a terminal
+    one, and every row whose observation is not the row before's next observation (a time-limit cut or a joined file)."""
+    obs, nxt = np.asarray(observations), np.asarray(next_observations)
+    n = obs.shape[0]
+    if n == 0:
+        return np.zeros(0, dtype=np.int64)
+    term = np.asarray(terminals).reshape(-1).astype(bool)
+    start = np.ones(n, dtype=bool)
+    start[1:] = term[:-1] | np.any(nxt[:-1] != obs[1:], axis=1)
+    return np.flatnonzero(start)
+
+
+def model_eval_rows(starts, episodes, seed):
+    """`episodes` rows out of `starts` for the evaluation in the model, from a seeded generator of its own (never the global
+    one): distinct starts while there are enough, drawn with replacement when there are fewer starts than episodes."""
+    starts = np.asarray(starts, dtype=np.int64)
+    if starts.size == 0:
+        raise ValueError("model_eval_rows: the dataset has no row to start an episode from")
+    rng = np.random.default_rng([int(seed), 0x4D45])
+    if starts.size >= episodes:
+        return np.sort(rng.choice(starts, size=episodes, replace=False))
+    return rng.choice(starts, size=episodes, replace=True)
+
+
 def dynamics_save_path(args, root):
     """`<root>/<env>/srcdatatype-<src>-tardatatype-<tar>-<shift>` (train_mobody.py:822-823, 843-844)."""
     return os.path.join(root, args.env, f"srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}")
@@ -376,6 +401,21 @@ def _run(args, rank, world, device):
         config.update({"dynamics": dynamics})
         policy.dynamics = dynamics
 
+    # Evaluation of the policy in the learned target model (no simulators in this build): two optional keys of the merged
+    # config, off by default.  Rank 0 evaluates; start states are episode starts of the target data.
+    eval_obs, ref_env_name = None, f"{args.env}-{args.shift_level}"               # train_mobody.py:331
+    if int(config.get("model_eval_episodes", 0)) > 0:
+        if dynamics is None:
+            say(f"model_eval_episodes / model_eval_horizon ignored: {args.policy} has no model to evaluate in")
+        elif rank == 0:
+            from mobody_amd.envs.infos import get_normalized_score
+            get_normalized_score(0.0, ref_env_name)   # an unknown task raises KeyError here, not at the first evaluation
+            n = tar_rb.size
+            term = 1.0 - tar_rb.not_done[:n].cpu().numpy()
+            rows = model_eval_rows(episode_starts(tar_rb.state[:n].cpu().numpy(), tar_rb.next_state[:n].cpu().numpy(), term),
+                                   int(config["model_eval_episodes"]), args.seed)
+            eval_obs = tar_rb.state[torch.as_tensor(rows, device=tar_rb.state.device)].contiguous()
+
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
     start = time.time()
@@ -400,6 +440,16 @@ def _run(args, rank, world, device):
                 err = dynamics.model_error(s_, a_, s2_, r_)
                 writer.add_scalar("test/model error next_obs", err["obs_mse"], global_step=t + 1)
                 writer.add_scalar("test/model error reward", err["reward_mse"], global_step=t + 1)
+            if writer is not None and eval_obs is not None:
+                # eval_policy_batch's return (:60-98) with the learned target model in the simulator's place: an ESTIMATE
+                # whose error grows with the horizon -- hence tags of its own, never the simulator's 'test/target return'
+                ev = policy.evaluate_in_model(eval_obs, int(config.get("model_eval_horizon", 1000)))
+                writer.add_scalar("test/model target return", ev["return_mean"], global_step=t + 1)
+                writer.add_scalar("test/model target normalized score", get_normalized_score(ev["return_mean"], ref_env_name),
+                                  global_step=t + 1)
+                writer.add_scalar("test/model episode length", ev["length_mean"], global_step=t + 1)
+                writer.add_scalar("test/model penalty", ev["penalty_mean"], global_step=t + 1)
+                writer.add_scalar("test/model alive frac", ev["alive_frac"], global_step=t + 1)
             if writer is not None:
                 writer.flush()
             if args.save_model:
