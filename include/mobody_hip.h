@@ -327,6 +327,53 @@ typedef struct MobodyEnsEval MobodyEnsEval;
 int64_t mobody_ens_evaluate_workspace(const MobodyEnsEval* a);
 int mobody_ens_evaluate(const MobodyEnsEval* a, void* stream);
 
+/* Open-loop model error over recorded trajectories, on the device: B windows of a transition dataset held in dataset
+ * order (`data`, rows 0 .. data_rows-1; ring form pitch >= 2S+A+2 or five arrays, pitch 0) are replayed through the ensemble
+ * -- the model starts at the recorded state of row row0[b], is fed the RECORDED actions, and its state, reward and
+ * termination flag are compared with the recorded ones at every step (the compounding-error curve).  Model fields as
+ * MobodyEnsEval.  First, per row b:  obs_state[b] = data.state[row0[b]],  act_state[b] = data.action[row0[b]].  Then for
+ * t = 0 .. H-1, with data row r = min(row0[b] + t, data_rows - 1):
+ *   (obs', raw, term, pen) = mobody_ens_step(obs_state, act_state) with alive = NULL, noise = elite_idx = NULL, call id
+ *                            call0 + t + call_dev[0], use_penalty = 0 (raw = the ensemble's mean reward: seven adds, one
+ *                            multiply by 1/7), this block's use_trg, uncertainty_mode and model
+ *   obs_err[t][b]    = sqrtf(sum_{d=0..S-1} (obs'[b][d] - data.next_state[r][d])^2)   fp32, sequential in increasing d, no fma
+ *   rew_err[t][b]    = raw - data.reward[r]                                          signed; the caller squares it
+ *   penalty[t][b]    = pen;   term_model[t][b] = term (the predicate on the model's obs')
+ *   obs_state[b]     = (reset_every > 0 && (t + 1) % reset_every == 0) ? data.next_state[r] : obs'
+ *   act_state[b]     = data.action[min(r + 1, data_rows - 1)]
+ * reset_every = 0 is the open loop, reset_every = 1 the one-step error at every offset of the window.  Every row runs all H
+ * steps; nothing is masked, so a NaN from the model stays visible in the tables.  4 launches per step (member forward,
+ * sample, reward head, accounting) plus one for the row state; no host work and no synchronisation between steps.
+ * row0 lives on the device and is NOT checked: the kernels clamp every row index into [0, data_rows - 1], so no load
+ * leaves the view, but a window that runs over an episode boundary or past the last row compares against rows that do
+ * not belong to it -- choosing windows with row0[b] >= 0 and row0[b] + H <= data_rows inside one episode is the caller's
+ * job.  MOBODY_E_ARG, before any runtime call: struct_bytes, uncertainty_mode, B < 0, H < 0, reset_every < 0, and when
+ * B > 0 data_rows < 1, every null pointer (data and its state / action / next_state / reward count; not_done is not
+ * read; the four tables only when H > 0), a pitch that is neither 0 nor at least 2S+A+2, n_elites, task, precision / planes / T blob as
+ * mobody_ens_evaluate.  B == 0 returns 0; H == 0 with B > 0 only sets the row state.
+ * workspace: mobody_ens_replay_workspace(a) floats (reads S, A, B). */
+struct MobodyEnsReplay {
+  int32_t struct_bytes, uncertainty_mode;
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T;
+  int32_t precision, S, A, task;
+  const MobodyBufferView* data;
+  int64_t data_rows;
+  const int64_t* row0;              /* DEVICE array [B] */
+  int64_t B;
+  int32_t H, reset_every, n_elites;
+  const int32_t* elites;            /* HOST array */
+  uint32_t seed, call0;
+  const int64_t* call_dev;          /* nullable */
+  int32_t use_trg;
+  float *obs_state, *act_state;     /* [B][S], [B][A] */
+  float *obs_err, *rew_err, *penalty;   /* [H][B] each */
+  uint8_t* term_model;              /* [H][B] */
+  float* workspace;
+};
+typedef struct MobodyEnsReplay MobodyEnsReplay;
+int64_t mobody_ens_replay_workspace(const MobodyEnsReplay* a);
+int mobody_ens_replay(const MobodyEnsReplay* a, void* stream);
+
 /* Termination predicate alone: done[B] (uint8) = terminal_fn(next_obs[B][S])  (terminal_funs.py:10-121). */
 int mobody_termination(int task, const float* next_obs, int64_t B, int S, uint8_t* done, void* stream);
 

@@ -93,6 +93,15 @@ class MobodyEnsEval(C.Structure):
                 ("workspace", vp)]
 
 
+class MobodyEnsReplay(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
+                ("mopo_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32), ("task", i32),
+                ("data", C.POINTER(MobodyBufferView)), ("data_rows", i64), ("row0", vp), ("B", i64), ("H", i32),
+                ("reset_every", i32), ("n_elites", i32), ("elites", C.POINTER(i32)), ("seed", u32), ("call0", u32),
+                ("call_dev", vp), ("use_trg", i32), ("obs_state", vp), ("act_state", vp), ("obs_err", vp), ("rew_err", vp),
+                ("penalty", vp), ("term_model", vp), ("workspace", vp)]
+
+
 # Argument blocks of the train step and of the pre-training step: one field per argument, in the header's order.  Float and
 # counter pointers are c_void_p (torch data_ptr()); what keeps two of them apart is the field NAME the caller writes.
 class MobodyCritic(C.Structure):
@@ -175,6 +184,8 @@ PROTOTYPES = {
     "mobody_ens_rollout": (C.c_int, [C.POINTER(MobodyEnsRollout), vp]),
     "mobody_ens_evaluate_workspace": (i64, [C.POINTER(MobodyEnsEval)]),
     "mobody_ens_evaluate": (C.c_int, [C.POINTER(MobodyEnsEval), vp]),
+    "mobody_ens_replay_workspace": (i64, [C.POINTER(MobodyEnsReplay)]),
+    "mobody_ens_replay": (C.c_int, [C.POINTER(MobodyEnsReplay), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_rollout": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp, i64, C.c_int, C.POINTER(i32), C.c_int, u32, u32, f32,
                                  C.c_int, C.c_int, f32, C.c_int, C.POINTER(MobodyBufferView), i64, vp, vp, vp]),

@@ -20,6 +20,7 @@ import torch
 from ... import _lib, dp, ops
 
 MODEL_EVAL_SEED = 0xE7A1                  # seed offset of evaluate_policy's noise / elite stream (cf. mobody.GRAPH_DYN_SEED)
+OPEN_LOOP_SEED = 0x0B1E                   # seed offset of open_loop_error's noise / elite stream
 
 
 class StandardScaler(object):
@@ -86,6 +87,8 @@ class MOBODYEnsembleDynamics(object):
         self._ws = None
         # evaluate_policy: its own row state / workspace / call word (per B), chunk graph, call counter, capture count
         self._eval, self._eval_graph, self._eval_calls, self.eval_captures = None, None, 0, 0
+        # open_loop_error: its own row state / tables / workspace (per B, H) and call counter
+        self._replay, self._replay_calls, self._replay_rows = None, 0, None
         self._pre_ws_by_b, self._pre_bufs_by_b, self._train_calls = {}, {}, 0
         # 1: replay full pre-training batches as one HIP graph (1 GPU, device noise).  Off by default since round 3: the step is
         # ~20 launches of 5-20 us, the host's eager launches stay ahead of the GPU, and a graph replay measured SLOWER (0.260 ms
@@ -211,6 +214,60 @@ class MOBODYEnsembleDynamics(object):
         else:
             means = [float("nan")] * 4
         out.update(return_mean=means[0], length_mean=means[1], penalty_mean=means[2], alive_frac=means[3])
+        return out
+
+    @torch.no_grad()
+    def open_loop_error(self, buffer, row0, horizon, reset_every=0, use_trg=True, seed_offset=OPEN_LOOP_SEED):
+        """Open-loop error of this model over recorded trajectories (`mobody_ens_replay`): every window starts at the recorded
+        state of row `row0[b]` of `buffer` (a ReplayBuffer whose rows < buffer.size are in dataset order), the model is fed
+        the recorded actions for `horizon` steps, and its state, reward and termination flag are compared with the recorded
+        ones at every step.  reset_every = K > 0 puts the recorded next state back after every K-th step (K = 1: the
+        one-step error at every offset of the window).  Choosing windows that stay inside one episode is the caller's job
+        (train_mobody.open_loop_windows); a window that leaves the data is a ValueError here, before anything is launched.
+
+        Always the device Philox generator, on a seed stream (`seed_offset`) and a call counter of its own, advanced by
+        `horizon` per call, with its own row state, tables and workspace: no training RNG stream, counter, ring or workspace
+        is read or written, whatever config['rng'] says.  Returns device tensors: the tables `obs_err`, `rew_err`, `penalty`
+        [H][B] and `term_model` [H][B] (bool), and the per-step summaries [H] `obs_err_mean`, `rew_mse` and `term_agree` (the
+        share of rows whose flag equals the recorded 1 - not_done of that data row).  A host `row0` is checked on the host,
+        uploaded once per distinct set of windows, and the call does not synchronise; a device `row0` is read back for the check."""
+        m = self.model
+        m.inference()
+        H, n = int(horizon), int(buffer.size)
+        host = row0.detach().cpu().numpy() if isinstance(row0, torch.Tensor) else np.asarray(row0)
+        if host.ndim != 1 or host.dtype.kind not in "iu":
+            raise ValueError("open_loop_error: row0 must be a 1-D integer array or tensor")
+        if H < 0 or int(reset_every) < 0:
+            raise ValueError(f"open_loop_error: horizon {H} / reset_every {reset_every} must be >= 0")
+        host = host.astype(np.int64)
+        if host.size and (int(host.min()) < 0 or int(host.max()) + H > n):
+            raise ValueError(f"open_loop_error: windows of {H} steps from rows {int(host.min())}..{int(host.max())} leave the "
+                             f"{n} rows of the buffer (need 0 <= row0 and row0 + horizon <= size)")
+        if isinstance(row0, torch.Tensor) and row0.device == torch.device(m.device) and row0.dtype == torch.int64:
+            rows = row0.contiguous()
+        else:                                             # the same windows again (the CLI's cadence): no second upload
+            sig = host.tobytes()
+            if self._replay_rows is None or self._replay_rows[0] != sig:
+                self._replay_rows = (sig, torch.from_numpy(host).to(m.device))
+            rows = self._replay_rows[1]
+        B, S, A = rows.shape[0], m.obs_dim, m.action_dim
+        if self._replay is None or self._replay[0] != (B, H):
+            self._replay = ((B, H), ops.replay_state(B, H, S, A, m.device), None)
+        key, st, ws = self._replay
+        call0 = self._replay_calls + 1
+        self._replay_calls += H
+        ws = ops.ens_replay(m.packed(), S, A, self._task_id, buffer._fields(), n, rows, H, list(m.elites_host()),
+                            (self.seed + int(seed_offset) + dp.rank_salt()) & 0xFFFFFFFF, call0 & 0xFFFFFFFF, st,
+                            reset_every=int(reset_every), use_trg=use_trg, ws=ws, dyn_planes=m.planes() if self.precision else None,
+                            precision=self.precision, mopo=m.packed_mopo() if getattr(m, "mopo", False) else None,
+                            uncertainty_mode=self._unc_id)
+        self._replay = (key, st, ws)
+        out = {k: st[k].clone() for k in ("obs_err", "rew_err", "penalty")}
+        out["term_model"] = st["term_model"] != 0
+        data_row = (rows[None, :] + torch.arange(H, device=m.device)[:, None]).reshape(-1)
+        recorded = (1.0 - buffer.not_done[data_row, 0]).reshape(H, B) != 0
+        out.update(obs_err_mean=out["obs_err"].mean(1), rew_mse=(out["rew_err"] ** 2).mean(1),
+                   term_agree=(out["term_model"] == recorded).to(torch.float32).mean(1))
         return out
 
     def model_error(self, obs, action, next_obs, reward):

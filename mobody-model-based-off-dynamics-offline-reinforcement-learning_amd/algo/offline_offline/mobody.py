@@ -382,6 +382,11 @@ class MOBODY(object):
         eval_policy_batch, train_mobody.py:60-98).  Reads the policy and the model only: no training state moves."""
         return self.dynamics.evaluate_policy(self.policy, init_obs, horizon, **kw)
 
+    def open_loop_error(self, buffer, row0, horizon, **kw):
+        """Open-loop error of the learned model over recorded windows of `buffer` (MOBODYEnsembleDynamics.open_loop_error).
+        Reads the model and the buffer only: no training state moves."""
+        return self.dynamics.open_loop_error(buffer, row0, horizon, **kw)
+
     def _rollout_into_fake(self, init_obss, rollout_length, use_trg=True):
         """Same transitions as rollout()+add_batch, entirely on the device (`mobody_ens_rollout`): rows keep their index, an
         alive mask replaces the shrinking batch, the penalty filter and the alive update are formed in the sample kernel and

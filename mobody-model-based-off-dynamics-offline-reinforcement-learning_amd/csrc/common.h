@@ -94,6 +94,22 @@ int launch_eval_account(const float* r_mu, const float* penalty, const float* ne
                         const DynEvalHook& h, long long B, int S, hipStream_t st);
 int launch_eval_init(const float* init_obs, const DynEvalHook& h, long long B, int S, hipStream_t st);
 
+// open-loop error accounting of mobody_ens_replay (trajectory_truth.hip): the caller's row state and the tables' rows of
+// window step t, which dyn_step_impl's last launch fills in k_dyn_finalize's place (the step's obs / act ARE obs_state /
+// act_state), and the two launches
+struct DynReplayHook {
+  const MobodyBufferView* data;
+  long long data_rows;
+  const long long* row0;               // [B] device
+  float *obs_state, *act_state;        // [B][S], [B][A]
+  float *obs_err, *rew_err, *penalty;  // [B] each: row t of the [H][B] tables
+  uint8_t* term_model;                 // [B]: row t
+  int t, reset;                        // window step; obs_state <- the recorded next state after this step
+};
+int launch_replay_account(const float* r_mu, const float* penalty, const float* next_obs, const uint8_t* terminal,
+                          const DynReplayHook& h, long long B, int S, int A, hipStream_t st);
+int launch_replay_init(const DynReplayHook& h, long long B, int S, int A, hipStream_t st);
+
 // device-side view of one packed MLP (member 0 pointers + strides), built from MobodyMlpLayout
 struct MlpView {
   const float *w1, *b1, *w2, *b2, *w3, *b3;

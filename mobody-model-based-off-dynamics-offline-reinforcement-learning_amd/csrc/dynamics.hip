@@ -405,8 +405,9 @@ extern "C" int64_t mobody_dyn_step_workspace(int S, int A, int64_t B) {
 // (std, sample, reward head, penalty, termination) is the same code.
 // `who`: the public entry point named in error texts.  keep / alive_out / env_filter / use_filter: the rollout's bookkeeping.
 // `eval`: the last launch is k_eval_account on the caller's row state, not k_dyn_finalize (a.reward / a.raw_reward unused).
+// `replay`: likewise k_replay_account (trajectory_truth.hip), the errors of one window step against recorded data.
 static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep, uint8_t* alive_out, float env_filter,
-                         int use_filter, void* stream, const DynEvalHook* eval = nullptr) {
+                         int use_filter, void* stream, const DynEvalHook* eval = nullptr, const DynReplayHook* replay = nullptr) {
   const int S = a.S, A = a.A, precision = a.precision;
   const int64_t B = a.B;
   MobodyDynLayout L;
@@ -416,7 +417,7 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
              "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
   MB_REQUIRE(B >= 0, "%s: B < 0", who);
   if (B == 0) return 0;                      // empty batch: nothing to do (pointers may be null)
-  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && (a.reward || eval) && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
+  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && (a.reward || eval || replay) && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
   MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d", who, a.task);
   MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
   MB_REQUIRE(a.elite_idx != nullptr || (a.elites != nullptr && a.n_elites >= 1 && a.n_elites <= NENS),
@@ -466,6 +467,9 @@ static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep,
 
   if (eval != nullptr) {
     return launch_eval_account(r_mu, a.penalty, a.next_obs, alive_out, *eval, B, S, st);
+  }
+  if (replay != nullptr) {
+    return launch_replay_account(r_mu, a.penalty, a.next_obs, a.terminal, *replay, B, S, A, st);
   }
   DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
   hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, fa);
@@ -689,6 +693,94 @@ extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
     s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
     s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
     rc = dyn_step_impl(who, s, nullptr, w.alive_next, 0.f, 0, stream, &hook);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// ---- open-loop error over recorded trajectories (the model fed the data's actions, compared with the data's outcomes) ----
+namespace mobody {
+struct ReplayWs {
+  float *next_obs, *penalty, *dyn;
+  uint8_t* terminal;
+  long long total;
+};
+static void replay_carve(int S, long long B, float* base, ReplayWs& w) {
+  long long off = 0;
+  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  w.next_obs = take(B * S); w.penalty = take(B);
+  w.dyn = take((long long)NENS * B * S + (long long)NENS * B);
+  w.terminal = (uint8_t*)take((B + 3) / 4);
+  w.total = off;
+}
+}  // namespace mobody
+
+extern "C" int64_t mobody_ens_replay_workspace(const MobodyEnsReplay* a) {
+  if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyEnsReplay) || a->B < 0 || a->S < 1 || a->A < 1)
+    return fail(MOBODY_E_ARG, "mobody_ens_replay_workspace: null struct, wrong struct_bytes, B < 0 or S, A < 1");
+  ReplayWs w;
+  replay_carve(a->S, a->B, nullptr, w);
+  return w.total;
+}
+
+// One launch for the row state, then H steps of 4 launches: member forward -> sample -> reward head -> accounting
+extern "C" int mobody_ens_replay(const MobodyEnsReplay* ap, void* stream) {
+  const char* who = "mobody_ens_replay";
+  MB_BLOCK(who, ap, MobodyEnsReplay);
+  const MobodyEnsReplay& a = *ap;
+  const int S = a.S, A = a.A, precision = a.precision;
+  const int64_t B = a.B;
+  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
+             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
+  MB_REQUIRE(B >= 0, "%s: B < 0", who);
+  MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
+  MB_REQUIRE(a.reset_every >= 0, "%s: reset_every < 0", who);
+  if (B == 0) return 0;
+  MB_REQUIRE(a.data_rows >= 1, "%s: data_rows %lld < 1", who, (long long)a.data_rows);
+  MB_REQUIRE(a.dyn_blob, "%s: null pointer dyn_blob", who);
+  MB_REQUIRE(a.data, "%s: null pointer data", who);
+  MB_REQUIRE(a.data->state, "%s: null pointer data->state", who);
+  MB_REQUIRE(a.data->action, "%s: null pointer data->action", who);
+  MB_REQUIRE(a.data->next_state, "%s: null pointer data->next_state", who);
+  MB_REQUIRE(a.data->reward, "%s: null pointer data->reward", who);
+  MB_REQUIRE(a.row0, "%s: null pointer row0", who);
+  MB_REQUIRE(a.elites, "%s: null pointer elites", who);
+  MB_REQUIRE(a.obs_state, "%s: null pointer obs_state", who);
+  MB_REQUIRE(a.act_state, "%s: null pointer act_state", who);
+  MB_REQUIRE(a.H == 0 || a.obs_err, "%s: null pointer obs_err", who);
+  MB_REQUIRE(a.H == 0 || a.rew_err, "%s: null pointer rew_err", who);
+  MB_REQUIRE(a.H == 0 || a.penalty, "%s: null pointer penalty", who);
+  MB_REQUIRE(a.H == 0 || a.term_model, "%s: null pointer term_model", who);
+  MB_REQUIRE(a.workspace, "%s: null pointer workspace", who);
+  MB_REQUIRE(a.data->pitch == 0 || a.data->pitch >= 2LL * S + A + 2, "%s: data->pitch %lld is neither 0 nor at least 2S + A + 2 = %d", who,
+             (long long)a.data->pitch, 2 * S + A + 2);
+  MB_REQUIRE(a.n_elites >= 1 && a.n_elites <= NENS, "%s: n_elites %d outside 1..7", who, a.n_elites);
+  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
+  if (rc) return rc;
+  MB_REQUIRE(precision == PREC_F32 || !a.mopo_blob || a.mopo_blob_T, "%s: the split-precision modes need the T blob of the MLP (mopo_blob_T)", who);
+  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d (task)", who, a.task);
+  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26 (task)", who);
+  MobodyDynLayout L;
+  rc = mobody_dyn_layout(S, A, &L);
+  if (rc) return rc;
+  ReplayWs w;
+  replay_carve(S, B, a.workspace, w);
+  hipStream_t st = as_stream(stream);
+  DynReplayHook hook{a.data, a.data_rows, (const long long*)a.row0, a.obs_state, a.act_state, nullptr, nullptr, nullptr, nullptr, 0, 0};
+  rc = launch_replay_init(hook, B, S, A, st);
+  if (rc) return rc;
+  for (int t = 0; t < a.H; ++t) {
+    MobodyEnsStep s{};
+    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
+    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = a.obs_state; s.act = a.act_state; s.B = B;
+    s.alive = nullptr; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
+    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.use_penalty = 0;
+    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
+    hook.obs_err = a.obs_err + (int64_t)t * B; hook.rew_err = a.rew_err + (int64_t)t * B; hook.penalty = a.penalty + (int64_t)t * B;
+    hook.term_model = a.term_model + (int64_t)t * B;
+    hook.t = t; hook.reset = a.reset_every > 0 && (t + 1) % a.reset_every == 0;
+    rc = dyn_step_impl(who, s, nullptr, nullptr, 0.f, 0, stream, nullptr, &hook);
     if (rc) return rc;
   }
   return 0;

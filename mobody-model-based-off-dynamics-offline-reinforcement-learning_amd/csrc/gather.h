@@ -13,6 +13,12 @@ __host__ __device__ inline bool view_packed(const MobodyBufferView& b, int S, in
          b.action == b.state + S && b.next_state == b.action + A && b.reward == b.next_state + S && b.not_done == b.reward + 1;
 }
 
+// Field pointers of row `row` of a view, either storage form (pitch 0: five contiguous arrays of their own widths).
+__host__ __device__ inline const float* view_state(const MobodyBufferView& b, long long row, int S) { return b.state + row * (b.pitch ? b.pitch : S); }
+__host__ __device__ inline const float* view_action(const MobodyBufferView& b, long long row, int A) { return b.action + row * (b.pitch ? b.pitch : A); }
+__host__ __device__ inline const float* view_next_state(const MobodyBufferView& b, long long row, int S) { return b.next_state + row * (b.pitch ? b.pitch : S); }
+__host__ __device__ inline const float* view_reward(const MobodyBufferView& b, long long row) { return b.reward + row * (b.pitch ? b.pitch : 1); }
+
 struct GatherArgs {
   MobodyBufferView bufs[3];
   int packed[3];            // view_packed(bufs[k])

@@ -751,3 +751,39 @@ def ens_evaluate(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, e
     a.workspace = ptr(ws)
     check(load().mobody_ens_evaluate(C.byref(a), cur_stream()), "mobody_ens_evaluate")
     return ws
+
+
+def replay_state(B, H, S, A, device):
+    """The caller-owned row state and tables of mobody_ens_replay: obs_state[B,S], act_state[B,A], obs_err / rew_err /
+    penalty float[H,B], term_model uint8[H,B].  Uninitialised: the call sets every word."""
+    f = dict(dtype=torch.float32, device=device)
+    return dict(obs_state=torch.empty(B, S, **f), act_state=torch.empty(B, A, **f), obs_err=torch.empty(H, B, **f),
+                rew_err=torch.empty(H, B, **f), penalty=torch.empty(H, B, **f),
+                term_model=torch.empty(H, B, dtype=torch.uint8, device=device))
+
+
+def ens_replay(dyn_blob, S, A, task_id, data, data_rows, row0, H, elites, seed, call0, state, reset_every=0, use_trg=True,
+               ws=None, dyn_planes=None, precision=0, mopo=None, uncertainty_mode=0, call_dev=None):
+    """Open-loop error of the model over B recorded windows of `data` (a RingView or a 5-tuple of separate tensors, rows in
+    dataset order) starting at the device int64 rows `row0` (mobody_ens_replay): the model is fed the recorded actions and
+    its state, reward and termination flag are compared with the recorded ones for H steps, into the tables of `state`
+    (replay_state).  reset_every = K > 0 puts the recorded next state back after every K-th step.  Returns the workspace."""
+    assert row0.dtype == torch.int64 and row0.dim() == 1
+    B = row0.shape[0]
+    assert state["obs_state"].shape == (B, S) and state["obs_err"].shape == (int(H), B)
+    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
+    view = buffer_view(data)
+    mb, mbt = mopo if mopo is not None else (None, None)
+    a = _lib.MobodyEnsReplay(C.sizeof(_lib.MobodyEnsReplay), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
+                             ptr(mbt), prec_id(precision), S, A, task_id, C.pointer(view), int(data_rows), ptr(row0), B, int(H),
+                             int(reset_every), len(elites), el, seed, call0, ptr(call_dev), int(bool(use_trg)),
+                             ptr(state["obs_state"]), ptr(state["act_state"]), ptr(state["obs_err"]), ptr(state["rew_err"]),
+                             ptr(state["penalty"]), ptr(state["term_model"]), None)
+    need = load().mobody_ens_replay_workspace(C.byref(a))
+    if need < 0:
+        raise _lib.MobodyError("mobody_ens_replay_workspace: " + load().mobody_last_error().decode())
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(max(need, 1), dtype=torch.float32, device=row0.device)
+    a.workspace = ptr(ws)
+    check(load().mobody_ens_replay(C.byref(a), cur_stream()), "mobody_ens_replay")
+    return ws

@@ -238,6 +238,35 @@ def model_eval_rows(starts, episodes, seed):
     return rng.choice(starts, size=episodes, replace=True)
 
 
+OPEN_LOOP_STEPS = (1, 2, 5, 10, 20, 50, 100, 200, 500, 1000)      # window steps whose error is logged (plus the horizon)
+
+
+def open_loop_windows(starts, n_rows, horizon, count, seed):
+    """`count` window starts for the open-loop model error (pure NumPy): a start i is valid iff the `horizon` rows
+    i .. i + horizon - 1 exist and belong to one episode, i.e. i + horizon <= n_rows and no episode start lies in
+    (i, i + horizon).  Distinct valid starts, sorted, from a seeded generator of its own (never the global one, and not
+    model_eval_rows's); all of them when there are fewer than `count`; ValueError naming the longest run of contiguous
+    rows when there is none."""
+    starts = np.asarray(starts, dtype=np.int64)
+    n_rows, horizon = int(n_rows), int(horizon)
+    if horizon < 1:
+        raise ValueError(f"open_loop_windows: horizon {horizon} must be at least 1")
+    is_start = np.zeros(n_rows + 1, dtype=np.int64)
+    is_start[starts[starts < n_rows]] = 1
+    inside = np.cumsum(is_start)                                 # inside[j] = episode starts in [0, j]
+    i = np.arange(max(n_rows - horizon + 1, 0), dtype=np.int64)
+    valid = i[inside[i + horizon - 1] - inside[i] == 0]          # none in (i, i + horizon)
+    if valid.size == 0:
+        edges = np.unique(np.concatenate([[0], starts[starts < n_rows], [n_rows]]))
+        longest = int(np.max(np.diff(edges))) if n_rows > 0 else 0
+        raise ValueError(f"open_loop_windows: no window of {horizon} contiguous rows in the {n_rows} rows of the dataset "
+                         f"(the longest run of contiguous rows is {longest})")
+    if valid.size <= count:
+        return valid
+    rng = np.random.default_rng([int(seed), 0x4F4C])
+    return np.sort(rng.choice(valid, size=int(count), replace=False))
+
+
 def dynamics_save_path(args, root):
     """`<root>/<env>/srcdatatype-<src>-tardatatype-<tar>-<shift>` (train_mobody.py:822-823, 843-844)."""
     return os.path.join(root, args.env, f"srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}")
@@ -383,6 +412,19 @@ def _run(args, rank, world, device):
         tar_rb.convert_D4RL(tar_ds)
         say(f"datasets: {src_rb.size} source / {tar_rb.size} target transitions")
 
+    # Open-loop error of the learned target model over recorded target trajectories: two optional keys of the merged config,
+    # off by default.  Rank 0 measures.  The windows are chosen once, here, before any model is built or trained: a horizon
+    # longer than every episode of the target data ends the run now, not at the first evaluation.
+    ol_rows, ol_h = None, int(config.get("model_error_horizon", 0))
+    if ol_h > 0:
+        if not uses_model(args.policy):
+            say(f"model_error_horizon / model_error_windows ignored: {args.policy} has no model to measure")
+        elif rank == 0:
+            n = tar_rb.size
+            term = 1.0 - tar_rb.not_done[:n].cpu().numpy()
+            ol_rows = open_loop_windows(episode_starts(tar_rb.state[:n].cpu().numpy(), tar_rb.next_state[:n].cpu().numpy(), term),
+                                        n, ol_h, int(config.get("model_error_windows", 256)), args.seed)
+
     outdir = f"{args.dir}/{args.policy}/{args.env}-srcdatatype-{args.srctype}-tardatatype-{args.tartype}-{args.shift_level}/r{args.seed}{args.out_dir_remark}"
     writer = None
     if args.scalars:                                                                   # train_mobody.py:455-458
@@ -440,6 +482,17 @@ def _run(args, rank, world, device):
                 err = dynamics.model_error(s_, a_, s2_, r_)
                 writer.add_scalar("test/model error next_obs", err["obs_mse"], global_step=t + 1)
                 writer.add_scalar("test/model error reward", err["reward_mse"], global_step=t + 1)
+            if writer is not None and ol_rows is not None:
+                # the compounding-error curve (the model fed the recorded actions, reset_every = 0) and, on the same
+                # windows, the one-step error at every offset (reset_every = 1); one host read per call
+                ol = policy.open_loop_error(tar_rb, ol_rows, ol_h)
+                curve = torch.stack([ol["obs_err_mean"], ol["rew_mse"], ol["term_agree"]]).tolist()
+                for k in sorted({k for k in OPEN_LOOP_STEPS if k <= ol_h} | {ol_h}):
+                    writer.add_scalar(f"test/open-loop obs error h{k}", curve[0][k - 1], global_step=t + 1)
+                    writer.add_scalar(f"test/open-loop reward mse h{k}", curve[1][k - 1], global_step=t + 1)
+                    writer.add_scalar(f"test/open-loop term agree h{k}", curve[2][k - 1], global_step=t + 1)
+                one = policy.open_loop_error(tar_rb, ol_rows, ol_h, reset_every=1)["obs_err_mean"].mean().reshape(1).tolist()
+                writer.add_scalar("test/one-step obs error", one[0], global_step=t + 1)
             if writer is not None and eval_obs is not None:
                 # eval_policy_batch's return (:60-98) with the learned target model in the simulator's place: an ESTIMATE
                 # whose error grows with the horizon -- hence tags of its own, never the simulator's 'test/target return'
