@@ -558,6 +558,53 @@ int mobody_actor_backward(const MobodyActor* a, void* stream);
 int mobody_td3bc_actor_forward(const MobodyActor* a, void* stream);
 int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream);
 
+/* ---- IQL baseline (the reference's algo/offline_offline/iql.py) -----------------------------------------------
+ * One block type for the step's three calls, in the step's order; each call reads the fields named for it, `grad` / `m, v` /
+ * `t` / `t_dev` / `lr` are those of the net the call trains (gradient form or fused form by the rule above).  Every row is
+ * trained on (d.Nt is not read).  All nets are packed MLPs: V = mobody_mlp_layout(S, 1, 1), twin-Q = (S + A, 1, 2), the policy
+ * = (S, 2 A, 1) whose first A outputs are mu and whose last A (logstd) take an exactly zero gradient.  The T blobs are read in
+ * every precision (the backward streams them) and written by the fused forms.
+ *   mobody_iql_value    iql.py:174-185, :217-220.  Forwards target-Q(s, a) and V(s) (one launch), then V's backward with the
+ *                       expectile seed formed in its prologue: adv = min(Qt1, Qt2) - V, L_V = mean(|lam - 1[adv < 0]| adv^2).
+ *                       Reads v_blob(_T), qtarg_blob(_T), state, action; writes adv[N], loss_out[0] = local share of L_V and,
+ *                       when log_out != NULL, log_out[0] = sum adv / N_global, log_out[1] = sum V / N_global (train/adv, train/value).
+ *   mobody_iql_critic   iql.py:187-196, :222-228.  V(s') with the updated V next to Q(s, a) (one launch), then mobody_critic's
+ *                       backward and update with y = r + nd gamma V(s') (its q_next form): Adam on q_blob, Polyak on qtarg_blob.
+ *                       Reads v_blob(_T), q_blob(_T), qtarg_blob(_T), state .. not_done, bump; loss_out[0] = L_Q.
+ *   mobody_iql_actor    iql.py:91-95, :198-202, :233-237.  The policy forward (linear 2 A outputs), then its backward with the
+ *                       advantage-weighted regression seed in the prologue: w = min(exp(temp adv), 100) from the adv of
+ *                       mobody_iql_value (V before its update), L_pi = mean over N A of w (tanh(mu) - a)^2 -- no max_action.
+ *                       Fused form: the Adam step runs at the cosine learning rate of gradient step k (t, or t_dev[0]),
+ *                       lr (1 + cos(pi (k - 1) / T_max)) / 2, formed in double and rounded to fp32; with t_dev on the device.
+ *                       The gradient form writes `grad` only (the caller steps with the scheduled rate).
+ *                       Reads pi_blob(_T), state, action, adv; loss_out[0] = L_pi.
+ * The same workspace (mobody_iql_workspace floats) for all three.
+ * Refused with MOBODY_E_ARG before any runtime call, with the field named: 2 A > 128, lam outside (0, 1), T_max < 1 (actor).
+ * (Declared as a tagged struct plus its typedef, as MobodyEnsEval.) */
+typedef struct MobodyIql MobodyIql;
+struct MobodyIql {
+  int32_t struct_bytes;
+  int32_t reserved;         /* 0 */
+  MobodyTrainDims d;
+  MobodyHyper h;            /* gamma, tau, precision are read */
+  float lam, temp;
+  int64_t T_max;
+  float *v_blob, *v_blob_T, *q_blob, *q_blob_T, *qtarg_blob, *qtarg_blob_T, *pi_blob, *pi_blob_T;
+  const float *state, *action, *next_state, *reward, *not_done;
+  float* adv;
+  float* grad;
+  float *m, *v;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  int64_t* bump;            /* mobody_iql_critic, as MobodyCritic.bump */
+  float *loss_out, *log_out, *workspace;
+};
+int64_t mobody_iql_workspace(const MobodyTrainDims* d);
+int mobody_iql_value(const MobodyIql* a, void* stream);
+int mobody_iql_critic(const MobodyIql* a, void* stream);
+int mobody_iql_actor(const MobodyIql* a, void* stream);
+
 /* Expectile loss of the V function (update_v_function, mobody.py:231-242): adv = min(qt[0],qt[1]) - v;
  * dz3[N][16] column 0 = dL_V/dV (1/N_global scaling), loss_out[0] = local share of L_V; lossp_ws: ceil(N/256) floats. */
 int mobody_value_loss_grad(const float* qt, const float* v, int64_t N, int64_t N_global, float* dz3, float* loss_out,

@@ -119,6 +119,14 @@ class MobodyActor(C.Structure):
                 ("loss_out", vp)]
 
 
+class MobodyIql(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("reserved", i32), ("d", MobodyTrainDims), ("h", MobodyHyper), ("lam", f32), ("temp", f32),
+                ("T_max", i64), ("v_blob", vp), ("v_blob_T", vp), ("q_blob", vp), ("q_blob_T", vp), ("qtarg_blob", vp),
+                ("qtarg_blob_T", vp), ("pi_blob", vp), ("pi_blob_T", vp), ("state", vp), ("action", vp), ("next_state", vp),
+                ("reward", vp), ("not_done", vp), ("adv", vp), ("grad", vp), ("m", vp), ("v", vp), ("t", i64), ("t_dev", vp),
+                ("lr", f32), ("bump", vp), ("loss_out", vp), ("log_out", vp), ("workspace", vp)]
+
+
 class MobodyAdam(C.Structure):
     _fields_ = [("struct_bytes", i32), ("in_dim", i32), ("out_dim", i32), ("members", i32), ("blob", vp), ("blob_T", vp),
                 ("grad", vp), ("m", vp), ("v", vp), ("target", vp), ("target_T", vp), ("t", i64), ("t_dev", vp), ("lr", f32), ("tau", f32),
@@ -145,7 +153,7 @@ def block(cls, **fields):
     return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
 
 
-BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
+BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -209,6 +217,10 @@ PROTOTYPES = {
     "mobody_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_td3bc_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_td3bc_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_iql_workspace": (i64, [C.POINTER(MobodyTrainDims)]),
+    "mobody_iql_value": (C.c_int, [C.POINTER(MobodyIql), vp]),
+    "mobody_iql_critic": (C.c_int, [C.POINTER(MobodyIql), vp]),
+    "mobody_iql_actor": (C.c_int, [C.POINTER(MobodyIql), vp]),
     "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),

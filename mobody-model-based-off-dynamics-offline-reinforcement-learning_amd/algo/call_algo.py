@@ -3,19 +3,21 @@
 `call_algo(algo_name, config, mode, device, **kwargs)` lower-cases the name, looks the class up
 and returns `cls(config, device)`; `mode` and kwargs are accepted and ignored exactly as the
 reference does.  Unknown names raise KeyError like the reference's dict lookup.  Of the baseline
-algorithms TD3_BC is built (`offline_offline/td3_bc.py`); dara, bosa, iql and igdf are outside the accelerated path.
+algorithms TD3_BC (`offline_offline/td3_bc.py`) and IQL (`offline_offline/iql.py`) are built (IQL from an IQL config only: without `lam`,
+`temp`, `max_step` its constructor raises NotImplementedError); dara, bosa and igdf are outside the accelerated path.
 """
 from .offline_offline.mobody import MOBODY
 from .offline_offline.td3_bc import TD3BC
+from .offline_offline.iql import IQL
 
-_BASELINES = ("dara", "bosa", "iql", "igdf")
+_BASELINES = ("dara", "bosa", "igdf")
 
 
 def call_algo(algo_name, config, mode, device, **kwargs):
     algo_name = algo_name.lower()
-    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC}
+    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC, "iql": IQL}
     if algo_name in _BASELINES:
         raise NotImplementedError(f"'{algo_name}' is a reference baseline outside the MI355X-accelerated path; "
-                                  "only 'mobody' and 'td3_bc' are built here")
+                                  "only 'mobody', 'td3_bc' and 'iql' are built here")
     algo = algo_to_call[algo_name]          # KeyError for unknown names, as in the reference
     return algo(config, device)

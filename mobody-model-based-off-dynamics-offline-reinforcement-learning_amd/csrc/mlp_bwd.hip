@@ -166,7 +166,57 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   const int Np3 = a.Np3;
   const int t = threadIdx.x;
   float l0 = 0.f, l1 = 0.f;
-  if constexpr (SEED == 4) {                          // mode 4: eight threads per row (TB * 8 == NTHREADS)
+  if constexpr (SEED == 5) {                          // mode 5: one thread per row, all in wave 0 (TB <= 64)
+    static_assert(MLP_TILE_ROWS <= 64, "mode 5 reduces its three partial sums inside wave 0");
+    const IqlSeed& q = sd.iq;
+    if (t < 64) {
+      const bool ok = t < rows_here;
+      const long long row = row0 + (ok ? t : 0);
+      const float q0 = q.qt[row], q1 = q.qt[a.rows + row], vv = q.v[row];
+      const float adv = fminf(q0, q1) - vv;
+      const float w = fabsf(q.lam - (adv < 0.f ? 1.f : 0.f));
+      const float v = ok ? -2.f * w * adv * q.inv : 0.f;
+      float s0 = ok ? w * adv * adv : 0.f, s1 = ok ? adv : 0.f, s2 = ok ? vv : 0.f;
+      if (t < TB) Xs[t] = v;
+      if (ok) {
+        q.adv_out[row] = adv;
+        float* g = sd.dz3_out + row * Np3;
+        g[0] = v;
+        for (int c = 1; c < Np3; ++c) g[c] = 0.f;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) { s0 += __shfl_xor(s0, o); s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+      if (t == 0) {
+        const long long T = cdiv(a.rows, (long long)TB);
+        sd.lossp[tile] = s0; sd.lossp[T + tile] = s1; sd.lossp[2 * T + tile] = s2;
+      }
+    }
+    return;
+  } else if constexpr (SEED == 6) {                   // mode 6: one thread per (row, column)
+    const IqlSeed& q = sd.iq;
+    if (tile == 0 && t == 0 && q.bc_out != nullptr) { // the policy's Adam constants at this step's cosine learning rate
+      const long long k = q.t_dev[0];
+      const double kd = (double)k;
+      q.bc_out[0] = (float)((double)cosine_lr(q.lr0, k, q.T_max) / (1.0 - pow(0.9, kd)));
+      q.bc_out[1] = (float)sqrt(1.0 - pow(0.999, kd));
+    }
+    for (int e = t; e < TB * Np3; e += NTHREADS) {
+      const int rr = e / Np3, j = e - rr * Np3;
+      const bool ok = rr < rows_here && j < q.A;
+      const long long row = row0 + (rr < rows_here ? rr : 0);
+      const int jc = j < q.A ? j : 0;
+      const float z = q.z[row * q.ldz + jc], av = q.act[row * q.A + jc], adv = q.adv[row];   // unconditional, clamped
+      float v = 0.f;                                  // columns >= A (logstd, padding) and rows past the batch: exactly 0
+      if (ok) {
+        const float w = fminf(expf(q.temp * adv), 100.f);      // e may be inf: the clamp comes first, nothing multiplies e
+        const float th = tanhf(z), df = th - av;
+        v = 2.f * w * df * (1.f - th * th) * q.inv;
+        l0 += w * (df * df);
+      }
+      Xs[rr * LDX + j] = v;
+      if (rr < rows_here) sd.dz3_out[(row0 + rr) * Np3 + j] = v;
+    }
+  } else if constexpr (SEED == 4) {                   // mode 4: eight threads per row (TB * 8 == NTHREADS)
     static_assert(MLP_TILE_ROWS * 8 == NTHREADS, "mode 4 spreads a row's A <= 24 action columns over eight lanes");
     // sq = sum_j (pi - a)^2 needs A words of pi and of act per row: lane `sub` of a row's eight takes columns sub, sub + 8,
     // sub + 16 (A <= 24, checked by the launcher), all requested beside q0, q1 and stats[0] -- one round trip -- and the eight
@@ -282,6 +332,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
     if constexpr (SEED == SEED_RT) sd.lossp[tile * 2 + m] = l0;
+    else if constexpr (SEED == 6) sd.lossp[tile] = l0;
     else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
 }
@@ -322,7 +373,7 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
   // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
   // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
   // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
-  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4);
+  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4 || SEED == 5);
   constexpr bool with_db = SEED != 2 && SEED != 4;
   const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
@@ -1080,7 +1131,7 @@ int mlp3_weight_grads(const Mlp3WgradArgs& a, hipStream_t st) {
   g.job[2] = WgradJob{a.dz3, rows * L.Np3, L.Np3, L.Np3, a.h2, hs, HID, HID, L.w3, L.Np3, L.Np3, HID, 1, 0, 0, 0};
   GradReduceArgs r{L, a.slabs, slab_stride, a.nsplit, a.dbp, a.ntiles, a.grad, a.loss, a.adam, nullptr};
   if (a.bc_ws != nullptr && a.adam.on && a.adam.t_dev != nullptr) {
-    g.bc_out = a.bc_ws; g.bc_t = a.adam.t_dev; g.bc_lr = a.adam.lr;
+    if (!a.bc_ready) { g.bc_out = a.bc_ws; g.bc_t = a.adam.t_dev; g.bc_lr = a.adam.lr; }
     r.bc_dev = a.bc_ws;
   }
   int rc = launch_wgrad(g, st);
@@ -1095,6 +1146,48 @@ int launch_grad_reduce(const GradReduceArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)(wblocks + bblocks + lblocks)), dim3(256), 0, st, a);
   MB_LAUNCH_OK("k_grad_reduce");
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// IQL's two trained one-member nets: the backward of k_mlp3_bwd<false, 0, 1, PM> with the seed form compiled in --
+// mode 5, the expectile seed of the V net (rank-1 output layer), or mode 6, the advantage-weighted regression seed of the
+// policy net (K = Np3 GEMM).  Instances of their own: no kernel that existed before them changes.
+// ------------------------------------------------------------------------------------------------
+template <int PM, int SEED>
+__global__ __launch_bounds__(NTHREADS, 3) void k_mlp3_bwd_seed(Mlp3BwdArgs a) {
+  __shared__ float red[8];
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  mlp3_bwd_tile<false, 0, 1, PM, SEED>(a, 0, blockIdx.x, 1, Xs, red);
+}
+
+template <int PM, int SEED>
+static int launch_bwd_seed_t(const Mlp3BwdArgs& a, hipStream_t st) {
+  constexpr size_t lds = split_lds_bytes<(PM > 0 ? PM : 1), MLP_TILE_ROWS>();
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_bwd_seed<PM, SEED>, lds);
+    if (rc) return rc;
+    once = true;
+  }
+  ProfScope prof(PROF_MLP_BWD, st);
+  hipLaunchKernelGGL((k_mlp3_bwd_seed<PM, SEED>), dim3((unsigned)cdiv(a.rows, MLP_TILE_ROWS)), dim3(NTHREADS), lds, st, a);
+  MB_LAUNCH_OK("k_mlp3_bwd_seed");
+  return 0;
+}
+template <int PM>
+static int launch_bwd_seed_m(const Mlp3BwdArgs& a, hipStream_t st) {
+  return a.seed.mode == 5 ? launch_bwd_seed_t<PM, 5>(a, st) : launch_bwd_seed_t<PM, 6>(a, st);
+}
+
+int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st) {
+  MB_REQUIRE((a.seed.mode == 5 || a.seed.mode == 6) && a.m1 && a.m2 && !a.swish && a.seed.dz3_out && a.seed.lossp,
+             "launch_mlp3_bwd_seed: seed mode %d: needs mode 5 or 6 of a ReLU net with sign words", a.seed.mode);
+  MB_REQUIRE(a.seed.mode != 5 || a.Np3 == 16, "launch_mlp3_bwd_seed: seed mode 5 seeds a one-output net (Np3=%d)", a.Np3);
+  if (a.rows <= 0) return 0;
+  if (a.prec != PREC_F32 && a.w2t_planes != nullptr)
+    return a.prec == PREC_BF16 ? launch_bwd_seed_m<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_seed_m<2>(a, st)
+         : a.prec == PREC_BF16X3 ? launch_bwd_seed_m<3>(a, st) : launch_bwd_seed_m<4>(a, st);
+  return launch_bwd_seed_m<0>(a, st);
 }
 
 }  // namespace mobody

@@ -51,15 +51,39 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 // Where each runs: launch_mlp3_bwd (k_mlp3_bwd) takes modes 0 and 1 and chooses between them at run time; modes 2 and 3 exist
 // only as the two tiles of launch_actor_bwd_chain (k_actor_bwd_chain), compiled in, with mode 2's dx / bcw handed to mode 3 in
 // agent-scope stores and loads; mode 4 is mode 2's alternative as the first tile (the chain's third template argument).
+//   5  IQL's V net (iql.py:174-185, asymmetric_l2_loss :117-118), one output: adv = min(qt[0], qt[1]) - v,
+//        dz3[row][0] = -2 |lam - 1[adv < 0]| adv / N_global; adv_out[row] = adv (the policy phase's weights come from it);
+//        lossp[tile] = sum |lam - 1[adv<0]| adv^2, lossp[T + tile] = sum adv, lossp[2 T + tile] = sum v (T row tiles)
+//   6  IQL's policy net (update_policy + bc_loss, iql.py:91-95, :198-202), Np3 = pad16(2 A) outputs of which the first A are mu:
+//        w = min(exp(temp * adv[row]), 100), th = tanh(z[row][j]);  j < A: dz3 = 2 w (th - a)(1 - th^2) / (N_global A), j >= A: 0
+//        (the logstd half takes no gradient); lossp[tile] = sum w (th - a)^2.  Its first tile also forms, from the device step
+//        count, the Adam constants of the policy's cosine learning rate for the k_grad_reduce launch behind it (bc_out).
+// Modes 5 and 6 run in launch_mlp3_bwd_seed (k_mlp3_bwd_seed), compiled in; their row-wise arguments are `iq`, which shares the
+// bytes of `ar`.
+struct IqlSeed {
+  const float *qt, *v;         // mode 5: [2][rows] target twin-Q(s, a), [rows] V(s)
+  const float *z, *act, *adv;  // mode 6: [rows][ldz] linear policy outputs, [rows][A] actions, [rows] adv of mode 5
+  float* adv_out;              // mode 5
+  float* bc_out;               // mode 6, or null: {lr_k / (1 - 0.9^k), sqrt(1 - 0.999^k)}, k = t_dev[0]
+  const long long* t_dev;
+  long long T_max;
+  float lam, temp, inv, lr0;   // inv: 1 / N_global (mode 5), 1 / (N_global A) (mode 6)
+  int A, ldz;
+};
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
   union { float gamma; float exp_scale; };   // mode 1: the discount; mode 4: the exponent scale k of the BC weight
   float inv_ng;
-  ActorRowArgs ar;                           // modes 2, 3, 4
+  union {
+    ActorRowArgs ar;                         // modes 2, 3, 4
+    IqlSeed iq;                              // modes 5, 6
+  };
   float* dz3_out;
   float* lossp;
 };
+static_assert(sizeof(IqlSeed) <= sizeof(ActorRowArgs) && alignof(IqlSeed) == alignof(ActorRowArgs),
+              "IqlSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
 
 struct Mlp3BwdArgs {
   BwdSeed seed;
@@ -91,6 +115,12 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
 // tile's two member workgroups to finish runs that tile's actor backward (mlp_bwd.hip k_actor_bwd_chain).  tickets: one int per
 // row tile, zero on entry and on exit.
 int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st);
+// one net (member 0), sign words, seed mode 5 or 6 formed in the prologue; no dx
+int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st);
+// learning rate of 1-based gradient step k under CosineAnnealingLR(T_max), eta_min 0 (closed form, in double, rounded to fp32 once)
+__host__ __device__ inline float cosine_lr(float lr0, long long k, long long T_max) {
+  return (float)((double)lr0 * (1.0 + cos(3.14159265358979323846 * (double)(k - 1) / (double)T_max)) * 0.5);
+}
 
 // ---- host side: the one place an Mlp3BwdArgs is filled; each helper owns one group of fields (the seed and dx are the caller's).
 // launch_mlp3_bwd picks its kernel from swish, prec + w2t_planes and m1 + m2, so every caller states those explicitly. ----
@@ -351,6 +381,8 @@ struct Mlp3WgradArgs {
   LossFinal loss;
   AdamTarget adam;
   int prec;
+  int bc_ready;            // bc_ws already holds the constants of adam.t_dev[0] (an earlier launch formed them): the weight-gradient
+                           // launch does not
 };
 int mlp3_weight_grads(const Mlp3WgradArgs& a, hipStream_t st);
 

@@ -263,13 +263,14 @@ extern "C" int64_t mobody_train_workspace(const MobodyTrainDims* d) {
   return w.total;
 }
 
-static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* stream) {
+// extra (with q_next, or null): a one-member forward that shares the launch of Q(s, a) -- IQL's V(s'), which writes q_next
+static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* stream, const char* who = "mobody_critic",
+                       const Mlp3FwdArgs* extra = nullptr) {
   // gather != null (phase 0, q_next == null): state .. not_done are not read by the first forward launch but WRITTEN by it --
   // its tiles draw and fetch the minibatch rows themselves (layers.h FwdGather; the block arrives with `g` filled)
   // phase: 0 the whole step; 1 only its forwards (nothing of them reads `reward`); 2 only the backward, weight gradients and
   // reduction / optimizer step -- the caller may let another stream finish rewriting `reward` (penalty_type 'par': an ensemble
   // step on the source rows) between the two
-  const char* who = "mobody_critic";
   const MobodyTrainDims* d = &a.d;
   const MobodyHyper* h = &a.h;
   const bool fused = a.m != nullptr;
@@ -328,7 +329,8 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
       else if (!rc) rc = launch_mlp3_forward(ft, 2, ACT_RELU, prec, st);
     }
   } else {
-    rc = launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);                  // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229)
+    // q_next = V(s') supplied by the caller (update_q_functions_1, :210-229), or evaluated beside Q(s, a) (`extra`)
+    rc = extra != nullptr ? launch_mlp3_forward(fq, 2, *extra, 1, ACT_RELU, prec, st) : launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);
   }
   if (rc || a.phase == 1) return rc;
   const float invNg = 1.f / (float)d->N_global;
@@ -486,6 +488,187 @@ extern "C" int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream) {
   MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
   MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
   return actor_backward_impl(*a, stream, who, true);
+}
+
+// ---- IQL (the reference's algo/offline_offline/iql.py): V with the expectile seed, twin-Q against V(s') through critic_impl, the
+// policy with the advantage-weighted regression seed and a cosine learning rate.  DESIGN 5r. ----
+namespace mobody {
+// training scratch of one one-member net on the step's N rows
+struct IqlNetWs {
+  float *out, *x, *h1, *h2, *dz3, *dz2, *dz1, *dbp, *slabs, *lossp, *bc;
+  uint32_t *m1, *m2;
+  int *e_h1, *e_dz2;
+  int nsplit, ntiles;
+};
+struct IqlWs {
+  TrainWs tw;              // the critic's scratch, where mobody_critic carves it
+  MobodyMlpLayout Lv, Lp;
+  IqlNetWs v, p;
+  float *qt, *vnext;       // target twin-Q(s, a) [2][N], V(s') [N]
+  long long total;
+};
+
+static int carve_iql(const MobodyTrainDims& d, float* base, IqlWs& w) {
+  int rc = carve(d, base, w.tw);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(d.S, 1, 1, &w.Lv);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(d.S, 2 * d.A, 1, &w.Lp);
+  if (rc) return rc;
+  const long long N = d.N, N32 = (N + 31) & ~31LL, mw = cdiv(N, 32) * HID;
+  long long off = w.tw.total;
+  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  auto net = [&](const MobodyMlpLayout& L, IqlNetWs& n, int nloss) {
+    n.ntiles = (int)cdiv(N, MLP_TILE_ROWS); n.nsplit = wgrad_nsplit(N, 1);
+    n.out = take(N * L.out_dim); n.x = take(N * L.Kp1); n.h1 = take(N32 * HID); n.h2 = take(N * HID);
+    n.m1 = (uint32_t*)take(mw); n.m2 = (uint32_t*)take(mw);
+    n.e_h1 = (int*)take(N32 / 32); n.e_dz2 = (int*)take(N32 / 32);
+    n.dz3 = take(N * L.Np3); n.dz2 = take(N32 * HID); n.dz1 = take(N * HID);
+    n.dbp = take((long long)n.ntiles * (2 * HID + L.Np3));
+    n.slabs = take(((L.total_floats + 3) & ~3LL) * n.nsplit);
+    n.lossp = take((long long)nloss * n.ntiles); n.bc = take(4);
+  };
+  net(w.Lv, w.v, 3);
+  net(w.Lp, w.p, 1);
+  w.qt = take(2 * N); w.vnext = take(N);
+  w.total = off;
+  return 0;
+}
+
+// what the three entry points check alike, before any runtime call
+static int iql_check(const MobodyIql* a, const char* who) {
+  MB_BLOCK(who, a, MobodyIql);
+  int rc = check_dims(&a->d, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->d.S >= 1 && a->d.A >= 1 && 2 * a->d.A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, a->d.A);
+  MB_REQUIRE(a->lam > 0.f && a->lam < 1.f, "%s: lam %g outside (0, 1)", who, (double)a->lam);
+  MB_REQUIRE((a->grad != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad || (a->m && a->v), "%s: null pointer", who);
+  MB_REQUIRE(a->m == nullptr || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  MB_REQUIRE(a->state && a->action && a->loss_out && a->workspace, "%s: null pointer", who);
+  return check_precision(who, a->h.precision, true);
+}
+
+// dW, db of one of the two nets from what its forward and backward left, the loss scalar and (fused) the Adam step
+static int iql_weight_grads(const MobodyMlpLayout& L, const IqlNetWs& n, long long N, float* grad, const LossFinal& lf,
+                            const AdamTarget& adam, int prec, bool bc_ready, hipStream_t st) {
+  Mlp3WgradArgs g = wgrad_net(L, N, n.nsplit);
+  wgrad_set_saves(g, n.x, 0, n.h1, n.h2, n.e_h1);
+  wgrad_set_grads(g, n.dz3, n.dz2, n.dz1, n.dbp, n.ntiles, n.e_dz2);
+  wgrad_set_scratch(g, n.slabs, n.bc);
+  wgrad_set_result(g, grad, lf, adam, prec);
+  g.bc_ready = bc_ready ? 1 : 0;
+  return mlp3_weight_grads(g, st);
+}
+}  // namespace mobody
+
+extern "C" int64_t mobody_iql_workspace(const MobodyTrainDims* d) {
+  if (check_dims(d, "mobody_iql_workspace")) return -1;
+  if (d->S < 1 || d->A < 1 || 2 * d->A > 128) { fail(MOBODY_E_ARG, "mobody_iql_workspace: d.A %d: 2 A > 128", d->A); return -1; }
+  IqlWs w;
+  if (carve_iql(*d, nullptr, w)) return -1;
+  return w.total;
+}
+
+// iql.py:174-185 (update_v_function), :217-220
+extern "C" int mobody_iql_value(const MobodyIql* a, void* stream) {
+  const char* who = "mobody_iql_value";
+  int rc = iql_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->v_blob && a->v_blob_T && a->qtarg_blob && a->adv, "%s: null pointer", who);
+  const int prec = a->h.precision;
+  MB_REQUIRE(prec == PREC_F32 || a->qtarg_blob_T, "%s: the split-precision modes need qtarg_blob_T", who);
+  IqlWs w;
+  rc = carve_iql(a->d, a->workspace, w);
+  if (rc) return rc;
+  const bool fused = a->m != nullptr;
+  const AdamTarget adam = fused ? adam_target(a->v_blob, a->v_blob_T, a->m, a->v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
+  hipStream_t st = as_stream(stream);
+  const long long N = a->d.N;
+  const int S = a->d.S, A = a->d.A;
+  const float *vT = prec != PREC_F32 ? a->v_blob_T : nullptr, *tT = prec != PREC_F32 ? a->qtarg_blob_T : nullptr;
+  // target twin-Q(s, a) (no grad, :175-177) and V(s) with its saves (:179) read the same rows: one launch
+  const Mlp3FwdArgs ft = fwd_args(a->qtarg_blob, w.tw.Lq, a->state, S, a->action, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
+  const Mlp3FwdArgs fv = fwd_args(a->v_blob, w.Lv, a->state, S, nullptr, 0, N, w.v.out, 0, 1.f, w.v.x, w.v.h1, w.v.h2, w.v.m1, w.v.m2, vT,
+                                  prec == PREC_F16X2 ? w.v.e_h1 : nullptr);
+  rc = launch_mlp3_forward(ft, 2, fv, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  const float invNg = 1.f / (float)a->d.N_global;
+  Mlp3BwdArgs b = bwd_args(w.Lv, a->v_blob_T, nullptr, w.v.h1, w.v.h2, N, w.v.dz2, w.v.dz1, w.v.dbp, w.v.m1, w.v.m2, prec, w.v.e_dz2);
+  b.seed.mode = 5; b.seed.iq.qt = w.qt; b.seed.iq.v = w.v.out; b.seed.iq.adv_out = a->adv; b.seed.iq.lam = a->lam; b.seed.iq.inv = invNg;
+  b.seed.dz3_out = w.v.dz3; b.seed.lossp = w.v.lossp;
+  rc = launch_mlp3_bwd_seed(b, st);
+  if (rc) return rc;
+  LossFinal lf{};
+  lf.kind = 1; lf.nparts = w.v.ntiles; lf.scale = invNg; lf.parts = w.v.lossp; lf.out = a->loss_out;
+  rc = iql_weight_grads(w.Lv, w.v, N, a->grad, lf, adam, prec, false, st);
+  if (rc || a->log_out == nullptr) return rc;
+  // the logged scalars of a logging step (:181-183): two more partial sums of the seed prologue
+  for (int k = 0; k < 2; ++k) {
+    hipLaunchKernelGGL(k_sum_scale, dim3(1), dim3(256), 0, st, w.v.lossp + (long long)(k + 1) * w.v.ntiles, w.v.ntiles, invNg, a->log_out + k);
+    MB_LAUNCH_OK("k_sum_scale");
+  }
+  return 0;
+}
+
+// iql.py:187-196 (update_q_functions), :222-228
+extern "C" int mobody_iql_critic(const MobodyIql* a, void* stream) {
+  const char* who = "mobody_iql_critic";
+  int rc = iql_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->v_blob && a->v_blob_T && a->q_blob && a->q_blob_T && a->qtarg_blob && a->next_state && a->reward && a->not_done, "%s: null pointer", who);
+  IqlWs w;
+  rc = carve_iql(a->d, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->h.precision;
+  MobodyCritic c{};
+  c.struct_bytes = (int32_t)sizeof(MobodyCritic);
+  c.d = a->d; c.h = a->h;
+  c.q_blob = a->q_blob; c.q_blob_T = a->q_blob_T; c.qtarg_blob = a->qtarg_blob; c.qtarg_blob_T = a->qtarg_blob_T;
+  c.state = const_cast<float*>(a->state); c.action = const_cast<float*>(a->action); c.next_state = const_cast<float*>(a->next_state);
+  c.reward = const_cast<float*>(a->reward); c.not_done = const_cast<float*>(a->not_done);
+  c.q_next = w.vnext; c.grad_q = a->grad; c.m = a->m; c.v = a->v; c.t = a->t; c.t_dev = a->t_dev; c.lr = a->lr;
+  c.loss_out = a->loss_out; c.workspace = a->workspace; c.bump = a->bump;
+  // V(s') with the V net mobody_iql_value has just updated (:189), beside Q(s, a)
+  const Mlp3FwdArgs fvn = fwd_args(a->v_blob, w.Lv, a->next_state, a->d.S, nullptr, 0, a->d.N, w.vnext, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   prec != PREC_F32 ? a->v_blob_T : nullptr);
+  return critic_impl(c, nullptr, stream, who, &fvn);
+}
+
+// iql.py:91-95 (bc_loss), :198-202 (update_policy), :233-237
+extern "C" int mobody_iql_actor(const MobodyIql* a, void* stream) {
+  const char* who = "mobody_iql_actor";
+  int rc = iql_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->T_max >= 1, "%s: T_max %lld < 1", who, (long long)a->T_max);
+  MB_REQUIRE(a->pi_blob && a->pi_blob_T && a->adv, "%s: null pointer", who);
+  IqlWs w;
+  rc = carve_iql(a->d, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->h.precision;
+  const bool fused = a->m != nullptr, dev = fused && a->t_dev != nullptr;
+  // the step's learning rate: from the host count here, from the device count in the backward launch's first tile
+  const float lr_k = dev || !fused ? a->lr : cosine_lr(a->lr, a->t, a->T_max);
+  const AdamTarget adam = fused ? adam_target(a->pi_blob, a->pi_blob_T, a->m, a->v, nullptr, a->t, a->t_dev, lr_k, -1.f, 1.f, prec) : AdamTarget{};
+  hipStream_t st = as_stream(stream);
+  const long long N = a->d.N;
+  const int S = a->d.S, A = a->d.A;
+  // the linear 2 A outputs (mu | logstd, :92-93) with the saves of the backward
+  const Mlp3FwdArgs fp = fwd_args(a->pi_blob, w.Lp, a->state, S, nullptr, 0, N, w.p.out, 0, 1.f, w.p.x, w.p.h1, w.p.h2, w.p.m1, w.p.m2,
+                                  prec != PREC_F32 ? a->pi_blob_T : nullptr, prec == PREC_F16X2 ? w.p.e_h1 : nullptr);
+  rc = launch_mlp3_forward(fp, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  const float inv = 1.f / ((float)a->d.N_global * (float)A);
+  Mlp3BwdArgs b = bwd_args(w.Lp, a->pi_blob_T, nullptr, w.p.h1, w.p.h2, N, w.p.dz2, w.p.dz1, w.p.dbp, w.p.m1, w.p.m2, prec, w.p.e_dz2);
+  b.seed.mode = 6; b.seed.iq.z = w.p.out; b.seed.iq.ldz = 2 * A; b.seed.iq.act = a->action; b.seed.iq.adv = a->adv; b.seed.iq.A = A;
+  b.seed.iq.temp = a->temp; b.seed.iq.inv = inv;
+  if (dev) { b.seed.iq.bc_out = w.p.bc; b.seed.iq.t_dev = (const long long*)a->t_dev; b.seed.iq.T_max = a->T_max; b.seed.iq.lr0 = a->lr; }
+  b.seed.dz3_out = w.p.dz3; b.seed.lossp = w.p.lossp;
+  rc = launch_mlp3_bwd_seed(b, st);
+  if (rc) return rc;
+  LossFinal lf{};
+  lf.kind = 1; lf.nparts = w.p.ntiles; lf.scale = inv; lf.parts = w.p.lossp; lf.out = a->loss_out;
+  return iql_weight_grads(w.Lp, w.p, N, a->grad, lf, adam, prec, dev, st);
 }
 
 extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,

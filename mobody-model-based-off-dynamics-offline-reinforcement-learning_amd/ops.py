@@ -334,6 +334,59 @@ def td3bc_actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, st
     check(load().mobody_td3bc_actor_backward(C.byref(blk), cur_stream()), "mobody_td3bc_actor_backward")
 
 
+# IQL (iql.py): one block type for the three calls of the step (MobodyIql); `nets` = (v_func, q_funcs, target_q_funcs, policy)
+# as objects with .blob / .blob_T, `opt` the Adam state of the net the call trains (m, v given: fused form; grad: gradient form)
+def iql_workspace(dims, device):
+    n = load().mobody_iql_workspace(C.byref(dims))
+    if n < 0:
+        raise _lib.MobodyError("mobody_iql_workspace: " + load().mobody_last_error().decode())
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def cosine_lr(lr0, k, T_max):
+    """Learning rate of 1-based gradient step k under CosineAnnealingLR(T_max) (eta_min 0): the closed form in double, rounded to
+    fp32 once -- the value mobody_iql_actor's fused form uses (csrc/train.h cosine_lr)."""
+    import math
+    import numpy as np
+    lr0 = float(np.float32(lr0))
+    return float(np.float32(lr0 * (1.0 + math.cos(math.pi * (k - 1) / T_max)) * 0.5))
+
+
+def _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws):
+    vf, q, qt, pi = nets
+    s, a, s2, r, nd = batch
+    return _lib.MobodyIql(struct_bytes=_BYTES[_lib.MobodyIql], d=dims, h=hyp, lam=float(lam), temp=float(temp), T_max=int(T_max),
+                          v_blob=ptr(vf.blob), v_blob_T=ptr(vf.blob_T), q_blob=ptr(q.blob), q_blob_T=ptr(q.blob_T),
+                          qtarg_blob=ptr(qt.blob), qtarg_blob_T=ptr(qt.blob_T), pi_blob=ptr(pi.blob), pi_blob_T=ptr(pi.blob_T),
+                          state=ptr(s), action=ptr(a), next_state=ptr(s2), reward=ptr(r), not_done=ptr(nd), adv=ptr(adv),
+                          loss_out=ptr(loss_out), workspace=ptr(ws))
+
+
+def _iql_call(name, blk, grad, m, v, t, t_dev, lr, bump=None, log_out=None):
+    blk.grad, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(grad), ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    blk.bump, blk.log_out = ptr(bump), ptr(log_out)
+    check(getattr(load(), name)(C.byref(blk), cur_stream()), name)
+
+
+def iql_value(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0,
+              log_out=None):
+    """V update (iql.py:174-185): writes adv[N] (before the update), loss_out[0] = L_V; log_out[2] = mean adv, mean V."""
+    _iql_call("mobody_iql_value", _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws), grad, m, v, t, t_dev, lr,
+              log_out=log_out)
+
+
+def iql_critic(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0,
+               bump=None):
+    """Twin-Q update against y = r + nd gamma V(s') (iql.py:187-196), Adam + Polyak in the fused form."""
+    _iql_call("mobody_iql_critic", _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws), grad, m, v, t, t_dev, lr,
+              bump=bump)
+
+
+def iql_actor(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0):
+    """Policy update (iql.py:198-202) from adv; fused form: Adam at cosine_lr(lr, t or t_dev[0], T_max)."""
+    _iql_call("mobody_iql_actor", _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws), grad, m, v, t, t_dev, lr)
+
+
 def value_loss_grad(qt, v, n_global):
     """qt [2,N] target twin-Q(s,a), v [N] -> (dz3[N,16], loss[1]) of the expectile V loss."""
     N = v.numel()

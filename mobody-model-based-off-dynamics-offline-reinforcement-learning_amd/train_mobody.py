@@ -1,5 +1,6 @@
 """CLI driver -- mirror of the reference's `train_mobody.py` for mode 3 (offline-offline): `--policy MOBODY` and the model-free
-baseline `--policy TD3_BC` (no ensemble dynamics is built, loaded or trained for it, train_mobody.py:820).
+baselines `--policy TD3_BC` and `--policy IQL` (no ensemble dynamics is built, loaded or trained for them, train_mobody.py:820;
+`--max_step` is also T_max of IQL's cosine schedule).
 
 Accepts the reference's flags with the same names, types and defaults (train_mobody.py:210-307),
 merges configuration in the same precedence (yaml <- --params JSON <- CLI-derived keys, :407-416,
@@ -160,6 +161,14 @@ _BUILTIN_YAML = {
 }
 
 
+# `iql`'s, kept beside the table: load_yaml stays the reference's file lookup for it (no config tree, no file), build_config falls
+# back to these values; tests/golden/g24_iql_configs.json holds the reference's four files
+_BUILTIN_IQL = dict(ac_gradient_clip=100, alpha=0.2, batch_size=128, actor_lr=0.0003, critic_lr=0.0003, gamma=0.99,
+                max_epochs_since_update_decay_interval=150000.0, state_dim=17, action_dim=3, hidden_sizes=256, max_action=1,
+                temperature_opt=False, tau=0.005, update_interval=2, expl_noise=0.2, eval_episode=10, eval_freq=10000,
+                start_steps=5000, max_step=500000, tar_env_interact_freq=10, device="cuda", lam=0.7, temp=3.0, save_freq=5000)
+
+
 def uses_model(policy):
     """The ensemble dynamics is built, loaded or trained only for model-based policies (train_mobody.py:820)."""
     return "mb" in policy.lower() or "mobody" in policy.lower()
@@ -181,7 +190,12 @@ def load_yaml(domain, policy, env_base):
 def build_config(args, state_dim, action_dim, max_action):
     """yaml <- --params <- CLI keys (train_mobody.py:407-416, 470-531); env dims override the yaml's."""
     domain = domain_of(args.env)
-    config = load_yaml(domain, args.policy.lower(), args.env.split("-")[0])
+    try:
+        config = load_yaml(domain, args.policy.lower(), args.env.split("-")[0])
+    except FileNotFoundError:
+        if args.policy.lower() != "iql" or domain != "mujoco":
+            raise
+        config = dict(_BUILTIN_IQL)                   # the reference's config/mujoco/iql/*.yaml (its four files are identical)
     if args.params is not None:
         config.update(json.loads(args.params))
     shift = args.shift_level
@@ -471,7 +485,8 @@ def _run(args, rank, world, device):
             else:
                 q, pi, bc = policy.losses()
             dt = time.time() - start
-            say(f"step {t + 1}: q_loss {q:.4f} pi_loss {pi:.4f} bc_loss {bc:.4f}  {args.log_every / dt:.1f} grad-steps/s")
+            third = getattr(policy, "third_loss_name", "bc_loss")       # IQL reports its V loss there
+            say(f"step {t + 1}: q_loss {q:.4f} pi_loss {pi:.4f} {third} {bc:.4f}  {args.log_every / dt:.1f} grad-steps/s")
             start = time.time()
         if (t + 1) % config["eval_freq"] == 0 and rank == 0:           # rank 0 alone: no collective in this block
             # The reference's evaluation block (train_mobody.py:928-975) rolls the policy out in the simulators; of it, what

@@ -77,7 +77,9 @@ def kernels(lib, tmp):
             m = re.match(r"^(?:[0-9a-f]+ )?<(\S+)>:$", line)
             if m:
                 cur = code.setdefault(m.group(1), [])
-            elif cur is not None and line.strip():
+            elif cur is not None and line.strip() and line.strip() != "...":
+                # ("..." is the disassembler's mark for the zero padding between two functions, not an instruction: a kernel
+                #  that gets a neighbour behind it would otherwise count one line more)
                 # drop the address comment and symbolic branch targets (they carry the mangled name)
                 cur.append(re.sub(r"\s*<[^>]*>", "", line.split("//")[0]).strip())
         # demangled names: the symbol table printed twice, plain and with -C, lines in the same order
