@@ -655,6 +655,53 @@ int mobody_dara_loss_grad(const float* z_sas, const float* z_sa, const int32_t* 
 int mobody_dara_penalty(const float* z_sas, const float* z_sa, int64_t n, float coef, float* reward, float* delta_out,
                         void* stream);
 
+/* ---- DARA baseline (the reference's algo/offline_offline/dara.py) ---------------------------------------------
+ * DARA's step is IQL's (the three mobody_iql_* calls above, same nets and blocks) behind two additions, each one call on the
+ * block below.  The classifier's two heads are packed MLPs: sa = mobody_mlp_layout(S + A, 2, 1), sas = (2 S + A, 2, 1); their T
+ * blobs are read in every precision and written by the fused form.  Rows are [src | tar]: rows < n_src carry label 0, the rest
+ * label 1 (n_src = 0 means d.N / 2; the reference's randperm of the rows is dropped: the loss is a mean over rows).
+ *   mobody_dara_classifier  dara.py:131-144, :202-223.  One classifier update on d.N rows: x_sas = [s | a | s'] + noise_std eps,
+ *                       x_sa = [s | a] + noise_std eps' (eps explicit unit normals noise_sas / noise_sa, or the device generator's
+ *                       streams 4 / 5 at (seed, call) -- with call_dev != NULL at call id call_dev[0] + call_offset), both heads'
+ *                       forwards in one launch at `precision`, per head the backward with the loss seed formed in its prologue
+ *                       (cross_entropy applied to the head's softmax PROBABILITIES, as the reference does) and the weight
+ *                       gradients.  Gradient form: grad_sa and grad_sas are written.  Fused form (m_*, v_* given): ONE Adam
+ *                       over both heads, one step count t (or t_dev[0]) at rate lr.  loss_out[0] = loss_sa, [1] = loss_sas
+ *                       (local share, scaled by 1 / N_global).
+ *   mobody_dara_relabel     dara.py:281-292.  Noise-free pass of both heads on the first n_src rows of state | action | next_state
+ *                       (read in place), penalty = clamp(log p~_sas[1] - log p~_sa[1] - log p~_sas[0] + log p~_sa[0], -10, 10),
+ *                       p~ = softmax(head probabilities) + 1e-10 (mobody_dara_penalty's arithmetic); reward[row] += eta * penalty
+ *                       for row < n_src (eta == 0: no reward is written), delta_out[row] = penalty and log_out[0] = its mean when
+ *                       given.  Rows >= n_src are not touched.
+ * Both take mobody_dara_workspace floats: mobody_iql_workspace's, which the IQL calls of the step use, with the classifier's
+ * scratch behind them.  Refused with MOBODY_E_ARG before any runtime call, with the field named: 2 A > 128, 2 S + A > 256, N odd
+ * without n_src, n_src outside [0, N], precision, null pointers, both or neither of the gradient blobs and the optimizer state. */
+typedef struct MobodyDara MobodyDara;
+struct MobodyDara {
+  int32_t struct_bytes;
+  int32_t precision;
+  MobodyTrainDims d;
+  int64_t n_src;
+  float *sa_blob, *sa_blob_T, *sas_blob, *sas_blob_T;
+  const float *state, *action, *next_state;
+  float* reward;
+  const float *noise_sas, *noise_sa;
+  float noise_std, eta;
+  uint32_t seed, call;
+  const int64_t* call_dev;
+  int64_t call_offset;
+  float *grad_sa, *grad_sas;
+  float *m_sa, *v_sa, *m_sas, *v_sas;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  int32_t reserved;
+  float *delta_out, *loss_out, *log_out, *workspace;
+};
+int64_t mobody_dara_workspace(const MobodyTrainDims* d);
+int mobody_dara_classifier(const MobodyDara* a, void* stream);
+int mobody_dara_relabel(const MobodyDara* a, void* stream);
+
 /* ---- dynamics pre-training (MOBODYEnsembleDynamics.learn / validate, algo/dynamics/mobody_dynamics.py:300-384,
  *      594-653, 1113-1140; Swish/reparameterisation mobody_module.py:9-15,237-243) ----------------------------------
  * All trained parameters of the 7-member ensemble live in ONE blob: three MobodyMlpLayout regions with 7 members

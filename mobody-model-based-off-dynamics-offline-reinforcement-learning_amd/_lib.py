@@ -127,6 +127,15 @@ class MobodyIql(C.Structure):
                 ("lr", f32), ("bump", vp), ("loss_out", vp), ("log_out", vp), ("workspace", vp)]
 
 
+class MobodyDara(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("d", MobodyTrainDims), ("n_src", i64), ("sa_blob", vp), ("sa_blob_T", vp),
+                ("sas_blob", vp), ("sas_blob_T", vp), ("state", vp), ("action", vp), ("next_state", vp), ("reward", vp),
+                ("noise_sas", vp), ("noise_sa", vp), ("noise_std", f32), ("eta", f32), ("seed", u32), ("call", u32), ("call_dev", vp),
+                ("call_offset", i64), ("grad_sa", vp), ("grad_sas", vp), ("m_sa", vp), ("v_sa", vp), ("m_sas", vp), ("v_sas", vp),
+                ("t", i64), ("t_dev", vp), ("lr", f32), ("reserved", i32), ("delta_out", vp), ("loss_out", vp), ("log_out", vp),
+                ("workspace", vp)]
+
+
 class MobodyAdam(C.Structure):
     _fields_ = [("struct_bytes", i32), ("in_dim", i32), ("out_dim", i32), ("members", i32), ("blob", vp), ("blob_T", vp),
                 ("grad", vp), ("m", vp), ("v", vp), ("target", vp), ("target_T", vp), ("t", i64), ("t_dev", vp), ("lr", f32), ("tau", f32),
@@ -153,7 +162,7 @@ def block(cls, **fields):
     return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
 
 
-BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
+BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -221,6 +230,9 @@ PROTOTYPES = {
     "mobody_iql_value": (C.c_int, [C.POINTER(MobodyIql), vp]),
     "mobody_iql_critic": (C.c_int, [C.POINTER(MobodyIql), vp]),
     "mobody_iql_actor": (C.c_int, [C.POINTER(MobodyIql), vp]),
+    "mobody_dara_workspace": (i64, [C.POINTER(MobodyTrainDims)]),
+    "mobody_dara_classifier": (C.c_int, [C.POINTER(MobodyDara), vp]),
+    "mobody_dara_relabel": (C.c_int, [C.POINTER(MobodyDara), vp]),
     "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),

@@ -6,6 +6,7 @@
 // cross_entropy (log_softmax) to those probabilities, and the penalty applies softmax to them once more.
 // Row-wise kernels: HBM streaming over a few floats per row.
 #include "common.h"
+#include "dara.h"
 #include "layers.h"
 #include "rng.h"
 #include "train.h"
@@ -14,18 +15,8 @@ namespace mobody {
 
 constexpr uint32_t STREAM_CLS_SAS = 4, STREAM_CLS_SA = 5;
 
-struct DaraInArgs {
-  const float *s, *a, *s2;
-  const float *noise_sas, *noise_sa;     // explicit unit normals [N][2S+A], [N][S+A] or null -> device generator
-  long long N;
-  int S, A;
-  float std;
-  uint32_t seed, call;
-  float *x_sas, *x_sa;                   // [N][2S+A], [N][S+A]
-};
-
 // classifier inputs with additive Gaussian noise  (Classifier.forward with_noise=True, mobody.py:19-31)
-__global__ __launch_bounds__(256) void k_dara_inputs(DaraInArgs a) {
+__device__ __forceinline__ void dara_inputs_body(const DaraInArgs& a) {
   const int W3 = 2 * a.S + a.A, W2 = a.S + a.A;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= a.N * W3) return;
@@ -42,24 +33,11 @@ __global__ __launch_bounds__(256) void k_dara_inputs(DaraInArgs a) {
     a.x_sa[g2] = v + e2 * a.std;
   }
 }
-
-__device__ __forceinline__ void softmax2(float z0, float z1, float& p0, float& p1) {
-  const float m = fmaxf(z0, z1);
-  const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-  const float inv = 1.f / (e0 + e1);
-  p0 = e0 * inv; p1 = e1 * inv;
-}
-
-// loss = CE(softmax(z)) with CE's own log_softmax (double softmax); returns -log q[label] and dL/dz
-__device__ __forceinline__ float ce_on_probs(float z0, float z1, int label, float scale, float& dz0, float& dz1) {
-  float p0, p1, q0, q1;
-  softmax2(z0, z1, p0, p1);                   // head output (torch.nn.Softmax, :25,31)
-  softmax2(p0, p1, q0, q1);                   // F.cross_entropy's softmax over the probabilities (:169-170)
-  const float g0 = q0 - (label == 0 ? 1.f : 0.f), g1 = q1 - (label == 1 ? 1.f : 0.f);      // dL/dp
-  const float dot = g0 * p0 + g1 * p1;
-  dz0 = scale * p0 * (g0 - dot);               // through the first softmax
-  dz1 = scale * p1 * (g1 - dot);
-  return -logf(label == 0 ? q0 : q1);
+__global__ __launch_bounds__(256) void k_dara_inputs(DaraInArgs a) { dara_inputs_body(a); }
+// the same rows with the generator's call id read from a device word (a captured DARA step, dara.py:131-144)
+__global__ __launch_bounds__(256) void k_dara_inputs_dev(DaraInArgs a, const long long* call_dev, long long call_offset) {
+  a.call = (uint32_t)(call_dev[0] + call_offset);
+  dara_inputs_body(a);
 }
 
 struct DaraLossArgs {
@@ -128,6 +106,22 @@ __global__ __launch_bounds__(256) void k_dara_penalty(const float* z_sas, const 
   if (reward) reward[row] += coef * d;
 }
 
+int launch_dara_inputs(const DaraInArgs& a, const long long* call_dev, long long call_offset, hipStream_t st) {
+  if (a.N <= 0) return 0;
+  const dim3 grid((unsigned)cdiv(a.N * (2 * a.S + a.A), 256));
+  if (call_dev != nullptr) hipLaunchKernelGGL(k_dara_inputs_dev, grid, dim3(256), 0, st, a, call_dev, call_offset);
+  else hipLaunchKernelGGL(k_dara_inputs, grid, dim3(256), 0, st, a);
+  MB_LAUNCH_OK("k_dara_inputs");
+  return 0;
+}
+
+int launch_dara_penalty(const float* z_sas, const float* z_sa, long long n, float coef, float* reward, float* delta_out, hipStream_t st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(k_dara_penalty, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, z_sas, z_sa, n, coef, reward, delta_out);
+  MB_LAUNCH_OK("k_dara_penalty");
+  return 0;
+}
+
 // ---- generic MLP gradient (dz3 + saved activations -> gradient blob) ----
 // its scratch: the backward half of a net's record (the caller owns x, h1, h2)
 static NetScratch carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, long long& total) {
@@ -180,9 +174,7 @@ extern "C" int mobody_dara_inputs(const float* s, const float* a, const float* s
   if (N == 0) return 0;
   MB_REQUIRE(s && a && s2 && x_sas && x_sa, "mobody_dara_inputs: null pointer");
   DaraInArgs d{s, a, s2, noise_sas, noise_sa, N, S, A, std, seed, call, x_sas, x_sa};
-  hipLaunchKernelGGL(k_dara_inputs, dim3((unsigned)cdiv(N * (2 * S + A), 256)), dim3(256), 0, as_stream(stream), d);
-  MB_LAUNCH_OK("k_dara_inputs");
-  return 0;
+  return launch_dara_inputs(d, nullptr, 0, as_stream(stream));
 }
 
 extern "C" int mobody_dara_loss_grad(const float* z_sas, const float* z_sa, const int32_t* labels, int64_t N,
@@ -207,8 +199,5 @@ extern "C" int mobody_dara_penalty(const float* z_sas, const float* z_sa, int64_
   MB_REQUIRE(n >= 0, "mobody_dara_penalty: n < 0");
   if (n == 0) return 0;
   MB_REQUIRE(z_sas && z_sa && (reward || delta_out), "mobody_dara_penalty: null pointer");
-  hipLaunchKernelGGL(k_dara_penalty, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, as_stream(stream), z_sas, z_sa,
-                     (long long)n, coef, reward, delta_out);
-  MB_LAUNCH_OK("k_dara_penalty");
-  return 0;
+  return launch_dara_penalty(z_sas, z_sa, n, coef, reward, delta_out, as_stream(stream));
 }

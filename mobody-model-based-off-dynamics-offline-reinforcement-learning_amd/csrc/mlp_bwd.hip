@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "dara.h"
 #include "layers_bf.h"
 #include "train.h"
 
@@ -216,6 +217,25 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
       Xs[rr * LDX + j] = v;
       if (rr < rows_here) sd.dz3_out[(row0 + rr) * Np3 + j] = v;
     }
+  } else if constexpr (SEED == 7) {                   // mode 7: one thread per row fills the row's Np3 columns
+    const DaraSeed& q = sd.da;
+    if (t < TB) {
+      const bool ok = t < rows_here;
+      const long long row = row0 + (ok ? t : 0);
+      const float z0 = q.z[row * q.ldz], z1 = q.z[row * q.ldz + 1];               // unconditional, clamped
+      float d0, d1;
+      const float l = ce_on_probs(z0, z1, row < q.n_src ? 0 : 1, q.inv, d0, d1);
+      if (!ok) d0 = d1 = 0.f;                         // rows past the batch: exactly 0
+      l0 = ok ? l : 0.f;
+      float* xr = Xs + t * LDX;
+      xr[0] = d0; xr[1] = d1;
+      for (int c = 2; c < Np3; ++c) xr[c] = 0.f;
+      if (ok) {
+        float* g = sd.dz3_out + row * Np3;
+        g[0] = d0; g[1] = d1;
+        for (int c = 2; c < Np3; ++c) g[c] = 0.f;
+      }
+    }
   } else if constexpr (SEED == 4) {                   // mode 4: eight threads per row (TB * 8 == NTHREADS)
     static_assert(MLP_TILE_ROWS * 8 == NTHREADS, "mode 4 spreads a row's A <= 24 action columns over eight lanes");
     // sq = sum_j (pi - a)^2 needs A words of pi and of act per row: lane `sub` of a row's eight takes columns sub, sub + 8,
@@ -332,7 +352,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
     if constexpr (SEED == SEED_RT) sd.lossp[tile * 2 + m] = l0;
-    else if constexpr (SEED == 6) sd.lossp[tile] = l0;
+    else if constexpr (SEED == 6 || SEED == 7) sd.lossp[tile] = l0;
     else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
 }
@@ -1151,7 +1171,8 @@ int launch_grad_reduce(const GradReduceArgs& a, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 // IQL's two trained one-member nets: the backward of k_mlp3_bwd<false, 0, 1, PM> with the seed form compiled in --
 // mode 5, the expectile seed of the V net (rank-1 output layer), or mode 6, the advantage-weighted regression seed of the
-// policy net (K = Np3 GEMM).  Instances of their own: no kernel that existed before them changes.
+// policy net (K = Np3 GEMM).  Mode 7, the double-softmax cross-entropy seed of DARA's two classifier heads, rides
+// mode 6's path.  Instances of their own: no kernel that existed before them changes.
 // ------------------------------------------------------------------------------------------------
 template <int PM, int SEED>
 __global__ __launch_bounds__(NTHREADS, 3) void k_mlp3_bwd_seed(Mlp3BwdArgs a) {
@@ -1176,13 +1197,14 @@ static int launch_bwd_seed_t(const Mlp3BwdArgs& a, hipStream_t st) {
 }
 template <int PM>
 static int launch_bwd_seed_m(const Mlp3BwdArgs& a, hipStream_t st) {
-  return a.seed.mode == 5 ? launch_bwd_seed_t<PM, 5>(a, st) : launch_bwd_seed_t<PM, 6>(a, st);
+  return a.seed.mode == 5 ? launch_bwd_seed_t<PM, 5>(a, st) : a.seed.mode == 6 ? launch_bwd_seed_t<PM, 6>(a, st) : launch_bwd_seed_t<PM, 7>(a, st);
 }
 
 int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st) {
-  MB_REQUIRE((a.seed.mode == 5 || a.seed.mode == 6) && a.m1 && a.m2 && !a.swish && a.seed.dz3_out && a.seed.lossp,
-             "launch_mlp3_bwd_seed: seed mode %d: needs mode 5 or 6 of a ReLU net with sign words", a.seed.mode);
+  MB_REQUIRE((a.seed.mode == 5 || a.seed.mode == 6 || a.seed.mode == 7) && a.m1 && a.m2 && !a.swish && a.seed.dz3_out && a.seed.lossp,
+             "launch_mlp3_bwd_seed: seed mode %d: needs mode 5, 6 or 7 of a ReLU net with sign words", a.seed.mode);
   MB_REQUIRE(a.seed.mode != 5 || a.Np3 == 16, "launch_mlp3_bwd_seed: seed mode 5 seeds a one-output net (Np3=%d)", a.Np3);
+  MB_REQUIRE(a.seed.mode != 7 || a.Np3 == 16, "launch_mlp3_bwd_seed: seed mode 7 seeds a two-output net (Np3=%d)", a.Np3);
   if (a.rows <= 0) return 0;
   if (a.prec != PREC_F32 && a.w2t_planes != nullptr)
     return a.prec == PREC_BF16 ? launch_bwd_seed_m<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_seed_m<2>(a, st)

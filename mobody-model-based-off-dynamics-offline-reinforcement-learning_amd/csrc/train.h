@@ -58,8 +58,12 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //        w = min(exp(temp * adv[row]), 100), th = tanh(z[row][j]);  j < A: dz3 = 2 w (th - a)(1 - th^2) / (N_global A), j >= A: 0
 //        (the logstd half takes no gradient); lossp[tile] = sum w (th - a)^2.  Its first tile also forms, from the device step
 //        count, the Adam constants of the policy's cosine learning rate for the k_grad_reduce launch behind it (bc_out).
-// Modes 5 and 6 run in launch_mlp3_bwd_seed (k_mlp3_bwd_seed), compiled in; their row-wise arguments are `iq`, which shares the
-// bytes of `ar`.
+//   7  DARA's classifier heads (dara.py:131-144, :217-219), two real outputs of an Np3 = 16 net: z = z[row][0..1], label = 0 for
+//        row < n_src, else 1; dz3[row][0..1] = d/dz of cross_entropy(softmax(z), label) / N_global -- the loss applies its own
+//        log_softmax to the head's probabilities (ce_on_probs, dara.h: the one copy of that arithmetic) --, columns >= 2: 0;
+//        lossp[tile] = sum -log q[label].  Rides mode 6's general K = Np3 path for dz3 W3^T.
+// Modes 5, 6 and 7 run in launch_mlp3_bwd_seed (k_mlp3_bwd_seed), compiled in; their row-wise arguments are `iq` (5, 6) or `da`
+// (7), which share the bytes of `ar`.
 struct IqlSeed {
   const float *qt, *v;         // mode 5: [2][rows] target twin-Q(s, a), [rows] V(s)
   const float *z, *act, *adv;  // mode 6: [rows][ldz] linear policy outputs, [rows][A] actions, [rows] adv of mode 5
@@ -70,6 +74,12 @@ struct IqlSeed {
   float lam, temp, inv, lr0;   // inv: 1 / N_global (mode 5), 1 / (N_global A) (mode 6)
   int A, ldz;
 };
+struct DaraSeed {
+  const float* z;              // [rows][ldz] the head's two logits
+  long long n_src;             // rows < n_src carry label 0, the rest label 1
+  float inv;                   // 1 / N_global
+  int ldz;
+};
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
@@ -78,12 +88,15 @@ struct BwdSeed {
   union {
     ActorRowArgs ar;                         // modes 2, 3, 4
     IqlSeed iq;                              // modes 5, 6
+    DaraSeed da;                             // mode 7
   };
   float* dz3_out;
   float* lossp;
 };
 static_assert(sizeof(IqlSeed) <= sizeof(ActorRowArgs) && alignof(IqlSeed) == alignof(ActorRowArgs),
               "IqlSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
+static_assert(sizeof(DaraSeed) <= sizeof(ActorRowArgs) && alignof(DaraSeed) == alignof(ActorRowArgs),
+              "DaraSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
 
 struct Mlp3BwdArgs {
   BwdSeed seed;
@@ -115,7 +128,7 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
 // tile's two member workgroups to finish runs that tile's actor backward (mlp_bwd.hip k_actor_bwd_chain).  tickets: one int per
 // row tile, zero on entry and on exit.
 int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st);
-// one net (member 0), sign words, seed mode 5 or 6 formed in the prologue; no dx
+// one net (member 0), sign words, seed mode 5, 6 or 7 formed in the prologue; no dx
 int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st);
 // learning rate of 1-based gradient step k under CosineAnnealingLR(T_max), eta_min 0 (closed form, in double, rounded to fp32 once)
 __host__ __device__ inline float cosine_lr(float lr0, long long k, long long T_max) {

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "dara.h"
 #include "layers.h"
 #include "train.h"
 
@@ -508,6 +509,20 @@ struct IqlWs {
   long long total;
 };
 
+// one net's record on N rows, nloss loss partials per row tile
+template <class Take>
+static void carve_iql_net(const MobodyMlpLayout& L, long long N, int nloss, IqlNetWs& n, Take&& take) {
+  const long long N32 = (N + 31) & ~31LL, mw = cdiv(N, 32) * HID;
+  n.ntiles = (int)cdiv(N, MLP_TILE_ROWS); n.nsplit = wgrad_nsplit(N, 1);
+  n.out = take(N * L.out_dim); n.x = take(N * L.Kp1); n.h1 = take(N32 * HID); n.h2 = take(N * HID);
+  n.m1 = (uint32_t*)take(mw); n.m2 = (uint32_t*)take(mw);
+  n.e_h1 = (int*)take(N32 / 32); n.e_dz2 = (int*)take(N32 / 32);
+  n.dz3 = take(N * L.Np3); n.dz2 = take(N32 * HID); n.dz1 = take(N * HID);
+  n.dbp = take((long long)n.ntiles * (2 * HID + L.Np3));
+  n.slabs = take(((L.total_floats + 3) & ~3LL) * n.nsplit);
+  n.lossp = take((long long)nloss * n.ntiles); n.bc = take(4);
+}
+
 static int carve_iql(const MobodyTrainDims& d, float* base, IqlWs& w) {
   int rc = carve(d, base, w.tw);
   if (rc) return rc;
@@ -515,19 +530,10 @@ static int carve_iql(const MobodyTrainDims& d, float* base, IqlWs& w) {
   if (rc) return rc;
   rc = mobody_mlp_layout(d.S, 2 * d.A, 1, &w.Lp);
   if (rc) return rc;
-  const long long N = d.N, N32 = (N + 31) & ~31LL, mw = cdiv(N, 32) * HID;
+  const long long N = d.N;
   long long off = w.tw.total;
   auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  auto net = [&](const MobodyMlpLayout& L, IqlNetWs& n, int nloss) {
-    n.ntiles = (int)cdiv(N, MLP_TILE_ROWS); n.nsplit = wgrad_nsplit(N, 1);
-    n.out = take(N * L.out_dim); n.x = take(N * L.Kp1); n.h1 = take(N32 * HID); n.h2 = take(N * HID);
-    n.m1 = (uint32_t*)take(mw); n.m2 = (uint32_t*)take(mw);
-    n.e_h1 = (int*)take(N32 / 32); n.e_dz2 = (int*)take(N32 / 32);
-    n.dz3 = take(N * L.Np3); n.dz2 = take(N32 * HID); n.dz1 = take(N * HID);
-    n.dbp = take((long long)n.ntiles * (2 * HID + L.Np3));
-    n.slabs = take(((L.total_floats + 3) & ~3LL) * n.nsplit);
-    n.lossp = take((long long)nloss * n.ntiles); n.bc = take(4);
-  };
+  auto net = [&](const MobodyMlpLayout& L, IqlNetWs& n, int nloss) { carve_iql_net(L, N, nloss, n, take); };
   net(w.Lv, w.v, 3);
   net(w.Lp, w.p, 1);
   w.qt = take(2 * N); w.vnext = take(N);
@@ -669,6 +675,147 @@ extern "C" int mobody_iql_actor(const MobodyIql* a, void* stream) {
   LossFinal lf{};
   lf.kind = 1; lf.nparts = w.p.ntiles; lf.scale = inv; lf.parts = w.p.lossp; lf.out = a->loss_out;
   return iql_weight_grads(w.Lp, w.p, N, a->grad, lf, adam, prec, dev, st);
+}
+
+// ---- DARA (the reference's algo/offline_offline/dara.py): IQL's step behind one domain-classifier update per step and a relabel
+// of the source rewards with the classifier's log-ratio.  The two heads are one-member nets trained like V and the policy: paired
+// forward, loss seed in the backward prologue (mode 7), weight gradients with the reduce and Adam fused.  DESIGN 5s. ----
+namespace mobody {
+struct DaraWs {
+  IqlWs iq;                // IQL's scratch, where its three entry points carve it
+  MobodyMlpLayout Lsa, Lsas;
+  IqlNetWs sa, sas;
+  float *xin_sa, *xin_sas; // noisy input rows [N][S+A], [N][2S+A] (the forward's sources; its save_x is the padded copy)
+  float* delta;            // [N] per-row penalty when the caller keeps none
+  long long total;
+};
+
+static int carve_dara(const MobodyTrainDims& d, float* base, DaraWs& w) {
+  int rc = carve_iql(d, base, w.iq);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(d.S + d.A, 2, 1, &w.Lsa);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(2 * d.S + d.A, 2, 1, &w.Lsas);
+  if (rc) return rc;
+  const long long N = d.N;
+  long long off = w.iq.total;
+  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  carve_iql_net(w.Lsa, N, 1, w.sa, take);
+  carve_iql_net(w.Lsas, N, 1, w.sas, take);
+  w.xin_sa = take(N * (d.S + d.A)); w.xin_sas = take(N * (2 * d.S + d.A));
+  w.delta = take(N);
+  w.total = off;
+  return 0;
+}
+
+// what the two entry points check alike, before any runtime call; n_src: the source rows (a->n_src, or N / 2)
+static int dara_check(const MobodyDara* a, const char* who, long long& n_src) {
+  MB_BLOCK(who, a, MobodyDara);
+  int rc = check_dims(&a->d, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->d.S >= 1 && a->d.A >= 1 && 2 * a->d.A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, a->d.A);
+  MB_REQUIRE(2 * a->d.S + a->d.A <= 256, "%s: 2 S + A = %d > 256 (the widest input a packed MLP takes)", who, 2 * a->d.S + a->d.A);
+  MB_REQUIRE(a->n_src >= 0 && a->n_src <= a->d.N, "%s: n_src %lld outside [0, N = %lld]", who, (long long)a->n_src, (long long)a->d.N);
+  MB_REQUIRE(a->n_src != 0 || a->d.N % 2 == 0, "%s: N %lld is odd and n_src is not given (rows are [src | tar], n_src = N / 2)", who, (long long)a->d.N);
+  n_src = a->n_src != 0 ? a->n_src : a->d.N / 2;
+  MB_REQUIRE(a->sa_blob && a->sa_blob_T && a->sas_blob && a->sas_blob_T && a->state && a->action && a->next_state && a->workspace, "%s: null pointer", who);
+  return check_precision(who, a->precision, true);
+}
+}  // namespace mobody
+
+extern "C" int64_t mobody_dara_workspace(const MobodyTrainDims* d) {
+  if (check_dims(d, "mobody_dara_workspace")) return -1;
+  if (d->S < 1 || d->A < 1 || 2 * d->A > 128) { fail(MOBODY_E_ARG, "mobody_dara_workspace: d.A %d: 2 A > 128", d->A); return -1; }
+  if (2 * d->S + d->A > 256) { fail(MOBODY_E_ARG, "mobody_dara_workspace: 2 S + A = %d > 256", 2 * d->S + d->A); return -1; }
+  DaraWs w;
+  if (carve_dara(*d, nullptr, w)) return -1;
+  return w.total;
+}
+
+// dara.py:131-144 (Classifier.forward, with_noise), :202-223 (update_classifier)
+extern "C" int mobody_dara_classifier(const MobodyDara* a, void* stream) {
+  const char* who = "mobody_dara_classifier";
+  long long n_src = 0;
+  int rc = dara_check(a, who, n_src);
+  if (rc) return rc;
+  const bool any_grad = a->grad_sa != nullptr || a->grad_sas != nullptr, any_opt = a->m_sa || a->v_sa || a->m_sas || a->v_sas;
+  MB_REQUIRE(any_grad != any_opt, "%s: exactly one of grad_sa, grad_sas and the optimizer state m, v of both heads must be given", who);
+  MB_REQUIRE((a->grad_sa && a->grad_sas) || (a->m_sa && a->v_sa && a->m_sas && a->v_sas), "%s: null pointer", who);
+  MB_REQUIRE(!any_opt || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  MB_REQUIRE(a->loss_out, "%s: null pointer", who);
+  MB_REQUIRE(a->noise_std >= 0.f, "%s: noise_std %g < 0", who, (double)a->noise_std);
+  DaraWs w;
+  rc = carve_dara(a->d, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->precision;
+  const bool fused = any_opt;
+  hipStream_t st = as_stream(stream);
+  const long long N = a->d.N;
+  const int S = a->d.S, A = a->d.A;
+  // 1. the noisy rows [s | a | s'] and [s | a] (:132-141), one row-wise launch
+  DaraInArgs in{a->state, a->action, a->next_state, a->noise_sas, a->noise_sa, N, S, A, a->noise_std, a->seed, a->call, w.xin_sas, w.xin_sa};
+  rc = launch_dara_inputs(in, (const long long*)a->call_dev, a->call_offset, st);
+  if (rc) return rc;
+  // 2. both heads' forwards with the saves of their backwards (:136, :142): one launch
+  const bool f16 = prec == PREC_F16X2;
+  const Mlp3FwdArgs f_sas = fwd_args(a->sas_blob, w.Lsas, w.xin_sas, 2 * S + A, nullptr, 0, N, w.sas.out, 0, 1.f, w.sas.x, w.sas.h1, w.sas.h2, w.sas.m1,
+                                     w.sas.m2, prec != PREC_F32 ? a->sas_blob_T : nullptr, f16 ? w.sas.e_h1 : nullptr);
+  const Mlp3FwdArgs f_sa = fwd_args(a->sa_blob, w.Lsa, w.xin_sa, S + A, nullptr, 0, N, w.sa.out, 0, 1.f, w.sa.x, w.sa.h1, w.sa.h2, w.sa.m1, w.sa.m2,
+                                    prec != PREC_F32 ? a->sa_blob_T : nullptr, f16 ? w.sa.e_h1 : nullptr);
+  rc = launch_mlp3_forward(f_sas, 1, f_sa, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  // 3., 4. per head: the backward with the double-softmax cross-entropy seed in its prologue (:217-219), then the weight
+  // gradients with the loss scalar and (fused) the Adam step; one optimizer over both heads = one step count (:192)
+  const float invNg = 1.f / (float)a->d.N_global;
+  struct Head { const MobodyMlpLayout& L; const IqlNetWs& n; float *blob, *blob_T, *grad, *m, *v, *loss; };
+  const Head heads[2] = {{w.Lsas, w.sas, a->sas_blob, a->sas_blob_T, a->grad_sas, a->m_sas, a->v_sas, a->loss_out + 1},
+                         {w.Lsa, w.sa, a->sa_blob, a->sa_blob_T, a->grad_sa, a->m_sa, a->v_sa, a->loss_out}};
+  for (const Head& h : heads) {
+    Mlp3BwdArgs b = bwd_args(h.L, h.blob_T, nullptr, h.n.h1, h.n.h2, N, h.n.dz2, h.n.dz1, h.n.dbp, h.n.m1, h.n.m2, prec, h.n.e_dz2);
+    b.seed.mode = 7; b.seed.da.z = h.n.out; b.seed.da.ldz = 2; b.seed.da.n_src = n_src; b.seed.da.inv = invNg;
+    b.seed.dz3_out = h.n.dz3; b.seed.lossp = h.n.lossp;
+    rc = launch_mlp3_bwd_seed(b, st);
+    if (rc) return rc;
+    const AdamTarget adam = fused ? adam_target(h.blob, h.blob_T, h.m, h.v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
+    LossFinal lf{};
+    lf.kind = 1; lf.nparts = h.n.ntiles; lf.scale = invNg; lf.parts = h.n.lossp; lf.out = h.loss;
+    rc = iql_weight_grads(h.L, h.n, N, h.grad, lf, adam, prec, false, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// dara.py:281-292 (the reward modification of train())
+extern "C" int mobody_dara_relabel(const MobodyDara* a, void* stream) {
+  const char* who = "mobody_dara_relabel";
+  long long n_src = 0;
+  int rc = dara_check(a, who, n_src);
+  if (rc) return rc;
+  MB_REQUIRE(a->reward || a->delta_out || a->log_out, "%s: null pointer (reward, delta_out and log_out)", who);
+  MB_REQUIRE(n_src < (1LL << 31), "%s: n_src %lld does not fit the mean's launch", who, n_src);
+  DaraWs w;
+  rc = carve_dara(a->d, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->precision;
+  hipStream_t st = as_stream(stream);
+  const int S = a->d.S, A = a->d.A;
+  // noise-free pass of both heads on the source rows (:282), state | action | next_state read in place: one launch, no saves
+  Mlp3FwdArgs f_sas = fwd_net(a->sas_blob, w.Lsas, n_src), f_sa = fwd_net(a->sa_blob, w.Lsa, n_src);
+  if (prec != PREC_F32) { fwd_set_planes(f_sas, a->sas_blob_T, w.Lsas); fwd_set_planes(f_sa, a->sa_blob_T, w.Lsa); }
+  fwd_set_src(f_sas, 0, a->state, S, S); fwd_set_src(f_sas, 1, a->action, A, A); fwd_set_src(f_sas, 2, a->next_state, S, S);
+  fwd_set_src(f_sa, 0, a->state, S, S); fwd_set_src(f_sa, 1, a->action, A, A);
+  fwd_set_out(f_sas, w.sas.out, 0, 1.f); fwd_set_out(f_sa, w.sa.out, 0, 1.f);
+  rc = launch_mlp3_forward(f_sas, 1, f_sa, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  // reward[row] += eta * penalty (:283-292); eta == 0 leaves every reward's bits alone
+  float* delta = a->delta_out ? a->delta_out : (a->log_out ? w.delta : nullptr);
+  float* reward = a->eta != 0.f ? a->reward : nullptr;
+  if (reward == nullptr && delta == nullptr) return 0;
+  rc = launch_dara_penalty(w.sas.out, w.sa.out, n_src, a->eta, reward, delta, st);
+  if (rc || a->log_out == nullptr) return rc;
+  hipLaunchKernelGGL(k_sum_scale, dim3(1), dim3(256), 0, st, delta, (int)n_src, 1.f / (float)n_src, a->log_out);   // train/reward penalty (:290)
+  MB_LAUNCH_OK("k_sum_scale");
+  return 0;
 }
 
 extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,

@@ -387,6 +387,48 @@ def iql_actor(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=
     _iql_call("mobody_iql_actor", _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws), grad, m, v, t, t_dev, lr)
 
 
+# DARA (dara.py): the classifier update and the relabel in front of IQL's three calls, one block type (MobodyDara).  `heads` =
+# (sa_classifier, sas_classifier) as objects with .blob / .blob_T; `batch` = (state, action, next_state, reward, ...) of [src | tar]
+def dara_workspace(dims, device):
+    """Floats of the DARA step's scratch: iql_workspace's (the same tensor serves the IQL calls) + the classifier's."""
+    n = load().mobody_dara_workspace(C.byref(dims))
+    if n < 0:
+        raise _lib.MobodyError("mobody_dara_workspace: " + load().mobody_last_error().decode())
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _dara_block(dims, precision, heads, batch, ws, n_src):
+    sa, sas = heads
+    return _lib.MobodyDara(struct_bytes=_BYTES[_lib.MobodyDara], precision=prec_id(precision), d=dims, n_src=int(n_src),
+                           sa_blob=ptr(sa.blob), sa_blob_T=ptr(sa.blob_T), sas_blob=ptr(sas.blob), sas_blob_T=ptr(sas.blob_T),
+                           state=ptr(batch[0]), action=ptr(batch[1]), next_state=ptr(batch[2]), workspace=ptr(ws))
+
+
+def dara_classifier(dims, precision, heads, batch, noise_std, loss_out, ws, n_src=0, noise_sas=None, noise_sa=None, seed=0, call=0,
+                    call_dev=None, call_offset=0, grads=None, opts=None, t=0, t_dev=None, lr=0.0):
+    """One classifier update (dara.py:202-223) on the d.N rows [src | tar] of `batch`; loss_out[2] = (loss_sa, loss_sas).
+    grads = (grad_sa, grad_sas): the gradient form; opts = ((m_sa, v_sa), (m_sas, v_sas)): ONE fused Adam over both heads at step
+    t (or t_dev[0]) and rate lr.  Noise: explicit unit normals, or the device generator at (seed, call) -- call_dev[0] +
+    call_offset when call_dev is given."""
+    blk = _dara_block(dims, precision, heads, batch, ws, n_src)
+    blk.noise_std, blk.noise_sas, blk.noise_sa = float(noise_std), ptr(noise_sas), ptr(noise_sa)
+    blk.seed, blk.call, blk.call_dev, blk.call_offset = int(seed) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF, ptr(call_dev), int(call_offset)
+    if grads is not None:
+        blk.grad_sa, blk.grad_sas = ptr(grads[0]), ptr(grads[1])
+    if opts is not None:
+        (blk.m_sa, blk.v_sa), (blk.m_sas, blk.v_sas) = (ptr(opts[0][0]), ptr(opts[0][1])), (ptr(opts[1][0]), ptr(opts[1][1]))
+    blk.t, blk.t_dev, blk.lr, blk.loss_out = int(t), ptr(t_dev), float(lr), ptr(loss_out)
+    check(load().mobody_dara_classifier(C.byref(blk), cur_stream()), "mobody_dara_classifier")
+
+
+def dara_relabel(dims, precision, heads, batch, eta, ws, n_src=0, delta_out=None, log_out=None):
+    """reward[:n_src] += eta * penalty of a noise-free classifier pass on the source rows (dara.py:281-292); delta_out[n_src] =
+    the penalty, log_out[1] = its mean."""
+    blk = _dara_block(dims, precision, heads, batch, ws, n_src)
+    blk.reward, blk.eta, blk.delta_out, blk.log_out = ptr(batch[3]), float(eta), ptr(delta_out), ptr(log_out)
+    check(load().mobody_dara_relabel(C.byref(blk), cur_stream()), "mobody_dara_relabel")
+
+
 def value_loss_grad(qt, v, n_global):
     """qt [2,N] target twin-Q(s,a), v [N] -> (dz3[N,16], loss[1]) of the expectile V loss."""
     N = v.numel()

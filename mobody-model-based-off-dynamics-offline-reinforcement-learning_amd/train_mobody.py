@@ -176,7 +176,15 @@ def uses_model(policy):
 
 def load_yaml(domain, policy, env_base):
     """config/<domain>/<policy>/<env>.yaml next to the script (train_mobody.py:410-411); a built-in copy of the mujoco
-    hyper-parameters of `mobody` and `td3_bc` is used when no config tree is present."""
+    hyper-parameters of `mobody` and `td3_bc` is used when no config tree is present.  With $MOBODY_CONFIG_ROOT set,
+    $MOBODY_CONFIG_ROOT/<domain>/<policy>/<env>.yaml is looked up first (a reference checkout's config/ directory: the only
+    source of `dara`'s hyper-parameters); unset, nothing changes."""
+    root = os.environ.get("MOBODY_CONFIG_ROOT")
+    if root:
+        path = os.path.join(root, domain, policy, env_base + ".yaml")
+        if os.path.exists(path):
+            with open(path, "r", encoding="utf-8") as f:
+                return yaml.safe_load(f)
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.path.join(here, "config", domain, policy, env_base + ".yaml")
     if os.path.exists(path):
