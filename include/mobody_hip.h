@@ -702,6 +702,69 @@ int64_t mobody_dara_workspace(const MobodyTrainDims* d);
 int mobody_dara_classifier(const MobodyDara* a, void* stream);
 int mobody_dara_relabel(const MobodyDara* a, void* stream);
 
+/* ---- IGDF baseline (the reference's algo/offline_offline/igdf.py) ---------------------------------------------
+ * IGDF's step is IQL's behind a data filter: two contrastive encoders score the source rows, the k best are kept, and the critic
+ * loss is row-weighted.  The encoders are packed MLPs with linear outputs: sa = mobody_mlp_layout(S + A, Z, 1), ss = (S, Z, 1),
+ * Z = repr_dim <= 128; their T blobs are read in every precision and written by the fused form.  Row-wise pieces, callable alone:
+ *   mobody_igdf_contrast  igdf.py:427-440.  The in-batch contrastive loss on n rows: logits l[i][0] = phi_i . psi_tar_i,
+ *                       l[i][j] = phi_i . psi_src_{j-1} (j = 1 .. n-1), binary cross-entropy against a 1 in column 0 in the stable
+ *                       form max(l, 0) - l y + log1p(exp(-|l|)), mean over n^2.  phi [n][ldz], psi_tar [n][ldz], psi_src
+ *                       [n-1][ldz]: columns >= Z are never read.  Writes loss_out[0], dz3_sa [n][Np3] = dL/dphi and dz3_ss
+ *                       [2n-1][Np3] = dL/dpsi (tar rows, then src rows), Np3 = round_up(Z, 16), columns >= Z zero.  The n x n
+ *                       logits never reach memory; all sums run in a fixed order (no float atomics): two runs give the same
+ *                       bits.  lossp: ceil(n / 32) floats of scratch.  2 <= n <= 4096, 1 <= Z <= 128, ldz >= Z.
+ *   mobody_igdf_select    igdf.py:505-508, :515.  kept[k] = positions of the k largest of score[n] in ascending order
+ *                       (argsort(score)[-k:]), w[k] = exp(importance_weight * score[kept]).  The order is total for every bit
+ *                       pattern: an integer key of the float, ties to the lower index first, a non-finite score below every finite
+ *                       one (-0 below +0): the ranks are always a permutation.  1 <= k <= n <= 4096.
+ * and the calls on the block below:
+ *   mobody_igdf_info      igdf.py:418-447.  One contrastive update: both encoders' forwards in one launch (sa on the n rows
+ *                       state | action, ss on the 2n-1 rows of next_state = [tar s' (n) | src s' (n-1)]), mobody_igdf_contrast,
+ *                       then per encoder the backward (dz3 from memory) and the weight gradients.  Gradient form: grad_sa, grad_ss
+ *                       are written.  Fused form (m_*, v_* given): ONE Adam over both encoders, one step count t (or t_dev[0])
+ *                       at rate lr; bump (fused form, or NULL): a device word the last optimizer launch increments.
+ *                       loss_out[0] = the loss.
+ *   mobody_igdf_filter    igdf.py:494-524.  Both encoders' forwards (one launch) on the first n rows of the staged batch state |
+ *                       action | next_state (read in place, rows [src(n) | tar(d.N - k)]), score_i = phi_i . psi_i / (|phi_i|
+ *                       |psi_i|) over the Z real columns (no epsilon), mobody_igdf_select, then the training batch out_* =
+ *                       [kept src rows | tar rows], d.N = k + n_tar rows, and row_weight[d.N] = w on the kept rows, 1 on the
+ *                       target rows.  Optional: score_out[n], kept_out[k].  The staged batch is not modified.
+ *   mobody_igdf_critic    igdf.py:468-479.  mobody_iql_critic with the critic loss mean(w (q1 - y)^2) + mean(w (q2 - y)^2):
+ *                       dz3 = 2 w (q_m - y) / N_global.  row_weight NULL: mobody_iql_critic, bit for bit.
+ * mobody_igdf_workspace(d, n, Z) floats: mobody_iql_workspace(d)'s in front (the IQL calls of the step use the same tensor), the
+ * encoders' scratch for n (sa) and 2n-1 (ss) rows behind.  Refused with MOBODY_E_ARG before any runtime call, with the field
+ * named: n outside [2, 4096], Z outside [1, 128], k outside [1, n], d.N < k (filter), 2 A > 128, precision, null pointers, both
+ * or neither of the gradient blobs and the optimizer state. */
+typedef struct MobodyIgdf MobodyIgdf;
+struct MobodyIgdf {
+  int32_t struct_bytes;
+  int32_t precision;
+  MobodyTrainDims d;
+  int64_t n, k;
+  int32_t Z;
+  float importance_weight;
+  float *sa_blob, *sa_blob_T, *ss_blob, *ss_blob_T;
+  const float *state, *action, *next_state, *reward, *not_done;
+  float *out_state, *out_action, *out_next_state, *out_reward, *out_not_done, *row_weight;
+  float* score_out;
+  int32_t* kept_out;
+  float *grad_sa, *grad_ss;
+  float *m_sa, *v_sa, *m_ss, *v_ss;
+  int64_t t;
+  const int64_t* t_dev;
+  int64_t* bump;
+  float lr;
+  int32_t reserved;
+  float *loss_out, *workspace;
+};
+int64_t mobody_igdf_workspace(const MobodyTrainDims* d, int64_t n, int32_t Z);
+int mobody_igdf_contrast(const float* phi, const float* psi_tar, const float* psi_src, int64_t n, int32_t Z, int32_t ldz,
+                         float* dz3_sa, float* dz3_ss, float* lossp, float* loss_out, void* stream);
+int mobody_igdf_select(const float* score, int64_t n, int64_t k, float importance_weight, int32_t* kept, float* w, void* stream);
+int mobody_igdf_info(const MobodyIgdf* a, void* stream);
+int mobody_igdf_filter(const MobodyIgdf* a, void* stream);
+int mobody_igdf_critic(const MobodyIql* a, const float* row_weight, void* stream);
+
 /* ---- dynamics pre-training (MOBODYEnsembleDynamics.learn / validate, algo/dynamics/mobody_dynamics.py:300-384,
  *      594-653, 1113-1140; Swish/reparameterisation mobody_module.py:9-15,237-243) ----------------------------------
  * All trained parameters of the 7-member ensemble live in ONE blob: three MobodyMlpLayout regions with 7 members

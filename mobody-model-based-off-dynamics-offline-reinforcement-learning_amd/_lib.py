@@ -136,6 +136,15 @@ class MobodyDara(C.Structure):
                 ("workspace", vp)]
 
 
+class MobodyIgdf(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("d", MobodyTrainDims), ("n", i64), ("k", i64), ("Z", i32),
+                ("importance_weight", f32), ("sa_blob", vp), ("sa_blob_T", vp), ("ss_blob", vp), ("ss_blob_T", vp), ("state", vp),
+                ("action", vp), ("next_state", vp), ("reward", vp), ("not_done", vp), ("out_state", vp), ("out_action", vp),
+                ("out_next_state", vp), ("out_reward", vp), ("out_not_done", vp), ("row_weight", vp), ("score_out", vp),
+                ("kept_out", vp), ("grad_sa", vp), ("grad_ss", vp), ("m_sa", vp), ("v_sa", vp), ("m_ss", vp), ("v_ss", vp),
+                ("t", i64), ("t_dev", vp), ("bump", vp), ("lr", f32), ("reserved", i32), ("loss_out", vp), ("workspace", vp)]
+
+
 class MobodyAdam(C.Structure):
     _fields_ = [("struct_bytes", i32), ("in_dim", i32), ("out_dim", i32), ("members", i32), ("blob", vp), ("blob_T", vp),
                 ("grad", vp), ("m", vp), ("v", vp), ("target", vp), ("target_T", vp), ("t", i64), ("t_dev", vp), ("lr", f32), ("tau", f32),
@@ -162,7 +171,7 @@ def block(cls, **fields):
     return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
 
 
-BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
+BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -233,6 +242,12 @@ PROTOTYPES = {
     "mobody_dara_workspace": (i64, [C.POINTER(MobodyTrainDims)]),
     "mobody_dara_classifier": (C.c_int, [C.POINTER(MobodyDara), vp]),
     "mobody_dara_relabel": (C.c_int, [C.POINTER(MobodyDara), vp]),
+    "mobody_igdf_workspace": (i64, [C.POINTER(MobodyTrainDims), i64, i32]),
+    "mobody_igdf_contrast": (C.c_int, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp]),
+    "mobody_igdf_select": (C.c_int, [vp, i64, i64, f32, vp, vp, vp]),
+    "mobody_igdf_info": (C.c_int, [C.POINTER(MobodyIgdf), vp]),
+    "mobody_igdf_filter": (C.c_int, [C.POINTER(MobodyIgdf), vp]),
+    "mobody_igdf_critic": (C.c_int, [C.POINTER(MobodyIql), vp, vp]),
     "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),

@@ -3,23 +3,26 @@
 `call_algo(algo_name, config, mode, device, **kwargs)` lower-cases the name, looks the class up
 and returns `cls(config, device)`; `mode` and kwargs are accepted and ignored exactly as the
 reference does.  Unknown names raise KeyError like the reference's dict lookup.  Of the baseline
-algorithms TD3_BC (`offline_offline/td3_bc.py`), IQL (`offline_offline/iql.py`) and DARA (`offline_offline/dara.py`) are built, IQL
-and DARA from a config of their own only: without `lam`, `temp`, `max_step` -- and, for DARA, `gaussian_noise_std`, `dara_eta` and,
-when `dara_eta` is 0, `eta` -- the constructor raises NotImplementedError.  bosa and igdf are outside the accelerated path.
+algorithms TD3_BC (`offline_offline/td3_bc.py`), IQL (`offline_offline/iql.py`), DARA (`offline_offline/dara.py`) and IGDF
+(`offline_offline/igdf.py`) are built, IQL, DARA and IGDF from a config of their own only: without `lam`, `temp`, `max_step` -- for
+DARA also `gaussian_noise_std`, `dara_eta` and, when `dara_eta` is 0, `eta`; for IGDF also `xi`, `importance_weight`, `repr_dim`,
+`ensemble_size`, `repr_norm`, `ortho_init`, `info_update_step` -- the constructor raises NotImplementedError.  bosa is outside the
+accelerated path.
 """
 from .offline_offline.mobody import MOBODY
 from .offline_offline.td3_bc import TD3BC
 from .offline_offline.iql import IQL
 from .offline_offline.dara import DARA
+from .offline_offline.igdf import IGDF
 
-_BASELINES = ("bosa", "igdf")
+_BASELINES = ("bosa",)
 
 
 def call_algo(algo_name, config, mode, device, **kwargs):
     algo_name = algo_name.lower()
-    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC, "iql": IQL, "dara": DARA}
+    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC, "iql": IQL, "dara": DARA, "igdf": IGDF}
     if algo_name in _BASELINES:
         raise NotImplementedError(f"'{algo_name}' is a reference baseline outside the MI355X-accelerated path; "
-                                  "only 'mobody', 'td3_bc', 'iql' and 'dara' are built here")
+                                  "only 'mobody', 'td3_bc', 'iql', 'dara' and 'igdf' are built here")
     algo = algo_to_call[algo_name]          # KeyError for unknown names, as in the reference
     return algo(config, device)

@@ -216,6 +216,10 @@ class IQL(MOBODY):
             writer.add_scalar("train/value", v_mean, self.total_it)
             writer.add_scalar("train/q1", q1_mean, self.total_it)
 
+    def _critic(self, *args, **kw):
+        """The twin-Q phase's call (a subclass with a row-weighted loss puts its own here)."""
+        ops.iql_critic(*args, **kw)
+
     def _update(self, b, N, Nt, dev=False, log=False):
         """V -> Q (+ Polyak) -> policy.  dev: the step counts are the device words of the captured step (already advanced)."""
         dims, hyp = self._dims(N, N, N, N)
@@ -230,14 +234,14 @@ class IQL(MOBODY):
                 ov.t += 1; oq.t += 1; op.t += 1
             ops.iql_value(*head, self._loss[3:4], self._ws, m=ov.m, v=ov.v, t=ov.t, t_dev=c[3:4] if dev else None, lr=ov.lr,
                           log_out=self._log if log else None)
-            ops.iql_critic(*head, self._loss[0:1], self._ws, m=oq.m, v=oq.v, t=oq.t, t_dev=c[1:2] if dev else None, lr=oq.lr,
-                           bump=c[0:1] if dev else None)
+            self._critic(*head, self._loss[0:1], self._ws, m=oq.m, v=oq.v, t=oq.t, t_dev=c[1:2] if dev else None, lr=oq.lr,
+                         bump=c[0:1] if dev else None)
             ops.iql_actor(*head, self._loss[1:2], self._ws, m=op.m, v=op.v, t=op.t, t_dev=c[2:3] if dev else None, lr=op.lr)
             return
         assert not dev, "the captured step is the fused form"
         ops.iql_value(*head, self._loss[3:4], self._ws, grad=ov.grad, log_out=self._log if log else None)
         ov.step()
-        ops.iql_critic(*head, self._loss[0:1], self._ws, grad=oq.grad)
+        self._critic(*head, self._loss[0:1], self._ws, grad=oq.grad)
         oq.step(target=self.target_q_funcs, tau=self.tau)
         ops.iql_actor(*head, self._loss[1:2], self._ws, grad=op.grad)
         lr0 = op.lr

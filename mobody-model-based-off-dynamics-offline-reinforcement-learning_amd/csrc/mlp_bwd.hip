@@ -236,6 +236,23 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
         for (int c = 2; c < Np3; ++c) g[c] = 0.f;
       }
     }
+  } else if constexpr (SEED == 8) {                   // mode 8: mode 1 with a row weight, one thread per row
+    if (t < TB) {
+      const bool ok = t < rows_here;
+      const long long row = row0 + (ok ? t : 0);
+      const float qn = sd.qnext ? sd.qnext[row] : fminf(sd.qt[row], sd.qt[a.rows + row]);
+      const float y = sd.r[row] + sd.nd[row] * sd.gamma * qn;
+      const float d = sd.q[(long long)m * a.rows + row] - y;
+      const float wr = sd.cw.w[row];
+      const float v = ok ? 2.f * wr * d * sd.inv_ng : 0.f;
+      l0 = ok ? wr * (d * d) : 0.f;
+      if (ok) {
+        float* g = sd.dz3_out + ((long long)m * a.rows + row) * Np3;
+        g[0] = v;
+        for (int c = 1; c < Np3; ++c) g[c] = 0.f;
+      }
+      Xs[t] = v;
+    }
   } else if constexpr (SEED == 4) {                   // mode 4: eight threads per row (TB * 8 == NTHREADS)
     static_assert(MLP_TILE_ROWS * 8 == NTHREADS, "mode 4 spreads a row's A <= 24 action columns over eight lanes");
     // sq = sum_j (pi - a)^2 needs A words of pi and of act per row: lane `sub` of a row's eight takes columns sub, sub + 8,
@@ -351,7 +368,7 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   if (t == 0) {
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
-    if constexpr (SEED == SEED_RT) sd.lossp[tile * 2 + m] = l0;
+    if constexpr (SEED == SEED_RT || SEED == 8) sd.lossp[tile * 2 + m] = l0;
     else if constexpr (SEED == 6 || SEED == 7) sd.lossp[tile] = l0;
     else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
@@ -393,7 +410,7 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
   // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
   // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
   // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
-  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4 || SEED == 5);
+  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4 || SEED == 5 || SEED == 8);
   constexpr bool with_db = SEED != 2 && SEED != 4;
   const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
@@ -1210,6 +1227,42 @@ int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st) {
     return a.prec == PREC_BF16 ? launch_bwd_seed_m<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_seed_m<2>(a, st)
          : a.prec == PREC_BF16X3 ? launch_bwd_seed_m<3>(a, st) : launch_bwd_seed_m<4>(a, st);
   return launch_bwd_seed_m<0>(a, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// IGDF's row-weighted critic: the twin-Q backward of seed mode 1 with the weight compiled in as mode 8 -- an instance of
+// its own, so that the kernels of the unweighted critic keep their code.
+// ------------------------------------------------------------------------------------------------
+template <int PM>
+__global__ __launch_bounds__(NTHREADS, 3) void k_mlp3_bwd_wcritic(Mlp3BwdArgs a) {
+  __shared__ float red[8];
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  mlp3_bwd_tile<false, 0, 1, PM, 8>(a, blockIdx.y, blockIdx.x, 2, Xs, red);
+}
+
+template <int PM>
+static int launch_bwd_wcritic_t(const Mlp3BwdArgs& a, hipStream_t st) {
+  constexpr size_t lds = split_lds_bytes<(PM > 0 ? PM : 1), MLP_TILE_ROWS>();
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_bwd_wcritic<PM>, lds);
+    if (rc) return rc;
+    once = true;
+  }
+  ProfScope prof(PROF_MLP_BWD, st);
+  hipLaunchKernelGGL((k_mlp3_bwd_wcritic<PM>), dim3((unsigned)cdiv(a.rows, MLP_TILE_ROWS), 2u), dim3(NTHREADS), lds, st, a);
+  MB_LAUNCH_OK("k_mlp3_bwd_wcritic");
+  return 0;
+}
+
+int launch_mlp3_bwd_wcritic(const Mlp3BwdArgs& a, hipStream_t st) {
+  MB_REQUIRE(a.seed.mode == 8 && a.seed.cw.w && a.m1 && a.m2 && !a.swish && a.seed.dz3_out && a.seed.lossp && a.Np3 == 16,
+             "launch_mlp3_bwd_wcritic: needs seed mode 8 with its row weights on a one-output ReLU twin net with sign words");
+  if (a.rows <= 0) return 0;
+  if (a.prec != PREC_F32 && a.w2t_planes != nullptr)
+    return a.prec == PREC_BF16 ? launch_bwd_wcritic_t<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_wcritic_t<2>(a, st)
+         : a.prec == PREC_BF16X3 ? launch_bwd_wcritic_t<3>(a, st) : launch_bwd_wcritic_t<4>(a, st);
+  return launch_bwd_wcritic_t<0>(a, st);
 }
 
 }  // namespace mobody

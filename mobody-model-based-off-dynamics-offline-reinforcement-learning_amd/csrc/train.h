@@ -62,6 +62,9 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //        row < n_src, else 1; dz3[row][0..1] = d/dz of cross_entropy(softmax(z), label) / N_global -- the loss applies its own
 //        log_softmax to the head's probabilities (ce_on_probs, dara.h: the one copy of that arithmetic) --, columns >= 2: 0;
 //        lossp[tile] = sum -log q[label].  Rides mode 6's general K = Np3 path for dz3 W3^T.
+//   8  IGDF's row-weighted critic (igdf.py:468-479): mode 1 with a per-row weight w = cw.w[row], dz3[m][row][0] = 2 w (q_m - y) /
+//        N_global, lossp[tile*2 + m] = sum w (q_m - y)^2; runs in launch_mlp3_bwd_wcritic (k_mlp3_bwd_wcritic), compiled in, so the
+//        kernels of mode 1 keep their code.  Its weight pointer rides in the bytes of `ar`, which modes 1 and 8 do not read.
 // Modes 5, 6 and 7 run in launch_mlp3_bwd_seed (k_mlp3_bwd_seed), compiled in; their row-wise arguments are `iq` (5, 6) or `da`
 // (7), which share the bytes of `ar`.
 struct IqlSeed {
@@ -80,6 +83,9 @@ struct DaraSeed {
   float inv;                   // 1 / N_global
   int ldz;
 };
+struct CriticSeed {
+  const float* w;              // [rows] row weights of the critic loss (mode 8 reads nothing else of the union)
+};
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
@@ -89,6 +95,7 @@ struct BwdSeed {
     ActorRowArgs ar;                         // modes 2, 3, 4
     IqlSeed iq;                              // modes 5, 6
     DaraSeed da;                             // mode 7
+    CriticSeed cw;                           // mode 8
   };
   float* dz3_out;
   float* lossp;
@@ -97,6 +104,9 @@ static_assert(sizeof(IqlSeed) <= sizeof(ActorRowArgs) && alignof(IqlSeed) == ali
               "IqlSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
 static_assert(sizeof(DaraSeed) <= sizeof(ActorRowArgs) && alignof(DaraSeed) == alignof(ActorRowArgs),
               "DaraSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
+
+static_assert(sizeof(CriticSeed) <= sizeof(ActorRowArgs) && alignof(CriticSeed) == alignof(ActorRowArgs),
+              "CriticSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
 
 struct Mlp3BwdArgs {
   BwdSeed seed;
@@ -130,6 +140,8 @@ int launch_mlp3_bwd(const Mlp3BwdArgs& a, int members, bool with_dx, hipStream_t
 int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tickets, hipStream_t st);
 // one net (member 0), sign words, seed mode 5, 6 or 7 formed in the prologue; no dx
 int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st);
+// the twin-Q net (two members), sign words, seed mode 8 (mode 1's fields + cw.w) formed in the prologue; no dx
+int launch_mlp3_bwd_wcritic(const Mlp3BwdArgs& a, hipStream_t st);
 // learning rate of 1-based gradient step k under CosineAnnealingLR(T_max), eta_min 0 (closed form, in double, rounded to fp32 once)
 __host__ __device__ inline float cosine_lr(float lr0, long long k, long long T_max) {
   return (float)((double)lr0 * (1.0 + cos(3.14159265358979323846 * (double)(k - 1) / (double)T_max)) * 0.5);

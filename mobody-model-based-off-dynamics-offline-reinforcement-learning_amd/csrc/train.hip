@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "dara.h"
+#include "igdf.h"
 #include "layers.h"
 #include "train.h"
 
@@ -264,9 +265,10 @@ extern "C" int64_t mobody_train_workspace(const MobodyTrainDims* d) {
   return w.total;
 }
 
-// extra (with q_next, or null): a one-member forward that shares the launch of Q(s, a) -- IQL's V(s'), which writes q_next
+// extra (with q_next, or null): a one-member forward that shares the launch of Q(s, a) -- IQL's V(s'), which writes q_next.
+// row_weight (or null): IGDF's per-row weights of the loss (seed mode 8, train.h)
 static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* stream, const char* who = "mobody_critic",
-                       const Mlp3FwdArgs* extra = nullptr) {
+                       const Mlp3FwdArgs* extra = nullptr, const float* row_weight = nullptr) {
   // gather != null (phase 0, q_next == null): state .. not_done are not read by the first forward launch but WRITTEN by it --
   // its tiles draw and fetch the minibatch rows themselves (layers.h FwdGather; the block arrives with `g` filled)
   // phase: 0 the whole step; 1 only its forwards (nothing of them reads `reward`); 2 only the backward, weight gradients and
@@ -339,7 +341,12 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
   bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = a.reward; bq.seed.nd = a.not_done;
   bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
-  rc = launch_mlp3_bwd(bq, 2, false, st);
+  if (row_weight != nullptr) {                     // IGDF: the same seed with the row's weight, an instance of its own (mode 8)
+    bq.seed.mode = 8; bq.seed.cw.w = row_weight;
+    rc = launch_mlp3_bwd_wcritic(bq, st);
+  } else {
+    rc = launch_mlp3_bwd(bq, 2, false, st);
+  }
   if (rc) return rc;
   LossFinal lf{};                                  // q_loss = mse(q1,y)+mse(q2,y), local share of the global mean
   lf.kind = 1; lf.nparts = 2 * w.ntiles; lf.scale = invNg; lf.parts = w.lossp; lf.out = a.loss_out;
@@ -617,9 +624,8 @@ extern "C" int mobody_iql_value(const MobodyIql* a, void* stream) {
   return 0;
 }
 
-// iql.py:187-196 (update_q_functions), :222-228
-extern "C" int mobody_iql_critic(const MobodyIql* a, void* stream) {
-  const char* who = "mobody_iql_critic";
+// iql.py:187-196 (update_q_functions), :222-228; row_weight: igdf.py:468-479
+static int iql_critic_impl(const MobodyIql* a, const float* row_weight, void* stream, const char* who) {
   int rc = iql_check(a, who);
   if (rc) return rc;
   MB_REQUIRE(a->v_blob && a->v_blob_T && a->q_blob && a->q_blob_T && a->qtarg_blob && a->next_state && a->reward && a->not_done, "%s: null pointer", who);
@@ -638,8 +644,10 @@ extern "C" int mobody_iql_critic(const MobodyIql* a, void* stream) {
   // V(s') with the V net mobody_iql_value has just updated (:189), beside Q(s, a)
   const Mlp3FwdArgs fvn = fwd_args(a->v_blob, w.Lv, a->next_state, a->d.S, nullptr, 0, a->d.N, w.vnext, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr,
                                    prec != PREC_F32 ? a->v_blob_T : nullptr);
-  return critic_impl(c, nullptr, stream, who, &fvn);
+  return critic_impl(c, nullptr, stream, who, &fvn, row_weight);
 }
+
+extern "C" int mobody_iql_critic(const MobodyIql* a, void* stream) { return iql_critic_impl(a, nullptr, stream, "mobody_iql_critic"); }
 
 // iql.py:91-95 (bc_loss), :198-202 (update_policy), :233-237
 extern "C" int mobody_iql_actor(const MobodyIql* a, void* stream) {
@@ -816,6 +824,149 @@ extern "C" int mobody_dara_relabel(const MobodyDara* a, void* stream) {
   hipLaunchKernelGGL(k_sum_scale, dim3(1), dim3(256), 0, st, delta, (int)n_src, 1.f / (float)n_src, a->log_out);   // train/reward penalty (:290)
   MB_LAUNCH_OK("k_sum_scale");
   return 0;
+}
+
+// ---- IGDF (the reference's algo/offline_offline/igdf.py): IQL's step behind a data filter -- two contrastive encoders score the
+// source rows, the k best are kept -- with a row-weighted critic loss.  The encoders are one-member nets trained like DARA's heads,
+// except that their loss couples the rows: its gradient is formed by k_igdf_contrast and read from memory (seed mode 0).
+// DESIGN 5t. ----
+namespace mobody {
+struct IgdfWs {
+  IqlWs iq;                // IQL's scratch, where its three entry points carve it
+  MobodyMlpLayout Lsa, Lss;
+  IqlNetWs sa, ss;         // records on n and 2n-1 rows
+  float* score;            // [n]
+  int32_t* kept;           // [n]
+  long long total;
+};
+
+static int carve_igdf(const MobodyTrainDims& d, long long n, int Z, float* base, IgdfWs& w) {
+  int rc = carve_iql(d, base, w.iq);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(d.S + d.A, Z, 1, &w.Lsa);
+  if (rc) return rc;
+  rc = mobody_mlp_layout(d.S, Z, 1, &w.Lss);
+  if (rc) return rc;
+  long long off = w.iq.total;
+  auto take = [&](long long c) { float* p = base ? base + off : nullptr; off += (c + 3) & ~3LL; return p; };
+  carve_iql_net(w.Lsa, n, 1, w.sa, take);
+  carve_iql_net(w.Lss, 2 * n - 1, 1, w.ss, take);
+  w.score = take(n); w.kept = (int32_t*)take(n);
+  w.total = off;
+  return 0;
+}
+
+static int igdf_check_sizes(const char* who, const MobodyTrainDims* d, long long n, int Z) {
+  int rc = check_dims(d, who);
+  if (rc) return rc;
+  MB_REQUIRE(d->S >= 1 && d->A >= 1 && 2 * d->A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, d->A);
+  MB_REQUIRE(d->S + d->A <= 256, "%s: S + A = %d > 256 (the widest input a packed MLP takes)", who, d->S + d->A);
+  MB_REQUIRE(n >= 2 && n <= IGDF_MAX_N, "%s: n %lld outside [2, %d]", who, n, IGDF_MAX_N);
+  MB_REQUIRE(Z >= 1 && Z <= IGDF_MAX_Z, "%s: Z %d outside [1, %d]", who, Z, IGDF_MAX_Z);
+  return 0;
+}
+
+// what the two entry points check alike, before any runtime call
+static int igdf_check(const MobodyIgdf* a, const char* who) {
+  MB_BLOCK(who, a, MobodyIgdf);
+  int rc = igdf_check_sizes(who, &a->d, a->n, a->Z);
+  if (rc) return rc;
+  MB_REQUIRE(a->sa_blob && a->sa_blob_T && a->ss_blob && a->ss_blob_T && a->state && a->action && a->next_state && a->workspace, "%s: null pointer", who);
+  return check_precision(who, a->precision, true);
+}
+}  // namespace mobody
+
+extern "C" int64_t mobody_igdf_workspace(const MobodyTrainDims* d, int64_t n, int32_t Z) {
+  if (igdf_check_sizes("mobody_igdf_workspace", d, n, Z)) return -1;
+  IgdfWs w;
+  if (carve_igdf(*d, n, Z, nullptr, w)) return -1;
+  return w.total;
+}
+
+// igdf.py:418-447 (update_info, one step)
+extern "C" int mobody_igdf_info(const MobodyIgdf* a, void* stream) {
+  const char* who = "mobody_igdf_info";
+  int rc = igdf_check(a, who);
+  if (rc) return rc;
+  const bool any_grad = a->grad_sa != nullptr || a->grad_ss != nullptr, any_opt = a->m_sa || a->v_sa || a->m_ss || a->v_ss;
+  MB_REQUIRE(any_grad != any_opt, "%s: exactly one of grad_sa, grad_ss and the optimizer state m, v of both encoders must be given", who);
+  MB_REQUIRE((a->grad_sa && a->grad_ss) || (a->m_sa && a->v_sa && a->m_ss && a->v_ss), "%s: null pointer", who);
+  MB_REQUIRE(!any_opt || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  MB_REQUIRE(a->bump == nullptr || (any_opt && a->bump != a->t_dev), "%s: bump is incremented by the optimizer launch: it needs m, v and must not be the step word", who);
+  MB_REQUIRE(a->loss_out, "%s: null pointer", who);
+  IgdfWs w;
+  rc = carve_igdf(a->d, a->n, a->Z, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->precision;
+  const bool fused = any_opt, f16 = prec == PREC_F16X2;
+  hipStream_t st = as_stream(stream);
+  const long long n = a->n, n2 = 2 * n - 1;
+  const int S = a->d.S, A = a->d.A, Z = a->Z;
+  // 1. phi = encoder_sa([s | a]) on the n target rows, psi = encoder_ss(s') on [tar s' | src s'] (:424-434): one launch, with the
+  // saves of the backwards.  (The reference encodes n^2 next states of which 2n-1 are distinct.)
+  const Mlp3FwdArgs f_sa = fwd_args(a->sa_blob, w.Lsa, a->state, S, a->action, A, n, w.sa.out, 0, 1.f, w.sa.x, w.sa.h1, w.sa.h2, w.sa.m1, w.sa.m2,
+                                    prec != PREC_F32 ? a->sa_blob_T : nullptr, f16 ? w.sa.e_h1 : nullptr);
+  const Mlp3FwdArgs f_ss = fwd_args(a->ss_blob, w.Lss, a->next_state, S, nullptr, 0, n2, w.ss.out, 0, 1.f, w.ss.x, w.ss.h1, w.ss.h2, w.ss.m1, w.ss.m2,
+                                    prec != PREC_F32 ? a->ss_blob_T : nullptr, f16 ? w.ss.e_h1 : nullptr);
+  rc = launch_mlp3_forward(f_ss, 1, f_sa, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  // 2. the loss partials and dL/dphi, dL/dpsi (:434-440)
+  rc = launch_igdf_contrast(w.sa.out, w.ss.out, w.ss.out + n * Z, n, Z, Z, w.Lsa.Np3, w.sa.dz3, w.ss.dz3, w.sa.lossp, st);
+  if (rc) return rc;
+  // 3., 4. per encoder: the backward from dz3 in memory, then the weight gradients with (sa) the loss scalar and (fused) the Adam
+  // step; one optimizer over both encoders = one step count (:407)
+  struct Enc { const MobodyMlpLayout& L; const IqlNetWs& r; long long rows; float *blob, *blob_T, *grad, *m, *v; };
+  const Enc encs[2] = {{w.Lsa, w.sa, n, a->sa_blob, a->sa_blob_T, a->grad_sa, a->m_sa, a->v_sa},
+                       {w.Lss, w.ss, n2, a->ss_blob, a->ss_blob_T, a->grad_ss, a->m_ss, a->v_ss}};
+  for (int e = 0; e < 2; ++e) {
+    const Enc& h = encs[e];
+    Mlp3BwdArgs b = bwd_args(h.L, h.blob_T, h.r.dz3, h.r.h1, h.r.h2, h.rows, h.r.dz2, h.r.dz1, h.r.dbp, h.r.m1, h.r.m2, prec, h.r.e_dz2);
+    rc = launch_mlp3_bwd(b, 1, false, st);
+    if (rc) return rc;
+    AdamTarget adam = fused ? adam_target(h.blob, h.blob_T, h.m, h.v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
+    if (fused && e == 1) adam.bump = (long long*)a->bump;
+    LossFinal lf{};
+    if (e == 0) { lf.kind = 1; lf.nparts = (int)cdiv(n, IGDF_TILE); lf.scale = 1.f / ((float)n * (float)n); lf.parts = w.sa.lossp; lf.out = a->loss_out; }
+    rc = iql_weight_grads(h.L, h.r, h.rows, h.grad, lf, adam, prec, false, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+// igdf.py:494-524 (the data filter of train())
+extern "C" int mobody_igdf_filter(const MobodyIgdf* a, void* stream) {
+  const char* who = "mobody_igdf_filter";
+  int rc = igdf_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->k >= 1 && a->k <= a->n, "%s: k %lld outside [1, n = %lld]", who, (long long)a->k, (long long)a->n);
+  MB_REQUIRE(a->d.N >= a->k, "%s: d.N %lld < k %lld (the training batch is the k kept rows and the target rows)", who, (long long)a->d.N, (long long)a->k);
+  MB_REQUIRE(a->reward && a->not_done && a->out_state && a->out_action && a->out_next_state && a->out_reward && a->out_not_done && a->row_weight,
+             "%s: null pointer", who);
+  IgdfWs w;
+  rc = carve_igdf(a->d, a->n, a->Z, a->workspace, w);
+  if (rc) return rc;
+  const int prec = a->precision;
+  hipStream_t st = as_stream(stream);
+  const long long n = a->n;
+  const int S = a->d.S, A = a->d.A, Z = a->Z;
+  // both encoders on the source rows (:500), state | action and next_state read in place: one launch, no saves
+  Mlp3FwdArgs f_sa = fwd_net(a->sa_blob, w.Lsa, n), f_ss = fwd_net(a->ss_blob, w.Lss, n);
+  if (prec != PREC_F32) { fwd_set_planes(f_sa, a->sa_blob_T, w.Lsa); fwd_set_planes(f_ss, a->ss_blob_T, w.Lss); }
+  fwd_set_src(f_sa, 0, a->state, S, S); fwd_set_src(f_sa, 1, a->action, A, A);
+  fwd_set_src(f_ss, 0, a->next_state, S, S);
+  fwd_set_out(f_sa, w.sa.out, 0, 1.f); fwd_set_out(f_ss, w.ss.out, 0, 1.f);
+  rc = launch_mlp3_forward(f_sa, 1, f_ss, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  float* score = a->score_out ? a->score_out : w.score;
+  rc = launch_igdf_score(w.sa.out, w.ss.out, n, Z, Z, score, st);
+  if (rc) return rc;
+  IgdfBatch b{a->state, a->action, a->next_state, a->reward, a->not_done, a->out_state, a->out_action, a->out_next_state, a->out_reward,
+              a->out_not_done, a->row_weight, a->d.N - a->k, S, A};
+  return launch_igdf_select(score, n, a->k, a->importance_weight, a->kept_out ? a->kept_out : w.kept, nullptr, b, st);
+}
+
+extern "C" int mobody_igdf_critic(const MobodyIql* a, const float* row_weight, void* stream) {
+  return iql_critic_impl(a, row_weight, stream, "mobody_igdf_critic");
 }
 
 extern "C" int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,

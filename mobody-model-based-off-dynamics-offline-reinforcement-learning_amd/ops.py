@@ -429,6 +429,80 @@ def dara_relabel(dims, precision, heads, batch, eta, ws, n_src=0, delta_out=None
     check(load().mobody_dara_relabel(C.byref(blk), cur_stream()), "mobody_dara_relabel")
 
 
+# IGDF (igdf.py): the contrastive update and the per-step filter in front of IQL's three calls, one block type (MobodyIgdf), and the
+# row-weighted critic.  `encs` = (encoder_sa, encoder_ss) as objects with .blob / .blob_T and out_dim Z
+def igdf_workspace(dims, n, Z, device):
+    """Floats of the IGDF step's scratch: iql_workspace's (the same tensor serves the IQL calls) + the encoders' on n / 2n-1 rows."""
+    c = load().mobody_igdf_workspace(C.byref(dims), int(n), int(Z))
+    if c < 0:
+        raise _lib.MobodyError("mobody_igdf_workspace: " + load().mobody_last_error().decode())
+    return torch.empty(c, dtype=torch.float32, device=device)
+
+
+def igdf_contrast(phi, psi_tar, psi_src, Z):
+    """phi [n, ldz], psi_tar [n, ldz], psi_src [n-1, ldz] -> (loss[1], dz3_sa[n, Np3], dz3_ss[2n-1, Np3]) of the in-batch
+    contrastive loss (igdf.py:427-440); columns >= Z of the inputs are not read."""
+    n, ldz = phi.shape
+    Np3 = (int(Z) + 15) // 16 * 16
+    dev = phi.device
+    dz_sa = torch.empty(n, Np3, dtype=torch.float32, device=dev)
+    dz_ss = torch.empty(2 * n - 1, Np3, dtype=torch.float32, device=dev)
+    lossp = torch.empty((n + 31) // 32, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    check(load().mobody_igdf_contrast(ptr(phi), ptr(psi_tar), ptr(psi_src), n, int(Z), ldz, ptr(dz_sa), ptr(dz_ss), ptr(lossp), ptr(loss),
+                                      cur_stream()), "mobody_igdf_contrast")
+    return loss, dz_sa, dz_ss
+
+
+def igdf_select(score, k, importance_weight, kept=None, w=None):
+    """(kept int32[k], w[k]): the positions of the k largest scores in ascending order and exp(importance_weight * score) there."""
+    n = score.numel()
+    kept = torch.empty(int(k), dtype=torch.int32, device=score.device) if kept is None else kept
+    w = torch.empty(int(k), dtype=torch.float32, device=score.device) if w is None else w
+    check(load().mobody_igdf_select(ptr(score), n, int(k), float(importance_weight), ptr(kept), ptr(w), cur_stream()), "mobody_igdf_select")
+    return kept, w
+
+
+def _igdf_block(dims, precision, encs, n, Z, batch, ws):
+    sa, ss = encs
+    return _lib.MobodyIgdf(struct_bytes=_BYTES[_lib.MobodyIgdf], precision=prec_id(precision), d=dims, n=int(n), Z=int(Z),
+                           sa_blob=ptr(sa.blob), sa_blob_T=ptr(sa.blob_T), ss_blob=ptr(ss.blob), ss_blob_T=ptr(ss.blob_T),
+                           state=ptr(batch[0]), action=ptr(batch[1]), next_state=ptr(batch[2]), workspace=ptr(ws))
+
+
+def igdf_info(dims, precision, encs, n, Z, batch, loss_out, ws, grads=None, opts=None, t=0, t_dev=None, lr=0.0, bump=None):
+    """One contrastive update (igdf.py:418-447) on batch = (state[n, S], action[n, A], next_state[2n-1, S] = [tar s' | src s']);
+    loss_out[1].  grads = (grad_sa, grad_ss): the gradient form; opts = ((m_sa, v_sa), (m_ss, v_ss)): ONE fused Adam over both
+    encoders at step t (or t_dev[0]) and rate lr; bump: a device word the last optimizer launch increments."""
+    blk = _igdf_block(dims, precision, encs, n, Z, batch, ws)
+    if grads is not None:
+        blk.grad_sa, blk.grad_ss = ptr(grads[0]), ptr(grads[1])
+    if opts is not None:
+        (blk.m_sa, blk.v_sa), (blk.m_ss, blk.v_ss) = (ptr(opts[0][0]), ptr(opts[0][1])), (ptr(opts[1][0]), ptr(opts[1][1]))
+    blk.t, blk.t_dev, blk.lr, blk.bump, blk.loss_out = int(t), ptr(t_dev), float(lr), ptr(bump), ptr(loss_out)
+    check(load().mobody_igdf_info(C.byref(blk), cur_stream()), "mobody_igdf_info")
+
+
+def igdf_filter(dims, precision, encs, n, k, Z, importance_weight, staged, out, row_weight, ws, score_out=None, kept_out=None):
+    """The data filter (igdf.py:494-524): scores the first n rows of `staged` = (state, action, next_state, reward, not_done) of
+    [src(n) | tar], keeps the k best in ascending score order and writes `out` = [kept src | tar] (dims.N = k + n_tar rows) and
+    row_weight[dims.N] = exp(importance_weight * score) on the kept rows, 1 on the target rows."""
+    blk = _igdf_block(dims, precision, encs, n, Z, staged, ws)
+    blk.k, blk.importance_weight, blk.reward, blk.not_done = int(k), float(importance_weight), ptr(staged[3]), ptr(staged[4])
+    blk.out_state, blk.out_action, blk.out_next_state, blk.out_reward, blk.out_not_done = [ptr(t) for t in out]
+    blk.row_weight, blk.score_out, blk.kept_out = ptr(row_weight), ptr(score_out), ptr(kept_out)
+    check(load().mobody_igdf_filter(C.byref(blk), cur_stream()), "mobody_igdf_filter")
+
+
+def igdf_critic(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0,
+                bump=None, row_weight=None):
+    """iql_critic with the loss mean(w (q1 - y)^2) + mean(w (q2 - y)^2) (igdf.py:468-479); row_weight None: iql_critic."""
+    blk = _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws)
+    blk.grad, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(grad), ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    blk.bump = ptr(bump)
+    check(load().mobody_igdf_critic(C.byref(blk), ptr(row_weight), cur_stream()), "mobody_igdf_critic")
+
+
 def value_loss_grad(qt, v, n_global):
     """qt [2,N] target twin-Q(s,a), v [N] -> (dz3[N,16], loss[1]) of the expectile V loss."""
     N = v.numel()

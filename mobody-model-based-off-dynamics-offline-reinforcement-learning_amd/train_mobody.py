@@ -178,7 +178,7 @@ def load_yaml(domain, policy, env_base):
     """config/<domain>/<policy>/<env>.yaml next to the script (train_mobody.py:410-411); a built-in copy of the mujoco
     hyper-parameters of `mobody` and `td3_bc` is used when no config tree is present.  With $MOBODY_CONFIG_ROOT set,
     $MOBODY_CONFIG_ROOT/<domain>/<policy>/<env>.yaml is looked up first (a reference checkout's config/ directory: the only
-    source of `dara`'s hyper-parameters); unset, nothing changes."""
+    source of `dara`'s and `igdf`'s hyper-parameters); unset, nothing changes."""
     root = os.environ.get("MOBODY_CONFIG_ROOT")
     if root:
         path = os.path.join(root, domain, policy, env_base + ".yaml")
@@ -482,6 +482,10 @@ def _run(args, rank, world, device):
 
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
+    if config.get("info_pretrain") and hasattr(policy, "update_info"):
+        # IGDF's contrastive encoders: the reference's driver never trains them (they keep their initial values); an optional key
+        # of the merged config runs the class's update_info once, info_update_step steps, before the loop
+        policy.update_info(src_rb, tar_rb, config["batch_size"], writer)
     start = time.time()
     for t in range(int(config["max_step"])):
         policy.train(src_rb, tar_rb, config["batch_size"], writer, None)
