@@ -905,6 +905,158 @@ int mobody_dyn_validate_mopo(const float* dyn_blob, const float* mopo_blob, int 
 int mobody_mlp_transpose(int in_dim, int out_dim, int members, const float* blob, float* blob_T, int precision,
                          void* stream);
 
+/* ---- packed MLPs of any hidden width (BOSA's VAE nets, the reference's algo/offline_offline/bosa.py) ----------
+ * in_dim -> hidden -> hidden -> out_dim, ReLU on both hidden layers, `members` independent copies: the shape of the policy
+ * VAE's encoder / decoder (bosa.py:28-47, one member) and of the dynamics VAE's EnsembleFC stacks (bosa.py:176-200, :208-236).
+ * 1 <= in_dim <= 256, 8 <= hidden <= 1024, 1 <= out_dim <= 256, 1 <= members <= 8.  Parameter blob, per member, all row major:
+ * W1[Kp1][Hp] b1[Hp] W2[Hp][Hp] b2[Hp] W3[Hp][Np3] b3[Np3] (W stored [in][out]), Kp1 = round_up(in_dim, 16),
+ * Hp = round_up(hidden, 32), Np3 = round_up(out_dim, 32).  Padding is zero and stays zero through training: a padded hidden
+ * unit has pre-activation 0, so its ReLU mask and with it every gradient entry of the padding is exactly 0, and Adam maps a
+ * zero gradient with m = v = 0 to a zero update.  Gradients and both Adam moments use the same layout.  The wide nets run in
+ * exact fp32 (v_mfma_f32_32x32x2_f32) only: a `precision` other than 0 is MOBODY_E_ARG. */
+typedef struct MobodyWideLayout {
+  int32_t in_dim, hidden, out_dim, members, Kp1, Hp, Np3, _pad;
+  int64_t w1, b1, w2, b2, w3, b3;   /* float offsets inside one member */
+  int64_t member_floats, total_floats;
+} MobodyWideLayout;
+int mobody_wide_layout(int in_dim, int hidden, int out_dim, int members, MobodyWideLayout* out);
+
+enum { MOBODY_WIDE_OUT_RAW = 0, MOBODY_WIDE_OUT_TANH = 1 };
+
+/*   mobody_wide_mlp3_forward   bosa.py:49-70, :238-255 (the nn.Sequential / EnsembleFC stacks).  out[members][rows][out_dim] =
+ *                       layer3(relu(layer2(relu(layer1(x))))), raw or max_action * tanh.  x = [src0 | src1 | src2] row by row;
+ *                       source i is [rows][src_width_i] row major, member e's copy src_member_stride_i floats behind member
+ *                       e-1's (0: every member reads the same rows); a width of 0 drops the source; the widths add up to in_dim.
+ *                       src_rows_i (0: `rows`): the source holds that many rows and row r of x reads its row r % src_rows_i (the
+ *                       estimator's decoder runs num_samples copies of the batch against one copy of the states).
+ *                       x_shared = 1 when every used source has stride 0, else 0 (checked).  Saves (each nullable): save_x
+ *                       [x_shared ? 1 : members][rows][Kp1], save_h1 and save_h2 [members][rows][Hp], padding columns zero; what
+ *                       is not saved lives in `workspace` (mobody_wide_mlp3_forward_workspace floats; NULL when all three saves
+ *                       are given).  Four launches: the concatenation, one product per layer with its bias / activation folded in. */
+typedef struct MobodyWideFwd MobodyWideFwd;
+struct MobodyWideFwd {
+  int32_t struct_bytes;
+  int32_t precision;
+  MobodyWideLayout layout;
+  const float* blob;
+  const float *src0, *src1, *src2;
+  int32_t src_width0, src_width1, src_width2, x_shared;
+  int64_t src_member_stride0, src_member_stride1, src_member_stride2;
+  int64_t src_rows0, src_rows1, src_rows2;
+  int64_t rows;
+  int32_t out_mode;
+  float max_action;
+  float *out, *save_x, *save_h1, *save_h2, *workspace;
+};
+int64_t mobody_wide_mlp3_forward_workspace(const MobodyWideLayout* L, int64_t rows);
+int mobody_wide_mlp3_forward(const MobodyWideFwd* a, void* stream);
+
+/*   mobody_wide_mlp3_backward  what loss.backward() does to such a stack (bosa.py:525, :545).  From dz3[members][rows][out_dim] (the
+ *                       gradient of the loss with respect to the last layer's pre-activation output; for the tanh output mode the
+ *                       caller folds the tanh's derivative in) and the forward's saves x, h1, h2 it writes the parameter gradient
+ *                       `grad` in blob layout, padding included (zeros), and -- dx != NULL -- dx[members][rows][dx_col1 - dx_col0],
+ *                       the gradient with respect to columns [dx_col0, dx_col1) of x.  Every sum over rows runs inside one
+ *                       workgroup in ascending row order, no float atomics: two runs give the same bits.  workspace:
+ *                       mobody_wide_mlp3_backward_workspace floats.  Six launches, seven with dx: three weight gradients, two
+ *                       masked input gradients, the three bias gradients in one. */
+typedef struct MobodyWideBwd MobodyWideBwd;
+struct MobodyWideBwd {
+  int32_t struct_bytes;
+  int32_t precision;
+  MobodyWideLayout layout;
+  const float* blob;
+  const float *dz3, *x, *h1, *h2;
+  int32_t x_shared, reserved;
+  int64_t rows;
+  float* grad;
+  float* dx;
+  int32_t dx_col0, dx_col1;
+  float* workspace;
+};
+int64_t mobody_wide_mlp3_backward_workspace(const MobodyWideLayout* L, int64_t rows);
+int mobody_wide_mlp3_backward(const MobodyWideBwd* a, void* stream);
+
+/*   mobody_wide_adam          torch.optim.Adam(lr) with torch's defaults (bosa.py:424-425) on n floats of a flat blob -- one
+ *                       wide net or several laid end to end -- from a gradient of the same layout.  t is the 1-based step count;
+ *                       t_dev (nullable): a DEVICE int64 read instead, so that a captured graph advances.  One launch. */
+typedef struct MobodyWideAdam MobodyWideAdam;
+struct MobodyWideAdam {
+  int32_t struct_bytes;
+  int32_t reserved;
+  float* blob;
+  const float* grad;
+  float *m, *v;
+  int64_t n;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr;
+  int32_t reserved1;
+};
+int mobody_wide_adam(const MobodyWideAdam* a, void* stream);
+
+/* ---- BOSA's VAE stage (bosa.py:23-133, :203-327, :516-550) ----------------------------------------------------
+ * Both VAEs are two wide nets each, the encoder's blob directly followed by the decoder's in ONE tensor (gradient and Adam
+ * moments alike), with Lz the latent width:
+ *   kind MOBODY_BOSA_POLICY    members = 1, Lz = 2 A; encoder mobody_wide_layout(S + A, hidden, 2 Lz, 1) on [s | a];
+ *                              decoder (S + Lz, hidden, A, 1) on [s | z], output max_action * tanh
+ *   kind MOBODY_BOSA_DYNAMICS  members = E, Lz = 2 S; encoder (2 S + A, hidden, 2 Lz, E) on [s | a | s'], the same rows for
+ *                              every member; decoder (S + A + Lz, hidden, S, E) on [s | a | z_e], linear output
+ * Columns [0, Lz) of the encoder's output are the `mean` head, [Lz, 2 Lz) the `log_std` head.
+ *   mobody_bosa_reparam   bosa.py:116-117, :68, :521 (and :309-310, :253, :539), the row-wise piece, callable alone.  enc
+ *                       [n][2 Lz] (n = members * B rows), eps [n][Lz].  log_std = clamp(., -4, 15), std = exp, z = mean + std *
+ *                       eps -> z [n][Lz]; kl_out[0] = -0.5 mean(1 + log(std^2) - mean^2 - std^2) over the n Lz elements.  With
+ *                       dz != NULL ([n][Lz], dLoss/dz) it also writes denc [n][2 Lz], the gradient of
+ *                       (the loss behind dz) + beta * KL with respect to enc: the clamp passes gradient where -4 <= x <= 15, both
+ *                       ends inclusive, as torch's does.  Fixed summation order.  lossp: ceil(n Lz / 256) floats of scratch.
+ *   mobody_bosa_vae       bosa.py:516-550.  One training step of the VAE `kind` on B rows: encoder forward, the
+ *                       reparameterisation, decoder forward, recon = mean((u - target)^2) over all elements (the member axis
+ *                       included; target = action | next_state), KL as above, loss = recon + beta * KL, both backwards into
+ *                       `grad` (always written, blob layout), and -- m, v given -- one Adam over both nets with the step count t
+ *                       (or t_dev[0]) at rate lr.  eps [members][B][Lz], or NULL: element i is drawn from the device generator,
+ *                       stream MOBODY_BOSA_STREAM_POLICY / _DYNAMICS, call `call` + (call_dev ? call_dev[0] : 0).
+ *                       loss_out = (recon, KL, loss).  26 launches (25 without Adam).
+ *   mobody_bosa_loglik    bosa.py:72-105, :257-298.  The importance-sampling estimator, forward only, n = num_samples in [1, 64]:
+ *                       encode, draw n latents per row (and member), decode the n B rows, w = sum log N(x; dec, sqrt(beta / 4)) +
+ *                       sum log N(z; 0, 1) - sum log N(z; mean, std), ll = logsumexp_n(w) - log n with the maximum subtracted.
+ *                       ll [members][B]; dynamics only: min_ll [B] = min over members, mask [B] = (min_ll > log_eps) as 0 / 1,
+ *                       mask_mean [1] (each nullable).  w_out (nullable) [members][n][B].  eps: the reference's layouts, [B][n][Lz]
+ *                       (policy) / [n][members][B][Lz] (dynamics), or NULL: drawn at that linear index from stream
+ *                       MOBODY_BOSA_STREAM_POLICY_LL / _DYNAMICS_LL.  Forward only: grad, m, v must be NULL; t, t_dev, lr and
+ *                       loss_out are not read.  10 launches, 11 with mask_mean.
+ * mobody_bosa_workspace(a) floats serve both calls on the block (for mobody_bosa_loglik with its num_samples).  Refused with
+ * MOBODY_E_ARG before any runtime call, with the field named: kind, members != 1 for the policy VAE, a net outside
+ * mobody_wide_layout's ranges, precision != 0, B < 1, beta <= 0, num_samples outside [1, 64], one of m, v without the other,
+ * null pointers. */
+enum { MOBODY_BOSA_POLICY = 0, MOBODY_BOSA_DYNAMICS = 1 };
+enum { MOBODY_BOSA_STREAM_POLICY = 6, MOBODY_BOSA_STREAM_DYNAMICS = 7, MOBODY_BOSA_STREAM_POLICY_LL = 8, MOBODY_BOSA_STREAM_DYNAMICS_LL = 9 };
+typedef struct MobodyBosaVae MobodyBosaVae;
+struct MobodyBosaVae {
+  int32_t struct_bytes;
+  int32_t kind;
+  int32_t S, A, hidden, members;
+  int32_t precision, num_samples;
+  int64_t B;
+  float beta, max_action;
+  float* blob;
+  const float *state, *action, *next_state;
+  const float* eps;
+  uint32_t seed, call;
+  const int64_t* call_dev;
+  float* grad;
+  float *m, *v;
+  int64_t t;
+  const int64_t* t_dev;
+  float lr, log_eps;
+  float* loss_out;
+  float *ll, *min_ll, *mask, *mask_mean, *w_out;
+  float* workspace;
+};
+int64_t mobody_bosa_workspace(const MobodyBosaVae* a);
+int mobody_bosa_reparam(const float* enc, const float* eps, const float* dz, int64_t n, int32_t Lz, float beta, float* z,
+                        float* denc, float* lossp, float* kl_out, void* stream);
+int mobody_bosa_vae(const MobodyBosaVae* a, void* stream);
+int mobody_bosa_loglik(const MobodyBosaVae* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,12 +166,52 @@ class MobodyPretrainMopo(C.Structure):
                 ("t_dev", vp), ("lr", f32), ("loss_out", vp), ("loss_acc", vp), ("workspace", vp)]
 
 
+class MobodyWideLayout(C.Structure):
+    _fields_ = [("in_dim", i32), ("hidden", i32), ("out_dim", i32), ("members", i32), ("Kp1", i32), ("Hp", i32), ("Np3", i32),
+                ("_pad", i32), ("w1", i64), ("b1", i64), ("w2", i64), ("b2", i64), ("w3", i64), ("b3", i64),
+                ("member_floats", i64), ("total_floats", i64)]
+
+
+class MobodyWideFwd(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("layout", MobodyWideLayout), ("blob", vp), ("src0", vp), ("src1", vp),
+                ("src2", vp), ("src_width0", i32), ("src_width1", i32), ("src_width2", i32), ("x_shared", i32),
+                ("src_member_stride0", i64), ("src_member_stride1", i64), ("src_member_stride2", i64), ("src_rows0", i64),
+                ("src_rows1", i64), ("src_rows2", i64), ("rows", i64),
+                ("out_mode", i32), ("max_action", f32), ("out", vp), ("save_x", vp), ("save_h1", vp), ("save_h2", vp),
+                ("workspace", vp)]
+
+
+class MobodyWideBwd(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("layout", MobodyWideLayout), ("blob", vp), ("dz3", vp), ("x", vp),
+                ("h1", vp), ("h2", vp), ("x_shared", i32), ("reserved", i32), ("rows", i64), ("grad", vp), ("dx", vp),
+                ("dx_col0", i32), ("dx_col1", i32), ("workspace", vp)]
+
+
+class MobodyWideAdam(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("reserved", i32), ("blob", vp), ("grad", vp), ("m", vp), ("v", vp), ("n", i64), ("t", i64),
+                ("t_dev", vp), ("lr", f32), ("reserved1", i32)]
+
+
+class MobodyBosaVae(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("kind", i32), ("S", i32), ("A", i32), ("hidden", i32), ("members", i32), ("precision", i32),
+                ("num_samples", i32), ("B", i64), ("beta", f32), ("max_action", f32), ("blob", vp), ("state", vp), ("action", vp),
+                ("next_state", vp), ("eps", vp), ("seed", u32), ("call", u32), ("call_dev", vp), ("grad", vp), ("m", vp), ("v", vp),
+                ("t", i64), ("t_dev", vp), ("lr", f32), ("log_eps", f32), ("loss_out", vp), ("ll", vp), ("min_ll", vp), ("mask", vp),
+                ("mask_mean", vp), ("w_out", vp), ("workspace", vp)]
+
+
+WIDE_OUT_MODES = {"raw": 0, "tanh": 1}
+BOSA_KINDS = {"policy": 0, "dynamics": 1}
+BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9}    # MOBODY_BOSA_STREAM_*
+
+
 def block(cls, **fields):
     """An argument block with struct_bytes set and `fields` by name (everything else zero / NULL)."""
     return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
 
 
-BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo)}
+BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
+                                             MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -272,6 +312,16 @@ PROTOTYPES = {
     "mobody_dyn_validate_mopo": (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, vp, vp]),
     "mobody_dyn_validate_workspace": (i64, [C.c_int, C.c_int, i64]),
     "mobody_dyn_validate": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, i64, C.c_int, vp, vp, vp]),
+    "mobody_wide_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MobodyWideLayout)]),
+    "mobody_wide_mlp3_forward_workspace": (i64, [C.POINTER(MobodyWideLayout), i64]),
+    "mobody_wide_mlp3_forward": (C.c_int, [C.POINTER(MobodyWideFwd), vp]),
+    "mobody_wide_mlp3_backward_workspace": (i64, [C.POINTER(MobodyWideLayout), i64]),
+    "mobody_wide_mlp3_backward": (C.c_int, [C.POINTER(MobodyWideBwd), vp]),
+    "mobody_wide_adam": (C.c_int, [C.POINTER(MobodyWideAdam), vp]),
+    "mobody_bosa_workspace": (i64, [C.POINTER(MobodyBosaVae)]),
+    "mobody_bosa_reparam": (C.c_int, [vp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp]),
+    "mobody_bosa_vae": (C.c_int, [C.POINTER(MobodyBosaVae), vp]),
+    "mobody_bosa_loglik": (C.c_int, [C.POINTER(MobodyBosaVae), vp]),
 }
 
 _lib = None
@@ -352,4 +402,10 @@ def pretrain_layout(S, A):
 def pretrain_mopo_layout(S, A):
     L = MobodyPretrainMopoLayout()
     check(load().mobody_pretrain_mopo_layout(S, A, C.byref(L)), "mobody_pretrain_mopo_layout")
+    return L
+
+
+def wide_layout(in_dim, hidden, out_dim, members=1):
+    L = MobodyWideLayout()
+    check(load().mobody_wide_layout(in_dim, hidden, out_dim, members, C.byref(L)), "mobody_wide_layout")
     return L

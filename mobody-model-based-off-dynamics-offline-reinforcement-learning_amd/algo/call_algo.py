@@ -6,23 +6,21 @@ reference does.  Unknown names raise KeyError like the reference's dict lookup. 
 algorithms TD3_BC (`offline_offline/td3_bc.py`), IQL (`offline_offline/iql.py`), DARA (`offline_offline/dara.py`) and IGDF
 (`offline_offline/igdf.py`) are built, IQL, DARA and IGDF from a config of their own only: without `lam`, `temp`, `max_step` -- for
 DARA also `gaussian_noise_std`, `dara_eta` and, when `dara_eta` is 0, `eta`; for IGDF also `xi`, `importance_weight`, `repr_dim`,
-`ensemble_size`, `repr_norm`, `ortho_init`, `info_update_step` -- the constructor raises NotImplementedError.  bosa is outside the
-accelerated path.
+`ensemble_size`, `repr_norm`, `ortho_init`, `info_update_step` -- the constructor raises NotImplementedError.  BOSA
+(`offline_offline/bosa.py`) is built as far as its VAE stage: the behaviour and dynamics VAEs, their checkpoints and both likelihood
+estimators; a config without one of the seventeen keys the reference reads without defaults (`vae_policy_lr` ... `update_interval`)
+raises NotImplementedError in the constructor, and so does the train() call that would enter the critic / actor stage.
 """
 from .offline_offline.mobody import MOBODY
 from .offline_offline.td3_bc import TD3BC
 from .offline_offline.iql import IQL
 from .offline_offline.dara import DARA
 from .offline_offline.igdf import IGDF
-
-_BASELINES = ("bosa",)
+from .offline_offline.bosa import BOSA
 
 
 def call_algo(algo_name, config, mode, device, **kwargs):
     algo_name = algo_name.lower()
-    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC, "iql": IQL, "dara": DARA, "igdf": IGDF}
-    if algo_name in _BASELINES:
-        raise NotImplementedError(f"'{algo_name}' is a reference baseline outside the MI355X-accelerated path; "
-                                  "only 'mobody', 'td3_bc', 'iql', 'dara' and 'igdf' are built here")
+    algo_to_call = {"mobody": MOBODY, "td3_bc": TD3BC, "iql": IQL, "dara": DARA, "igdf": IGDF, "bosa": BOSA}
     algo = algo_to_call[algo_name]          # KeyError for unknown names, as in the reference
     return algo(config, device)

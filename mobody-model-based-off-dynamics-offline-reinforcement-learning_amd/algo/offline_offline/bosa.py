@@ -1,0 +1,437 @@
+"""BOSA baseline, VAE stage -- host-side mirror of the reference's `algo/offline_offline/bosa.py` (class BOSA), written from the
+algorithm.
+
+BOSA trains in two stages (bosa.py:552-639).  While `total_it < vae_iteration` a train() call only fits two VAEs on the mixed
+batch [tar(bs) | src(bs)]: a behaviour VAE over actions (`vae_policy`, VAE_Policy :23-133) and an ensemble dynamics VAE over next
+states (`vae_dyna`, VAE_Dynamics_Ensemble :203-327).  Afterwards a TD3-style critic / actor is trained, the critic masked by the
+dynamics VAE's importance-sampled log-likelihood and the actor regularised by the policy VAE's.  THIS CLASS BUILDS THE FIRST STAGE:
+the VAE steps, their checkpoints, and both likelihood estimators the second stage will consume.  A train() call that would enter
+the second stage raises NotImplementedError before it changes any state.
+
+Same plugin surface as the reference: `BOSA(config, device)`, `.train(src_rb, tar_rb, batch_size, writer, wandbrun)` (the
+reference's takes four arguments and its driver passes five), `.vae_policy .vae_dyna .vae_policy_optimizer .vae_dyna_optimizer`,
+`.vae_policy_train(batch) .vae_dyna_train(batch) .vae_models_train(batch)`, `.select_action(state, test)`, `.save/.load(prefix)`.
+
+Both VAEs are 750 wide in the reference's configs, so they run on the wide-MLP kernels (csrc/wide.hip, csrc/bosa.hip),
+in exact fp32 whatever MOBODY_MFMA / config['mfma'] says: the split-precision planes exist for 256-wide layers only.  With
+rng='device' and no logging step a whole train() call -- the gather of both buffers, the policy-VAE step, the dynamics-VAE step --
+replays as one HIP graph; the noise call ids and both Adam step counts then live in device words.
+
+Where the reference is odd: `vae_models_train` increments `total_it` a second time, so the VAE stage lasts
+`vae_iteration // 2` train() calls (`vae_steps`); `elbo_policy_loss`, `elbo_dyna_loss`, `iwae_*_loss` and `lamda_dyna` are never
+used by train() and are not built; EnsembleFC's unit-variance initial weights saturate the `log_std` clamp of an untrained 750-wide
+dynamics VAE (kept); `log(epsilon_dyna_exp)` masks every row until the dynamics VAE is well trained (kept).
+"""
+import math
+
+import numpy as np
+import torch
+
+from ... import _lib, dp, ops, packing
+from .mobody import _PackedNet
+
+_KEYS = ("vae_policy_lr", "vae_policy_hidden_dim", "vae_policy_beta", "vae_dyna_lr", "vae_dyna_ensemble", "vae_dyna_hidden_dim",
+         "vae_dyna_beta", "vae_iteration", "lamda_policy", "lamda_dyna", "epsilon_policy_exp", "epsilon_dyna_exp", "conservation_coef",
+         "num_samples", "noise_clip", "expl_noise", "update_interval")
+LOG_KEYS = ("VAE_Policy/reconstruction_loss", "VAE_Policy/KL_loss", "VAE_Policy/vae_loss", "VAE_Dynamics/reconstruction_loss",
+            "VAE_Dynamics/KL_loss", "VAE_Dynamics/vae_loss")
+SEED_POLICY, SEED_DYNA = 108, 109          # seed ids of the two VAEs' noise streams (101-107 are index streams)
+
+
+def vae_steps(vae_iteration):
+    """train() calls the VAE stage lasts: a call enters it while the once-incremented total_it is below vae_iteration and then
+    increments total_it again (bosa.py:509, :553, :560), so total_it is 2, 4, 6, ... after the calls."""
+    return max(int(vae_iteration), 0) // 2
+
+
+def _check_config(config):
+    missing = [k for k in _KEYS if k not in config]
+    if missing:
+        raise NotImplementedError(f"BOSA is built from a BOSA config only: config lacks {missing} (the reference's "
+                                  "config/*/bosa/*.yaml values are read without defaults; none are substituted here)")
+    for k in ("vae_policy_hidden_dim", "vae_dyna_hidden_dim"):
+        if not 8 <= int(config[k]) <= 1024:
+            raise ValueError(f"config['{k}'] = {config[k]} outside 8..1024")
+    if not 1 <= int(config["vae_dyna_ensemble"]) <= 8:
+        raise ValueError(f"config['vae_dyna_ensemble'] = {config['vae_dyna_ensemble']} outside 1..8")
+    if not 1 <= int(config["num_samples"]) <= 64:
+        raise ValueError(f"config['num_samples'] = {config['num_samples']} outside 1..64")
+    for k in ("vae_policy_beta", "vae_dyna_beta", "epsilon_policy_exp", "epsilon_dyna_exp"):
+        if not float(config[k]) > 0.0:
+            raise ValueError(f"config['{k}'] = {config[k]} must be positive")
+    if int(config["vae_iteration"]) < 0:
+        raise ValueError(f"config['vae_iteration'] = {config['vae_iteration']} < 0")
+
+
+class _WideVae(object):
+    """nn.Module-like handle on one VAE: two wide nets in ONE blob (encoder | decoder), the gradient in the same layout."""
+
+    def __init__(self, kind, S, A, hidden, members, beta, max_action, device):
+        self.kind, self.S, self.A, self.hidden, self.beta = kind, int(S), int(A), int(hidden), float(beta)
+        self.ensemble_size = 1 if kind == "policy" else int(members)
+        self.latent_dim = 2 * self.A if kind == "policy" else 2 * self.S
+        self.max_action, self.device = float(max_action), device
+        Lz, E = self.latent_dim, self.ensemble_size
+        if kind == "policy":
+            self.enc_layout, self.dec_layout = _lib.wide_layout(S + A, hidden, 2 * Lz, 1), _lib.wide_layout(S + Lz, hidden, A, 1)
+        else:
+            self.enc_layout, self.dec_layout = _lib.wide_layout(2 * S + A, hidden, 2 * Lz, E), _lib.wide_layout(S + A + Lz, hidden, S, E)
+        self.n_enc = self.enc_layout.total_floats
+        self.blob = torch.zeros(self.n_enc + self.dec_layout.total_floats, dtype=torch.float32, device=device)
+        self.grad = torch.zeros_like(self.blob)
+        self._pack = packing.pack_bosa_vae_policy if kind == "policy" else packing.pack_bosa_vae_dynamics
+        self.blob.copy_(torch.cat(self._pack(self._initial(), device)))
+        self.version = 1
+
+    def _initial(self):
+        S, A, H, Lz, E = self.S, self.A, self.hidden, self.latent_dim, self.ensemble_size
+        sd = {}
+        if self.kind == "policy":                                       # nn.Linear's default (bosa.py:38-55)
+            for k, (i, o) in (("encoder_shared.0", (S + A, H)), ("encoder_shared.2", (H, H)), ("mean", (H, Lz)), ("log_std", (H, Lz)),
+                              ("decoder.0", (S + Lz, H)), ("decoder.2", (H, H)), ("decoder.4", (H, A))):
+                bound = 1.0 / np.sqrt(i)
+                sd[k + ".weight"], sd[k + ".bias"] = torch.empty(o, i).uniform_(-bound, bound), torch.empty(o).uniform_(-bound, bound)
+        else:                                                           # EnsembleFC: fmod(randn, 2), zero bias (bosa.py:188-196)
+            for k, (i, o) in (("encoder_shared.0", (2 * S + A, H)), ("encoder_shared.2", (H, H)), ("mean", (H, Lz)), ("log_std", (H, Lz)),
+                              ("decoder.0", (S + A + Lz, H)), ("decoder.2", (H, H)), ("decoder.4", (H, S))):
+                sd[k + ".W"], sd[k + ".b"] = torch.fmod(torch.randn(E, i, o), 2), torch.zeros(E, 1, o)
+        return sd
+
+    def state_dict(self):
+        enc, dec = self.blob[:self.n_enc], self.blob[self.n_enc:]
+        if self.kind == "policy":
+            return packing.unpack_bosa_vae_policy(enc, dec, self.S, self.A, self.hidden)
+        return packing.unpack_bosa_vae_dynamics(enc, dec, self.S, self.A, self.hidden, self.ensemble_size)
+
+    def pack(self, sd):
+        """A dict with this VAE's keys and shapes -> one tensor in blob layout (encoder | decoder)."""
+        want = {k: tuple(v.shape) for k, v in self.state_dict().items()}
+        got = {k: tuple(torch.as_tensor(v).shape) for k, v in sd.items()}
+        if got != want:
+            raise ValueError(f"{self.kind} VAE: state_dict keys / shapes {got} do not match {want}")
+        return torch.cat(self._pack(sd, self.device))
+
+    def load_state_dict(self, sd):
+        self.blob.copy_(self.pack(sd))                                   # in place: captured graphs and Adam hold the pointer
+        self.version += 1
+
+    def parameters(self):
+        return list(self.state_dict().values())
+
+    def block(self, B, num_samples=0, **fields):
+        return ops.bosa_block(self.kind, self.S, self.A, self.hidden, self.ensemble_size, B, self.beta, self.max_action, num_samples,
+                              blob=self.blob, **fields)
+
+
+class _WideAdam(object):
+    """torch.optim.Adam(vae.parameters(), lr) (bosa.py:406, :414): one optimizer over the VAE's 14 parameters, one step count;
+    state_dict in torch's format, parameters in the module's order."""
+
+    def __init__(self, vae, lr):
+        self.vae, self.lr, self.t = vae, float(lr), 0
+        self.m, self.v = torch.zeros_like(vae.blob), torch.zeros_like(vae.blob)
+
+    def _unpack(self, blob):
+        v = self.vae
+        enc, dec = blob[:v.n_enc], blob[v.n_enc:]
+        if v.kind == "policy":
+            return list(packing.unpack_bosa_vae_policy(enc, dec, v.S, v.A, v.hidden).values())
+        return list(packing.unpack_bosa_vae_dynamics(enc, dec, v.S, v.A, v.hidden, v.ensemble_size).values())
+
+    def state_dict(self):
+        ms, vs = self._unpack(self.m), self._unpack(self.v)
+        state = {i: dict(step=torch.tensor(float(self.t)), exp_avg=ms[i], exp_avg_sq=vs[i]) for i in range(len(ms))} if self.t else {}
+        group = dict(lr=self.lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False, foreach=None,
+                     capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, params=list(range(len(ms))))
+        return dict(state=state, param_groups=[group])
+
+    def load_state_dict(self, sd):
+        st = sd["state"]
+        self.lr = float(sd["param_groups"][0]["lr"])
+        if not st:
+            self.t = 0
+            self.m.zero_(); self.v.zero_()
+            return
+        keys = list(self.vae.state_dict())
+        if sorted(st) != list(range(len(keys))):
+            raise ValueError(f"{self.vae.kind} VAE optimizer: expected the state of {len(keys)} parameters, got {sorted(st)}")
+        for name, dst in (("exp_avg", self.m), ("exp_avg_sq", self.v)):
+            dst.copy_(self.vae.pack({k: st[i][name] for i, k in enumerate(keys)}))
+        self.t = int(float(st[0]["step"]))
+
+
+class BOSA(object):
+    third_loss_name = "vae_dyna_loss"
+
+    def __init__(self, config, device):
+        # 1. the keys the reference reads without defaults: a config without them is not a BOSA run (the refusal has the type the
+        #    registry gave for 'bosa' before this class existed).  2. ranges.  3. data parallel.  4. the device.
+        _check_config(config)
+        d = torch.distributed
+        if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
+            raise NotImplementedError("data-parallel BOSA is not built: run 'bosa' on one GPU (only 'mobody' has the exchange "
+                                      "protocol of mobody_amd.dp wired through the CLI)")
+        self.config = config
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("BOSA (MI355X build) needs a GPU device; there is no CPU fallback")
+        S, A = int(config["state_dim"]), int(config["action_dim"])
+        self.S, self.A, self.max_action = S, A, float(config["max_action"])
+        self.discount, self.tau = config.get("gamma"), config.get("tau")
+        self.update_interval = config["update_interval"]
+        self.vae_iteration = int(config["vae_iteration"])
+        self.vae_policy_beta, self.vae_dyna_beta = float(config["vae_policy_beta"]), float(config["vae_dyna_beta"])
+        self.lamda_policy, self.lamda_dyna = config["lamda_policy"], config["lamda_dyna"]
+        self.epsilon_policy_exp, self.epsilon_dyna_exp = float(config["epsilon_policy_exp"]), float(config["epsilon_dyna_exp"])
+        self.conservation_coef, self.num_samples = config["conservation_coef"], int(config["num_samples"])
+        self.noise_clip, self.expl_noise = config["noise_clip"], config["expl_noise"]
+        self.rng, self.seed = config.get("rng", "numpy"), int(config.get("seed", 0))
+        self.use_graph = int(config.get("graph", 0))
+        self.vae_policy = _WideVae("policy", S, A, config["vae_policy_hidden_dim"], 1, self.vae_policy_beta, self.max_action, self.device)
+        self.vae_policy_optimizer = _WideAdam(self.vae_policy, config["vae_policy_lr"])
+        self.vae_dyna = _WideVae("dynamics", S, A, config["vae_dyna_hidden_dim"], config["vae_dyna_ensemble"], self.vae_dyna_beta, 1.0,
+                                 self.device)
+        self.vae_dyna_optimizer = _WideAdam(self.vae_dyna, config["vae_dyna_lr"])
+        # the TD3 actor of the second stage (Actor, bosa.py:330-349): untrained here, select_action works
+        self.actor = _PackedNet(S, A, 1, ("",), self.device, out_mode=1, max_action=self.max_action, precision=ops.prec_id(ops.default_mfma()))
+        self.dynamics = None
+        self.total_it = 0
+        self._noise_calls = 0                                     # VAE noise draws done (rng='device': the streams' call id)
+        self._loss = torch.zeros(6, dtype=torch.float32, device=self.device)         # LOG_KEYS order
+        self._ctr = torch.zeros(3, dtype=torch.int64, device=self.device)            # [replays since capture, policy t, dyna t]
+        self._batch, self._batch_key, self._ws = None, None, {}
+        self._graph, self._graph_key, self._graph_base = None, None, None
+        self.noise_fn = None          # optional hook (tests): (kind, shape) -> fp32 array of that shape, the VAE's latent noise
+        self._synced = True
+
+    # ------------------------------------------------------------------ acting
+    def select_action(self, state, test=False):
+        """bosa.py:431-434."""
+        x = state if isinstance(state, torch.Tensor) else torch.as_tensor(np.asarray(state), dtype=torch.float32)
+        return self.actor(x.reshape(1, -1).to(self.device)).squeeze().cpu().numpy()
+
+    def _seed_for(self, k):
+        return (self.seed + k + dp.rank_salt()) & 0xFFFFFFFF
+
+    def _health_check(self):
+        """The wide nets run in exact fp32 and report no f16 range faults; a non-finite parameter is reported here (a device
+        sync: called on logging steps, in save() and at the end of the CLI's run, never per step)."""
+        for name, v in (("vae_policy", self.vae_policy), ("vae_dyna", self.vae_dyna)):
+            if not bool(torch.isfinite(v.blob).all()):
+                raise FloatingPointError(f"{name}: non-finite parameters after {self.total_it} counts of total_it")
+
+    # ------------------------------------------------------------------ the VAE steps (bosa.py:507-550)
+    def _workspace(self, vae, B, num_samples=0):
+        key = (vae.kind, B, num_samples)
+        if key not in self._ws:
+            self._ws[key] = ops.bosa_workspace(vae.block(B, num_samples), self.device)
+        return self._ws[key]
+
+    def _vae_step(self, vae, opt, b, loss, dev=False):
+        """One training step of `vae` on the staged batch b.  dev: the captured form -- noise call id and step count in device words."""
+        B = b[0].shape[0]
+        sid = SEED_POLICY if vae.kind == "policy" else SEED_DYNA
+        eps = None
+        if self.noise_fn is not None:
+            eps = torch.as_tensor(self.noise_fn(vae.kind, (vae.ensemble_size, B, vae.latent_dim)), dtype=torch.float32).to(self.device).contiguous()
+        elif self.rng != "device":                     # the reference's torch.randn_like(std), from torch's generator
+            eps = torch.randn(vae.ensemble_size, B, vae.latent_dim, device=self.device)
+        if not dev:
+            opt.t += 1
+        call, t_dev, call_dev = self._noise_calls, None, None
+        if dev:
+            base = self._graph_base
+            call, t_dev, call_dev = base["noise"] + 1, self._ctr[1:2] if vae.kind == "policy" else self._ctr[2:3], self._ctr[0:1]
+        blk = vae.block(B, state=b[0], action=b[1], next_state=b[2], eps=eps, seed=self._seed_for(sid), call=call, call_dev=call_dev,
+                        grad=vae.grad, m=opt.m, v=opt.v, t=opt.t, t_dev=t_dev, lr=opt.lr, loss_out=loss, workspace=self._workspace(vae, B))
+        self._keep = (eps,)
+        ops.bosa_vae(blk)
+
+    @staticmethod
+    def _as_batch(batch, device):
+        return tuple(torch.as_tensor(t, dtype=torch.float32).to(device).contiguous() for t in batch[:3])
+
+    def _log_dict(self, lo, hi):
+        return dict(zip(LOG_KEYS[lo:hi], [float(x) for x in self._loss[lo:hi].tolist()]))
+
+    def vae_policy_train(self, batch):
+        """bosa.py:516-532 on (state, action, ...); returns the reference's log dict (a device read)."""
+        self._noise_calls += 1
+        self._vae_step(self.vae_policy, self.vae_policy_optimizer, self._as_batch(batch, self.device), self._loss[0:3])
+        return self._log_dict(0, 3)
+
+    def vae_dyna_train(self, batch):
+        """bosa.py:534-550."""
+        self._noise_calls += 1
+        self._vae_step(self.vae_dyna, self.vae_dyna_optimizer, self._as_batch(batch, self.device), self._loss[3:6])
+        return self._log_dict(3, 6)
+
+    def vae_models_train(self, batch):
+        """bosa.py:507-514: counts total_it once more, then both VAE steps."""
+        self.total_it += 1
+        self._graph = None
+        log = self.vae_policy_train(batch)
+        log.update(self.vae_dyna_train(batch))
+        return log
+
+    # ------------------------------------------------------------------ the estimators (bosa.py:72-105, :257-298, :584-591)
+    def _loglik(self, vae, state, action, next_state, num_samples, log_eps=0.0, mask=False):
+        n = self.num_samples if num_samples is None else int(num_samples)
+        if not 1 <= n <= 64:
+            raise ValueError(f"num_samples = {n} outside 1..64")
+        b = self._as_batch((state, action, next_state if next_state is not None else state), self.device)
+        B, E = b[0].shape[0], vae.ensemble_size
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+        out = dict(ll=new(E, B))
+        if mask:
+            out.update(min_ll=new(B), mask=new(B), mask_mean=new(1))
+        eps, policy = None, vae.kind == "policy"
+        shape = (B, n, vae.latent_dim) if policy else (n, E, B, vae.latent_dim)
+        if self.noise_fn is not None:
+            eps = torch.as_tensor(self.noise_fn(vae.kind + "_ll", shape), dtype=torch.float32).to(self.device).contiguous()
+        elif self.rng != "device":
+            eps = torch.randn(*shape, device=self.device)
+        self._noise_calls += 1
+        self._graph = None                                          # a captured step's call ids continue from the host's counts
+        ops.bosa_loglik(vae.block(B, n, state=b[0], action=b[1], next_state=b[2], eps=eps, seed=self._seed_for(SEED_POLICY if policy else SEED_DYNA),
+                                  call=self._noise_calls, log_eps=float(log_eps), workspace=self._workspace(vae, B, n), **out))
+        return out
+
+    def policy_log_likelihood(self, state, action, num_samples=None):
+        """VAE_Policy.importance_sampling_estimator(state, action, vae_policy_beta, num_samples) -> [B]."""
+        return self._loglik(self.vae_policy, state, action, None, num_samples)["ll"][0]
+
+    def dyna_log_likelihood(self, state, action, next_state, num_samples=None):
+        """VAE_Dynamics_Ensemble.importance_sampling_estimator(...) -> [E, B]."""
+        return self._loglik(self.vae_dyna, state, action, next_state, num_samples)["ll"]
+
+    def dyna_mask(self, state, action, next_state):
+        """The critic's mask (bosa.py:584-591): (min over members of the log-likelihood > log(epsilon_dyna_exp)) as 0 / 1 floats,
+        and its mean (`critic_mask_ratio`, a device scalar)."""
+        out = self._loglik(self.vae_dyna, state, action, next_state, None, log_eps=math.log(self.epsilon_dyna_exp), mask=True)
+        return out["mask"], out["mask_mean"][0]
+
+    # ------------------------------------------------------------------ training (bosa.py:552-639)
+    def _gather(self, src, tar, bs):
+        """Rows [tar(bs) | src(bs)] (bosa.py:557-558); the index draws in the reference's order, src first."""
+        if self.rng == "device":
+            for rb in (src, tar):
+                if rb.size <= 0:
+                    raise ValueError("low >= high")
+                rb._draws += 1
+            salt = dp.rank_salt()
+            ops.gather_batch_rng([tar._fields(), src._fields()], [bs, bs], [(rb.seed + salt) & 0xFFFFFFFF for rb in (tar, src)],
+                                 [tar._draws, src._draws], None, [tar.ptr_size[1:2], src.ptr_size[1:2]], self.S, self.A, self._batch)
+        else:
+            i_src = src.draw_indices(bs)
+            i_tar = tar.draw_indices(bs)
+            ops.gather_batch([tar._fields(), src._fields()], [i_tar, i_src], self.S, self.A, out=self._batch)
+
+    def _graph_step(self, src, tar, bs):
+        """Replay (capturing first) one VAE-stage call: both gathers, the policy-VAE step, the dynamics-VAE step."""
+        po, do = self.vae_policy_optimizer, self.vae_dyna_optimizer
+        key = (bs, id(src), id(tar), src.state.data_ptr(), tar.state.data_ptr(), tuple(t.data_ptr() for t in self._batch),
+               self.vae_policy.blob.data_ptr(), self.vae_dyna.blob.data_ptr(), po.m.data_ptr(), do.m.data_ptr())
+        base = self._graph_base
+        if self._graph is not None and (tar._draws, src._draws) != (base["tar"] + base["replays"], base["src"] + base["replays"]):
+            self._graph = None                                      # somebody else drew from a buffer: re-seed the call ids
+        if self._graph is None or self._graph_key != key:
+            torch.cuda.synchronize()
+            self._ctr.copy_(torch.tensor([0, po.t, do.t], dtype=torch.int64))
+            self._graph_base = dict(noise=self._noise_calls, tar=tar._draws, src=src._draws, replays=0)
+            base, c, salt = self._graph_base, self._ctr, dp.rank_salt()
+            self._workspace(self.vae_policy, 2 * bs), self._workspace(self.vae_dyna, 2 * bs)     # sized outside the capture
+
+            def step():
+                # call ids: base + 1 + replays done (c[0]); the gather advances both Adam step counts (it does not read them),
+                # the last launch advances c[0]
+                ops.gather_batch_rng([tar._fields(), src._fields()], [bs, bs], [(rb.seed + salt) & 0xFFFFFFFF for rb in (tar, src)],
+                                     [base["tar"] + 1, base["src"] + 1], c[0:1], [tar.ptr_size[1:2], src.ptr_size[1:2]], self.S, self.A,
+                                     self._batch, bump=(c[1:2], c[2:3]))
+                self._vae_step(self.vae_policy, po, self._batch, self._loss[0:3], dev=True)
+                self._vae_step(self.vae_dyna, do, self._batch, self._loss[3:6], dev=True)
+                ops.counter_add(c[0:1], 1)
+            g = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    step()
+            except Exception as exc:
+                import warnings
+                torch.cuda.synchronize()
+                warnings.warn(f"HIP-graph capture of the VAE-stage step failed ({exc!r}); continuing eagerly")
+                self.use_graph, self._graph = 0, None
+                return False
+            self._graph, self._graph_key = g, key
+        self._graph.replay()
+        self._graph_base["replays"] += 1
+        tar._draws += 1
+        src._draws += 1
+        self._noise_calls += 1
+        po.t += 1
+        do.t += 1
+        return True
+
+    def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
+        """One call of the reference's train(), VAE stage.  total_it += 1; fewer than batch_size rows in either buffer: return;
+        draw src(bs) then tar(bs); total_it < vae_iteration: both VAE steps, and total_it += 1 once more."""
+        bs = int(batch_size)
+        short = src_replay_buffer.size < bs or tar_replay_buffer.size < bs
+        if not short and not self.total_it + 1 < self.vae_iteration:
+            raise NotImplementedError(f"BOSA's critic / actor stage is not built: this call would leave the VAE stage (total_it "
+                                      f"{self.total_it}, vae_iteration {self.vae_iteration}: {vae_steps(self.vae_iteration)} train() "
+                                      "calls); nothing was changed")
+        self.total_it += 1
+        if short:
+            return
+        self.total_it += 1                                          # vae_models_train's own count (bosa.py:509)
+        log5k = writer is not None and self.total_it % 5000 == 0
+        N = 2 * bs
+        want = self.use_graph == 1 or (self.use_graph == 2 and N < 4096)
+        if (want and self.rng == "device" and self.noise_fn is None and not log5k and self._batch_key == (N,)
+                and self._graph_step(src_replay_buffer, tar_replay_buffer, bs)):
+            return
+        self._graph = None                                          # an eager step moves the host-side counts
+        if self._batch_key != (N,):
+            dev = self.device
+            self._batch = tuple(torch.empty(N, w, device=dev) for w in (self.S, self.A, self.S, 1, 1))
+            self._batch_key = (N,)
+        self._gather(src_replay_buffer, tar_replay_buffer, bs)
+        self._noise_calls += 1                                      # one call id for both VAEs' streams
+        self._vae_step(self.vae_policy, self.vae_policy_optimizer, self._batch, self._loss[0:3])
+        self._vae_step(self.vae_dyna, self.vae_dyna_optimizer, self._batch, self._loss[3:6])
+        if log5k:                                                   # bosa.py:636-639
+            self._health_check()
+            for k, v in self._log_dict(0, 6).items():
+                writer.add_scalar(f"train/{k}", v, self.total_it)
+
+    def losses(self):
+        """(policy-VAE loss, dynamics-VAE reconstruction loss, dynamics-VAE loss) of the last step (forces a device sync)."""
+        x = self._loss.tolist()
+        return float(x[2]), float(x[3]), float(x[5])
+
+    def log_line(self):
+        """The CLI's periodic line: the six VAE losses under their own names (a device sync)."""
+        return " ".join(f"{k} {v:.4f}" for k, v in self._log_dict(0, 6).items())
+
+    def max_train_steps(self):
+        """train() calls this build can run from a fresh object: the VAE stage's."""
+        return vae_steps(self.vae_iteration)
+
+    # ------------------------------------------------------------------ checkpoints (bosa.py:641-665)
+    def save(self, filename):
+        """The reference's four VAE files.  Its six critic / actor files belong to the second stage and are not written."""
+        self._health_check()
+        torch.save(self.vae_policy.state_dict(), filename + "_vae_policy")
+        torch.save(self.vae_policy_optimizer.state_dict(), filename + "_vae_policy_optimizer")
+        torch.save(self.vae_dyna.state_dict(), filename + "_vae_dynamics")
+        torch.save(self.vae_dyna_optimizer.state_dict(), filename + "_vae_dynamics_optimizer")
+
+    def load(self, filename):
+        """Reads the four VAE files (the reference's load goes on to pass a file NAME to the actor optimizer's load_state_dict
+        and cannot run; the critic / actor files are the second stage's)."""
+        ld = lambda s: torch.load(filename + s, map_location="cpu", weights_only=True)
+        self.vae_policy.load_state_dict(ld("_vae_policy"))
+        self.vae_policy_optimizer.load_state_dict(ld("_vae_policy_optimizer"))
+        self.vae_dyna.load_state_dict(ld("_vae_dynamics"))
+        self.vae_dyna_optimizer.load_state_dict(ld("_vae_dynamics_optimizer"))
+        self._graph = None

@@ -956,3 +956,92 @@ def ens_replay(dyn_blob, S, A, task_id, data, data_rows, row0, H, elites, seed, 
     a.workspace = ptr(ws)
     check(load().mobody_ens_replay(C.byref(a), cur_stream()), "mobody_ens_replay")
     return ws
+
+
+# ---- wide MLPs (csrc/wide.hip): BOSA's VAE nets, exact fp32 whatever MOBODY_MFMA says ------------------------------------
+def wide_mlp3_forward(blob, L, sources, out_mode="raw", max_action=1.0, save=False, precision=0):
+    """The wide net `blob` (layout L = _lib.wide_layout(...)) on x = the `sources` (up to three) side by side.  A 2-D source
+    [rows, w] is read by every member, a 3-D one [members, rows, w] holds one copy per member.  Returns out
+    [members, rows, out_dim], or with save=True (out, x, h1, h2): the tensors mobody_wide_mlp3_backward reads, x
+    [1 or members, rows, Kp1] and h1, h2 [members, rows, Hp]."""
+    srcs = [_f32(s) for s in sources]
+    assert 1 <= len(srcs) <= 3
+    rows, dev, E = srcs[0].shape[-2], blob.device, L.members
+    shared = all(s.dim() == 2 for s in srcs)
+    for s in srcs:
+        assert s.shape[-2] == rows and (s.dim() == 2 or (s.dim() == 3 and s.shape[0] == E)), tuple(s.shape)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = new(E, rows, L.out_dim)
+    x, h1, h2 = new(1 if shared else E, rows, L.Kp1), new(E, rows, L.Hp), new(E, rows, L.Hp)
+    a = _lib.block(_lib.MobodyWideFwd, precision=prec_id(precision), layout=L, blob=ptr(blob), x_shared=int(shared), rows=rows,
+                   out_mode=_lib.WIDE_OUT_MODES[out_mode], max_action=float(max_action), out=ptr(out), save_x=ptr(x),
+                   save_h1=ptr(h1), save_h2=ptr(h2))
+    for i, s in enumerate(srcs):
+        setattr(a, "src%d" % i, ptr(s))
+        setattr(a, "src_width%d" % i, s.shape[-1])
+        setattr(a, "src_member_stride%d" % i, 0 if s.dim() == 2 else rows * s.shape[-1])
+    check(load().mobody_wide_mlp3_forward(C.byref(a), cur_stream()), "mobody_wide_mlp3_forward")
+    return (out, x, h1, h2) if save else out
+
+
+def wide_mlp3_backward(blob, L, dz3, x, h1, h2, grad=None, dx_cols=None, ws=None, precision=0):
+    """Parameter gradient (blob layout, padding written as zero) of a wide net from dz3 [members, rows, out_dim] and the
+    forward's saves; dx_cols = (c0, c1): also d loss / d x[:, c0:c1] as [members, rows, c1 - c0].  Returns (grad, dx or None)."""
+    rows, dev, E = dz3.shape[1], blob.device, L.members
+    grad = torch.empty(L.total_floats, dtype=torch.float32, device=dev) if grad is None else grad
+    need = load().mobody_wide_mlp3_backward_workspace(C.byref(L), rows)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    dx, c0, c1 = None, 0, 0
+    if dx_cols is not None:
+        c0, c1 = dx_cols
+        assert 0 <= c0 < c1 <= L.in_dim, dx_cols
+        dx = torch.empty(E, rows, c1 - c0, dtype=torch.float32, device=dev)
+    a = _lib.block(_lib.MobodyWideBwd, precision=prec_id(precision), layout=L, blob=ptr(blob), dz3=ptr(dz3), x=ptr(x), h1=ptr(h1),
+                   h2=ptr(h2), x_shared=int(x.shape[0] == 1), rows=rows, grad=ptr(grad), dx=ptr(dx), dx_col0=c0, dx_col1=c1, workspace=ptr(ws))
+    check(load().mobody_wide_mlp3_backward(C.byref(a), cur_stream()), "mobody_wide_mlp3_backward")
+    return grad, dx
+
+
+def wide_adam(blob, grad, m, v, lr, t=0, t_dev=None):
+    """One torch-default Adam step on a flat wide blob (or several laid end to end); t_dev: device int64 step count."""
+    a = _lib.block(_lib.MobodyWideAdam, blob=ptr(blob), grad=ptr(grad), m=ptr(m), v=ptr(v), n=blob.numel(), t=int(t), t_dev=ptr(t_dev),
+                   lr=float(lr))
+    check(load().mobody_wide_adam(C.byref(a), cur_stream()), "mobody_wide_adam")
+
+
+# ---- BOSA's VAE stage (csrc/bosa.hip) -------------------------------------------------------------------------------------
+def bosa_block(kind, S, A, hidden, members, B, beta, max_action=1.0, num_samples=0, **fields):
+    """A MobodyBosaVae block of the VAE `kind` ('policy' | 'dynamics'); tensors by field name."""
+    return _lib.block(_lib.MobodyBosaVae, kind=_lib.BOSA_KINDS[kind], S=int(S), A=int(A), hidden=int(hidden), members=int(members),
+                      B=int(B), beta=float(beta), max_action=float(max_action), num_samples=int(num_samples),
+                      **{k: (ptr(v) if isinstance(v, torch.Tensor) or v is None else v) for k, v in fields.items()})
+
+
+def bosa_workspace(blk, device):
+    n = load().mobody_bosa_workspace(C.byref(blk))
+    if n < 0:
+        raise _lib.MobodyError("mobody_bosa_workspace: bad block: " + load().mobody_last_error().decode(errors="replace"))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bosa_reparam(enc, eps, beta, dz=None):
+    """enc [n, 2 Lz], eps [n, Lz] -> (z [n, Lz], kl [1], denc [n, 2 Lz] or None): clamp / exp / reparameterise, the KL term and
+    -- dz = dLoss/dz given -- the gradient of Loss + beta KL with respect to enc (bosa.py:116-117, :68, :521)."""
+    n, Lz = eps.shape
+    dev = enc.device
+    z = torch.empty(n, Lz, dtype=torch.float32, device=dev)
+    kl = torch.empty(1, dtype=torch.float32, device=dev)
+    denc = torch.empty(n, 2 * Lz, dtype=torch.float32, device=dev) if dz is not None else None
+    lossp = torch.empty((n * Lz + 255) // 256, dtype=torch.float32, device=dev)
+    check(load().mobody_bosa_reparam(ptr(enc), ptr(eps), ptr(dz), n, Lz, float(beta), ptr(z), ptr(denc), ptr(lossp), ptr(kl),
+                                     cur_stream()), "mobody_bosa_reparam")
+    return z, kl, denc
+
+
+def bosa_vae(blk):
+    check(load().mobody_bosa_vae(C.byref(blk), cur_stream()), "mobody_bosa_vae")
+
+
+def bosa_loglik(blk):
+    check(load().mobody_bosa_loglik(C.byref(blk), cur_stream()), "mobody_bosa_loglik")

@@ -192,3 +192,91 @@ def unpack_pretrain_mopo(blob, S, A, into=None):
         for k, v in out.items():
             into[k] = v
     return out
+
+
+# ---- wide MLPs (csrc/wide.hip, MobodyWideLayout): BOSA's VAE nets --------------------------------------------------------
+def pack_wide(W1, b1, W2, b2, W3, b3, device):
+    """W_i [E, in, out], b_i [E, out] (EnsembleFC's orientation; an nn.Linear weight goes in as weight.t()[None]) -> the flat
+    zero-padded blob of mobody_wide_layout(in, hidden, out, E)."""
+    g = lambda t: torch.as_tensor(t, dtype=torch.float32).to(device)
+    W1, b1, W2, b2, W3, b3 = (g(t) for t in (W1, b1, W2, b2, W3, b3))
+    E, in_dim, hidden = W1.shape
+    out_dim = W3.shape[2]
+    assert W2.shape == (E, hidden, hidden) and W3.shape == (E, hidden, out_dim), (tuple(W2.shape), tuple(W3.shape))
+    assert b1.shape == (E, hidden) and b2.shape == (E, hidden) and b3.shape == (E, out_dim)
+    L = _lib.wide_layout(in_dim, hidden, out_dim, E)
+    blob = torch.zeros(E, L.member_floats, dtype=torch.float32, device=device)
+    for off, t, K, N in ((L.w1, W1, L.Kp1, L.Hp), (L.w2, W2, L.Hp, L.Hp), (L.w3, W3, L.Hp, L.Np3)):
+        blob[:, off:off + K * N].view(E, K, N)[:, :t.shape[1], :t.shape[2]] = t
+    for off, t in ((L.b1, b1), (L.b2, b2), (L.b3, b3)):
+        blob[:, off:off + t.shape[1]] = t
+    return blob.reshape(-1)
+
+
+def unpack_wide(blob, in_dim, hidden, out_dim, members):
+    """Inverse of pack_wide: (W1, b1, W2, b2, W3, b3) as clones, W_i [E, in, out], b_i [E, out].  Works on any tensor in blob
+    layout (a gradient, an Adam moment)."""
+    L = _lib.wide_layout(in_dim, hidden, out_dim, members)
+    blob = blob.reshape(members, L.member_floats)
+    W = lambda off, K, N, k, n: blob[:, off:off + K * N].view(members, K, N)[:, :k, :n].clone()
+    b = lambda off, n: blob[:, off:off + n].clone()
+    return (W(L.w1, L.Kp1, L.Hp, in_dim, hidden), b(L.b1, hidden), W(L.w2, L.Hp, L.Hp, hidden, hidden), b(L.b2, hidden),
+            W(L.w3, L.Hp, L.Np3, hidden, out_dim), b(L.b3, out_dim))
+
+
+def wide_padding_mask(in_dim, hidden, out_dim, members, device="cpu"):
+    """Bool tensor in blob layout: True on the padding entries (the ones no reference parameter maps to)."""
+    ones = lambda *s: torch.ones(*s)
+    used = pack_wide(ones(members, in_dim, hidden), ones(members, hidden), ones(members, hidden, hidden), ones(members, hidden),
+                     ones(members, hidden, out_dim), ones(members, out_dim), device)
+    return used == 0
+
+
+# BOSA's VAEs (bosa.py:23-133, :203-327) are two wide nets each: the encoder with the `mean` and `log_std` heads packed as ONE
+# output layer (columns [0, L) mean, [L, 2L) log_std), and the decoder.
+def pack_bosa_vae_policy(sd, device):
+    """VAE_Policy.state_dict() -> (encoder blob, decoder blob)."""
+    g = lambda k: torch.as_tensor(sd[k], dtype=torch.float32)
+    lin = lambda p: (g(p + ".weight").t()[None], g(p + ".bias")[None])
+    (W1, b1), (W2, b2) = lin("encoder_shared.0"), lin("encoder_shared.2")
+    (Wm, bm), (Ws, bs) = lin("mean"), lin("log_std")
+    enc = pack_wide(W1, b1, W2, b2, torch.cat([Wm, Ws], 2), torch.cat([bm, bs], 1), device)
+    (D1, d1), (D2, d2), (D3, d3) = lin("decoder.0"), lin("decoder.2"), lin("decoder.4")
+    return enc, pack_wide(D1, d1, D2, d2, D3, d3, device)
+
+
+def unpack_bosa_vae_policy(enc, dec, S, A, hidden, latent=None):
+    """Inverse of pack_bosa_vae_policy (any tensors in blob layout): a dict with VAE_Policy's keys, nn.Linear orientation."""
+    Lz = 2 * A if latent is None else latent
+    W1, b1, W2, b2, W3, b3 = unpack_wide(enc, S + A, hidden, 2 * Lz, 1)
+    D1, d1, D2, d2, D3, d3 = unpack_wide(dec, S + Lz, hidden, A, 1)
+    out = {}
+    for p, W, b in (("encoder_shared.0", W1, b1), ("encoder_shared.2", W2, b2), ("mean", W3[:, :, :Lz], b3[:, :Lz]),
+                    ("log_std", W3[:, :, Lz:], b3[:, Lz:]), ("decoder.0", D1, d1), ("decoder.2", D2, d2), ("decoder.4", D3, d3)):
+        out[p + ".weight"] = W[0].t().contiguous()
+        out[p + ".bias"] = b[0].contiguous()
+    return out
+
+
+def pack_bosa_vae_dynamics(sd, device):
+    """VAE_Dynamics_Ensemble.state_dict() (`<layer>.W [E, in, out]`, `<layer>.b [E, 1, out]`) -> (encoder blob, decoder blob)."""
+    g = lambda k: torch.as_tensor(sd[k], dtype=torch.float32)
+    fc = lambda p: (g(p + ".W"), g(p + ".b")[:, 0])
+    (W1, b1), (W2, b2) = fc("encoder_shared.0"), fc("encoder_shared.2")
+    (Wm, bm), (Ws, bs) = fc("mean"), fc("log_std")
+    enc = pack_wide(W1, b1, W2, b2, torch.cat([Wm, Ws], 2), torch.cat([bm, bs], 1), device)
+    (D1, d1), (D2, d2), (D3, d3) = fc("decoder.0"), fc("decoder.2"), fc("decoder.4")
+    return enc, pack_wide(D1, d1, D2, d2, D3, d3, device)
+
+
+def unpack_bosa_vae_dynamics(enc, dec, S, A, hidden, members, latent=None):
+    """Inverse of pack_bosa_vae_dynamics: a dict with VAE_Dynamics_Ensemble's keys and shapes."""
+    Lz = 2 * S if latent is None else latent
+    W1, b1, W2, b2, W3, b3 = unpack_wide(enc, 2 * S + A, hidden, 2 * Lz, members)
+    D1, d1, D2, d2, D3, d3 = unpack_wide(dec, S + A + Lz, hidden, S, members)
+    out = {}
+    for p, W, b in (("encoder_shared.0", W1, b1), ("encoder_shared.2", W2, b2), ("mean", W3[:, :, :Lz], b3[:, :Lz]),
+                    ("log_std", W3[:, :, Lz:], b3[:, Lz:]), ("decoder.0", D1, d1), ("decoder.2", D2, d2), ("decoder.4", D3, d3)):
+        out[p + ".W"] = W.contiguous()
+        out[p + ".b"] = b[:, None, :].contiguous()
+    return out

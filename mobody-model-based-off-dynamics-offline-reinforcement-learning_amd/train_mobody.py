@@ -178,7 +178,7 @@ def load_yaml(domain, policy, env_base):
     """config/<domain>/<policy>/<env>.yaml next to the script (train_mobody.py:410-411); a built-in copy of the mujoco
     hyper-parameters of `mobody` and `td3_bc` is used when no config tree is present.  With $MOBODY_CONFIG_ROOT set,
     $MOBODY_CONFIG_ROOT/<domain>/<policy>/<env>.yaml is looked up first (a reference checkout's config/ directory: the only
-    source of `dara`'s and `igdf`'s hyper-parameters); unset, nothing changes."""
+    source of `dara`'s, `igdf`'s and `bosa`'s hyper-parameters); unset, nothing changes."""
     root = os.environ.get("MOBODY_CONFIG_ROOT")
     if root:
         path = os.path.join(root, domain, policy, env_base + ".yaml")
@@ -424,6 +424,11 @@ def _run(args, rank, world, device):
 
     terminal_fn = get_termination_fn(task)
     policy = call_algo(args.policy, config, args.mode, device, terminal_fn=terminal_fn)
+    if hasattr(policy, "max_train_steps") and int(config["max_step"]) > policy.max_train_steps():
+        # BOSA: only the VAE stage is built; refuse the run now, not after vae_iteration // 2 steps of training
+        raise SystemExit(f"--policy {args.policy}: --max_step {config['max_step']} runs past the VAE stage (vae_iteration "
+                         f"{config['vae_iteration']}); the critic / actor stage is not built: the largest max_step is "
+                         f"{policy.max_train_steps()}")
     src_rb = utils.ReplayBuffer(state_dim, action_dim, device, rng=args.rng, seed=args.seed + 1)
     tar_rb = utils.ReplayBuffer(state_dim, action_dim, device, rng=args.rng, seed=args.seed + 2)
     if synthetic_mode:
@@ -490,15 +495,19 @@ def _run(args, rank, world, device):
     for t in range(int(config["max_step"])):
         policy.train(src_rb, tar_rb, config["batch_size"], writer, None)
         if (t + 1) % args.log_every == 0:
-            if world > 1:                             # losses() is this rank's share of the global means (kernels scale by
-                share = policy._loss[:3].clone()      # 1 / N_global): summed on log steps only
-                torch.distributed.all_reduce(share)
-                q, pi, bc = (float(x) for x in share.tolist())
+            if hasattr(policy, "log_line"):           # BOSA's VAE stage: its own losses under their own names
+                line = policy.log_line()
             else:
-                q, pi, bc = policy.losses()
+                if world > 1:                         # losses() is this rank's share of the global means (kernels scale by
+                    share = policy._loss[:3].clone()  # 1 / N_global): summed on log steps only
+                    torch.distributed.all_reduce(share)
+                    q, pi, bc = (float(x) for x in share.tolist())
+                else:
+                    q, pi, bc = policy.losses()
+                third = getattr(policy, "third_loss_name", "bc_loss")       # IQL reports its V loss there
+                line = f"q_loss {q:.4f} pi_loss {pi:.4f} {third} {bc:.4f}"
             dt = time.time() - start
-            third = getattr(policy, "third_loss_name", "bc_loss")       # IQL reports its V loss there
-            say(f"step {t + 1}: q_loss {q:.4f} pi_loss {pi:.4f} {third} {bc:.4f}  {args.log_every / dt:.1f} grad-steps/s")
+            say(f"step {t + 1}: {line}  {args.log_every / dt:.1f} grad-steps/s")
             start = time.time()
         if (t + 1) % config["eval_freq"] == 0 and rank == 0:           # rank 0 alone: no collective in this block
             # The reference's evaluation block (train_mobody.py:928-975) rolls the policy out in the simulators; of it, what
