@@ -1019,7 +1019,9 @@ int mobody_wide_adam(const MobodyWideAdam* a, void* stream);
  *                       encode, draw n latents per row (and member), decode the n B rows, w = sum log N(x; dec, sqrt(beta / 4)) +
  *                       sum log N(z; 0, 1) - sum log N(z; mean, std), ll = logsumexp_n(w) - log n with the maximum subtracted.
  *                       ll [members][B]; dynamics only: min_ll [B] = min over members, mask [B] = (min_ll > log_eps) as 0 / 1,
- *                       mask_mean [1] (each nullable).  w_out (nullable) [members][n][B].  eps: the reference's layouts, [B][n][Lz]
+ *                       mask_mean [1] (each nullable).  A NaN ll of any member makes the row's min_ll NaN and its mask 0, as
+ *                       torch.min and the comparison do (:585-590): the minimum does not skip a NaN member.  w_out (nullable)
+ *                       [members][n][B].  eps: the reference's layouts, [B][n][Lz]
  *                       (policy) / [n][members][B][Lz] (dynamics), or NULL: drawn at that linear index from stream
  *                       MOBODY_BOSA_STREAM_POLICY_LL / _DYNAMICS_LL.  Forward only: grad, m, v must be NULL; t, t_dev, lr and
  *                       loss_out are not read.  10 launches, 11 with mask_mean.

@@ -148,6 +148,9 @@ __global__ __launch_bounds__(256) void k_bosa_ll_sample(LlSampleArgs a) {
 }
 
 // Estimator, reducing half (:100-104 | :293-297, :585-590): one thread per row b; members in ascending order.
+// torch.min propagates NaN (dyna_ll.min(dim=0), :585) and NaN > log(eps) is False, so a row on which one member's ll is NaN has
+// min_ll = NaN and mask = 0; fminf would drop the NaN and let the row through on the other members (csrc/dynamics.hip's norms
+// follow the same rule).
 struct LlReduceArgs {
   const float *dec, *x;   // [E][n B][D], [B][D]
   float* pq;              // in: (pz, qzx); the w of each sample is kept in its first slot
@@ -161,6 +164,7 @@ __global__ __launch_bounds__(256) void k_bosa_ll_reduce(LlReduceArgs a) {
   if (b >= a.B) return;
   const float var2 = 2.f * (a.sd * a.sd), log_sd = logf(a.sd);
   float lo = INFINITY;
+  bool bad = false;
   for (int e = 0; e < a.E; ++e) {
     float mx = -INFINITY;
     for (int s = 0; s < a.n; ++s) {
@@ -180,8 +184,10 @@ __global__ __launch_bounds__(256) void k_bosa_ll_reduce(LlReduceArgs a) {
     for (int s = 0; s < a.n; ++s) sum += expf(a.pq[2 * ((long long)e * a.n * a.B + (long long)s * a.B + b)] - mx);
     const float ll = mx + logf(sum) - a.log_n;
     a.ll[(long long)e * a.B + b] = ll;
+    bad = bad || (ll != ll);
     lo = fminf(lo, ll);
   }
+  if (bad) lo = __builtin_nanf("");
   if (a.min_ll != nullptr) a.min_ll[b] = lo;
   if (a.mask != nullptr) a.mask[b] = lo > a.log_eps ? 1.f : 0.f;
 }

@@ -959,17 +959,21 @@ def ens_replay(dyn_blob, S, A, task_id, data, data_rows, row0, H, elites, seed, 
 
 
 # ---- wide MLPs (csrc/wide.hip): BOSA's VAE nets, exact fp32 whatever MOBODY_MFMA says ------------------------------------
-def wide_mlp3_forward(blob, L, sources, out_mode="raw", max_action=1.0, save=False, precision=0):
+def wide_mlp3_forward(blob, L, sources, out_mode="raw", max_action=1.0, save=False, precision=0, source_rows=None):
     """The wide net `blob` (layout L = _lib.wide_layout(...)) on x = the `sources` (up to three) side by side.  A 2-D source
-    [rows, w] is read by every member, a 3-D one [members, rows, w] holds one copy per member.  Returns out
-    [members, rows, out_dim], or with save=True (out, x, h1, h2): the tensors mobody_wide_mlp3_backward reads, x
-    [1 or members, rows, Kp1] and h1, h2 [members, rows, Hp]."""
+    [rows, w] is read by every member, a 3-D one [members, rows, w] holds one copy per member.  source_rows: one entry per
+    source, None / 0 for a full source or its period p (src_rows): the source is then passed as [p, w] / [members, p, w] and row
+    r of x reads its row r % p; at least one source is full and gives `rows`.  Returns out [members, rows, out_dim], or with
+    save=True (out, x, h1, h2): the tensors mobody_wide_mlp3_backward reads, x [1 or members, rows, Kp1] and h1, h2
+    [members, rows, Hp]."""
     srcs = [_f32(s) for s in sources]
     assert 1 <= len(srcs) <= 3
-    rows, dev, E = srcs[0].shape[-2], blob.device, L.members
+    periods = [int(p or 0) for p in (source_rows if source_rows is not None else [0] * len(srcs))]
+    assert len(periods) == len(srcs) and not all(periods), periods
+    rows, dev, E = [s.shape[-2] for s, p in zip(srcs, periods) if not p][0], blob.device, L.members
     shared = all(s.dim() == 2 for s in srcs)
-    for s in srcs:
-        assert s.shape[-2] == rows and (s.dim() == 2 or (s.dim() == 3 and s.shape[0] == E)), tuple(s.shape)
+    for s, p in zip(srcs, periods):                  # a period beyond `rows` is the entry point's to refuse
+        assert s.shape[-2] == (p or rows) and (s.dim() == 2 or (s.dim() == 3 and s.shape[0] == E)), tuple(s.shape)
     new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
     out = new(E, rows, L.out_dim)
     x, h1, h2 = new(1 if shared else E, rows, L.Kp1), new(E, rows, L.Hp), new(E, rows, L.Hp)
@@ -979,7 +983,8 @@ def wide_mlp3_forward(blob, L, sources, out_mode="raw", max_action=1.0, save=Fal
     for i, s in enumerate(srcs):
         setattr(a, "src%d" % i, ptr(s))
         setattr(a, "src_width%d" % i, s.shape[-1])
-        setattr(a, "src_member_stride%d" % i, 0 if s.dim() == 2 else rows * s.shape[-1])
+        setattr(a, "src_member_stride%d" % i, 0 if s.dim() == 2 else s.shape[-2] * s.shape[-1])
+        setattr(a, "src_rows%d" % i, periods[i])
     check(load().mobody_wide_mlp3_forward(C.byref(a), cur_stream()), "mobody_wide_mlp3_forward")
     return (out, x, h1, h2) if save else out
 

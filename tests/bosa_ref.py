@@ -110,6 +110,56 @@ def loglik(enc, dec, kind, s, a, s2, eps, beta, max_action=1.0):
     return (mx + np.log(np.exp(w - mx).sum(1, keepdims=True)))[:, 0] - np.log(n), w
 
 
+def batch(seed, S, A, B):
+    """Seeded fp32 (state, action in (-1, 1), next_state) rows."""
+    rng = np.random.default_rng(seed)
+    f = lambda *s: rng.standard_normal(s).astype(np.float32)
+    return f(B, S), np.tanh(f(B, A)), f(B, S)
+
+
+def estimator_case(kind, S, A, E, B, n):
+    """The estimator tests' inputs: (s, a, s2, eps in the reference's layout, far).  Row `far` has its target far from any
+    decoding, so every w of it lies below -1e4."""
+    s, a, s2 = batch(9, S, A, B)
+    far = B - 1
+    if kind == "policy":
+        a[far] = 60.0
+    else:
+        s2[far] = 60.0
+    Lz = dims(kind, S, A)[1]
+    eps = np.random.default_rng(n).standard_normal((B, n, Lz) if kind == "policy" else (n, E, B, Lz)).astype(np.float32)
+    return s, a, s2, eps, far
+
+
+def estimator_tolerance(ll64, w64):
+    """rtol 1e-5 with atol 1e-5 x max_s |w_s| of the row, [E, B]."""
+    return 1e-5 * np.abs(ll64) + 1e-5 * np.abs(w64).max(1)
+
+
+def mask_threshold(ll64, tol):
+    """A log_eps for the mask test: the middle of the widest gap between neighbouring fp64 minima over members around their
+    median.  Returns (threshold, gap, the larger tolerance of the two rows on either side of the gap); the test is meaningful
+    only where the gap exceeds ten times that tolerance."""
+    order = np.argsort(ll64.min(0))
+    lo64 = ll64.min(0)[order]
+    mid = len(lo64) // 2
+    cand = range(max(mid - 3, 0), min(mid + 3, len(lo64) - 1))
+    j = max(cand, key=lambda i: lo64[i + 1] - lo64[i])
+    return 0.5 * (lo64[j] + lo64[j + 1]), lo64[j + 1] - lo64[j], tol[:, order[j:j + 2]].max()
+
+
+# shapes whose B crosses the estimator's workgroup boundaries (k_bosa_ll_reduce: one thread per row, 256 per workgroup;
+# k_bosa_mask_mean: a 256-strided loop): name -> ((S, A, hidden, members, B), num_samples)
+LL_BOUNDARY_CASES = {"tiny-b257": ((3, 1, 8, 1, 257), 64), "small-b513": ((17, 6, 72, 2, 513), 4), "odd-b300": ((17, 6, 72, 5, 300), 2)}
+# the VAE step (dynamics) with more than 256 per-workgroup partial sums of both losses: 5 x 300 x 90 latent elements = 528
+# partial sums, 5 x 300 x 45 output elements = 264 (k_bosa_finish's strided loops take a second trip past 256)
+VAE_BOUNDARY_SHAPE = (45, 24, 72, 5, 300)
+# its parameter seed: of 135 000 pre-clamp log_std values some fall within 1e-5 of -4 at most seeds, where the kernel's fp32 gate
+# and the restatement's could differ; at this one the nearest is 2.2e-5 away in the step whose gradients are compared (asserted in
+# tests/test_bosa_ref.py)
+VAE_BOUNDARY_SEED = 22
+
+
 
 NET_KEYS = ("encoder_shared.0", "encoder_shared.2", "mean", "log_std", "decoder.0", "decoder.2", "decoder.4")
 

@@ -92,6 +92,81 @@ def test_estimator_algebra(kind):
     assert np.isclose(w1[0, 0, 2], ln(x, u, np.sqrt(0.125)) + ln(z, 0.0, 1.0) - ln(z, mean[0, 2], std[0, 2]), rtol=1e-12)
 
 
+# ---- the shapes that cross workgroup boundaries (tests/test_hip_bosa.py): what the GPU cases can and would catch -------------------
+@pytest.mark.parametrize("name", list(BR.LL_BOUNDARY_CASES))
+def test_mask_threshold_has_a_usable_gap_at_the_boundary_shapes(name):
+    """The GPU test's precondition, from the restatement alone: next to the median of the fp64 minima there is a gap of more than
+    ten tolerances, and the threshold in its middle splits the rows -- so a change of seeds cannot turn the mask check vacuous."""
+    (S, A, H, E, B), n = BR.LL_BOUNDARY_CASES[name]
+    assert B > 256 and B % 256 != 0
+    enc, dec = BR.vae_params(21, "dynamics", S, A, H, E)
+    s, a, s2, eps, far = BR.estimator_case("dynamics", S, A, E, B, n)
+    ll64, w64 = BR.loglik(enc, dec, "dynamics", s, a, s2, eps, 0.5, 1.0)
+    assert (w64[:, :, far] < -1e4).all() and np.isfinite(ll64).all()
+    thr, gap, row_tol = BR.mask_threshold(ll64, BR.estimator_tolerance(ll64, w64))
+    print("%s: gap %.3f / ten tolerances %.4f" % (name, gap, 10 * row_tol))
+    assert gap > 10 * row_tol
+    want = ll64.min(0) > thr
+    assert 0 < want.sum() < B and not want[far]
+    if B > 257:                                                                   # rows of the later workgroups on both sides
+        assert want[256:].any() and not want[256:].all()
+
+
+def test_unwritten_rows_past_one_workgroup_fail_the_finiteness_check():
+    """An estimator that leaves rows 256.. of its NaN-prefilled outputs alone (one workgroup's worth written) is caught."""
+    (S, A, H, E, B), n = BR.LL_BOUNDARY_CASES["odd-b300"]
+    enc, dec = BR.vae_params(21, "dynamics", S, A, H, E)
+    s, a, s2, eps, far = BR.estimator_case("dynamics", S, A, E, B, n)
+    ll64 = BR.loglik(enc, dec, "dynamics", s, a, s2, eps, 0.5, 1.0)[0]
+    got = np.full((E, B), np.nan, np.float32)
+    got[:, :256] = ll64[:, :256]
+    assert np.isfinite(got[:, :256]).all() and not np.isfinite(got).all()
+    mask = np.full(B, np.nan, np.float32)                                         # ... and a mask mean over 256 rows only is not B's
+    mask[:256] = 1.0
+    assert mask[:256].sum() / B != 1.0 and not np.isfinite(mask).all()
+
+
+def test_a_loss_from_the_first_256_partial_sums_misses_the_tolerance():
+    """k_bosa_finish adds the per-workgroup partial sums (256 elements each) in 256-strided loops.  At the boundary shape the KL
+    term has 528 partial sums and the reconstruction 264: a loss from the first 256 alone is off by far more than rtol 1e-5."""
+    S, A, H, E, B = BR.VAE_BOUNDARY_SHAPE
+    enc, dec = (WR.f64(p) for p in BR.vae_params(BR.VAE_BOUNDARY_SEED, "dynamics", S, A, H, E))
+    s, a, s2 = BR.batch(101, S, A, B)
+    eps = np.random.default_rng(4).standard_normal((E, B, 2 * S)).astype(np.float32)
+    (rec, kl, tot), _, ex = BR.vae_step(enc, dec, "dynamics", s, a, s2, eps, 0.5, 1.0)
+    kl_terms = (1.0 + np.log(ex["std"] ** 2) - ex["mean"] ** 2 - ex["std"] ** 2).reshape(-1)           # element (e B + b) Lz + l
+    rec_terms = ((ex["u"] - np.asarray(s2, np.float64)[None]) ** 2).reshape(-1)                          # element (e B + b) D + d
+    partial = lambda t: np.add.reduceat(t, np.arange(0, t.size, 256))
+    pk, pr = partial(kl_terms), partial(rec_terms)
+    assert (pk.size, pr.size) == (528, 264) and kl_terms.size == 135000 and rec_terms.size == 67500
+    assert np.isclose(-0.5 * pk.sum() / kl_terms.size, kl, rtol=1e-12) and np.isclose(pr.sum() / rec_terms.size, rec, rtol=1e-12)
+    kl_cut, rec_cut = -0.5 * pk[:256].sum() / kl_terms.size, pr[:256].sum() / rec_terms.size
+    for cut, full in ((kl_cut, kl), (rec_cut, rec), (rec_cut + 0.5 * kl, tot), (rec + 0.5 * kl_cut, tot)):
+        assert abs(cut - full) > 100 * 1e-5 * abs(full)
+    # both clamp branches at this shape, in comparable shares, and nothing within fp32 rounding of a clamp end
+    pre = ex["pre"]
+    inside, below = ((pre >= -4) & (pre <= 15)).mean(), (pre < -4).mean()
+    assert inside > 0.25 and below > 0.25 and (np.abs(pre + 4) > 1e-5).all() and (np.abs(pre - 15) > 1e-5).all()
+
+
+def test_a_nan_member_poisons_the_minimum_and_masks_the_row():
+    """The reference's rule (torch.min propagates NaN, NaN > log(eps) is False; NumPy's min and comparison do the same): a row on
+    which one member's likelihood is NaN has min_ll = NaN and mask = 0, whatever the other members give."""
+    S, A, H, E, B = SHAPES["small"]
+    enc, dec = BR.vae_params(21, "dynamics", S, A, H, E)
+    s, a, s2 = BR.batch(9, S, A, B)
+    eps = np.random.default_rng(1).standard_normal((4, E, B, 2 * S)).astype(np.float32)
+    eps[:, 1, [0, 5, B - 1], 3] = np.nan
+    with np.errstate(invalid="ignore"):
+        ll = BR.loglik(enc, dec, "dynamics", s, a, s2, eps, 0.5, 1.0)[0]
+        lo = ll.min(0)
+        mask = lo > -1e30
+    bad = np.zeros(B, bool)
+    bad[[0, 5, B - 1]] = True
+    assert np.isnan(ll[1, bad]).all() and np.isfinite(ll[0]).all() and np.isfinite(ll[1, ~bad]).all()
+    assert np.isnan(lo[bad]).all() and not mask[bad].any() and mask[~bad].all() and mask.mean() == (B - 3) / B
+
+
 @pytest.fixture(scope="module")
 def lib():
     import __graft_entry__ as ge

@@ -6,6 +6,11 @@ units in the last place (4 u), so z = mean + std eps is within 8 u (|mean| + |st
 four such factors: 16 u x the sum of the terms' magnitudes; a blocked gradient is exactly 0.  The estimator: ll rtol 1e-5 with atol
 1e-5 x max_s |w_s| of the row; min over members exact given ll; the mask threshold sits in the middle of the widest gap between
 neighbouring fp64 min-ll values around their median, and that gap must exceed ten times the tolerance there.
+
+Every workspace mobody_bosa_workspace sizes is followed by NaN sentinel floats whose bits are checked after each call, and is itself
+NaN-filled, so a read before the first write shows.  bosa_ref.LL_BOUNDARY_CASES / VAE_BOUNDARY_SHAPE cross the 256-row and
+256-partial-sum boundaries of the row-wise kernels (tests/test_bosa_ref.py shows that they would catch a fault there).  A NaN
+likelihood of one member makes the row's min_ll NaN and its mask 0, as torch.min and the comparison do in the reference.
 """
 import numpy as np
 import pytest
@@ -18,6 +23,7 @@ from test_hip_train import params_close
 pytestmark = pytest.mark.gpu
 U = WR.U
 NAN = float("nan")
+GUARD, NAN_BITS = 64, 0x7FC00000
 
 # name -> (S, A, hidden, members, batch rows): the fixture variants' shapes, and the reference's real width
 SHAPES = {"small": (17, 6, 72, 2, 16), "odd": (17, 6, 72, 5, 66), "tiny": (3, 1, 8, 1, 4), "pen": (45, 24, 72, 2, 8),
@@ -31,10 +37,19 @@ def dev():
     return torch.device("cuda:0")
 
 
-def batch(seed, S, A, B):
-    rng = np.random.default_rng(seed)
-    f = lambda *s: rng.standard_normal(s).astype(np.float32)
-    return f(B, S), np.tanh(f(B, A)), f(B, S)
+batch = BR.batch
+
+
+def guarded_workspace(blk, dev):
+    """(workspace, the whole buffer): mobody_bosa_workspace floats, NaN-filled, and GUARD NaN sentinel floats behind them."""
+    from mobody_amd import ops
+    n = ops.bosa_workspace(blk, dev).numel()
+    buf = torch.full((n + GUARD,), NAN, device=dev)
+    return buf[:n], buf
+
+
+def guard_intact(buf):
+    return bool((buf[-GUARD:].view(torch.int32) == NAN_BITS).all())
 
 
 class Vae:
@@ -53,7 +68,7 @@ class Vae:
         self.loss = torch.full((3,), NAN, device=dev)
         self.Lz = BR.dims(kind, self.S, self.A)[1]
         self.ns = num_samples
-        self.ws = ops.bosa_workspace(self.block(), dev)
+        self.ws, self.wsbuf = guarded_workspace(self.block(), dev)
         self.keep = []
 
     def block(self, **ff):
@@ -72,6 +87,7 @@ class Vae:
         ops.bosa_vae(self.block(grad=self.grad, loss_out=self.loss, workspace=self.ws, eps=e, **self.dev_batch(b), **opt, **ff))
         torch.cuda.synchronize()
         assert torch.isnan(self.gbuf[-1])
+        assert guard_intact(self.wsbuf), "mobody_bosa_vae wrote behind its workspace"
         return self.loss.cpu().numpy()
 
     def grads(self):
@@ -138,10 +154,20 @@ def test_reparam_kernel_at_the_clamp_edges(dev):
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_vae_step_vs_fp64(dev, kind, name):
     """Losses and every gradient of one step; then three fused steps against the fp64 trajectory; explicit noise."""
-    shape = SHAPES[name]
+    vae_step_vs_fp64(dev, kind, name, SHAPES[name], 1.0 if name != "pen" else 1.5)
+
+
+def test_vae_step_vs_fp64_past_256_partial_sums(dev):
+    """The dynamics VAE at 5 x 300 rows of the pen shape: 528 partial sums of the KL term and 264 of the reconstruction, so both of
+    k_bosa_finish's 256-strided loops take a second trip, and every row-wise kernel runs hundreds of workgroups."""
+    S, A, H, E, B = BR.VAE_BOUNDARY_SHAPE
+    assert -(-E * B * 2 * S // 256) == 528 and -(-E * B * S // 256) == 264
+    vae_step_vs_fp64(dev, "dynamics", "boundary", BR.VAE_BOUNDARY_SHAPE, 1.0, seed=BR.VAE_BOUNDARY_SEED)
+
+
+def vae_step_vs_fp64(dev, kind, name, shape, ma, seed=21):
     S, A, H, E, B = shape
-    ma = 1.0 if name != "pen" else 1.5
-    v = Vae(kind, shape, dev, beta=0.5, max_action=ma)
+    v = Vae(kind, shape, dev, seed=seed, beta=0.5, max_action=ma)
     lr, rng = 1e-3, np.random.default_rng(4)
     enc64, dec64 = WR.f64(v.enc), WR.f64(v.dec)
     m64 = [{k: 0.0 for k in WR.KEYS} for _ in range(2)]
@@ -205,7 +231,7 @@ def test_vae_step_is_bit_identical_and_device_noise_matches_the_generator(dev, k
 def run_ll(v, b, eps, n, log_eps=0.0, far_row=None):
     from mobody_amd import ops
     v.ns = n
-    v.ws = ops.bosa_workspace(v.block(), v.dev)
+    v.ws, v.wsbuf = guarded_workspace(v.block(), v.dev)
     new = lambda *s: torch.full(s, NAN, device=v.dev)
     out = dict(ll=new(v.E, v.B), w_out=new(v.E, n, v.B))
     if v.kind == "dynamics":
@@ -213,27 +239,25 @@ def run_ll(v, b, eps, n, log_eps=0.0, far_row=None):
     e = torch.from_numpy(eps).to(v.dev) if eps is not None else None
     ops.bosa_loglik(v.block(workspace=v.ws, eps=e, log_eps=float(log_eps), **v.dev_batch(b), **out))
     torch.cuda.synchronize()
+    assert guard_intact(v.wsbuf), "mobody_bosa_loglik wrote behind its workspace"
     return {k: t.cpu().numpy() for k, t in out.items()}
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name,n", [("small", 1), ("small", 4), ("odd", 4), ("tiny", 64), ("pen", 4), ("real", 1), ("odd", 64)])
+@pytest.mark.parametrize("name,n", [("small", 1), ("small", 4), ("odd", 4), ("tiny", 64), ("pen", 4), ("real", 1), ("odd", 64)] +
+                         [(k, c[1]) for k, c in BR.LL_BOUNDARY_CASES.items()])
 def test_estimator_vs_fp64(dev, kind, name, n):
-    shape = SHAPES[name]
+    shape = SHAPES[name] if name in SHAPES else BR.LL_BOUNDARY_CASES[name][0]
     S, A, H, E, B = shape
     v = Vae(kind, shape, dev, beta=0.5, max_action=1.0)
-    s, a, s2 = batch(9, S, A, B)
-    far = B - 1                                              # one row whose w all lie below -1e4: the target far from any decoding
-    if kind == "policy":
-        a[far] = 60.0
-    else:
-        s2[far] = 60.0
-    rng = np.random.default_rng(n)
-    eps = rng.standard_normal((B, n, v.Lz) if kind == "policy" else (n, v.E, B, v.Lz)).astype(np.float32)
+    # `far`: one row whose w all lie below -1e4, the target far from any decoding
+    s, a, s2, eps, far = BR.estimator_case(kind, S, A, v.E, B, n)
     ll64, w64 = BR.loglik(v.enc, v.dec, kind, s, a, s2, eps, 0.5, 1.0)
-    got = run_ll(v, (s, a, s2), eps, n)
+    got = run_ll(v, (s, a, s2), eps, n)                     # every output pre-filled with NaN
     assert (w64[:, :, far] < -1e4).all() and np.isfinite(got["ll"]).all()
-    tol = 1e-5 * np.abs(ll64) + 1e-5 * np.abs(w64).max(1)
+    for k, t in got.items():
+        assert np.isfinite(t).all(), "%s: %d entries left unwritten or not finite" % (k, (~np.isfinite(t)).sum())
+    tol = BR.estimator_tolerance(ll64, w64)
     print("ll: worst error / tolerance %.3f" % (np.abs(got["ll"] - ll64) / tol).max())
     assert (np.abs(got["ll"] - ll64) <= tol).all()
     assert (np.abs(got["w_out"] - w64) <= 1e-5 * np.abs(w64) + 1e-5 * np.abs(w64).max(1, keepdims=True)).all()
@@ -241,18 +265,50 @@ def test_estimator_vs_fp64(dev, kind, name, n):
         return
     assert np.array_equal(got["min_ll"], got["ll"].min(0)), "min over members is not exact"
     # threshold in the widest gap between neighbouring fp64 minima around the median
-    order = np.argsort(ll64.min(0))
-    lo64 = ll64.min(0)[order]
-    mid = len(lo64) // 2
-    cand = range(max(mid - 3, 0), min(mid + 3, len(lo64) - 1))
-    j = max(cand, key=lambda i: lo64[i + 1] - lo64[i])
-    thr = 0.5 * (lo64[j] + lo64[j + 1])
-    row_tol = tol[:, order[j:j + 2]].max()                      # of the two rows on either side of the gap
-    assert lo64[j + 1] - lo64[j] > 10 * row_tol, "no usable gap for the mask threshold"
+    thr, gap, row_tol = BR.mask_threshold(ll64, tol)            # row_tol: of the two rows on either side of the gap
+    assert gap > 10 * row_tol, "no usable gap for the mask threshold"
     got = run_ll(v, (s, a, s2), eps, n, log_eps=thr)
     want = (ll64.min(0) > thr).astype(np.float32)
     assert 0 < want.sum() < B and np.array_equal(got["mask"], want)
+    assert np.array_equal(got["min_ll"], got["ll"].min(0)) and np.isfinite(got["mask_mean"]).all()
     assert got["mask_mean"][0] == np.float32(want.sum() / np.float32(B))
+
+
+@pytest.mark.parametrize("members", [2, 1])
+def test_nan_member_poisons_min_ll_and_masks_the_row(dev, members):
+    """torch.min propagates NaN and NaN > log(eps) is False (bosa.py:585-590), so a row on which one member's likelihood is NaN
+    has min_ll = NaN and mask = 0 in the reference; fminf would drop the NaN and let the row through on the other members (with one
+    member: min_ll = +Inf, mask = 1).  NaN noise of one latent column makes that member's ll NaN on three rows; every other
+    entry keeps the bits of the clean run.  Against the kernel before the flag in k_bosa_ll_reduce this test failed (min_ll
+    finite or +Inf and mask 1 on the planted rows, mask_mean 1)."""
+    S, A, H, _, B = SHAPES["small"]
+    n, m = 4, members - 1                                    # the planted member: 1 of 2, or the only one
+    v = Vae("dynamics", (S, A, H, members, B), dev, beta=0.5, max_action=1.0)
+    b = batch(9, S, A, B)
+    clean = np.random.default_rng(1).standard_normal((n, members, B, v.Lz)).astype(np.float32)
+    rows = [0, 5, B - 1]
+    bad = np.zeros(B, bool)
+    bad[rows] = True
+    eps = clean.copy()
+    eps[:, m, rows, 3] = np.nan
+    log_eps = -1e30                                          # every finite row passes
+    ref = run_ll(v, b, clean, n, log_eps=log_eps)
+    got = run_ll(v, b, eps, n, log_eps=log_eps)
+    assert np.isfinite(ref["ll"]).all() and (ref["mask"] == 1).all() and ref["mask_mean"][0] == 1
+    # what the restatement's semantics give on the planted rows (NumPy's min propagates NaN as torch's does)
+    with np.errstate(invalid="ignore"):
+        ll64 = BR.loglik(v.enc, v.dec, "dynamics", *b, eps, 0.5, 1.0)[0]
+        assert np.isnan(ll64[m, bad]).all() and np.isnan(ll64.min(0)[bad]).all() and not (ll64.min(0)[bad] > log_eps).any()
+    assert np.isnan(got["ll"][m, bad]).all(), got["ll"][m, bad]
+    assert np.isnan(got["min_ll"][bad]).all(), got["min_ll"][bad]
+    assert (got["mask"][bad] == 0).all(), got["mask"][bad]
+    # everything else: the clean run's bits
+    touched = np.zeros((members, B), bool)
+    touched[m, bad] = True
+    i32 = lambda x: np.ascontiguousarray(x).view(np.int32)
+    assert np.array_equal(i32(got["ll"][~touched]), i32(ref["ll"][~touched]))
+    assert np.array_equal(i32(got["min_ll"][~bad]), i32(ref["min_ll"][~bad])) and np.array_equal(i32(got["mask"][~bad]), i32(ref["mask"][~bad]))
+    assert (got["mask"][~bad] == 1).all() and got["mask_mean"][0] == np.float32(B - 3) / np.float32(B)
 
 
 def test_estimator_device_noise_and_refusals(dev):

@@ -195,6 +195,48 @@ def test_dynamics_vae_state_dict_round_trip(lib, S, A, H, E):
     assert enc[e * Le.member_floats + Le.w3 + 4 * Le.Np3 + 2 * S + 1] == sd["log_std.W"][e, 4, 1]
 
 
+CORNER_IDS = ["h%d-r%d-e%d-%dx%d" % (c[0], c[1], c[2], c[3][0], c[3][1]) for c in WR.CORNER_CASES]
+
+
+@pytest.mark.parametrize("case", WR.CORNER_CASES, ids=CORNER_IDS)
+def test_backward_tolerance_is_reachable_in_fp32_at_the_corner_shapes(case):
+    """The precondition of tests/test_hip_wide.py's backward tolerance (rtol 1e-5, atol 1e-5 x the tensor's largest entry), from
+    the restatement alone: the same expressions evaluated in float32 NumPy stay within HALF of it of the fp64 ones, on the inputs
+    the GPU test uses (its seeds; the activations are the fp64 forward's, rounded, in place of the kernel's saves).  So a correct
+    fp32 kernel passes, and the tolerance is not so loose that it is met by accident of the shape: single-entry tensors (dx at
+    in_dim = 1 with one row, b3 at out_dim = 1) are compared relative to themselves."""
+    hidden, rows, E, (in_dim, out_dim), mode, widths, per_member = case
+    p, srcs, x = WR.case_inputs(case)
+    out, h1, h2 = WR.forward(p, x, mode, 1.7)
+    assert (h1 > 0).any() and (h2 > 0).any()
+    x32, h1, h2 = x.astype(np.float32), h1.astype(np.float32), h2.astype(np.float32)
+    dz3 = np.random.default_rng(5).standard_normal((E, rows, out_dim)).astype(np.float32)
+    g64, g32 = WR.backward(p, x32, h1, h2, dz3), WR.backward(p, x32, h1, h2, dz3, dtype=np.float32)
+    for k in WR.KEYS + ("dx",):
+        assert g32[k].dtype == np.float32 and g64[k].dtype == np.float64
+        tol = 1e-5 * np.abs(g64[k]).max() + 1e-5 * np.abs(g64[k])
+        ratio = (np.abs(g32[k] - g64[k]) / tol).max()
+        print("%s: fp32 evaluation error / tolerance %.3f" % (k, ratio))
+        assert ratio <= 0.5, (k, ratio)
+
+
+def test_corner_cases_cover_the_layout_domain(lib):
+    """Every minimum and maximum of mobody_wide_layout's ranges, a shape with no padding in any dimension, every dimension both
+    with and without padding, and row counts of exactly one 16-row chunk and one and two 64-row tiles."""
+    from mobody_amd import _lib
+    cs = WR.CORNER_CASES
+    for idx, lo, hi in ((0, 8, 1024), (2, 1, 8)):
+        assert {lo, hi} <= {c[idx] for c in cs}
+    assert {1, 256} <= {c[3][0] for c in cs} and {1, 65, 256} <= {c[3][1] for c in cs}
+    assert {1, 16, 64, 128} <= {c[1] for c in cs}
+    pads = []
+    for c in cs:
+        L = _lib.wide_layout(c[3][0], c[0], c[3][1], c[2])
+        pads.append((L.Kp1 - L.in_dim, L.Hp - L.hidden, L.Np3 - L.out_dim))
+        assert sum(c[5]) == c[3][0]
+    assert (0, 0, 0) in pads and all(any(p[d] for p in pads) and any(not p[d] for p in pads) for d in range(3))
+
+
 def test_restatement_gradients_match_finite_differences():
     """The fp64 restatement's backward against central differences of its own forward (loss = sum(out * c))."""
     in_dim, hidden, out_dim, E, rows = 5, 8, 3, 2, 4
