@@ -22,13 +22,11 @@ Where the reference is odd: `save` writes six files and leaves out V
 writes them too (as IQL's), `load` reads the six and the three extras when present; its `alpha` property reads a `log_alpha` that
 does not exist and is left out.  Not built: data-parallel DARA (refused in the constructor, before any collective).
 """
-import os
-
 import torch
 
 from ... import ops
 from .iql import IQL
-from .mobody import REFRESH_EVERY, _Adam, _Classifier, _PackedNet
+from .mobody import _Adam, _Classifier, _PackedNet, _PairedAdam, refuse_data_parallel, refuse_missing_keys
 
 _KEYS = ("lam", "temp", "max_step", "gaussian_noise_std", "dara_eta")
 NOISE_SEED = 31             # seed offset of the classifier-noise streams (as MOBODY.update_classifier)
@@ -58,58 +56,16 @@ class _DaraClassifier(_Classifier):
         return torch.softmax(zs[0], 1), torch.softmax(za[0], 1)
 
 
-class _ClassifierAdam(object):
-    """torch.optim.Adam(classifier.parameters()) (dara.py:192): ONE optimizer over both heads, so one step count; state_dict in
-    torch's format with its 12 parameters in `Classifier.parameters()` order, sa_classifier first."""
-
-    def __init__(self, classifier):
-        self.sa, self.sas = classifier.opt_sa, classifier.opt_sas
-
-    @property
-    def t(self):
-        return self.sa.t
-
-    @t.setter
-    def t(self, value):
-        self.sa.t = self.sas.t = int(value)
-
-    @property
-    def lr(self):
-        return self.sa.lr
-
-    def state_dict(self):
-        a, b = self.sa.state_dict(), self.sas.state_dict()
-        state = dict(a["state"])
-        state.update({k + 6: v for k, v in b["state"].items()})
-        return dict(state=state, param_groups=[dict(a["param_groups"][0], params=list(range(12)))])
-
-    def load_state_dict(self, sd):
-        st, group = sd["state"], sd["param_groups"][0]
-        if st and sorted(st) != list(range(12)):
-            raise ValueError(f"classifier_optimizer: expected the state of 12 parameters, got {sorted(st)}")
-        half = lambda lo: dict(state={k - lo: st[k] for k in range(lo, lo + 6)} if st else {}, param_groups=[dict(group, params=list(range(6)))])
-        self.sa.load_state_dict(half(0))
-        self.sas.load_state_dict(half(6))
-        if self.sa.t != self.sas.t:
-            raise ValueError(f"classifier_optimizer: the two heads' step counts differ ({self.sa.t}, {self.sas.t}); one optimizer steps both")
-
-
 class DARA(IQL):
     def __init__(self, config, device, target_entropy=None):
-        # The reference reads these keys without defaults.  A config without them -- a MOBODY or an IQL config handed to 'dara' -- is
-        # not a DARA run: nothing is invented for them, and the refusal has the type the registry gave for 'dara' before this class
-        # existed.  It comes before every other check.
+        # The reference reads these keys without defaults: a MOBODY or an IQL config handed to 'dara' is not a DARA run.  This
+        # refusal comes before every other check.
         missing = [k for k in _KEYS if k not in config]
         if not missing and config["dara_eta"] == 0 and "eta" not in config:
             missing = ["eta"]
-        if missing:
-            raise NotImplementedError(f"DARA is built from a DARA config only: config lacks {missing} (the reference's "
-                                      "config/mujoco/dara/*.yaml values are lam 0.7, temp 3.0, max_step 500000, gaussian_noise_std "
-                                      "1.0, eta 0.1, and --dara_eta from the command line; no defaults are substituted here)")
-        d = torch.distributed
-        if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
-            raise NotImplementedError("data-parallel DARA is not built: run 'dara' on one GPU (only 'mobody' has the "
-                                      "exchange protocol of mobody_amd.dp wired through the CLI)")
+        refuse_missing_keys("DARA", missing, "config/mujoco/dara/*.yaml values are lam 0.7, temp 3.0, max_step 500000, "
+                            "gaussian_noise_std 1.0, eta 0.1, and --dara_eta from the command line")
+        refuse_data_parallel("DARA", "dara")
         if not float(config["gaussian_noise_std"]) >= 0.0:
             raise ValueError(f"config['gaussian_noise_std'] = {config['gaussian_noise_std']} < 0")
         if 2 * int(config["state_dim"]) + int(config["action_dim"]) > 256:
@@ -117,7 +73,8 @@ class DARA(IQL):
         IQL.__init__(self, config, device, target_entropy)
         self.eta = float(config["dara_eta"] if config["dara_eta"] != 0 else config["eta"])      # dara.py:164-167
         self.classifier = _DaraClassifier(self.S, self.A, self.device, config["gaussian_noise_std"], config["actor_lr"], self.precision)
-        self.classifier_optimizer = _ClassifierAdam(self.classifier)
+        # torch.optim.Adam(classifier.parameters()) (dara.py:192), in `Classifier.parameters()` order: sa_classifier first
+        self.classifier_optimizer = _PairedAdam("classifier_optimizer", "heads", sa=self.classifier.opt_sa, sas=self.classifier.opt_sas)
         self._ctr = torch.zeros(5, dtype=torch.int64, device=self.device)      # [rng call, critic t, actor t, V t, classifier t]
         self._cbatch = None                                                    # the classifier's own batch (dara.py:203-204)
         self._cls_loss = torch.zeros(2, dtype=torch.float32, device=self.device)   # (loss_sa, loss_sas) of the last step
@@ -127,13 +84,8 @@ class DARA(IQL):
     def _heads(self):
         return (self.classifier.sa_classifier, self.classifier.sas_classifier)
 
-    def _health_check(self):
-        IQL._health_check(self)
-        for n in self._heads():                               # 'fallback' moved the nets to bf16x3: the heads follow
-            if n.precision != self.precision:
-                n.precision = self.precision
-                ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
-                n.version += 1
+    def _extra_nets(self):
+        return IQL._extra_nets(self) + self._heads()
 
     # ------------------------------------------------------------------ training
     def _dims(self, N, Nt, Ng, Ntg):
@@ -144,11 +96,11 @@ class DARA(IQL):
             self._ws_key = (N, Nt)
         return ops.train_dims(self.S, self.A, N, Nt, Ng, Ntg), ops.hyper(self.config)
 
-    def _batches(self, N):
-        if self._batch_key != (N,):
-            mk = lambda: tuple(torch.empty(N, w, device=self.device) for w in (self.S, self.A, self.S, 1, 1))
-            self._batch, self._cbatch = mk(), mk()
-            self._batch_key = (N,)
+    def _buffers(self, bs, N, alloc=False):
+        fit = IQL._buffers(self, bs, N, alloc)
+        if alloc and not fit:
+            self._cbatch = self._rows5(N)
+        return fit
 
     def _classifier_step(self, cb, N, dev=False, noise=None):
         """mobody_dara_classifier on the rows `cb`.  dev: the captured step -- the step count and the noise call id are device
@@ -179,7 +131,7 @@ class DARA(IQL):
         (unit normals [N, 2S+A], [N, S+A]) let a caller supply the batch and the noise; `classifier_noise_fn` (n_rows -> that pair)
         is asked otherwise, and without it the device generator draws."""
         N = 2 * int(batch_size)
-        self._batches(N)
+        self._buffers(int(batch_size), N, alloc=True)
         cb = self._cbatch
         if rows is None:
             self._gather([src_replay_buffer, tar_replay_buffer], [int(batch_size)] * 2, cb)
@@ -202,52 +154,34 @@ class DARA(IQL):
                          log_out=self._pen if log else None)
 
     def _graph_segments(self, src, tar, batch_size, world, segmented):
-        S, A, c, b, cb = self.S, self.A, self._ctr, self._batch, self._cbatch
-        bufs, bs = [src, tar], int(batch_size)
+        b, cb, bs = self._batch, self._cbatch, int(batch_size)
         N = 2 * bs
 
         def fused_step():
             # both gathers draw with call id c[0] + 1, on index streams of their own; the first advances the classifier's step count,
-            # the second the three of IQL's phases (neither reads them); the critic's optimizer launch advances c[0]
-            common = dict(buffers=[rb._fields() for rb in bufs], counts=[bs, bs], call_offsets=[1, 1], counter=c[0:1],
-                          sizes=[rb.ptr_size[1:2] for rb in bufs], S=S, A=A)
-            ops.gather_batch_rng(seeds=[self._seed_for(104), self._seed_for(105)], out=cb, bump=(c[4:5],), **common)
+            # the second the three of IQL's phases
+            self._captured_gather(src, tar, bs, cb, seed_ids=(104, 105), bump=(4,))
             self._classifier_step(cb, N, dev=True)
-            ops.gather_batch_rng(seeds=[self._seed_for(101), self._seed_for(102)], out=b, bump=(c[1:2], c[2:3], c[3:4]), **common)
+            self._captured_gather(src, tar, bs, b)
             self._relabel(b, N)
             self._update(b, N, N, dev=True)
         return [fused_step]
 
-    def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
-        """One gradient step, dara.py:271-324.  Index draws in the reference's order: src, tar (classifier), src, tar (training)."""
-        self.total_it += 1
-        if not self._synced:
-            self.sync_replicas()
-        N = 2 * int(batch_size)
-        log5k = writer is not None and self.total_it % 5000 == 0
-        if (self.total_it - 1) % REFRESH_EVERY == 0 or log5k:
-            self._health_check()
-        if self._batch is not None and self._batch_key == (N,) and self._graph_ok(writer):
-            if self._graph is None:                       # the capture reads the classifier's count from its device word
-                self._ctr[4] = self.classifier_optimizer.t
-            if self._graph_step(src_replay_buffer, tar_replay_buffer, batch_size):
-                self.classifier_optimizer.t += 1
-                return
-        if self._graph is not None:                       # an eager step moves the host-side counts
-            self._graph = None
-        self._batches(N)
-        b = self._batch
-        self.update_classifier(src_replay_buffer, tar_replay_buffer, batch_size, writer)
-        self._gather([src_replay_buffer, tar_replay_buffer], [int(batch_size)] * 2, b)
-        self._relabel(b, N, log=log5k)
+    def _graph_step(self, src, tar, batch_size):
+        if self._graph is None:                           # the capture reads the classifier's count from its device word
+            self._ctr[4] = self.classifier_optimizer.t
+        if not IQL._graph_step(self, src, tar, batch_size):
+            return False
+        self.classifier_optimizer.t += 1
+        return True
+
+    def _draw(self, src, tar, bs, N, writer, log5k):
+        """dara.py:271-292.  Index draws in the reference's order: src, tar (classifier), src, tar (training)."""
+        self.update_classifier(src, tar, bs, writer)
+        self._gather([src, tar], [bs, bs], self._batch)
+        self._relabel(self._batch, N, log=log5k)
         if log5k:
             writer.add_scalar("train/reward penalty", float(self._pen), global_step=self.total_it)
-        self._update(b, N, N, log=log5k)
-        if log5k:
-            adv_mean, v_mean, q1_mean = [float(x) for x in torch.cat([self._log, self._q1_mean.reshape(1)]).tolist()]
-            writer.add_scalar("train/adv", adv_mean, self.total_it)
-            writer.add_scalar("train/value", v_mean, self.total_it)
-            writer.add_scalar("train/q1", q1_mean, self.total_it)
 
     def classifier_losses(self):
         """(loss_sa, loss_sas) of the last classifier step (forces a device sync)."""
@@ -260,19 +194,6 @@ class DARA(IQL):
         torch.save(self.classifier_optimizer.state_dict(), filename + "_classifier_optimizer")
 
     def load(self, filename):
-        self._graph = None
-        self._synced = False
-        ld = lambda s: torch.load(filename + s, map_location="cpu", weights_only=True)
-        self.q_funcs.load_state_dict(ld("_critic"))
-        self.q_optimizer.load_state_dict(ld("_critic_optimizer"))
-        self.policy.load_state_dict(ld("_actor"))
-        self.policy_optimizer.load_state_dict(ld("_actor_optimizer"))
-        self.classifier.load_state_dict(ld("_classifier"))
-        self.classifier_optimizer.load_state_dict(ld("_classifier_optimizer"))
-        if os.path.exists(filename + "_value"):           # the three files the reference's save leaves out
-            self.v_func.load_state_dict(ld("_value"))
-            self.v_optimizer.load_state_dict(ld("_value_optimizer"))
-        if os.path.exists(filename + "_actor_lr_scheduler"):
-            self.policy_lr_schedule.load_state_dict(ld("_actor_lr_scheduler"))
-        else:                                             # a reference checkpoint: the optimizer file holds the scheduled rate
-            self.policy_optimizer.lr = self.policy_lr_schedule.base_lrs[0]
+        IQL.load(self, filename, optional=("_value", "_actor_lr_scheduler"))     # the three files the reference's save leaves out
+        self.classifier.load_state_dict(self._ld(filename, "_classifier"))
+        self.classifier_optimizer.load_state_dict(self._ld(filename, "_classifier_optimizer"))

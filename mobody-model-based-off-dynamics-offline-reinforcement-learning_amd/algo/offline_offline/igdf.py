@@ -31,7 +31,7 @@ import torch
 
 from ... import ops
 from .iql import IQL
-from .mobody import REFRESH_EVERY, _Adam, _PackedNet
+from .mobody import _Adam, _PackedNet, _PairedAdam, refuse_data_parallel, refuse_missing_keys
 
 _KEYS = ("lam", "temp", "max_step", "xi", "importance_weight", "repr_dim", "ensemble_size", "repr_norm", "ortho_init", "info_update_step")
 MAX_ROWS = 4096             # rows the selection and the contrastive kernel take (csrc/igdf.h)
@@ -66,42 +66,6 @@ class _ContrastiveInfo(object):
         return self.encoder_sa.parameters() + self.encoder_ss.parameters()
 
 
-class _InfoAdam(object):
-    """torch.optim.Adam(info.parameters()) (igdf.py:407): ONE optimizer over both encoders, so one step count; state_dict in torch's
-    format with its 12 parameters in `ContrastiveInfo.parameters()` order, encoder_sa first."""
-
-    def __init__(self, info, lr):
-        self.sa, self.ss = _Adam(info.encoder_sa, lr), _Adam(info.encoder_ss, lr)
-
-    @property
-    def t(self):
-        return self.sa.t
-
-    @t.setter
-    def t(self, value):
-        self.sa.t = self.ss.t = int(value)
-
-    @property
-    def lr(self):
-        return self.sa.lr
-
-    def state_dict(self):
-        a, b = self.sa.state_dict(), self.ss.state_dict()
-        state = dict(a["state"])
-        state.update({k + 6: v for k, v in b["state"].items()})
-        return dict(state=state, param_groups=[dict(a["param_groups"][0], params=list(range(12)))])
-
-    def load_state_dict(self, sd):
-        st, group = sd["state"], sd["param_groups"][0]
-        if st and sorted(st) != list(range(12)):
-            raise ValueError(f"info_optimizer: expected the state of 12 parameters, got {sorted(st)}")
-        half = lambda lo: dict(state={k - lo: st[k] for k in range(lo, lo + 6)} if st else {}, param_groups=[dict(group, params=list(range(6)))])
-        self.sa.load_state_dict(half(0))
-        self.ss.load_state_dict(half(6))
-        if self.sa.t != self.ss.t:
-            raise ValueError(f"info_optimizer: the two encoders' step counts differ ({self.sa.t}, {self.ss.t}); one optimizer steps both")
-
-
 def kept_rows(batch_size, xi):
     """k = int(bs * float(xi)) (igdf.py:507); k < 1 breaks the reference's slicing ([-0:] keeps every row) and is refused."""
     k = int(int(batch_size) * float(xi))
@@ -112,15 +76,11 @@ def kept_rows(batch_size, xi):
 
 class IGDF(IQL):
     def __init__(self, config, device, target_entropy=None):
-        # The reference reads these keys without defaults.  A config without them -- a MOBODY, TD3_BC or DARA config handed to 'igdf'
-        # -- is not an IGDF run: nothing is invented for them, and the refusal has the type the registry gave for 'igdf' before this
-        # class existed.  It comes before every other check.
-        missing = [k for k in _KEYS if k not in config]
-        if missing:
-            raise NotImplementedError(f"IGDF is built from an IGDF config only: config lacks {missing} (the reference's "
-                                      "config/*/igdf/*.yaml values are lam 0.7, temp 3.0, xi 0.75, importance_weight 1.0, repr_dim 64, "
-                                      "ensemble_size 1, repr_norm False, ortho_init False, info_update_step 7000; no defaults are "
-                                      "substituted here)")
+        # The reference reads these keys without defaults: a MOBODY, TD3_BC or DARA config handed to 'igdf' is not an IGDF run.  This
+        # refusal comes before every other check.
+        refuse_missing_keys("IGDF", [k for k in _KEYS if k not in config],
+                            "config/*/igdf/*.yaml values are lam 0.7, temp 3.0, xi 0.75, importance_weight 1.0, repr_dim 64, "
+                            "ensemble_size 1, repr_norm False, ortho_init False, info_update_step 7000")
         if int(config["ensemble_size"]) != 1:
             raise NotImplementedError(f"config['ensemble_size'] = {config['ensemble_size']}: only ensemble_size 1 is built (the "
                                       "reference's train() fails on an ensemble: torch.diag of a 3-D tensor)")
@@ -135,16 +95,15 @@ class IGDF(IQL):
             raise ValueError(f"config['repr_dim'] = {config['repr_dim']} outside 1..128")
         if int(config["info_update_step"]) < 0:
             raise ValueError(f"config['info_update_step'] = {config['info_update_step']} < 0")
-        d = torch.distributed
-        if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
-            raise NotImplementedError("data-parallel IGDF is not built: run 'igdf' on one GPU (only 'mobody' has the "
-                                      "exchange protocol of mobody_amd.dp wired through the CLI)")
+        refuse_data_parallel("IGDF", "igdf")
         IQL.__init__(self, config, device, target_entropy)
         self._no_info_graph = False
         self.xi, self.importance_weight, self.Z = xi, float(config["importance_weight"]), int(config["repr_dim"])
         self.output_gain = config.get("output_gain")          # read under ortho_init only: stored, unused
         self.info = _ContrastiveInfo(self.S, self.A, self.Z, self.device, self.precision)
-        self.info_optimizer = _InfoAdam(self.info, config["actor_lr"])
+        # torch.optim.Adam(info.parameters()) (igdf.py:407), in `ContrastiveInfo.parameters()` order: encoder_sa first
+        self.info_optimizer = _PairedAdam("info_optimizer", "encoders", sa=_Adam(self.info.encoder_sa, config["actor_lr"]),
+                                          ss=_Adam(self.info.encoder_ss, config["actor_lr"]))
         self._stage, self._stage_key = None, None             # the drawn rows [src(bs) | tar(bs)] the filter reads
         self._w = self._score = self._kept = None             # row weights [N], scores [bs], kept positions [k] of the last step
         self._ictr = torch.zeros(2, dtype=torch.int64, device=self.device)     # [info rng call, info t]
@@ -155,14 +114,14 @@ class IGDF(IQL):
     def _encs(self):
         return (self.info.encoder_sa, self.info.encoder_ss)
 
+    def _extra_nets(self):
+        return IQL._extra_nets(self) + self._encs()
+
     def _health_check(self):
+        before = self.precision
         IQL._health_check(self)
-        for n in self._encs():                                # 'fallback' moved the nets to bf16x3: the encoders follow
-            if n.precision != self.precision:
-                n.precision = self.precision
-                ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
-                n.version += 1
-                self._info_graph = None
+        if self.precision != before:                          # 'fallback' moved the nets to bf16x3
+            self._info_graph = None
 
     # ------------------------------------------------------------------ training
     def _dims(self, N, Nt, Ng, Ntg):
@@ -173,17 +132,20 @@ class IGDF(IQL):
             self._ws_key = (N, Nt, bs)
         return ops.train_dims(self.S, self.A, N, Nt, Ng, Ntg), ops.hyper(self.config)
 
-    def _buffers(self, bs, k):
-        N = k + bs
-        if self._stage_key != bs or self._batch_key != (N,):
+    def _rows(self, bs):
+        return kept_rows(bs, self.xi) + bs
+
+    def _buffers(self, bs, N, alloc=False):
+        fit = self._batch is not None and self._batch_key == (N,) and self._stage_key == bs
+        if alloc and not fit:
             if not 2 <= bs <= MAX_ROWS:
                 raise ValueError(f"batch_size {bs} outside [2, {MAX_ROWS}] (the rows the filter's selection takes)")
-            mk = lambda rows: tuple(torch.empty(rows, w, device=self.device) for w in (self.S, self.A, self.S, 1, 1))
-            self._stage, self._batch = mk(2 * bs), mk(N)
+            self._stage, self._batch = self._rows5(2 * bs), self._rows5(N)
             self._w = torch.zeros(N, dtype=torch.float32, device=self.device)
             self._score = torch.zeros(bs, dtype=torch.float32, device=self.device)
-            self._kept = torch.zeros(k, dtype=torch.int32, device=self.device)
+            self._kept = torch.zeros(N - bs, dtype=torch.int32, device=self.device)
             self._stage_key, self._batch_key = bs, (N,)
+        return fit
 
     def _filter(self, bs, k):
         """mobody_igdf_filter: the staged rows -> the training batch and its row weights (igdf.py:494-524)."""
@@ -196,46 +158,19 @@ class IGDF(IQL):
         ops.igdf_critic(*args, row_weight=self._w, **kw)
 
     def _graph_segments(self, src, tar, batch_size, world, segmented):
-        S, A, c = self.S, self.A, self._ctr
-        bufs, bs = [src, tar], int(batch_size)
-        k = kept_rows(bs, self.xi)
-        N = k + bs
+        bs = int(batch_size)
+        N = self._rows(bs)
 
         def fused_step():
-            # the gather draws with call id c[0] + 1 and advances the three Adam step counts (it does not read them); the
-            # critic's optimizer launch advances c[0]
-            ops.gather_batch_rng(buffers=[rb._fields() for rb in bufs], counts=[bs, bs], seeds=[self._seed_for(101), self._seed_for(102)],
-                                 call_offsets=[1, 1], counter=c[0:1], sizes=[rb.ptr_size[1:2] for rb in bufs], S=S, A=A, out=self._stage,
-                                 bump=(c[1:2], c[2:3], c[3:4]))
-            self._filter(bs, k)
+            self._captured_gather(src, tar, bs, self._stage)
+            self._filter(bs, N - bs)
             self._update(self._batch, N, N, dev=True)
         return [fused_step]
 
-    def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
-        """One gradient step, igdf.py:487-549.  Index draws in the reference's order: src, tar."""
-        self.total_it += 1
-        if not self._synced:
-            self.sync_replicas()
-        bs = int(batch_size)
-        k = kept_rows(bs, self.xi)
-        N = k + bs
-        log5k = writer is not None and self.total_it % 5000 == 0
-        if (self.total_it - 1) % REFRESH_EVERY == 0 or log5k:
-            self._health_check()
-        if (self._batch is not None and self._batch_key == (N,) and self._stage_key == bs and self._graph_ok(writer)
-                and self._graph_step(src_replay_buffer, tar_replay_buffer, batch_size)):
-            return
-        if self._graph is not None:                       # an eager step moves the host-side counts
-            self._graph = None
-        self._buffers(bs, k)
-        self._gather([src_replay_buffer, tar_replay_buffer], [bs, bs], self._stage)
-        self._filter(bs, k)
-        self._update(self._batch, N, N, log=log5k)
-        if log5k:
-            adv_mean, v_mean, q1_mean = [float(x) for x in torch.cat([self._log, self._q1_mean.reshape(1)]).tolist()]
-            writer.add_scalar("train/adv", adv_mean, self.total_it)
-            writer.add_scalar("train/value", v_mean, self.total_it)
-            writer.add_scalar("train/q1", q1_mean, self.total_it)
+    def _draw(self, src, tar, bs, N, writer, log5k):
+        """igdf.py:487-524.  Index draws in the reference's order: src, tar."""
+        self._gather([src, tar], [bs, bs], self._stage)
+        self._filter(bs, N - bs)
 
     # ------------------------------------------------------------------ the contrastive update (igdf.py:418-447)
     def _info_buffers(self, n):
@@ -342,6 +277,5 @@ class IGDF(IQL):
         IQL.load(self, filename)
         self._info_graph = None
         if os.path.exists(filename + "_info"):            # the two files the reference's save leaves out
-            ld = lambda s: torch.load(filename + s, map_location="cpu", weights_only=True)
-            self.info.load_state_dict(ld("_info"))
-            self.info_optimizer.load_state_dict(ld("_info_optimizer"))
+            self.info.load_state_dict(self._ld(filename, "_info"))
+            self.info_optimizer.load_state_dict(self._ld(filename, "_info_optimizer"))

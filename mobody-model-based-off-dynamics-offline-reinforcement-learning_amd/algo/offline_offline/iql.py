@@ -23,12 +23,13 @@ its `save` writes; `update_interval` and `target_entropy` are stored and unused,
 `log_alpha` that does not exist and is left out.  Not built: data-parallel IQL (refused in the constructor, before any collective).
 """
 import math
+import os
 
 import numpy as np
 import torch
 
 from ... import ops
-from .mobody import MOBODY, REFRESH_EVERY, _Adam, _PackedNet
+from .mobody import MOBODY, REFRESH_EVERY, _Adam, _PackedNet, refuse_data_parallel, refuse_missing_keys
 
 
 def step_config(config):
@@ -105,18 +106,11 @@ class IQL(MOBODY):
     third_loss_name = "v_loss"            # losses()[2], where MOBODY and TD3_BC report the BC loss
 
     def __init__(self, config, device, target_entropy=None):
-        d = torch.distributed
-        if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
-            raise NotImplementedError("data-parallel IQL is not built: run 'iql' on one GPU (only 'mobody' has the "
-                                      "exchange protocol of mobody_amd.dp wired through the CLI)")
-        # The reference reads config['lam'], ['temp'] and ['max_step'] without defaults.  A config without them -- a MOBODY or TD3_BC
-        # config handed to 'iql' -- is not an IQL run: nothing is invented for them (T_max above all shapes the whole schedule), and
-        # the refusal has the type the registry gave for 'iql' before this class existed.
-        missing = [k for k in ("lam", "temp", "max_step") if k not in config]
-        if missing:
-            raise NotImplementedError(f"IQL is built from an IQL config only: config lacks {missing} (the reference's "
-                                      "config/mujoco/iql/*.yaml values are lam 0.7, temp 3.0, max_step 500000; no defaults are "
-                                      "substituted here)")
+        refuse_data_parallel("IQL", "iql")
+        # The reference reads config['lam'], ['temp'] and ['max_step'] without defaults: a MOBODY or TD3_BC config handed to 'iql' is
+        # not an IQL run (T_max above all shapes the whole schedule).
+        refuse_missing_keys("IQL", [k for k in ("lam", "temp", "max_step") if k not in config],
+                            "config/mujoco/iql/*.yaml values are lam 0.7, temp 3.0, max_step 500000")
         self.lam, self.temp, self.T_max = float(config["lam"]), float(config["temp"]), int(config["max_step"])
         if not 0.0 < self.lam < 1.0:
             raise ValueError(f"config['lam'] = {self.lam} outside (0, 1)")
@@ -149,13 +143,8 @@ class IQL(MOBODY):
         t.blob.copy_(self.tau * q.blob + (1.0 - self.tau) * t.blob)
         ops.mlp_transpose(t.blob, t.in_dim, t.out_dim, t.members, out=t.blob_T, precision=t.precision)
 
-    def _health_check(self):
-        MOBODY._health_check(self)
-        if self.v_func.precision != self.precision:          # 'fallback' moved the nets to bf16x3: V follows
-            n = self.v_func
-            n.precision = self.precision
-            ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
-            n.version += 1
+    def _extra_nets(self):
+        return (self.v_func,)
 
     # ------------------------------------------------------------------ training
     def _dims(self, N, Nt, Ng, Ntg):
@@ -174,42 +163,58 @@ class IQL(MOBODY):
         logs = writer is not None and self.total_it % 5000 == 0
         return bool(want and self.rng == "device" and self.fused_update and not logs)
 
+    def _captured_gather(self, src, tar, bs, out, seed_ids=(101, 102), bump=(1, 2, 3)):
+        """The draw [src(bs) | tar(bs)] of a captured step: call id c[0] + 1 (the critic's optimizer launch advances c[0]); the
+        launch advances the step words `bump` of the optimizers that follow it (it does not read them)."""
+        c, bufs = self._ctr, [src, tar]
+        ops.gather_batch_rng(buffers=[rb._fields() for rb in bufs], counts=[bs, bs], seeds=[self._seed_for(k) for k in seed_ids],
+                             call_offsets=[1, 1], counter=c[0:1], sizes=[rb.ptr_size[1:2] for rb in bufs], S=self.S, A=self.A,
+                             out=out, bump=tuple(c[k:k + 1] for k in bump))
+
     def _graph_segments(self, src, tar, batch_size, world, segmented):
-        S, A, c, b = self.S, self.A, self._ctr, self._batch
-        bufs, N = [src, tar], 2 * int(batch_size)
+        bs = int(batch_size)
 
         def fused_step():
-            # the gather draws with call id c[0] + 1 and advances the three Adam step counts (it does not read them); the
-            # critic's optimizer launch advances c[0]
-            ops.gather_batch_rng(buffers=[rb._fields() for rb in bufs], counts=[int(batch_size)] * 2,
-                                 seeds=[self._seed_for(101), self._seed_for(102)], call_offsets=[1, 1], counter=c[0:1],
-                                 sizes=[rb.ptr_size[1:2] for rb in bufs], S=S, A=A, out=b, bump=(c[1:2], c[2:3], c[3:4]))
-            self._update(b, N, N, dev=True)
+            self._captured_gather(src, tar, bs, self._batch)
+            self._update(self._batch, 2 * bs, 2 * bs, dev=True)
         return [fused_step]
 
+    # What a baseline with IQL's three phases behind a step of its own overrides: _rows, _buffers and _draw (DARA, IGDF).
+    def _rows(self, bs):
+        """Rows of the training batch at batch size bs."""
+        return 2 * bs
+
+    def _rows5(self, rows):
+        return tuple(torch.empty(rows, w, device=self.device) for w in (self.S, self.A, self.S, 1, 1))
+
+    def _buffers(self, bs, N, alloc=False):
+        """Whether the cached minibatch tensors fit the step; alloc: make them fit."""
+        fit = self._batch is not None and self._batch_key == (N,)
+        if alloc and not fit:
+            self._batch, self._batch_key = self._rows5(N), (N,)
+        return fit
+
+    def _draw(self, src, tar, bs, N, writer, log5k):
+        """The eager step up to IQL's phases: fill self._batch.  Index draws in the reference's order: src, tar."""
+        self._gather([src, tar], [bs, bs], self._batch)
+
     def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
-        """One gradient step, iql.py:204-240.  Index draws in the reference's order: src, tar."""
+        """One gradient step (iql.py:204-240, dara.py:271-324, igdf.py:487-549)."""
         self.total_it += 1
         if not self._synced:
             self.sync_replicas()
-        S, A = self.S, self.A
-        N = 2 * int(batch_size)
+        bs = int(batch_size)
+        N = self._rows(bs)
         log5k = writer is not None and self.total_it % 5000 == 0
         if (self.total_it - 1) % REFRESH_EVERY == 0 or log5k:
             self._health_check()
-        if (self._batch is not None and self._batch_key == (N,) and self._graph_ok(writer)
-                and self._graph_step(src_replay_buffer, tar_replay_buffer, batch_size)):
+        if self._buffers(bs, N) and self._graph_ok(writer) and self._graph_step(src_replay_buffer, tar_replay_buffer, batch_size):
             return
         if self._graph is not None:                       # an eager step moves the host-side counts
             self._graph = None
-        if self._batch_key != (N,):
-            dev = self.device
-            self._batch = (torch.empty(N, S, device=dev), torch.empty(N, A, device=dev), torch.empty(N, S, device=dev),
-                           torch.empty(N, 1, device=dev), torch.empty(N, 1, device=dev))
-            self._batch_key = (N,)
-        b = self._batch
-        self._gather([src_replay_buffer, tar_replay_buffer], [int(batch_size)] * 2, b)
-        self._update(b, N, N, log=log5k)
+        self._buffers(bs, N, alloc=True)
+        self._draw(src_replay_buffer, tar_replay_buffer, bs, N, writer, log5k)
+        self._update(self._batch, N, N, log=log5k)
         if log5k:      # the three scalars of a logging step, each from BEFORE the update of its net (:181-183, :193-194)
             adv_mean, v_mean, q1_mean = [float(x) for x in torch.cat([self._log, self._q1_mean.reshape(1)]).tolist()]
             writer.add_scalar("train/adv", adv_mean, self.total_it)
@@ -269,14 +274,23 @@ class IQL(MOBODY):
         torch.save(sd, filename + "_actor_optimizer")
         torch.save(self.policy_lr_schedule.state_dict(), filename + "_actor_lr_scheduler")
 
-    def load(self, filename):
+    def _ld(self, filename, suffix):
+        return torch.load(filename + suffix, map_location="cpu", weights_only=True)
+
+    def load(self, filename, optional=()):
+        """optional: of "_value" (with its optimizer's file) and "_actor_lr_scheduler", the files a checkpoint may lack."""
         self._graph = None                              # re-capture: the device-side Adam step counts change
         self._synced = False
-        ld = lambda s: torch.load(filename + s, map_location="cpu", weights_only=True)
+        ld = lambda s: self._ld(filename, s)
+        have = lambda s: s not in optional or os.path.exists(filename + s)
         self.q_funcs.load_state_dict(ld("_critic"))
         self.q_optimizer.load_state_dict(ld("_critic_optimizer"))
-        self.v_func.load_state_dict(ld("_value"))
-        self.v_optimizer.load_state_dict(ld("_value_optimizer"))
+        if have("_value"):
+            self.v_func.load_state_dict(ld("_value"))
+            self.v_optimizer.load_state_dict(ld("_value_optimizer"))
         self.policy.load_state_dict(ld("_actor"))
         self.policy_optimizer.load_state_dict(ld("_actor_optimizer"))
-        self.policy_lr_schedule.load_state_dict(ld("_actor_lr_scheduler"))   # (restores the optimizer's base rate)
+        if have("_actor_lr_scheduler"):
+            self.policy_lr_schedule.load_state_dict(ld("_actor_lr_scheduler"))   # (restores the optimizer's base rate)
+        else:                                             # a reference checkpoint: the optimizer file holds the scheduled rate
+            self.policy_optimizer.lr = self.policy_lr_schedule.base_lrs[0]

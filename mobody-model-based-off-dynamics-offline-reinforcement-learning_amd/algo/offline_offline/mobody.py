@@ -141,6 +141,64 @@ class _Adam(object):
         self.t = int(float(st[0]["step"]))
 
 
+class _PairedAdam(object):
+    """torch.optim.Adam over the parameters of two nets (DARA's classifier, dara.py:192; IGDF's encoders, igdf.py:407): ONE
+    optimizer, so one step count; state_dict in torch's format with its 12 parameters in order, the first net's first.
+    `pair`: the two nets' _Adam under the names they are reached by (sa=, sas= / sa=, ss=); `what` and `nets`: the words the
+    messages carry ('classifier_optimizer', 'heads')."""
+
+    def __init__(self, what, nets, **pair):
+        self.what, self.nets = what, nets
+        self.first, self.second = pair.values()
+        self.__dict__.update(pair)
+
+    @property
+    def t(self):
+        return self.first.t
+
+    @t.setter
+    def t(self, value):
+        self.first.t = self.second.t = int(value)
+
+    @property
+    def lr(self):
+        return self.first.lr
+
+    def state_dict(self):
+        a, b = self.first.state_dict(), self.second.state_dict()
+        state = dict(a["state"])
+        state.update({k + 6: v for k, v in b["state"].items()})
+        return dict(state=state, param_groups=[dict(a["param_groups"][0], params=list(range(12)))])
+
+    def load_state_dict(self, sd):
+        st, group = sd["state"], sd["param_groups"][0]
+        if st and sorted(st) != list(range(12)):
+            raise ValueError(f"{self.what}: expected the state of 12 parameters, got {sorted(st)}")
+        half = lambda lo: dict(state={k - lo: st[k] for k in range(lo, lo + 6)} if st else {}, param_groups=[dict(group, params=list(range(6)))])
+        self.first.load_state_dict(half(0))
+        self.second.load_state_dict(half(6))
+        if self.first.t != self.second.t:
+            raise ValueError(f"{self.what}: the two {self.nets}' step counts differ ({self.first.t}, {self.second.t}); one optimizer steps both")
+
+
+def refuse_data_parallel(name, key):
+    """The constructors of the baselines without an exchange protocol: refuse a multi-rank job before any collective."""
+    d = torch.distributed
+    if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
+        raise NotImplementedError(f"data-parallel {name} is not built: run '{key}' on one GPU (only 'mobody' has the "
+                                  "exchange protocol of mobody_amd.dp wired through the CLI)")
+
+
+def refuse_missing_keys(name, missing, values):
+    """A config without the keys the reference reads without defaults is another algorithm's config: nothing is invented for
+    them, and the refusal has the type the registry gave for the name before its class existed.  `values`: where the reference
+    keeps them and what they are there."""
+    if missing:
+        article = "an" if name[0] in "AEIO" else "a"
+        raise NotImplementedError(f"{name} is built from {article} {name} config only: config lacks {missing} (the reference's "
+                                  f"{values}; no defaults are substituted here)")
+
+
 class _Classifier(object):
     """Domain classifier (mobody.py:11-33): two packed MLPs `sa_classifier` (S+A -> 2) and `sas_classifier`
     (2S+A -> 2) whose heads output softmax probabilities.  Training and the reward-penalty sweep run through the
@@ -485,7 +543,8 @@ class MOBODY(object):
             warnings.warn("falling back to mfma='bf16x3': " + msg)
             self.mfma, self.precision = "bf16x3", ops.prec_id("bf16x3")
             self.config["mfma"] = "bf16x3"
-            for n in (self.q_funcs, self.target_q_funcs, self.policy):   # T blobs and planes again, from the intact fp32 weights
+            # T blobs and planes again, from the intact fp32 weights: every net the object runs at the configured mode
+            for n in (self.q_funcs, self.target_q_funcs, self.policy) + tuple(self._extra_nets()):
                 n.precision = self.precision
                 ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
                 n.version += 1
@@ -494,6 +553,11 @@ class MOBODY(object):
             return
         self._fault = msg
         raise FloatingPointError(msg)
+
+    def _extra_nets(self):
+        """The nets a subclass runs at the configured MFMA mode besides the twin-Q, its target and the policy: a fallback moves
+        them too.  (None here: the base's V and classifier are fp32 nets.)"""
+        return ()
 
     def _health_rewind(self, step, opt):
         """Host step counts back to the updates that were applied.  `step` is the faulting optimizer's own count; within a

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from .mobody import MOBODY, REFRESH_EVERY
+from .mobody import MOBODY, REFRESH_EVERY, refuse_data_parallel
 
 DARA_REWARD_COEF = 0.1          # td3_bc.py:200 (a literal there, not config['penalty_coef'])
 
@@ -42,10 +42,7 @@ def step_config(config):
 
 class TD3BC(MOBODY):
     def __init__(self, config, device, target_entropy=None):
-        d = torch.distributed
-        if d.is_available() and d.is_initialized() and d.get_world_size() > 1:
-            raise NotImplementedError("data-parallel TD3_BC is not built: run 'td3_bc' on one GPU (only 'mobody' has the "
-                                      "exchange protocol of mobody_amd.dp wired through the CLI)")
+        refuse_data_parallel("TD3_BC", "td3_bc")
         self.user_config = config
         MOBODY.__init__(self, step_config(config), device)
 

@@ -30,6 +30,13 @@ struct TrainWs {
   MobodyMlpLayout Lq, La;
 };
 
+// hands a workspace out front to back, every piece rounded up to 4 floats; base == null: the sizes alone (no device is touched)
+struct Carver {
+  float* base;
+  long long off = 0;
+  float* operator()(long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; }
+};
+
 static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   int rc = mobody_mlp_layout(d.S + d.A, 1, 2, &w.Lq);
   if (rc) return rc;
@@ -37,8 +44,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   if (rc) return rc;
   const long long N = d.N, Nt = d.Nt;
   const long long N32 = (N + 31) & ~31LL;             // h1 / dz2 hold fp16 planes of whole 32-row tiles in the f16 mode (same bytes)
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   w.pi = take(N * d.A);
   w.pin = take(N * d.A);
   w.qt = take(2 * N);
@@ -72,7 +78,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   }
   w.bc = take(4);
   w.tickets = (int*)take(w.ntiles);
-  w.total = off;
+  w.total = take.off;
   return 0;
 }
 
@@ -501,24 +507,61 @@ extern "C" int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream) {
 // ---- IQL (the reference's algo/offline_offline/iql.py): V with the expectile seed, twin-Q against V(s') through critic_impl, the
 // policy with the advantage-weighted regression seed and a cosine learning rate.  DESIGN 5r. ----
 namespace mobody {
-// training scratch of one one-member net on the step's N rows
-struct IqlNetWs {
+// training scratch of one single-member net on `rows` rows: IQL's V and policy, DARA's heads, IGDF's encoders
+struct OneNetScratch {
   float *out, *x, *h1, *h2, *dz3, *dz2, *dz1, *dbp, *slabs, *lossp, *bc;
   uint32_t *m1, *m2;
   int *e_h1, *e_dz2;
   int nsplit, ntiles;
 };
+
+// where one net's gradient goes: into `grad` (the gradient form), or through Adam on m, v at step t / t_dev[0] and rate lr (fused)
+struct NetOpt { float *grad, *m, *v; int64_t t; const int64_t* t_dev; float lr; };
+
+// One trained net: its layout, scratch, rows, weights and MFMA mode, bound once.  The three steps every net of the family takes
+// are written here and nowhere else; what differs between the algorithms -- sources, loss seed, loss wiring -- stays with the caller.
+struct TrainedNet {
+  const MobodyMlpLayout& L; const OneNetScratch& s; long long rows; float *blob, *blob_T; int prec;
+  // the forward on one or two sources, linear outputs to s.out, with the saves of the backward
+  Mlp3FwdArgs forward(const float* s0, int n0, const float* s1 = nullptr, int n1 = 0) const {
+    return fwd_args(blob, L, s0, n0, s1, n1, rows, s.out, 0, 1.f, s.x, s.h1, s.h2, s.m1, s.m2, prec != PREC_F32 ? blob_T : nullptr,
+                    prec == PREC_F16X2 ? s.e_h1 : nullptr);
+  }
+  // the backward from dz3 in memory; dz3 == null: from a loss seed in the prologue, which leaves dz3 and the loss partials in the
+  // scratch -- the caller sets the seed's mode and the fields of that mode
+  Mlp3BwdArgs backward(const float* dz3 = nullptr) const {
+    Mlp3BwdArgs b = bwd_args(L, blob_T, dz3, s.h1, s.h2, rows, s.dz2, s.dz1, s.dbp, s.m1, s.m2, prec, s.e_dz2);
+    if (dz3 == nullptr) { b.seed.dz3_out = s.dz3; b.seed.lossp = s.lossp; }
+    return b;
+  }
+  // dW, db from what the forward and the backward left, the loss scalar out[0] = scale * sum(parts[0..nparts)) (out == null: none)
+  // and, fused, the Adam step; bc_ready: the backward's seed has written the bias corrections; bump: AdamTarget::bump
+  int finish(const NetOpt& o, const float* parts, int nparts, float scale, float* out, bool bc_ready, hipStream_t st,
+             int64_t* bump = nullptr) const {
+    AdamTarget adam = o.m ? adam_target(blob, blob_T, o.m, o.v, nullptr, o.t, o.t_dev, o.lr, -1.f, 1.f, prec) : AdamTarget{};
+    if (o.m) adam.bump = (long long*)bump;
+    LossFinal lf{};
+    if (out != nullptr) { lf.kind = 1; lf.nparts = nparts; lf.scale = scale; lf.parts = parts; lf.out = out; }
+    Mlp3WgradArgs g = wgrad_net(L, rows, s.nsplit);
+    wgrad_set_saves(g, s.x, 0, s.h1, s.h2, s.e_h1);
+    wgrad_set_grads(g, s.dz3, s.dz2, s.dz1, s.dbp, s.ntiles, s.e_dz2);
+    wgrad_set_scratch(g, s.slabs, s.bc);
+    wgrad_set_result(g, o.grad, lf, adam, prec);
+    g.bc_ready = bc_ready ? 1 : 0;
+    return mlp3_weight_grads(g, st);
+  }
+};
+
 struct IqlWs {
   TrainWs tw;              // the critic's scratch, where mobody_critic carves it
   MobodyMlpLayout Lv, Lp;
-  IqlNetWs v, p;
+  OneNetScratch v, p;
   float *qt, *vnext;       // target twin-Q(s, a) [2][N], V(s') [N]
   long long total;
 };
 
-// one net's record on N rows, nloss loss partials per row tile
-template <class Take>
-static void carve_iql_net(const MobodyMlpLayout& L, long long N, int nloss, IqlNetWs& n, Take&& take) {
+// one net's scratch on N rows, nloss loss partials per row tile
+static void carve_one_net(const MobodyMlpLayout& L, long long N, int nloss, OneNetScratch& n, Carver& take) {
   const long long N32 = (N + 31) & ~31LL, mw = cdiv(N, 32) * HID;
   n.ntiles = (int)cdiv(N, MLP_TILE_ROWS); n.nsplit = wgrad_nsplit(N, 1);
   n.out = take(N * L.out_dim); n.x = take(N * L.Kp1); n.h1 = take(N32 * HID); n.h2 = take(N * HID);
@@ -537,47 +580,55 @@ static int carve_iql(const MobodyTrainDims& d, float* base, IqlWs& w) {
   if (rc) return rc;
   rc = mobody_mlp_layout(d.S, 2 * d.A, 1, &w.Lp);
   if (rc) return rc;
-  const long long N = d.N;
-  long long off = w.tw.total;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  auto net = [&](const MobodyMlpLayout& L, IqlNetWs& n, int nloss) { carve_iql_net(L, N, nloss, n, take); };
-  net(w.Lv, w.v, 3);
-  net(w.Lp, w.p, 1);
-  w.qt = take(2 * N); w.vnext = take(N);
-  w.total = off;
+  Carver take{base, w.tw.total};
+  carve_one_net(w.Lv, d.N, 3, w.v, take);
+  carve_one_net(w.Lp, d.N, 1, w.p, take);
+  w.qt = take(2 * d.N); w.vnext = take(d.N);
+  w.total = take.off;
+  return 0;
+}
+
+// The size bounds the family's entry points and its *_workspace functions share.  s_in (1 or 2; 0: none): the algorithm's widest
+// extra net reads s_in S + A input columns (IGDF's encoder_sa, DARA's sas head).
+static int family_sizes(const char* who, const MobodyTrainDims* d, int s_in = 0) {
+  int rc = check_dims(d, who);
+  if (rc) return rc;
+  MB_REQUIRE(d->S >= 1 && d->A >= 1 && 2 * d->A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, d->A);
+  MB_REQUIRE(s_in * d->S + d->A <= 256, "%s: %sS + A = %d > 256 (the widest input a packed MLP takes)", who, s_in == 2 ? "2 " : "",
+             s_in * d->S + d->A);
+  return 0;
+}
+
+// "exactly one of the gradient blobs and the optimizer state": one net, or two that one optimizer steps (one t, t_dev and lr).
+// grads: the block's gradient field names; nets: " of both heads" and the like, or ""
+static int check_opt(const char* who, const NetOpt* o, int n, const char* grads, const char* nets) {
+  bool any_grad = false, all_grad = true, any_opt = false, all_opt = true;
+  for (int k = 0; k < n; ++k) {
+    any_grad |= o[k].grad != nullptr; all_grad &= o[k].grad != nullptr;
+    any_opt |= o[k].m != nullptr || o[k].v != nullptr; all_opt &= o[k].m != nullptr && o[k].v != nullptr;
+  }
+  MB_REQUIRE(any_grad != any_opt, "%s: exactly one of %s and the optimizer state m, v%s must be given", who, grads, nets);
+  MB_REQUIRE(all_grad || all_opt, "%s: null pointer", who);
+  MB_REQUIRE(!any_opt || o[0].t_dev != nullptr || o[0].t >= 1, "%s: step t must be >= 1", who);
   return 0;
 }
 
 // what the three entry points check alike, before any runtime call
 static int iql_check(const MobodyIql* a, const char* who) {
   MB_BLOCK(who, a, MobodyIql);
-  int rc = check_dims(&a->d, who);
+  int rc = family_sizes(who, &a->d);
   if (rc) return rc;
-  MB_REQUIRE(a->d.S >= 1 && a->d.A >= 1 && 2 * a->d.A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, a->d.A);
   MB_REQUIRE(a->lam > 0.f && a->lam < 1.f, "%s: lam %g outside (0, 1)", who, (double)a->lam);
-  MB_REQUIRE((a->grad != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad and the optimizer state m, v must be given", who);
-  MB_REQUIRE(a->grad || (a->m && a->v), "%s: null pointer", who);
-  MB_REQUIRE(a->m == nullptr || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  const NetOpt o{a->grad, a->m, a->v, a->t, a->t_dev, a->lr};
+  rc = check_opt(who, &o, 1, "grad", "");
+  if (rc) return rc;
   MB_REQUIRE(a->state && a->action && a->loss_out && a->workspace, "%s: null pointer", who);
   return check_precision(who, a->h.precision, true);
-}
-
-// dW, db of one of the two nets from what its forward and backward left, the loss scalar and (fused) the Adam step
-static int iql_weight_grads(const MobodyMlpLayout& L, const IqlNetWs& n, long long N, float* grad, const LossFinal& lf,
-                            const AdamTarget& adam, int prec, bool bc_ready, hipStream_t st) {
-  Mlp3WgradArgs g = wgrad_net(L, N, n.nsplit);
-  wgrad_set_saves(g, n.x, 0, n.h1, n.h2, n.e_h1);
-  wgrad_set_grads(g, n.dz3, n.dz2, n.dz1, n.dbp, n.ntiles, n.e_dz2);
-  wgrad_set_scratch(g, n.slabs, n.bc);
-  wgrad_set_result(g, grad, lf, adam, prec);
-  g.bc_ready = bc_ready ? 1 : 0;
-  return mlp3_weight_grads(g, st);
 }
 }  // namespace mobody
 
 extern "C" int64_t mobody_iql_workspace(const MobodyTrainDims* d) {
-  if (check_dims(d, "mobody_iql_workspace")) return -1;
-  if (d->S < 1 || d->A < 1 || 2 * d->A > 128) { fail(MOBODY_E_ARG, "mobody_iql_workspace: d.A %d: 2 A > 128", d->A); return -1; }
+  if (family_sizes("mobody_iql_workspace", d)) return -1;
   IqlWs w;
   if (carve_iql(*d, nullptr, w)) return -1;
   return w.total;
@@ -594,27 +645,21 @@ extern "C" int mobody_iql_value(const MobodyIql* a, void* stream) {
   IqlWs w;
   rc = carve_iql(a->d, a->workspace, w);
   if (rc) return rc;
-  const bool fused = a->m != nullptr;
-  const AdamTarget adam = fused ? adam_target(a->v_blob, a->v_blob_T, a->m, a->v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
   hipStream_t st = as_stream(stream);
   const long long N = a->d.N;
   const int S = a->d.S, A = a->d.A;
-  const float *vT = prec != PREC_F32 ? a->v_blob_T : nullptr, *tT = prec != PREC_F32 ? a->qtarg_blob_T : nullptr;
+  const TrainedNet v{w.Lv, w.v, N, a->v_blob, a->v_blob_T, prec};
   // target twin-Q(s, a) (no grad, :175-177) and V(s) with its saves (:179) read the same rows: one launch
-  const Mlp3FwdArgs ft = fwd_args(a->qtarg_blob, w.tw.Lq, a->state, S, a->action, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr, tT);
-  const Mlp3FwdArgs fv = fwd_args(a->v_blob, w.Lv, a->state, S, nullptr, 0, N, w.v.out, 0, 1.f, w.v.x, w.v.h1, w.v.h2, w.v.m1, w.v.m2, vT,
-                                  prec == PREC_F16X2 ? w.v.e_h1 : nullptr);
-  rc = launch_mlp3_forward(ft, 2, fv, 1, ACT_RELU, prec, st);
+  const Mlp3FwdArgs ft = fwd_args(a->qtarg_blob, w.tw.Lq, a->state, S, a->action, A, N, w.qt, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  prec != PREC_F32 ? a->qtarg_blob_T : nullptr);
+  rc = launch_mlp3_forward(ft, 2, v.forward(a->state, S), 1, ACT_RELU, prec, st);
   if (rc) return rc;
   const float invNg = 1.f / (float)a->d.N_global;
-  Mlp3BwdArgs b = bwd_args(w.Lv, a->v_blob_T, nullptr, w.v.h1, w.v.h2, N, w.v.dz2, w.v.dz1, w.v.dbp, w.v.m1, w.v.m2, prec, w.v.e_dz2);
+  Mlp3BwdArgs b = v.backward();
   b.seed.mode = 5; b.seed.iq.qt = w.qt; b.seed.iq.v = w.v.out; b.seed.iq.adv_out = a->adv; b.seed.iq.lam = a->lam; b.seed.iq.inv = invNg;
-  b.seed.dz3_out = w.v.dz3; b.seed.lossp = w.v.lossp;
   rc = launch_mlp3_bwd_seed(b, st);
   if (rc) return rc;
-  LossFinal lf{};
-  lf.kind = 1; lf.nparts = w.v.ntiles; lf.scale = invNg; lf.parts = w.v.lossp; lf.out = a->loss_out;
-  rc = iql_weight_grads(w.Lv, w.v, N, a->grad, lf, adam, prec, false, st);
+  rc = v.finish({a->grad, a->m, a->v, a->t, a->t_dev, a->lr}, w.v.lossp, w.v.ntiles, invNg, a->loss_out, false, st);
   if (rc || a->log_out == nullptr) return rc;
   // the logged scalars of a logging step (:181-183): two more partial sums of the seed prologue
   for (int k = 0; k < 2; ++k) {
@@ -663,26 +708,20 @@ extern "C" int mobody_iql_actor(const MobodyIql* a, void* stream) {
   const bool fused = a->m != nullptr, dev = fused && a->t_dev != nullptr;
   // the step's learning rate: from the host count here, from the device count in the backward launch's first tile
   const float lr_k = dev || !fused ? a->lr : cosine_lr(a->lr, a->t, a->T_max);
-  const AdamTarget adam = fused ? adam_target(a->pi_blob, a->pi_blob_T, a->m, a->v, nullptr, a->t, a->t_dev, lr_k, -1.f, 1.f, prec) : AdamTarget{};
   hipStream_t st = as_stream(stream);
-  const long long N = a->d.N;
-  const int S = a->d.S, A = a->d.A;
+  const int A = a->d.A;
+  const TrainedNet pi{w.Lp, w.p, a->d.N, a->pi_blob, a->pi_blob_T, prec};
   // the linear 2 A outputs (mu | logstd, :92-93) with the saves of the backward
-  const Mlp3FwdArgs fp = fwd_args(a->pi_blob, w.Lp, a->state, S, nullptr, 0, N, w.p.out, 0, 1.f, w.p.x, w.p.h1, w.p.h2, w.p.m1, w.p.m2,
-                                  prec != PREC_F32 ? a->pi_blob_T : nullptr, prec == PREC_F16X2 ? w.p.e_h1 : nullptr);
-  rc = launch_mlp3_forward(fp, 1, ACT_RELU, prec, st);
+  rc = launch_mlp3_forward(pi.forward(a->state, a->d.S), 1, ACT_RELU, prec, st);
   if (rc) return rc;
   const float inv = 1.f / ((float)a->d.N_global * (float)A);
-  Mlp3BwdArgs b = bwd_args(w.Lp, a->pi_blob_T, nullptr, w.p.h1, w.p.h2, N, w.p.dz2, w.p.dz1, w.p.dbp, w.p.m1, w.p.m2, prec, w.p.e_dz2);
+  Mlp3BwdArgs b = pi.backward();
   b.seed.mode = 6; b.seed.iq.z = w.p.out; b.seed.iq.ldz = 2 * A; b.seed.iq.act = a->action; b.seed.iq.adv = a->adv; b.seed.iq.A = A;
   b.seed.iq.temp = a->temp; b.seed.iq.inv = inv;
   if (dev) { b.seed.iq.bc_out = w.p.bc; b.seed.iq.t_dev = (const long long*)a->t_dev; b.seed.iq.T_max = a->T_max; b.seed.iq.lr0 = a->lr; }
-  b.seed.dz3_out = w.p.dz3; b.seed.lossp = w.p.lossp;
   rc = launch_mlp3_bwd_seed(b, st);
   if (rc) return rc;
-  LossFinal lf{};
-  lf.kind = 1; lf.nparts = w.p.ntiles; lf.scale = inv; lf.parts = w.p.lossp; lf.out = a->loss_out;
-  return iql_weight_grads(w.Lp, w.p, N, a->grad, lf, adam, prec, dev, st);
+  return pi.finish({a->grad, a->m, a->v, a->t, a->t_dev, lr_k}, w.p.lossp, w.p.ntiles, inv, a->loss_out, dev, st);
 }
 
 // ---- DARA (the reference's algo/offline_offline/dara.py): IQL's step behind one domain-classifier update per step and a relabel
@@ -692,7 +731,7 @@ namespace mobody {
 struct DaraWs {
   IqlWs iq;                // IQL's scratch, where its three entry points carve it
   MobodyMlpLayout Lsa, Lsas;
-  IqlNetWs sa, sas;
+  OneNetScratch sa, sas;
   float *xin_sa, *xin_sas; // noisy input rows [N][S+A], [N][2S+A] (the forward's sources; its save_x is the padded copy)
   float* delta;            // [N] per-row penalty when the caller keeps none
   long long total;
@@ -706,23 +745,20 @@ static int carve_dara(const MobodyTrainDims& d, float* base, DaraWs& w) {
   rc = mobody_mlp_layout(2 * d.S + d.A, 2, 1, &w.Lsas);
   if (rc) return rc;
   const long long N = d.N;
-  long long off = w.iq.total;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
-  carve_iql_net(w.Lsa, N, 1, w.sa, take);
-  carve_iql_net(w.Lsas, N, 1, w.sas, take);
+  Carver take{base, w.iq.total};
+  carve_one_net(w.Lsa, N, 1, w.sa, take);
+  carve_one_net(w.Lsas, N, 1, w.sas, take);
   w.xin_sa = take(N * (d.S + d.A)); w.xin_sas = take(N * (2 * d.S + d.A));
   w.delta = take(N);
-  w.total = off;
+  w.total = take.off;
   return 0;
 }
 
 // what the two entry points check alike, before any runtime call; n_src: the source rows (a->n_src, or N / 2)
 static int dara_check(const MobodyDara* a, const char* who, long long& n_src) {
   MB_BLOCK(who, a, MobodyDara);
-  int rc = check_dims(&a->d, who);
+  int rc = family_sizes(who, &a->d, 2);
   if (rc) return rc;
-  MB_REQUIRE(a->d.S >= 1 && a->d.A >= 1 && 2 * a->d.A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, a->d.A);
-  MB_REQUIRE(2 * a->d.S + a->d.A <= 256, "%s: 2 S + A = %d > 256 (the widest input a packed MLP takes)", who, 2 * a->d.S + a->d.A);
   MB_REQUIRE(a->n_src >= 0 && a->n_src <= a->d.N, "%s: n_src %lld outside [0, N = %lld]", who, (long long)a->n_src, (long long)a->d.N);
   MB_REQUIRE(a->n_src != 0 || a->d.N % 2 == 0, "%s: N %lld is odd and n_src is not given (rows are [src | tar], n_src = N / 2)", who, (long long)a->d.N);
   n_src = a->n_src != 0 ? a->n_src : a->d.N / 2;
@@ -732,9 +768,7 @@ static int dara_check(const MobodyDara* a, const char* who, long long& n_src) {
 }  // namespace mobody
 
 extern "C" int64_t mobody_dara_workspace(const MobodyTrainDims* d) {
-  if (check_dims(d, "mobody_dara_workspace")) return -1;
-  if (d->S < 1 || d->A < 1 || 2 * d->A > 128) { fail(MOBODY_E_ARG, "mobody_dara_workspace: d.A %d: 2 A > 128", d->A); return -1; }
-  if (2 * d->S + d->A > 256) { fail(MOBODY_E_ARG, "mobody_dara_workspace: 2 S + A = %d > 256", 2 * d->S + d->A); return -1; }
+  if (family_sizes("mobody_dara_workspace", d, 2)) return -1;
   DaraWs w;
   if (carve_dara(*d, nullptr, w)) return -1;
   return w.total;
@@ -746,17 +780,16 @@ extern "C" int mobody_dara_classifier(const MobodyDara* a, void* stream) {
   long long n_src = 0;
   int rc = dara_check(a, who, n_src);
   if (rc) return rc;
-  const bool any_grad = a->grad_sa != nullptr || a->grad_sas != nullptr, any_opt = a->m_sa || a->v_sa || a->m_sas || a->v_sas;
-  MB_REQUIRE(any_grad != any_opt, "%s: exactly one of grad_sa, grad_sas and the optimizer state m, v of both heads must be given", who);
-  MB_REQUIRE((a->grad_sa && a->grad_sas) || (a->m_sa && a->v_sa && a->m_sas && a->v_sas), "%s: null pointer", who);
-  MB_REQUIRE(!any_opt || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  // one optimizer over both heads = one step count and rate (:192); sas first, as the launches go
+  const NetOpt opt[2] = {{a->grad_sas, a->m_sas, a->v_sas, a->t, a->t_dev, a->lr}, {a->grad_sa, a->m_sa, a->v_sa, a->t, a->t_dev, a->lr}};
+  rc = check_opt(who, opt, 2, "grad_sa, grad_sas", " of both heads");
+  if (rc) return rc;
   MB_REQUIRE(a->loss_out, "%s: null pointer", who);
   MB_REQUIRE(a->noise_std >= 0.f, "%s: noise_std %g < 0", who, (double)a->noise_std);
   DaraWs w;
   rc = carve_dara(a->d, a->workspace, w);
   if (rc) return rc;
   const int prec = a->precision;
-  const bool fused = any_opt;
   hipStream_t st = as_stream(stream);
   const long long N = a->d.N;
   const int S = a->d.S, A = a->d.A;
@@ -765,29 +798,19 @@ extern "C" int mobody_dara_classifier(const MobodyDara* a, void* stream) {
   rc = launch_dara_inputs(in, (const long long*)a->call_dev, a->call_offset, st);
   if (rc) return rc;
   // 2. both heads' forwards with the saves of their backwards (:136, :142): one launch
-  const bool f16 = prec == PREC_F16X2;
-  const Mlp3FwdArgs f_sas = fwd_args(a->sas_blob, w.Lsas, w.xin_sas, 2 * S + A, nullptr, 0, N, w.sas.out, 0, 1.f, w.sas.x, w.sas.h1, w.sas.h2, w.sas.m1,
-                                     w.sas.m2, prec != PREC_F32 ? a->sas_blob_T : nullptr, f16 ? w.sas.e_h1 : nullptr);
-  const Mlp3FwdArgs f_sa = fwd_args(a->sa_blob, w.Lsa, w.xin_sa, S + A, nullptr, 0, N, w.sa.out, 0, 1.f, w.sa.x, w.sa.h1, w.sa.h2, w.sa.m1, w.sa.m2,
-                                    prec != PREC_F32 ? a->sa_blob_T : nullptr, f16 ? w.sa.e_h1 : nullptr);
-  rc = launch_mlp3_forward(f_sas, 1, f_sa, 1, ACT_RELU, prec, st);
+  const TrainedNet heads[2] = {{w.Lsas, w.sas, N, a->sas_blob, a->sas_blob_T, prec}, {w.Lsa, w.sa, N, a->sa_blob, a->sa_blob_T, prec}};
+  rc = launch_mlp3_forward(heads[0].forward(w.xin_sas, 2 * S + A), 1, heads[1].forward(w.xin_sa, S + A), 1, ACT_RELU, prec, st);
   if (rc) return rc;
   // 3., 4. per head: the backward with the double-softmax cross-entropy seed in its prologue (:217-219), then the weight
-  // gradients with the loss scalar and (fused) the Adam step; one optimizer over both heads = one step count (:192)
+  // gradients with the loss scalar (loss_out = (loss_sa, loss_sas)) and (fused) the Adam step
   const float invNg = 1.f / (float)a->d.N_global;
-  struct Head { const MobodyMlpLayout& L; const IqlNetWs& n; float *blob, *blob_T, *grad, *m, *v, *loss; };
-  const Head heads[2] = {{w.Lsas, w.sas, a->sas_blob, a->sas_blob_T, a->grad_sas, a->m_sas, a->v_sas, a->loss_out + 1},
-                         {w.Lsa, w.sa, a->sa_blob, a->sa_blob_T, a->grad_sa, a->m_sa, a->v_sa, a->loss_out}};
-  for (const Head& h : heads) {
-    Mlp3BwdArgs b = bwd_args(h.L, h.blob_T, nullptr, h.n.h1, h.n.h2, N, h.n.dz2, h.n.dz1, h.n.dbp, h.n.m1, h.n.m2, prec, h.n.e_dz2);
-    b.seed.mode = 7; b.seed.da.z = h.n.out; b.seed.da.ldz = 2; b.seed.da.n_src = n_src; b.seed.da.inv = invNg;
-    b.seed.dz3_out = h.n.dz3; b.seed.lossp = h.n.lossp;
+  for (int k = 0; k < 2; ++k) {
+    const TrainedNet& h = heads[k];
+    Mlp3BwdArgs b = h.backward();
+    b.seed.mode = 7; b.seed.da.z = h.s.out; b.seed.da.ldz = 2; b.seed.da.n_src = n_src; b.seed.da.inv = invNg;
     rc = launch_mlp3_bwd_seed(b, st);
     if (rc) return rc;
-    const AdamTarget adam = fused ? adam_target(h.blob, h.blob_T, h.m, h.v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
-    LossFinal lf{};
-    lf.kind = 1; lf.nparts = h.n.ntiles; lf.scale = invNg; lf.parts = h.n.lossp; lf.out = h.loss;
-    rc = iql_weight_grads(h.L, h.n, N, h.grad, lf, adam, prec, false, st);
+    rc = h.finish(opt[k], h.s.lossp, h.s.ntiles, invNg, a->loss_out + (1 - k), false, st);
     if (rc) return rc;
   }
   return 0;
@@ -834,7 +857,7 @@ namespace mobody {
 struct IgdfWs {
   IqlWs iq;                // IQL's scratch, where its three entry points carve it
   MobodyMlpLayout Lsa, Lss;
-  IqlNetWs sa, ss;         // records on n and 2n-1 rows
+  OneNetScratch sa, ss;       // on n and 2n-1 rows
   float* score;            // [n]
   int32_t* kept;           // [n]
   long long total;
@@ -847,20 +870,17 @@ static int carve_igdf(const MobodyTrainDims& d, long long n, int Z, float* base,
   if (rc) return rc;
   rc = mobody_mlp_layout(d.S, Z, 1, &w.Lss);
   if (rc) return rc;
-  long long off = w.iq.total;
-  auto take = [&](long long c) { float* p = base ? base + off : nullptr; off += (c + 3) & ~3LL; return p; };
-  carve_iql_net(w.Lsa, n, 1, w.sa, take);
-  carve_iql_net(w.Lss, 2 * n - 1, 1, w.ss, take);
+  Carver take{base, w.iq.total};
+  carve_one_net(w.Lsa, n, 1, w.sa, take);
+  carve_one_net(w.Lss, 2 * n - 1, 1, w.ss, take);
   w.score = take(n); w.kept = (int32_t*)take(n);
-  w.total = off;
+  w.total = take.off;
   return 0;
 }
 
 static int igdf_check_sizes(const char* who, const MobodyTrainDims* d, long long n, int Z) {
-  int rc = check_dims(d, who);
+  int rc = family_sizes(who, d, 1);
   if (rc) return rc;
-  MB_REQUIRE(d->S >= 1 && d->A >= 1 && 2 * d->A <= 128, "%s: d.A %d: the policy's 2 A outputs must fit 128 columns (2 A > 128)", who, d->A);
-  MB_REQUIRE(d->S + d->A <= 256, "%s: S + A = %d > 256 (the widest input a packed MLP takes)", who, d->S + d->A);
   MB_REQUIRE(n >= 2 && n <= IGDF_MAX_N, "%s: n %lld outside [2, %d]", who, n, IGDF_MAX_N);
   MB_REQUIRE(Z >= 1 && Z <= IGDF_MAX_Z, "%s: Z %d outside [1, %d]", who, Z, IGDF_MAX_Z);
   return 0;
@@ -888,46 +908,35 @@ extern "C" int mobody_igdf_info(const MobodyIgdf* a, void* stream) {
   const char* who = "mobody_igdf_info";
   int rc = igdf_check(a, who);
   if (rc) return rc;
-  const bool any_grad = a->grad_sa != nullptr || a->grad_ss != nullptr, any_opt = a->m_sa || a->v_sa || a->m_ss || a->v_ss;
-  MB_REQUIRE(any_grad != any_opt, "%s: exactly one of grad_sa, grad_ss and the optimizer state m, v of both encoders must be given", who);
-  MB_REQUIRE((a->grad_sa && a->grad_ss) || (a->m_sa && a->v_sa && a->m_ss && a->v_ss), "%s: null pointer", who);
-  MB_REQUIRE(!any_opt || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
-  MB_REQUIRE(a->bump == nullptr || (any_opt && a->bump != a->t_dev), "%s: bump is incremented by the optimizer launch: it needs m, v and must not be the step word", who);
+  // one optimizer over both encoders = one step count and rate (:407)
+  const NetOpt opt[2] = {{a->grad_sa, a->m_sa, a->v_sa, a->t, a->t_dev, a->lr}, {a->grad_ss, a->m_ss, a->v_ss, a->t, a->t_dev, a->lr}};
+  rc = check_opt(who, opt, 2, "grad_sa, grad_ss", " of both encoders");
+  if (rc) return rc;
+  MB_REQUIRE(a->bump == nullptr || (a->m_sa != nullptr && a->bump != a->t_dev), "%s: bump is incremented by the optimizer launch: it needs m, v and must not be the step word", who);
   MB_REQUIRE(a->loss_out, "%s: null pointer", who);
   IgdfWs w;
   rc = carve_igdf(a->d, a->n, a->Z, a->workspace, w);
   if (rc) return rc;
   const int prec = a->precision;
-  const bool fused = any_opt, f16 = prec == PREC_F16X2;
   hipStream_t st = as_stream(stream);
   const long long n = a->n, n2 = 2 * n - 1;
   const int S = a->d.S, A = a->d.A, Z = a->Z;
   // 1. phi = encoder_sa([s | a]) on the n target rows, psi = encoder_ss(s') on [tar s' | src s'] (:424-434): one launch, with the
   // saves of the backwards.  (The reference encodes n^2 next states of which 2n-1 are distinct.)
-  const Mlp3FwdArgs f_sa = fwd_args(a->sa_blob, w.Lsa, a->state, S, a->action, A, n, w.sa.out, 0, 1.f, w.sa.x, w.sa.h1, w.sa.h2, w.sa.m1, w.sa.m2,
-                                    prec != PREC_F32 ? a->sa_blob_T : nullptr, f16 ? w.sa.e_h1 : nullptr);
-  const Mlp3FwdArgs f_ss = fwd_args(a->ss_blob, w.Lss, a->next_state, S, nullptr, 0, n2, w.ss.out, 0, 1.f, w.ss.x, w.ss.h1, w.ss.h2, w.ss.m1, w.ss.m2,
-                                    prec != PREC_F32 ? a->ss_blob_T : nullptr, f16 ? w.ss.e_h1 : nullptr);
-  rc = launch_mlp3_forward(f_ss, 1, f_sa, 1, ACT_RELU, prec, st);
+  const TrainedNet encs[2] = {{w.Lsa, w.sa, n, a->sa_blob, a->sa_blob_T, prec}, {w.Lss, w.ss, n2, a->ss_blob, a->ss_blob_T, prec}};
+  rc = launch_mlp3_forward(encs[1].forward(a->next_state, S), 1, encs[0].forward(a->state, S, a->action, A), 1, ACT_RELU, prec, st);
   if (rc) return rc;
   // 2. the loss partials and dL/dphi, dL/dpsi (:434-440)
   rc = launch_igdf_contrast(w.sa.out, w.ss.out, w.ss.out + n * Z, n, Z, Z, w.Lsa.Np3, w.sa.dz3, w.ss.dz3, w.sa.lossp, st);
   if (rc) return rc;
   // 3., 4. per encoder: the backward from dz3 in memory, then the weight gradients with (sa) the loss scalar and (fused) the Adam
-  // step; one optimizer over both encoders = one step count (:407)
-  struct Enc { const MobodyMlpLayout& L; const IqlNetWs& r; long long rows; float *blob, *blob_T, *grad, *m, *v; };
-  const Enc encs[2] = {{w.Lsa, w.sa, n, a->sa_blob, a->sa_blob_T, a->grad_sa, a->m_sa, a->v_sa},
-                       {w.Lss, w.ss, n2, a->ss_blob, a->ss_blob_T, a->grad_ss, a->m_ss, a->v_ss}};
+  // step (the last one advances `bump`)
   for (int e = 0; e < 2; ++e) {
-    const Enc& h = encs[e];
-    Mlp3BwdArgs b = bwd_args(h.L, h.blob_T, h.r.dz3, h.r.h1, h.r.h2, h.rows, h.r.dz2, h.r.dz1, h.r.dbp, h.r.m1, h.r.m2, prec, h.r.e_dz2);
-    rc = launch_mlp3_bwd(b, 1, false, st);
+    const TrainedNet& h = encs[e];
+    rc = launch_mlp3_bwd(h.backward(h.s.dz3), 1, false, st);
     if (rc) return rc;
-    AdamTarget adam = fused ? adam_target(h.blob, h.blob_T, h.m, h.v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
-    if (fused && e == 1) adam.bump = (long long*)a->bump;
-    LossFinal lf{};
-    if (e == 0) { lf.kind = 1; lf.nparts = (int)cdiv(n, IGDF_TILE); lf.scale = 1.f / ((float)n * (float)n); lf.parts = w.sa.lossp; lf.out = a->loss_out; }
-    rc = iql_weight_grads(h.L, h.r, h.rows, h.grad, lf, adam, prec, false, st);
+    rc = h.finish(opt[e], w.sa.lossp, (int)cdiv(n, IGDF_TILE), 1.f / ((float)n * (float)n), e == 0 ? a->loss_out : nullptr, false, st,
+                  e == 1 ? a->bump : nullptr);
     if (rc) return rc;
   }
   return 0;

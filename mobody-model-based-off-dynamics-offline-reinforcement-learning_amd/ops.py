@@ -230,11 +230,16 @@ def hyper(cfg):
                             prec_id(cfg.get("mfma", default_mfma())))
 
 
-def train_workspace(dims, device):
-    n = load().mobody_train_workspace(C.byref(dims))
+def _workspace(name, device, *args):
+    """The scratch tensor of the size the library's entry `name` reports for `args`."""
+    n = getattr(load(), name)(*args)
     if n < 0:
-        raise _lib.MobodyError("mobody_train_workspace: " + load().mobody_last_error().decode())
+        raise _lib.MobodyError(name + ": " + load().mobody_last_error().decode())
     return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def train_workspace(dims, device):
+    return _workspace("mobody_train_workspace", device, C.byref(dims))
 
 
 def mlp_transpose(blob, in_dim, out_dim, members, out=None, precision=0):
@@ -337,10 +342,7 @@ def td3bc_actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, st
 # IQL (iql.py): one block type for the three calls of the step (MobodyIql); `nets` = (v_func, q_funcs, target_q_funcs, policy)
 # as objects with .blob / .blob_T, `opt` the Adam state of the net the call trains (m, v given: fused form; grad: gradient form)
 def iql_workspace(dims, device):
-    n = load().mobody_iql_workspace(C.byref(dims))
-    if n < 0:
-        raise _lib.MobodyError("mobody_iql_workspace: " + load().mobody_last_error().decode())
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return _workspace("mobody_iql_workspace", device, C.byref(dims))
 
 
 def cosine_lr(lr0, k, T_max):
@@ -362,10 +364,11 @@ def _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws):
                           loss_out=ptr(loss_out), workspace=ptr(ws))
 
 
-def _iql_call(name, blk, grad, m, v, t, t_dev, lr, bump=None, log_out=None):
+def _iql_call(name, blk, grad, m, v, t, t_dev, lr, bump=None, log_out=None, extra=()):
+    """extra: the entry's own arguments between the block and the stream"""
     blk.grad, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(grad), ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
     blk.bump, blk.log_out = ptr(bump), ptr(log_out)
-    check(getattr(load(), name)(C.byref(blk), cur_stream()), name)
+    check(getattr(load(), name)(C.byref(blk), *extra, cur_stream()), name)
 
 
 def iql_value(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0,
@@ -391,10 +394,18 @@ def iql_actor(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=
 # (sa_classifier, sas_classifier) as objects with .blob / .blob_T; `batch` = (state, action, next_state, reward, ...) of [src | tar]
 def dara_workspace(dims, device):
     """Floats of the DARA step's scratch: iql_workspace's (the same tensor serves the IQL calls) + the classifier's."""
-    n = load().mobody_dara_workspace(C.byref(dims))
-    if n < 0:
-        raise _lib.MobodyError("mobody_dara_workspace: " + load().mobody_last_error().decode())
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return _workspace("mobody_dara_workspace", device, C.byref(dims))
+
+
+def _pair_opt(blk, second, grads, opts, t, t_dev, lr, loss_out):
+    """The gradient blobs or the Adam state of a block that trains two nets, `sa` and `second`, under one step count and rate."""
+    for k, net in enumerate(("sa", second)):
+        if grads is not None:
+            setattr(blk, "grad_" + net, ptr(grads[k]))
+        if opts is not None:
+            setattr(blk, "m_" + net, ptr(opts[k][0]))
+            setattr(blk, "v_" + net, ptr(opts[k][1]))
+    blk.t, blk.t_dev, blk.lr, blk.loss_out = int(t), ptr(t_dev), float(lr), ptr(loss_out)
 
 
 def _dara_block(dims, precision, heads, batch, ws, n_src):
@@ -413,11 +424,7 @@ def dara_classifier(dims, precision, heads, batch, noise_std, loss_out, ws, n_sr
     blk = _dara_block(dims, precision, heads, batch, ws, n_src)
     blk.noise_std, blk.noise_sas, blk.noise_sa = float(noise_std), ptr(noise_sas), ptr(noise_sa)
     blk.seed, blk.call, blk.call_dev, blk.call_offset = int(seed) & 0xFFFFFFFF, int(call) & 0xFFFFFFFF, ptr(call_dev), int(call_offset)
-    if grads is not None:
-        blk.grad_sa, blk.grad_sas = ptr(grads[0]), ptr(grads[1])
-    if opts is not None:
-        (blk.m_sa, blk.v_sa), (blk.m_sas, blk.v_sas) = (ptr(opts[0][0]), ptr(opts[0][1])), (ptr(opts[1][0]), ptr(opts[1][1]))
-    blk.t, blk.t_dev, blk.lr, blk.loss_out = int(t), ptr(t_dev), float(lr), ptr(loss_out)
+    _pair_opt(blk, "sas", grads, opts, t, t_dev, lr, loss_out)
     check(load().mobody_dara_classifier(C.byref(blk), cur_stream()), "mobody_dara_classifier")
 
 
@@ -433,10 +440,7 @@ def dara_relabel(dims, precision, heads, batch, eta, ws, n_src=0, delta_out=None
 # row-weighted critic.  `encs` = (encoder_sa, encoder_ss) as objects with .blob / .blob_T and out_dim Z
 def igdf_workspace(dims, n, Z, device):
     """Floats of the IGDF step's scratch: iql_workspace's (the same tensor serves the IQL calls) + the encoders' on n / 2n-1 rows."""
-    c = load().mobody_igdf_workspace(C.byref(dims), int(n), int(Z))
-    if c < 0:
-        raise _lib.MobodyError("mobody_igdf_workspace: " + load().mobody_last_error().decode())
-    return torch.empty(c, dtype=torch.float32, device=device)
+    return _workspace("mobody_igdf_workspace", device, C.byref(dims), int(n), int(Z))
 
 
 def igdf_contrast(phi, psi_tar, psi_src, Z):
@@ -475,11 +479,8 @@ def igdf_info(dims, precision, encs, n, Z, batch, loss_out, ws, grads=None, opts
     loss_out[1].  grads = (grad_sa, grad_ss): the gradient form; opts = ((m_sa, v_sa), (m_ss, v_ss)): ONE fused Adam over both
     encoders at step t (or t_dev[0]) and rate lr; bump: a device word the last optimizer launch increments."""
     blk = _igdf_block(dims, precision, encs, n, Z, batch, ws)
-    if grads is not None:
-        blk.grad_sa, blk.grad_ss = ptr(grads[0]), ptr(grads[1])
-    if opts is not None:
-        (blk.m_sa, blk.v_sa), (blk.m_ss, blk.v_ss) = (ptr(opts[0][0]), ptr(opts[0][1])), (ptr(opts[1][0]), ptr(opts[1][1]))
-    blk.t, blk.t_dev, blk.lr, blk.bump, blk.loss_out = int(t), ptr(t_dev), float(lr), ptr(bump), ptr(loss_out)
+    _pair_opt(blk, "ss", grads, opts, t, t_dev, lr, loss_out)
+    blk.bump = ptr(bump)
     check(load().mobody_igdf_info(C.byref(blk), cur_stream()), "mobody_igdf_info")
 
 
@@ -497,10 +498,8 @@ def igdf_filter(dims, precision, encs, n, k, Z, importance_weight, staged, out, 
 def igdf_critic(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws, grad=None, m=None, v=None, t=0, t_dev=None, lr=0.0,
                 bump=None, row_weight=None):
     """iql_critic with the loss mean(w (q1 - y)^2) + mean(w (q2 - y)^2) (igdf.py:468-479); row_weight None: iql_critic."""
-    blk = _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws)
-    blk.grad, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(grad), ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
-    blk.bump = ptr(bump)
-    check(load().mobody_igdf_critic(C.byref(blk), ptr(row_weight), cur_stream()), "mobody_igdf_critic")
+    _iql_call("mobody_igdf_critic", _iql_block(dims, hyp, lam, temp, T_max, nets, batch, adv, loss_out, ws), grad, m, v, t, t_dev, lr,
+              bump=bump, extra=(ptr(row_weight),))
 
 
 def value_loss_grad(qt, v, n_global):
@@ -732,10 +731,7 @@ def pretrain_transpose(blob, S, A, out=None, precision=0):
 
 
 def pretrain_workspace(S, A, b, device):
-    n = load().mobody_pretrain_workspace(S, A, b)
-    if n < 0:
-        raise _lib.MobodyError("mobody_pretrain_workspace: " + load().mobody_last_error().decode())
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return _workspace("mobody_pretrain_workspace", device, S, A, b)
 
 
 def pretrain_gather(state, action, next_state, reward, idx, start, b, out=None, start_dev=None):
@@ -805,10 +801,7 @@ def pretrain_mopo_transpose(blob, S, A, out=None, precision=0):
 
 
 def pretrain_mopo_workspace(S, A, b, device):
-    n = load().mobody_pretrain_mopo_workspace(S, A, b)
-    if n < 0:
-        raise _lib.MobodyError("mobody_pretrain_mopo_workspace: " + load().mobody_last_error().decode())
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return _workspace("mobody_pretrain_mopo_workspace", device, S, A, b)
 
 
 def pretrain_mopo_grads(S, A, b, use_trg, encoder_loss_coef, blob, blob_T, xenc, act, rew, grad, loss_out, ws, noise=None,
