@@ -211,7 +211,8 @@ def block(cls, **fields):
 
 
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
-                                             MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae)}
+                                             MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyEnsStep, MobodyEnsRollout,
+                                             MobodyEnsEval, MobodyEnsReplay)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}

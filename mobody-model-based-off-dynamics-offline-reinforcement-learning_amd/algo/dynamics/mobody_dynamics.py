@@ -122,13 +122,19 @@ class MOBODYEnsembleDynamics(object):
         need = 7 * B * (m.obs_dim + 1)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty(max(need, 1), dtype=torch.float32, device=m.device)
-        return ops.dyn_step(m.packed(), m.obs_dim, m.action_dim, self._task_id, obs, action, noise=noise,
-                            elite_idx=elite_idx, alive=alive, elites=m.elites_host(),
-                            seed=(self.seed + seed_offset + dp.rank_salt()) & 0xFFFFFFFF, call=call, call_dev=call_dev,
-                            penalty_coef=float(self._penalty_coef or 0.0),
-                            use_penalty=bool(use_penalty), use_trg=bool(use_trg), want_mean=want_mean,
-                            workspace=self._ws, planes=m.planes() if self.precision else None, precision=self.precision,
-                            mopo=m.packed_mopo() if getattr(m, "mopo", False) else None, uncertainty_mode=self._unc_id)
+        kw = self._model_kw(seed_offset)
+        return ops.dyn_step(kw.pop("dyn_blob"), obs=obs, act=action, noise=noise, elite_idx=elite_idx, alive=alive, call=call,
+                            call_dev=call_dev, penalty_coef=float(self._penalty_coef or 0.0), use_penalty=bool(use_penalty),
+                            use_trg=bool(use_trg), want_mean=want_mean, workspace=self._ws, planes=kw.pop("dyn_planes"), **kw)
+
+    def _model_kw(self, seed_offset=0):
+        """The model-side arguments of ops.rollout / ens_evaluate / ens_replay by keyword (ops.dyn_step calls the first two
+        `blob` and `planes`); the seed is the rank-salted one of the stream `seed_offset`."""
+        m = self.model
+        return dict(dyn_blob=m.packed(), dyn_planes=m.planes() if self.precision else None, S=m.obs_dim, A=m.action_dim,
+                    task_id=self._task_id, elites=m.elites_host(), seed=(self.seed + int(seed_offset) + dp.rank_salt()) & 0xFFFFFFFF,
+                    precision=self.precision, mopo=m.packed_mopo() if getattr(m, "mopo", False) else None,
+                    uncertainty_mode=self._unc_id)
 
     @torch.no_grad()
     def step(self, obs, action, use_penalty=True, use_trg=True):
@@ -156,23 +162,20 @@ class MOBODYEnsembleDynamics(object):
         B, H, chunk = obs.shape[0], int(horizon), int(chunk)
         if H < 0 or chunk < 0:
             raise ValueError(f"evaluate_policy: horizon {H} / chunk {chunk} must be >= 0")
-        S, A = m.obs_dim, m.action_dim
+        S = m.obs_dim
         if self._eval is None or self._eval[0] != B:
             self._eval = (B, ops.eval_state(B, S, m.device), None, torch.zeros(1, dtype=torch.int64, device=m.device))
             self._eval_graph = None
         _, st, ws, ctr = self._eval
-        mopo = m.packed_mopo() if getattr(m, "mopo", False) else None
-        planes = m.planes() if self.precision else None
-        seed = (self.seed + int(seed_offset) + dp.rank_salt()) & 0xFFFFFFFF
+        kw = self._model_kw(seed_offset)
+        mopo, planes, seed = kw["mopo"], kw["dyn_planes"], kw["seed"]
         call0 = self._eval_calls + 1
         self._eval_calls += H
 
         def run(h, call, resume, call_dev=None):
-            return ops.ens_evaluate(m.packed(), actor_net.blob, S, A, self._task_id, actor_net.max_action,
-                                    None if resume else obs, h, list(m.elites_host()), seed, call & 0xFFFFFFFF, st,
-                                    use_trg=use_trg, discount=discount, resume=resume, ws=ws, dyn_planes=planes,
-                                    actor_blob_T=actor_net.blob_T, precision=self.precision, mopo=mopo,
-                                    uncertainty_mode=self._unc_id, call_dev=call_dev)
+            return ops.ens_evaluate(actor_blob=actor_net.blob, max_action=actor_net.max_action, init_obs=None if resume else obs,
+                                    H=h, call0=call & 0xFFFFFFFF, state=st, use_trg=use_trg, discount=discount, resume=resume,
+                                    ws=ws, actor_blob_T=actor_net.blob_T, call_dev=call_dev, **kw)
 
         if chunk == 0 or H <= chunk:
             ws = run(H, call0, False)
@@ -256,11 +259,8 @@ class MOBODYEnsembleDynamics(object):
         key, st, ws = self._replay
         call0 = self._replay_calls + 1
         self._replay_calls += H
-        ws = ops.ens_replay(m.packed(), S, A, self._task_id, buffer._fields(), n, rows, H, list(m.elites_host()),
-                            (self.seed + int(seed_offset) + dp.rank_salt()) & 0xFFFFFFFF, call0 & 0xFFFFFFFF, st,
-                            reset_every=int(reset_every), use_trg=use_trg, ws=ws, dyn_planes=m.planes() if self.precision else None,
-                            precision=self.precision, mopo=m.packed_mopo() if getattr(m, "mopo", False) else None,
-                            uncertainty_mode=self._unc_id)
+        ws = ops.ens_replay(data=buffer._fields(), data_rows=n, row0=rows, H=H, call0=call0 & 0xFFFFFFFF, state=st,
+                            reset_every=int(reset_every), use_trg=use_trg, ws=ws, **self._model_kw(seed_offset))
         self._replay = (key, st, ws)
         out = {k: st[k].clone() for k in ("obs_err", "rew_err", "penalty")}
         out["term_model"] = st["term_model"] != 0

@@ -456,14 +456,12 @@ class MOBODY(object):
         obs = init_obss.contiguous()
         B = obs.shape[0]
         m.inference()
-        self._roll_ws = ops.rollout(m.packed(), self.policy.blob, self.S, self.A, dyn._task_id, self.policy.max_action, obs,
-                                    rollout_length, list(m.elites_host()),
-                                    (dyn.seed + dp.rank_salt()) & 0xFFFFFFFF, dyn._calls + 1, float(dyn._penalty_coef or 0.0),
-                                    use_trg, True, self.config["env_filter"], self.config["filter_bad_rollout"],   # quirk Q1
-                                    fb._fields(), fb.max_size, fb.ptr_size, getattr(self, "_roll_ws", None),
-                                    dyn_planes=m.planes() if dyn.precision else None, actor_blob_T=self.policy.blob_T,
-                                    precision=dyn.precision, mopo=m.packed_mopo() if getattr(m, "mopo", False) else None,
-                                    uncertainty_mode=dyn._unc_id)
+        self._roll_ws = ops.rollout(actor_blob=self.policy.blob, max_action=self.policy.max_action, init_obs=obs, H=rollout_length,
+                                    call0=dyn._calls + 1, penalty_coef=float(dyn._penalty_coef or 0.0),
+                                    use_penalty=use_trg, use_trg=True,                                             # quirk Q1
+                                    env_filter=self.config["env_filter"], filter_bad_rollout=self.config["filter_bad_rollout"],
+                                    buf=fb._fields(), cap=fb.max_size, ptr_size=fb.ptr_size, ws=getattr(self, "_roll_ws", None),
+                                    actor_blob_T=self.policy.blob_T, **dyn._model_kw())
         dyn._calls += rollout_length
         fb._pull()
         return B * rollout_length

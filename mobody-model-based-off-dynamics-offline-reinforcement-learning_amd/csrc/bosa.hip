@@ -231,8 +231,7 @@ static int bosa_nets(const char* who, const MobodyBosaVae* a, BosaNets& n) {
 
 static void bosa_carve(const BosaNets& n, long long B, int ns, float* base, BosaWs& w) {
   const long long E = n.E, nB = (long long)ns * B, Hp = n.enc.Hp;
-  long long off = 0;
-  auto take = [&](long long f) { float* p = base ? base + off : nullptr; off += (f + 3) / 4 * 4; return p; };
+  Carver take{base};
   w.enc_x = take(B * n.enc.Kp1);
   w.enc_h1 = take(E * B * Hp); w.enc_h2 = take(E * B * Hp);
   w.enc_out = take(E * B * 2 * n.Lz);
@@ -247,7 +246,7 @@ static void bosa_carve(const BosaNets& n, long long B, int ns, float* base, Bosa
   w.klp = take(cdiv(E * B * n.Lz, 256));
   w.recp = take(cdiv(E * B * n.D, 256));
   w.pq = take(2 * E * nB);
-  w.floats = off;
+  w.floats = take.off;
 }
 
 static int bosa_common(const char* who, const MobodyBosaVae* a, BosaNets& n) {

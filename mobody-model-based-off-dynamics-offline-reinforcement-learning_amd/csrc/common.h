@@ -81,7 +81,14 @@ int launch_ring_append(const MobodyBufferView& ring, long long cap, long long* p
                        const uint8_t* keep, long long M, int32_t* scan_ws, hipStream_t st);
 __host__ __device__ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// return accounting of mobody_ens_evaluate (trajectory_return.hip): the caller's row state, which dyn_step_impl's last launch
+// hands a workspace out front to back, every piece rounded up to 4 floats; base == null: the sizes alone (no device is touched)
+struct Carver {
+  float* base;
+  long long off = 0;
+  float* operator()(long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; }
+};
+
+// return accounting of mobody_ens_evaluate (trajectory_return.hip): the caller's row state, which the step's tail launch
 // updates in k_dyn_finalize's place (the step's obs / alive ARE obs_state / alive), and the two launches
 struct DynEvalHook {
   float* obs_state;
@@ -95,7 +102,7 @@ int launch_eval_account(const float* r_mu, const float* penalty, const float* ne
 int launch_eval_init(const float* init_obs, const DynEvalHook& h, long long B, int S, hipStream_t st);
 
 // open-loop error accounting of mobody_ens_replay (trajectory_truth.hip): the caller's row state and the tables' rows of
-// window step t, which dyn_step_impl's last launch fills in k_dyn_finalize's place (the step's obs / act ARE obs_state /
+// window step t, which the step's tail launch fills in k_dyn_finalize's place (the step's obs / act ARE obs_state /
 // act_state), and the two launches
 struct DynReplayHook {
   const MobodyBufferView* data;

@@ -125,10 +125,9 @@ int launch_dara_penalty(const float* z_sas, const float* z_sa, long long n, floa
 // ---- generic MLP gradient (dz3 + saved activations -> gradient blob) ----
 // its scratch: the backward half of a net's record (the caller owns x, h1, h2)
 static NetScratch carve_bwd(const MobodyMlpLayout& L, long long rows, float* base, long long& total) {
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   const NetScratch s = carve_net(L, rows, false, L.Np3, take);
-  total = off;
+  total = take.off;
   return s;
 }
 

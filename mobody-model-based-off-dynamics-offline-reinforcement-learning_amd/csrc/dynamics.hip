@@ -394,92 +394,168 @@ extern "C" int mobody_dyn_forward(const float* dyn_blob, const float* dyn_planes
   return launch_dyn_fwd(dyn_blob, L, obs, act, B, use_trg, mean, dyn_planes, precision, as_stream(stream));
 }
 
-extern "C" int64_t mobody_dyn_step_workspace(int S, int A, int64_t B) {
-  (void)A;
-  return (int64_t)NENS * B * S + (int64_t)NENS * B;    // ensemble means + per-member reward means
-}
+// ---- the ensemble step: one host path for the single step and the three trajectory drivers --------------------------
+namespace mobody {
 
-// a.mopo_blob != null: the MOPO ablation (config['mopo'], mobody_module.py:114-118,218-219,251-254,264-266,288-289) --
+// floats of the step's own workspace: the ensemble means [E][B][S] and the per-member reward means [E][B]
+static long long dyn_step_floats(int S, long long B) { return (long long)NENS * B * S + (long long)NENS * B; }
+
+#define MB_NONNULL(who, blk, f) MB_REQUIRE((blk).f != nullptr, "%s: null pointer " #f, who)
+
+// the rollout's bookkeeping, formed in the sample kernel (the last four fields of DynSampleArgs); every part optional
+struct SampleBook { uint8_t *keep, *alive_out; float env_filter; int use_filter; };
+
+// The model a call runs: what the four argument blocks share, read out of a block once (MobodyEnsStep's `call` is its call0).
+// mopo_blob != null: the MOPO ablation (config['mopo'], mobody_module.py:114-118,218-219,251-254,264-266,288-289) --
 // mean[e] = obs + MLP_e([obs, act]) with the 7-member Swish MLP (S+A -> 256 -> 256 -> S) za_src1..3 packed as
 // mobody_mlp_layout(S + A, S, 7); encoders and decoder are bypassed, forward_trg == forward_src.  Everything after the means
 // (std, sample, reward head, penalty, termination) is the same code.
-// `who`: the public entry point named in error texts.  keep / alive_out / env_filter / use_filter: the rollout's bookkeeping.
-// `eval`: the last launch is k_eval_account on the caller's row state, not k_dyn_finalize (a.reward / a.raw_reward unused).
-// `replay`: likewise k_replay_account (trajectory_truth.hip), the errors of one window step against recorded data.
-static int dyn_step_impl(const char* who, const MobodyEnsStep& a, uint8_t* keep, uint8_t* alive_out, float env_filter,
-                         int use_filter, void* stream, const DynEvalHook* eval = nullptr, const DynReplayHook* replay = nullptr) {
-  const int S = a.S, A = a.A, precision = a.precision;
-  const int64_t B = a.B;
-  MobodyDynLayout L;
-  int rc = mobody_dyn_layout(S, A, &L);
-  if (rc) return rc;
-  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
-             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
-  MB_REQUIRE(B >= 0, "%s: B < 0", who);
-  if (B == 0) return 0;                      // empty batch: nothing to do (pointers may be null)
-  MB_REQUIRE(a.dyn_blob && a.obs && a.act && a.next_obs && (a.reward || eval || replay) && a.terminal && a.penalty && a.workspace, "%s: null pointer", who);
-  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d", who, a.task);
-  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
-  MB_REQUIRE(a.elite_idx != nullptr || (a.elites != nullptr && a.n_elites >= 1 && a.n_elites <= NENS),
-             "%s: need elite_idx or 1..7 elites", who);
-  hipStream_t st = as_stream(stream);
-  float* mean = a.mean_out ? a.mean_out : a.workspace;
-  float* r_mu = a.workspace + (int64_t)NENS * B * S;
-  rc = check_precision(who, precision, a.dyn_planes != nullptr);
-  if (rc) return rc;
-  if (a.mopo_blob != nullptr) {
-    MobodyMlpLayout ML;
-    rc = mobody_mlp_layout(S + A, S, NENS, &ML);
+struct EnsModel {
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T;
+  int precision, S, A, task;
+  const int32_t* elites; int n_elites;
+  uint32_t seed, call0; const int64_t* call_dev;
+  int use_trg, uncertainty_mode;
+  MobodyDynLayout L; MobodyMlpLayout ML;       // set by check(): the ensemble's layers and, for the mopo model, its MLP
+
+  template <class Block>
+  static EnsModel of(const Block& a, uint32_t call0) {
+    return {a.dyn_blob, a.dyn_planes, a.mopo_blob, a.mopo_blob_T, a.precision, a.S, a.A, a.task, a.elites,
+            a.n_elites, a.seed, call0, a.call_dev, a.use_trg, a.uncertainty_mode};
+  }
+
+  // the rules an empty batch is held to as well
+  int check_batch(const char* who, int64_t B) const {
+    MB_REQUIRE(uncertainty_mode >= MOBODY_UNC_PAIRWISE && uncertainty_mode <= MOBODY_UNC_ENS_STD,
+               "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, uncertainty_mode);
+    MB_REQUIRE(B >= 0, "%s: B < 0", who);
+    return 0;
+  }
+
+  // The range and pointer rules of a batch with rows, every refusal naming its field; then the layouts.  `who`: the public
+  // entry point named in error texts.  need_elites false: the single step was handed per-row picks (elite_idx).
+  int check(const char* who, bool need_elites = true) {
+    MB_REQUIRE(dyn_blob, "%s: null pointer dyn_blob", who);
+    MB_REQUIRE(!need_elites || elites, "%s: null pointer elites", who);
+    MB_REQUIRE(!need_elites || (n_elites >= 1 && n_elites <= NENS), "%s: n_elites %d outside 1..7", who, n_elites);
+    int rc = check_precision(who, precision, dyn_planes != nullptr);
     if (rc) return rc;
-    MB_REQUIRE(precision == PREC_F32 || a.mopo_blob_T != nullptr, "%s: the split-precision modes need the T blob of the MLP", who);
-    Mlp3FwdArgs f = fwd_net(a.mopo_blob, ML, B);
-    fwd_set_src(f, 0, a.obs, S, S);
-    fwd_set_src(f, 1, a.act, A, A);
-    fwd_set_out(f, mean, 0, 1.f, a.obs, S);
-    if (precision != PREC_F32) fwd_set_planes(f, a.mopo_blob_T, ML);
-    rc = launch_mlp3_forward(f, NENS, ACT_SWISH, precision, st);
-  } else {
-    rc = launch_dyn_fwd(a.dyn_blob, L, a.obs, a.act, B, a.use_trg, mean, a.dyn_planes, precision, st);
+    MB_REQUIRE(precision == PREC_F32 || !mopo_blob || mopo_blob_T, "%s: the split-precision modes need the T blob of the MLP (mopo_blob_T)", who);
+    MB_REQUIRE(task >= MOBODY_TERM_NEVER && task <= MOBODY_TERM_PEN, "%s: unknown termination id %d (task)", who, task);
+    MB_REQUIRE(task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26 (task)", who);
+    rc = mobody_dyn_layout(S, A, &L);
+    if (rc || !mopo_blob) return rc;
+    return mobody_mlp_layout(S + A, S, NENS, &ML);
   }
-  if (rc) return rc;
 
-  DynSampleArgs sa{};
-  sa.mean = mean; sa.noise = a.noise; sa.elite_idx = a.elite_idx; sa.alive = a.alive;
-  for (int k = 0; k < NENS; ++k) sa.elites[k] = (a.elites && k < a.n_elites) ? a.elites[k] : 0;
-  sa.n_elites = a.n_elites; sa.seed = a.seed; sa.call = a.call; sa.call_dev = (const long long*)a.call_dev; sa.B = B; sa.S = S; sa.task = a.task;
-  sa.next_obs = a.next_obs; sa.penalty = a.penalty; sa.terminal = a.terminal;
-  sa.keep = keep; sa.alive_out = alive_out; sa.env_filter = env_filter; sa.use_filter = use_filter;
-  const int rpb = 256 / S < 64 ? 256 / S : 64;         // whole rows per workgroup (S <= 256 is checked by the layout)
-  const dim3 grid((unsigned)cdiv(B, rpb));
-  if (a.uncertainty_mode == MOBODY_UNC_ALEATORIC) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ALEATORIC>, grid, dim3(256), 0, st, sa, rpb);
-  else if (a.uncertainty_mode == MOBODY_UNC_ENS_STD) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ENS_STD>, grid, dim3(256), 0, st, sa, rpb);
-  else hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_PAIRWISE>, grid, dim3(256), 0, st, sa, rpb);
-  MB_LAUNCH_OK("k_dyn_sample");
-
-  // reward head on [s, a, s'] shared by the 7 members  (mobody_dynamics.py:235)
-  Mlp3FwdArgs m = fwd_reward_head(a.dyn_blob, L, precision != PREC_F32 ? a.dyn_planes : nullptr, B);
-  fwd_set_src(m, 0, a.obs, S, S);
-  fwd_set_src(m, 1, a.act, A, A);
-  fwd_set_src(m, 2, a.next_obs, S, S);
-  fwd_set_out(m, r_mu, 0, 1.f);
-  rc = launch_mlp3_forward(m, NENS, ACT_SWISH, precision, st);
-  if (rc) return rc;
-
-  if (eval != nullptr) {
-    return launch_eval_account(r_mu, a.penalty, a.next_obs, alive_out, *eval, B, S, st);
+  // The MobodyEnsStep of trajectory step t on the rows (obs, act): call id call0 + t (uint32 wrap; the kernel adds
+  // call_dev[0]).  The caller adds its outputs and workspace (the single step also noise, elite_idx and its penalty form).
+  MobodyEnsStep step(int t, const float* obs, const float* act, int64_t B, const uint8_t* alive) const {
+    MobodyEnsStep s{};
+    s.dyn_blob = dyn_blob; s.dyn_planes = dyn_planes; s.mopo_blob = mopo_blob; s.mopo_blob_T = mopo_blob_T;
+    s.precision = precision; s.S = S; s.A = A; s.task = task; s.obs = obs; s.act = act; s.B = B; s.alive = alive;
+    s.elites = elites; s.n_elites = n_elites; s.seed = seed; s.call = call0 + (uint32_t)t; s.call_dev = call_dev;
+    s.use_trg = use_trg; s.uncertainty_mode = uncertainty_mode;
+    return s;
   }
-  if (replay != nullptr) {
-    return launch_replay_account(r_mu, a.penalty, a.next_obs, a.terminal, *replay, B, S, A, st);
+
+  // The launches of one step on checked arguments: member forward (or the mopo MLP, the observation added in its output
+  // stage) -> k_dyn_sample<MODE> -> reward head -> tail(r_mu), the launch the step ends in.
+  template <class Tail>
+  int launch(const MobodyEnsStep& a, const SampleBook& bk, hipStream_t st, Tail&& tail) const {
+    const int64_t B = a.B;
+    float* mean = a.mean_out ? a.mean_out : a.workspace;
+    float* r_mu = a.workspace + (int64_t)NENS * B * S;
+    int rc;
+    if (mopo_blob != nullptr) {
+      Mlp3FwdArgs f = fwd_net(mopo_blob, ML, B);
+      fwd_set_src(f, 0, a.obs, S, S);
+      fwd_set_src(f, 1, a.act, A, A);
+      fwd_set_out(f, mean, 0, 1.f, a.obs, S);
+      if (precision != PREC_F32) fwd_set_planes(f, mopo_blob_T, ML);
+      rc = launch_mlp3_forward(f, NENS, ACT_SWISH, precision, st);
+    } else {
+      rc = launch_dyn_fwd(dyn_blob, L, a.obs, a.act, B, use_trg, mean, dyn_planes, precision, st);
+    }
+    if (rc) return rc;
+
+    DynSampleArgs sa{};
+    sa.mean = mean; sa.noise = a.noise; sa.elite_idx = a.elite_idx; sa.alive = a.alive;
+    for (int k = 0; k < NENS; ++k) sa.elites[k] = (elites && k < n_elites) ? elites[k] : 0;
+    sa.n_elites = n_elites; sa.seed = seed; sa.call = a.call; sa.call_dev = (const long long*)call_dev; sa.B = B; sa.S = S; sa.task = task;
+    sa.next_obs = a.next_obs; sa.penalty = a.penalty; sa.terminal = a.terminal;
+    sa.keep = bk.keep; sa.alive_out = bk.alive_out; sa.env_filter = bk.env_filter; sa.use_filter = bk.use_filter;
+    const int rpb = 256 / S < 64 ? 256 / S : 64;         // whole rows per workgroup (S <= 256 is checked by the layout)
+    const dim3 grid((unsigned)cdiv(B, rpb));
+    if (uncertainty_mode == MOBODY_UNC_ALEATORIC) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ALEATORIC>, grid, dim3(256), 0, st, sa, rpb);
+    else if (uncertainty_mode == MOBODY_UNC_ENS_STD) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ENS_STD>, grid, dim3(256), 0, st, sa, rpb);
+    else hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_PAIRWISE>, grid, dim3(256), 0, st, sa, rpb);
+    MB_LAUNCH_OK("k_dyn_sample");
+
+    // reward head on [s, a, s'] shared by the 7 members  (mobody_dynamics.py:235)
+    Mlp3FwdArgs m = fwd_reward_head(dyn_blob, L, precision != PREC_F32 ? dyn_planes : nullptr, B);
+    fwd_set_src(m, 0, a.obs, S, S);
+    fwd_set_src(m, 1, a.act, A, A);
+    fwd_set_src(m, 2, a.next_obs, S, S);
+    fwd_set_out(m, r_mu, 0, 1.f);
+    rc = launch_mlp3_forward(m, NENS, ACT_SWISH, precision, st);
+    return rc ? rc : tail(r_mu);
   }
-  DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
-  hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, fa);
+};
+
+// the single step's and the rollout's tail: reward = the members' mean reward, less the penalty when the step asks for it
+static int launch_finalize(const float* r_mu, const MobodyEnsStep& a, hipStream_t st) {
+  DynFinalArgs fa{r_mu, a.penalty, a.reward, a.raw_reward, a.B, (a.penalty_coef != 0.f && a.use_penalty) ? a.penalty_coef : 0.f};
+  hipLaunchKernelGGL(k_dyn_finalize, dim3((unsigned)cdiv(a.B, 256)), dim3(256), 0, st, fa);
   MB_LAUNCH_OK("k_dyn_finalize");
   return 0;
 }
 
+// mobody_ens_step and its two positional forms, which differ in `who` alone
+static int ens_step(const char* who, const MobodyEnsStep& a, void* stream) {
+  EnsModel m = EnsModel::of(a, a.call);
+  int rc = mobody_dyn_layout(a.S, a.A, &m.L);         // the single step refuses a bad (S, A) for an empty batch too
+  if (rc) return rc;
+  rc = m.check_batch(who, a.B);
+  if (rc || a.B == 0) return rc;                      // empty batch: nothing to do (pointers may be null)
+  rc = m.check(who, a.elite_idx == nullptr);
+  if (rc) return rc;
+  MB_NONNULL(who, a, obs); MB_NONNULL(who, a, act); MB_NONNULL(who, a, next_obs); MB_NONNULL(who, a, reward);
+  MB_NONNULL(who, a, terminal); MB_NONNULL(who, a, penalty); MB_NONNULL(who, a, workspace);
+  hipStream_t st = as_stream(stream);
+  return m.launch(a, SampleBook{}, st, [&](const float* r_mu) { return launch_finalize(r_mu, a, st); });
+}
+
+// a = pi(s) of the rollout and of the evaluation: the actor's arguments checked, then its forward
+struct Policy {
+  const float *blob, *blob_T;
+  float max_action;
+  MobodyMlpLayout La;
+
+  int check(const char* who, const EnsModel& m) {
+    MB_REQUIRE(blob, "%s: null pointer actor_blob", who);
+    MB_REQUIRE(m.precision == PREC_F32 || blob_T, "%s: the split-precision modes need the actor's T blob (actor_blob_T)", who);
+    return mobody_mlp_layout(m.S, m.A, 1, &La);
+  }
+  int launch(const float* obs, float* act, int64_t B, int precision, hipStream_t st) const {
+    Mlp3FwdArgs p = fwd_net(blob, La, B);
+    fwd_set_src(p, 0, obs, La.in_dim, La.in_dim);
+    fwd_set_out(p, act, 1, max_action);
+    if (precision != PREC_F32) fwd_set_planes(p, blob_T, La);
+    return launch_mlp3_forward(p, 1, ACT_RELU, precision, st);
+  }
+};
+
+}  // namespace mobody
+
+extern "C" int64_t mobody_dyn_step_workspace(int S, int A, int64_t B) {
+  (void)A;
+  return dyn_step_floats(S, B);
+}
+
 extern "C" int mobody_ens_step(const MobodyEnsStep* a, void* stream) {
   MB_BLOCK("mobody_ens_step", a, MobodyEnsStep);
-  return dyn_step_impl("mobody_ens_step", *a, nullptr, nullptr, 0.f, 0, stream);
+  return ens_step("mobody_ens_step", *a, stream);
 }
 
 extern "C" int mobody_dyn_step(const float* dyn_blob, const float* dyn_planes, int precision, int S, int A, int task,
@@ -489,14 +565,13 @@ extern "C" int mobody_dyn_step(const float* dyn_blob, const float* dyn_planes, i
                                float penalty_coef, int use_penalty,
                                int use_trg, float* next_obs, float* reward, uint8_t* terminal, float* penalty,
                                float* raw_reward, float* mean_out, float* workspace, void* stream) {
-  MobodyEnsStep a{};
-  a.dyn_blob = dyn_blob; a.dyn_planes = dyn_planes; a.precision = precision; a.S = S; a.A = A; a.task = task;
-  a.obs = obs; a.act = act; a.B = B; a.noise = noise; a.elite_idx = elite_idx; a.alive = alive; a.elites = elites;
-  a.n_elites = n_elites; a.seed = seed; a.call = call; a.call_dev = call_dev; a.penalty_coef = penalty_coef;
-  a.use_penalty = use_penalty; a.use_trg = use_trg; a.uncertainty_mode = MOBODY_UNC_PAIRWISE;
+  const EnsModel m{dyn_blob, dyn_planes, nullptr, nullptr, precision, S, A, task, elites, n_elites, seed, call, call_dev, use_trg,
+                   MOBODY_UNC_PAIRWISE};
+  MobodyEnsStep a = m.step(0, obs, act, B, alive);
+  a.noise = noise; a.elite_idx = elite_idx; a.penalty_coef = penalty_coef; a.use_penalty = use_penalty;
   a.next_obs = next_obs; a.reward = reward; a.terminal = terminal; a.penalty = penalty; a.raw_reward = raw_reward;
   a.mean_out = mean_out; a.workspace = workspace;
-  return dyn_step_impl("mobody_dyn_step", a, nullptr, nullptr, 0.f, 0, stream);
+  return ens_step("mobody_dyn_step", a, stream);
 }
 
 extern "C" int mobody_mopo_step(const float* dyn_blob, const float* dyn_planes, const float* mopo_blob, const float* mopo_blob_T,
@@ -506,15 +581,13 @@ extern "C" int mobody_mopo_step(const float* dyn_blob, const float* dyn_planes, 
                                 float* reward, uint8_t* terminal, float* penalty, float* raw_reward, float* mean_out,
                                 float* workspace, void* stream) {
   MB_REQUIRE(B == 0 || mopo_blob != nullptr, "mobody_mopo_step: null MLP blob");
-  MobodyEnsStep a{};
-  a.dyn_blob = dyn_blob; a.dyn_planes = dyn_planes; a.mopo_blob = mopo_blob; a.mopo_blob_T = mopo_blob_T;
-  a.precision = precision; a.S = S; a.A = A; a.task = task;
-  a.obs = obs; a.act = act; a.B = B; a.noise = noise; a.elite_idx = elite_idx; a.alive = alive; a.elites = elites;
-  a.n_elites = n_elites; a.seed = seed; a.call = call; a.penalty_coef = penalty_coef;
-  a.use_penalty = use_penalty; a.use_trg = 1; a.uncertainty_mode = MOBODY_UNC_PAIRWISE;
+  const EnsModel m{dyn_blob, dyn_planes, mopo_blob, mopo_blob_T, precision, S, A, task, elites, n_elites, seed, call, nullptr, 1,
+                   MOBODY_UNC_PAIRWISE};
+  MobodyEnsStep a = m.step(0, obs, act, B, alive);
+  a.noise = noise; a.elite_idx = elite_idx; a.penalty_coef = penalty_coef; a.use_penalty = use_penalty;
   a.next_obs = next_obs; a.reward = reward; a.terminal = terminal; a.penalty = penalty; a.raw_reward = raw_reward;
   a.mean_out = mean_out; a.workspace = workspace;
-  return dyn_step_impl("mobody_mopo_step", a, nullptr, nullptr, 0.f, 0, stream);
+  return ens_step("mobody_mopo_step", a, stream);
 }
 
 // ---- whole H-step imagined rollout on the device (MOBODY.rollout + add_batch, mobody.py:596-657, utils.py:43-92) ----
@@ -526,13 +599,12 @@ struct RolloutWs {
   long long total;
 };
 static void rollout_carve(int S, int A, long long B, float* base, RolloutWs& w) {
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   w.obs[0] = take(B * S); w.obs[1] = take(B * S); w.act = take(B * A); w.reward = take(B); w.penalty = take(B);
-  w.dyn = take((long long)NENS * B * S + (long long)NENS * B);
+  w.dyn = take(dyn_step_floats(S, B));
   w.terminal = (uint8_t*)take((B + 3) / 4); w.keep = (uint8_t*)take((B + 3) / 4); w.alive = (uint8_t*)take((B + 3) / 4);
   w.scan = (int32_t*)take(B + 1040);
-  w.total = off;
+  w.total = take.off;
 }
 }  // namespace mobody
 
@@ -544,49 +616,41 @@ extern "C" int64_t mobody_rollout_workspace(int S, int A, int64_t B) {
 
 // H steps of policy forward -> ensemble step (latent or mopo means) -> two-launch append: 7 launches per step for both models
 static int rollout_impl(const char* who, const MobodyEnsRollout& a, void* stream) {
-  const int S = a.S, A = a.A, precision = a.precision;
+  const int S = a.S, A = a.A;
   const int64_t B = a.B;
-  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
-             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
-  MB_REQUIRE(B >= 0 && a.H >= 0, "%s: bad sizes", who);
+  EnsModel m = EnsModel::of(a, a.call0);
+  int rc = m.check_batch(who, B);
+  if (rc) return rc;
+  MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
   if (B == 0 || a.H == 0) return 0;
-  MB_REQUIRE(B <= a.cap, "%s: %lld rows per step overflow the ring of %lld twice", who, (long long)B, (long long)a.cap);
-  const MobodyBufferView* ring = a.ring;
-  MB_REQUIRE(a.dyn_blob && a.actor_blob && a.init_obs && a.elites && ring && ring->state && ring->action && ring->next_state && ring->reward &&
-                 ring->not_done && a.ptr_size && a.workspace, "%s: null pointer", who);
-  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
+  MB_REQUIRE(B <= a.cap, "%s: %lld rows per step overflow the ring of %lld twice (B > cap)", who, (long long)B, (long long)a.cap);
+  rc = m.check(who);
   if (rc) return rc;
-  MB_REQUIRE(precision == PREC_F32 || a.actor_blob_T, "%s: the split-precision modes need the actor's T blob", who);
-  MobodyMlpLayout La;
-  rc = mobody_mlp_layout(S, A, 1, &La);
+  Policy pi{a.actor_blob, a.actor_blob_T, a.max_action};
+  rc = pi.check(who, m);
   if (rc) return rc;
+  MB_NONNULL(who, a, init_obs); MB_NONNULL(who, a, ring); MB_NONNULL(who, a, ring->state); MB_NONNULL(who, a, ring->action);
+  MB_NONNULL(who, a, ring->next_state); MB_NONNULL(who, a, ring->reward); MB_NONNULL(who, a, ring->not_done);
+  MB_NONNULL(who, a, ptr_size); MB_NONNULL(who, a, workspace);
   RolloutWs w;
   rollout_carve(S, A, B, a.workspace, w);
   hipStream_t st = as_stream(stream);
   // the appends' arrival ticket (first words of the scan region) has to start at zero; every append leaves it at zero
   if (hipMemsetAsync(w.scan, 0, 8 * sizeof(int32_t), st) != hipSuccess) return fail(MOBODY_E_LAUNCH, "%s: memset failed", who);
+  // rows that terminated earlier keep their index and are flagged (alive mask); the penalty filter and the alive update
+  // are formed in the sample kernel
+  const SampleBook bk{w.keep, w.alive, a.env_filter, a.filter_bad_rollout};
   const float* obs = a.init_obs;
   for (int t = 0; t < a.H; ++t) {
     float* nxt = w.obs[t & 1];
-    // a = pi(s)  (select_action, mobody.py:612)
-    Mlp3FwdArgs p = fwd_net(a.actor_blob, La, B);
-    fwd_set_src(p, 0, obs, S, S);
-    fwd_set_out(p, w.act, 1, a.max_action);
-    if (precision != PREC_F32) fwd_set_planes(p, a.actor_blob_T, La);
-    rc = launch_mlp3_forward(p, 1, ACT_RELU, precision, st);
+    rc = pi.launch(obs, w.act, B, m.precision, st);                  // a = pi(s)  (select_action, mobody.py:612)
     if (rc) return rc;
-    // one imagined transition for every row; rows that terminated earlier keep their index and are flagged (alive mask);
-    // the penalty filter and the alive update are formed in the sample kernel
-    MobodyEnsStep s{};
-    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
-    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = obs; s.act = w.act; s.B = B;
-    s.alive = t == 0 ? nullptr : w.alive; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
-    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.penalty_coef = a.penalty_coef; s.use_penalty = a.use_penalty;
-    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    MobodyEnsStep s = m.step(t, obs, w.act, B, t == 0 ? nullptr : w.alive);
+    s.penalty_coef = a.penalty_coef; s.use_penalty = a.use_penalty;
     s.next_obs = nxt; s.reward = w.reward; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
-    rc = dyn_step_impl(who, s, w.keep, w.alive, a.env_filter, a.filter_bad_rollout, stream);
+    rc = m.launch(s, bk, st, [&](const float* r_mu) { return launch_finalize(r_mu, s, st); });
     if (rc) return rc;
-    rc = launch_ring_append(*ring, a.cap, (long long*)a.ptr_size, S, A, obs, w.act, nxt,
+    rc = launch_ring_append(*a.ring, a.cap, (long long*)a.ptr_size, S, A, obs, w.act, nxt,
                             w.reward, w.terminal, w.keep, B, w.scan, st);
     if (rc) return rc;
     obs = nxt;
@@ -613,12 +677,11 @@ struct EvalWs {
   long long total;
 };
 static void eval_carve(int S, int A, long long B, float* base, EvalWs& w) {
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   w.act = take(B * A); w.next_obs = take(B * S); w.penalty = take(B);
-  w.dyn = take((long long)NENS * B * S + (long long)NENS * B);
+  w.dyn = take(dyn_step_floats(S, B));
   w.terminal = (uint8_t*)take((B + 3) / 4); w.alive_next = (uint8_t*)take((B + 3) / 4);
-  w.total = off;
+  w.total = take.off;
 }
 }  // namespace mobody
 
@@ -636,63 +699,38 @@ extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
   const char* who = "mobody_ens_evaluate";
   MB_BLOCK(who, ap, MobodyEnsEval);
   const MobodyEnsEval& a = *ap;
-  const int S = a.S, A = a.A, precision = a.precision;
+  const int S = a.S;
   const int64_t B = a.B;
-  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
-             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
-  MB_REQUIRE(B >= 0, "%s: B < 0", who);
+  EnsModel m = EnsModel::of(a, a.call0);
+  int rc = m.check_batch(who, B);
+  if (rc) return rc;
   MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
   MB_REQUIRE(a.resume == 0 || a.resume == 1, "%s: resume %d is neither 0 nor 1", who, a.resume);
   MB_REQUIRE(a.discount > 0.f && a.discount <= 1.f, "%s: discount %g outside (0, 1]", who, (double)a.discount);   // NaN fails both
   if (B == 0) return 0;
-  MB_REQUIRE(a.dyn_blob, "%s: null pointer dyn_blob", who);
-  MB_REQUIRE(a.actor_blob, "%s: null pointer actor_blob", who);
+  rc = m.check(who);
+  if (rc) return rc;
+  Policy pi{a.actor_blob, a.actor_blob_T, a.max_action};
+  rc = pi.check(who, m);
+  if (rc) return rc;
   MB_REQUIRE(a.resume == 1 || a.init_obs, "%s: null pointer init_obs (resume == 0)", who);
-  MB_REQUIRE(a.elites, "%s: null pointer elites", who);
-  MB_REQUIRE(a.obs_state, "%s: null pointer obs_state", who);
-  MB_REQUIRE(a.alive, "%s: null pointer alive", who);
-  MB_REQUIRE(a.ret, "%s: null pointer ret", who);
-  MB_REQUIRE(a.pen_sum, "%s: null pointer pen_sum", who);
-  MB_REQUIRE(a.disc, "%s: null pointer disc", who);
-  MB_REQUIRE(a.length, "%s: null pointer length", who);
-  MB_REQUIRE(a.workspace, "%s: null pointer workspace", who);
-  MB_REQUIRE(a.n_elites >= 1 && a.n_elites <= NENS, "%s: n_elites %d outside 1..7", who, a.n_elites);
-  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
-  if (rc) return rc;
-  MB_REQUIRE(precision == PREC_F32 || a.actor_blob_T, "%s: the split-precision modes need the actor's T blob (actor_blob_T)", who);
-  MB_REQUIRE(precision == PREC_F32 || !a.mopo_blob || a.mopo_blob_T, "%s: the split-precision modes need the T blob of the MLP (mopo_blob_T)", who);
-  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d (task)", who, a.task);
-  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26", who);
-  MobodyDynLayout L;
-  rc = mobody_dyn_layout(S, A, &L);
-  if (rc) return rc;
-  MobodyMlpLayout La;
-  rc = mobody_mlp_layout(S, A, 1, &La);
-  if (rc) return rc;
+  MB_NONNULL(who, a, obs_state); MB_NONNULL(who, a, alive); MB_NONNULL(who, a, ret); MB_NONNULL(who, a, pen_sum);
+  MB_NONNULL(who, a, disc); MB_NONNULL(who, a, length); MB_NONNULL(who, a, workspace);
   EvalWs w;
-  eval_carve(S, A, B, a.workspace, w);
+  eval_carve(S, a.A, B, a.workspace, w);
   hipStream_t st = as_stream(stream);
   const DynEvalHook hook{a.obs_state, a.alive, a.ret, a.pen_sum, a.disc, a.length, a.discount};
   if (a.resume == 0) {
     rc = launch_eval_init(a.init_obs, hook, B, S, st);
     if (rc) return rc;
   }
+  SampleBook bk{}; bk.alive_out = w.alive_next;
   for (int t = 0; t < a.H; ++t) {
-    // a = pi(s)  (eval_policy_batch's policy.select_action, train_mobody.py:76)
-    Mlp3FwdArgs p = fwd_net(a.actor_blob, La, B);
-    fwd_set_src(p, 0, a.obs_state, S, S);
-    fwd_set_out(p, w.act, 1, a.max_action);
-    if (precision != PREC_F32) fwd_set_planes(p, a.actor_blob_T, La);
-    rc = launch_mlp3_forward(p, 1, ACT_RELU, precision, st);
+    rc = pi.launch(a.obs_state, w.act, B, m.precision, st);          // a = pi(s)  (eval_policy_batch, train_mobody.py:76)
     if (rc) return rc;
-    MobodyEnsStep s{};
-    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
-    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = a.obs_state; s.act = w.act; s.B = B;
-    s.alive = a.alive; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
-    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.use_penalty = 0;
-    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    MobodyEnsStep s = m.step(t, a.obs_state, w.act, B, a.alive);
     s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
-    rc = dyn_step_impl(who, s, nullptr, w.alive_next, 0.f, 0, stream, &hook);
+    rc = m.launch(s, bk, st, [&](const float* r_mu) { return launch_eval_account(r_mu, w.penalty, w.next_obs, w.alive_next, hook, B, S, st); });
     if (rc) return rc;
   }
   return 0;
@@ -706,12 +744,11 @@ struct ReplayWs {
   long long total;
 };
 static void replay_carve(int S, long long B, float* base, ReplayWs& w) {
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   w.next_obs = take(B * S); w.penalty = take(B);
-  w.dyn = take((long long)NENS * B * S + (long long)NENS * B);
+  w.dyn = take(dyn_step_floats(S, B));
   w.terminal = (uint8_t*)take((B + 3) / 4);
-  w.total = off;
+  w.total = take.off;
 }
 }  // namespace mobody
 
@@ -728,41 +765,25 @@ extern "C" int mobody_ens_replay(const MobodyEnsReplay* ap, void* stream) {
   const char* who = "mobody_ens_replay";
   MB_BLOCK(who, ap, MobodyEnsReplay);
   const MobodyEnsReplay& a = *ap;
-  const int S = a.S, A = a.A, precision = a.precision;
+  const int S = a.S, A = a.A;
   const int64_t B = a.B;
-  MB_REQUIRE(a.uncertainty_mode >= MOBODY_UNC_PAIRWISE && a.uncertainty_mode <= MOBODY_UNC_ENS_STD,
-             "%s: unknown uncertainty_mode %d (0 pairwise-diff, 1 aleatoric, 2 ensemble_std)", who, a.uncertainty_mode);
-  MB_REQUIRE(B >= 0, "%s: B < 0", who);
+  EnsModel m = EnsModel::of(a, a.call0);
+  int rc = m.check_batch(who, B);
+  if (rc) return rc;
   MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
   MB_REQUIRE(a.reset_every >= 0, "%s: reset_every < 0", who);
   if (B == 0) return 0;
   MB_REQUIRE(a.data_rows >= 1, "%s: data_rows %lld < 1", who, (long long)a.data_rows);
-  MB_REQUIRE(a.dyn_blob, "%s: null pointer dyn_blob", who);
-  MB_REQUIRE(a.data, "%s: null pointer data", who);
-  MB_REQUIRE(a.data->state, "%s: null pointer data->state", who);
-  MB_REQUIRE(a.data->action, "%s: null pointer data->action", who);
-  MB_REQUIRE(a.data->next_state, "%s: null pointer data->next_state", who);
-  MB_REQUIRE(a.data->reward, "%s: null pointer data->reward", who);
-  MB_REQUIRE(a.row0, "%s: null pointer row0", who);
-  MB_REQUIRE(a.elites, "%s: null pointer elites", who);
-  MB_REQUIRE(a.obs_state, "%s: null pointer obs_state", who);
-  MB_REQUIRE(a.act_state, "%s: null pointer act_state", who);
-  MB_REQUIRE(a.H == 0 || a.obs_err, "%s: null pointer obs_err", who);
-  MB_REQUIRE(a.H == 0 || a.rew_err, "%s: null pointer rew_err", who);
-  MB_REQUIRE(a.H == 0 || a.penalty, "%s: null pointer penalty", who);
-  MB_REQUIRE(a.H == 0 || a.term_model, "%s: null pointer term_model", who);
-  MB_REQUIRE(a.workspace, "%s: null pointer workspace", who);
+  rc = m.check(who);
+  if (rc) return rc;
+  MB_NONNULL(who, a, data); MB_NONNULL(who, a, data->state); MB_NONNULL(who, a, data->action); MB_NONNULL(who, a, data->next_state);
+  MB_NONNULL(who, a, data->reward); MB_NONNULL(who, a, row0); MB_NONNULL(who, a, obs_state); MB_NONNULL(who, a, act_state);
+  if (a.H > 0) {                                       // the four tables are written by the steps alone
+    MB_NONNULL(who, a, obs_err); MB_NONNULL(who, a, rew_err); MB_NONNULL(who, a, penalty); MB_NONNULL(who, a, term_model);
+  }
+  MB_NONNULL(who, a, workspace);
   MB_REQUIRE(a.data->pitch == 0 || a.data->pitch >= 2LL * S + A + 2, "%s: data->pitch %lld is neither 0 nor at least 2S + A + 2 = %d", who,
              (long long)a.data->pitch, 2 * S + A + 2);
-  MB_REQUIRE(a.n_elites >= 1 && a.n_elites <= NENS, "%s: n_elites %d outside 1..7", who, a.n_elites);
-  int rc = check_precision(who, precision, a.dyn_planes != nullptr);
-  if (rc) return rc;
-  MB_REQUIRE(precision == PREC_F32 || !a.mopo_blob || a.mopo_blob_T, "%s: the split-precision modes need the T blob of the MLP (mopo_blob_T)", who);
-  MB_REQUIRE(a.task >= MOBODY_TERM_NEVER && a.task <= MOBODY_TERM_PEN, "%s: unknown termination id %d (task)", who, a.task);
-  MB_REQUIRE(a.task != MOBODY_TERM_PEN || S > 26, "%s: pen predicate needs S > 26 (task)", who);
-  MobodyDynLayout L;
-  rc = mobody_dyn_layout(S, A, &L);
-  if (rc) return rc;
   ReplayWs w;
   replay_carve(S, B, a.workspace, w);
   hipStream_t st = as_stream(stream);
@@ -770,17 +791,12 @@ extern "C" int mobody_ens_replay(const MobodyEnsReplay* ap, void* stream) {
   rc = launch_replay_init(hook, B, S, A, st);
   if (rc) return rc;
   for (int t = 0; t < a.H; ++t) {
-    MobodyEnsStep s{};
-    s.dyn_blob = a.dyn_blob; s.dyn_planes = a.dyn_planes; s.mopo_blob = a.mopo_blob; s.mopo_blob_T = a.mopo_blob_T;
-    s.precision = precision; s.S = S; s.A = A; s.task = a.task; s.obs = a.obs_state; s.act = a.act_state; s.B = B;
-    s.alive = nullptr; s.elites = a.elites; s.n_elites = a.n_elites; s.seed = a.seed;
-    s.call = a.call0 + (uint32_t)t; s.call_dev = a.call_dev; s.use_penalty = 0;
-    s.use_trg = a.use_trg; s.uncertainty_mode = a.uncertainty_mode;
+    MobodyEnsStep s = m.step(t, a.obs_state, a.act_state, B, nullptr);
     s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
     hook.obs_err = a.obs_err + (int64_t)t * B; hook.rew_err = a.rew_err + (int64_t)t * B; hook.penalty = a.penalty + (int64_t)t * B;
     hook.term_model = a.term_model + (int64_t)t * B;
     hook.t = t; hook.reset = a.reset_every > 0 && (t + 1) % a.reset_every == 0;
-    rc = dyn_step_impl(who, s, nullptr, nullptr, 0.f, 0, stream, nullptr, &hook);
+    rc = m.launch(s, SampleBook{}, st, [&](const float* r_mu) { return launch_replay_account(r_mu, w.penalty, w.next_obs, w.terminal, hook, B, S, A, st); });
     if (rc) return rc;
   }
   return 0;

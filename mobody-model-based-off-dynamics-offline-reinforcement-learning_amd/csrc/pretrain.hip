@@ -589,8 +589,7 @@ static NetScratch pre_net(const MobodyMlpLayout& L, long long rows, int np3, Tak
 static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, PreWs& w) {
   const long long E = NENS, R2 = 2 * b, R4 = 4 * b;
   const int S = L.S, A = L.A;
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   static_assert(LATENT % 8 == 0, "the decoder's input rows zt are its weight-gradient operand x: Kp1 == LATENT");
   w.enc = pre_net(L.enc, R2, L.tr.Np3, take); w.tr = pre_net(L.tr, R4, L.tr.Np3, take); w.rw = pre_net(L.rw, R2, L.tr.Np3, take);
   w.enc_out = take(E * R2 * 32); w.tr_out = take(E * R4 * S); w.xrw = take(E * R2 * (2 * S + A)); w.rw_out = take(E * R2 * 2);
@@ -602,7 +601,7 @@ static int pre_carve(const MobodyPretrainLayout& L, long long b, float* base, Pr
   w.lo.lat = 0; w.lo.rt = 2LL * w.lo.n_lat; w.lo.rw = w.lo.rt + 2LL * w.lo.n_rt;
   w.lossp = take(w.lo.rw + w.lo.n_rw);
   w.bc = take(8);
-  w.total = off;
+  w.total = take.off;
   return 0;
 }
 
@@ -1102,8 +1101,7 @@ struct MopoWs {
 static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* base, MopoWs& w) {
   const long long E = NENS, R1 = b, R2 = 2 * b;
   const int S = L.S, A = L.A;
-  long long off = 0;
-  auto take = [&](long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; };
+  Carver take{base};
   w.dyn = pre_net(L.dyn, R1, L.dyn.Np3, take); w.rw = pre_net(L.rw, R2, L.rw.Np3, take);
   w.f = take(E * R1 * S); w.xrw = take(E * R2 * (2 * S + A)); w.rw_out = take(E * R2 * 2);
   w.dz3rw = take(E * R2 * 16); w.dz3d = take(E * R1 * L.dyn.Np3); w.dfake = take(E * R2 * S); w.fnz = take(E * R1 * S);
@@ -1112,7 +1110,7 @@ static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* bas
   w.lo.rt = 0; w.lo.rw = 2LL * w.lo.n_rt;
   w.lossp = take(w.lo.rw + w.lo.n_rw);
   w.bc = take(8);
-  w.total = off;
+  w.total = take.off;
   return 0;
 }
 }  // namespace mobody

@@ -30,13 +30,6 @@ struct TrainWs {
   MobodyMlpLayout Lq, La;
 };
 
-// hands a workspace out front to back, every piece rounded up to 4 floats; base == null: the sizes alone (no device is touched)
-struct Carver {
-  float* base;
-  long long off = 0;
-  float* operator()(long long n) { float* p = base ? base + off : nullptr; off += (n + 3) & ~3LL; return p; }
-};
-
 static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   int rc = mobody_mlp_layout(d.S + d.A, 1, 2, &w.Lq);
   if (rc) return rc;

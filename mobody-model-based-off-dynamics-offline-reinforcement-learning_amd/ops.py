@@ -169,9 +169,7 @@ def dyn_step(blob, S, A, task_id, obs, act, noise=None, elite_idx=None, alive=No
         assert noise.shape == (7, B, S)
     if elite_idx is not None:
         elite_idx = torch.as_tensor(elite_idx).to(device=dev, dtype=torch.int32).contiguous()
-    need = load().mobody_dyn_step_workspace(S, A, B)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    workspace = _workspace("mobody_dyn_step_workspace", dev, S, A, B, ws=workspace)
     o = out or {}
     nxt = o.get("next_obs", None)
     if nxt is None:
@@ -181,12 +179,11 @@ def dyn_step(blob, S, A, task_id, obs, act, noise=None, elite_idx=None, alive=No
     pen = o["penalty"] if "penalty" in o else torch.empty(B, 1, dtype=torch.float32, device=dev)
     raw = o["raw_reward"] if "raw_reward" in o else torch.empty(B, 1, dtype=torch.float32, device=dev)
     mean = torch.empty(7, B, S, dtype=torch.float32, device=dev) if want_mean else None
-    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
-    mb, mbt = mopo if mopo is not None else (None, None)
-    a = _lib.MobodyEnsStep(C.sizeof(_lib.MobodyEnsStep), unc_id(uncertainty_mode), ptr(blob), ptr(planes), ptr(mb), ptr(mbt),
-                           prec_id(precision), S, A, task_id, ptr(obs), ptr(act), B, ptr(noise), ptr(elite_idx), ptr(alive),
-                           el, len(elites), seed, call, int(bool(use_penalty)), ptr(call_dev), float(penalty_coef),
-                           int(bool(use_trg)), ptr(nxt), ptr(rew), ptr(term), ptr(pen), ptr(raw), ptr(mean), ptr(workspace))
+    model = _model_fields(blob, planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg)
+    a = _lib.MobodyEnsStep(struct_bytes=_BYTES[_lib.MobodyEnsStep], obs=ptr(obs), act=ptr(act), B=B, noise=ptr(noise),
+                           elite_idx=ptr(elite_idx), alive=ptr(alive), call=call, use_penalty=int(bool(use_penalty)),
+                           penalty_coef=float(penalty_coef), next_obs=ptr(nxt), reward=ptr(rew), terminal=ptr(term),
+                           penalty=ptr(pen), raw_reward=ptr(raw), mean_out=ptr(mean), workspace=ptr(workspace), **model)
     check(load().mobody_ens_step(C.byref(a), cur_stream()), "mobody_ens_step")
     res = dict(next_obs=nxt, reward=rew, terminal=term, penalty=pen, raw_reward=raw)
     if want_mean:
@@ -230,12 +227,30 @@ def hyper(cfg):
                             prec_id(cfg.get("mfma", default_mfma())))
 
 
-def _workspace(name, device, *args):
-    """The scratch tensor of the size the library's entry `name` reports for `args`."""
+def _workspace(name, device, *args, ws=None):
+    """The scratch tensor of the size the library's entry `name` reports for `args`: `ws` when that is large enough."""
     n = getattr(load(), name)(*args)
     if n < 0:
         raise _lib.MobodyError(name + ": " + load().mobody_last_error().decode())
-    return torch.empty(n, dtype=torch.float32, device=device)
+    return ws if ws is not None and ws.numel() >= n else torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _model_fields(dyn_blob, dyn_planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg):
+    """The fields the four MobodyEns* blocks share (the model a call runs), spread by the block's one constructor call.
+    mopo = (blob, blob_T) of the MOPO ablation's MLP or None.  The dict owns the host array `elites` points to."""
+    mb, mbt = mopo if mopo is not None else (None, None)
+    return dict(uncertainty_mode=unc_id(uncertainty_mode), dyn_blob=ptr(dyn_blob), dyn_planes=ptr(dyn_planes), mopo_blob=ptr(mb),
+                mopo_blob_T=ptr(mbt), precision=prec_id(precision), S=S, A=A, task=task_id,
+                elites=(C.c_int32 * len(elites))(*[int(e) for e in elites]), n_elites=len(elites), seed=seed,
+                call_dev=ptr(call_dev), use_trg=int(bool(use_trg)))
+
+
+def _run_with_workspace(name, blk, ws, device):
+    """Point `blk` at a workspace of the size `name`_workspace reports for it (`ws` when large enough) and call `name`."""
+    ws = _workspace(name + "_workspace", device, C.byref(blk), ws=ws)
+    blk.workspace = ptr(ws)
+    check(getattr(load(), name)(C.byref(blk), cur_stream()), name)
+    return ws
 
 
 def train_workspace(dims, device):
@@ -658,14 +673,8 @@ def gather_batch_rng(buffers, counts, seeds, call_offsets, counter, sizes, S, A,
     """Gather with device-drawn indices: buffers = list of RingView / 5-tuples, sizes = list of device int64[1] views,
     counter = device int64[1] or None.  `out` = (state, action, next_state, reward, not_done) destination tensors.
     bump: up to four device int64[1] words (not `counter`) the launch increments by one."""
-    n = len(buffers)
-    views = (_lib.MobodyBufferView * n)(*[buffer_view(b) for b in buffers])
-    cnt = (C.c_int64 * n)(*[int(c) for c in counts])
-    sd = (C.c_uint32 * n)(*[int(s) & 0xFFFFFFFF for s in seeds])
-    off = (C.c_int64 * n)(*[int(o) for o in call_offsets])
-    sz = (C.c_void_p * n)(*[ptr(s) for s in sizes])
-    bp = (C.c_void_p * max(1, len(bump)))(*[ptr(t) for t in bump])
-    check(load().mobody_gather_batch_rng(views, cnt, n, S, A, sd, off, ptr(counter), sz, *[ptr(t) for t in out], bp, len(bump),
+    g, (views, cnt, sd, off, sz, bp) = _gather_rng_args(buffers, counts, seeds, call_offsets, counter, sizes, bump)
+    check(load().mobody_gather_batch_rng(views, cnt, g.nbuf, S, A, sd, off, g.counter, sz, *[ptr(t) for t in out], bp, g.nbump,
                                          cur_stream()), "mobody_gather_batch_rng")
     return out
 
@@ -831,9 +840,7 @@ def dyn_validate_mopo(blob, mopo_blob, S, A, obs, act, next_obs, rew, ws=None):
     """validate() of a mopo model: mean_e = s + MLP_e([s, a]) from `mopo_blob` (mobody_mlp_layout(S + A, S, 7)), the reward
     head from the inference blob.  out[0:7] transition MSE, out[7:14] reward MSE (device tensor)."""
     B = obs.shape[0]
-    need = load().mobody_dyn_validate_workspace(S, A, B)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float32, device=obs.device)
+    ws = _workspace("mobody_dyn_validate_workspace", obs.device, S, A, B, ws=ws)
     out = torch.empty(14, dtype=torch.float32, device=obs.device)
     check(load().mobody_dyn_validate_mopo(ptr(blob), ptr(mopo_blob), S, A, ptr(_f32(obs)), ptr(_f32(act)), ptr(_f32(next_obs)),
                                           ptr(_f32(rew).reshape(-1).contiguous()), B, ptr(out), ptr(ws), cur_stream()),
@@ -844,9 +851,7 @@ def dyn_validate_mopo(blob, mopo_blob, S, A, obs, act, next_obs, rew, ws=None):
 def dyn_validate(blob, S, A, obs, act, next_obs, rew, use_trg, ws=None):
     """validate(): out[0:7] per-member transition MSE, out[7:14] per-member reward MSE (device tensor)."""
     B = obs.shape[0]
-    need = load().mobody_dyn_validate_workspace(S, A, B)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float32, device=obs.device)
+    ws = _workspace("mobody_dyn_validate_workspace", obs.device, S, A, B, ws=ws)
     out = torch.empty(14, dtype=torch.float32, device=obs.device)
     check(load().mobody_dyn_validate(ptr(blob), S, A, ptr(_f32(obs)), ptr(_f32(act)), ptr(_f32(next_obs)),
                                      ptr(_f32(rew).reshape(-1).contiguous()), B, int(bool(use_trg)), ptr(out), ptr(ws),
@@ -861,22 +866,14 @@ def rollout(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, elites
     MOPO ablation's MLP; uncertainty_mode: name or MOBODY_UNC_* id.  Returns the workspace."""
     init_obs = _f32(init_obs)
     B = init_obs.shape[0]
-    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
     view = buffer_view(buf)
-    mb, mbt = mopo if mopo is not None else (None, None)
-    a = _lib.MobodyEnsRollout(C.sizeof(_lib.MobodyEnsRollout), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
-                              ptr(mbt), ptr(actor_blob), ptr(actor_blob_T), prec_id(precision), S, A, task_id, ptr(init_obs), B,
-                              int(H), len(elites), el, seed, call0, ptr(call_dev), float(max_action), float(penalty_coef),
-                              float(env_filter), int(bool(use_penalty)), int(bool(use_trg)), int(bool(filter_bad_rollout)),
-                              C.pointer(view), cap, ptr(ptr_size), None)
-    need = load().mobody_ens_rollout_workspace(C.byref(a))
-    if need < 0:
-        raise _lib.MobodyError("mobody_ens_rollout_workspace: " + load().mobody_last_error().decode())
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.float32, device=init_obs.device)
-    a.workspace = ptr(ws)
-    check(load().mobody_ens_rollout(C.byref(a), cur_stream()), "mobody_ens_rollout")
-    return ws
+    model = _model_fields(dyn_blob, dyn_planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg)
+    a = _lib.MobodyEnsRollout(struct_bytes=_BYTES[_lib.MobodyEnsRollout], actor_blob=ptr(actor_blob), actor_blob_T=ptr(actor_blob_T),
+                              init_obs=ptr(init_obs), B=B, H=int(H), call0=call0, max_action=float(max_action),
+                              penalty_coef=float(penalty_coef), env_filter=float(env_filter), use_penalty=int(bool(use_penalty)),
+                              filter_bad_rollout=int(bool(filter_bad_rollout)), ring=C.pointer(view), cap=cap,
+                              ptr_size=ptr(ptr_size), **model)
+    return _run_with_workspace("mobody_ens_rollout", a, ws, init_obs.device)
 
 
 def eval_state(B, S, device):
@@ -898,21 +895,13 @@ def ens_evaluate(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, e
     if init_obs is not None:
         init_obs = _f32(init_obs)
         assert init_obs.shape == (B, S)
-    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
-    mb, mbt = mopo if mopo is not None else (None, None)
-    a = _lib.MobodyEnsEval(C.sizeof(_lib.MobodyEnsEval), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
-                           ptr(mbt), ptr(actor_blob), ptr(actor_blob_T), prec_id(precision), S, A, task_id, ptr(init_obs), B,
-                           int(H), len(elites), el, seed, call0, ptr(call_dev), float(max_action), float(discount),
-                           int(bool(use_trg)), int(bool(resume)), ptr(state["obs_state"]), ptr(state["alive"]),
-                           ptr(state["ret"]), ptr(state["pen_sum"]), ptr(state["disc"]), ptr(state["length"]), None)
-    need = load().mobody_ens_evaluate_workspace(C.byref(a))
-    if need < 0:
-        raise _lib.MobodyError("mobody_ens_evaluate_workspace: " + load().mobody_last_error().decode())
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.float32, device=state["obs_state"].device)
-    a.workspace = ptr(ws)
-    check(load().mobody_ens_evaluate(C.byref(a), cur_stream()), "mobody_ens_evaluate")
-    return ws
+    model = _model_fields(dyn_blob, dyn_planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg)
+    a = _lib.MobodyEnsEval(struct_bytes=_BYTES[_lib.MobodyEnsEval], actor_blob=ptr(actor_blob), actor_blob_T=ptr(actor_blob_T),
+                           init_obs=ptr(init_obs), B=B, H=int(H), call0=call0, max_action=float(max_action),
+                           discount=float(discount), resume=int(bool(resume)), obs_state=ptr(state["obs_state"]),
+                           alive=ptr(state["alive"]), ret=ptr(state["ret"]), pen_sum=ptr(state["pen_sum"]),
+                           disc=ptr(state["disc"]), length=ptr(state["length"]), **model)
+    return _run_with_workspace("mobody_ens_evaluate", a, ws, state["obs_state"].device)
 
 
 def replay_state(B, H, S, A, device):
@@ -933,22 +922,13 @@ def ens_replay(dyn_blob, S, A, task_id, data, data_rows, row0, H, elites, seed, 
     assert row0.dtype == torch.int64 and row0.dim() == 1
     B = row0.shape[0]
     assert state["obs_state"].shape == (B, S) and state["obs_err"].shape == (int(H), B)
-    el = (C.c_int32 * len(elites))(*[int(e) for e in elites])
     view = buffer_view(data)
-    mb, mbt = mopo if mopo is not None else (None, None)
-    a = _lib.MobodyEnsReplay(C.sizeof(_lib.MobodyEnsReplay), unc_id(uncertainty_mode), ptr(dyn_blob), ptr(dyn_planes), ptr(mb),
-                             ptr(mbt), prec_id(precision), S, A, task_id, C.pointer(view), int(data_rows), ptr(row0), B, int(H),
-                             int(reset_every), len(elites), el, seed, call0, ptr(call_dev), int(bool(use_trg)),
-                             ptr(state["obs_state"]), ptr(state["act_state"]), ptr(state["obs_err"]), ptr(state["rew_err"]),
-                             ptr(state["penalty"]), ptr(state["term_model"]), None)
-    need = load().mobody_ens_replay_workspace(C.byref(a))
-    if need < 0:
-        raise _lib.MobodyError("mobody_ens_replay_workspace: " + load().mobody_last_error().decode())
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1), dtype=torch.float32, device=row0.device)
-    a.workspace = ptr(ws)
-    check(load().mobody_ens_replay(C.byref(a), cur_stream()), "mobody_ens_replay")
-    return ws
+    model = _model_fields(dyn_blob, dyn_planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg)
+    a = _lib.MobodyEnsReplay(struct_bytes=_BYTES[_lib.MobodyEnsReplay], data=C.pointer(view), data_rows=int(data_rows), row0=ptr(row0),
+                             B=B, H=int(H), reset_every=int(reset_every), call0=call0, obs_state=ptr(state["obs_state"]),
+                             act_state=ptr(state["act_state"]), obs_err=ptr(state["obs_err"]), rew_err=ptr(state["rew_err"]),
+                             penalty=ptr(state["penalty"]), term_model=ptr(state["term_model"]), **model)
+    return _run_with_workspace("mobody_ens_replay", a, ws, row0.device)
 
 
 # ---- wide MLPs (csrc/wide.hip): BOSA's VAE nets, exact fp32 whatever MOBODY_MFMA says ------------------------------------
