@@ -1058,6 +1058,18 @@ int mobody_bosa_reparam(const float* enc, const float* eps, const float* dz, int
                         float* denc, float* lossp, float* kl_out, void* stream);
 int mobody_bosa_vae(const MobodyBosaVae* a, void* stream);
 int mobody_bosa_loglik(const MobodyBosaVae* a, void* stream);
+/*   mobody_bosa_critic    bosa.py:580-607: the twin-Q update of BOSA's second stage on a MobodyCritic block whose q_next
+ *                       [N] the caller supplies (min target-Q(s', a') with its clipped target noise); phase, gather and
+ *                       policy_forward must be 0 / NULL, the actor and target blobs are not read.  Q(s, a) with saves, then the
+ *                       backward seeded with dz3[m][row][0] = 2 w (q_m - y) / N_global + c, w = row_weight[row], c = row_const[row]
+ *                       (seed mode 9; c == 0 gives mobody_igdf_critic's seed bit for bit), the weight gradients and -- m, v given --
+ *                       Adam, WITHOUT a Polyak update.  BOSA: w = mask / 2, c = conservation_coef / batch_size on the source rows
+ *                       and 0 on the target rows.  loss_out[1] = sum over members and the rows with c != 0 of q_m, divided by
+ *                       cons_rows_global (src_q1.mean() + src_q2.mean()); loss_out[0] = sum_m sum_rows w (q_m - y)^2 / N_global +
+ *                       cons_coef * loss_out[1] (critic_loss; critic_td_loss is the difference).  workspace:
+ *                       mobody_train_workspace floats. */
+int mobody_bosa_critic(const MobodyCritic* a, const float* row_weight, const float* row_const, float cons_coef,
+                       int64_t cons_rows_global, void* stream);
 
 #ifdef __cplusplus
 }

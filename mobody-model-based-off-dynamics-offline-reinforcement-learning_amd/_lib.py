@@ -289,6 +289,7 @@ PROTOTYPES = {
     "mobody_igdf_info": (C.c_int, [C.POINTER(MobodyIgdf), vp]),
     "mobody_igdf_filter": (C.c_int, [C.POINTER(MobodyIgdf), vp]),
     "mobody_igdf_critic": (C.c_int, [C.POINTER(MobodyIql), vp, vp]),
+    "mobody_bosa_critic": (C.c_int, [C.POINTER(MobodyCritic), vp, vp, f32, i64, vp]),
     "mobody_adam_polyak": (C.c_int, [C.POINTER(MobodyAdam), vp]),
     "mobody_value_loss_grad": (C.c_int, [vp, vp, i64, i64, vp, vp, vp, vp]),
     "mobody_par_penalty": (C.c_int, [vp, vp, vp, f32, i64, C.c_int, vp]),

@@ -253,6 +253,26 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
       }
       Xs[t] = v;
     }
+  } else if constexpr (SEED == 9) {                   // mode 9: mode 8 plus a per-row constant, one thread per row
+    if (t < TB) {
+      const bool ok = t < rows_here;
+      const long long row = row0 + (ok ? t : 0);
+      const float qn = sd.qnext ? sd.qnext[row] : fminf(sd.qt[row], sd.qt[a.rows + row]);
+      const float y = sd.r[row] + sd.nd[row] * sd.gamma * qn;
+      const float qm = sd.q[(long long)m * a.rows + row];
+      const float d = qm - y;
+      const float wr = sd.cs.w[row], cr = sd.cs.c[row];
+      const float td = 2.f * wr * d * sd.inv_ng;
+      const float v = ok ? (cr != 0.f ? td + cr : td) : 0.f;       // c == 0: mode 8's value, the sign of a zero included
+      l0 = ok ? wr * (d * d) : 0.f;
+      l1 = ok && cr != 0.f ? qm : 0.f;
+      if (ok) {
+        float* g = sd.dz3_out + ((long long)m * a.rows + row) * Np3;
+        g[0] = v;
+        for (int c = 1; c < Np3; ++c) g[c] = 0.f;
+      }
+      Xs[t] = v;
+    }
   } else if constexpr (SEED == 4) {                   // mode 4: eight threads per row (TB * 8 == NTHREADS)
     static_assert(MLP_TILE_ROWS * 8 == NTHREADS, "mode 4 spreads a row's A <= 24 action columns over eight lanes");
     // sq = sum_j (pi - a)^2 needs A words of pi and of act per row: lane `sub` of a row's eight takes columns sub, sub + 8,
@@ -368,7 +388,8 @@ __device__ __forceinline__ void bwd_seed(const Mlp3BwdArgs& a, float* Xs, float*
   if (t == 0) {
     l0 = red[0] + red[1] + red[2] + red[3];
     l1 = red[4] + red[5] + red[6] + red[7];
-    if constexpr (SEED == SEED_RT || SEED == 8) sd.lossp[tile * 2 + m] = l0;
+    if constexpr (SEED == 9) { sd.lossp[2 * (tile * 2 + m)] = l0; sd.lossp[2 * (tile * 2 + m) + 1] = l1; }
+    else if constexpr (SEED == SEED_RT || SEED == 8) sd.lossp[tile * 2 + m] = l0;
     else if constexpr (SEED == 6 || SEED == 7) sd.lossp[tile] = l0;
     else { sd.lossp[2 * tile] = l0; sd.lossp[2 * tile + 1] = l1; }
   }
@@ -410,7 +431,7 @@ __device__ __forceinline__ void mlp3_bwd_tile(const Mlp3BwdArgs& a, int m, int t
   // Seed modes 1 and 2 seed column 0 of a one-output net: dz3 W3^T is the rank-1 product seed[row] * W3^T[0][col], formed in
   // registers -- no weight ring, no K = Np3 GEMM.  (An fp32 fma chain whose only non-zero product is its first yields
   // round(v * w): the same values as the GEMM gave, up to the sign of an exact zero.)  Mode 2 also has no bias partials.
-  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4 || SEED == 5 || SEED == 8);
+  const bool rank1 = SEED == SEED_RT ? a.seed.mode == 1 : (SEED == 2 || SEED == 4 || SEED == 5 || SEED == 8 || SEED == 9);
   constexpr bool with_db = SEED != 2 && SEED != 4;
   const int c0 = (64 * w + (lane & 31)) * 4;        // wide_idx(0, col) of this lane's two columns: same round trip as the masks
   const float w3c[2] = {w3t[c0], w3t[c0 + 128]};
@@ -1263,6 +1284,42 @@ int launch_mlp3_bwd_wcritic(const Mlp3BwdArgs& a, hipStream_t st) {
     return a.prec == PREC_BF16 ? launch_bwd_wcritic_t<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_wcritic_t<2>(a, st)
          : a.prec == PREC_BF16X3 ? launch_bwd_wcritic_t<3>(a, st) : launch_bwd_wcritic_t<4>(a, st);
   return launch_bwd_wcritic_t<0>(a, st);
+}
+
+// ------------------------------------------------------------------------------------------------
+// BOSA's masked conservative critic: mode 8 plus a per-row constant, compiled in as mode 9 -- again an instance of its
+// own, so that the kernels of modes 1 and 8 keep their code.
+// ------------------------------------------------------------------------------------------------
+template <int PM>
+__global__ __launch_bounds__(NTHREADS, 3) void k_mlp3_bwd_ccritic(Mlp3BwdArgs a) {
+  __shared__ float red[8];
+  extern __shared__ __attribute__((aligned(16))) float Xs[];
+  mlp3_bwd_tile<false, 0, 1, PM, 9>(a, blockIdx.y, blockIdx.x, 2, Xs, red);
+}
+
+template <int PM>
+static int launch_bwd_ccritic_t(const Mlp3BwdArgs& a, hipStream_t st) {
+  constexpr size_t lds = split_lds_bytes<(PM > 0 ? PM : 1), MLP_TILE_ROWS>();
+  static bool once = false;
+  if (!once) {
+    int rc = allow_big_lds(k_mlp3_bwd_ccritic<PM>, lds);
+    if (rc) return rc;
+    once = true;
+  }
+  ProfScope prof(PROF_MLP_BWD, st);
+  hipLaunchKernelGGL((k_mlp3_bwd_ccritic<PM>), dim3((unsigned)cdiv(a.rows, MLP_TILE_ROWS), 2u), dim3(NTHREADS), lds, st, a);
+  MB_LAUNCH_OK("k_mlp3_bwd_ccritic");
+  return 0;
+}
+
+int launch_mlp3_bwd_ccritic(const Mlp3BwdArgs& a, hipStream_t st) {
+  MB_REQUIRE(a.seed.mode == 9 && a.seed.cs.w && a.seed.cs.c && a.m1 && a.m2 && !a.swish && a.seed.dz3_out && a.seed.lossp && a.Np3 == 16,
+             "launch_mlp3_bwd_ccritic: needs seed mode 9 with its row weights and constants on a one-output ReLU twin net with sign words");
+  if (a.rows <= 0) return 0;
+  if (a.prec != PREC_F32 && a.w2t_planes != nullptr)
+    return a.prec == PREC_BF16 ? launch_bwd_ccritic_t<1>(a, st) : a.prec == PREC_BF16X2 ? launch_bwd_ccritic_t<2>(a, st)
+         : a.prec == PREC_BF16X3 ? launch_bwd_ccritic_t<3>(a, st) : launch_bwd_ccritic_t<4>(a, st);
+  return launch_bwd_ccritic_t<0>(a, st);
 }
 
 }  // namespace mobody

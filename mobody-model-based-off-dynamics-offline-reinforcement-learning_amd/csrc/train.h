@@ -65,6 +65,10 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 //   8  IGDF's row-weighted critic (igdf.py:468-479): mode 1 with a per-row weight w = cw.w[row], dz3[m][row][0] = 2 w (q_m - y) /
 //        N_global, lossp[tile*2 + m] = sum w (q_m - y)^2; runs in launch_mlp3_bwd_wcritic (k_mlp3_bwd_wcritic), compiled in, so the
 //        kernels of mode 1 keep their code.  Its weight pointer rides in the bytes of `ar`, which modes 1 and 8 do not read.
+//   9  BOSA's masked conservative critic (bosa.py:596-598): mode 8 plus a per-row constant c = cs.c[row],
+//        dz3[m][row][0] = 2 w (q_m - y) / N_global + c  (c == 0: exactly mode 8's value); the partial sums are PAIRS,
+//        lossp[2 (tile*2 + m)] = sum w (q_m - y)^2 and lossp[2 (tile*2 + m) + 1] = sum_{c != 0} q_m (LossFinal kind 2's layout); runs in
+//        launch_mlp3_bwd_ccritic (k_mlp3_bwd_ccritic), compiled in, so the kernels of modes 1 and 8 keep their code.
 // Modes 5, 6 and 7 run in launch_mlp3_bwd_seed (k_mlp3_bwd_seed), compiled in; their row-wise arguments are `iq` (5, 6) or `da`
 // (7), which share the bytes of `ar`.
 struct IqlSeed {
@@ -86,6 +90,10 @@ struct DaraSeed {
 struct CriticSeed {
   const float* w;              // [rows] row weights of the critic loss (mode 8 reads nothing else of the union)
 };
+struct ConsSeed {
+  const float* w;              // [rows] row weights, as CriticSeed's
+  const float* c;              // [rows] additive constants of the seed; rows with c != 0 enter the second partial sum
+};
 struct BwdSeed {
   int mode;
   const float *q, *qt, *qnext, *r, *nd;      // mode 1 ([2][rows] q and qt, [rows] the rest)
@@ -96,6 +104,7 @@ struct BwdSeed {
     IqlSeed iq;                              // modes 5, 6
     DaraSeed da;                             // mode 7
     CriticSeed cw;                           // mode 8
+    ConsSeed cs;                             // mode 9
   };
   float* dz3_out;
   float* lossp;
@@ -107,6 +116,9 @@ static_assert(sizeof(DaraSeed) <= sizeof(ActorRowArgs) && alignof(DaraSeed) == a
 
 static_assert(sizeof(CriticSeed) <= sizeof(ActorRowArgs) && alignof(CriticSeed) == alignof(ActorRowArgs),
               "CriticSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
+
+static_assert(sizeof(ConsSeed) <= sizeof(ActorRowArgs) && alignof(ConsSeed) == alignof(ActorRowArgs),
+              "ConsSeed rides in ActorRowArgs' bytes: the argument block of every backward kernel keeps its layout");
 
 struct Mlp3BwdArgs {
   BwdSeed seed;
@@ -142,6 +154,8 @@ int launch_actor_bwd_chain(const Mlp3BwdArgs& q, const Mlp3BwdArgs& pi, int* tic
 int launch_mlp3_bwd_seed(const Mlp3BwdArgs& a, hipStream_t st);
 // the twin-Q net (two members), sign words, seed mode 8 (mode 1's fields + cw.w) formed in the prologue; no dx
 int launch_mlp3_bwd_wcritic(const Mlp3BwdArgs& a, hipStream_t st);
+// the twin-Q net (two members), sign words, seed mode 9 (mode 1's fields + cs.w, cs.c) formed in the prologue; no dx
+int launch_mlp3_bwd_ccritic(const Mlp3BwdArgs& a, hipStream_t st);
 // learning rate of 1-based gradient step k under CosineAnnealingLR(T_max), eta_min 0 (closed form, in double, rounded to fp32 once)
 __host__ __device__ inline float cosine_lr(float lr0, long long k, long long T_max) {
   return (float)((double)lr0 * (1.0 + cos(3.14159265358979323846 * (double)(k - 1) / (double)T_max)) * 0.5);

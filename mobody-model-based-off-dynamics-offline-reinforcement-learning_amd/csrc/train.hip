@@ -23,6 +23,7 @@ struct TrainWs {
   int *eh1q, *eh1a, *edz2;              // f16 mode: scale exponents of the 32-row tiles of the h1 / dz2 planes
   float *pin;            // pi(s') of the critic phase (pi holds pi(s) for the actor phase)
   float *pi, *qt, *q, *qb, *xq, *h1q, *h2q, *xa, *h1a, *h2a, *dz3q, *dz2, *dz1, *dz3a, *dxa, *bcw, *dbp, *slabs, *lossp;
+  float *lossp_pairs;      // seed mode 9: a pair of partial sums per (row tile, member)
   float *bc;               // Adam bias corrections of a device step count: two floats per net (critic, actor), mlp3_weight_grads
   int *tickets;            // one per row tile: arrivals of the tile's two frozen-Q workgroups in k_actor_bwd_chain (zeroed by k_actor_stats)
   long long total;
@@ -71,6 +72,7 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   }
   w.bc = take(4);
   w.tickets = (int*)take(w.ntiles);
+  w.lossp_pairs = take(4LL * w.ntiles);           // behind everything else: no other piece moves
   w.total = take.off;
   return 0;
 }
@@ -266,8 +268,12 @@ extern "C" int64_t mobody_train_workspace(const MobodyTrainDims* d) {
 
 // extra (with q_next, or null): a one-member forward that shares the launch of Q(s, a) -- IQL's V(s'), which writes q_next.
 // row_weight (or null): IGDF's per-row weights of the loss (seed mode 8, train.h)
+// cons (or null; needs row_weight): BOSA's conservative term (seed mode 9): the per-row constants of the seed, and what turns the
+// second partial sum into loss_out -- loss_out[0] = sum w (q_m - y)^2 / N_global + coef * loss_out[1], loss_out[1] = sum_{c != 0} q_m /
+// rows.  The fused form then steps the critic without touching its target (BOSA's Polyak update waits for the delayed actor step).
+struct ConsTerm { const float* c; float coef, rows; };
 static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* stream, const char* who = "mobody_critic",
-                       const Mlp3FwdArgs* extra = nullptr, const float* row_weight = nullptr) {
+                       const Mlp3FwdArgs* extra = nullptr, const float* row_weight = nullptr, const ConsTerm* cons = nullptr) {
   // gather != null (phase 0, q_next == null): state .. not_done are not read by the first forward launch but WRITTEN by it --
   // its tiles draw and fetch the minibatch rows themselves (layers.h FwdGather; the block arrives with `g` filled)
   // phase: 0 the whole step; 1 only its forwards (nothing of them reads `reward`); 2 only the backward, weight gradients and
@@ -283,7 +289,7 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   rc = check_precision(who, h->precision, a.q_next != nullptr || (a.actor_blob_T && a.qtarg_blob_T));
   if (rc) return rc;
   if (fused) {
-    MB_REQUIRE(a.qtarg_blob, "%s: null pointer", who);
+    MB_REQUIRE(a.qtarg_blob || cons != nullptr, "%s: null pointer", who);
     MB_REQUIRE(a.t_dev != nullptr || a.t >= 1, "%s: step t must be >= 1", who);
     MB_REQUIRE(a.bump == nullptr || a.bump != a.t_dev, "%s: bump must not be the step word the launch reads", who);
   } else {
@@ -294,8 +300,12 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   if (rc) return rc;
   AdamTarget adam{};
   if (fused) {
-    adam = adam_target(a.q_blob, a.q_blob_T, a.m, a.v, a.qtarg_blob, a.t, a.t_dev, a.lr, h->tau, 1.f, h->precision);
-    adam.target_T = a.qtarg_blob_T;
+    if (cons != nullptr) {
+      adam = adam_target(a.q_blob, a.q_blob_T, a.m, a.v, nullptr, a.t, a.t_dev, a.lr, -1.f, 1.f, h->precision);
+    } else {
+      adam = adam_target(a.q_blob, a.q_blob_T, a.m, a.v, a.qtarg_blob, a.t, a.t_dev, a.lr, h->tau, 1.f, h->precision);
+      adam.target_T = a.qtarg_blob_T;
+    }
     adam.bump = (long long*)a.bump;
   }
   const float *q_blob = a.q_blob, *state = a.state, *action = a.action, *next_state = a.next_state, *q_next = a.q_next;
@@ -340,7 +350,16 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
   bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = a.reward; bq.seed.nd = a.not_done;
   bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
-  if (row_weight != nullptr) {                     // IGDF: the same seed with the row's weight, an instance of its own (mode 8)
+  if (cons != nullptr) {                           // BOSA: weight and constant (mode 9); its partial sums are pairs, 4 per row tile
+    bq.seed.mode = 9; bq.seed.cs.w = row_weight; bq.seed.cs.c = cons->c;
+    bq.seed.lossp = w.lossp_pairs;
+    rc = launch_mlp3_bwd_ccritic(bq, st);
+    if (rc) return rc;
+    LossFinal lc{};                                // kind 2 without the q scale: out[0] = s0 / ng + bc_coef * out[1], out[1] = s1 / ntg_a
+    lc.kind = 2; lc.nparts = 2 * w.ntiles; lc.scale_q = 0; lc.bc_coef = cons->coef; lc.ng = (float)d->N_global; lc.ntg_a = cons->rows;
+    lc.parts = w.lossp_pairs; lc.out = a.loss_out;
+    return weight_grads(w.Lq, w.xq, w.h1q, w.h2q, w.eh1q, w.dz3q, N, w, a.grad_q, lc, adam, prec, st);
+  } else if (row_weight != nullptr) {              // IGDF: the same seed with the row's weight, an instance of its own (mode 8)
     bq.seed.mode = 8; bq.seed.cw.w = row_weight;
     rc = launch_mlp3_bwd_wcritic(bq, st);
   } else {
@@ -371,6 +390,22 @@ extern "C" int mobody_critic(const MobodyCritic* a, void* stream) {
   for (int k = 0; k < gr->nbuf; ++k)
     MB_REQUIRE(gr->counts[k] == 0 || fg.g.packed[k], "%s: source %d is not a row-interleaved ring (mobody_ring_pitch)", who, k);
   return critic_impl(*a, &fg, stream);
+}
+
+// BOSA's critic update (bosa.py:580-607) on bootstrap values the caller supplies: Q(s, a) with saves, seed mode 9, the
+// weight gradients with the optimizer step fused -- and no Polyak update
+extern "C" int mobody_bosa_critic(const MobodyCritic* a, const float* row_weight, const float* row_const, float cons_coef,
+                                  int64_t cons_rows_global, void* stream) {
+  const char* who = "mobody_bosa_critic";
+  MB_BLOCK(who, a, MobodyCritic);
+  MB_REQUIRE((a->grad_q != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_q and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad_q || (a->m && a->v), "%s: null pointer", who);
+  MB_REQUIRE(a->phase == 0 && a->gather == nullptr && a->policy_forward == 0, "%s: phase, gather and policy_forward must be 0 / NULL", who);
+  MB_REQUIRE(a->q_next != nullptr, "%s: q_next is NULL: the caller supplies min target-Q(s', a') with its clipped target noise", who);
+  MB_REQUIRE(row_weight != nullptr && row_const != nullptr, "%s: row_weight / row_const is NULL", who);
+  MB_REQUIRE(cons_rows_global >= 1, "%s: cons_rows_global %lld < 1", who, (long long)cons_rows_global);
+  const ConsTerm cons{row_const, cons_coef, (float)cons_rows_global};
+  return critic_impl(*a, nullptr, stream, who, nullptr, row_weight, &cons);
 }
 
 // td3bc: the TD3_BC form (the entry point has checked Nt == N, no v_true, scale_q) -- no Q(s_t, a_t) forward and no second statistic

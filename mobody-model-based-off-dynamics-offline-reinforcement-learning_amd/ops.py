@@ -325,6 +325,18 @@ def critic_update(dims, hyp, actor_blob, q_blob, q_blob_T, qtarg_blob, batch, m,
     check(load().mobody_critic(C.byref(blk), cur_stream()), "mobody_critic")
 
 
+def bosa_critic(dims, hyp, q_blob, q_blob_T, batch, q_next, row_weight, row_const, cons_coef, cons_rows, loss_out, ws, grad_q=None,
+                m=None, v=None, t=0, t_dev=None, lr=0.0):
+    """BOSA's critic update (seed mode 9) on caller-supplied bootstrap values q_next [N]: the loss mean_rows(w (q1 - y)^2) +
+    mean_rows(w (q2 - y)^2) + cons_coef * (sum_{c != 0} (q1 + q2) / cons_rows) with the seed's per-row constant c = row_const.
+    loss_out[0] = that loss, loss_out[1] = the conservative term.  grad_q: the gradient form; m, v: Adam fused, and no Polyak
+    update (the target nets follow the delayed actor step)."""
+    blk = _critic_block(dims, hyp, None, q_blob, q_blob_T, None, batch, loss_out, ws, q_next, False, None, None)
+    blk.grad_q, blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(grad_q), ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    check(load().mobody_bosa_critic(C.byref(blk), ptr(row_weight), ptr(row_const), float(cons_coef), int(cons_rows), cur_stream()),
+          "mobody_bosa_critic")
+
+
 def actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, m, v, t, lr, loss_out, ws,
                  v_true=None, t_dev=None):
     blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, action, stats, ws)
