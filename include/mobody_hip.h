@@ -558,6 +558,24 @@ int mobody_actor_backward(const MobodyActor* a, void* stream);
 int mobody_td3bc_actor_forward(const MobodyActor* a, void* stream);
 int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream);
 
+/* BOSA actor phase (the reference's bosa.py:612-629) on the same MobodyActor block (its size stays) and workspace:
+ * pi = actor(s), q = critic_1(s, pi) -- member 0 of the twin-Q blob ALONE, not the minimum --, norm_q = 1 / mean|q| detached,
+ * actor_loss = -norm_q mean(q) + lamda mean(-ll(s, pi)).  The second term reaches the actor as a per-element addend.
+ *   mobody_bosa_actor_forward   pi(s) with its saves, member 0's Q(s, pi) with its ReLU signs, stats[0] = sum |q_0|, stats[1] = sum q_0
+ *                               over the local rows; pi_out [N][A] is a copy of pi(s): what the caller hands to
+ *                               mobody_bosa_loglik_grad as `action`.  a->action is not read.  3 launches and the copy.
+ *   mobody_bosa_actor_backward  dq_0/da under the seed -(1/m)/N_global, m = stats[0]/N_global (:614, :620); d(pre-tanh) = (dq_0/da +
+ *                               dpi_extra) * max_action (1 - (pi / max_action)^2) with dpi_extra [N][A] from the caller (BOSA:
+ *                               -(lamda / N) dll_da, :617-620); the actor's weight gradients into grad_actor or, fused, its Adam step
+ *                               (t / t_dev as above).  loss_out[0] = -(1/m) stats[1] / N_global, loss_out[1] = 0.  6 launches: two
+ *                               row-wise seeds, the two backwards in seed mode 0, the weight gradients and their reduction.
+ * Every launch is a later launch on the stream; no kernel waits on another and no tickets are used.  Precisions: 0 (f32), 3 (bf16x3)
+ * and 4 (f16x2) run, through the launches the other phases use at that precision; 1 (bf16) and 2 (bf16x2) are refused by name.
+ * Refused with MOBODY_E_ARG before any runtime call: d.N > 2^21, v_true != NULL, policy_ready != 0, such a precision, pi_out /
+ * dpi_extra NULL, both or neither of grad_actor and m, v, null pointers. */
+int mobody_bosa_actor_forward(const MobodyActor* a, float* pi_out /* [N][A] */, void* stream);
+int mobody_bosa_actor_backward(const MobodyActor* a, const float* dpi_extra /* [N][A] */, void* stream);
+
 /* ---- IQL baseline (the reference's algo/offline_offline/iql.py) -----------------------------------------------
  * One block type for the step's three calls, in the step's order; each call reads the fields named for it, `grad` / `m, v` /
  * `t` / `t_dev` / `lr` are those of the net the call trains (gradient form or fused form by the rule above).  Every row is
@@ -975,6 +993,12 @@ struct MobodyWideBwd {
 };
 int64_t mobody_wide_mlp3_backward_workspace(const MobodyWideLayout* L, int64_t rows);
 int mobody_wide_mlp3_backward(const MobodyWideBwd* a, void* stream);
+/*   mobody_wide_mlp3_input_grad  the same block with grad == NULL and dx != NULL: dx alone, for a net whose parameters are held fixed
+ *                       (the estimator's gradient, bosa.py:615-619, differentiates through the frozen VAE).  Three launches -- dz2,
+ *                       dz1 and dx[:, dx_col0:dx_col1], the products mobody_wide_mlp3_backward issues, in its order -- so dx has the
+ *                       bits of the full backward's dx.  x is not read.  The same workspace entry.  Refused as its sibling refuses,
+ *                       and additionally: grad given, dx missing. */
+int mobody_wide_mlp3_input_grad(const MobodyWideBwd* a, void* stream);
 
 /*   mobody_wide_adam          torch.optim.Adam(lr) with torch's defaults (bosa.py:424-425) on n floats of a flat blob -- one
  *                       wide net or several laid end to end -- from a gradient of the same layout.  t is the 1-based step count;
@@ -1025,12 +1049,28 @@ int mobody_wide_adam(const MobodyWideAdam* a, void* stream);
  *                       (policy) / [n][members][B][Lz] (dynamics), or NULL: drawn at that linear index from stream
  *                       MOBODY_BOSA_STREAM_POLICY_LL / _DYNAMICS_LL.  Forward only: grad, m, v must be NULL; t, t_dev, lr and
  *                       loss_out are not read.  10 launches, 11 with mask_mean.
+ *   mobody_bosa_loglik_grad  bosa.py:615-619: the policy VAE's estimator AND its derivative with respect to the action,
+ *                       what autograd gives the actor loss's neg_log_beta term per row; kind MOBODY_BOSA_DYNAMICS is refused (that
+ *                       estimator only runs under no_grad, :583-590).  a->action is the point of evaluation (the class passes
+ *                       pi(s)).  ll and w_out are written by mobody_bosa_loglik itself, eps follows its rules (NULL: stream
+ *                       MOBODY_BOSA_STREAM_POLICY_LL at `call`).  dll_da[b][j] = d ll[b] / d action[b][j] with the VAE's parameters
+ *                       and eps held fixed: with p_k = softmax_k(w_k) and var = beta / 4, the direct term -sum_k p_k (a - u_k) / var,
+ *                       plus the encoder's input gradient over columns [S, S + A) of the seed [sum_k g_k | pass (sum_k g_k eps_k std
+ *                       + 1)], g_k = dz_k - p_k z_k, dz_k the decoder's latent input gradient of p_k (a - u_k) / var * max_action
+ *                       (1 - (u_k / max_action)^2) on row k B + b; `pass` is mobody_bosa_reparam's inclusive clamp test.  The
+ *                       estimator's launches, then 9: two row-wise kernels, mobody_wide_mlp3_input_grad on the decoder (n B rows)
+ *                       and on the encoder, the final sum.  Later launches on one stream; no kernel waits on another; every loop is
+ *                       bounded by an argument; fixed summation order, no float atomics.  workspace:
+ *                       mobody_bosa_loglik_grad_workspace floats (mobody_bosa_workspace's pieces first, then the seed, dz and
+ *                       backward scratch on n B rows); -1 for a bad block.  Refused as mobody_bosa_loglik refuses, and: kind,
+ *                       dll_da NULL.
  * mobody_bosa_workspace(a) floats serve both calls on the block (for mobody_bosa_loglik with its num_samples).  Refused with
  * MOBODY_E_ARG before any runtime call, with the field named: kind, members != 1 for the policy VAE, a net outside
  * mobody_wide_layout's ranges, precision != 0, B < 1, beta <= 0, num_samples outside [1, 64], one of m, v without the other,
  * null pointers. */
 enum { MOBODY_BOSA_POLICY = 0, MOBODY_BOSA_DYNAMICS = 1 };
-enum { MOBODY_BOSA_STREAM_POLICY = 6, MOBODY_BOSA_STREAM_DYNAMICS = 7, MOBODY_BOSA_STREAM_POLICY_LL = 8, MOBODY_BOSA_STREAM_DYNAMICS_LL = 9 };
+enum { MOBODY_BOSA_STREAM_POLICY = 6, MOBODY_BOSA_STREAM_DYNAMICS = 7, MOBODY_BOSA_STREAM_POLICY_LL = 8, MOBODY_BOSA_STREAM_DYNAMICS_LL = 9,
+       MOBODY_BOSA_STREAM_TARGET_NOISE = 10 /* the second stage's target noise [N][A] (bosa.py:571), drawn by the host class with mobody_rng_normal */ };
 typedef struct MobodyBosaVae MobodyBosaVae;
 struct MobodyBosaVae {
   int32_t struct_bytes;
@@ -1058,6 +1098,8 @@ int mobody_bosa_reparam(const float* enc, const float* eps, const float* dz, int
                         float* denc, float* lossp, float* kl_out, void* stream);
 int mobody_bosa_vae(const MobodyBosaVae* a, void* stream);
 int mobody_bosa_loglik(const MobodyBosaVae* a, void* stream);
+int64_t mobody_bosa_loglik_grad_workspace(const MobodyBosaVae* a);
+int mobody_bosa_loglik_grad(const MobodyBosaVae* a, float* dll_da /* [B][A] */, void* stream);
 /*   mobody_bosa_critic    bosa.py:580-607: the twin-Q update of BOSA's second stage on a MobodyCritic block whose q_next
  *                       [N] the caller supplies (min target-Q(s', a') with its clipped target noise); phase, gather and
  *                       policy_forward must be 0 / NULL, the actor and target blobs are not read.  Q(s, a) with saves, then the

@@ -202,7 +202,7 @@ class MobodyBosaVae(C.Structure):
 
 WIDE_OUT_MODES = {"raw": 0, "tanh": 1}
 BOSA_KINDS = {"policy": 0, "dynamics": 1}
-BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9}    # MOBODY_BOSA_STREAM_*
+BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9, "target_noise": 10}    # MOBODY_BOSA_STREAM_*
 
 
 def block(cls, **fields):
@@ -276,6 +276,8 @@ PROTOTYPES = {
     "mobody_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_td3bc_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp]),
     "mobody_td3bc_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp]),
+    "mobody_bosa_actor_forward": (C.c_int, [C.POINTER(MobodyActor), vp, vp]),
+    "mobody_bosa_actor_backward": (C.c_int, [C.POINTER(MobodyActor), vp, vp]),
     "mobody_iql_workspace": (i64, [C.POINTER(MobodyTrainDims)]),
     "mobody_iql_value": (C.c_int, [C.POINTER(MobodyIql), vp]),
     "mobody_iql_critic": (C.c_int, [C.POINTER(MobodyIql), vp]),
@@ -319,11 +321,14 @@ PROTOTYPES = {
     "mobody_wide_mlp3_forward": (C.c_int, [C.POINTER(MobodyWideFwd), vp]),
     "mobody_wide_mlp3_backward_workspace": (i64, [C.POINTER(MobodyWideLayout), i64]),
     "mobody_wide_mlp3_backward": (C.c_int, [C.POINTER(MobodyWideBwd), vp]),
+    "mobody_wide_mlp3_input_grad": (C.c_int, [C.POINTER(MobodyWideBwd), vp]),
     "mobody_wide_adam": (C.c_int, [C.POINTER(MobodyWideAdam), vp]),
     "mobody_bosa_workspace": (i64, [C.POINTER(MobodyBosaVae)]),
     "mobody_bosa_reparam": (C.c_int, [vp, vp, vp, i64, i32, f32, vp, vp, vp, vp, vp]),
     "mobody_bosa_vae": (C.c_int, [C.POINTER(MobodyBosaVae), vp]),
     "mobody_bosa_loglik": (C.c_int, [C.POINTER(MobodyBosaVae), vp]),
+    "mobody_bosa_loglik_grad_workspace": (i64, [C.POINTER(MobodyBosaVae)]),
+    "mobody_bosa_loglik_grad": (C.c_int, [C.POINTER(MobodyBosaVae), vp, vp]),
 }
 
 _lib = None

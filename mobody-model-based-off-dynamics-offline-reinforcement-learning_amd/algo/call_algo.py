@@ -7,9 +7,11 @@ algorithms TD3_BC (`offline_offline/td3_bc.py`), IQL (`offline_offline/iql.py`),
 (`offline_offline/igdf.py`) are built, IQL, DARA and IGDF from a config of their own only: without `lam`, `temp`, `max_step` -- for
 DARA also `gaussian_noise_std`, `dara_eta` and, when `dara_eta` is 0, `eta`; for IGDF also `xi`, `importance_weight`, `repr_dim`,
 `ensemble_size`, `repr_norm`, `ortho_init`, `info_update_step` -- the constructor raises NotImplementedError.  BOSA
-(`offline_offline/bosa.py`) is built as far as its VAE stage: the behaviour and dynamics VAEs, their checkpoints and both likelihood
-estimators; a config without one of the seventeen keys the reference reads without defaults (`vae_policy_lr` ... `update_interval`)
-raises NotImplementedError in the constructor, and so does the train() call that would enter the critic / actor stage.
+(`offline_offline/bosa.py`) is built in two parts: its VAE stage -- the behaviour and dynamics VAEs, their checkpoints and both
+likelihood estimators -- always, its critic / actor stage when config['critic_actor'] is truthy (then `gamma`, `tau`, `actor_lr` and
+`critic_lr` are required as well).  A config without one of the seventeen keys the reference reads without defaults (`vae_policy_lr`
+... `update_interval`) raises NotImplementedError in the constructor, and so does -- with `critic_actor` unset -- the train() call that
+would enter the critic / actor stage.
 """
 from .offline_offline.mobody import MOBODY
 from .offline_offline.td3_bc import TD3BC

@@ -4,9 +4,13 @@ algorithm.
 BOSA trains in two stages (bosa.py:552-639).  While `total_it < vae_iteration` a train() call only fits two VAEs on the mixed
 batch [tar(bs) | src(bs)]: a behaviour VAE over actions (`vae_policy`, VAE_Policy :23-133) and an ensemble dynamics VAE over next
 states (`vae_dyna`, VAE_Dynamics_Ensemble :203-327).  Afterwards a TD3-style critic / actor is trained, the critic masked by the
-dynamics VAE's importance-sampled log-likelihood and the actor regularised by the policy VAE's.  THIS CLASS BUILDS THE FIRST STAGE:
-the VAE steps, their checkpoints, and both likelihood estimators the second stage will consume.  A train() call that would enter
-the second stage raises NotImplementedError before it changes any state.
+dynamics VAE's importance-sampled log-likelihood and the actor regularised by the policy VAE's.  Without further keys this class
+builds the first stage -- the VAE steps, their checkpoints and both likelihood estimators -- and a train() call that would enter the
+second stage raises NotImplementedError before it changes any state.  With config['critic_actor'] truthy the second
+stage is built too: the twin-Q critic with the masked conservative seed (`mobody_bosa_critic`), the delayed actor step through
+critic_1 alone with the derivative of the policy VAE's estimator (`mobody_bosa_actor_forward / _backward`,
+`mobody_bosa_loglik_grad`), the three target nets, the reference's ten checkpoint files plus the targets', and `critic_actor_train`
+beside `vae_models_train`.  Stage-2 calls always run eagerly; config['graph'] only replays the VAE stage.
 
 Same plugin surface as the reference: `BOSA(config, device)`, `.train(src_rb, tar_rb, batch_size, writer, wandbrun)` (the
 reference's takes four arguments and its driver passes five), `.vae_policy .vae_dyna .vae_policy_optimizer .vae_dyna_optimizer`,
@@ -23,12 +27,14 @@ used by train() and are not built; EnsembleFC's unit-variance initial weights sa
 dynamics VAE (kept); `log(epsilon_dyna_exp)` masks every row until the dynamics VAE is well trained (kept).
 """
 import math
+import os
+import warnings
 
 import numpy as np
 import torch
 
 from ... import _lib, dp, ops, packing
-from .mobody import _PackedNet
+from .mobody import REFRESH_EVERY, _Adam, _PackedNet, refuse_missing_keys
 
 _KEYS = ("vae_policy_lr", "vae_policy_hidden_dim", "vae_policy_beta", "vae_dyna_lr", "vae_dyna_ensemble", "vae_dyna_hidden_dim",
          "vae_dyna_beta", "vae_iteration", "lamda_policy", "lamda_dyna", "epsilon_policy_exp", "epsilon_dyna_exp", "conservation_coef",
@@ -36,6 +42,12 @@ _KEYS = ("vae_policy_lr", "vae_policy_hidden_dim", "vae_policy_beta", "vae_dyna_
 LOG_KEYS = ("VAE_Policy/reconstruction_loss", "VAE_Policy/KL_loss", "VAE_Policy/vae_loss", "VAE_Dynamics/reconstruction_loss",
             "VAE_Dynamics/KL_loss", "VAE_Dynamics/vae_loss")
 SEED_POLICY, SEED_DYNA = 108, 109          # seed ids of the two VAEs' noise streams (101-107 are index streams)
+SEED_TARGET = 110                          # seed id of the second stage's target-noise stream (rng='device')
+STAGE2_KEYS = ("gamma", "tau", "actor_lr", "critic_lr")      # what config['critic_actor'] additionally requires
+STAGE2_LOG_KEYS = ("critic_mask_ratio", "critic_loss", "critic_td_loss", "critic_cons_loss", "actor_loss", "neg_log_beta_mean",
+                   "neg_log_beta_max", "lamda_policy")       # bosa.py:591-627, the order of the device words
+STAGE2_FILES = ("_critic_1", "_critic_1_optimizer", "_critic_2", "__critic_2_optimizer", "_actor", "_actor_optimizer")   # bosa.py:646-651
+TARGET_FILES = ("_actor_target", "_critic_1_target", "_critic_2_target")
 
 
 def vae_steps(vae_iteration):
@@ -160,6 +172,26 @@ class _WideAdam(object):
         self.t = int(float(st[0]["step"]))
 
 
+class _Member(object):
+    """critic_1 / critic_2 (Critic, bosa.py:351-366) as views of one member of the packed twin-Q net: state_dict in the reference
+    module's layout, `net.{0,2,4}.{weight,bias}`."""
+
+    def __init__(self, net, member):
+        self.net, self.member = net, member
+
+    def state_dict(self):
+        pre = self.net.prefixes[self.member]
+        return {k[len(pre):].replace("network.", "net."): v for k, v in self.net.state_dict().items() if k.startswith(pre)}
+
+    def parameters(self):
+        return list(self.state_dict().values())
+
+
+def _merge_members(net, sds):
+    """One state dict per member in the reference's layout -> what net.load_state_dict reads."""
+    return {pre + k.replace("net.", "network."): v for pre, sd in zip(net.prefixes, sds) for k, v in sd.items()}
+
+
 class BOSA(object):
     third_loss_name = "vae_dyna_loss"
 
@@ -175,6 +207,8 @@ class BOSA(object):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("BOSA (MI355X build) needs a GPU device; there is no CPU fallback")
+        if config.get("critic_actor"):                            # 5. the second stage's own keys, before anything is built
+            refuse_missing_keys("BOSA", [k for k in STAGE2_KEYS if k not in config], "config/*/bosa/*.yaml values")
         S, A = int(config["state_dim"]), int(config["action_dim"])
         self.S, self.A, self.max_action = S, A, float(config["max_action"])
         self.discount, self.tau = config.get("gamma"), config.get("tau")
@@ -203,6 +237,35 @@ class BOSA(object):
         self._graph, self._graph_key, self._graph_base = None, None, None
         self.noise_fn = None          # optional hook (tests): (kind, shape) -> fp32 array of that shape, the VAE's latent noise
         self._synced = True
+        self.critic_actor = bool(config.get("critic_actor"))
+        self._in_stage2 = False                                   # the last train() call was a stage-2 call
+        if self.critic_actor:
+            self._init_stage2(config)
+
+    def _init_stage2(self, config):
+        """Actor (bosa.py:420), critic_1 / critic_2 (:423-426) as the two members of one packed twin-Q net with ONE Adam over both
+        (the reference steps its two optimizers together, always: the same updates), and the three targets (:429-431)."""
+        S, A, dev = self.S, self.A, self.device
+        self.precision = self.actor.precision
+        if self.precision in (1, 2):
+            raise ValueError(f"BOSA's critic / actor stage runs at mfma 'f32', 'bf16x3' or 'f16x2', not {ops.default_mfma()!r}")
+        self.tau = float(config["tau"])
+        self.f16_guard = ops.check_f16_guard(config.get("f16_guard", "raise"))
+        if self.f16_guard != "off":
+            with torch.cuda.device(dev):
+                self._health = ops.health_block(dev)
+        self.critic = _PackedNet(S + A, 1, 2, ("network1.", "network2."), dev, precision=self.precision)
+        self.critic_1, self.critic_2 = _Member(self.critic, 0), _Member(self.critic, 1)
+        self.critic_optimizer = _Adam(self.critic, config["critic_lr"])
+        self.actor_optimizer = _Adam(self.actor, config["actor_lr"])
+        self.actor_target, self.critic_target = self.actor.clone().eval(), self.critic.clone().eval()
+        self.critic_1_target, self.critic_2_target = _Member(self.critic_target, 0), _Member(self.critic_target, 1)
+        self._hyp = _lib.MobodyHyper(float(config["gamma"]), self.tau, self.max_action, 1.0, 0.0, 0, 1, self.precision)
+        self._s2 = torch.zeros(8, dtype=torch.float32, device=dev)          # STAGE2_LOG_KEYS order
+        self._s2[7] = float(self.lamda_policy)
+        self._closs, self._aloss = torch.zeros(2, device=dev), torch.zeros(2, device=dev)
+        self._stats = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._s2_key, self._s2_buf = None, None
 
     # ------------------------------------------------------------------ acting
     def select_action(self, state, test=False):
@@ -219,6 +282,39 @@ class BOSA(object):
         for name, v in (("vae_policy", self.vae_policy), ("vae_dyna", self.vae_dyna)):
             if not bool(torch.isfinite(v.blob).all()):
                 raise FloatingPointError(f"{name}: non-finite parameters after {self.total_it} counts of total_it")
+        if self.critic_actor:
+            self._health_check_stage2()
+
+    def _health_check_stage2(self):
+        """The device health words, as TD3BC reads them: an f16x2 weight-range fault or a non-finite optimizer result of the actor
+        or critic has frozen every optimizer launch since.  'raise' reports it; 'fallback' moves an F16_RANGE fault to bf16x3 --
+        T blobs and planes of all four packed nets again from the intact fp32 weights -- and goes on (the host step counts are
+        not rewound: the frozen steps stay counted)."""
+        words = ops.health_bound(self.device)
+        if words is None:
+            return
+        mask, step = ops.health_read(words)
+        if mask == 0:
+            return
+        nets = (("actor", self.actor), ("critic", self.critic), ("actor_target", self.actor_target), ("critic_target", self.critic_target))
+        found = []
+        for name, n in nets:
+            m = float(ops._mlp_w2(n.blob, n.layout, n.members).abs().max())
+            if (n.precision == 4 and not (m < ops.F16_W_LIMIT)) or not bool(torch.isfinite(n.blob).all()):
+                found.append(f"{name} (max |W2| = {m:g})")
+        msg = (f"device health word {'|'.join(ops.health_bits(mask))}" + (f" at Adam step {step}" if step else "") + ": " +
+               (", ".join(found) or "no net of this object (another object on this device)") + "; the optimizer steps since were "
+               f"frozen.  f16x2 planes hold |w| < {ops.F16_W_LIMIT}: use MOBODY_MFMA=bf16x3 (or f16_guard='fallback')")
+        if self.f16_guard == "fallback" and mask == _lib.HEALTH_F16_RANGE and found:
+            warnings.warn("falling back to mfma 'bf16x3': " + msg)
+            self.precision = self._hyp.precision = ops.prec_id("bf16x3")
+            for _, n in nets:
+                n.precision = self.precision
+                ops.mlp_transpose(n.blob, n.in_dim, n.out_dim, n.members, out=n.blob_T, precision=self.precision)
+                n.version += 1
+            ops.health_clear()
+            return
+        raise FloatingPointError(msg)
 
     # ------------------------------------------------------------------ the VAE steps (bosa.py:507-550)
     def _workspace(self, vae, B, num_samples=0):
@@ -372,10 +468,14 @@ class BOSA(object):
         return True
 
     def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
-        """One call of the reference's train(), VAE stage.  total_it += 1; fewer than batch_size rows in either buffer: return;
-        draw src(bs) then tar(bs); total_it < vae_iteration: both VAE steps, and total_it += 1 once more."""
+        """One call of the reference's train() (bosa.py:552-639).  total_it += 1; fewer than batch_size rows in either buffer: return;
+        draw src(bs) then tar(bs); total_it < vae_iteration: both VAE steps, and total_it += 1 once more.  Otherwise the call belongs to
+        the critic / actor stage: with config['critic_actor'] the gather plus critic_actor_train (always eager, whatever
+        config['graph'] says), without it NotImplementedError before anything changes."""
         bs = int(batch_size)
         short = src_replay_buffer.size < bs or tar_replay_buffer.size < bs
+        if self.critic_actor and not short and not self.total_it + 1 < self.vae_iteration:
+            return self._train_stage2(src_replay_buffer, tar_replay_buffer, bs, writer)
         if not short and not self.total_it + 1 < self.vae_iteration:
             raise NotImplementedError(f"BOSA's critic / actor stage is not built: this call would leave the VAE stage (total_it "
                                       f"{self.total_it}, vae_iteration {self.vae_iteration}: {vae_steps(self.vae_iteration)} train() "
@@ -383,6 +483,7 @@ class BOSA(object):
         self.total_it += 1
         if short:
             return
+        self._in_stage2 = False
         self.total_it += 1                                          # vae_models_train's own count (bosa.py:509)
         log5k = writer is not None and self.total_it % 5000 == 0
         N = 2 * bs
@@ -404,34 +505,182 @@ class BOSA(object):
             for k, v in self._log_dict(0, 6).items():
                 writer.add_scalar(f"train/{k}", v, self.total_it)
 
+    # ------------------------------------------------------------------ the critic / actor stage (bosa.py:565-634)
+    def _stage2_buffers(self, N):
+        if self._s2_key != N:
+            dev, f = self.device, lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+            bs = N - N // 2
+            c = torch.zeros(N, dtype=torch.float32, device=dev)
+            c[N // 2:] = float(self.conservation_coef) / bs        # the seed's constant on the source rows (:597-598)
+            dims = ops.train_dims(self.S, self.A, N, N)
+            blk = self.vae_policy.block(N, self.num_samples)
+            self._s2_buf = dict(dims=dims, ws=ops.train_workspace(dims, dev), c=c, w=f(N), pi=f(N, self.A), dll=f(N, self.A), dpi=f(N, self.A),
+                                ll=f(1, N), gws=ops.bosa_loglik_grad_workspace(blk, dev), bs=bs)
+            self._s2_key = N
+        return self._s2_buf
+
+    def _noise(self, kind, shape, seed_id, stream):
+        """Normal draws of the second stage: the test hook, torch's generator (the reference's), or -- rng='device' -- a device stream."""
+        if self.noise_fn is not None:
+            return torch.as_tensor(self.noise_fn(kind, shape), dtype=torch.float32).to(self.device).contiguous()
+        if self.rng != "device":
+            return torch.randn(*shape, device=self.device)
+        self._noise_calls += 1
+        n = int(np.prod(shape))
+        return ops.rng_normal(self._seed_for(seed_id), _lib.BOSA_STREAMS[stream], self._noise_calls, n, self.device).reshape(shape)
+
+    def critic_actor_train(self, batch_mix):
+        """bosa.py:553, :565-634 on the mixed rows (state, action, next_state, reward, not_done), [tar(bs) | src(bs)]: counts total_it,
+        the masked conservative critic step, and -- when total_it % update_interval == 0 -- the actor step and the three Polyak
+        updates.  The eight logged scalars stay in device words (stage2_log() reads them).  Under rng other than 'device' the normal
+        draws come in the reference's order: target noise, dynamics estimator, policy estimator."""
+        self.total_it += 1
+        self._in_stage2, self._graph = True, None
+        b = tuple(torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous() for t in batch_mix[:5])
+        s, a, s2 = b[0], b[1], b[2]
+        b = (s, a, s2, b[3].reshape(-1, 1), b[4].reshape(-1, 1))
+        N, S, A = s.shape[0], self.S, self.A
+        z = self._stage2_buffers(N)
+        q, qt, qo, ao = self.critic, self.critic_target, self.critic_optimizer, self.actor_optimizer
+        actor_step = self.total_it % self.update_interval == 0
+        # target noise and the bootstrap value min Q_target(s', a') (:571-577)
+        noise = self._noise("target", (N, A), SEED_TARGET, "target_noise")
+        a2 = (self.actor_target(s2) + (noise * self.expl_noise).clamp(-self.noise_clip, self.noise_clip)).clamp(-self.max_action, self.max_action)
+        q_next = ops.mlp3_forward(qt.blob, S + A, 1, 2, s2, a2, blob_T=qt.blob_T, precision=qt.precision).min(0)[0].reshape(N).contiguous()
+        mask, ratio = self.dyna_mask(s, a, s2)                       # :583-591
+        self._s2[0:1].copy_(ratio.reshape(1))
+        torch.mul(mask, 0.5, out=z["w"])
+        self._keep2 = (b, q_next, mask, noise)
+        crit = (z["dims"], self._hyp, q.blob, q.blob_T, b, q_next, z["w"], z["c"], float(self.conservation_coef), z["bs"], self._closs, z["ws"])
+        if actor_step:               # gradient form, then Adam with the Polyak update: the actor step reads only the online critic
+            ops.bosa_critic(*crit, grad_q=qo.grad)
+            qo.step(target=qt, tau=self.tau)
+        else:
+            qo.t += 1
+            ops.bosa_critic(*crit, m=qo.m, v=qo.v, t=qo.t, lr=qo.lr)
+        self._s2[1:2].copy_(self._closs[0:1])
+        self._s2[3:4].copy_(self._closs[1:2])
+        torch.sub(self._closs[0:1], self._closs[1:2] * float(self.conservation_coef), out=self._s2[2:3])
+        if not actor_step:
+            return
+        act = self.actor
+        ops.bosa_actor_forward(z["dims"], self._hyp, act.blob, q.blob, s, self._stats, z["pi"], z["ws"], actor_blob_T=act.blob_T, q_blob_T=q.blob_T)
+        n, vae = self.num_samples, self.vae_policy
+        eps = None
+        if self.noise_fn is not None or self.rng != "device":
+            eps = self._noise("policy_ll", (N, n, vae.latent_dim), SEED_POLICY, "policy_ll")
+        else:
+            self._noise_calls += 1
+        blk = vae.block(N, n, state=s, action=z["pi"], eps=eps, seed=self._seed_for(SEED_POLICY), call=self._noise_calls, ll=z["ll"],
+                        workspace=z["gws"])
+        ops.bosa_loglik_grad(blk, z["dll"])
+        torch.mul(z["dll"], -float(self.lamda_policy) / N, out=z["dpi"])           # d(lamda mean(-ll)) / d pi  (:615-620)
+        ops.bosa_actor_backward(z["dims"], self._hyp, act.blob, act.blob_T, q.blob, q.blob_T, s, self._stats, z["dpi"], self._aloss, z["ws"],
+                                grad_actor=ao.grad)
+        ao.step(target=self.actor_target, tau=self.tau)
+        self._keep2 += (eps,)
+        nlb = -z["ll"][0]
+        torch.mean(nlb, dim=0, keepdim=True, out=self._s2[5:6])
+        torch.amax(nlb, dim=0, keepdim=True, out=self._s2[6:7])
+        torch.add(self._aloss[0:1], self._s2[5:6] * float(self.lamda_policy), out=self._s2[4:5])
+
+    def stage2_log(self):
+        """The reference's log_dict of the last stage-2 call (a device sync): the four critic scalars, and after an actor step the
+        four actor scalars of the latest one."""
+        x = [float(v) for v in self._s2.tolist()]
+        return dict(zip(STAGE2_LOG_KEYS[:8 if self.actor_optimizer.t else 4], x))
+
+    def _train_stage2(self, src, tar, bs, writer):
+        N = 2 * bs
+        if self._batch_key != (N,):
+            self._batch = tuple(torch.empty(N, w, device=self.device) for w in (self.S, self.A, self.S, 1, 1))
+            self._batch_key = (N,)
+        log5k = writer is not None and (self.total_it + 1) % 5000 == 0
+        if self.total_it % REFRESH_EVERY == 0 or log5k:             # TD3BC's cadence: every REFRESH_EVERY calls and on logging steps
+            self._health_check()
+        self._gather(src, tar, bs)
+        actor_call = (self.total_it + 1) % self.update_interval == 0
+        self.critic_actor_train(self._batch)
+        if log5k:                                                   # bosa.py:636-639: this call's log_dict
+            log = self.stage2_log()
+            for k in STAGE2_LOG_KEYS[:8 if actor_call else 4]:
+                writer.add_scalar(f"train/{k}", log[k], self.total_it)
+
     def losses(self):
-        """(policy-VAE loss, dynamics-VAE reconstruction loss, dynamics-VAE loss) of the last step (forces a device sync)."""
+        """(policy-VAE loss, dynamics-VAE reconstruction loss, dynamics-VAE loss) of the last step (forces a device sync); after a
+        stage-2 call (critic_loss, actor_loss, critic_td_loss)."""
+        if self._in_stage2:
+            x = self._s2.tolist()
+            return float(x[1]), float(x[4]), float(x[2])
         x = self._loss.tolist()
         return float(x[2]), float(x[3]), float(x[5])
 
     def log_line(self):
-        """The CLI's periodic line: the six VAE losses under their own names (a device sync)."""
+        """The CLI's periodic line: the six VAE losses under their own names, or the second stage's scalars (a device sync)."""
+        if self._in_stage2:
+            return " ".join(f"{k} {v:.4f}" for k, v in self.stage2_log().items())
         return " ".join(f"{k} {v:.4f}" for k, v in self._log_dict(0, 6).items())
 
     def max_train_steps(self):
-        """train() calls this build can run from a fresh object: the VAE stage's."""
+        """train() calls this build can run from a fresh object: the VAE stage's; with config['critic_actor'] there is no bound."""
+        if self.critic_actor:
+            return math.inf
         return vae_steps(self.vae_iteration)
 
     # ------------------------------------------------------------------ checkpoints (bosa.py:641-665)
     def save(self, filename):
-        """The reference's four VAE files.  Its six critic / actor files belong to the second stage and are not written."""
+        """The reference's four VAE files.  Its six critic / actor files belong to the second stage: written, with the three targets',
+        under config['critic_actor'] only (_save_stage2)."""
         self._health_check()
         torch.save(self.vae_policy.state_dict(), filename + "_vae_policy")
         torch.save(self.vae_policy_optimizer.state_dict(), filename + "_vae_policy_optimizer")
         torch.save(self.vae_dyna.state_dict(), filename + "_vae_dynamics")
         torch.save(self.vae_dyna_optimizer.state_dict(), filename + "_vae_dynamics_optimizer")
+        if self.critic_actor:
+            self._save_stage2(filename)
+
+    def _save_stage2(self, filename):
+        """The reference's six critic / actor files under its names (bosa.py:646-651, `__critic_2_optimizer` with its two
+        underscores), modules in its layout; the one Adam over both critics is written as its two halves.  And the three target nets,
+        which the reference does not save: a resumed run continues bit for bit."""
+        qs = self.critic_optimizer.state_dict()
+        half = lambda lo: dict(state={k - lo: v for k, v in qs["state"].items() if lo <= k < lo + 6},
+                               param_groups=[dict(qs["param_groups"][0], params=list(range(6)))])
+        named = lambda sd: {k.replace("network.", "net."): v for k, v in sd.items()}
+        for suffix, obj in zip(STAGE2_FILES + TARGET_FILES,
+                               (self.critic_1.state_dict(), half(0), self.critic_2.state_dict(), half(6), named(self.actor.state_dict()),
+                                self.actor_optimizer.state_dict(), named(self.actor_target.state_dict()), self.critic_1_target.state_dict(),
+                                self.critic_2_target.state_dict())):
+            torch.save(obj, filename + suffix)
+
+    def _load_stage2(self, ld, filename):
+        """Reads what _save_stage2 wrote.  A checkpoint without the three target files (the reference's ten) loads with the targets
+        copied from the online nets."""
+        unnamed = lambda sd: {k.replace("net.", "network."): v for k, v in sd.items()}
+        self.critic.load_state_dict(_merge_members(self.critic, (ld("_critic_1"), ld("_critic_2"))))
+        self.actor.load_state_dict(unnamed(ld("_actor")))
+        h1, h2 = ld("_critic_1_optimizer"), ld("__critic_2_optimizer")
+        state = dict(h1["state"])
+        state.update({k + 6: v for k, v in h2["state"].items()})
+        if len(h1["state"]) != len(h2["state"]) or (state and float(h1["state"][0]["step"]) != float(h2["state"][0]["step"])):
+            raise ValueError("critic optimizers: the two critics' step counts differ; one optimizer steps both")
+        self.critic_optimizer.load_state_dict(dict(state=state, param_groups=[dict(h1["param_groups"][0], params=list(range(12)))]))
+        self.actor_optimizer.load_state_dict(ld("_actor_optimizer"))
+        if all(os.path.exists(filename + f) for f in TARGET_FILES):
+            self.actor_target.load_state_dict(unnamed(ld("_actor_target")))
+            self.critic_target.load_state_dict(_merge_members(self.critic_target, (ld("_critic_1_target"), ld("_critic_2_target"))))
+        else:
+            self.actor_target.load_state_dict(self.actor.state_dict())
+            self.critic_target.load_state_dict(self.critic.state_dict())
 
     def load(self, filename):
         """Reads the four VAE files (the reference's load goes on to pass a file NAME to the actor optimizer's load_state_dict
-        and cannot run; the critic / actor files are the second stage's)."""
+        and cannot run; the critic / actor files are the second stage's: read with config['critic_actor'], see _load_stage2)."""
         ld = lambda s: torch.load(filename + s, map_location="cpu", weights_only=True)
         self.vae_policy.load_state_dict(ld("_vae_policy"))
         self.vae_policy_optimizer.load_state_dict(ld("_vae_policy_optimizer"))
         self.vae_dyna.load_state_dict(ld("_vae_dynamics"))
         self.vae_dyna_optimizer.load_state_dict(ld("_vae_dynamics_optimizer"))
+        if self.critic_actor:
+            self._load_stage2(ld, filename)
         self._graph = None

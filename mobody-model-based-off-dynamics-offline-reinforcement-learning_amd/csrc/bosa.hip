@@ -192,6 +192,78 @@ __global__ __launch_bounds__(256) void k_bosa_ll_reduce(LlReduceArgs a) {
   if (a.mask != nullptr) a.mask[b] = lo > a.log_eps ? 1.f : 0.f;
 }
 
+// Estimator's gradient, decoder half: one thread per row b, as k_bosa_ll_reduce.  p_k = softmax_k(w_k) from the w kept in
+// pq's first slot, the maximum subtracted as that kernel does, written into pq's second slot for the encoder half; then per action
+// column the direct term -sum_k p_k (a - u_k) / var and the decoder's seed on row k B + b (the tanh's derivative folded in); samples in
+// ascending order.  var = sd * sd with the forward's sd = (float)sqrt(beta / 4), so that the term is the derivative of the pxz the
+// forward formed (var2 = 2 sd sd there); the rounded beta / 4 differs from it in the last place.
+struct LlgSeedArgs {
+  const float *u, *action;   // [n B][A], [B][A]
+  float* pq;
+  long long B;
+  int n, A;
+  float sd, max_action;
+  float *direct, *seed;      // [B][A], [n B][A]
+};
+__global__ __launch_bounds__(256) void k_bosa_llg_seed(LlgSeedArgs a) {
+  const long long b = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (b >= a.B) return;
+  const float var = a.sd * a.sd;
+  float mx = -INFINITY;
+  for (int k = 0; k < a.n; ++k) mx = fmaxf(mx, a.pq[2 * ((long long)k * a.B + b)]);
+  float sum = 0.f;
+  for (int k = 0; k < a.n; ++k) sum += expf(a.pq[2 * ((long long)k * a.B + b)] - mx);
+  for (int k = 0; k < a.n; ++k) {
+    const long long r = (long long)k * a.B + b;
+    a.pq[2 * r + 1] = expf(a.pq[2 * r] - mx) / sum;
+  }
+  for (int j = 0; j < a.A; ++j) {
+    const float act = a.action[b * a.A + j];
+    float direct = 0.f;
+    for (int k = 0; k < a.n; ++k) {
+      const long long r = (long long)k * a.B + b;
+      const float u = a.u[r * a.A + j], y = u / a.max_action;
+      const float pr = a.pq[2 * r + 1] * ((act - u) / var);
+      direct -= pr;
+      a.seed[r * a.A + j] = pr * a.max_action * (1.f - y * y);
+    }
+    a.direct[b * a.A + j] = direct;
+  }
+}
+
+// Encoder half: one thread per latent element (b, l).  g_k = dz_k - p_k z_k; denc[b] = [sum_k g_k | pass (sum_k g_k eps_k std + 1)],
+// pass as in k_bosa_reparam.
+struct LlgEncArgs {
+  const float *enc, *z, *dz, *pq;   // [B][2 Lz], [n B][Lz], [n B][Lz], p_k in the second slot
+  EpsSrc eps;                       // [B][n][Lz]
+  long long B;
+  int n, Lz;
+  float* denc;                      // [B][2 Lz]
+};
+__global__ __launch_bounds__(256) void k_bosa_llg_enc(LlgEncArgs a) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.B * a.Lz) return;
+  const long long b = i / a.Lz;
+  const int l = (int)(i - b * a.Lz);
+  const float pre = a.enc[b * 2 * a.Lz + a.Lz + l];
+  const float std = expf(fminf(fmaxf(pre, LOG_STD_MIN), LOG_STD_MAX));
+  float gm = 0.f, gs = 0.f;
+  for (int k = 0; k < a.n; ++k) {
+    const long long r = (long long)k * a.B + b;
+    const float g = a.dz[r * a.Lz + l] - a.pq[2 * r + 1] * a.z[r * a.Lz + l];
+    gm += g;
+    gs += g * eps_at(a.eps, (b * a.n + k) * a.Lz + l) * std;
+  }
+  const bool pass = pre >= LOG_STD_MIN && pre <= LOG_STD_MAX;
+  a.denc[b * 2 * a.Lz + l] = gm;
+  a.denc[b * 2 * a.Lz + a.Lz + l] = pass ? gs + 1.f : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_bosa_llg_sum(const float* direct, const float* dxa, long long total, float* out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) out[i] = direct[i] + dxa[i];
+}
+
 __global__ __launch_bounds__(256) void k_bosa_mask_mean(const float* mask, long long B, float* out) {
   __shared__ float red[256];
   float s = 0.f;                                       // a count below 2^24: exact in any order
@@ -425,5 +497,89 @@ extern "C" int mobody_bosa_loglik(const MobodyBosaVae* a, void* stream) {
     hipLaunchKernelGGL(k_bosa_mask_mean, dim3(1), dim3(256), 0, st, (const float*)a->mask, B, a->mask_mean);
     MB_LAUNCH_OK("k_bosa_mask_mean");
   }
+  return 0;
+}
+
+// the gradient's workspace: mobody_bosa_workspace's pieces first (the forward runs on them as it is), then the pieces on n B rows
+struct BosaGradWs {
+  float *seed, *dz, *bwd, *dxa, *direct;
+  long long floats;
+};
+static void bosa_grad_carve(const BosaNets& n, long long B, int ns, float* base, BosaWs& w, BosaGradWs& g) {
+  bosa_carve(n, B, ns, base, w);
+  const long long nB = (long long)ns * B;
+  Carver take{base, w.floats};
+  g.seed = take(nB * n.D);
+  g.dz = take(nB * n.Lz);
+  g.bwd = take(2 * nB * n.dec.Hp);
+  g.dxa = take(B * n.D);
+  g.direct = take(B * n.D);
+  g.floats = take.off;
+}
+
+extern "C" int64_t mobody_bosa_loglik_grad_workspace(const MobodyBosaVae* a) {
+  BosaNets n;
+  if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyBosaVae) || a->kind != MOBODY_BOSA_POLICY || a->B < 1 || a->num_samples < 1 ||
+      a->num_samples > 64 || bosa_nets("mobody_bosa_loglik_grad_workspace", a, n))
+    return -1;
+  BosaWs w;
+  BosaGradWs g;
+  bosa_grad_carve(n, a->B, a->num_samples, nullptr, w, g);
+  return g.floats;
+}
+
+extern "C" int mobody_bosa_loglik_grad(const MobodyBosaVae* a, float* dll_da, void* stream) {
+  const char* who = "mobody_bosa_loglik_grad";
+  MB_BLOCK(who, a, MobodyBosaVae);
+  MB_REQUIRE(a->kind == MOBODY_BOSA_POLICY, "%s: kind %d: the gradient is the policy VAE's (kind 0); the dynamics estimator is only used without one", who,
+             a->kind);
+  BosaNets n;
+  int rc = bosa_common(who, a, n);
+  if (rc) return rc;
+  MB_REQUIRE(a->num_samples >= 1 && a->num_samples <= 64, "%s: num_samples %d outside [1, 64]", who, a->num_samples);
+  MB_REQUIRE(a->grad == nullptr && a->m == nullptr && a->v == nullptr, "%s: grad, m, v must be NULL: the VAE's parameters are held fixed", who);
+  MB_REQUIRE(a->blob && a->state && a->action && a->ll && a->workspace, "%s: null pointer", who);
+  MB_REQUIRE(dll_da != nullptr, "%s: dll_da is NULL", who);
+  MB_REQUIRE(a->mask_mean == nullptr || a->mask != nullptr, "%s: mask_mean needs mask", who);
+  const int ns = a->num_samples;
+  const long long B = a->B, rows = (long long)ns * B;
+  MB_REQUIRE(rows <= (1 << 21), "%s: num_samples * B = %lld > 2^21", who, rows);
+  // grids: B, B A and B Lz threads in 256s.  The layouts bound A by 64 (4 A <= 256) and B <= 2^21, so at most 2^20 workgroups: the
+  // check below cannot fail under the bounds above and states the limit the launches rely on.
+  MB_REQUIRE(cdiv(B * n.Lz, 256) <= 0x7fffffffLL, "%s: B %lld: grid of %lld workgroups", who, B, (long long)cdiv(B * n.Lz, 256));
+  BosaWs w;
+  BosaGradWs g;
+  bosa_grad_carve(n, B, ns, a->workspace, w, g);
+  if ((rc = mobody_bosa_loglik(a, stream))) return rc;      // ll, w_out; leaves x, h1, h2 of both nets, enc_out, z, u and w in the workspace
+  hipStream_t st = as_stream(stream);
+  {
+    LlgSeedArgs s{};
+    s.u = w.u; s.action = a->action; s.pq = w.pq; s.B = B; s.n = ns; s.A = n.D;
+    s.sd = (float)sqrt((double)a->beta / 4.0); s.max_action = a->max_action; s.direct = g.direct; s.seed = g.seed;
+    ProfScope scope(PROF_ROWWISE, st);
+    hipLaunchKernelGGL(k_bosa_llg_seed, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, s);
+    MB_LAUNCH_OK("k_bosa_llg_seed");
+  }
+  MobodyWideBwd bd{};
+  bd.struct_bytes = (int32_t)sizeof(bd); bd.layout = n.dec; bd.blob = a->blob + n.enc.total_floats; bd.dz3 = g.seed;
+  bd.x = w.dec_x; bd.h1 = w.dec_h1; bd.h2 = w.dec_h2; bd.x_shared = 1; bd.rows = rows;
+  bd.dx = g.dz; bd.dx_col0 = n.dec.in_dim - n.Lz; bd.dx_col1 = n.dec.in_dim; bd.workspace = g.bwd;
+  if ((rc = mobody_wide_mlp3_input_grad(&bd, stream))) return rc;
+  {
+    LlgEncArgs e{};
+    e.enc = w.enc_out; e.z = w.z; e.dz = g.dz; e.pq = w.pq; e.eps = eps_src(a, MOBODY_BOSA_STREAM_POLICY_LL);
+    e.B = B; e.n = ns; e.Lz = n.Lz; e.denc = w.denc;
+    ProfScope scope(PROF_ROWWISE, st);
+    hipLaunchKernelGGL(k_bosa_llg_enc, dim3((unsigned)cdiv(B * n.Lz, 256)), dim3(256), 0, st, e);
+    MB_LAUNCH_OK("k_bosa_llg_enc");
+  }
+  MobodyWideBwd be{};
+  be.struct_bytes = (int32_t)sizeof(be); be.layout = n.enc; be.blob = a->blob; be.dz3 = w.denc;
+  be.x = w.enc_x; be.h1 = w.enc_h1; be.h2 = w.enc_h2; be.x_shared = 1; be.rows = B;
+  be.dx = g.dxa; be.dx_col0 = a->S; be.dx_col1 = a->S + a->A; be.workspace = w.bwd;
+  if ((rc = mobody_wide_mlp3_input_grad(&be, stream))) return rc;
+  ProfScope scope(PROF_ROWWISE, st);
+  hipLaunchKernelGGL(k_bosa_llg_sum, dim3((unsigned)cdiv(B * n.D, 256)), dim3(256), 0, st, (const float*)g.direct, (const float*)g.dxa, B * n.D, dll_da);
+  MB_LAUNCH_OK("k_bosa_llg_sum");
   return 0;
 }

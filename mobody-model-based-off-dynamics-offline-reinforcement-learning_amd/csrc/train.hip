@@ -127,6 +127,39 @@ __global__ __launch_bounds__(1024) void k_actor_stats(const float* qp, const flo
   if (threadIdx.x == 0) { stats[0] = s0; stats[1] = s1; }
 }
 
+// BOSA's actor phase (bosa.py:612-629): Q is critic_1 alone.  stats[0] = sum_rows |q_0|, stats[1] = sum_rows q_0, each
+// thread adding its rows in increasing order.
+__global__ __launch_bounds__(1024) void k_bosa_actor_stats(const float* q0, long long N, float* stats) {
+  __shared__ float sm[16];
+  float s0 = 0.f, s1 = 0.f;
+  for (long long r = threadIdx.x; r < N; r += 1024) { const float q = q0[r]; s0 += fabsf(q); s1 += q; }
+  s0 = block_sum(s0, sm);
+  s1 = block_sum(s1, sm);
+  if (threadIdx.x == 0) { stats[0] = s0; stats[1] = s1; }
+}
+// the frozen critic_1's seed: dz3[row][0] = -(1 / m) / N_global, m = stats[0] / N_global (norm_q, detached, :614); padding 0
+__global__ __launch_bounds__(256) void k_bosa_q_seed(const float* stats, long long N, float ng, int Np3, float* dz3) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * Np3) return;
+  dz3[i] = i % Np3 == 0 ? -(1.f / (stats[0] / ng)) / ng : 0.f;
+}
+// the actor's seed: d(pre-tanh)[row][j] = (dq/da + dpi_extra) * max_action (1 - (pi / max_action)^2), padding 0; thread 0 also leaves
+// the pair (sum -q_0, 0) that LossFinal kind 2 turns into -(1 / m) stats[1] / N_global
+__global__ __launch_bounds__(256) void k_bosa_actor_seed(const float* dxa, const float* extra, const float* pi, const float* stats,
+                                                         long long N, int A, int Np3, float max_action, float* dz3, float* lossp) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) { lossp[0] = -stats[1]; lossp[1] = 0.f; }
+  if (i >= N * Np3) return;
+  const long long row = i / Np3;
+  const int j = (int)(i - row * Np3);
+  float v = 0.f;
+  if (j < A) {
+    const float y = pi[row * A + j] / max_action;
+    v = (dxa[row * A + j] + extra[row * A + j]) * max_action * (1.f - y * y);
+  }
+  dz3[i] = v;
+}
+
 // expectile regression of V towards min target-Q (update_v_function, mobody.py:231-242; asymmetric_l2_loss :85-86):
 // adv = min(Qt1,Qt2)(s,a) - V(s); L_V = mean(|0.7 - 1[adv<0]| * adv^2); dz3[row][0] = dL/dV
 __global__ __launch_bounds__(256) void k_v_loss(const float* qt, const float* v, long long N, float invNg, int Np3,
@@ -530,6 +563,87 @@ extern "C" int mobody_td3bc_actor_backward(const MobodyActor* a, void* stream) {
   MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
   MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
   return actor_backward_impl(*a, stream, who, true);
+}
+
+// ---- BOSA's actor phase (bosa.py:612-629): Q = critic_1 (member 0) alone, and the estimator's term arrives as a
+// per-element addend dpi_extra.  Existing launches in seed mode 0 -- dz3 read from memory -- between three row-wise kernels; each
+// launch reads what the one before it on the stream wrote, nothing waits inside a kernel. ----
+static constexpr unsigned BOSA_ACTOR_PREC = 1u << PREC_F32 | 1u << PREC_BF16X3 | 1u << PREC_F16X2;
+static int bosa_actor_check(const MobodyActor* a, const char* who) {
+  MB_BLOCK(who, a, MobodyActor);
+  int rc = check_dims(&a->d, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->d.N <= (1 << 21), "%s: d.N %lld > 2^21", who, (long long)a->d.N);
+  MB_REQUIRE(a->v_true == nullptr, "%s: v_true given: there is no V function", who);
+  MB_REQUIRE(a->policy_ready == 0, "%s: policy_ready %d: pi(s) is evaluated here", who, a->policy_ready);
+  return check_precision(who, a->h.precision, a->actor_blob_T && a->q_blob_T, BOSA_ACTOR_PREC);
+}
+
+extern "C" int mobody_bosa_actor_forward(const MobodyActor* a, float* pi_out, void* stream) {
+  const char* who = "mobody_bosa_actor_forward";
+  int rc = bosa_actor_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE(a->actor_blob && a->q_blob && a->state && a->stats && a->workspace, "%s: null pointer", who);
+  MB_REQUIRE(pi_out != nullptr, "%s: pi_out is NULL", who);
+  const MobodyTrainDims* d = &a->d;
+  const MobodyHyper* h = &a->h;
+  const int prec = h->precision;
+  const float *aT = prec != PREC_F32 ? a->actor_blob_T : nullptr, *qT = prec != PREC_F32 ? a->q_blob_T : nullptr;
+  TrainWs w;
+  rc = carve(*d, a->workspace, w);
+  if (rc) return rc;
+  hipStream_t st = as_stream(stream);
+  const long long N = d->N;
+  const int S = d->S, A = d->A;
+  const Mlp3FwdArgs fpi = fwd_args(a->actor_blob, w.La, a->state, S, nullptr, 0, N, w.pi, 1, h->max_action, w.xa, w.h1a, w.h2a, w.ma1, w.ma2, aT,
+                                   prec == PREC_F16X2 ? w.eh1a : nullptr);
+  // member 0 of the twin-Q blob: a one-member launch; dQ/da through the frozen net needs only the ReLU signs
+  const Mlp3FwdArgs fq = fwd_args(a->q_blob, w.Lq, a->state, S, w.pi, A, N, w.q, 0, 1.f, nullptr, nullptr, nullptr, w.mq1, w.mq2, qT);
+  rc = launch_mlp3_forward(fpi, 1, ACT_RELU, prec, st);
+  if (!rc) rc = launch_mlp3_forward(fq, 1, ACT_RELU, prec, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_bosa_actor_stats, dim3(1), dim3(1024), 0, st, (const float*)w.q, N, a->stats);
+  MB_LAUNCH_OK("k_bosa_actor_stats");
+  const hipError_t e = hipMemcpyAsync(pi_out, w.pi, sizeof(float) * N * A, hipMemcpyDeviceToDevice, st);
+  if (e != hipSuccess) return fail(MOBODY_E_LAUNCH, "%s: hipMemcpyAsync: %s", who, hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int mobody_bosa_actor_backward(const MobodyActor* a, const float* dpi_extra, void* stream) {
+  const char* who = "mobody_bosa_actor_backward";
+  int rc = bosa_actor_check(a, who);
+  if (rc) return rc;
+  MB_REQUIRE((a->grad_actor != nullptr) != (a->m != nullptr || a->v != nullptr), "%s: exactly one of grad_actor and the optimizer state m, v must be given", who);
+  MB_REQUIRE(a->grad_actor || (a->m && a->v), "%s: null pointer", who);
+  MB_REQUIRE(a->actor_blob && a->actor_blob_T && a->q_blob && a->q_blob_T && a->state && a->stats && a->loss_out && a->workspace, "%s: null pointer", who);
+  MB_REQUIRE(dpi_extra != nullptr, "%s: dpi_extra is NULL", who);
+  const bool fused = a->m != nullptr;
+  MB_REQUIRE(!fused || a->t_dev != nullptr || a->t >= 1, "%s: step t must be >= 1", who);
+  const MobodyTrainDims* d = &a->d;
+  const MobodyHyper* h = &a->h;
+  const int prec = h->precision;
+  TrainWs w;
+  rc = carve(*d, a->workspace, w);
+  if (rc) return rc;
+  const AdamTarget adam = fused ? adam_target(a->actor_blob, a->actor_blob_T, a->m, a->v, nullptr, a->t, a->t_dev, a->lr, -1.f, 1.f, prec) : AdamTarget{};
+  hipStream_t st = as_stream(stream);
+  const long long N = d->N;
+  const float ng = (float)d->N_global;
+  hipLaunchKernelGGL(k_bosa_q_seed, dim3((unsigned)cdiv(N * w.Lq.Np3, 256)), dim3(256), 0, st, (const float*)a->stats, N, ng, w.Lq.Np3, w.dz3q);
+  MB_LAUNCH_OK("k_bosa_q_seed");
+  // dq_0/da through the frozen critic_1 (its parameters take no gradient): member 0 alone, sign words, no dz2 / dz1
+  Mlp3BwdArgs bq = bwd_args(w.Lq, a->q_blob_T, w.dz3q, nullptr, nullptr, N, nullptr, nullptr, w.dbp, w.mq1, w.mq2, prec);
+  bq.dx = w.dxa; bq.dx_c0 = d->S; bq.dx_n = d->A;
+  if ((rc = launch_mlp3_bwd(bq, 1, true, st))) return rc;
+  hipLaunchKernelGGL(k_bosa_actor_seed, dim3((unsigned)cdiv(N * w.La.Np3, 256)), dim3(256), 0, st, (const float*)w.dxa, dpi_extra, (const float*)w.pi,
+                     (const float*)a->stats, N, d->A, w.La.Np3, h->max_action, w.dz3a, w.lossp);
+  MB_LAUNCH_OK("k_bosa_actor_seed");
+  const Mlp3BwdArgs ba = bwd_args(w.La, a->actor_blob_T, w.dz3a, w.h1a, w.h2a, N, w.dz2, w.dz1, w.dbp, w.ma1, w.ma2, prec, w.edz2);
+  if ((rc = launch_mlp3_bwd(ba, 1, false, st))) return rc;
+  LossFinal lf{};                                  // kind 2 on one pair: loss_out[0] = (1 / m) (-stats[1]) / N_global, loss_out[1] = 0
+  lf.kind = 2; lf.nparts = 1; lf.scale_q = 1; lf.weight = 1.f; lf.bc_coef = 0.f; lf.ng = ng; lf.ntg_a = 1.f;
+  lf.parts = w.lossp; lf.stats = a->stats; lf.out = a->loss_out;
+  return weight_grads(w.La, w.xa, w.h1a, w.h2a, w.eh1a, w.dz3a, N, w, a->grad_actor, lf, adam, prec, st);
 }
 
 // ---- IQL (the reference's algo/offline_offline/iql.py): V with the expectile seed, twin-Q against V(s') through critic_impl, the

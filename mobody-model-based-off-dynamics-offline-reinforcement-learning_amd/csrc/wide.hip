@@ -171,6 +171,44 @@ static int check_wide_layout(const char* who, const MobodyWideLayout* L) {
   return 0;
 }
 
+// The three products of the input-gradient chain, shared by mobody_wide_mlp3_backward and mobody_wide_mlp3_input_grad (the same
+// problems, so the same bits).  dz2 = (dz3 W3^T) [h2 > 0]
+static WideGemm gemm_dz2(const MobodyWideBwd* a, float* dz2) {
+  const MobodyWideLayout& L = a->layout;
+  const long long rows = a->rows, act = rows * L.Hp;
+  WideGemm g{};
+  g.A = a->dz3; g.sAe = rows * L.out_dim; g.sAm = L.out_dim; g.sAk = 1;
+  g.B = a->blob + L.w3; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Np3;
+  g.C = dz2; g.sCe = act; g.ldc = L.Hp;
+  g.M = g.MA = (int)rows; g.N = g.NB = L.Hp; g.K = L.out_dim;
+  g.epi = WEPI_RELU_MASK; g.mask = a->h2; g.sme = act; g.ldmask = L.Hp;
+  return g;
+}
+// dz1 = (dz2 W2^T) [h1 > 0]
+static WideGemm gemm_dz1(const MobodyWideBwd* a, const float* dz2, float* dz1) {
+  const MobodyWideLayout& L = a->layout;
+  const long long rows = a->rows, act = rows * L.Hp;
+  WideGemm g{};
+  g.A = dz2; g.sAe = act; g.sAm = L.Hp; g.sAk = 1;
+  g.B = a->blob + L.w2; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Hp;
+  g.C = dz1; g.sCe = act; g.ldc = L.Hp;
+  g.M = g.MA = (int)rows; g.N = g.NB = L.Hp; g.K = L.Hp;
+  g.epi = WEPI_RELU_MASK; g.mask = a->h1; g.sme = act; g.ldmask = L.Hp;
+  return g;
+}
+// dX[:, col0:col1] = dz1 W1[col0:col1, :]^T
+static WideGemm gemm_dx(const MobodyWideBwd* a, const float* dz1) {
+  const MobodyWideLayout& L = a->layout;
+  const long long rows = a->rows, act = rows * L.Hp;
+  const int w = a->dx_col1 - a->dx_col0;
+  WideGemm g{};
+  g.A = dz1; g.sAe = act; g.sAm = L.Hp; g.sAk = 1;
+  g.B = a->blob + L.w1 + (long long)a->dx_col0 * L.Hp; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Hp;
+  g.C = a->dx; g.sCe = rows * w; g.ldc = w;
+  g.M = g.MA = (int)rows; g.N = g.NB = w; g.K = L.Hp; g.epi = WEPI_STORE;
+  return g;
+}
+
 }  // namespace mobody
 
 using namespace mobody;
@@ -298,26 +336,14 @@ extern "C" int mobody_wide_mlp3_backward(const MobodyWideBwd* a, void* stream) {
   g.C = a->grad + L.w3; g.sCe = L.member_floats; g.ldc = L.Np3;
   g.M = g.MA = L.Hp; g.N = L.Np3; g.NB = L.out_dim; g.K = (int)rows; g.epi = WEPI_STORE;
   if ((rc = launch_wide_gemm(g, E, st, PROF_WGRAD))) return rc;
-  // dz2 = (dz3 W3^T) [h2 > 0]
-  g.A = a->dz3; g.sAe = rows * L.out_dim; g.sAm = L.out_dim; g.sAk = 1;
-  g.B = a->blob + L.w3; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Np3;
-  g.C = dz2; g.sCe = act; g.ldc = L.Hp;
-  g.M = g.MA = (int)rows; g.N = g.NB = L.Hp; g.K = L.out_dim;
-  g.epi = WEPI_RELU_MASK; g.mask = a->h2; g.sme = act; g.ldmask = L.Hp;
-  if ((rc = launch_wide_gemm(g, E, st, PROF_MLP_BWD))) return rc;
+  if ((rc = launch_wide_gemm(gemm_dz2(a, dz2), E, st, PROF_MLP_BWD))) return rc;
   // dW2 = h1^T dz2
   g.A = a->h1; g.sAe = act; g.sAm = 1; g.sAk = L.Hp;
   g.B = dz2; g.sBe = act; g.sBk = L.Hp; g.sBn = 1;
   g.C = a->grad + L.w2; g.sCe = L.member_floats; g.ldc = L.Hp;
   g.M = g.MA = L.Hp; g.N = g.NB = L.Hp; g.K = (int)rows; g.epi = WEPI_STORE;
   if ((rc = launch_wide_gemm(g, E, st, PROF_WGRAD))) return rc;
-  // dz1 = (dz2 W2^T) [h1 > 0]
-  g.A = dz2; g.sAe = act; g.sAm = L.Hp; g.sAk = 1;
-  g.B = a->blob + L.w2; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Hp;
-  g.C = dz1; g.sCe = act; g.ldc = L.Hp;
-  g.M = g.MA = (int)rows; g.N = g.NB = L.Hp; g.K = L.Hp;
-  g.epi = WEPI_RELU_MASK; g.mask = a->h1;
-  if ((rc = launch_wide_gemm(g, E, st, PROF_MLP_BWD))) return rc;
+  if ((rc = launch_wide_gemm(gemm_dz1(a, dz2, dz1), E, st, PROF_MLP_BWD))) return rc;
   // dW1 = x^T dz1
   g.A = a->x; g.sAe = a->x_shared ? 0 : rows * L.Kp1; g.sAm = 1; g.sAk = L.Kp1;
   g.B = dz1; g.sBe = act; g.sBk = L.Hp; g.sBn = 1;
@@ -334,15 +360,30 @@ extern "C" int mobody_wide_mlp3_backward(const MobodyWideBwd* a, void* stream) {
     hipLaunchKernelGGL(k_wide_bias, dim3((unsigned)((L.Hp > L.Np3 ? L.Hp : L.Np3) / 32), 3, (unsigned)E), dim3(256), 0, st, b);
     MB_LAUNCH_OK("k_wide_bias");
   }
-  if (want_dx) {                                   // dX[:, col0:col1] = dz1 W1[col0:col1, :]^T
-    const int w = a->dx_col1 - a->dx_col0;
-    g.A = dz1; g.sAe = act; g.sAm = L.Hp; g.sAk = 1;
-    g.B = a->blob + L.w1 + (long long)a->dx_col0 * L.Hp; g.sBe = L.member_floats; g.sBk = 1; g.sBn = L.Hp;
-    g.C = a->dx; g.sCe = rows * w; g.ldc = w;
-    g.M = g.MA = (int)rows; g.N = g.NB = w; g.K = L.Hp; g.epi = WEPI_STORE;
-    if ((rc = launch_wide_gemm(g, E, st, PROF_MLP_BWD))) return rc;
-  }
+  if (want_dx && (rc = launch_wide_gemm(gemm_dx(a, dz1), E, st, PROF_MLP_BWD))) return rc;
   return 0;
+}
+
+extern "C" int mobody_wide_mlp3_input_grad(const MobodyWideBwd* a, void* stream) {
+  const char* who = "mobody_wide_mlp3_input_grad";
+  MB_BLOCK(who, a, MobodyWideBwd);
+  int rc = check_wide_layout(who, &a->layout);
+  if (rc) return rc;
+  const MobodyWideLayout& L = a->layout;
+  MB_REQUIRE(a->precision == PREC_F32, "%s: precision %d: the wide nets run in exact fp32 (precision 0) only", who, a->precision);
+  MB_REQUIRE(a->rows >= 1 && a->rows <= (1 << 21), "%s: rows %lld outside [1, 2^21]", who, (long long)a->rows);
+  MB_REQUIRE(a->grad == nullptr, "%s: grad must be NULL: the parameter gradient is mobody_wide_mlp3_backward's", who);
+  MB_REQUIRE(a->dx != nullptr, "%s: dx is NULL: the input gradient is all this entry writes", who);
+  MB_REQUIRE(a->blob && a->dz3 && a->h1 && a->h2 && a->workspace, "%s: null pointer", who);
+  MB_REQUIRE(a->x_shared == 0 || a->x_shared == 1, "%s: x_shared %d", who, a->x_shared);
+  MB_REQUIRE(a->dx_col0 >= 0 && a->dx_col0 < a->dx_col1 && a->dx_col1 <= L.in_dim, "%s: dx columns [%d, %d) outside [0, %d)", who, a->dx_col0,
+             a->dx_col1, L.in_dim);
+  const int E = L.members;
+  float *dz2 = a->workspace, *dz1 = a->workspace + E * a->rows * L.Hp;
+  hipStream_t st = as_stream(stream);
+  if ((rc = launch_wide_gemm(gemm_dz2(a, dz2), E, st, PROF_MLP_BWD))) return rc;
+  if ((rc = launch_wide_gemm(gemm_dz1(a, dz2, dz1), E, st, PROF_MLP_BWD))) return rc;
+  return launch_wide_gemm(gemm_dx(a, dz1), E, st, PROF_MLP_BWD);
 }
 
 extern "C" int mobody_wide_adam(const MobodyWideAdam* a, void* stream) {

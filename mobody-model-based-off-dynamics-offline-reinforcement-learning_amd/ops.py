@@ -366,6 +366,22 @@ def td3bc_actor_update(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, st
     check(load().mobody_td3bc_actor_backward(C.byref(blk), cur_stream()), "mobody_td3bc_actor_backward")
 
 
+# BOSA actor phase (bosa.py:612-629): the same block and workspace; Q is member 0 alone and the estimator's term is an addend
+def bosa_actor_forward(dims, hyp, actor_blob, q_blob, state, stats, pi_out, ws, actor_blob_T=None, q_blob_T=None):
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, None, stats, ws)
+    check(load().mobody_bosa_actor_forward(C.byref(blk), ptr(pi_out), cur_stream()), "mobody_bosa_actor_forward")
+
+
+def bosa_actor_backward(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, stats, dpi_extra, loss_out, ws, grad_actor=None,
+                        m=None, v=None, t=0, t_dev=None, lr=0.0):
+    """dpi_extra [N, A]: what the rest of the loss adds to d loss / d pi (BOSA: -(lamda / N) dll_da).  grad_actor: the gradient form;
+    m, v: Adam fused.  loss_out[0] = -mean(q_0) / mean|q_0|, loss_out[1] = 0."""
+    blk = _actor_block(dims, hyp, actor_blob, actor_blob_T, q_blob, q_blob_T, state, None, stats, ws)
+    blk.grad_actor, blk.loss_out = ptr(grad_actor), ptr(loss_out)
+    blk.m, blk.v, blk.t, blk.t_dev, blk.lr = ptr(m), ptr(v), int(t), ptr(t_dev), float(lr)
+    check(load().mobody_bosa_actor_backward(C.byref(blk), ptr(dpi_extra), cur_stream()), "mobody_bosa_actor_backward")
+
+
 # IQL (iql.py): one block type for the three calls of the step (MobodyIql); `nets` = (v_func, q_funcs, target_q_funcs, policy)
 # as objects with .blob / .blob_T, `opt` the Adam state of the net the call trains (m, v given: fused form; grad: gradient form)
 def iql_workspace(dims, device):
@@ -1035,3 +1051,32 @@ def bosa_vae(blk):
 
 def bosa_loglik(blk):
     check(load().mobody_bosa_loglik(C.byref(blk), cur_stream()), "mobody_bosa_loglik")
+
+
+def wide_mlp3_input_grad(blob, L, dz3, h1, h2, dx_cols, ws=None, precision=0, x_shared=True):
+    """d loss / d x[:, c0:c1] of a wide net whose parameters are held fixed, as [members, rows, c1 - c0]: the three input-gradient
+    products of wide_mlp3_backward without its weight gradients, so the same bits.  x_shared: the block's field, as the forward that
+    saved h1 / h2 had it (x itself is not read)."""
+    rows, dev, E = dz3.shape[1], blob.device, L.members
+    need = load().mobody_wide_mlp3_backward_workspace(C.byref(L), rows)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    c0, c1 = dx_cols
+    assert 0 <= c0 < c1 <= L.in_dim, dx_cols
+    dx = torch.empty(E, rows, c1 - c0, dtype=torch.float32, device=dev)
+    a = _lib.block(_lib.MobodyWideBwd, precision=prec_id(precision), layout=L, blob=ptr(blob), dz3=ptr(dz3), h1=ptr(h1), h2=ptr(h2),
+                   x_shared=int(bool(x_shared)), rows=rows, dx=ptr(dx), dx_col0=c0, dx_col1=c1, workspace=ptr(ws))
+    check(load().mobody_wide_mlp3_input_grad(C.byref(a), cur_stream()), "mobody_wide_mlp3_input_grad")
+    return dx
+
+
+def bosa_loglik_grad_workspace(blk, device):
+    n = load().mobody_bosa_loglik_grad_workspace(C.byref(blk))
+    if n < 0:
+        raise _lib.MobodyError("mobody_bosa_loglik_grad_workspace: bad block: " + load().mobody_last_error().decode(errors="replace"))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bosa_loglik_grad(blk, dll_da):
+    """The policy VAE's estimator (blk.ll, blk.w_out as bosa_loglik writes them) and dll_da [B, A] = d ll / d blk.action."""
+    check(load().mobody_bosa_loglik_grad(C.byref(blk), ptr(dll_da), cur_stream()), "mobody_bosa_loglik_grad")

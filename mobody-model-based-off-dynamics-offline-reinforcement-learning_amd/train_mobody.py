@@ -425,7 +425,8 @@ def _run(args, rank, world, device):
     terminal_fn = get_termination_fn(task)
     policy = call_algo(args.policy, config, args.mode, device, terminal_fn=terminal_fn)
     if hasattr(policy, "max_train_steps") and int(config["max_step"]) > policy.max_train_steps():
-        # BOSA: only the VAE stage is built; refuse the run now, not after vae_iteration // 2 steps of training
+        # BOSA without config['critic_actor']: only the VAE stage runs; refuse the run now, not after vae_iteration // 2 steps of
+        # training (with the key there is no bound)
         raise SystemExit(f"--policy {args.policy}: --max_step {config['max_step']} runs past the VAE stage (vae_iteration "
                          f"{config['vae_iteration']}); the critic / actor stage is not built: the largest max_step is "
                          f"{policy.max_train_steps()}")
@@ -495,7 +496,7 @@ def _run(args, rank, world, device):
     for t in range(int(config["max_step"])):
         policy.train(src_rb, tar_rb, config["batch_size"], writer, None)
         if (t + 1) % args.log_every == 0:
-            if hasattr(policy, "log_line"):           # BOSA's VAE stage: its own losses under their own names
+            if hasattr(policy, "log_line"):           # BOSA: the stage's own losses under their own names
                 line = policy.log_line()
             else:
                 if world > 1:                         # losses() is this rank's share of the global means (kernels scale by
