@@ -153,10 +153,23 @@ def dyna_mask(enc, dec, s, a, s2, eps, beta, epsilon):
 
 # the cases of tests/test_hip_bosa_stage2.py's mode-9 check: walker shapes, rows one past one and past eight 32-row tiles
 MODE9_S, MODE9_A, MODE9_ROWS, MODE9_COEF = 17, 6, (33, 257), 0.1
+# the row edges at walker shapes (the smallest N, exact 32-row tiles, the product's 256, 1024 and one past it) and other widths at
+# N = 65 (a narrow net, pen's A = 24, ant's S = 111): (N, (S, A)), tests/bosa_actor_cases.py's EDGE_CASES
+MODE9_EDGE_CASES = [(N, (MODE9_S, MODE9_A)) for N in (2, 32, 64, 256, 1024, 1025)] + [(65, SA) for SA in ((11, 3), (45, 24), (111, 8))]
 
 
-def mode9_case(N, rows):
-    """(rows[:N] of the five batch arrays, q_next [N], w [N] = BOSA's mask / 2, c [N]: coef / source rows on the second half)."""
+def mode9_params(SA=(MODE9_S, MODE9_A)):
+    """The twin-Q state dict of the mode-9 cases at (S, A)."""
+    import iql_ref as IR
+    return IR.iql_params(SA[0], SA[1], 431, 16.0)[1]
+
+
+def mode9_case(N, rows=None, SA=(MODE9_S, MODE9_A), seed=501):
+    """(rows[:N] of the five batch arrays, q_next [N], w [N] = BOSA's mask / 2, c [N]: coef / source rows on the second half).
+    rows None: the seeded batch at (S, A) = SA."""
+    if rows is None:
+        import golden_util as gu
+        rows = gu.gi.batch(seed, max(N, 64), SA[0], SA[1])
     rows = [np.asarray(x[:N]) for x in rows]
     rng = np.random.default_rng(N)
     q_next = rng.standard_normal(N).astype(np.float32) * np.float32(3)

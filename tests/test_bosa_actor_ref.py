@@ -1,7 +1,10 @@
 """CPU checks for BOSA's actor phase and stage-2 step: the new entries' declarations, that every refusal of theirs comes
 before any runtime call (nothing is launched here) with its field named, the gradient workspace against its closed form, the keyed
 constructor's missing-key refusals, and the precondition of the GPU tests' normalised tolerances -- a float32 evaluation of the fp64
-restatement on the GPU tests' exact inputs stays within half of them."""
+restatement on the GPU tests' exact inputs stays within half of them: at the fixture variants' shapes and at every wide, edge and
+product-batch case of tests/bosa_actor_cases.py and bosa2_ref.MODE9_EDGE_CASES.  The offsets through which the GPU tests read p_k, the
+encoder's seed and the actor's seed out of the two workspaces are partial sums of closed forms that are held against the library's
+totals here, at the old shape and at new ones."""
 import ctypes as C
 import os
 import re
@@ -132,6 +135,31 @@ def test_loglik_grad_workspace_closed_form(lib, n):
     assert lib.mobody_bosa_loglik_grad_workspace(C.byref(blk)) == base + r4(nB * A) + r4(nB * Lz) + r4(2 * nB * Hp) + 2 * r4(B * A)
 
 
+@pytest.mark.parametrize("shape,B,n", [((17, 6, 72), 33, 3), ((45, 24, 750), 64, 4), ((128, 64, 1024), 17, 2), ((3, 1, 8), 4, 64), ((1, 1, 8), 33, 3)])
+def test_workspace_offsets_the_gpu_tests_read_through_add_up_to_the_library_totals(lib, shape, B, n):
+    """The GPU tests read p_k (pq's second slot) and the encoder's seed out of the estimator's workspace at offsets that depend on
+    (S, A, H, B, n) through the layouts' Kp1 and Hp: tests/bosa_actor_cases.py's closed form, of which those offsets are partial
+    sums, gives the library's totals at the old shape and at new ones (pen at the product's width, the largest policy VAE, n = 64,
+    the smallest layout)."""
+    from mobody_amd import _lib
+    S, A, H = shape
+    blk = _lib.block(_lib.MobodyBosaVae, kind=0, S=S, A=A, hidden=H, members=1, B=B, beta=0.5, max_action=1.0, num_samples=n)
+    base, grad = BC.bosa_workspace_floats(S, A, H, B, n)
+    assert lib.mobody_bosa_workspace(C.byref(blk)) == base and lib.mobody_bosa_loglik_grad_workspace(C.byref(blk)) == grad
+    assert 0 < BC.denc_offset(S, A, H, B, n) < BC.pq_offset(S, A, H, B, n) == base - ((2 * n * B + 3) & ~3)
+
+
+@pytest.mark.parametrize("S,A,N", [(17, 6, 33), (17, 6, 2), (17, 6, 256), (17, 6, 1025), (11, 3, 65), (45, 24, 65), (111, 8, 65)])
+def test_train_workspace_offset_of_the_actor_seed_adds_up_to_the_library_total(lib, S, A, N):
+    """dz3a_offset depends on (S, A, N) through the layouts' Kp1 / Np3 and the 32-row tiles: the closed form it is a partial sum of
+    gives mobody_train_workspace at the old shape and at the new row edges and widths."""
+    from mobody_amd import _lib
+    d = _lib.MobodyTrainDims(S, A, N, N, N, N)
+    assert lib.mobody_train_workspace(C.byref(d)) == BC.train_workspace_floats(S, A, N)
+    off, Np3 = BC.dz3a_offset(S, A, N)
+    assert Np3 > A and off % 4 == 0                 # every case has padding columns, which the GPU test holds at exactly 0
+
+
 @pytest.mark.parametrize("entry", ("mobody_bosa_actor_forward", "mobody_bosa_actor_backward"))
 def test_actor_refusals_come_before_any_runtime_call(lib, entry):
     from mobody_amd import _lib
@@ -193,6 +221,104 @@ def test_float32_estimator_gradient_within_half_the_gpu_tolerance():
         assert np.abs(ex["direct"]).max() > 1e-3 * np.abs(d64).max() and np.abs(ex["dxa"]).max() > 1e-3 * np.abs(d64).max(), c
     print("float32 dll_da: worst error / tolerance %.4f; ll: %.4f" % (worst_d, worst_ll))
     assert worst_d <= 0.5 and worst_ll <= 0.5
+
+
+def test_float32_estimator_gradient_within_half_the_gpu_tolerance_at_the_wide_cases():
+    """The same at tests/bosa_actor_cases.py's LLG_WIDE_CASES (the product's shape, exact tiles, workgroup edges, the largest n, the
+    corners of the policy VAE's layout, beta 0.05).  At B up to 513 some pre-clamp log_std comes nearer to -4 than 1e-4 (1.8e-5 at
+    (17, 6, 72), B 256), so the gate's margin is held against the float32 evaluation's own error of that value instead: no
+    pre-clamp log_std lies within eight times the largest |pre32 - pre64| of the case of a clamp edge, and both evaluations pass the
+    same columns.  The peaked cases are what their name says: against the same inputs at beta 0.5 the weights of a row spread
+    further, the largest |w| is more than four times and the direct term more than nine times as large."""
+    worst_d = worst_ll = 0.0
+    for c in BC.LLG_WIDE_CASES:
+        shape, n, B, ma, beta = c
+        _, _, _, enc, dec, s, a, eps = BC.llg_case(*c)
+        d64, ll64, ex = BC.llg_reference(*c)
+        d32, ll32, ex32 = B2.loglik_grad_action(enc, dec, s, a, eps, beta, ma, dtype=np.float32)
+        margin = min(np.abs(ex["pre"] + 4).min(), np.abs(ex["pre"] - 15).min())
+        pre_err = np.abs(ex32["pre"] - ex["pre"]).max()
+        passes = lambda pre: (pre >= -4) & (pre <= 15)
+        assert margin > 8 * pre_err and np.array_equal(passes(ex["pre"]), passes(ex32["pre"])), (c, margin, pre_err)
+        tol_d, tol_ll = BC.llg_tolerances(d64, ll64, ex["w"])
+        rd, rl = (np.abs(d32 - d64) / tol_d).max(), (np.abs(ll32 - ll64) / tol_ll).max()
+        print("%s: float32 dll_da error / tolerance %.4f, ll %.4f; clamp margin %.2e (float32 error of pre %.1e)" % (BC.llg_id(c), rd, rl, margin, pre_err))
+        worst_d, worst_ll = max(worst_d, rd), max(worst_ll, rl)
+        if n == 1:
+            assert (ex["p"] == 1.0).all()
+        assert np.abs(ex["direct"]).max() > 1e-3 * np.abs(d64).max() and np.abs(ex["dxa"]).max() > 1e-3 * np.abs(d64).max(), c
+        if beta == BC.PEAKED_BETA:
+            base = BC.llg_reference(shape, n, B, ma)[2]
+            spread = lambda w: (w.max(0) - w.min(0)).max()
+            assert spread(ex["w"]) > spread(base["w"]) and np.abs(ex["w"]).max() > 4 * np.abs(base["w"]).max()
+            assert np.abs(ex["direct"]).max() > 9 * np.abs(base["direct"]).max()
+    print("float32 dll_da: worst error / tolerance %.4f; ll: %.4f" % (worst_d, worst_ll))
+    assert worst_d <= 0.5 and worst_ll <= 0.5
+
+
+def _float32_actor_ratios(N, SA, qcut):
+    """(d(pre-tanh), gradient, pi, loss head) of a float32 evaluation of the actor step, each as error / tolerance."""
+    logs64, g64, ex64 = BC.actor_reference(N, 1.0, 0.0, qcut=qcut, SA=SA)
+    logs32, g32, ex32 = BC.actor_reference(N, 1.0, 0.0, dtype=np.float32, qcut=qcut, SA=SA)
+    d64, d32 = BC.pre_tanh_seed(ex64, 1.0), BC.pre_tanh_seed(ex32, 1.0, np.float32)
+    tol = B2.grad_tolerance(g64)
+    head = -ex64["norm_q"] * ex64["q"].mean()
+    if qcut:
+        assert 0.2 < (ex64["q"] < 0).mean() < 0.3 and abs(head) < 0.9
+    return ((np.abs(d32 - d64) / BC.seed_tolerance(d64)).max(), max((np.abs(g32[k] - g64[k]) / tol[k]).max() for k in WR.KEYS),
+            (np.abs(ex32["pi"] - ex64["pi"]) / (1e-5 + 1e-5 * np.abs(ex64["pi"]))).max(),
+            abs(float(-ex32["norm_q"] * ex32["q"].mean()) - head) / (1e-5 * abs(head)))
+
+
+@pytest.mark.parametrize("c", BC.EDGE_CASES, ids=BC.edge_id)
+def test_float32_actor_step_within_half_the_gpu_tolerance_at_the_edges(c):
+    """tests/bosa_actor_cases.py's EDGE_CASES, with the qcut = 0.25 variant where the GPU test runs it."""
+    N, SA = c
+    for qcut in ((0.0, 0.25) if N in BC.QCUT_ROWS and SA == BC.ACTOR_SA else (0.0,)):
+        ratios = _float32_actor_ratios(N, SA, qcut)
+        print("%s qcut=%g: float32 d(pre-tanh) error / tolerance %.4f, gradient %.4f, pi %.4f, loss head %.4f" % ((BC.edge_id(c), qcut) + ratios))
+        assert max(ratios) <= 0.5
+
+
+@pytest.mark.parametrize("c", B2.MODE9_EDGE_CASES, ids=BC.edge_id)
+@pytest.mark.parametrize("w_zero", (False, True))
+def test_float32_mode9_within_half_the_gpu_tolerance_at_the_edges(c, w_zero):
+    """As tests/test_bosa2_ref.py::test_mode9_cases_float32_evaluation_within_half_the_gpu_tolerance, at the edge cases that
+    tests/test_hip_bosa_stage2.py runs: gradients against grad_tolerance, the two losses against rtol 1e-5."""
+    N, SA = c
+    assert B2.MODE9_EDGE_CASES == BC.EDGE_CASES
+    q = B2.twin_from_state_dict(B2.mode9_params(SA))
+    rows, q_next, w, c9 = B2.mode9_case(N, SA=SA)
+    assert 0 < (w != 0).sum() < N
+    if w_zero:
+        w = np.zeros_like(w)
+    s, a, _, r, nd = rows
+    out = {}
+    for dt in (np.float64, np.float32):
+        y = np.asarray(r, dt).reshape(-1) + np.asarray(nd, dt).reshape(-1) * dt(0.99) * np.asarray(q_next, dt)
+        out[dt] = B2.critic_step(q, s, a, y, 2 * w, B2.MODE9_COEF, dtype=dt, c=c9)
+    (l64, _, g64), (l32, _, g32) = out[np.float64], out[np.float32]
+    tol = B2.grad_tolerance(g64)
+    worst = max((np.abs(g32[k] - g64[k]) / tol[k]).max() for k in WR.KEYS)
+    scalars = max(abs(l32[k] - l64[k]) / (1e-5 * abs(l64[k])) for k in ("critic_loss", "critic_cons_loss"))
+    print("%s w_zero=%s: float32 gradients, worst error / tolerance %.4f; losses / rtol 1e-5 %.4f" % (BC.edge_id(c), w_zero, worst, scalars))
+    assert worst <= 0.5 and scalars <= 0.5
+
+
+def test_float32_stage2_scalars_within_half_the_gpu_tolerance_at_the_product_batch():
+    """BC.BATCH_SHAPE, two calls: the mask threshold sits in a gap of more than ten estimator tolerances (the GPU test asserts the
+    masks exactly), both masks keep rows on either side, and the float32 scalars stay within half of the class test's bound."""
+    cfg, _, _, _, mixed, (gap, tol) = BC.batch_setup()
+    assert len(mixed[0]) == 256 and gap > 10 * tol and np.exp(-700) < cfg["epsilon_dyna_exp"] < 1
+    worst = {}
+    for call, l32, l64, st in BC.stage2_calls("batch", np.float32):
+        assert 0.25 <= st["mask"].mean() <= 0.75
+        terms = BC.scalar_terms(l64, cfg)
+        for k in B2.STAGE2_SCALARS[:8 if call % 2 == 0 else 4]:
+            worst[k] = max(worst.get(k, 0.0), abs(l32[k] - l64[k]) / (1e-5 * abs(l64[k]) + 1e-5 * terms[k] + 1e-300))
+    assert call == 2 and st["ta"] == 1 and st["tq"] == 2
+    print("batch", {k: round(v, 4) for k, v in worst.items()})
+    assert max(worst.values()) <= 0.5, worst
 
 
 @pytest.mark.parametrize("N", BC.ACTOR_ROWS)

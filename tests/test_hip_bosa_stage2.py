@@ -9,13 +9,15 @@ whose derivative with respect to q_m is the seed 2 w (q_m - y) / N + c.  Toleran
 the same sum divided by N where mode 8 multiplies by the rounded 1 / N, so it may differ in the last place.
 tests/test_bosa2_ref.py holds the precondition of the normalised tolerance: a float32 evaluation of tests/bosa2_ref.critic_step on
 these inputs stays within half of it (measured 0.009 to 0.083).  The fp64 reference is that restatement, checked here against torch
-autograd of the loss above.
+autograd of the loss above.  bosa2_ref.MODE9_EDGE_CASES adds the row edges at walker shapes -- N = 2 (one target and one source row),
+32, 64, the product's 256, 1024 and 1025 -- and N = 65 at (S, A) = (11, 3), (45, 24) and (111, 8), with the same check; their float32
+precondition is tests/test_bosa_actor_ref.py's.  The c = 0 and the fused-form checks also run at 256 rows.
 
 The split-precision instances of the kernel run once each against the same fp64 reference at the bounds the project already holds
 those modes to: f16x2 and bf16x3 (fp32-grade) at the exact-fp32 tolerance, as every `mfma`-parametrised suite does
 (tests/test_hip_igdf.py::test_weighted_critic_vs_fp64_and_null_weight for mode 8); bf16x2 and bf16 at
 tests/test_hip_precision.py::test_train_step_lower_modes_vs_oracle's: the loss within tol, gradients within 10 tol x the largest
-entry, tol = 2e-4 and 5e-2.
+entry, tol = 2e-4 and 5e-2.  f16x2 and bf16x3 run again at 256 rows and at pen's widths with 65 rows, at the exact-fp32 tolerance.
 """
 import numpy as np
 import pytest
@@ -44,8 +46,9 @@ def dev():
 class Critic:
     """The twin-Q net on the device and one mobody_bosa_critic call in either form."""
 
-    def __init__(self, pq, N, dev, gamma=0.99, mode=MODE):
+    def __init__(self, pq, N, dev, gamma=0.99, mode=MODE, SA=(S, A)):
         from mobody_amd import ops
+        S, A = SA
         self.q = Net(pq, S + A, 1, 2, dev, mode)
         self.q.gbuf = torch.full((self.q.blob.numel() + 1,), NAN, device=dev)
         self.q.grad = self.q.gbuf[:-1]
@@ -63,8 +66,8 @@ class Critic:
         return self.loss[:2].cpu().numpy()
 
 
-def case(N, dev, seed=501):
-    return B2.mode9_case(N, gu.gi.batch(seed, max(N, 64), S, A))
+def case(N, dev, seed=501, SA=(S, A)):
+    return B2.mode9_case(N, gu.gi.batch(seed, max(N, 64), *SA))
 
 
 def restated(pq, rows, q_next, w, c, gamma=0.99):
@@ -120,28 +123,51 @@ def check(cr, rows, q_next, w, c, pq, dev, tag):
 
 @pytest.mark.parametrize("N", [33, 257])
 def test_mode9_vs_fp64(N, dev):
-    _, pq, _ = IR.iql_params(S, A, 431, 16.0)
-    rows, q_next, w, c = case(N, dev)
+    mode9_vs_fp64(N, (S, A), dev)
+
+
+@pytest.mark.parametrize("c", B2.MODE9_EDGE_CASES, ids=lambda c: "N%d-s%da%d" % (c[0], c[1][0], c[1][1]))
+def test_mode9_vs_fp64_at_row_edges_and_other_widths(c, dev):
+    """B2.MODE9_EDGE_CASES: at (17, 6) the smallest N (one target and one source row), one and two exact 32-row tiles, the product's
+    256, 1024 and one past it; at N = 65 a narrow net (11, 3), pen's A = 24 and ant's S = 111.  tests/test_bosa_actor_ref.py holds
+    the float32 precondition of each."""
+    mode9_vs_fp64(c[0], c[1], dev)
+
+
+def mode9_vs_fp64(N, SA, dev):
+    pq = B2.mode9_params(SA)
+    rows, q_next, w, c = case(N, dev, SA=SA)
     assert 0 < (w != 0).sum() < N and (c[:N // 2] == 0).all() and (c[N // 2:] != 0).all()
-    check(Critic(pq, N, dev), rows, q_next, w, c, pq, dev, "mixed N=%d" % N)
+    check(Critic(pq, N, dev, SA=SA), rows, q_next, w, c, pq, dev, "mixed N=%d (S, A)=%s" % (N, SA))
     # no row passes the mask: the only gradient is the conservative term's, the TD part of the loss is exactly 0
-    got, grads = check(Critic(pq, N, dev), rows, q_next, np.zeros_like(w), c, pq, dev, "w = 0, N=%d" % N)
+    got, grads = check(Critic(pq, N, dev, SA=SA), rows, q_next, np.zeros_like(w), c, pq, dev, "w = 0, N=%d (S, A)=%s" % (N, SA))
     assert np.float32(got[0]) == np.float32(COEF) * np.float32(got[1]) and any(np.abs(g).max() > 0 for g in grads.values())
 
 
 @pytest.mark.parametrize("mode,tol", [("f16x2", None), ("bf16x3", None), ("bf16x2", 2e-4), ("bf16", 5e-2)])
 def test_mode9_split_precision_instances(mode, tol, dev):
     """k_mlp3_bwd_ccritic<1..4> (and the forward / weight-gradient kernels of the mode) on the 257-row case."""
-    N = 257
-    _, pq, _ = IR.iql_params(S, A, 431, 16.0)
-    rows, q_next, w, c = case(N, dev)
-    cr = Critic(pq, N, dev, mode=mode)
+    split_precision_instance(mode, tol, 257, (S, A), dev)
+
+
+@pytest.mark.parametrize("c", [(256, (S, A)), (65, (45, 24))], ids=lambda c: "N%d-s%da%d" % (c[0], c[1][0], c[1][1]))
+@pytest.mark.parametrize("mode", ["f16x2", "bf16x3"])
+def test_mode9_fp32_grade_split_modes_at_the_product_rows_and_pen(mode, c, dev):
+    """The two fp32-grade split modes at the exact-fp32 tolerance on 256 rows (eight exact tiles) and at pen's widths."""
+    split_precision_instance(mode, None, c[0], c[1], dev)
+
+
+def split_precision_instance(mode, tol, N, SA, dev):
+    pq = B2.mode9_params(SA)
+    rows, q_next, w, c = case(N, dev, SA=SA)
+    cr = Critic(pq, N, dev, mode=mode, SA=SA)
     got = cr.run(to_dev(rows, dev), *(torch.as_tensor(t).to(dev) for t in (q_next, w, c)), N - N // 2)
     want_loss, want_cons, want = restated(pq, rows, q_next, w, c)
     grads = cr.q.unpack(cr.q.grad)
     scale = max(float(np.abs(v).max()) for v in want.values())
     worst = max(float(np.abs(grads[k] - want[k]).max()) for k in want) / scale
-    print("%s: critic_loss %.7g / %.7g, cons %.7g / %.7g, worst gradient error / largest entry %.3g" % (mode, got[0], want_loss, got[1], want_cons, worst))
+    print("%s N=%d (S, A)=%s: critic_loss %.7g / %.7g, cons %.7g / %.7g, worst gradient error / largest entry %.3g" %
+          (mode, N, SA, got[0], want_loss, got[1], want_cons, worst))
     if tol is None:
         close(float(got[0]), want_loss, rtol=1e-5, atol=0)
         close(float(got[1]), want_cons, rtol=1e-5, atol=0)
@@ -152,7 +178,7 @@ def test_mode9_split_precision_instances(mode, tol, dev):
         assert worst <= 10 * tol
 
 
-@pytest.mark.parametrize("N", [33, 257])
+@pytest.mark.parametrize("N", [33, 257, 256])
 def test_mode9_with_zero_constants_is_mode8_bit_for_bit(N, dev):
     """mobody_igdf_critic bootstraps from its own V(s'); with not_done = 0 both calls regress onto y = r whatever q_next holds."""
     from mobody_amd import ops
@@ -172,7 +198,14 @@ def test_mode9_with_zero_constants_is_mode8_bit_for_bit(N, dev):
 
 
 def test_fused_form_is_the_gradient_form_plus_adam_and_moves_no_target(dev):
-    N = 257
+    fused_is_gradient_plus_adam(257, dev)
+
+
+def test_fused_form_is_the_gradient_form_plus_adam_at_the_product_rows(dev):
+    fused_is_gradient_plus_adam(256, dev)
+
+
+def fused_is_gradient_plus_adam(N, dev):
     _, pq, _ = IR.iql_params(S, A, 431, 16.0)
     rows, q_next, w, c = case(N, dev)
     b, args = to_dev(rows, dev), [torch.as_tensor(t).to(dev) for t in (q_next, w, c)]
