@@ -56,7 +56,10 @@ __device__ __forceinline__ int chain_input(float* Xs, const CriticFwdTile& ch) {
 // GATHER: the input tile comes straight from the replay rings (layers.h fwd_gather_tile); fg / second: the stage's arguments and
 // which net of the pair this tile belongs to
 // ROLE / ch: a tile of the merged critic forward (above)
-template <int ACT, int PM, int NT, bool DS = false, bool GATHER = false, int ROLE = CF_NONE>
+// PUB: the launch goes on to the critic backward of the same rows in whichever workgroup finishes them last (critic_fwd_bf.hip):
+// what that tile's seed and masks read -- q / qt and the sign words of a CF_Q tile, reward / not_done of the CF_NEXT tile -- leaves
+// in write-through agent-scope stores (tile.h agent_store); every other save stays a plain store
+template <int ACT, int PM, int NT, bool DS = false, bool GATHER = false, int ROLE = CF_NONE, bool PUB = false>
 __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, float* Xs, const FwdGather* fg = nullptr, bool second = false,
                                                  const CriticFwdTile& ch = CriticFwdTile{}) {
   char* Ps = reinterpret_cast<char*>(Xs);
@@ -73,7 +76,7 @@ __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, fl
   wide_prefetch(w1, a.Kp1, ring);
   int c0;
   if constexpr (ROLE == CF_NEXT) {
-    c0 = fwd_gather_tile(*fg, true, Xs, row0, rows_here, ch.owes);
+    c0 = fwd_gather_tile<FWD_COLS_NET, PUB>(*fg, true, Xs, row0, rows_here, ch.owes);
   } else if constexpr (ROLE == CF_Q) {
     if (ch.chained) {
       lds_barrier();                               // the output stage before this tile has read its partial sums (and left a')
@@ -115,25 +118,27 @@ __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, fl
     gs.plane_stride = a.h1p_plane;
     gs.e_out = a.save_e1 + (long long)m * cdiv(a.rows, 32) + row0 / 32;
   }
-  const int e1 = wide_layer_to_planes<ACT, MT, PM, TB, DS>(Xs, Ps, scr, w1, a.b1 + m * a.sb1, a.Kp1, ring,
+  constexpr bool PQ = PUB && ROLE == CF_Q;
+  const int e1 = wide_layer_to_planes<ACT, MT, PM, TB, DS, PQ>(Xs, Ps, scr, w1, a.b1 + m * a.sb1, a.Kp1, ring,
                                                            [&] { bf_prefetch<PM>(w2b, bring); }, t.mask1, full, mg, rows_here, t.h1, gs, d1);
   TR(2);
   auto emit = [&](int row, int col, float v, float bias) {
     if constexpr (ROLE == CF_NEXT) chain_emit(a, t.out, rows_here, row, col, v, bias, ch);
+    else if constexpr (PQ) fwd_emit_pub(a, t.out, row0, rows_here, row, col, v, bias);
     else fwd_emit(a, t.out, row0, rows_here, row, col, v, bias);
   };
   if constexpr (NT > 0) {
     NarrowRegs<NT> br;
     const int mycol = threadIdx.x % (16 * NT);
     float bias;
-    bf_layer<ACT, MT, PM, TB, DS>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [&] {
+    bf_layer<ACT, MT, PM, TB, DS, PQ>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [&] {
       narrow_prefetch<NT>(w3, 16 * NT, br);
       bias = b3[mycol < a.nout ? mycol : 0];
     }, t.mask2, mg, rows_here, t.h2, d2);
     TR(4);
     narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
   } else {
-    bf_layer<ACT, MT, PM, TB, DS>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [] {}, t.mask2, mg, rows_here, t.h2, d2);
+    bf_layer<ACT, MT, PM, TB, DS, PQ>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [] {}, t.mask2, mg, rows_here, t.h2, d2);
     narrow_layer(Xs, w3, HID, a.Np3, [&](int row, int col, float v) { emit(row, col, v, b3[col < a.nout ? col : 0]); }, TB);
   }
   TR(5);

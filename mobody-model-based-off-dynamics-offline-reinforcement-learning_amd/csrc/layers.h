@@ -235,10 +235,15 @@ int launch_mlp3_fwd_bf_gather(const Mlp3FwdArgs& a, int members_a, const Mlp3Fwd
 // output, pi = pi(s) with saves or null.  One launch where the merged kernel exists (f16x2, the pairs the gathering kernels
 // cover, [s' | a'] rows that fit behind the image: critic_fwd_bf.hip k_critic_fwd_bf); otherwise launch_mlp3_forward_gather(q, pn)
 // and then launch_mlp3_forward(qt, pi): same results, bit for bit.
+// bq (or null), tickets, chained: the critic backward of the same step (train.h; seed mode 1) and its 2 x row tiles ticket words
+// -- where the one-chain form of the merged kernel runs, the backward tiles run inside it (k_critic_chain_bf) and *chained is set:
+// the caller then skips launch_mlp3_bwd(bq).
+struct Mlp3BwdArgs;
 int launch_critic_forward_gather(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi,
-                                 const FwdGather& fg, int prec, hipStream_t st);
+                                 const FwdGather& fg, int prec, hipStream_t st, const Mlp3BwdArgs* bq = nullptr, int* tickets = nullptr,
+                                 bool* chained = nullptr);
 int launch_critic_fwd_bf(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi, const FwdGather& fg,
-                         hipStream_t st);
+                         hipStream_t st, const Mlp3BwdArgs* bq = nullptr, int* tickets = nullptr, bool* chained = nullptr);
 size_t critic_fwd_bf_lds(int S, int A);          // LDS bytes of a k_critic_fwd_bf workgroup
 constexpr size_t CRITIC_FWD_LDS_MAX = 40 * 1024; // four workgroups per CU
 
@@ -273,8 +278,9 @@ __device__ __forceinline__ int fwd_load_sources(const Mlp3FwdArgs& a, int m, flo
 // The pi(s) tile of the merged critic forward (critic_fwd_bf.hip) reads the state columns alone (FWD_COLS_STATE: the first
 // g.S columns of net a's part of the row) and owes no minibatch array; where that launch evaluates pi(s') of a row block twice,
 // the second copy fetches the same chunks and leaves reward / not_done to the first (`owes` false).
+// PUB: reward / not_done are read by another workgroup of the same launch (tile.h agent_store).
 enum FwdGatherCols { FWD_COLS_NET = 0, FWD_COLS_STATE = 1 };
-template <int NQ, int COLS = FWD_COLS_NET>
+template <int NQ, int COLS = FWD_COLS_NET, bool PUB = false>
 __device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here, bool owes = true) {
   const GatherArgs& g = fg.g;
   const int lane = threadIdx.x & 15, grp = threadIdx.x >> 4;
@@ -307,21 +313,27 @@ __device__ __forceinline__ void fwd_gather_rows(const FwdGather& fg, bool second
       for (int e = 0; e < 4; ++e) {
         const int c = 4 * q + e - off;
         if (c >= 0 && c < n) Xs[r * LDX + c] = ok ? v[p][j][e] : 0.f;
-        if (second && ok && owes && c == n) g.reward[row0 + r] = v[p][j][e];
-        if (second && ok && owes && c == n + 1) g.not_done[row0 + r] = v[p][j][e];
+        if (second && ok && owes && c == n) {
+          if constexpr (PUB) agent_store(g.reward + row0 + r, v[p][j][e]);
+          else g.reward[row0 + r] = v[p][j][e];
+        }
+        if (second && ok && owes && c == n + 1) {
+          if constexpr (PUB) agent_store(g.not_done + row0 + r, v[p][j][e]);
+          else g.not_done[row0 + r] = v[p][j][e];
+        }
       }
     }
   }
 }
 
 // Returns the width of the input tile, as fwd_load_sources.  One thread of the launch advances the bump words.
-template <int COLS = FWD_COLS_NET>
+template <int COLS = FWD_COLS_NET, bool PUB = false>
 __device__ __forceinline__ int fwd_gather_tile(const FwdGather& fg, bool second, float* Xs, long long row0, int rows_here, bool owes = true) {
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     for (int k = 0; k < fg.g.nbump; ++k) fg.g.bump[k][0] += 1;
   const int off = second ? fg.off[1] : fg.off[0], n = COLS == FWD_COLS_STATE ? fg.g.S : second ? fg.n[1] : fg.n[0];
-  if (((off + n + (second ? 2 : 0) + 3) >> 2) - (off >> 2) <= 16) fwd_gather_rows<1, COLS>(fg, second, Xs, row0, rows_here, owes);
-  else fwd_gather_rows<FWD_GATHER_NQ, COLS>(fg, second, Xs, row0, rows_here, owes);
+  if (((off + n + (second ? 2 : 0) + 3) >> 2) - (off >> 2) <= 16) fwd_gather_rows<1, COLS, PUB>(fg, second, Xs, row0, rows_here, owes);
+  else fwd_gather_rows<FWD_GATHER_NQ, COLS, PUB>(fg, second, Xs, row0, rows_here, owes);
   return n;
 }
 
@@ -375,6 +387,16 @@ __device__ __forceinline__ void fwd_emit(const Mlp3FwdArgs& a, float* out, long 
     if (a.out_mode == 1) y = a.max_action * tanhf(y);
     if (a.resid != nullptr) y += a.resid[(row0 + row) * a.resid_ld + col];
     out[row * a.out_ld + col] = y;
+  }
+}
+// the same element where another workgroup of the launch reads it (tile.h agent_store)
+__device__ __forceinline__ void fwd_emit_pub(const Mlp3FwdArgs& a, float* out, long long row0, int rows_here, int row, int col,
+                                             float v, float bias) {
+  if (row < rows_here && col < a.nout) {
+    float y = v + bias;
+    if (a.out_mode == 1) y = a.max_action * tanhf(y);
+    if (a.resid != nullptr) y += a.resid[(row0 + row) * a.resid_ld + col];
+    agent_store(out + row * a.out_ld + col, y);
   }
 }
 

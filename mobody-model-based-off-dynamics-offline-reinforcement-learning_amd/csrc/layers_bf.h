@@ -10,7 +10,8 @@
 namespace mobody {
 
 // sign words of a ReLU layer's OUTPUT y (y > 0 <=> pre-activation > 0); layout as wide_layer's masks
-template <int MT>
+// PUB: the words are read by another workgroup of the same launch (tile.h agent_store)
+template <int MT, bool PUB = false>
 __device__ __forceinline__ void relu_mask_words(f32x16 (&y)[MT][2], uint32_t* mask, int mask_groups) {
   const int i = lane_id() & 31, hh = lane_id() >> 5;
 #pragma unroll
@@ -22,7 +23,10 @@ __device__ __forceinline__ void relu_mask_words(f32x16 (&y)[MT][2], uint32_t* ma
       for (int r = 0; r < 16; ++r)                      // y is a ReLU output (>= +0, never -0): y > 0 <=> its bit pattern is non-zero --
         word |= min(__float_as_uint(y[mt][nt][r]), 1u) << ((r & 3) + 8 * (r >> 2) + 4 * hh);   // v_min_u32 + v_lshl_or instead of cmp + cndmask + lshl_or
       word |= (uint32_t)__shfl_xor((int)word, 32);
-      if (hh == 0 && mt < mask_groups) mask[mt * HID + 64 * wave_col() + 32 * nt + i] = word;
+      if (hh == 0 && mt < mask_groups) {
+        if constexpr (PUB) agent_store(mask + mt * HID + 64 * wave_col() + 32 * nt + i, word);
+        else mask[mt * HID + 64 * wave_col() + 32 * nt + i] = word;
+      }
     }
 }
 
@@ -92,7 +96,7 @@ __device__ __forceinline__ void planes_from_acc(f32x16 (&acc)[MT][2], char* Ps, 
 // activations: gsave (fp32 rows, this tile's base) and gs (fp16 planes for the weight-gradient GEMM); optional sign words.
 // DS (Swish training forward): dsave also receives d = dy/dz of every element (fp32 rows; mobody_module.py:9-15), with the
 // fp32 training kernel's formulas (sig = 1 / (1 + exp(-z)), y = z sig, d = sig (1 + z (1 - sig)); layers.h wide_layer_swish_d).
-template <int ACT, int MT, int PM, int TB, bool DS = false, class Ring, class Between>
+template <int ACT, int MT, int PM, int TB, bool DS = false, bool PUB = false, class Ring, class Between>
 __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* scr, const float* __restrict__ W,
                                                     const float* __restrict__ b, int Kp, Ring& ring, Between&& between,
                                                     uint32_t* mask = nullptr, bool full = true, int mask_groups = 0,
@@ -154,13 +158,13 @@ __device__ __forceinline__ int wide_layer_to_planes(float* Xs, char* Ps, float* 
   planes_from_acc<MT, PM, TB>(acc, Ps, e, gs, (min(rows_here, TB) + 31) / 32);
   if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, rows_here);
   TR(7);
-  if (mask != nullptr) relu_mask_words<MT>(acc, mask, mask_groups);
+  if (mask != nullptr) relu_mask_words<MT, PUB>(acc, mask, mask_groups);
   lds_barrier();
   return e;
 }
 
 // split-precision layer: planes (scaled by 2^e_in in the f16 mode) -> fp32 image (+ optional fp32 copy gsave, sign words)
-template <int ACT, int MT, int PM, int TB, bool DS = false, class Between>
+template <int ACT, int MT, int PM, int TB, bool DS = false, bool PUB = false, class Between>
 __device__ __forceinline__ void bf_layer(float* Xs, const char* Ps, int e_in, const s16x8* __restrict__ Wb,
                                          const float* __restrict__ b, BfRing<PM>& ring, Between&& between,
                                          uint32_t* mask = nullptr, int mask_groups = 0, int rows_here = 1 << 30,
@@ -203,7 +207,7 @@ __device__ __forceinline__ void bf_layer(float* Xs, const char* Ps, int e_in, co
   lds_barrier();                                   // every wave has read the planes
   wide_foreach<MT>(acc, [&](int row, int col, float y) { Xs[row * LDX + col] = y; });
   if (gsave != nullptr) wide_store_rows<MT>(acc, gsave, rows_here);
-  if (mask != nullptr) relu_mask_words<MT>(acc, mask, mask_groups);
+  if (mask != nullptr) relu_mask_words<MT, PUB>(acc, mask, mask_groups);
   lds_barrier();
 }
 

@@ -238,8 +238,9 @@ static bool critic_forward_merges(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, c
 }
 
 int launch_critic_forward_gather(const Mlp3FwdArgs& q, const Mlp3FwdArgs& pn, const Mlp3FwdArgs& qt, const Mlp3FwdArgs* pi,
-                                 const FwdGather& fg, int prec, hipStream_t st) {
-  if (critic_forward_merges(q, pn, qt, pi, fg, prec)) return launch_critic_fwd_bf(q, pn, qt, pi, fg, st);
+                                 const FwdGather& fg, int prec, hipStream_t st, const Mlp3BwdArgs* bq, int* tickets, bool* chained) {
+  if (chained != nullptr) *chained = false;
+  if (critic_forward_merges(q, pn, qt, pi, fg, prec)) return launch_critic_fwd_bf(q, pn, qt, pi, fg, st, bq, tickets, chained);
   int rc = launch_mlp3_forward_gather(q, 2, pn, 1, fg, prec, st);
   if (rc) return rc;
   return pi != nullptr ? launch_mlp3_forward(qt, 2, *pi, 1, ACT_RELU, prec, st) : launch_mlp3_forward(qt, 2, ACT_RELU, prec, st);

@@ -49,6 +49,13 @@ __device__ __forceinline__ int wave_col() { return (threadIdx.x >> 6) & 3; }
 // nothing in these kernels hands global data between waves, so only lgkmcnt has to drain.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Words one workgroup hands to another inside a launch: write-through agent-scope stores on the producer, agent-scope
+// loads -- past the CU's L1 -- on the consumer.
+__device__ __forceinline__ void agent_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void agent_store(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float agent_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t agent_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SWISH = 2 };
 
 // 1 / x as ONE v_rcp_f32 (1 ulp) instead of the IEEE division sequence (v_div_scale x 2, v_rcp, four fma, v_div_fmas, v_div_fixup):

@@ -50,7 +50,8 @@ __device__ __forceinline__ float bc_weight(const ActorRowArgs& a, long long row)
 // one-output net only: the kernel forms dz3 W3^T as the rank-1 product it is instead of running the K = Np3 GEMM.
 // Where each runs: launch_mlp3_bwd (k_mlp3_bwd) takes modes 0 and 1 and chooses between them at run time; modes 2 and 3 exist
 // only as the two tiles of launch_actor_bwd_chain (k_actor_bwd_chain), compiled in, with mode 2's dx / bcw handed to mode 3 in
-// agent-scope stores and loads; mode 4 is mode 2's alternative as the first tile (the chain's third template argument).
+// agent-scope stores and loads; mode 4 is mode 2's alternative as the first tile (the chain's third template argument).  Mode 1
+// also runs, compiled in (bwd_tile.h SEED_CRITIC_CHAIN), as the tiles chained onto the merged critic forward (critic_fwd_bf.hip).
 //   5  IQL's V net (iql.py:174-185, asymmetric_l2_loss :117-118), one output: adv = min(qt[0], qt[1]) - v,
 //        dz3[row][0] = -2 |lam - 1[adv < 0]| adv / N_global; adv_out[row] = adv (the policy phase's weights come from it);
 //        lossp[tile] = sum |lam - 1[adv<0]| adv^2, lossp[T + tile] = sum adv, lossp[2 T + tile] = sum v (T row tiles)

@@ -26,6 +26,7 @@ struct TrainWs {
   float *lossp_pairs;      // seed mode 9: a pair of partial sums per (row tile, member)
   float *bc;               // Adam bias corrections of a device step count: two floats per net (critic, actor), mlp3_weight_grads
   int *tickets;            // one per row tile: arrivals of the tile's two frozen-Q workgroups in k_actor_bwd_chain (zeroed by k_actor_stats)
+  int *ctickets;           // two per row tile: arrivals of (tile, member)'s two producers in k_critic_chain_bf (any contents on entry)
   long long total;
   int nsplit_q, nsplit_a, ntiles;
   MobodyMlpLayout Lq, La;
@@ -73,6 +74,10 @@ static int carve(const MobodyTrainDims& d, float* base, TrainWs& w) {
   w.bc = take(4);
   w.tickets = (int*)take(w.ntiles);
   w.lossp_pairs = take(4LL * w.ntiles);           // behind everything else: no other piece moves
+  // The chained critic launch's tickets share the first half of these words: mode 9 (BOSA, always the separate backward launch)
+  // writes every pair before the reduction reads it, and a ticket may hold anything on entry (critic_fwd_bf.hip), so neither
+  // user minds what the other left.  The workspace keeps its size.
+  w.ctickets = (int*)w.lossp_pairs;
   w.total = take.off;
   return 0;
 }
@@ -350,6 +355,14 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   // online twin-Q(s, a), activations kept for the backward (:196), together with a' = pi(s') (:191) in one launch
   const Mlp3FwdArgs fq = fwd_args(q_blob, w.Lq, state, S, action, A, N, w.q, 0, 1.f, w.xq, w.h1q, w.h2q, w.mq1, w.mq2, qT,
                                   prec == PREC_F16X2 ? w.eh1q : nullptr);
+  const float invNg = 1.f / (float)d->N_global;
+  // TD error -> dz3 in the backward's prologue (mobody.py:190-207), then dz2, dz1 and the bias partials
+  Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
+  bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = a.reward; bq.seed.nd = a.not_done;
+  bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
+  // the plain seed (mode 1) of a whole step: the merged forward launch runs the backward tiles too where it can (critic_fwd_bf.hip)
+  const bool may_chain = a.phase == 0 && row_weight == nullptr && cons == nullptr;
+  bool chained = false;
   if (a.phase == 2) {
     // forwards already enqueued by the phase-1 call
   } else if (q_next == nullptr) {
@@ -367,7 +380,7 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
       FwdGather fg = *gather;
       fwd_set_gather(fg, 0, fq, 0);                // state | action open the ring row, next_state follows them
       fwd_set_gather(fg, 1, fpn, S + A);
-      rc = launch_critic_forward_gather(fq, fpn, ft, a.policy_forward ? &fpi : nullptr, fg, prec, st);
+      rc = launch_critic_forward_gather(fq, fpn, ft, a.policy_forward ? &fpi : nullptr, fg, prec, st, may_chain ? &bq : nullptr, w.ctickets, &chained);
     } else {
       rc = launch_mlp3_forward(fq, 2, fpn, 1, ACT_RELU, prec, st);
       if (!rc && a.policy_forward) rc = launch_mlp3_forward(ft, 2, fpi, 1, ACT_RELU, prec, st);
@@ -378,11 +391,6 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
     rc = extra != nullptr ? launch_mlp3_forward(fq, 2, *extra, 1, ACT_RELU, prec, st) : launch_mlp3_forward(fq, 2, ACT_RELU, prec, st);
   }
   if (rc || a.phase == 1) return rc;
-  const float invNg = 1.f / (float)d->N_global;
-  // TD error -> dz3 in the backward's prologue (mobody.py:190-207), then dz2, dz1 and the bias partials
-  Mlp3BwdArgs bq = bwd_args(w.Lq, a.q_blob_T, w.dz3q, w.h1q, w.h2q, N, w.dz2, w.dz1, w.dbp, w.mq1, w.mq2, prec, w.edz2);
-  bq.seed.mode = 1; bq.seed.q = w.q; bq.seed.qt = w.qt; bq.seed.qnext = q_next; bq.seed.r = a.reward; bq.seed.nd = a.not_done;
-  bq.seed.gamma = h->gamma; bq.seed.inv_ng = invNg; bq.seed.dz3_out = w.dz3q; bq.seed.lossp = w.lossp;
   if (cons != nullptr) {                           // BOSA: weight and constant (mode 9); its partial sums are pairs, 4 per row tile
     bq.seed.mode = 9; bq.seed.cs.w = row_weight; bq.seed.cs.c = cons->c;
     bq.seed.lossp = w.lossp_pairs;
@@ -395,7 +403,7 @@ static int critic_impl(const MobodyCritic& a, const FwdGather* gather, void* str
   } else if (row_weight != nullptr) {              // IGDF: the same seed with the row's weight, an instance of its own (mode 8)
     bq.seed.mode = 8; bq.seed.cw.w = row_weight;
     rc = launch_mlp3_bwd_wcritic(bq, st);
-  } else {
+  } else if (!chained) {
     rc = launch_mlp3_bwd(bq, 2, false, st);
   }
   if (rc) return rc;
