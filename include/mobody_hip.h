@@ -1070,7 +1070,7 @@ int mobody_wide_adam(const MobodyWideAdam* a, void* stream);
  * null pointers. */
 enum { MOBODY_BOSA_POLICY = 0, MOBODY_BOSA_DYNAMICS = 1 };
 enum { MOBODY_BOSA_STREAM_POLICY = 6, MOBODY_BOSA_STREAM_DYNAMICS = 7, MOBODY_BOSA_STREAM_POLICY_LL = 8, MOBODY_BOSA_STREAM_DYNAMICS_LL = 9,
-       MOBODY_BOSA_STREAM_TARGET_NOISE = 10 /* the second stage's target noise [N][A] (bosa.py:571), drawn by the host class with mobody_rng_normal */ };
+       MOBODY_BOSA_STREAM_TARGET_NOISE = 10 /* the second stage's target noise [N][A] (bosa.py:571), drawn by the host class with mobody_rng_normal, or inside mobody_bosa_target */ };
 typedef struct MobodyBosaVae MobodyBosaVae;
 struct MobodyBosaVae {
   int32_t struct_bytes;
@@ -1112,6 +1112,86 @@ int mobody_bosa_loglik_grad(const MobodyBosaVae* a, float* dll_da /* [B][A] */, 
  *                       mobody_train_workspace floats. */
 int mobody_bosa_critic(const MobodyCritic* a, const float* row_weight, const float* row_const, float cons_coef,
                        int64_t cons_rows_global, void* stream);
+
+/* ---- BOSA's critic / actor stage without a torch op (bosa.py:565-634) -------------------------------------------
+ * The row-wise pieces that sit between the stage's launches, so that a stage-2 call is a sequence of this library's launches
+ * alone and can be captured as a HIP graph.  The new kernels use no flags, no tickets and no atomics (float or integer); each launch
+ * reads what an earlier launch on the stream wrote and nothing waits inside a kernel; every loop is bounded by an argument (N, A,
+ * nbump, the fixed grid); every sum and maximum runs in a fixed order, so two runs give the same bits.
+ *   mobody_bosa_target    bosa.py:570-577: q_next [N] = min over the two target critics of Q_target(s', a') with
+ *                       a' = clamp(pi_target(s') + clamp(noise * expl_noise, -noise_clip, noise_clip), -max_action, max_action).
+ *                       Four launches, in order: mobody_mlp3_forward of the target actor (out_mode 1, max_action);
+ *                       k_bosa_target_action, in place over pi; mobody_mlp3_forward of the two-member target critic on [s' | a'];
+ *                       k_bosa_qnext.  noise [N][A], or NULL: element i is rng.h's unit normal (the one mobody_rng_normal writes at
+ *                       index i) of (seed, stream MOBODY_BOSA_STREAM_TARGET_NOISE, call + (call_dev ? call_dev[0] : 0)).  The four
+ *                       steps of a' are one correctly rounded fp32 operation each (multiply, clamp, add, clamp; nothing is
+ *                       contracted); both clamps keep a NaN, as torch.clamp does; the minimum does not skip a NaN member, as
+ *                       torch.min and mobody_bosa_loglik's min_ll do not.  The packed forwards' ReLU (fmaxf) turns a NaN
+ *                       pre-activation into 0, so k_bosa_qnext also reads the row's s' and a' and gives a row with a NaN among
+ *                       them q_next = NaN, as torch's forward would; no other row is touched.  On finite rows the result has the bits of mobody_rng_normal + torch's
+ *                       mul / clamp / add / clamp + mobody_mlp3_forward + torch.min at precisions 0 (f32), 3 (bf16x3) and 4 (f16x2);
+ *                       1 (bf16) and 2 (bf16x2) are refused by name, as the rest of the stage refuses them.  actor_blob_T / q_blob_T
+ *                       are read at precision != 0 only.  workspace: mobody_bosa_target_workspace floats = round4(N A) + round4(2 N)
+ *                       (a' and the twin Q, each piece rounded up to 4 floats); -1 for a bad block.  Both row-wise kernels run a
+ *                       grid-stride loop over at most 4 workgroups of 256 threads (the stage's batches are a few hundred rows).
+ *                       Refused with MOBODY_E_ARG before the first runtime call, the field named: struct_bytes, S outside [1, 256],
+ *                       A outside [1, 128], S + A > 256 (mobody_mlp_layout's ranges), N < 1 or N > 2^21, precision, a NULL
+ *                       actor_blob / q_blob / next_state / q_next / workspace, noise_clip < 0, max_action <= 0, a NaN among the three.
+ *   mobody_bosa_stage2_rows   ONE launch: row_weight[i] = mask[i] * 0.5 over N rows (mask != NULL) and / or dpi[i][j] = dll[i][j] *
+ *                       dpi_scale over N A elements (dll != NULL) -- single fp32 multiplies, torch.mul's bits.  dpi_scale is the
+ *                       caller's -(lamda / N), formed in double and rounded once (what torch.mul does with a Python scalar).
+ *   mobody_bosa_stage2_words  ONE launch of one workgroup: the logged words, STAGE2_LOG order.  closs != NULL (mobody_bosa_critic's
+ *                       loss_out): words[0] = mask_mean[0], words[1] = closs[0], words[3] = closs[1], words[2] = closs[0] - cons_coef *
+ *                       closs[1].  ll != NULL ([N], the policy estimator's): words[5] = mean_i(-ll[i]), words[6] = max_i(-ll[i]) with a
+ *                       NaN giving NaN (torch.amax), words[4] = aloss[0] + lamda * words[5]; thread t adds rows t, t + 256, ... in
+ *                       ascending order and a fixed tree joins the 256 partial results -- not torch.mean's bits, these words feed the
+ *                       log only.  words[7] is not touched.  Last, bump[k] += bump_inc[k] for k < nbump <= 4 (device int64 words, by
+ *                       one thread): a captured call advances its noise call id, step counts and draw count in its last launch.
+ *                       Refused with MOBODY_E_ARG before any runtime call, the field named (both entries): struct_bytes, N < 1 or
+ *                       N > 2^21, neither part given, a part's output or companion pointer NULL (row_weight, dpi; words, mask_mean,
+ *                       aloss), A outside [1, 128] with dll, a NaN dpi_scale, nbump outside [0, 4], bump NULL with nbump > 0.
+ * LAUNCHES of a stage-2 call: a critic call makes 4 (mobody_bosa_target) + 11 (mobody_bosa_loglik with mask_mean) + mobody_bosa_critic's
+ * + 2 (rows before the critic, words after it); an actor call makes those with the critic in gradient form + mobody_adam_polyak's
+ * + 3 (mobody_bosa_actor_forward and its copy) + mobody_bosa_loglik_grad's 19 + 6 (mobody_bosa_actor_backward) + mobody_adam_polyak's
+ * + 3 (rows before the critic, rows before the actor's backward, ONE words launch with both parts at the end): two beyond the named
+ * entries on a critic call and one more on an actor call. */
+typedef struct MobodyBosaTarget MobodyBosaTarget;
+struct MobodyBosaTarget {
+  int32_t struct_bytes;
+  int32_t precision;
+  int32_t S, A;
+  int64_t N;
+  const float *actor_blob, *actor_blob_T;   /* the TARGET actor, mobody_mlp_layout(S, A, 1) */
+  const float *q_blob, *q_blob_T;           /* the TARGET twin-Q, mobody_mlp_layout(S + A, 1, 2) */
+  const float* next_state;                  /* [N][S] */
+  const float* noise;                       /* [N][A] unit normals, or NULL */
+  uint32_t seed, call;
+  const int64_t* call_dev;                  /* nullable */
+  float expl_noise, noise_clip, max_action;
+  int32_t reserved;                         /* 0 */
+  float* q_next;                            /* [N] */
+  float* workspace;
+};
+int64_t mobody_bosa_target_workspace(const MobodyBosaTarget* a);
+int mobody_bosa_target(const MobodyBosaTarget* a, void* stream);
+typedef struct MobodyBosaStage2 MobodyBosaStage2;
+struct MobodyBosaStage2 {
+  int32_t struct_bytes;
+  int32_t A;
+  int64_t N;
+  const float* mask;                        /* [N], mobody_bosa_loglik's */
+  float* row_weight;                        /* [N] */
+  const float* dll;                         /* [N][A], mobody_bosa_loglik_grad's */
+  float* dpi;                               /* [N][A] */
+  float dpi_scale, cons_coef, lamda;
+  int32_t nbump;
+  const float *mask_mean, *closs, *ll, *aloss;
+  float* words;                             /* [8] */
+  int64_t* bump;
+  int64_t bump_inc[4];
+};
+int mobody_bosa_stage2_rows(const MobodyBosaStage2* a, void* stream);
+int mobody_bosa_stage2_words(const MobodyBosaStage2* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,18 @@ class MobodyBosaVae(C.Structure):
                 ("mask_mean", vp), ("w_out", vp), ("workspace", vp)]
 
 
+class MobodyBosaTarget(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("S", i32), ("A", i32), ("N", i64), ("actor_blob", vp), ("actor_blob_T", vp),
+                ("q_blob", vp), ("q_blob_T", vp), ("next_state", vp), ("noise", vp), ("seed", u32), ("call", u32), ("call_dev", vp),
+                ("expl_noise", f32), ("noise_clip", f32), ("max_action", f32), ("reserved", i32), ("q_next", vp), ("workspace", vp)]
+
+
+class MobodyBosaStage2(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("A", i32), ("N", i64), ("mask", vp), ("row_weight", vp), ("dll", vp), ("dpi", vp),
+                ("dpi_scale", f32), ("cons_coef", f32), ("lamda", f32), ("nbump", i32), ("mask_mean", vp), ("closs", vp), ("ll", vp),
+                ("aloss", vp), ("words", vp), ("bump", vp), ("bump_inc", i64 * 4)]
+
+
 WIDE_OUT_MODES = {"raw": 0, "tanh": 1}
 BOSA_KINDS = {"policy": 0, "dynamics": 1}
 BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9, "target_noise": 10}    # MOBODY_BOSA_STREAM_*
@@ -211,7 +223,7 @@ def block(cls, **fields):
 
 
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
-                                             MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyEnsStep, MobodyEnsRollout,
+                                             MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyBosaTarget, MobodyBosaStage2, MobodyEnsStep, MobodyEnsRollout,
                                              MobodyEnsEval, MobodyEnsReplay)}
 
 
@@ -329,6 +341,10 @@ PROTOTYPES = {
     "mobody_bosa_loglik": (C.c_int, [C.POINTER(MobodyBosaVae), vp]),
     "mobody_bosa_loglik_grad_workspace": (i64, [C.POINTER(MobodyBosaVae)]),
     "mobody_bosa_loglik_grad": (C.c_int, [C.POINTER(MobodyBosaVae), vp, vp]),
+    "mobody_bosa_target_workspace": (i64, [C.POINTER(MobodyBosaTarget)]),
+    "mobody_bosa_target": (C.c_int, [C.POINTER(MobodyBosaTarget), vp]),
+    "mobody_bosa_stage2_rows": (C.c_int, [C.POINTER(MobodyBosaStage2), vp]),
+    "mobody_bosa_stage2_words": (C.c_int, [C.POINTER(MobodyBosaStage2), vp]),
 }
 
 _lib = None

@@ -9,7 +9,8 @@ DARA also `gaussian_noise_std`, `dara_eta` and, when `dara_eta` is 0, `eta`; for
 `ensemble_size`, `repr_norm`, `ortho_init`, `info_update_step` -- the constructor raises NotImplementedError.  BOSA
 (`offline_offline/bosa.py`) is built in two parts: its VAE stage -- the behaviour and dynamics VAEs, their checkpoints and both
 likelihood estimators -- always, its critic / actor stage when config['critic_actor'] is truthy (then `gamma`, `tau`, `actor_lr` and
-`critic_lr` are required as well).  A config without one of the seventeen keys the reference reads without defaults (`vae_policy_lr`
+`critic_lr` are required as well; the optional config['critic_actor_graph'] = 1, read only then, replays that stage's calls as HIP
+graphs under rng='device', 0 -- the default -- runs them eagerly, any other value is a ValueError).  A config without one of the seventeen keys the reference reads without defaults (`vae_policy_lr`
 ... `update_interval`) raises NotImplementedError in the constructor, and so does -- with `critic_actor` unset -- the train() call that
 would enter the critic / actor stage.
 """

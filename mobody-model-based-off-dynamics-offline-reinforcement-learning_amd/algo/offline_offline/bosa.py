@@ -10,7 +10,9 @@ second stage raises NotImplementedError before it changes any state.  With confi
 stage is built too: the twin-Q critic with the masked conservative seed (`mobody_bosa_critic`), the delayed actor step through
 critic_1 alone with the derivative of the policy VAE's estimator (`mobody_bosa_actor_forward / _backward`,
 `mobody_bosa_loglik_grad`), the three target nets, the reference's ten checkpoint files plus the targets', and `critic_actor_train`
-beside `vae_models_train`.  Stage-2 calls always run eagerly; config['graph'] only replays the VAE stage.
+beside `vae_models_train`.  Stage-2 calls run eagerly whatever config['graph'] says (it only replays the VAE stage); with
+config['critic_actor_graph'] = 1 they run through the library's row-wise entries alone -- no torch op between the
+launches -- and replay as two HIP graphs, one for critic calls and one for actor calls, their counts in device words.
 
 Same plugin surface as the reference: `BOSA(config, device)`, `.train(src_rb, tar_rb, batch_size, writer, wandbrun)` (the
 reference's takes four arguments and its driver passes five), `.vae_policy .vae_dyna .vae_policy_optimizer .vae_dyna_optimizer`,
@@ -73,6 +75,9 @@ def _check_config(config):
             raise ValueError(f"config['{k}'] = {config[k]} must be positive")
     if int(config["vae_iteration"]) < 0:
         raise ValueError(f"config['vae_iteration'] = {config['vae_iteration']} < 0")
+    g = config.get("critic_actor_graph", 0)                 # read with config['critic_actor'] only, as the stage's other keys
+    if config.get("critic_actor") and (isinstance(g, bool) or g not in (0, 1)):
+        raise ValueError(f"config['critic_actor_graph'] = {g!r}: expected 0 (stage-2 calls run eagerly) or 1 (they replay as HIP graphs)")
 
 
 class _WideVae(object):
@@ -266,6 +271,13 @@ class BOSA(object):
         self._closs, self._aloss = torch.zeros(2, device=dev), torch.zeros(2, device=dev)
         self._stats = torch.zeros(2, dtype=torch.float32, device=dev)
         self._s2_key, self._s2_buf = None, None
+        # config['critic_actor_graph']: the stage's calls through the library's row-wise entries alone, replayed as two
+        # HIP graphs.  The device words: [next noise call id, critic step, actor step, next draw id of the target buffer].
+        self.critic_actor_graph = int(config.get("critic_actor_graph", 0))
+        self._s2_ctr = torch.zeros(4, dtype=torch.int64, device=dev)
+        self._s2_ctr_host = None                                  # what the words hold, as far as the host knows
+        self._s2_graphs, self._s2_graph_key, self._s2_warm, self._s2_capture_failed = {}, None, {}, False
+        self.stage2_replays, self.stage2_captures = 0, {"critic": 0, "actor": 0}
 
     # ------------------------------------------------------------------ acting
     def select_action(self, state, test=False):
@@ -470,8 +482,8 @@ class BOSA(object):
     def train(self, src_replay_buffer, tar_replay_buffer, batch_size=128, writer=None, wandbrun=None):
         """One call of the reference's train() (bosa.py:552-639).  total_it += 1; fewer than batch_size rows in either buffer: return;
         draw src(bs) then tar(bs); total_it < vae_iteration: both VAE steps, and total_it += 1 once more.  Otherwise the call belongs to
-        the critic / actor stage: with config['critic_actor'] the gather plus critic_actor_train (always eager, whatever
-        config['graph'] says), without it NotImplementedError before anything changes."""
+        the critic / actor stage: with config['critic_actor'] the gather plus critic_actor_train (eager whatever config['graph']
+        says; replayed under config['critic_actor_graph']), without it NotImplementedError before anything changes."""
         bs = int(batch_size)
         short = src_replay_buffer.size < bs or tar_replay_buffer.size < bs
         if self.critic_actor and not short and not self.total_it + 1 < self.vae_iteration:
@@ -516,6 +528,11 @@ class BOSA(object):
             blk = self.vae_policy.block(N, self.num_samples)
             self._s2_buf = dict(dims=dims, ws=ops.train_workspace(dims, dev), c=c, w=f(N), pi=f(N, self.A), dll=f(N, self.A), dpi=f(N, self.A),
                                 ll=f(1, N), gws=ops.bosa_loglik_grad_workspace(blk, dev), bs=bs)
+            if self.critic_actor_graph:                            # what the eager path lets torch allocate per call
+                tb = _lib.block(_lib.MobodyBosaTarget, S=self.S, A=self.A, N=N)
+                self._s2_buf.update(q_next=f(N), tws=ops.bosa_target_workspace(tb, dev), ll_d=f(self.vae_dyna.ensemble_size, N), min_ll=f(N),
+                                    mask=f(N), mask_mean=f(1))
+                self._workspace(self.vae_dyna, N, self.num_samples)
             self._s2_key = N
         return self._s2_buf
 
@@ -543,6 +560,10 @@ class BOSA(object):
         z = self._stage2_buffers(N)
         q, qt, qo, ao = self.critic, self.critic_target, self.critic_optimizer, self.actor_optimizer
         actor_step = self.total_it % self.update_interval == 0
+        if self.critic_actor_graph:                                  # the same step through the library's row-wise entries alone
+            self._stage2_launches(b, z, actor_step, dev=False)
+            self._s2_warm["actor" if actor_step else "critic"] = N
+            return
         # target noise and the bootstrap value min Q_target(s', a') (:571-577)
         noise = self._noise("target", (N, A), SEED_TARGET, "target_noise")
         a2 = (self.actor_target(s2) + (noise * self.expl_noise).clamp(-self.noise_clip, self.noise_clip)).clamp(-self.max_action, self.max_action)
@@ -584,6 +605,107 @@ class BOSA(object):
         torch.amax(nlb, dim=0, keepdim=True, out=self._s2[6:7])
         torch.add(self._aloss[0:1], self._s2[5:6] * float(self.lamda_policy), out=self._s2[4:5])
 
+    # ------------------------------------------------------------------ the same stage without a torch op
+    def _stage2_launches(self, b, z, actor_step, dev):
+        """critic_actor_train's step as launches of the library alone: mobody_bosa_target, the dynamics estimator with its mask,
+        mobody_bosa_stage2_rows / _words around the critic and the actor phase.  dev: the captured form -- the noise call ids and
+        both step counts are read from self._s2_ctr, which the last launch advances; otherwise the host's counts, which this
+        advances as critic_actor_train does.  Bit for bit the nets of the torch composition; the logged mean is summed in the
+        kernel's order, not torch.mean's."""
+        s, a, s2 = b[0], b[1], b[2]
+        N, n, A, c = s.shape[0], self.num_samples, self.A, self._s2_ctr
+        q, qt, qo, ao, act, vd, vp = self.critic, self.critic_target, self.critic_optimizer, self.actor_optimizer, self.actor, self.vae_dyna, self.vae_policy
+        noise = eps_d = eps_p = None
+        if self.noise_fn is not None or self.rng != "device":
+            noise = self._noise("target", (N, A), SEED_TARGET, "target_noise")
+            eps_d = self._noise("dynamics_ll", (n, vd.ensemble_size, N, vd.latent_dim), SEED_DYNA, "dynamics_ll")
+        if dev:
+            base, call_dev = 0, c[0:1]
+        else:                        # the draws' call ids follow the host's count, as _noise / _loglik advance it
+            base, call_dev = self._noise_calls + 1, None
+            self._noise_calls += (3 if actor_step else 2) if noise is None else 1
+        ops.bosa_target(ops.bosa_target_block(self.actor_target, qt, s2, z["q_next"], self.expl_noise, self.noise_clip, noise=noise,
+                                              seed=self._seed_for(SEED_TARGET), call=base, call_dev=call_dev, ws=z["tws"]))
+        ops.bosa_loglik(vd.block(N, n, state=s, action=a, next_state=s2, eps=eps_d, seed=self._seed_for(SEED_DYNA), call=base + 1, call_dev=call_dev,
+                                 log_eps=float(math.log(self.epsilon_dyna_exp)), workspace=self._workspace(vd, N, n), ll=z["ll_d"],
+                                 min_ll=z["min_ll"], mask=z["mask"], mask_mean=z["mask_mean"]))
+        ops.bosa_stage2_rows(N, mask=z["mask"], row_weight=z["w"])
+        self._keep2 = (b, z["q_next"], z["mask"], noise, eps_d)
+        crit = (z["dims"], self._hyp, q.blob, q.blob_T, b, z["q_next"], z["w"], z["c"], float(self.conservation_coef), z["bs"], self._closs, z["ws"])
+        if actor_step:
+            ops.bosa_critic(*crit, grad_q=qo.grad)
+            qo.step_dev(c[1:2], target=qt, tau=self.tau) if dev else qo.step(target=qt, tau=self.tau)
+        elif dev:
+            ops.bosa_critic(*crit, m=qo.m, v=qo.v, t_dev=c[1:2], lr=qo.lr)
+        else:
+            qo.t += 1
+            ops.bosa_critic(*crit, m=qo.m, v=qo.v, t=qo.t, lr=qo.lr)
+        words = dict(mask_mean=z["mask_mean"], closs=self._closs, cons_coef=float(self.conservation_coef))
+        if dev:                      # the words of the NEXT call: 2 or 3 noise ids, one step per net stepped, one draw
+            words.update(bump=c, bump_inc=(3 if actor_step else 2, 1, int(actor_step), 1))
+        if not actor_step:
+            ops.bosa_stage2_words(N, self._s2, **words)
+            return
+        ops.bosa_actor_forward(z["dims"], self._hyp, act.blob, q.blob, s, self._stats, z["pi"], z["ws"], actor_blob_T=act.blob_T, q_blob_T=q.blob_T)
+        if noise is not None:
+            eps_p = self._noise("policy_ll", (N, n, vp.latent_dim), SEED_POLICY, "policy_ll")
+        ops.bosa_loglik_grad(vp.block(N, n, state=s, action=z["pi"], eps=eps_p, seed=self._seed_for(SEED_POLICY), call=base + 2, call_dev=call_dev,
+                                      ll=z["ll"], workspace=z["gws"]), z["dll"])
+        ops.bosa_stage2_rows(N, dll=z["dll"], dpi=z["dpi"], dpi_scale=-float(self.lamda_policy) / N, A=A)
+        ops.bosa_actor_backward(z["dims"], self._hyp, act.blob, act.blob_T, q.blob, q.blob_T, s, self._stats, z["dpi"], self._aloss, z["ws"],
+                                grad_actor=ao.grad)
+        ao.step_dev(c[2:3], target=self.actor_target, tau=self.tau) if dev else ao.step(target=self.actor_target, tau=self.tau)
+        self._keep2 += (eps_p,)
+        ops.bosa_stage2_words(N, self._s2, ll=z["ll"], aloss=self._aloss, lamda=float(self.lamda_policy), **words)
+
+    def _stage2_replay(self, src, tar, bs, actor_call):
+        """Replay (capturing first) one stage-2 call: both gathers and _stage2_launches, as the critic graph or the actor graph.
+        The graphs take every count from the device words, which are rewritten -- no recapture -- whenever the host's own counts
+        have moved on without them (an eager call, an estimator call, load(), a draw by someone else); a changed batch size,
+        pointer, precision or buffer drops both graphs."""
+        N, z, qo, ao = 2 * bs, self._s2_buf, self.critic_optimizer, self.actor_optimizer
+        for rb in (src, tar):
+            if rb.size <= 0:
+                raise ValueError("low >= high")
+        nets = (self.actor, self.critic, self.actor_target, self.critic_target, self.vae_policy, self.vae_dyna)
+        key = (bs, id(src), id(tar), src.state.data_ptr(), tar.state.data_ptr(), tuple(t.data_ptr() for t in self._batch), self.precision,
+               tuple(n.blob.data_ptr() for n in nets), qo.m.data_ptr(), ao.m.data_ptr(), z["q_next"].data_ptr(), src._draws - tar._draws)
+        if self._s2_graph_key != key:
+            self._s2_graphs, self._s2_graph_key = {}, key
+        want = [self._noise_calls + 1, qo.t + 1, ao.t + 1, tar._draws + 1]
+        if self._s2_ctr_host != want:
+            self._s2_ctr.copy_(torch.tensor(want, dtype=torch.int64))
+            self._s2_ctr_host = want
+        kind = "actor" if actor_call else "critic"
+        g = self._s2_graphs.get(kind)
+        if g is None:
+            c, salt = self._s2_ctr, dp.rank_salt()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    ops.gather_batch_rng([tar._fields(), src._fields()], [bs, bs], [(rb.seed + salt) & 0xFFFFFFFF for rb in (tar, src)],
+                                         [0, src._draws - tar._draws], c[3:4], [tar.ptr_size[1:2], src.ptr_size[1:2]], self.S, self.A, self._batch)
+                    self._stage2_launches(self._batch, z, actor_call, dev=True)
+            except Exception as exc:
+                torch.cuda.synchronize()
+                warnings.warn(f"HIP-graph capture of the critic / actor stage's {kind} call failed ({exc!r}); continuing eagerly")
+                self._s2_graphs, self._s2_graph_key, self._s2_capture_failed = {}, None, True
+                return False
+            self._s2_graphs[kind] = g
+            self.stage2_captures[kind] += 1
+        g.replay()
+        self.total_it += 1
+        self._in_stage2, self._graph = True, None
+        tar._draws += 1
+        src._draws += 1
+        self._noise_calls += 3 if actor_call else 2
+        qo.t += 1
+        ao.t += int(actor_call)
+        self._s2_ctr_host = [self._noise_calls + 1, qo.t + 1, ao.t + 1, tar._draws + 1]
+        self.stage2_replays += 1
+        return True
+
     def stage2_log(self):
         """The reference's log_dict of the last stage-2 call (a device sync): the four critic scalars, and after an actor step the
         four actor scalars of the latest one."""
@@ -592,14 +714,21 @@ class BOSA(object):
 
     def _train_stage2(self, src, tar, bs, writer):
         N = 2 * bs
+        log5k = writer is not None and (self.total_it + 1) % 5000 == 0
+        health = self.total_it % REFRESH_EVERY == 0 or log5k
+        actor_call = (self.total_it + 1) % self.update_interval == 0
+        # config['critic_actor_graph']: the call replays unless it logs, is on the health cadence, or the buffers of this size -- and one
+        # eager call of its kind on them, which makes every launch once outside a capture -- are not there yet
+        if (self.critic_actor_graph == 1 and not self._s2_capture_failed and self.rng == "device" and self.noise_fn is None and not health
+                and self._batch_key == (N,) and self._s2_key == N and self._s2_warm.get("actor" if actor_call else "critic") == N
+                and self._stage2_replay(src, tar, bs, actor_call)):
+            return
         if self._batch_key != (N,):
             self._batch = tuple(torch.empty(N, w, device=self.device) for w in (self.S, self.A, self.S, 1, 1))
             self._batch_key = (N,)
-        log5k = writer is not None and (self.total_it + 1) % 5000 == 0
-        if self.total_it % REFRESH_EVERY == 0 or log5k:             # TD3BC's cadence: every REFRESH_EVERY calls and on logging steps
+        if health:                                                  # TD3BC's cadence: every REFRESH_EVERY calls and on logging steps
             self._health_check()
         self._gather(src, tar, bs)
-        actor_call = (self.total_it + 1) % self.update_interval == 0
         self.critic_actor_train(self._batch)
         if log5k:                                                   # bosa.py:636-639: this call's log_dict
             log = self.stage2_log()

@@ -1080,3 +1080,42 @@ def bosa_loglik_grad_workspace(blk, device):
 def bosa_loglik_grad(blk, dll_da):
     """The policy VAE's estimator (blk.ll, blk.w_out as bosa_loglik writes them) and dll_da [B, A] = d ll / d blk.action."""
     check(load().mobody_bosa_loglik_grad(C.byref(blk), ptr(dll_da), cur_stream()), "mobody_bosa_loglik_grad")
+
+
+# ---- BOSA's critic / actor stage without a torch op (csrc/bosa_stage2.hip; DESIGN 5za) ------------------------------------------
+def bosa_target_block(actor, q, next_state, q_next, expl_noise, noise_clip, noise=None, seed=0, call=0, call_dev=None, ws=None):
+    """A MobodyBosaTarget block: `actor`, `q` the TARGET nets (objects with blob / blob_T / precision / max_action, the twin-Q's
+    in_dim = S + A)."""
+    N, S = next_state.shape
+    return _lib.block(_lib.MobodyBosaTarget, precision=prec_id(actor.precision), S=S, A=actor.out_dim, N=N, actor_blob=ptr(actor.blob),
+                      actor_blob_T=ptr(actor.blob_T), q_blob=ptr(q.blob), q_blob_T=ptr(q.blob_T), next_state=ptr(next_state), noise=ptr(noise),
+                      seed=seed, call=call, call_dev=ptr(call_dev), expl_noise=float(expl_noise), noise_clip=float(noise_clip),
+                      max_action=float(actor.max_action), q_next=ptr(q_next), workspace=ptr(ws))
+
+
+def bosa_target_workspace(blk, device):
+    n = load().mobody_bosa_target_workspace(C.byref(blk))
+    if n < 0:
+        raise _lib.MobodyError("mobody_bosa_target_workspace: bad block: " + load().mobody_last_error().decode(errors="replace"))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bosa_target(blk):
+    """q_next [N] = min Q_target(s', clamp(pi_target(s') + clamp(noise * expl_noise, +-clip), +-max_action)) (bosa.py:570-577)."""
+    check(load().mobody_bosa_target(C.byref(blk), cur_stream()), "mobody_bosa_target")
+
+
+def bosa_stage2_rows(N, mask=None, row_weight=None, dll=None, dpi=None, dpi_scale=0.0, A=0):
+    """row_weight = mask * 0.5 and / or dpi = dll * dpi_scale, in one launch."""
+    blk = _lib.block(_lib.MobodyBosaStage2, N=N, A=A, mask=ptr(mask), row_weight=ptr(row_weight), dll=ptr(dll), dpi=ptr(dpi),
+                     dpi_scale=float(dpi_scale))
+    check(load().mobody_bosa_stage2_rows(C.byref(blk), cur_stream()), "mobody_bosa_stage2_rows")
+
+
+def bosa_stage2_words(N, words, mask_mean=None, closs=None, cons_coef=0.0, ll=None, aloss=None, lamda=0.0, bump=None, bump_inc=()):
+    """The stage's logged words (closs given: the critic's four; ll given: the actor's three) in one launch, which then adds
+    bump_inc[k] to the device int64 words bump[k]."""
+    blk = _lib.block(_lib.MobodyBosaStage2, N=N, mask_mean=ptr(mask_mean), closs=ptr(closs), cons_coef=float(cons_coef), ll=ptr(ll),
+                     aloss=ptr(aloss), lamda=float(lamda), words=ptr(words), bump=ptr(bump), nbump=len(bump_inc),
+                     bump_inc=(C.c_int64 * 4)(*[int(x) for x in bump_inc]))
+    check(load().mobody_bosa_stage2_words(C.byref(blk), cur_stream()), "mobody_bosa_stage2_words")

@@ -14,7 +14,18 @@ with each shape under a time limit of its own; a run of one shape merges its rec
   timeout -k 10 300 python tools/bench_bosa_stage2.py --bs 128 && timeout -k 10 600 python tools/bench_bosa_stage2.py --bs 4096
 
 Each leg is timed `--repeats` times (`--steps` calls between two device synchronisations, after `--warmup` calls), the legs alternating;
-medians and the min / max spread are reported.  Results: profiles/bosa_stage2.json (`--out`) with the build's source fingerprint."""
+medians and the min / max spread are reported.  Results: profiles/bosa_stage2.json (`--out`) with the build's source fingerprint.
+
+`--graph` times whole stage-2 train() calls instead -- the gather of both buffers included -- in three legs per call kind
+(critic call, actor call), alternating with the same warm-up, repeats and reporting:
+
+  eager_key0        config['critic_actor_graph'] unset: the torch composition between the launches, the call the parent commit makes (no
+                    kernel it runs differs from the parent's: tools/isa_diff.py)
+  eager_key1        the key set, replay held off: the same launches with the row-wise entries in place of the torch ops
+  replay_key1       the key set: the call replays its HIP graph
+
+and writes profiles/bosa_stage2_graph.json.  `--isa_diff` and `--bench_c2` take text to record in that document (the isa_diff line, the
+alternating bench.py c2 figures)."""
 import argparse
 import json
 import os
@@ -96,8 +107,98 @@ def make_legs(dev, bs, buffers):
     return legs, pol
 
 
+GRAPH_LAUNCHES = dict(critic_call="gather 1 + mobody_bosa_target 4 + the dynamics estimator with mask_mean 11 + mobody_bosa_stage2_rows 1 + "
+                                  "mobody_bosa_critic (fused) + mobody_bosa_stage2_words 1",
+                      actor_call="gather 1 + target 4 + estimator 11 + rows 1 + mobody_bosa_critic (gradient form) + mobody_adam_polyak + "
+                                 "mobody_bosa_actor_forward 3 and a copy + mobody_bosa_loglik_grad 19 + rows 1 + mobody_bosa_actor_backward 6 + "
+                                 "mobody_adam_polyak + mobody_bosa_stage2_words 1",
+                      eager_key0="the same without rows / words; about fifteen torch ops in their place, and mobody_rng_normal for the target noise")
+
+
+def make_graph_legs(dev, bs, buffers):
+    """{call kind: {leg: fn}} and the three objects.  A call's kind is chosen by the host from total_it, which each leg sets before its
+    call (1 -> an actor call at update_interval 2, 2 -> a critic call; neither is on the health cadence)."""
+    import numpy as np
+    import torch
+    from mobody_amd.algo.call_algo import call_algo
+    src, tar = buffers
+    pols = {}
+    for name, key in (("eager_key0", 0), ("eager_key1", 1), ("replay_key1", 1)):
+        torch.manual_seed(0); np.random.seed(0)
+        pol = call_algo("bosa", dict(CFG, rng="device", seed=0, batch_size=bs, vae_iteration=0, critic_actor=1, critic_actor_graph=key), 3, dev)
+        sd = pol.vae_dyna.state_dict()
+        pol.vae_dyna.load_state_dict({k: (v / v.shape[1] ** 0.5 if k.endswith(".W") else v) for k, v in sd.items()})
+        pols[name] = pol
+
+    def leg(name, total_it):
+        pol = pols[name]
+
+        def eager():                                   # _train_stage2's eager path: the gather, then the call
+            pol.total_it = total_it
+            pol._gather(src, tar, bs)
+            pol.critic_actor_train(pol._batch)
+
+        def replay():
+            pol.total_it = total_it
+            pol.train(src, tar, bs, None, None)
+        return replay if name == "replay_key1" else eager
+    for pol in pols.values():                          # sizes the buffers; with the key set, one eager call of each kind
+        for total_it in (2, 1):
+            pol.total_it = total_it
+            pol.train(src, tar, bs, None, None)
+    return dict(critic={n: leg(n, 2) for n in pols}, actor={n: leg(n, 1) for n in pols}), pols
+
+
+def graph_main(args, dev, src, tar, fp):
+    import torch
+    out = args.out if args.out != os.path.join(ROOT, "profiles", "bosa_stage2.json") else os.path.join(ROOT, "profiles", "bosa_stage2_graph.json")
+    runs = {}
+    if os.path.exists(out):
+        old = json.load(open(out))
+        if old.get("src_fingerprint") == fp:
+            runs = {r["bs"]: r for r in old.get("runs", [])}
+    for bs in sorted(args.bs):
+        kinds, pols = make_graph_legs(dev, bs, (src, tar))
+        legs = {f"{kind}_{name}": fn for kind, d in kinds.items() for name, fn in d.items()}
+        for fn in legs.values():
+            for _ in range(args.warmup):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in legs}
+        for _ in range(args.repeats):
+            for name, fn in legs.items():
+                ms[name].append(timed(fn, args.steps))
+        rp = pols["replay_key1"]
+        rec = dict(bs=bs, rows=2 * bs, hidden=H, members=E, replays=rp.stage2_replays, captures=rp.stage2_captures)
+        for name, v in ms.items():
+            rec[name] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), spread_ms=max(v) - min(v), runs_ms=v)
+        for kind in kinds:
+            base = rec[f"{kind}_eager_key0"]
+            rec[f"{kind}_replay_over_eager_key0"] = rec[f"{kind}_replay_key1"]["median_ms"] / base["median_ms"]
+            rec[f"{kind}_eager_key1_over_eager_key0"] = rec[f"{kind}_eager_key1"]["median_ms"] / base["median_ms"]
+            rec[f"{kind}_replay_gain_beyond_spread"] = base["median_ms"] - rec[f"{kind}_replay_key1"]["median_ms"] > base["spread_ms"]
+        runs[bs] = rec
+        print(json.dumps({k: (v if not isinstance(v, dict) else {a: (round(b, 4) if isinstance(b, float) else b) for a, b in v.items() if a != "runs_ms"})
+                          for k, v in rec.items()}), flush=True)
+        del kinds, legs, pols
+    doc = dict(what="ms per stage-2 train() call (gather included), walker2d shapes S=17 A=6, VAEs 750 wide, E=5, 2 bs mixed rows: the eager call "
+                    "with config['critic_actor_graph'] unset (the parent's call), the eager call with the key set, the replayed call; critic "
+                    "calls and actor calls separately; medians over alternating repeats",
+               launches=GRAPH_LAUNCHES, src_fingerprint=fp, device=torch.cuda.get_device_name(0), steps=args.steps, warmup=args.warmup,
+               repeats=args.repeats, src_rows=args.src_rows, isa_diff=args.isa_diff, bench_c2=args.bench_c2, parent_tool=args.parent_tool)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        head = json.dumps(doc, indent=1)
+        f.write(head[:head.rindex("}")].rstrip() + ',\n "runs": [\n  ' + ",\n  ".join(json.dumps(runs[k]) for k in sorted(runs)) + "\n ]\n}\n")
+    print("wrote", out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--graph", action="store_true", help="time whole stage-2 train() calls: key unset | key set, eager | key set, replayed")
+    ap.add_argument("--isa_diff", default=None, help="text recorded in the --graph document: the line of tools/isa_diff.py against the parent build")
+    ap.add_argument("--bench_c2", default=None, help="text recorded in the --graph document: bench.py's c2 figures against the parent, alternating")
+    ap.add_argument("--parent_tool", default=None, help="text recorded in the --graph document: the parent build's own run of this tool")
     ap.add_argument("--bs", type=int, nargs="+", default=[128, 4096])
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
@@ -115,6 +216,8 @@ def main():
     src = synthetic.fill_buffer(utils.ReplayBuffer(S, A, dev, max_size=args.src_rows, rng="device", seed=100), args.src_rows, TASK, 0)
     tar = synthetic.fill_buffer(utils.ReplayBuffer(S, A, dev, max_size=5000, rng="device", seed=200), 5000, TASK, 1000)
     fp = bench.src_fingerprint()
+    if args.graph:
+        return graph_main(args, dev, src, tar, fp)
     runs = {}
     if os.path.exists(args.out):                                  # the other shapes' records of the same build
         old = json.load(open(args.out))
