@@ -84,8 +84,10 @@ class DARA(IQL):
     def _heads(self):
         return (self.classifier.sa_classifier, self.classifier.sas_classifier)
 
-    def _extra_nets(self):
-        return IQL._extra_nets(self) + self._heads()
+    def _extra_named(self):
+        c = self.classifier
+        return IQL._extra_named(self) + (("classifier.sa_classifier", c.sa_classifier, c.opt_sa),
+                                         ("classifier.sas_classifier", c.sas_classifier, c.opt_sas))
 
     # ------------------------------------------------------------------ training
     def _dims(self, N, Nt, Ng, Ntg):

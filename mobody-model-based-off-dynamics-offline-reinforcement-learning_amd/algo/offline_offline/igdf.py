@@ -114,8 +114,9 @@ class IGDF(IQL):
     def _encs(self):
         return (self.info.encoder_sa, self.info.encoder_ss)
 
-    def _extra_nets(self):
-        return IQL._extra_nets(self) + self._encs()
+    def _extra_named(self):
+        o = self.info_optimizer
+        return IQL._extra_named(self) + (("info.encoder_sa", self.info.encoder_sa, o.sa), ("info.encoder_ss", self.info.encoder_ss, o.ss))
 
     def _health_check(self):
         before = self.precision

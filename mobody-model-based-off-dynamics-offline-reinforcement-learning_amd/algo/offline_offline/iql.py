@@ -143,8 +143,8 @@ class IQL(MOBODY):
         t.blob.copy_(self.tau * q.blob + (1.0 - self.tau) * t.blob)
         ops.mlp_transpose(t.blob, t.in_dim, t.out_dim, t.members, out=t.blob_T, precision=t.precision)
 
-    def _extra_nets(self):
-        return (self.v_func,)
+    def _extra_named(self):
+        return (("v_func", self.v_func, self.v_optimizer),)
 
     # ------------------------------------------------------------------ training
     def _dims(self, N, Nt, Ng, Ntg):

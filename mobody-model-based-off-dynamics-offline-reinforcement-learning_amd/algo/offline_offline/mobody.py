@@ -36,6 +36,7 @@ class _PackedNet(object):
         self.device, self.out_mode, self.max_action = device, out_mode, float(max_action)
         self.precision = int(precision)               # MFMA mode the net is evaluated in = format of the W2 planes in blob_T
         self.layout = _lib.mlp_layout(in_dim, out_dim, members)
+        self.version = 0                              # counts rewrites of the blobs; a clone() that never loads starts at 0 too
         if init:                                      # nn.Linear default init (kaiming_uniform a=sqrt(5))
             sd = {}
             for p in prefixes:
@@ -519,9 +520,11 @@ class MOBODY(object):
         if mask == 0:
             return
         cls = self.classifier
-        nets = (("q_funcs", self.q_funcs, self.q_optimizer), ("target_q_funcs", self.target_q_funcs, self.q_optimizer),
+        nets = [("q_funcs", self.q_funcs, self.q_optimizer), ("target_q_funcs", self.target_q_funcs, self.q_optimizer),
                 ("policy", self.policy, self.policy_optimizer), ("v_func", self.v_func, self.v_optimizer),
-                ("classifier.sa_classifier", cls.sa_classifier, cls.opt_sa), ("classifier.sas_classifier", cls.sas_classifier, cls.opt_sas))
+                ("classifier.sa_classifier", cls.sa_classifier, cls.opt_sa), ("classifier.sas_classifier", cls.sas_classifier, cls.opt_sas)]
+        # and whatever else a subclass runs at the configured mode: a fault there is named, and eligible for the fallback, too
+        nets += [x for x in self._extra_named() if all(x[1] is not n for _, n, _ in nets)]
         found = []
         for name, n, opt in nets:
             w2 = ops._mlp_w2(n.blob, n.layout, n.members)
@@ -552,10 +555,14 @@ class MOBODY(object):
         self._fault = msg
         raise FloatingPointError(msg)
 
-    def _extra_nets(self):
-        """The nets a subclass runs at the configured MFMA mode besides the twin-Q, its target and the policy: a fallback moves
-        them too.  (None here: the base's V and classifier are fp32 nets.)"""
+    def _extra_named(self):
+        """(printable name, net, its optimizer) of the nets a subclass runs at the configured MFMA mode besides the twin-Q, its
+        target and the policy: the health check looks for a fault in them too, and a fallback moves them.  (None here: the base's V
+        and classifier are fp32 nets.)"""
         return ()
+
+    def _extra_nets(self):
+        return tuple(n for _, n, _ in self._extra_named())
 
     def _health_rewind(self, step, opt):
         """Host step counts back to the updates that were applied.  `step` is the faulting optimizer's own count; within a

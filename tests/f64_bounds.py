@@ -9,6 +9,13 @@ c:  C_LAYER = 2^-17 for one GEMM fed the kernel's own inputs.  "f16x2" carries 2
     The exact fp32 mode ("f32", the control) accumulates 128 K = 2 steps: <= 2^-17.  The worst case of a sequential fp32
     sum over K = 256, 256 * 2^-24 = 2^-16, is C_E2E, used where the split forward's error also reaches the operands
     (end-to-end gradients of Engine.step / pretrain_grads, the forward of a whole net).
+    C_BF16X3 = C_LAYER for one "bf16x3" GEMM (tests/test_hip_bf16x3.py).  Three bf16 terms hold all 24 significand bits
+    (|t1| <= 2^-8 |x|, |t2| <= 2^-17 |x|, nothing left over), so the only operand error is the three dropped pairs:
+    x1 y2 + x2 y1 + x2 y2 <= 2 * 2^-25 + 2^-34 ~ 2^-24 per product.  The fp32 accumulation of K = 256 runs through
+    16 k-steps x 6 products = 96 dependent MFMA adds (bf_gemm; the weight gradient's 16-row blocks give fewer per wave),
+    <= 96 * 2^-24 = 2^-17.4: together ~2^-17.4 < 2^-17.  bf16 keeps fp32's exponent range: no scaling, hence no
+    subnormal term and no slice floor (split=False).  tests/test_bf16x3_ref.py shows that a product without the pair
+    (1, 1), without (0, 2) and (2, 0), or with two planes only misses this c.
 tiny_abs:
   * SUBNORMAL = 2^-39: "f16x2" scales each 32-row tile so that its largest magnitude m lands in [2^13, 2^14); the residual
     term of a value far below m falls into fp16 subnormals, an absolute error of ~2^-39 m per operand (csrc/tile_bf.h).
@@ -21,6 +28,7 @@ import torch
 
 C_LAYER = 2.0 ** -17
 C_E2E = 2.0 ** -16
+C_BF16X3 = C_LAYER
 SUBNORMAL = 2.0 ** -39
 SWISH_LIP = 1.1                     # max |d swish / dz| = 1.0998
 
