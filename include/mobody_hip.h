@@ -1193,6 +1193,79 @@ struct MobodyBosaStage2 {
 int mobody_bosa_stage2_rows(const MobodyBosaStage2* a, void* stream);
 int mobody_bosa_stage2_words(const MobodyBosaStage2* a, void* stream);
 
+/* ---- Fitted Q evaluation ------------------------------------------------------------------------------------------
+ * The reference has no counterpart: it scores a policy in its simulators, which this build does not have.  FQE needs the recorded
+ * target transitions and the frozen policy alone: a fresh twin-Q net is regressed onto y = r + gamma not_done Q_targ(s', pi(s'))
+ * (mobody_fqe_target supplies the bootstrap value, mobody_critic in its q_next form the update) and Q(s0, pi(s0)) is reported over
+ * episode starts (mobody_fqe_value).  Both entries take the policy in one of the two forms the six algorithm classes use:
+ *   head 0   a deterministic actor, mobody_mlp_layout(S, A, 1): action = mobody_mlp3_forward(out_mode 1, max_action)
+ *            (MOBODY, TD3_BC, BOSA)
+ *   head 1   a Gaussian policy, mobody_mlp_layout(S, 2 A, 1): action = columns [0, A) of the same out_mode 1 forward over all 2 A
+ *            columns = max_action * tanh(mu), what the IQL family's select_action(test=True) returns (IQL, DARA, IGDF)
+ * The new kernels use no flags, no tickets and no atomics; each launch reads what an earlier launch on the stream wrote; every loop
+ * is bounded by an argument; every sum and maximum runs in a fixed order, so two runs give the same bits.  The grid-stride kernels
+ * size their grid from the row count (one workgroup per 256 elements).
+ *   mobody_fqe_target   q_next [N] = the mean over the two members of Q_targ(s', pi(s')).  Launches, in order: the policy forward;
+ *                       k_fqe_action, the pitch-changing copy [N][2 A] -> [N][A], for head 1 only (head 0 SKIPS it: three launches);
+ *                       mobody_mlp3_forward of the two-member target net on [s' | a']; k_fqe_qnext, which forms
+ *                       __fmul_rn(__fadd_rn(q0, q1), 0.5f) and copies a' to action_out [N][A] when that is given.  The packed
+ *                       forwards' ReLU (fmaxf) turns a NaN pre-activation into 0, so k_fqe_qnext also reads the row's s' and a' and
+ *                       gives a row with a NaN among them q_next = NaN; every other row keeps its bits.  On finite rows the result
+ *                       has the bits of mobody_mlp3_forward, a slice [:, :A], mobody_mlp3_forward and (q[0] + q[1]) * 0.5 at
+ *                       precisions 0 (f32), 3 (bf16x3) and 4 (f16x2); 1 (bf16) and 2 (bf16x2) are refused by name.  The T blobs are
+ *                       read at precision != 0 only.  workspace: mobody_fqe_target_workspace floats = round4(N A) + round4(2 N) +
+ *                       (head 1: round4(2 N A)), each piece rounded up to 4 floats; -1 for a bad block.
+ *   mobody_fqe_value    the estimate over B start states: pi(s0) by the same head rule, the twin-Q forward of q_blob on [s0 | a0],
+ *                       k_fqe_value_rows (a row with a NaN among s0, a0 gets q = NaN in both members; q_out [2][B], when given, takes
+ *                       the rows) and k_fqe_value, ONE workgroup of 256 threads: out[4] = (mean q0, mean q1, mean 0.5 (q0 + q1),
+ *                       max |q0 - q1|), nan_flag[0] = 1 when a q is NaN (all four words are then NaN) and 0 otherwise.  Thread t
+ *                       adds rows t, t + 256, ... in ascending order and a fixed tree joins the 256 partial results; the third word
+ *                       is (sum q0 + sum q1) / (2 B) of the two joined sums.  workspace: mobody_fqe_value_workspace floats, the
+ *                       closed form above with B for N.
+ * Refused with MOBODY_E_ARG before the first runtime call, the field named (both entries): struct_bytes, head outside {0, 1},
+ * S outside [1, 256], A outside [1, 128] (head 0) or 2 A > 128 (head 1), S + A > 256, N (B) < 1 or > 2^21, precision, the T blobs
+ * missing at precision != 0, a NULL policy_blob / q_blob / next_state (state) / q_next (out, nan_flag) / workspace, max_action <= 0
+ * or NaN. */
+typedef struct MobodyFqeTarget MobodyFqeTarget;
+struct MobodyFqeTarget {
+  int32_t struct_bytes;
+  int32_t precision;
+  int32_t head;                             /* 0 deterministic actor, 1 Gaussian policy */
+  int32_t S, A;
+  int32_t reserved;                         /* 0 */
+  int64_t N;
+  const float *policy_blob, *policy_blob_T; /* the frozen policy: mobody_mlp_layout(S, A, 1) (head 0) or (S, 2 A, 1) (head 1) */
+  const float *q_blob, *q_blob_T;           /* FQE's TARGET twin-Q, mobody_mlp_layout(S + A, 1, 2) */
+  const float* next_state;                  /* [N][S] */
+  float max_action;
+  int32_t reserved1;                        /* 0 */
+  float* action_out;                        /* [N][A], or NULL */
+  float* q_next;                            /* [N] */
+  float* workspace;
+};
+int64_t mobody_fqe_target_workspace(const MobodyFqeTarget* a);
+int mobody_fqe_target(const MobodyFqeTarget* a, void* stream);
+typedef struct MobodyFqeValue MobodyFqeValue;
+struct MobodyFqeValue {
+  int32_t struct_bytes;
+  int32_t precision;
+  int32_t head;
+  int32_t S, A;
+  int32_t reserved;                         /* 0 */
+  int64_t B;
+  const float *policy_blob, *policy_blob_T;
+  const float *q_blob, *q_blob_T;           /* FQE's ONLINE twin-Q */
+  const float* state;                       /* [B][S] start states */
+  float max_action;
+  int32_t reserved1;                        /* 0 */
+  float* q_out;                             /* [2][B], or NULL */
+  float* out;                               /* [4] */
+  int32_t* nan_flag;                        /* [1] */
+  float* workspace;
+};
+int64_t mobody_fqe_value_workspace(const MobodyFqeValue* a);
+int mobody_fqe_value(const MobodyFqeValue* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -212,6 +212,18 @@ class MobodyBosaStage2(C.Structure):
                 ("aloss", vp), ("words", vp), ("bump", vp), ("bump_inc", i64 * 4)]
 
 
+class MobodyFqeTarget(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("head", i32), ("S", i32), ("A", i32), ("reserved", i32), ("N", i64),
+                ("policy_blob", vp), ("policy_blob_T", vp), ("q_blob", vp), ("q_blob_T", vp), ("next_state", vp), ("max_action", f32),
+                ("reserved1", i32), ("action_out", vp), ("q_next", vp), ("workspace", vp)]
+
+
+class MobodyFqeValue(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("head", i32), ("S", i32), ("A", i32), ("reserved", i32), ("B", i64),
+                ("policy_blob", vp), ("policy_blob_T", vp), ("q_blob", vp), ("q_blob_T", vp), ("state", vp), ("max_action", f32),
+                ("reserved1", i32), ("q_out", vp), ("out", vp), ("nan_flag", vp), ("workspace", vp)]
+
+
 WIDE_OUT_MODES = {"raw": 0, "tanh": 1}
 BOSA_KINDS = {"policy": 0, "dynamics": 1}
 BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9, "target_noise": 10}    # MOBODY_BOSA_STREAM_*
@@ -224,7 +236,7 @@ def block(cls, **fields):
 
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
                                              MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyBosaTarget, MobodyBosaStage2, MobodyEnsStep, MobodyEnsRollout,
-                                             MobodyEnsEval, MobodyEnsReplay)}
+                                             MobodyEnsEval, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -345,6 +357,10 @@ PROTOTYPES = {
     "mobody_bosa_target": (C.c_int, [C.POINTER(MobodyBosaTarget), vp]),
     "mobody_bosa_stage2_rows": (C.c_int, [C.POINTER(MobodyBosaStage2), vp]),
     "mobody_bosa_stage2_words": (C.c_int, [C.POINTER(MobodyBosaStage2), vp]),
+    "mobody_fqe_target_workspace": (i64, [C.POINTER(MobodyFqeTarget)]),
+    "mobody_fqe_target": (C.c_int, [C.POINTER(MobodyFqeTarget), vp]),
+    "mobody_fqe_value_workspace": (i64, [C.POINTER(MobodyFqeValue)]),
+    "mobody_fqe_value": (C.c_int, [C.POINTER(MobodyFqeValue), vp]),
 }
 
 _lib = None

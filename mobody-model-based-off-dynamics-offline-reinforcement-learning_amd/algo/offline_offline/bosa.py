@@ -285,6 +285,10 @@ class BOSA(object):
         x = state if isinstance(state, torch.Tensor) else torch.as_tensor(np.asarray(state), dtype=torch.float32)
         return self.actor(x.reshape(1, -1).to(self.device)).squeeze().cpu().numpy()
 
+    def eval_policy(self):
+        """(net, head) for fitted Q evaluation: the TD3 actor, head 0."""
+        return self.actor, 0
+
     def _seed_for(self, k):
         return (self.seed + k + dp.rank_salt()) & 0xFFFFFFFF
 

@@ -137,6 +137,10 @@ class IQL(MOBODY):
         action, _, mean = self.policy(x.to(self.device))
         return (mean if test else action).squeeze().cpu().numpy()
 
+    def eval_policy(self):
+        """(net, head) for fitted Q evaluation: the Gaussian policy, head 1 (max_action * tanh(mu), select_action's test action)."""
+        return self.policy, 1
+
     def update_target(self):
         """iql.py:168-172.  (train() does not call it: the critic's optimizer launch applies the Polyak update itself.)"""
         t, q = self.target_q_funcs, self.q_funcs

@@ -340,6 +340,10 @@ class MOBODY(object):
         action = policy(x.reshape(-1, self.S).to(self.device))
         return action.squeeze() if cuda else action.squeeze().cpu().numpy()
 
+    def eval_policy(self):
+        """(net, head) of the policy as fitted Q evaluation reads it (mobody_amd.fqe): the deterministic actor, head 0."""
+        return self.policy, 0
+
     # ------------------------------------------------------------------ DARA classifier (mobody.py:146-181, 354-381)
     def update_classifier(self, src_replay_buffer, tar_replay_buffer, batch_size, writer=None, noise=None, labels=None,
                           rows=None):

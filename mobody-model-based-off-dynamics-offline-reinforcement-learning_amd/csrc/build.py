@@ -22,7 +22,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    srcs = sorted(glob.glob(os.path.join(HERE, "*.hip")))
+    # fqe.hip is linked after the others: every older kernel's code object keeps its place and its bytes (tools/isa_diff.py)
+    srcs = sorted(glob.glob(os.path.join(HERE, "*.hip")), key=lambda s: (os.path.basename(s) == "fqe.hip", s))
     hdrs = sorted(glob.glob(os.path.join(HERE, "*.h"))) + [os.path.join(HERE, "..", "..", "include", "mobody_hip.h")]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)

@@ -1119,3 +1119,50 @@ def bosa_stage2_words(N, words, mask_mean=None, closs=None, cons_coef=0.0, ll=No
                      aloss=ptr(aloss), lamda=float(lamda), words=ptr(words), bump=ptr(bump), nbump=len(bump_inc),
                      bump_inc=(C.c_int64 * 4)(*[int(x) for x in bump_inc]))
     check(load().mobody_bosa_stage2_words(C.byref(blk), cur_stream()), "mobody_bosa_stage2_words")
+
+
+# ---- fitted Q evaluation (csrc/fqe.hip) -----------------------------------------------------------------------------
+def _block_workspace(name, blk, device):
+    n = getattr(load(), name)(C.byref(blk))
+    if n < 0:
+        raise _lib.MobodyError(name + ": bad block: " + load().mobody_last_error().decode(errors="replace"))
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _fqe_fields(policy, head, q, state, policy_T):
+    """The fields both FQE blocks share: `policy` the frozen net (head 0: out_dim A; head 1: out_dim 2 A), `q` a twin-Q (in_dim
+    S + A) whose precision the call runs at; policy_T: the policy's T blob in THAT precision's format (None: the policy's own)."""
+    S = state.shape[1]
+    return dict(precision=prec_id(q.precision), head=int(head), S=S, A=q.in_dim - S, policy_blob=ptr(policy.blob),
+                policy_blob_T=ptr(policy.blob_T if policy_T is None else policy_T), q_blob=ptr(q.blob), q_blob_T=ptr(q.blob_T),
+                max_action=float(policy.max_action))
+
+
+def fqe_target_block(policy, head, q_target, next_state, q_next, action_out=None, ws=None, policy_T=None):
+    """A MobodyFqeTarget block: `q_target` FQE's target twin-Q."""
+    return _lib.block(_lib.MobodyFqeTarget, N=next_state.shape[0], next_state=ptr(next_state), action_out=ptr(action_out),
+                      q_next=ptr(q_next), workspace=ptr(ws), **_fqe_fields(policy, head, q_target, next_state, policy_T))
+
+
+def fqe_target_workspace(blk, device):
+    return _block_workspace("mobody_fqe_target_workspace", blk, device)
+
+
+def fqe_target(blk):
+    """q_next [N] = mean over the two members of Q_targ(s', pi(s')), pi by the block's head rule."""
+    check(load().mobody_fqe_target(C.byref(blk), cur_stream()), "mobody_fqe_target")
+
+
+def fqe_value_block(policy, head, q, state, out, nan_flag, q_out=None, ws=None, policy_T=None):
+    """A MobodyFqeValue block: `q` FQE's online twin-Q, out float32[4], nan_flag int32[1], q_out [2][B] or None."""
+    return _lib.block(_lib.MobodyFqeValue, B=state.shape[0], state=ptr(state), q_out=ptr(q_out), out=ptr(out), nan_flag=ptr(nan_flag),
+                      workspace=ptr(ws), **_fqe_fields(policy, head, q, state, policy_T))
+
+
+def fqe_value_workspace(blk, device):
+    return _block_workspace("mobody_fqe_value_workspace", blk, device)
+
+
+def fqe_value(blk):
+    """out = (mean q0, mean q1, mean 0.5 (q0 + q1), max |q0 - q1|) of Q(s0, pi(s0)) over the block's start states."""
+    check(load().mobody_fqe_value(C.byref(blk), cur_stream()), "mobody_fqe_value")

@@ -486,6 +486,21 @@ def _run(args, rank, world, device):
                                    int(config["model_eval_episodes"]), args.seed)
             eval_obs = tar_rb.state[torch.as_tensor(rows, device=tar_rb.state.device)].contiguous()
 
+    # Fitted Q evaluation of the policy on the recorded target transitions (mobody_amd.fqe; every algorithm): optional keys of the
+    # merged config, off by default.  Rank 0 evaluates alone; start states are episode starts of the target data, chosen once.
+    fqe, fqe_obs = None, None
+    if int(config.get("fqe_steps", 0)) > 0 and rank == 0:
+        from mobody_amd.fqe import FQE
+        n = tar_rb.size
+        term = 1.0 - tar_rb.not_done[:n].cpu().numpy()
+        rows = model_eval_rows(episode_starts(tar_rb.state[:n].cpu().numpy(), tar_rb.next_state[:n].cpu().numpy(), term),
+                               int(config.get("fqe_episodes", 256)), args.seed)
+        fqe_obs = tar_rb.state[torch.as_tensor(rows, device=tar_rb.state.device)].contiguous()
+        net, head = policy.eval_policy()
+        fqe = FQE(net, head, state_dim, action_dim, max_action, float(config["gamma"]), device, net.precision,
+                  lr=float(config.get("fqe_lr", 3e-4)), tau=float(config.get("tau", 0.005)), batch_size=int(config.get("fqe_batch_size", 256)),
+                  seed=args.seed, rng=args.rng)
+
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
     if config.get("info_pretrain") and hasattr(policy, "update_info"):
@@ -540,6 +555,17 @@ def _run(args, rank, world, device):
                 writer.add_scalar("test/model episode length", ev["length_mean"], global_step=t + 1)
                 writer.add_scalar("test/model penalty", ev["penalty_mean"], global_step=t + 1)
                 writer.add_scalar("test/model alive frac", ev["alive_frac"], global_step=t + 1)
+            if writer is not None and fqe is not None:
+                # the discounted value at config['gamma'] of the policy as it is now, by FQE: an estimate whose bias grows with the
+                # policy's distance from the data; not a return, so no normalized score is derived from it
+                t0 = time.time()
+                fqe.prepare(warm_start=bool(int(config.get("fqe_warm_start", 0))))
+                if fqe.fit(tar_rb, int(config["fqe_steps"])):
+                    ev = fqe.value(fqe_obs)
+                    writer.add_scalar("test/fqe value", ev["value"], global_step=t + 1)
+                    writer.add_scalar("test/fqe head gap", ev["head_gap"], global_step=t + 1)
+                    writer.add_scalar("test/fqe td loss", fqe.td_loss(), global_step=t + 1)
+                    writer.add_scalar("test/fqe seconds", time.time() - t0, global_step=t + 1)
             if writer is not None:
                 writer.flush()
             if args.save_model:
