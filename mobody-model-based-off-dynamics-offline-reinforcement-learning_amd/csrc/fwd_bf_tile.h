@@ -131,12 +131,17 @@ __device__ __forceinline__ void mlp3_fwd_bf_tile(const Mlp3FwdArgs& a, int m, fl
     NarrowRegs<NT> br;
     const int mycol = threadIdx.x % (16 * NT);
     float bias;
+    // a one-output net (twin-Q) forms its output as an fma chain (tile.h narrow_run_one): a wave-uniform branch, and the one
+    // weight a lane needs travels in the first register of the fragments it does not fetch
+    const bool one = fwd_rank1<NT>(a);
     bf_layer<ACT, MT, PM, TB, DS, PQ>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [&] {
-      narrow_prefetch<NT>(w3, 16 * NT, br);
+      if (one) br.b[0][0] = narrow_prefetch_one(w3, 16 * NT);
+      else narrow_prefetch<NT>(w3, 16 * NT, br);
       bias = b3[mycol < a.nout ? mycol : 0];
     }, t.mask2, mg, rows_here, t.h2, d2);
     TR(4);
-    narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
+    if (one) narrow_run_one<TB / 16>(Xs, br.b[0][0], [&](int row, int col, float v) { emit(row, col, v, bias); });
+    else narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
   } else {
     bf_layer<ACT, MT, PM, TB, DS, PQ>(Xs, Ps, e1, w2b, a.b2 + m * a.sb2, bring, [] {}, t.mask2, mg, rows_here, t.h2, d2);
     narrow_layer(Xs, w3, HID, a.Np3, [&](int row, int col, float v) { emit(row, col, v, b3[col < a.nout ? col : 0]); }, TB);

@@ -379,6 +379,18 @@ __device__ __forceinline__ FwdTileOut fwd_tile_out(const Mlp3FwdArgs& a, int m, 
   return t;
 }
 
+// Whether this net's output layer runs as tile.h narrow_run_one: one live column of a 16-column output layer (twin-Q).
+// Uniform over the launch's member slice.  -DMOBODY_NO_FWD_RANK1 (build.py MOBODY_EXTRA_FLAGS) keeps the MFMA form everywhere: the
+// A/B parent.
+template <int NT>
+__device__ __forceinline__ bool fwd_rank1(const Mlp3FwdArgs& a) {
+#ifdef MOBODY_NO_FWD_RANK1
+  return false;
+#else
+  return NT == 1 && a.nout == 1;
+#endif
+}
+
 // One element of the output layer: bias, tanh * max_action, residual, guarded store.
 __device__ __forceinline__ void fwd_emit(const Mlp3FwdArgs& a, float* out, long long row0, int rows_here, int row, int col,
                                          float v, float bias) {

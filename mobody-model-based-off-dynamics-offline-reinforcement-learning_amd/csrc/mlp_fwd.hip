@@ -28,12 +28,15 @@ __device__ __forceinline__ void mlp3_fwd_tail(const Mlp3FwdArgs& a, int m, float
     // b3 of this thread's output columns: element e = threadIdx.x + 256 k has column e % (16 NT), the same for all k
     const int mycol = threadIdx.x % (16 * NT);
     float bias;
+    const bool one = fwd_rank1<NT>(a);             // a one-output net: the fma chain of tile.h narrow_run_one (as fwd_bf_tile.h)
     wide_layer<ACT, MLP_MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [&] {
-      narrow_prefetch<NT>(w3, 16 * NT, br);
+      if (one) br.b[0][0] = narrow_prefetch_one(w3, 16 * NT);
+      else narrow_prefetch<NT>(w3, 16 * NT, br);
       bias = b3[mycol < a.nout ? mycol : 0];
     }, mask2, full, (rows_here + 31) / 32);
     TR(4);
-    narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
+    if (one) narrow_run_one<TB / 16>(Xs, br.b[0][0], [&](int row, int col, float v) { emit(row, col, v, bias); });
+    else narrow_run<TB / 16, NT>(Xs, br, [&](int row, int col, float v) { emit(row, col, v, bias); });
   } else {
     wide_layer<ACT, MLP_MT>(Xs, a.w2 + m * a.sw2, a.b2 + m * a.sb2, HID, ring, save_h2, [] {}, mask2, full, (rows_here + 31) / 32);
     TR(4);

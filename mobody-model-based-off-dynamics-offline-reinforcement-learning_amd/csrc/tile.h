@@ -312,7 +312,10 @@ __device__ __forceinline__ void narrow_layer(const float* __restrict__ Xs, const
 // for ALL rows, so its weight fragments are just 16*NT registers that can be requested long before the layer
 // starts (narrow_prefetch); the four partial results meet in LDS.  The row-split narrow_gemm above keeps two of
 // four waves idle on a 32-row tile and walks K = 256 in four dependent load rounds (3.7 us per tile measured,
-// against 0.2 us of MFMA work).  Lane (i = lane&15, q = lane>>4) supplies k = 64w + 16q + s at step s.
+// against 0.2 us of MFMA work).  Lane (i = lane&15, q = lane>>4) supplies k = 64w + 16q + s at step s; one MFMA adds its four
+// k-blocks q = 0..3 onto the accumulator in that order, so an output element is ONE fp32 fma chain per wave -- s outer, q
+// inner -- and ((p0 + p1) + p2) + p3 over the waves (tests/fwd_rank1_ref.py states it, tests/test_hip_fwd_rank1.py holds the
+// layer to it).  Heads of more than one live column run here; a one-output net (twin-Q) takes narrow_run_one below.
 // --------------------------------------------------------------------------------------------
 template <int NT>
 struct NarrowRegs { float b[16][NT]; };
@@ -367,6 +370,50 @@ __device__ __forceinline__ void narrow_run(float* Xs, const NarrowRegs<NT>& br, 
   for (int e = threadIdx.x; e < ROWS * Np; e += NTHREADS) {
     const float v = ((Xs[e] + Xs[ROWS * Np + e]) + Xs[2 * ROWS * Np + e]) + Xs[3 * ROWS * Np + e];
     f(e / Np, e % Np, v);
+  }
+}
+
+// The same K-split layer for a net with ONE output (twin-Q: Np = 16, column 0 live), without the matrix core: narrow_run spends
+// 16 * MTN MFMAs per wave on 16 columns of which the caller keeps one, 16 strided weight loads and 4 * MTN partial stores per
+// lane, and a 16 * ROWS-element reduction.  Here lane l of wave w fetches the ONE weight W[64w + l][0] (narrow_prefetch_one,
+// where narrow_prefetch stands), lane r owns row r and runs one fp32 fma chain from zero over the wave's 64 k in exactly the
+// order the MFMA sequence of narrow_run accumulates that element -- v_mfma_f32_16x16x4_f32 adds its four k-blocks 0..3 in
+// that order onto C, and narrow_run issues steps s = 0..15, so the chain is: s outer, q inner, k = 64w + 16q + s -- with the
+// weight as a wave-uniform operand (v_readlane of lane 16q + s).  The four partials meet in LDS as 4 x ROWS floats behind the
+// same barrier and are summed ((p0 + p1) + p2) + p3 as there: every bit of narrow_run's column 0 (tests/test_hip_fwd_rank1.py
+// holds both to the NumPy statement of this order).  Lanes past ROWS repeat row lane - ROWS (no divergent flow around the
+// readlanes); their reads hit the same 16-byte slots as their twins'.  f(row, 0, value) once per row; overwrites Xs.
+__device__ __forceinline__ float narrow_prefetch_one(const float* __restrict__ W, int Np) {
+  const float wk = W[(size_t)(64 * wave_id() + lane_id()) * Np];
+  __builtin_amdgcn_sched_barrier(0);
+  return wk;
+}
+
+template <int MTN, class F>
+__device__ __forceinline__ void narrow_run_one(float* Xs, float wk, F&& f) {
+  constexpr int ROWS = 16 * MTN;
+  static_assert(ROWS <= 64 && (ROWS & (ROWS - 1)) == 0, "one lane per row");
+  const int lane = lane_id(), w = wave_id();
+  const float* xa = Xs + (lane & (ROWS - 1)) * LDX + 64 * w;
+  const int wki = __builtin_bit_cast(int, wk);
+  float acc = 0.f;
+#pragma unroll
+  for (int s4 = 0; s4 < 4; ++s4) {
+    f32x4 xv[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) xv[q] = *reinterpret_cast<const f32x4*>(xa + 16 * q + 4 * s4);
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        acc = fmaf(xv[q][u], __builtin_bit_cast(float, __builtin_amdgcn_readlane(wki, 16 * q + 4 * s4 + u)), acc);
+  }
+  lds_barrier();                                 // every wave has read its slice of the image
+  if (lane < ROWS) Xs[w * ROWS + lane] = acc;
+  lds_barrier();
+  if (threadIdx.x < ROWS) {
+    const int r = threadIdx.x;
+    f(r, 0, ((Xs[r] + Xs[ROWS + r]) + Xs[2 * ROWS + r]) + Xs[3 * ROWS + r]);
   }
 }
 
