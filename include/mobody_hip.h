@@ -1266,6 +1266,67 @@ struct MobodyFqeValue {
 int64_t mobody_fqe_value_workspace(const MobodyFqeValue* a);
 int mobody_fqe_value(const MobodyFqeValue* a, void* stream);
 
+/* ---- Every policy in the learned model, with member spread -----------------------------------------------------------
+ * mobody_ens_evaluate_policy is mobody_ens_evaluate for both policy head forms, with an optional fixed member per episode; the two
+ * entries run one host loop.  What it computes: the row state of mobody_ens_evaluate (same semantics per step, same accounting),
+ * with the action of step t formed by the head rule of mobody_fqe_target:
+ *   head 0   policy_blob is mobody_mlp_layout(S, A, 1); a = mobody_mlp3_forward(out_mode 1, max_action)
+ *   head 1   policy_blob is mobody_mlp_layout(S, 2 A, 1); a = columns [0, A) of the same out_mode 1 forward over all 2 A columns
+ *            = max_action * tanh(mu), what the IQL family's select_action(test=True) returns
+ * and the elite of row b at step t chosen by member_mode:
+ *   0   drawn per row and per step by the sample kernel (elite_idx = NULL), as mobody_ens_evaluate
+ *   1   member[b] for every step of the episode (PETS' TS-infinity): `member` int32 [B] is caller-owned row state, read and written
+ *       in this mode only.  resume == 0 sets member[b] = elites[b % n_elites]; resume == 1 reads it as it is.  Every step hands
+ *       `member` to the sample kernel as elite_idx; the noise stays the device generator's at call id call0 + t + call_dev[0].
+ *       With B = n_elites * K rows, row b is start state b / n_elites under member b % n_elites.
+ * Launches, in order.  resume == 0: k_eval_init, then k_eval_members (member_mode 1 only).  Per step: the policy forward;
+ * k_fqe_action, the pitch-changing copy [B][2 A] -> [B][A] (head 1 only: head 0 SKIPS it); the member forward; k_dyn_sample; the
+ * reward head; k_eval_account.  5 launches per step at head 0, 6 at head 1, whatever member_mode is.  With head = 0 and
+ * member_mode = 0 the launches and the bits are those of mobody_ens_evaluate.  Head 1 has the bits of mobody_mlp3_forward on the
+ * (S, 2 A, 1) net, the slice [:, :A], mobody_ens_step under the carried alive mask (elite_idx = member in mode 1) and the accounting.
+ * MOBODY_E_ARG before the first runtime call, the field named: struct_bytes, head outside {0, 1}, member_mode outside {0, 1},
+ * 2 A > 128 at head 1, a null `member` in mode 1, and everything mobody_ens_evaluate refuses (the policy's blobs under the names
+ * policy_blob / policy_blob_T).  B == 0 returns 0.  H == 0 with resume == 0 only initialises the row state, `member` included.
+ * workspace: mobody_ens_evaluate_policy_workspace(a) floats (reads S, A, B, head; -1 for a bad block) = round4(B A) + round4(B S) +
+ * round4(B) + round4(7 B S + 7 B) + 2 round4(ceil(B / 4)) + (head 1: round4(2 B A)), round4(n) = n rounded up to 4 floats: the
+ * pieces of mobody_ens_evaluate_workspace in their places, the Gaussian policy's output behind them.
+ * (Declared as a tagged struct plus its typedef, as MobodyEnsEval.) */
+struct MobodyEnsEvalPolicy {
+  int32_t struct_bytes, uncertainty_mode;
+  const float *dyn_blob, *dyn_planes, *mopo_blob, *mopo_blob_T, *policy_blob, *policy_blob_T;
+  int32_t precision, S, A, task;
+  const float* init_obs;            /* [B][S]; read only when resume == 0 */
+  int64_t B;
+  int32_t H, n_elites;
+  const int32_t* elites;            /* HOST array */
+  uint32_t seed, call0;
+  const int64_t* call_dev;          /* nullable */
+  float max_action, discount;       /* discount in (0, 1] */
+  int32_t use_trg, resume;
+  float* obs_state;                 /* [B][S] current observation */
+  uint8_t* alive;                   /* [B] */
+  float *ret, *pen_sum, *disc;      /* [B] each */
+  int32_t* length;                  /* [B] */
+  int32_t head, member_mode;        /* 0 / 1 each */
+  int32_t* member;                  /* [B]; member_mode 1 only (else nullable) */
+  float* workspace;
+};
+typedef struct MobodyEnsEvalPolicy MobodyEnsEvalPolicy;
+int64_t mobody_ens_evaluate_policy_workspace(const MobodyEnsEvalPolicy* a);
+int mobody_ens_evaluate_policy(const MobodyEnsEvalPolicy* a, void* stream);
+
+/* mobody_eval_summary: the figures of a finished row state, by member group.  Row b belongs to group b % G (G = 1: the overall
+ * figures only).  out [G + 1][4] = (mean return, mean length, mean penalty sum, alive share) per group, the last row the same four
+ * figures over all rows; nan_flag[0] = 1 when a ret or pen_sum is NaN, 0 otherwise.  One launch, k_eval_summary: ONE workgroup of
+ * 256 threads and no atomics (k_fqe_value's pattern).  Thread t adds rows t, t + 256, ... in ascending order into per-group
+ * accumulators and, in the same order, into accumulators over all rows; a fixed tree joins the 256 partial results, so two runs give
+ * the same bits.  Lengths and alive counts are summed as 64-bit integers and are exact; each mean is one division by the group's row
+ * count (the two integer means in fp64, rounded to fp32 once).  A NaN row makes its group's figure and the overall one NaN and
+ * leaves the other groups' bits alone.  An empty group (B <= its index) gets four NaNs and does not raise the flag.
+ * MOBODY_E_ARG before the first runtime call, the field named: G outside 1..7, B < 1, any null pointer.  No workspace (0 floats). */
+int mobody_eval_summary(const float* ret, const float* pen_sum, const int32_t* length, const uint8_t* alive, int64_t B, int G,
+                        float* out, int32_t* nan_flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,15 @@ class MobodyEnsEval(C.Structure):
                 ("workspace", vp)]
 
 
+class MobodyEnsEvalPolicy(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
+                ("mopo_blob_T", vp), ("policy_blob", vp), ("policy_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32),
+                ("task", i32), ("init_obs", vp), ("B", i64), ("H", i32), ("n_elites", i32), ("elites", C.POINTER(i32)),
+                ("seed", u32), ("call0", u32), ("call_dev", vp), ("max_action", f32), ("discount", f32), ("use_trg", i32),
+                ("resume", i32), ("obs_state", vp), ("alive", vp), ("ret", vp), ("pen_sum", vp), ("disc", vp), ("length", vp),
+                ("head", i32), ("member_mode", i32), ("member", vp), ("workspace", vp)]
+
+
 class MobodyEnsReplay(C.Structure):
     _fields_ = [("struct_bytes", i32), ("uncertainty_mode", i32), ("dyn_blob", vp), ("dyn_planes", vp), ("mopo_blob", vp),
                 ("mopo_blob_T", vp), ("precision", i32), ("S", i32), ("A", i32), ("task", i32),
@@ -236,7 +245,7 @@ def block(cls, **fields):
 
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
                                              MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyBosaTarget, MobodyBosaStage2, MobodyEnsStep, MobodyEnsRollout,
-                                             MobodyEnsEval, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue)}
+                                             MobodyEnsEval, MobodyEnsEvalPolicy, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -275,6 +284,9 @@ PROTOTYPES = {
     "mobody_ens_rollout": (C.c_int, [C.POINTER(MobodyEnsRollout), vp]),
     "mobody_ens_evaluate_workspace": (i64, [C.POINTER(MobodyEnsEval)]),
     "mobody_ens_evaluate": (C.c_int, [C.POINTER(MobodyEnsEval), vp]),
+    "mobody_ens_evaluate_policy_workspace": (i64, [C.POINTER(MobodyEnsEvalPolicy)]),
+    "mobody_ens_evaluate_policy": (C.c_int, [C.POINTER(MobodyEnsEvalPolicy), vp]),
+    "mobody_eval_summary": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, vp, vp, vp]),
     "mobody_ens_replay_workspace": (i64, [C.POINTER(MobodyEnsReplay)]),
     "mobody_ens_replay": (C.c_int, [C.POINTER(MobodyEnsReplay), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),

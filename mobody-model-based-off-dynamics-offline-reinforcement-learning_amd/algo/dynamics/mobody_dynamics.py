@@ -87,6 +87,8 @@ class MOBODYEnsembleDynamics(object):
         self._ws = None
         # evaluate_policy: its own row state / workspace / call word (per B), chunk graph, call counter, capture count
         self._eval, self._eval_graph, self._eval_calls, self.eval_captures = None, None, 0, 0
+        # ... through mobody_ens_evaluate_policy (head 1 / members): its own row state with `member`, graph and summary words
+        self._evalp, self._evalp_graph, self._evalp_T = None, None, None
         # open_loop_error: its own row state / tables / workspace (per B, H) and call counter
         self._replay, self._replay_calls, self._replay_rows = None, 0, None
         self._pre_ws_by_b, self._pre_bufs_by_b, self._train_calls = {}, {}, 0
@@ -144,7 +146,8 @@ class MOBODYEnsembleDynamics(object):
         return r["next_obs"], r["reward"], terminal, info
 
     @torch.no_grad()
-    def evaluate_policy(self, actor_net, init_obs, horizon, use_trg=True, discount=1.0, chunk=50, seed_offset=MODEL_EVAL_SEED):
+    def evaluate_policy(self, actor_net, init_obs, horizon, use_trg=True, discount=1.0, chunk=50, seed_offset=MODEL_EVAL_SEED,
+                        head=0, members=False, entry=None):
         """The policy's return in this model (`mobody_ens_evaluate`): eval_policy_batch's accounting (train_mobody.py:60-98)
         with the learned step in the simulator's place.  Every row of `init_obs` is one episode of at most `horizon` steps;
         a row's return is the discounted sum of the ensemble's raw mean rewards up to and including its terminating step.
@@ -155,7 +158,20 @@ class MOBODYEnsembleDynamics(object):
         state is initialised, then one captured graph of `chunk` steps is replayed horizon // chunk times (the call id lives
         in a device word the graph advances) and the remainder runs eagerly; chunk = 0: one eager call.  Returns device
         tensors `returns`, `lengths`, `penalty_sums`, `alive` [B] and the float means `return_mean`, `length_mean`,
-        `penalty_mean`, `alive_frac` (the one synchronisation)."""
+        `penalty_mean`, `alive_frac` (the one synchronisation).
+
+        head = 1: `actor_net` is a Gaussian policy (S, 2A, 1) and the action is max_action * tanh(mu); members = True: every
+        start state is rolled once per elite, each episode keeping its elite for its whole length (see _evaluate_policy_ens).
+        With the defaults the call takes the path above (`mobody_ens_evaluate`), bit for bit.  entry='policy' sends head 0 without
+        members through `mobody_ens_evaluate_policy` as well (the same launches per step; tools/bench_model_eval.py measures it).
+
+        On either path the policy is evaluated in the MODEL's MFMA format: when `actor_net` is in another one (its class's
+        F16_RANGE fallback to bf16x3 in an f16x2 model) a T blob in the model's format is built for this evaluation
+        (_policy_planes; the policy's own planes are not written).  With matching formats the policy's own T blob is read."""
+        if entry not in (None, "policy"):
+            raise ValueError(f"evaluate_policy: entry {entry!r}: None or 'policy'")
+        if int(head) != 0 or members or entry == "policy":
+            return self._evaluate_policy_ens(actor_net, init_obs, horizon, use_trg, discount, chunk, seed_offset, int(head), bool(members))
         m = self.model
         m.inference()
         obs = torch.as_tensor(init_obs, dtype=torch.float32).to(m.device).reshape(-1, m.obs_dim).contiguous()
@@ -169,13 +185,14 @@ class MOBODYEnsembleDynamics(object):
         _, st, ws, ctr = self._eval
         kw = self._model_kw(seed_offset)
         mopo, planes, seed = kw["mopo"], kw["dyn_planes"], kw["seed"]
+        actor_T = self._policy_planes(actor_net)          # the policy's own T blob unless its format is not the model's
         call0 = self._eval_calls + 1
         self._eval_calls += H
 
         def run(h, call, resume, call_dev=None):
             return ops.ens_evaluate(actor_blob=actor_net.blob, max_action=actor_net.max_action, init_obs=None if resume else obs,
                                     H=h, call0=call & 0xFFFFFFFF, state=st, use_trg=use_trg, discount=discount, resume=resume,
-                                    ws=ws, actor_blob_T=actor_net.blob_T, call_dev=call_dev, **kw)
+                                    ws=ws, actor_blob_T=actor_T, call_dev=call_dev, **kw)
 
         if chunk == 0 or H <= chunk:
             ws = run(H, call0, False)
@@ -185,7 +202,7 @@ class MOBODYEnsembleDynamics(object):
             ctr.fill_(call0)
             # every pointer and scalar the captured launches bake in (a reloaded model re-packs its blob: a new key).  The
             # graph keeps the tensors it reads alive, so a stale address is never handed out again while it could be replayed
-            held = [t for t in (ws, m.packed(), actor_net.blob, actor_net.blob_T, planes) + (mopo or ()) if t is not None]
+            held = [t for t in (ws, m.packed(), actor_net.blob, actor_T, planes) + (mopo or ()) if t is not None]
             key = (chunk, bool(use_trg), float(discount), seed, self.precision, self._unc_id, float(actor_net.max_action),
                    tuple(m.elites_host()), mopo is not None) + tuple(t.data_ptr() for t in held)
 
@@ -217,6 +234,101 @@ class MOBODYEnsembleDynamics(object):
         else:
             means = [float("nan")] * 4
         out.update(return_mean=means[0], length_mean=means[1], penalty_mean=means[2], alive_frac=means[3])
+        return out
+
+    def _policy_planes(self, net):
+        """The policy's T blob in the MODEL's MFMA format: the policy's own when the formats agree (or the model runs exact
+        fp32, which reads no planes), else -- e.g. after the policy's F16_RANGE fallback to bf16x3 -- a copy built here from the
+        policy's fp32 weights, rebuilt per evaluation (the policy trains in between).  The policy's own planes are not written.
+        A weight the model's f16x2 planes cannot hold is a ValueError (ops.mlp_transpose's check, one extra host read)."""
+        if net.precision == self.precision or self.precision == 0:
+            return net.blob_T
+        if self._evalp_T is None or self._evalp_T.shape != net.blob_T.shape:
+            self._evalp_T = torch.empty_like(net.blob_T)
+        ops.mlp_transpose(net.blob, net.in_dim, net.out_dim, net.members, out=self._evalp_T, precision=self.precision)
+        return self._evalp_T
+
+    def _evaluate_policy_ens(self, net, init_obs, horizon, use_trg, discount, chunk, seed_offset, head, members):
+        """evaluate_policy through `mobody_ens_evaluate_policy`: either policy head form and, with `members`, one return per
+        elite member.  members: the rows are init_obs.repeat_interleave(G, 0) with G = n_elites, row b is episode b // G under
+        member b % G for every step (PETS' TS-infinity), and the disagreement of the G member means is an error bar on the
+        estimate.  The same seed stream and call counter as evaluate_policy, a row state / workspace / chunk graph of its own
+        (the graph key also holds head and members); no training RNG stream, counter, ring or workspace moves.  The result is
+        read with ONE host read of `mobody_eval_summary`'s words and flag (the flag through an int32 view of the copy); only a
+        policy in another MFMA format than the model costs a second one, the weight check of _policy_planes.  Returns evaluate_policy's entries over all rows plus
+        `return_member_means` [G] (G = 1 without members), `return_member_spread` (max - min of them) and `nan`."""
+        if head not in (0, 1):
+            raise ValueError(f"evaluate_policy: head {head!r}: 0 (deterministic actor) or 1 (Gaussian policy)")
+        m = self.model
+        m.inference()
+        S, A = m.obs_dim, m.action_dim
+        want_out = A if head == 0 else 2 * A
+        if net.in_dim != S or net.out_dim != want_out or net.members != 1:
+            raise ValueError(f"evaluate_policy: head {head}: the policy must be a one-member {S} -> {want_out} net, got {net.in_dim} -> "
+                             f"{net.out_dim} x {net.members}")
+        obs = torch.as_tensor(init_obs, dtype=torch.float32).to(m.device).reshape(-1, S)
+        G = len(m.elites_host()) if members else 1
+        if members:
+            obs = obs.repeat_interleave(G, 0)
+        obs = obs.contiguous()
+        B, H, chunk = obs.shape[0], int(horizon), int(chunk)
+        if H < 0 or chunk < 0:
+            raise ValueError(f"evaluate_policy: horizon {H} / chunk {chunk} must be >= 0")
+        if self._evalp is None or self._evalp[0] != (B, G):
+            self._evalp = ((B, G), ops.eval_policy_state(B, S, m.device), None, torch.zeros(1, dtype=torch.int64, device=m.device),
+                           torch.zeros(4 * (G + 1) + 1, dtype=torch.float32, device=m.device))
+            self._evalp_graph = None
+        sig, st, ws, ctr, words = self._evalp
+        kw = self._model_kw(seed_offset)
+        mopo, planes, seed = kw["mopo"], kw["dyn_planes"], kw["seed"]
+        policy_T = self._policy_planes(net)
+        call0 = self._eval_calls + 1
+        self._eval_calls += H
+
+        def run(h, call, resume, call_dev=None):
+            return ops.ens_evaluate_policy(policy_blob=net.blob, max_action=net.max_action, init_obs=None if resume else obs, H=h,
+                                           call0=call & 0xFFFFFFFF, state=st, head=head, members=members, use_trg=use_trg,
+                                           discount=discount, resume=resume, ws=ws, policy_blob_T=policy_T, call_dev=call_dev, **kw)
+
+        if chunk == 0 or H <= chunk:
+            ws = run(H, call0, False)
+        else:
+            ws = run(0, call0, False)                         # initialise the row state (sizes the workspace)
+            n_full = H // chunk
+            ctr.fill_(call0)
+            held = [t for t in (ws, m.packed(), net.blob, policy_T, planes) + (mopo or ()) if t is not None]
+            key = (chunk, bool(use_trg), float(discount), seed, self.precision, self._unc_id, float(net.max_action),
+                   tuple(m.elites_host()), mopo is not None, head, members) + tuple(t.data_ptr() for t in held)
+
+            def body():
+                run(chunk, 0, True, call_dev=ctr)
+                ops.counter_add(ctr, chunk)
+
+            first = 0
+            if self._evalp_graph is None or self._evalp_graph[0] != key:
+                self._evalp_graph = None
+                body()                                        # the first chunk runs eagerly (capturing executes nothing)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    body()
+                self._evalp_graph = (key, g, held)
+                self.eval_captures += 1
+                first = 1
+            for _ in range(n_full - first):
+                self._evalp_graph[1].replay()
+            if H > n_full * chunk:
+                run(H - n_full * chunk, call0 + n_full * chunk, True)
+        self._evalp = (sig, st, ws, ctr, words)
+        out = dict(returns=st["ret"].clone(), lengths=st["length"].clone(), penalty_sums=st["pen_sum"].clone(), alive=st["alive"].clone())
+        if B > 0:
+            host = ops.eval_summary(st, G, out=words).cpu()   # the one host read
+            w, flag = host[:4 * (G + 1)].tolist(), int(host[4 * (G + 1):].view(torch.int32)[0])     # the flag is an int32 word
+        else:
+            w, flag = [float("nan")] * (4 * (G + 1)), 0
+        means = [w[4 * g] for g in range(G)]
+        out.update(return_mean=w[4 * G], length_mean=w[4 * G + 1], penalty_mean=w[4 * G + 2], alive_frac=w[4 * G + 3],
+                   return_member_means=means, return_member_spread=max(means) - min(means), nan=flag != 0)
         return out
 
     @torch.no_grad()

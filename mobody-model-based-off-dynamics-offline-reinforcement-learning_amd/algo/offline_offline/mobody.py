@@ -235,6 +235,18 @@ class _Classifier(object):
         return self.sa_classifier.parameters() + self.sas_classifier.parameters()
 
 
+def evaluate_in_model(self, init_obs, horizon, **kw):
+    """Return of the current policy in the learned model (MOBODYEnsembleDynamics.evaluate_policy: the stand-in for
+    eval_policy_batch, train_mobody.py:60-98).  The one method of all six algorithm classes: it reads `self.eval_policy()` --
+    (net, head), the deterministic actor or the Gaussian policy's tanh(mu) -- and `self.dynamics`, the model the driver hands
+    every policy.  members=True: one return per elite member and their spread.  Reads the policy and the model only: no
+    training state moves."""
+    if self.dynamics is None:
+        raise RuntimeError(f"{type(self).__name__}.evaluate_in_model: no model to evaluate in (self.dynamics is None)")
+    net, head = self.eval_policy()
+    return self.dynamics.evaluate_policy(net, init_obs, horizon, head=head, **kw)
+
+
 class MOBODY(object):
     def __init__(self, config, device, target_entropy=None):
         self.config = config
@@ -440,10 +452,7 @@ class MOBODY(object):
             res = {k: v[keep] for k, v in res.items()}
         return res, {"num_transitions": n_tr, "reward_mean": rew_mean}
 
-    def evaluate_in_model(self, init_obs, horizon, **kw):
-        """Return of the current policy in the learned model (MOBODYEnsembleDynamics.evaluate_policy: the stand-in for
-        eval_policy_batch, train_mobody.py:60-98).  Reads the policy and the model only: no training state moves."""
-        return self.dynamics.evaluate_policy(self.policy, init_obs, horizon, **kw)
+    evaluate_in_model = evaluate_in_model
 
     def open_loop_error(self, buffer, row0, horizon, **kw):
         """Open-loop error of the learned model over recorded windows of `buffer` (MOBODYEnsembleDynamics.open_loop_error).

@@ -101,6 +101,12 @@ int launch_eval_account(const float* r_mu, const float* penalty, const float* ne
                         const DynEvalHook& h, long long B, int S, hipStream_t st);
 int launch_eval_init(const float* init_obs, const DynEvalHook& h, long long B, int S, hipStream_t st);
 
+// what mobody_ens_evaluate_policy adds to those launches: member[b] = elites[b % n_elites] (k_eval_members,
+// trajectory_summary.hip; `elites` is the host array) and the Gaussian head's compaction dst [n][A] = columns [0, A) of
+// src [n][pitch] (k_fqe_action, fqe.hip: the one copy of that kernel)
+int launch_eval_members(const int32_t* elites, int n_elites, long long B, int32_t* member, hipStream_t st);
+int launch_fqe_action(const float* src, int pitch, long long n, int A, float* dst, hipStream_t st);
+
 // open-loop error accounting of mobody_ens_replay (trajectory_truth.hip): the caller's row state and the tables' rows of
 // window step t, which the step's tail launch fills in k_dyn_finalize's place (the step's obs / act ARE obs_state /
 // act_state), and the two launches

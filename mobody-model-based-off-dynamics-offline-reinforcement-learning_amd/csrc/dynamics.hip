@@ -531,11 +531,13 @@ struct Policy {
   const float *blob, *blob_T;
   float max_action;
   MobodyMlpLayout La;
+  int head = 0;                       // 0: the actor (S, A, 1); 1: the Gaussian policy (S, 2 A, 1), `act` of launch() is [B][2 A]
+  const char* name = "actor";         // the block's field names in the refusals: <name>_blob, <name>_blob_T
 
   int check(const char* who, const EnsModel& m) {
-    MB_REQUIRE(blob, "%s: null pointer actor_blob", who);
-    MB_REQUIRE(m.precision == PREC_F32 || blob_T, "%s: the split-precision modes need the actor's T blob (actor_blob_T)", who);
-    return mobody_mlp_layout(m.S, m.A, 1, &La);
+    MB_REQUIRE(blob, "%s: null pointer %s_blob", who, name);
+    MB_REQUIRE(m.precision == PREC_F32 || blob_T, "%s: the split-precision modes need the %s's T blob (%s_blob_T)", who, name, name);
+    return mobody_mlp_layout(m.S, head == 1 ? 2 * m.A : m.A, 1, &La);
   }
   int launch(const float* obs, float* act, int64_t B, int precision, hipStream_t st) const {
     Mlp3FwdArgs p = fwd_net(blob, La, B);
@@ -672,15 +674,17 @@ extern "C" int mobody_ens_rollout(const MobodyEnsRollout* a, void* stream) {
 // ---- the policy's return in the model (eval_policy_batch's accounting, train_mobody.py:60-98, over the learned step) ----
 namespace mobody {
 struct EvalWs {
-  float *act, *next_obs, *penalty, *dyn;
+  float *act, *next_obs, *penalty, *dyn, *act2;
   uint8_t *terminal, *alive_next;
   long long total;
 };
-static void eval_carve(int S, int A, long long B, float* base, EvalWs& w) {
+// head 1 appends the Gaussian policy's [B][2 A] output: the pieces of head 0 keep their places
+static void eval_carve(int S, int A, long long B, int head, float* base, EvalWs& w) {
   Carver take{base};
   w.act = take(B * A); w.next_obs = take(B * S); w.penalty = take(B);
   w.dyn = take(dyn_step_floats(S, B));
   w.terminal = (uint8_t*)take((B + 3) / 4); w.alive_next = (uint8_t*)take((B + 3) / 4);
+  w.act2 = head == 1 ? take(B * 2 * A) : nullptr;
   w.total = take.off;
 }
 }  // namespace mobody
@@ -689,16 +693,28 @@ extern "C" int64_t mobody_ens_evaluate_workspace(const MobodyEnsEval* a) {
   if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyEnsEval) || a->B < 0 || a->S < 1 || a->A < 1)
     return fail(MOBODY_E_ARG, "mobody_ens_evaluate_workspace: null struct, wrong struct_bytes, B < 0 or S, A < 1");
   EvalWs w;
-  eval_carve(a->S, a->A, a->B, nullptr, w);
+  eval_carve(a->S, a->A, a->B, 0, nullptr, w);
   return w.total;
 }
 
+// the two evaluation blocks differ in the policy's field names and in what MobodyEnsEvalPolicy adds
+static MobodyEnsEvalPolicy eval_block_of(const MobodyEnsEval& a) {
+  MobodyEnsEvalPolicy p{};
+  p.struct_bytes = (int32_t)sizeof(MobodyEnsEvalPolicy); p.uncertainty_mode = a.uncertainty_mode;
+  p.dyn_blob = a.dyn_blob; p.dyn_planes = a.dyn_planes; p.mopo_blob = a.mopo_blob; p.mopo_blob_T = a.mopo_blob_T;
+  p.policy_blob = a.actor_blob; p.policy_blob_T = a.actor_blob_T;
+  p.precision = a.precision; p.S = a.S; p.A = a.A; p.task = a.task; p.init_obs = a.init_obs; p.B = a.B; p.H = a.H;
+  p.n_elites = a.n_elites; p.elites = a.elites; p.seed = a.seed; p.call0 = a.call0; p.call_dev = a.call_dev;
+  p.max_action = a.max_action; p.discount = a.discount; p.use_trg = a.use_trg; p.resume = a.resume;
+  p.obs_state = a.obs_state; p.alive = a.alive; p.ret = a.ret; p.pen_sum = a.pen_sum; p.disc = a.disc; p.length = a.length;
+  p.workspace = a.workspace;
+  return p;
+}
+
 // H steps of 5 launches: policy forward -> member forward -> sample (alive update into the workspace) -> reward head ->
-// accounting; one launch more when the row state is initialised first
-extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
-  const char* who = "mobody_ens_evaluate";
-  MB_BLOCK(who, ap, MobodyEnsEval);
-  const MobodyEnsEval& a = *ap;
+// accounting; one launch more when the row state is initialised first.  head 1: the compaction [B][2 A] -> [B][A] after the
+// policy forward (6 per step); member_mode 1: k_eval_members with the initialisation, `member` as the sample kernel's elite_idx
+static int eval_impl(const char* who, const MobodyEnsEvalPolicy& a, const char* policy_name, void* stream) {
   const int S = a.S;
   const int64_t B = a.B;
   EnsModel m = EnsModel::of(a, a.call0);
@@ -707,33 +723,63 @@ extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
   MB_REQUIRE(a.H >= 0, "%s: H < 0", who);
   MB_REQUIRE(a.resume == 0 || a.resume == 1, "%s: resume %d is neither 0 nor 1", who, a.resume);
   MB_REQUIRE(a.discount > 0.f && a.discount <= 1.f, "%s: discount %g outside (0, 1]", who, (double)a.discount);   // NaN fails both
+  MB_REQUIRE(a.head == 0 || a.head == 1, "%s: head %d outside {0 (deterministic actor), 1 (Gaussian policy)}", who, a.head);
+  MB_REQUIRE(a.member_mode == 0 || a.member_mode == 1, "%s: member_mode %d outside {0 (an elite per row and step), 1 (one per episode)}",
+             who, a.member_mode);
   if (B == 0) return 0;
+  MB_REQUIRE(a.head == 0 || 2 * a.A <= 128, "%s: A %d: the Gaussian policy's 2 A outputs must fit 128 columns (head 1)", who, a.A);
   rc = m.check(who);
   if (rc) return rc;
-  Policy pi{a.actor_blob, a.actor_blob_T, a.max_action};
+  Policy pi{a.policy_blob, a.policy_blob_T, a.max_action};
+  pi.head = a.head; pi.name = policy_name;
   rc = pi.check(who, m);
   if (rc) return rc;
   MB_REQUIRE(a.resume == 1 || a.init_obs, "%s: null pointer init_obs (resume == 0)", who);
   MB_NONNULL(who, a, obs_state); MB_NONNULL(who, a, alive); MB_NONNULL(who, a, ret); MB_NONNULL(who, a, pen_sum);
-  MB_NONNULL(who, a, disc); MB_NONNULL(who, a, length); MB_NONNULL(who, a, workspace);
+  MB_NONNULL(who, a, disc); MB_NONNULL(who, a, length);
+  MB_REQUIRE(a.member_mode == 0 || a.member, "%s: null pointer member (member_mode == 1)", who);
+  MB_NONNULL(who, a, workspace);
   EvalWs w;
-  eval_carve(S, a.A, B, a.workspace, w);
+  eval_carve(S, a.A, B, a.head, a.workspace, w);
   hipStream_t st = as_stream(stream);
   const DynEvalHook hook{a.obs_state, a.alive, a.ret, a.pen_sum, a.disc, a.length, a.discount};
   if (a.resume == 0) {
     rc = launch_eval_init(a.init_obs, hook, B, S, st);
     if (rc) return rc;
+    if (a.member_mode == 1 && (rc = launch_eval_members(a.elites, a.n_elites, B, a.member, st))) return rc;
   }
   SampleBook bk{}; bk.alive_out = w.alive_next;
   for (int t = 0; t < a.H; ++t) {
-    rc = pi.launch(a.obs_state, w.act, B, m.precision, st);          // a = pi(s)  (eval_policy_batch, train_mobody.py:76)
+    rc = pi.launch(a.obs_state, a.head == 1 ? w.act2 : w.act, B, m.precision, st);   // a = pi(s)  (eval_policy_batch, train_mobody.py:76)
     if (rc) return rc;
+    if (a.head == 1 && (rc = launch_fqe_action(w.act2, 2 * a.A, B, a.A, w.act, st))) return rc;   // tanh(mu): columns [0, A)
     MobodyEnsStep s = m.step(t, a.obs_state, w.act, B, a.alive);
     s.next_obs = w.next_obs; s.terminal = w.terminal; s.penalty = w.penalty; s.workspace = w.dyn;
+    if (a.member_mode == 1) s.elite_idx = a.member;
     rc = m.launch(s, bk, st, [&](const float* r_mu) { return launch_eval_account(r_mu, w.penalty, w.next_obs, w.alive_next, hook, B, S, st); });
     if (rc) return rc;
   }
   return 0;
+}
+
+extern "C" int mobody_ens_evaluate(const MobodyEnsEval* ap, void* stream) {
+  const char* who = "mobody_ens_evaluate";
+  MB_BLOCK(who, ap, MobodyEnsEval);
+  return eval_impl(who, eval_block_of(*ap), "actor", stream);
+}
+
+extern "C" int64_t mobody_ens_evaluate_policy_workspace(const MobodyEnsEvalPolicy* a) {
+  if (a == nullptr || a->struct_bytes != (int32_t)sizeof(MobodyEnsEvalPolicy) || a->B < 0 || a->S < 1 || a->A < 1 || a->head < 0 || a->head > 1)
+    return fail(MOBODY_E_ARG, "mobody_ens_evaluate_policy_workspace: null struct, wrong struct_bytes, B < 0, S, A < 1 or head outside {0, 1}");
+  EvalWs w;
+  eval_carve(a->S, a->A, a->B, a->head, nullptr, w);
+  return w.total;
+}
+
+extern "C" int mobody_ens_evaluate_policy(const MobodyEnsEvalPolicy* ap, void* stream) {
+  const char* who = "mobody_ens_evaluate_policy";
+  MB_BLOCK(who, ap, MobodyEnsEvalPolicy);
+  return eval_impl(who, *ap, "policy", stream);
 }
 
 // ---- open-loop error over recorded trajectories (the model fed the data's actions, compared with the data's outcomes) ----

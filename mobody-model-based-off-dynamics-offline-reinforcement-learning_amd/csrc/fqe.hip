@@ -97,6 +97,14 @@ static int fqe_dims(const char* who, int head, int S, int A, long long rows, con
   return 0;
 }
 
+// the launch of k_fqe_action (declared in common.h: mobody_ens_evaluate_policy's head 1 takes the same copy)
+int launch_fqe_action(const float* src, int pitch, long long n, int A, float* dst, hipStream_t st) {
+  ProfScope scope(PROF_ROWWISE, st);
+  hipLaunchKernelGGL(k_fqe_action, dim3(fqe_grid(n * A)), dim3(256), 0, st, src, pitch, n, A, dst);
+  MB_LAUNCH_OK("k_fqe_action");
+  return 0;
+}
+
 struct FqeWs {
   float *pi2, *pi, *q;
   long long floats;
@@ -118,11 +126,7 @@ static int fqe_forwards(int prec, int head, int S, int A, long long rows, const 
   if ((rc = mobody_mlp3_forward(policy_blob, pT, prec, S, head == 1 ? 2 * A : A, 1, state, S, nullptr, 0, rows, 1, max_action,
                                 head == 1 ? w.pi2 : w.pi, nullptr, nullptr, nullptr, stream)))
     return rc;
-  if (head == 1) {
-    ProfScope scope(PROF_ROWWISE, st);
-    hipLaunchKernelGGL(k_fqe_action, dim3(fqe_grid(rows * A)), dim3(256), 0, st, (const float*)w.pi2, 2 * A, rows, A, w.pi);
-    MB_LAUNCH_OK("k_fqe_action");
-  }
+  if (head == 1 && (rc = launch_fqe_action(w.pi2, 2 * A, rows, A, w.pi, st))) return rc;
   return mobody_mlp3_forward(q_blob, qT, prec, S + A, 1, 2, state, S, w.pi, A, rows, 0, 1.f, w.q, nullptr, nullptr, nullptr, stream);
 }
 

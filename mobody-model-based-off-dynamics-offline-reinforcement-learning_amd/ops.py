@@ -932,6 +932,49 @@ def ens_evaluate(dyn_blob, actor_blob, S, A, task_id, max_action, init_obs, H, e
     return _run_with_workspace("mobody_ens_evaluate", a, ws, state["obs_state"].device)
 
 
+def eval_policy_state(B, S, device):
+    """The caller-owned row state of mobody_ens_evaluate_policy: eval_state plus member int32[B] (read and written in member
+    mode only).  Uninitialised: the first call (resume=False) sets it."""
+    st = eval_state(B, S, device)
+    st["member"] = torch.empty(B, dtype=torch.int32, device=device)
+    return st
+
+
+def ens_evaluate_policy(dyn_blob, policy_blob, S, A, task_id, max_action, init_obs, H, elites, seed, call0, state, head=0,
+                        members=False, use_trg=True, discount=1.0, resume=False, ws=None, dyn_planes=None, policy_blob_T=None,
+                        precision=0, mopo=None, uncertainty_mode=0, call_dev=None):
+    """ens_evaluate for both policy head forms (mobody_ens_evaluate_policy).  head 0: `policy_blob` is the deterministic actor
+    (S, A, 1); head 1: the Gaussian policy (S, 2A, 1), the action is max_action * tanh(mu).  members: every row keeps the elite
+    state["member"][b] = elites[b % len(elites)] for its whole episode (state from eval_policy_state).  Returns the workspace."""
+    B = state["obs_state"].shape[0]
+    if init_obs is not None:
+        init_obs = _f32(init_obs)
+        assert init_obs.shape == (B, S)
+    model = _model_fields(dyn_blob, dyn_planes, mopo, precision, S, A, task_id, elites, seed, uncertainty_mode, call_dev, use_trg)
+    a = _lib.MobodyEnsEvalPolicy(struct_bytes=_BYTES[_lib.MobodyEnsEvalPolicy], policy_blob=ptr(policy_blob),
+                                 policy_blob_T=ptr(policy_blob_T), init_obs=ptr(init_obs), B=B, H=int(H), call0=call0,
+                                 max_action=float(max_action), discount=float(discount), resume=int(bool(resume)),
+                                 obs_state=ptr(state["obs_state"]), alive=ptr(state["alive"]), ret=ptr(state["ret"]),
+                                 pen_sum=ptr(state["pen_sum"]), disc=ptr(state["disc"]), length=ptr(state["length"]),
+                                 head=int(head), member_mode=int(bool(members)), member=ptr(state["member"]) if members else None,
+                                 **model)
+    return _run_with_workspace("mobody_ens_evaluate_policy", a, ws, state["obs_state"].device)
+
+
+def eval_summary(state, G=1, out=None):
+    """The figures of a finished row state by member group b % G (mobody_eval_summary).  Returns `out`, float32 [4 (G + 1) + 1] on
+    the device: (mean return, mean length, mean penalty sum, alive share) per group, the same four over all rows, and the NaN
+    flag (int32 bits in the last word).  No synchronisation: the caller reads `out` once."""
+    dev = state["ret"].device
+    if out is None:
+        out = torch.empty(4 * (int(G) + 1) + 1, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 4 * (int(G) + 1) + 1
+    flag = out[4 * (int(G) + 1):4 * (int(G) + 1) + 1]
+    check(load().mobody_eval_summary(ptr(state["ret"]), ptr(state["pen_sum"]), ptr(state["length"]), ptr(state["alive"]),
+                                     state["ret"].shape[0], int(G), ptr(out), ptr(flag), cur_stream()), "mobody_eval_summary")
+    return out
+
+
 def replay_state(B, H, S, A, device):
     """The caller-owned row state and tables of mobody_ens_replay: obs_state[B,S], act_state[B,A], obs_err / rew_err /
     penalty float[H,B], term_model uint8[H,B].  Uninitialised: the call sets every word."""

@@ -470,12 +470,38 @@ def _run(args, rank, world, device):
                        rank=rank, world=world)
         config.update({"dynamics": dynamics})
         policy.dynamics = dynamics
+        if int(config.get("model_eval_dynamics", 0)):
+            say(f"model_eval_dynamics ignored: {args.policy} builds its own model")
+    elif int(config.get("model_eval_dynamics", 0)) and world > 1:
+        # data-parallel baselines are not built: every rank would build and pre-train a model only rank 0 evaluates in
+        raise SystemExit("model_eval_dynamics: not supported under a process group (run the baseline on one GPU)")
+    elif int(config.get("model_eval_dynamics", 0)):
+        # A baseline judged in the learned target model (optional key of the merged config, off by default): the same ensemble,
+        # the same load-or-train branches and flags as above, handed to the policy as the reference's driver hands it to every
+        # policy -- but an EVALUATOR only.  `dynamics` stays None here, so nothing below that samples a buffer for the model
+        # runs; torch's generators and the buffers' draw counts are put back after the model is built and pre-trained, so the
+        # trained policy and every non-`test/model` scalar row are bit for bit what they are without the key.
+        rng_state = (torch.get_rng_state(), torch.cuda.get_rng_state_all(), np.random.get_state(), random.getstate())
+        draws = (src_rb._draws, tar_rb._draws)
+        model = MOBODYModule(obs_dim=state_dim, action_dim=action_dim, hidden_dims=256, num_ensemble=7, num_elites=5,
+                             weight_decays=[2.5e-5, 5e-5, 7.5e-5, 7.5e-5, 1e-4], device=device,
+                             reward_relu=args.relu_reward, config=config)
+        eval_dynamics = MOBODYEnsembleDynamics(config, model, None, None, terminal_fn, penalty_coef=env_penalty_coef,
+                                               uncertainty_mode=config.get("uncertainty_mode", "pairwise-diff"),
+                                               rng=args.rng, seed=args.seed + 3)
+        build_dynamics(args, eval_dynamics, model, src_rb, tar_rb, NullLog(), task, explicit_synthetic=args.synthetic == 1,
+                       rank=rank, world=world)
+        policy.dynamics = eval_dynamics
+        torch.set_rng_state(rng_state[0]); torch.cuda.set_rng_state_all(rng_state[1])
+        np.random.set_state(rng_state[2]); random.setstate(rng_state[3])
+        src_rb._draws, tar_rb._draws = draws
 
     # Evaluation of the policy in the learned target model (no simulators in this build): two optional keys of the merged
     # config, off by default.  Rank 0 evaluates; start states are episode starts of the target data.
     eval_obs, ref_env_name = None, f"{args.env}-{args.shift_level}"               # train_mobody.py:331
+    eval_members = False
     if int(config.get("model_eval_episodes", 0)) > 0:
-        if dynamics is None:
+        if policy.dynamics is None:
             say(f"model_eval_episodes / model_eval_horizon ignored: {args.policy} has no model to evaluate in")
         elif rank == 0:
             from mobody_amd.envs.infos import get_normalized_score
@@ -485,6 +511,8 @@ def _run(args, rank, world, device):
             rows = model_eval_rows(episode_starts(tar_rb.state[:n].cpu().numpy(), tar_rb.next_state[:n].cpu().numpy(), term),
                                    int(config["model_eval_episodes"]), args.seed)
             eval_obs = tar_rb.state[torch.as_tensor(rows, device=tar_rb.state.device)].contiguous()
+            # one return per elite member and their spread next to the five tags (optional key, read only here)
+            eval_members = bool(int(config.get("model_eval_members", 0)))
 
     # Fitted Q evaluation of the policy on the recorded target transitions (mobody_amd.fqe; every algorithm): optional keys of the
     # merged config, off by default.  Rank 0 evaluates alone; start states are episode starts of the target data, chosen once.
@@ -548,13 +576,20 @@ def _run(args, rank, world, device):
             if writer is not None and eval_obs is not None:
                 # eval_policy_batch's return (:60-98) with the learned target model in the simulator's place: an ESTIMATE
                 # whose error grows with the horizon -- hence tags of its own, never the simulator's 'test/target return'
-                ev = policy.evaluate_in_model(eval_obs, int(config.get("model_eval_horizon", 1000)))
+                ev = policy.evaluate_in_model(eval_obs, int(config.get("model_eval_horizon", 1000)),
+                                              **(dict(members=True) if eval_members else {}))
                 writer.add_scalar("test/model target return", ev["return_mean"], global_step=t + 1)
                 writer.add_scalar("test/model target normalized score", get_normalized_score(ev["return_mean"], ref_env_name),
                                   global_step=t + 1)
                 writer.add_scalar("test/model episode length", ev["length_mean"], global_step=t + 1)
                 writer.add_scalar("test/model penalty", ev["penalty_mean"], global_step=t + 1)
                 writer.add_scalar("test/model alive frac", ev["alive_frac"], global_step=t + 1)
+                if eval_members:
+                    # every start state rolled once per elite, each episode under one member: the members' disagreement is an
+                    # error bar on the estimate above
+                    writer.add_scalar("test/model return member spread", ev["return_member_spread"], global_step=t + 1)
+                    for k, v in enumerate(ev["return_member_means"]):
+                        writer.add_scalar(f"test/model return member e{k}", v, global_step=t + 1)
             if writer is not None and fqe is not None:
                 # the discounted value at config['gamma'] of the policy as it is now, by FQE: an estimate whose bias grows with the
                 # policy's distance from the data; not a return, so no normalized score is derived from it

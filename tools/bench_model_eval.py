@@ -8,6 +8,13 @@
            a carried alive mask with the per-row sums kept in torch ops on the device (no host synchronisation inside the
            loop: the form most favourable to it)
 
+With `--head 0|1` (and `--members`) the eager and graph legs run through `mobody_ens_evaluate_policy` instead
+(MOBODYEnsembleDynamics.evaluate_policy(head=, members=, entry='policy'): `entry='policy'` is what sends `--head 0` without
+`--members`, which evaluate_policy would otherwise run through the old entry, through the NEW one; `--head 1` is a Gaussian
+policy (S, 2A, 1), one launch more per step; `--members` rolls every one of the B start states once per elite, B x 5 rows, each
+episode under one member) and the result is read through `mobody_eval_summary`; the compose leg is left out, and the default
+`--out` becomes profiles/model_eval_policy_run.json.  Without `--head` the tool measures what it always did.
+
 for B in {32, 1024} x H in {100, 1000} x mfma in {f16x2, f32}.  Every timed run ends in a synchronisation (the means are
 read back) and is bracketed by the host clock; after `--warmup` runs of each leg the legs alternate `--repeats` times;
 medians with the min / max spread are reported.  `below_compose`: the leg's median lies below compose's median by more
@@ -15,6 +22,7 @@ than the larger of the two spreads.  Results: one JSON document (`--out`, defaul
 build's source fingerprint; keys already in that file that this tool does not write are kept.
 
   python tools/bench_model_eval.py [--B 32 1024] [--H 100 1000] [--mfma f16x2 f32] [--chunk 50] [--warmup 1] [--repeats 5]
+                                   [--head 0|1 [--members]]
 """
 import argparse
 import json
@@ -30,7 +38,7 @@ if ROOT not in sys.path:
 S, A, TASK = 17, 6, "walker2d-medium-v2"
 
 
-def make_legs(dev, B, H, mfma, chunk):
+def make_legs(dev, B, H, mfma, chunk, head=None, members=False):
     import numpy as np
     import torch
     from mobody_amd import engine, synthetic
@@ -61,6 +69,11 @@ def make_legs(dev, B, H, mfma, chunk):
             obs = r["next_obs"]
         return torch.stack([ret.mean(), length.float().mean(), pen.mean(), alive.float().mean()]).tolist()
 
+    if head is not None:                                   # both legs through mobody_ens_evaluate_policy, whatever the head
+        from mobody_amd.algo.offline_offline.iql import _GaussianPolicy
+        net = pol.policy if head == 0 else _GaussianPolicy(S, A, 1.0, dev, pol.policy.precision)
+        run = lambda c: dyn.evaluate_policy(net, init, H, chunk=c, head=head, members=members, entry="policy")
+        return {"eager": lambda: run(0), "graph": lambda: run(chunk)}, dyn
     legs = {"eager": lambda: pol.evaluate_in_model(init, H, chunk=0), "graph": lambda: pol.evaluate_in_model(init, H, chunk=chunk),
             "compose": compose}
     return legs, dyn
@@ -83,8 +96,14 @@ def main():
     ap.add_argument("--chunk", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "model_eval.json"))
+    ap.add_argument("--head", type=int, choices=[0, 1], default=None, help="run the legs through mobody_ens_evaluate_policy at this head")
+    ap.add_argument("--members", action="store_true", help="with --head: every start state once per elite, one member per episode")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.members and args.head is None:
+        ap.error("--members needs --head")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "model_eval.json" if args.head is None else "model_eval_policy_run.json")
     import torch
     if not torch.cuda.is_available():
         sys.exit("bench_model_eval.py: no GPU (an evaluation time is a GPU measurement; there is no CPU fallback)")
@@ -94,7 +113,7 @@ def main():
     for mfma in args.mfma:
         for B in args.B:
             for H in args.H:
-                legs, dyn = make_legs(dev, B, H, mfma, args.chunk)
+                legs, dyn = make_legs(dev, B, H, mfma, args.chunk, args.head, args.members)
                 for fn in legs.values():
                     for _ in range(args.warmup):
                         fn()
@@ -105,10 +124,12 @@ def main():
                         ms[k].append(timed(fn))
                 assert dyn.eval_captures == (1 if H > args.chunk > 0 else 0), "the chunk graph was captured again"
                 rec = dict(B=B, H=H, mfma=mfma, chunk=args.chunk)
+                if args.head is not None:
+                    rec.update(head=args.head, members=args.members, rows=B * (len(dyn.model.elites_host()) if args.members else 1))
                 for k, v in ms.items():
                     rec[k] = dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), spread_ms=max(v) - min(v), runs_ms=v,
                                   us_per_step=statistics.median(v) * 1e3 / H)
-                for k in ("eager", "graph"):
+                for k in ("eager", "graph") if "compose" in rec else ():
                     gap = rec["compose"]["median_ms"] - rec[k]["median_ms"]
                     rec[k]["below_compose"] = gap > max(rec[k]["spread_ms"], rec["compose"]["spread_ms"])
                     rec[k]["compose_over_this"] = rec["compose"]["median_ms"] / rec[k]["median_ms"]
@@ -116,9 +137,10 @@ def main():
                 print(json.dumps({k: (v if not isinstance(v, dict) else {a: (round(b, 4) if isinstance(b, float) else b)
                                                                          for a, b in v.items() if a != "runs_ms"})
                                   for k, v in rec.items()}), flush=True)
-    doc = dict(what="ms per evaluation of B episodes x H steps in the learned model, walker2d shapes S=17 A=6: one eager "
-                    "mobody_ens_evaluate call | chunk-graph replay | Python composition of policy forward + dynamics.step_device; "
-                    "host clock around runs that end in a synchronisation, medians over alternating repeats",
+    what = ("one eager mobody_ens_evaluate call | chunk-graph replay | Python composition of policy forward + dynamics.step_device"
+            if args.head is None else "one eager mobody_ens_evaluate_policy call | chunk-graph replay, read through mobody_eval_summary")
+    doc = dict(what="ms per evaluation of B episodes x H steps in the learned model, walker2d shapes S=17 A=6: " + what +
+                    "; host clock around runs that end in a synchronisation, medians over alternating repeats",
                src_fingerprint=bench.src_fingerprint(), device=torch.cuda.get_device_name(0), warmup=args.warmup,
                repeats=args.repeats, runs=runs)
     if os.path.exists(args.out):
