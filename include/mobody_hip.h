@@ -106,6 +106,7 @@ typedef struct MobodyMlpLayout {
 
 const char* mobody_last_error(void);
 int mobody_abi_version(void);
+/* S in [2, 127], A in [1, 64] and 2S + A <= 256 (the reward head's input is one 256-wide tile: S = 127 only with A <= 2). */
 int mobody_dyn_layout(int S, int A, MobodyDynLayout* out);
 int mobody_mlp_layout(int in_dim, int out_dim, int members, MobodyMlpLayout* out);
 

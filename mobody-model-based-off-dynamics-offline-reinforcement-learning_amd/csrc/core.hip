@@ -121,8 +121,10 @@ extern "C" int mobody_abi_version(void) { return MOBODY_ABI_VERSION; }
 // latent heads :217-225,258-271; reward mean :295-302); transition3 is padded to 16 columns.
 extern "C" int mobody_dyn_layout(int S, int A, MobodyDynLayout* out) {
   MB_REQUIRE(out != nullptr, "mobody_dyn_layout: out is null");
-  MB_REQUIRE(S >= 2 && S <= 240 && A >= 1 && A <= 64, "mobody_dyn_layout: unsupported S=%d A=%d (S in [2,240], A in [1,64])", S, A);
-  MB_REQUIRE(round_up(2 * S + A, 8) <= 256, "mobody_dyn_layout: reward-head input 2S+A=%d exceeds 256", 2 * S + A);
+  // 2S + A <= 256 (the reward head's input, one 256-wide K tile) is the bound on S that holds: S <= 127 at A = 2, 1
+  MB_REQUIRE(S >= 2 && S <= 127 && A >= 1 && A <= 64,
+             "mobody_dyn_layout: unsupported S=%d A=%d (S in [2,127], A in [1,64], 2S+A <= 256)", S, A);
+  MB_REQUIRE(2 * S + A <= 256, "mobody_dyn_layout: unsupported S=%d A=%d: reward-head input 2S+A=%d exceeds 256", S, A, 2 * S + A);
   memset(out, 0, sizeof(*out));
   out->S = S; out->A = A; out->E = NENS;
   struct D { int id, in, out, Kp, Np; };

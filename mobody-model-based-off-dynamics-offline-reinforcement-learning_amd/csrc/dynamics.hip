@@ -485,7 +485,7 @@ struct EnsModel {
     sa.n_elites = n_elites; sa.seed = seed; sa.call = a.call; sa.call_dev = (const long long*)call_dev; sa.B = B; sa.S = S; sa.task = task;
     sa.next_obs = a.next_obs; sa.penalty = a.penalty; sa.terminal = a.terminal;
     sa.keep = bk.keep; sa.alive_out = bk.alive_out; sa.env_filter = bk.env_filter; sa.use_filter = bk.use_filter;
-    const int rpb = 256 / S < 64 ? 256 / S : 64;         // whole rows per workgroup (S <= 256 is checked by the layout)
+    const int rpb = 256 / S < 64 ? 256 / S : 64;         // whole rows per workgroup (the layout's 2S + A <= 256 holds S <= 127)
     const dim3 grid((unsigned)cdiv(B, rpb));
     if (uncertainty_mode == MOBODY_UNC_ALEATORIC) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ALEATORIC>, grid, dim3(256), 0, st, sa, rpb);
     else if (uncertainty_mode == MOBODY_UNC_ENS_STD) hipLaunchKernelGGL(k_dyn_sample<MOBODY_UNC_ENS_STD>, grid, dim3(256), 0, st, sa, rpb);

@@ -642,7 +642,8 @@ using namespace mobody;
 
 extern "C" int mobody_pretrain_layout(int S, int A, MobodyPretrainLayout* out) {
   MB_REQUIRE(out != nullptr, "mobody_pretrain_layout: out is null");
-  MB_REQUIRE(S >= 2 && S <= 128 && A >= 1 && A <= 64, "mobody_pretrain_layout: unsupported S=%d A=%d (S in [2,128], A in [1,64])", S, A);
+  MB_REQUIRE(S >= 2 && S <= 127 && A >= 1 && A <= 64 && 2 * S + A <= 256,
+             "mobody_pretrain_layout: unsupported S=%d A=%d (S in [2,127], A in [1,64], 2S+A <= 256)", S, A);
   memset(out, 0, sizeof(*out));
   out->S = S; out->A = A; out->za_in = LATENT + A;
   int rc = mobody_mlp_layout(S, 2 * LATENT, NENS, &out->enc);                       // zs1-3: S -> 256 -> 256 -> 32 (mu | logvar)
@@ -1117,7 +1118,8 @@ static int mopo_carve(const MobodyPretrainMopoLayout& L, long long b, float* bas
 
 extern "C" int mobody_pretrain_mopo_layout(int S, int A, MobodyPretrainMopoLayout* out) {
   MB_REQUIRE(out != nullptr, "mobody_pretrain_mopo_layout: out is null");
-  MB_REQUIRE(S >= 2 && S <= 128 && A >= 1 && A <= 64, "mobody_pretrain_mopo_layout: unsupported S=%d A=%d (S in [2,128], A in [1,64])", S, A);
+  MB_REQUIRE(S >= 2 && S <= 127 && A >= 1 && A <= 64 && 2 * S + A <= 256,
+             "mobody_pretrain_mopo_layout: unsupported S=%d A=%d (S in [2,127], A in [1,64], 2S+A <= 256)", S, A);
   memset(out, 0, sizeof(*out));
   out->S = S; out->A = A;
   int rc = mobody_mlp_layout(S + A, S, NENS, &out->dyn);                            // za_src1-3: S+A -> 256 -> 256 -> S

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from dyn_shapes import SHAPES as DYN_SHAPE_EDGES      # the (S, A) edges of the layout, each with the edge it stands for
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -39,7 +41,7 @@ def test_struct_sizes_match_header(lib):
     assert C.sizeof(_lib.MobodyHyper) == 8 * 4
 
 
-@pytest.mark.parametrize("S,A", [(17, 6), (111, 8), (45, 24), (11, 3)])
+@pytest.mark.parametrize("S,A", [(17, 6), (111, 8), (45, 24), (11, 3)] + DYN_SHAPE_EDGES)
 def test_dyn_layout(lib, S, A):
     from mobody_amd import _lib
     L = _lib.dyn_layout(S, A)
@@ -71,6 +73,14 @@ def test_argument_validation_reports_errors(lib):
     assert lib.mobody_dyn_layout(1000, 6, C.byref(L)) == -1
     assert b"unsupported" in lib.mobody_last_error()
     assert lib.mobody_dyn_layout(120, 40, C.byref(L)) == -1      # 2S+A > 256
+    # the bound on S that holds is 2S + A <= 256: S <= 127, and 127 only with A <= 2; the message says so
+    for S, A in ((1, 1), (127, 3), (128, 1), (17, 65), (17, 0)):
+        assert lib.mobody_dyn_layout(S, A, C.byref(L)) == -1, (S, A)
+        msg = lib.mobody_last_error().decode()
+        assert msg.startswith("mobody_dyn_layout: unsupported S=%d A=%d" % (S, A)) and "256" in msg, msg
+    assert "[2,127]" in msg and "240" not in msg
+    for S, A in ((127, 2), (96, 64)):
+        assert lib.mobody_dyn_layout(S, A, C.byref(L)) == 0 and (L.S, L.A, L.layer[10].Kp) == (S, A, 256)
     M = _lib.MobodyMlpLayout()
     assert lib.mobody_mlp_layout(300, 1, 1, C.byref(M)) == -1
     d = _lib.MobodyTrainDims(17, 6, 0, 0, 0, 0)
