@@ -1328,6 +1328,112 @@ int mobody_ens_evaluate_policy(const MobodyEnsEvalPolicy* a, void* stream);
 int mobody_eval_summary(const float* ret, const float* pen_sum, const int32_t* length, const uint8_t* alive, int64_t B, int G,
                         float* out, int32_t* nan_flag, void* stream);
 
+/* ---- The analytic off-dynamics control task, stepped on the device (mobody_amd/task.py holds the specification) ------
+ * A ground truth for the evaluators: a small analytic control task with the observation / action shapes and the termination
+ * predicates of the environments above, in a source and a shifted target variant.  MobodyTaskParams is the task a call runs (the
+ * three entries share it).  With z = s - mu, u_j = gain[j] * clamp(a_j / max_action, -1, 1), v = z[S-1], d_i = sum_j bmat[i][j] u_j
+ * (j ascending):
+ *   i not in {0, 1, S-1}:  z'_i     = z_i + dt (-f z_i + g d_i + c sin(z_{i-1}))
+ *   forward speed:         z'_{S-1} = v   + dt (-f v + g fwd),  fwd = mean(u_1..u_{A-1}), or u_0 when A == 1
+ *   angle:                 z'_1     = z_1 + dt (lam grav z_1 + g u_0 - k v)
+ *   height:                z'_0     = z_0 + dt (-f z_0 - h grav z_1^2)
+ *   noise:                 z'_i    += sigma * n_i; n = noise[b][i], or (noise == NULL) element b S + i of the unit-normal stream
+ *                          (seed, MOBODY_TASK_STREAM_NOISE, call + call_dev[0]), what mobody_rng_normal writes there; sigma == 0: none
+ *   next = z' + mu;  reward = z'_{S-1} + alive_bonus - ctrl_cost * mean_j(u_j^2);  terminal = the predicate `task` on next
+ * All of it fp32, every product and sum rounded on its own (no contraction), the sums in ascending j: two calls give the same bits.
+ * mu [S], gain [A] and bmat [S][A] are DEVICE tables the host forms once (no device cos).  S in [3, 256], A in [1, 64]. */
+enum { MOBODY_TASK_STREAM_NOISE = 4,   /* process noise [B][S] */
+       MOBODY_TASK_STREAM_ACTION = 5,  /* the built-in controllers' action noise [B][A] */
+       MOBODY_TASK_STREAM_START = 6 }; /* start states: element b S + i at call id e = the episode's index in its lane */
+enum { MOBODY_TASK_CTRL_RANDOM = 0,    /* a_j uniform in [-1, 1): 2 u - 1 of word (b A + j) & 3 of the stream's counter (b A + j) >> 2 */
+       MOBODY_TASK_CTRL_FEEDBACK = 1 };/* a_0 = -6 z_1 + 0.15 v, every other a_j = push; + eps_a * unit normal; clipped to [-1, 1] */
+struct MobodyTaskParams {
+  int32_t S, A, task, reserved;            /* task: MOBODY_TERM_*; reserved 0 */
+  const float *mu, *gain, *bmat;           /* device [S], [A], [S][A] */
+  float f, grav, dt, g, c, lam, k, h, sigma, alive_bonus, ctrl_cost, max_action;
+};
+typedef struct MobodyTaskParams MobodyTaskParams;
+
+/* mobody_task_step: one launch, k_task_step, over B rows.  k_dyn_sample's geometry: a workgroup owns 256 / S whole rows staged in
+ * LDS, one thread per (row, dim) element; one thread per row then forms the reward and the predicate.  No flags, tickets or
+ * atomics.  alive (nullable, uint8 [B]): a dead row is computed like any other and its terminal is written 0.  obs / next_obs may
+ * be the same array.  MOBODY_E_ARG before the first runtime call, the field named: struct_bytes, S, A, task (pen needs S > 26),
+ * max_action <= 0, B < 0, any null pointer among mu, gain, bmat, obs, act, next_obs, reward, terminal.  B == 0 returns 0. */
+struct MobodyTaskStep {
+  int32_t struct_bytes, reserved;
+  MobodyTaskParams p;
+  const float *obs, *act;           /* [B][S], [B][A] */
+  int64_t B;
+  const float* noise;               /* [B][S], or NULL: the device generator */
+  const uint8_t* alive;             /* [B], nullable */
+  uint32_t seed, call;
+  const int64_t* call_dev;          /* nullable device word added to `call` */
+  float *next_obs, *reward;         /* [B][S], [B] */
+  uint8_t* terminal;                /* [B] */
+};
+typedef struct MobodyTaskStep MobodyTaskStep;
+int mobody_task_step(const MobodyTaskStep* a, void* stream);
+
+/* mobody_task_evaluate: the TRUE return of a policy in the task, with the row-state contract of mobody_ens_evaluate_policy (resume,
+ * obs_state, alive, ret, disc, length, discount, call0, call_dev, H); pen_sum is initialised to zero and never written again, so
+ * mobody_eval_summary serves the row state unchanged.  head 0 / 1: the two policy forms of mobody_ens_evaluate_policy; head 2: the
+ * built-in controller (ctrl, ctrl_push, ctrl_eps; no policy blob is read).  Per step: the policy forward (heads 0, 1); k_fqe_action
+ * (head 1); k_task_advance, which forms the head-2 action, advances the task with the device generator at call id call0 + t +
+ * call_dev[0] and does k_eval_account's accounting on the row state (ret = fma(disc, reward, ret), length, disc, alive &= !terminal,
+ * obs_state = next) -- 2 / 3 / 1 launches per step at heads 0 / 1 / 2, one more (k_eval_init) when resume == 0.  Heads 0 and 1 have
+ * the bits of mobody_mlp3_forward (out_mode 1; the slice [:, :A] at head 1), mobody_task_step under the carried mask and the
+ * accounting.  A captured chunk replays with resume = 1.  MOBODY_E_ARG before the first runtime call, the field named: what
+ * mobody_task_step refuses of the task, head outside {0, 1, 2}, ctrl outside {0, 1} (head 2), 2 A > 128 (head 1), resume, discount
+ * outside (0, 1], H < 0, precision (an unknown id, or any id but f32 without policy_blob_T), any null pointer.  B == 0 returns 0.
+ * workspace: mobody_task_evaluate_workspace(a) floats = round4(B A) + (head 1: round4(2 B A)); -1 for a bad block. */
+struct MobodyTaskEval {
+  int32_t struct_bytes, precision;
+  MobodyTaskParams p;
+  const float *policy_blob, *policy_blob_T;
+  const float* init_obs;            /* [B][S]; read only when resume == 0 */
+  int64_t B;
+  int32_t H, head;
+  int32_t ctrl, resume;
+  float ctrl_push, ctrl_eps;
+  uint32_t seed, call0;
+  const int64_t* call_dev;          /* nullable */
+  float discount, reserved;
+  float* obs_state;                 /* [B][S] */
+  uint8_t* alive;                   /* [B] */
+  float *ret, *pen_sum, *disc;      /* [B] each */
+  int32_t* length;                  /* [B] */
+  float* workspace;
+};
+typedef struct MobodyTaskEval MobodyTaskEval;
+int64_t mobody_task_evaluate_workspace(const MobodyTaskEval* a);
+int mobody_task_evaluate(const MobodyTaskEval* a, void* stream);
+
+/* mobody_task_collect: a dataset from `lanes` parallel lanes, each stepped L times by a built-in controller; one launch per step
+ * (k_task_collect: controller, advance, record, reset) after one that sets the lanes' first start states.  Step t of lane b writes
+ * row b L + t of observations [lanes L][S], actions [lanes L][A], next_observations, rewards [lanes L] and terminals (uint8).  A lane
+ * restarts after a terminal step (terminals = 1) and after its time_limit-th step of an episode (terminals = 0 unless the predicate
+ * holds too).  The e-th start state of lane b is mu + init_std * element b S + i of the unit-normal stream (seed,
+ * MOBODY_TASK_STREAM_START, e).  Lane b < split runs controller 0 of (ctrl, ctrl_push, ctrl_eps), the others controller 1.  Step t
+ * draws at call id call0 + t.  MOBODY_E_ARG before the first runtime call, the field named: what mobody_task_step refuses of the
+ * task, lanes < 0, L < 0, time_limit < 1, split outside [0, lanes], ctrl outside {0, 1}, any null pointer.  lanes == 0 or L == 0
+ * returns 0.  workspace: mobody_task_collect_workspace(a) floats = round4(lanes S) + 2 round4(lanes). */
+struct MobodyTaskCollect {
+  int32_t struct_bytes, reserved;
+  MobodyTaskParams p;
+  int64_t lanes, split;
+  int32_t L, time_limit;
+  int32_t ctrl[2];
+  float ctrl_push[2], ctrl_eps[2];
+  float init_std;
+  uint32_t seed, call0, reserved1;
+  float *observations, *actions, *next_observations, *rewards;
+  uint8_t* terminals;
+  float* workspace;
+};
+typedef struct MobodyTaskCollect MobodyTaskCollect;
+int64_t mobody_task_collect_workspace(const MobodyTaskCollect* a);
+int mobody_task_collect(const MobodyTaskCollect* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

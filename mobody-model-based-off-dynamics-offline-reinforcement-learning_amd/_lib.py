@@ -233,6 +233,31 @@ class MobodyFqeValue(C.Structure):
                 ("reserved1", i32), ("q_out", vp), ("out", vp), ("nan_flag", vp), ("workspace", vp)]
 
 
+class MobodyTaskParams(C.Structure):
+    _fields_ = [("S", i32), ("A", i32), ("task", i32), ("reserved", i32), ("mu", vp), ("gain", vp), ("bmat", vp), ("f", f32),
+                ("grav", f32), ("dt", f32), ("g", f32), ("c", f32), ("lam", f32), ("k", f32), ("h", f32), ("sigma", f32),
+                ("alive_bonus", f32), ("ctrl_cost", f32), ("max_action", f32)]
+
+
+class MobodyTaskStep(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("reserved", i32), ("p", MobodyTaskParams), ("obs", vp), ("act", vp), ("B", i64), ("noise", vp),
+                ("alive", vp), ("seed", u32), ("call", u32), ("call_dev", vp), ("next_obs", vp), ("reward", vp), ("terminal", vp)]
+
+
+class MobodyTaskEval(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("p", MobodyTaskParams), ("policy_blob", vp), ("policy_blob_T", vp),
+                ("init_obs", vp), ("B", i64), ("H", i32), ("head", i32), ("ctrl", i32), ("resume", i32), ("ctrl_push", f32),
+                ("ctrl_eps", f32), ("seed", u32), ("call0", u32), ("call_dev", vp), ("discount", f32), ("reserved", f32),
+                ("obs_state", vp), ("alive", vp), ("ret", vp), ("pen_sum", vp), ("disc", vp), ("length", vp), ("workspace", vp)]
+
+
+class MobodyTaskCollect(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("reserved", i32), ("p", MobodyTaskParams), ("lanes", i64), ("split", i64), ("L", i32),
+                ("time_limit", i32), ("ctrl", i32 * 2), ("ctrl_push", f32 * 2), ("ctrl_eps", f32 * 2), ("init_std", f32), ("seed", u32),
+                ("call0", u32), ("reserved1", u32), ("observations", vp), ("actions", vp), ("next_observations", vp), ("rewards", vp),
+                ("terminals", vp), ("workspace", vp)]
+
+
 WIDE_OUT_MODES = {"raw": 0, "tanh": 1}
 BOSA_KINDS = {"policy": 0, "dynamics": 1}
 BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9, "target_noise": 10}    # MOBODY_BOSA_STREAM_*
@@ -245,7 +270,8 @@ def block(cls, **fields):
 
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
                                              MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyBosaTarget, MobodyBosaStage2, MobodyEnsStep, MobodyEnsRollout,
-                                             MobodyEnsEval, MobodyEnsEvalPolicy, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue)}
+                                             MobodyEnsEval, MobodyEnsEvalPolicy, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue,
+                                             MobodyTaskStep, MobodyTaskEval, MobodyTaskCollect)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -287,6 +313,11 @@ PROTOTYPES = {
     "mobody_ens_evaluate_policy_workspace": (i64, [C.POINTER(MobodyEnsEvalPolicy)]),
     "mobody_ens_evaluate_policy": (C.c_int, [C.POINTER(MobodyEnsEvalPolicy), vp]),
     "mobody_eval_summary": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, vp, vp, vp]),
+    "mobody_task_step": (C.c_int, [C.POINTER(MobodyTaskStep), vp]),
+    "mobody_task_evaluate_workspace": (i64, [C.POINTER(MobodyTaskEval)]),
+    "mobody_task_evaluate": (C.c_int, [C.POINTER(MobodyTaskEval), vp]),
+    "mobody_task_collect_workspace": (i64, [C.POINTER(MobodyTaskCollect)]),
+    "mobody_task_collect": (C.c_int, [C.POINTER(MobodyTaskCollect), vp]),
     "mobody_ens_replay_workspace": (i64, [C.POINTER(MobodyEnsReplay)]),
     "mobody_ens_replay": (C.c_int, [C.POINTER(MobodyEnsReplay), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),

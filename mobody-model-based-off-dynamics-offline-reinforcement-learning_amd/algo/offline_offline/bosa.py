@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from ... import _lib, dp, ops, packing
-from .mobody import REFRESH_EVERY, _Adam, _PackedNet, evaluate_in_model, refuse_missing_keys
+from .mobody import REFRESH_EVERY, _Adam, _PackedNet, evaluate_in_model, evaluate_in_task, refuse_missing_keys
 
 _KEYS = ("vae_policy_lr", "vae_policy_hidden_dim", "vae_policy_beta", "vae_dyna_lr", "vae_dyna_ensemble", "vae_dyna_hidden_dim",
          "vae_dyna_beta", "vae_iteration", "lamda_policy", "lamda_dyna", "epsilon_policy_exp", "epsilon_dyna_exp", "conservation_coef",
@@ -290,6 +290,7 @@ class BOSA(object):
         return self.actor, 0
 
     evaluate_in_model = evaluate_in_model          # the six classes' one method (mobody.py)
+    evaluate_in_task = evaluate_in_task
 
     def _seed_for(self, k):
         return (self.seed + k + dp.rank_salt()) & 0xFFFFFFFF

@@ -247,6 +247,13 @@ def evaluate_in_model(self, init_obs, horizon, **kw):
     return self.dynamics.evaluate_policy(net, init_obs, horizon, head=head, **kw)
 
 
+def evaluate_in_task(self, task, episodes, horizon, **kw):
+    """TRUE return of the current policy in the analytic control task `task` (mobody_amd.task.Task.evaluate): the one method of
+    all six algorithm classes, over `self.eval_policy()` as evaluate_in_model is.  Reads the policy only: no training state moves."""
+    net, head = self.eval_policy()
+    return task.evaluate(net, head, episodes, horizon, **kw)
+
+
 class MOBODY(object):
     def __init__(self, config, device, target_entropy=None):
         self.config = config
@@ -453,6 +460,7 @@ class MOBODY(object):
         return res, {"num_transitions": n_tr, "reward_mean": rew_mean}
 
     evaluate_in_model = evaluate_in_model
+    evaluate_in_task = evaluate_in_task
 
     def open_loop_error(self, buffer, row0, horizon, **kw):
         """Open-loop error of the learned model over recorded windows of `buffer` (MOBODYEnsembleDynamics.open_loop_error).

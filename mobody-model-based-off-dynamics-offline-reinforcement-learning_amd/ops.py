@@ -1209,3 +1209,69 @@ def fqe_value_workspace(blk, device):
 def fqe_value(blk):
     """out = (mean q0, mean q1, mean 0.5 (q0 + q1), max |q0 - q1|) of Q(s0, pi(s0)) over the block's start states."""
     check(load().mobody_fqe_value(C.byref(blk), cur_stream()), "mobody_fqe_value")
+
+
+# ------------------------------------------------------------------------------------------------
+# the analytic control task (mobody_amd/task.py; csrc/task.hip)
+# ------------------------------------------------------------------------------------------------
+TASK_CONSTANTS = ("f", "grav", "dt", "g", "c", "lam", "k", "h", "sigma", "alive_bonus", "ctrl_cost", "max_action")
+
+
+def task_params(S, A, task_id, mu, gain, bmat, **constants):
+    """MobodyTaskParams of device tables mu [S], gain [A], bmat [S][A] and the twelve constants by name (TASK_CONSTANTS)."""
+    assert set(constants) == set(TASK_CONSTANTS), set(constants) ^ set(TASK_CONSTANTS)
+    for t, n in ((mu, S), (gain, A), (bmat, S * A)):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n
+    return _lib.MobodyTaskParams(S=S, A=A, task=task_id, mu=ptr(mu), gain=ptr(gain), bmat=ptr(bmat),
+                                 **{k: float(v) for k, v in constants.items()})
+
+
+def task_step(p, obs, act, noise=None, alive=None, seed=0, call=0, call_dev=None, out=None):
+    """One step of the task `p` on B rows (mobody_task_step).  Returns dict(next_obs [B,S], reward [B], terminal uint8 [B]);
+    `out` may hand in those tensors (next_obs may be `obs`)."""
+    obs, act = _f32(obs), _f32(act)
+    dev, B = obs.device, obs.shape[0]
+    assert obs.shape == (B, p.S) and act.shape == (B, p.A)
+    if noise is not None:
+        noise = _f32(noise, dev)
+        assert noise.shape == (B, p.S)
+    o = out or {}
+    nxt = o["next_obs"] if "next_obs" in o else torch.empty(B, p.S, dtype=torch.float32, device=dev)
+    rew = o["reward"] if "reward" in o else torch.empty(B, dtype=torch.float32, device=dev)
+    term = o["terminal"] if "terminal" in o else torch.empty(B, dtype=torch.uint8, device=dev)
+    a = _lib.block(_lib.MobodyTaskStep, p=p, obs=ptr(obs), act=ptr(act), B=B, noise=ptr(noise), alive=ptr(alive), seed=seed,
+                   call=call & 0xFFFFFFFF, call_dev=ptr(call_dev), next_obs=ptr(nxt), reward=ptr(rew), terminal=ptr(term))
+    check(load().mobody_task_step(C.byref(a), cur_stream()), "mobody_task_step")
+    return dict(next_obs=nxt, reward=rew, terminal=term)
+
+
+def task_evaluate(p, policy_blob, head, init_obs, H, seed, call0, state, discount=1.0, resume=False, ws=None, policy_blob_T=None,
+                  precision=0, call_dev=None, ctrl=1, ctrl_push=0.0, ctrl_eps=0.0):
+    """H steps of the policy in the task `p` on the row state `state` (eval_state; mobody_task_evaluate).  head 0 / 1: the two
+    policy forms; head 2: the built-in controller (ctrl, ctrl_push, ctrl_eps; policy_blob may be None).  Returns the workspace."""
+    B = state["obs_state"].shape[0]
+    if init_obs is not None:
+        init_obs = _f32(init_obs)
+        assert init_obs.shape == (B, p.S)
+    a = _lib.block(_lib.MobodyTaskEval, precision=prec_id(precision), p=p, policy_blob=ptr(policy_blob), policy_blob_T=ptr(policy_blob_T),
+                   init_obs=ptr(init_obs), B=B, H=int(H), head=int(head), ctrl=int(ctrl), resume=int(bool(resume)),
+                   ctrl_push=float(ctrl_push), ctrl_eps=float(ctrl_eps), seed=seed, call0=call0 & 0xFFFFFFFF, call_dev=ptr(call_dev),
+                   discount=float(discount), obs_state=ptr(state["obs_state"]), alive=ptr(state["alive"]), ret=ptr(state["ret"]),
+                   pen_sum=ptr(state["pen_sum"]), disc=ptr(state["disc"]), length=ptr(state["length"]))
+    return _run_with_workspace("mobody_task_evaluate", a, ws, state["obs_state"].device)
+
+
+def task_collect(p, lanes, L, time_limit, ctrl, ctrl_push, ctrl_eps, split, init_std, seed, call0=0, ws=None):
+    """`lanes` lanes of L steps each under the built-in controllers (mobody_task_collect): ctrl / ctrl_push / ctrl_eps are pairs,
+    lane b < split runs the first.  Returns device tensors observations [lanes L, S], actions, next_observations, rewards
+    [lanes L], terminals uint8 [lanes L]; row b L + t is step t of lane b."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n, f = int(lanes) * int(L), dict(dtype=torch.float32, device=dev)
+    out = dict(observations=torch.empty(n, p.S, **f), actions=torch.empty(n, p.A, **f), next_observations=torch.empty(n, p.S, **f),
+               rewards=torch.empty(n, **f), terminals=torch.empty(n, dtype=torch.uint8, device=dev))
+    a = _lib.block(_lib.MobodyTaskCollect, p=p, lanes=int(lanes), split=int(split), L=int(L), time_limit=int(time_limit),
+                   ctrl=(C.c_int32 * 2)(*[int(c) for c in ctrl]), ctrl_push=(C.c_float * 2)(*[float(x) for x in ctrl_push]),
+                   ctrl_eps=(C.c_float * 2)(*[float(x) for x in ctrl_eps]), init_std=float(init_std), seed=seed, call0=call0 & 0xFFFFFFFF,
+                   **{k: ptr(v) for k, v in out.items()})
+    _run_with_workspace("mobody_task_collect", a, ws, dev)
+    return out

@@ -16,7 +16,11 @@ ODRL target file: .npz of its raw arrays, or the .hdf5 itself when h5py is impor
 dynamics follows the reference's load-or-train branches (`build_dynamics`, train_mobody.py:817-877): load
 `--dynamics_path` / the default `pretrained_dynamics/<env>/srcdatatype-...` tree when present and `--train_dynamics 0`,
 otherwise `MOBODYEnsembleDynamics.train` on the two buffers, then save in the reference's directory scheme.  A random
-"alive" ensemble is kept only under an explicit `--synthetic 1` with nothing to load.
+"alive" ensemble is kept only under an explicit `--synthetic 1` with nothing to load.  `--synthetic 2` is the analytic
+off-dynamics control task (mobody_amd/task.py): both buffers are filled with episodes collected in the task's source
+and shifted target domain (`--srctype` / `--tartype`: random, medium, expert, medium-expert), the dynamics takes the ordinary
+load-or-train branches, and at every `eval_freq` the policy is rolled through the TRUE task and the reference's own scalars
+`test/source return` / `test/target return` are written.
 
 Several GPUs: started once per GPU (`python -m mobody_amd.dp --gpus N -- <arguments>`, or `python -m torch.distributed.run
 --nproc-per-node N train_mobody.py <arguments>`) every process becomes one data-parallel rank (`dp.init_from_env`): same
@@ -71,7 +75,7 @@ def build_parser():
         else:
             p.add_argument(flag, default=default, type=typ)
     # additions of this build (not in the reference)
-    p.add_argument("--synthetic", default=None, type=int, help="1: synthetic buffers/networks (no gym/d4rl needed)")
+    p.add_argument("--synthetic", default=None, type=int, help="1: synthetic buffers/networks (no gym/d4rl needed); 2: the analytic control task (data + true returns)")
     p.add_argument("--rng", default="numpy", choices=["numpy", "device"], help="index/elite RNG: reference NumPy stream or device Philox")
     p.add_argument("--src_rows", default=int(1e6), type=int)
     p.add_argument("--tar_rows", default=5000, type=int)
@@ -410,6 +414,12 @@ def _run(args, rank, world, device):
             raise ValueError(f"--src_data has shapes {src_ds['observations'].shape[1]}/{src_ds['actions'].shape[1]}, "
                              f"env {args.env} expects {state_dim}/{action_dim}")
     max_action = 1.0
+    task_src = task_tar = None
+    if synthetic_mode == 2:
+        # the analytic control task: an unknown shift suffix ends the run here.  Every rank builds the same data from the seed.
+        from mobody_amd.task import Task, TaskSpec
+        task_src = Task(TaskSpec.from_env(args.env, args.shift_level, "source"), device, seed=args.seed)
+        task_tar = Task(TaskSpec.from_env(args.env, args.shift_level, "target"), device, seed=args.seed)
     # the same seed on every rank: the mirror folds the rank into its device-RNG seeds (dp.rank_salt) and broadcasts rank 0's
     # replica before the first step (sync_replicas), and every rank builds the same buffers
     torch.manual_seed(args.seed); np.random.seed(args.seed); random.seed(args.seed)
@@ -432,7 +442,20 @@ def _run(args, rank, world, device):
                          f"{policy.max_train_steps()}")
     src_rb = utils.ReplayBuffer(state_dim, action_dim, device, rng=args.rng, seed=args.seed + 1)
     tar_rb = utils.ReplayBuffer(state_dim, action_dim, device, rng=args.rng, seed=args.seed + 2)
-    if synthetic_mode:
+    data_returns = None
+    if synthetic_mode == 2:
+        # lanes of 2000 steps under the data type's controller(s), the first `rows` rows kept; seeds of their own per domain
+        src_ds = task_src.collect(args.srctype, args.src_rows, seed=args.seed + 1)
+        tar_ds = task_tar.collect(args.tartype, args.tar_rows, seed=args.seed + 2)
+        src_rb.convert_D4RL(src_ds)
+        tar_rb.convert_D4RL(tar_ds)
+        data_returns = tuple(float(np.mean(np.add.reduceat(np.asarray(d["rewards"], np.float64).reshape(-1),
+                                                           episode_starts(d["observations"], d["next_observations"], d["terminals"]))))
+                             for d in (src_ds, tar_ds))
+        say(f"task data: {src_rb.size} source ({args.srctype}, mean episode return {data_returns[0]:.1f}) / {tar_rb.size} target "
+            f"({args.tartype}, {data_returns[1]:.1f}) transitions")
+        src_ds = tar_ds = None
+    elif synthetic_mode:
         synthetic.fill_buffer(src_rb, args.src_rows, task, args.seed)
         synthetic.fill_buffer(tar_rb, args.tar_rows, task, args.seed + 100)
     else:                                             # train_mobody.py:548-557: both buffers adopt their datasets
@@ -529,6 +552,18 @@ def _run(args, rank, world, device):
                   lr=float(config.get("fqe_lr", 3e-4)), tau=float(config.get("tau", 0.005)), batch_size=int(config.get("fqe_batch_size", 256)),
                   seed=args.seed, rng=args.rng)
 
+    # The true task (--synthetic 2): rank 0 evaluates alone.  The two reference points of the normalized score, the `random` and
+    # `expert` controllers' returns in the target, are measured once; the data's mean episode returns are logged once.
+    task_ref_returns = None
+    task_eval = (int(config.get("task_eval_episodes", 32)), int(config.get("task_episode_steps", 1000)))
+    if task_tar is not None and rank == 0:
+        task_ref_returns = tuple(task_tar.evaluate(None, 2, task_eval[0], task_eval[1], controller=c, rng=args.rng)["return_mean"]
+                                 for c in ("random", "expert"))
+        say(f"task reference points in the target: random {task_ref_returns[0]:.1f}, expert {task_ref_returns[1]:.1f}")
+        if writer is not None:
+            writer.add_scalar("data/source return", data_returns[0], global_step=0)
+            writer.add_scalar("data/target return", data_returns[1], global_step=0)
+
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
     if config.get("info_pretrain") and hasattr(policy, "update_info"):
@@ -590,6 +625,17 @@ def _run(args, rank, world, device):
                     writer.add_scalar("test/model return member spread", ev["return_member_spread"], global_step=t + 1)
                     for k, v in enumerate(ev["return_member_means"]):
                         writer.add_scalar(f"test/model return member e{k}", v, global_step=t + 1)
+            if writer is not None and task_ref_returns is not None:
+                # the reference's own scalars (train_mobody.py:928-975), from the true task in the simulators' place
+                ev_s = policy.evaluate_in_task(task_src, task_eval[0], task_eval[1], rng=args.rng)
+                ev_t = policy.evaluate_in_task(task_tar, task_eval[0], task_eval[1], rng=args.rng)
+                r_rand, r_exp = task_ref_returns
+                writer.add_scalar("test/source return", ev_s["return_mean"], global_step=t + 1)
+                writer.add_scalar("test/target return", ev_t["return_mean"], global_step=t + 1)
+                writer.add_scalar("test/target episode length", ev_t["length_mean"], global_step=t + 1)
+                # reference points that coincide (a shift in which the expert falls at once, a tiny task_episode_steps): NaN
+                score = 100.0 * (ev_t["return_mean"] - r_rand) / (r_exp - r_rand) if r_exp != r_rand else float("nan")
+                writer.add_scalar("test/target normalized score", score, global_step=t + 1)
             if writer is not None and fqe is not None:
                 # the discounted value at config['gamma'] of the policy as it is now, by FQE: an estimate whose bias grows with the
                 # policy's distance from the data; not a return, so no normalized score is derived from it
