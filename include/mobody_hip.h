@@ -21,6 +21,8 @@
  *   mobody_pretrain / mobody_pretrain_mopo
  *                        <- one learn() batch: zero_grad + loss.backward (+ Adam.step)   algo/dynamics/mobody_dynamics.py:594-642
  *   mobody_pretrain_*    <- MOBODYEnsembleDynamics.learn / validate  algo/dynamics/mobody_dynamics.py:300-384,594-653,1113-1140
+ *   mobody_task_interact <- select_action + env.step + ReplayBuffer.add of the online modes, in the analytic task
+ *                           train_mobody.py:675-770, iql.py:74-89,160-166, utils.py:25-41
  *   mobody_rng_*         <- torch.normal / np.random.choice / np.random.randint draws
  *                           (mobody_dynamics.py:220, mobody_module.py:355-357, utils.py:128)
  *
@@ -1433,6 +1435,56 @@ struct MobodyTaskCollect {
 typedef struct MobodyTaskCollect MobodyTaskCollect;
 int64_t mobody_task_collect_workspace(const MobodyTaskCollect* a);
 int mobody_task_collect(const MobodyTaskCollect* a, void* stream);
+
+/* mobody_task_interact: ONE interaction of the current policy with the task on `lanes` parallel lanes, recorded straight into a
+ * replay ring (the driver's online modes 1 and 2, lines 675-770 of the reference's train_mobody.py).  Three launches, no host
+ * read, no flags, tickets or atomics:
+ *   1. the packed 3-layer forward on lane_obs, in `precision` with the net's T blob: head 0 = mobody_mlp_layout(S, A, 1), out_mode 1
+ *      (pi(s)); head 1 = mobody_mlp_layout(S, 2 A, 1), raw (mu | logstd)
+ *   2. k_task_interact (k_task's geometry: a workgroup owns 256 / S whole lanes).  With c = the interaction count count[0]:
+ *        head 0: base = pi;  head 1 (select_action(test=False) of the reference's iql.py, lines 74-89 and 160-166):
+ *                base = max_action * tanh(mu + exp(clamp(logstd, -20, 2)) * n1),  n1 = element b A + j of (seed, MOBODY_TASK_STREAM_POLICY, c)
+ *        expl != 0: a = clamp(base + (expl * max_action) * n2, -max_action, max_action), n2 = the same element of (seed,
+ *                MOBODY_TASK_STREAM_EXPLORE, c) (its mode-2 loop, lines 733-735); expl == 0: nothing is drawn and a = base
+ *        step:   mobody_task_step's arithmetic on (lane_obs, a), process noise from (seed, MOBODY_TASK_STREAM_NOISE, call0 + c)
+ *        lane:   t = lane_t + 1; stored done = predicate && t < time_limit; the episode ends when the predicate holds or
+ *                t == time_limit (the mode-1 loop, lines 684-709).  On an end done_count += 1, ret_sum += lane_ret + reward, len_sum += t,
+ *                lane_t = lane_ret = 0, lane_ep += 1 and lane_obs = mu + init_std * element b S + i of (seed,
+ *                MOBODY_TASK_STREAM_START, lane_ep) (mobody_task_collect's rule); otherwise lane_t = t, lane_ret += reward,
+ *                lane_obs = next.  The accumulators are per LANE: the host adds them in lane order when it reads them.
+ *        record: lane b writes (state, a, next, reward, not_done = 1 - done) into row (ptr + b) mod cap of `ring`, ptr = ptr_size[0],
+ *                and zeroes the padding of a row-interleaved ring's row as mobody_ring_append does.  ptr_size and count are only read.
+ *   3. k_task_commit, one thread: ptr = (ptr + lanes) mod cap, size = min(size + lanes, cap), count += 1.
+ * Every product and sum is an fp32 operation of its own in the order written; head 0 has the bits of mobody_mlp3_forward,
+ * mobody_rng_normal, mobody_task_step and mobody_ring_append composed.  A captured call replays (nothing it bakes in changes).
+ * MOBODY_E_ARG before the first runtime call, the field named: struct_bytes, what mobody_task_step refuses of the task, head outside
+ * {0, 1}, 2 A > 128 (head 1), lanes < 0, lanes > cap, time_limit < 1, expl < 0, precision (an unknown id, or any id but f32 without
+ * policy_blob_T), any null pointer (those of the view included).  lanes == 0 returns 0 and writes nothing.
+ * workspace: mobody_task_interact_workspace(a) floats = round4(lanes A) (head 1: round4(2 lanes A)); -1 for a bad block. */
+enum { MOBODY_TASK_STREAM_POLICY = 11,   /* the Gaussian policy's action sample [lanes][A], call id = the interaction count */
+       MOBODY_TASK_STREAM_EXPLORE = 12 };/* exploration noise [lanes][A], call id = the interaction count */
+struct MobodyTaskInteract {
+  int32_t struct_bytes, precision;
+  MobodyTaskParams p;
+  const float *policy_blob, *policy_blob_T;
+  int64_t lanes, cap;
+  int32_t head, time_limit;
+  float expl, init_std;
+  uint32_t seed, call0;
+  const MobodyBufferView* ring;     /* HOST struct of device pointers, `cap` rows */
+  int64_t* ptr_size;                /* device int64[2] = {ptr, size} of the ring */
+  int64_t* count;                   /* device word: interactions so far */
+  float* lane_obs;                  /* [lanes][S]: the lanes' current states */
+  int32_t *lane_t, *lane_ep;        /* [lanes]: steps into the episode, episode index */
+  float* lane_ret;                  /* [lanes]: the running episode return */
+  int32_t* done_count;              /* [lanes]: finished episodes */
+  float* ret_sum;                   /* [lanes]: sum of their returns */
+  int32_t* len_sum;                 /* [lanes]: sum of their lengths */
+  float* workspace;
+};
+typedef struct MobodyTaskInteract MobodyTaskInteract;
+int64_t mobody_task_interact_workspace(const MobodyTaskInteract* a);
+int mobody_task_interact(const MobodyTaskInteract* a, void* stream);
 
 #ifdef __cplusplus
 }

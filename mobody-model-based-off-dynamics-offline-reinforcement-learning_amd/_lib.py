@@ -263,6 +263,14 @@ BOSA_KINDS = {"policy": 0, "dynamics": 1}
 BOSA_STREAMS = {"policy": 6, "dynamics": 7, "policy_ll": 8, "dynamics_ll": 9, "target_noise": 10}    # MOBODY_BOSA_STREAM_*
 
 
+class MobodyTaskInteract(C.Structure):
+    _fields_ = [("struct_bytes", i32), ("precision", i32), ("p", MobodyTaskParams), ("policy_blob", vp), ("policy_blob_T", vp),
+                ("lanes", i64), ("cap", i64), ("head", i32), ("time_limit", i32), ("expl", f32), ("init_std", f32), ("seed", u32),
+                ("call0", u32), ("ring", C.POINTER(MobodyBufferView)), ("ptr_size", vp), ("count", vp), ("lane_obs", vp),
+                ("lane_t", vp), ("lane_ep", vp), ("lane_ret", vp), ("done_count", vp), ("ret_sum", vp), ("len_sum", vp),
+                ("workspace", vp)]
+
+
 def block(cls, **fields):
     """An argument block with struct_bytes set and `fields` by name (everything else zero / NULL)."""
     return cls(struct_bytes=BLOCK_BYTES[cls], **fields)
@@ -271,7 +279,7 @@ def block(cls, **fields):
 BLOCK_BYTES = {cls: C.sizeof(cls) for cls in (MobodyCritic, MobodyActor, MobodyIql, MobodyDara, MobodyIgdf, MobodyAdam, MobodyPretrain, MobodyPretrainMopo,
                                              MobodyWideFwd, MobodyWideBwd, MobodyWideAdam, MobodyBosaVae, MobodyBosaTarget, MobodyBosaStage2, MobodyEnsStep, MobodyEnsRollout,
                                              MobodyEnsEval, MobodyEnsEvalPolicy, MobodyEnsReplay, MobodyFqeTarget, MobodyFqeValue,
-                                             MobodyTaskStep, MobodyTaskEval, MobodyTaskCollect)}
+                                             MobodyTaskStep, MobodyTaskEval, MobodyTaskCollect, MobodyTaskInteract)}
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x2": 2, "bf16x3": 3, "f16x2": 4}
@@ -318,6 +326,8 @@ PROTOTYPES = {
     "mobody_task_evaluate": (C.c_int, [C.POINTER(MobodyTaskEval), vp]),
     "mobody_task_collect_workspace": (i64, [C.POINTER(MobodyTaskCollect)]),
     "mobody_task_collect": (C.c_int, [C.POINTER(MobodyTaskCollect), vp]),
+    "mobody_task_interact_workspace": (i64, [C.POINTER(MobodyTaskInteract)]),
+    "mobody_task_interact": (C.c_int, [C.POINTER(MobodyTaskInteract), vp]),
     "mobody_ens_replay_workspace": (i64, [C.POINTER(MobodyEnsReplay)]),
     "mobody_ens_replay": (C.c_int, [C.POINTER(MobodyEnsReplay), vp]),
     "mobody_rollout_workspace": (i64, [C.c_int, C.c_int, i64]),

@@ -22,9 +22,9 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=True):
-    # fqe.hip is linked after the others, trajectory_summary.hip after fqe.hip, task.hip after that: every older kernel's code
-    # object keeps its place and its bytes (tools/isa_diff.py)
-    last = {"fqe.hip": 1, "trajectory_summary.hip": 2, "task.hip": 3}
+    # fqe.hip is linked after the others, trajectory_summary.hip after fqe.hip, task.hip after that, task_online.hip last: every
+    # older kernel's code object keeps its place and its bytes (tools/isa_diff.py)
+    last = {"fqe.hip": 1, "trajectory_summary.hip": 2, "task.hip": 3, "task_online.hip": 4}
     srcs = sorted(glob.glob(os.path.join(HERE, "*.hip")), key=lambda s: (last.get(os.path.basename(s), 0), s))
     hdrs = sorted(glob.glob(os.path.join(HERE, "*.h"))) + [os.path.join(HERE, "..", "..", "include", "mobody_hip.h")]
     objdir = os.path.join(HERE, "build")

@@ -1275,3 +1275,26 @@ def task_collect(p, lanes, L, time_limit, ctrl, ctrl_push, ctrl_eps, split, init
                    **{k: ptr(v) for k, v in out.items()})
     _run_with_workspace("mobody_task_collect", a, ws, dev)
     return out
+
+
+def online_state(lanes, S, device):
+    """The lanes' state and counters of mobody_task_interact, all zero: lane_obs [lanes, S], lane_t / lane_ep / done_count / len_sum
+    int32 [lanes], lane_ret / ret_sum [lanes] and the interaction count word (int64 [1])."""
+    f, i = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+    return dict(lane_obs=torch.zeros(lanes, S, **f), lane_t=torch.zeros(lanes, **i), lane_ep=torch.zeros(lanes, **i),
+                lane_ret=torch.zeros(lanes, **f), done_count=torch.zeros(lanes, **i), ret_sum=torch.zeros(lanes, **f),
+                len_sum=torch.zeros(lanes, **i), count=torch.zeros(1, dtype=torch.int64, device=device))
+
+
+def task_interact(p, policy_blob, head, ring, cap, ptr_size, state, time_limit, expl, init_std, seed, call0=0, ws=None,
+                  policy_blob_T=None, precision=0):
+    """One interaction of the policy with the task `p` on the lanes of `state` (online_state), recorded into `ring` (a RingView or
+    the 5-tuple of ring tensors) of `cap` rows at the device words ptr_size (mobody_task_interact: 3 launches, no host read).
+    Returns the workspace."""
+    lanes = state["lane_obs"].shape[0]
+    view = buffer_view(ring)
+    a = _lib.block(_lib.MobodyTaskInteract, precision=prec_id(precision), p=p, policy_blob=ptr(policy_blob), policy_blob_T=ptr(policy_blob_T),
+                   lanes=lanes, cap=int(cap), head=int(head), time_limit=int(time_limit), expl=float(expl), init_std=float(init_std),
+                   seed=seed, call0=call0 & 0xFFFFFFFF, ring=C.pointer(view), ptr_size=ptr(ptr_size),
+                   **{k: ptr(v) for k, v in state.items()})
+    return _run_with_workspace("mobody_task_interact", a, ws, state["lane_obs"].device)

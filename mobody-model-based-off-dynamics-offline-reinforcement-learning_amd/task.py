@@ -54,8 +54,8 @@ action noise of std eps_a is added (stream 5, element b A + j), then the action 
 
 `random` draws actions uniformly in [-1, 1); `medium-expert` gives the first half of the lanes to `medium`, the rest to `expert`.
 
-Isolation: evaluation and collection draw from seed ids of their own (SEED_TASK_EVAL, SEED_TASK_COLLECT, next to FQE's 111 and
-112) through the device generator; the algorithm's counters, the buffers' `_draws` and torch's generators do not move.
+Isolation: evaluation, collection and the online interaction draw from seed ids of their own (SEED_TASK_EVAL, SEED_TASK_COLLECT,
+SEED_TASK_ONLINE, next to FQE's 111 and 112) through the device generator; the algorithm's counters, the buffers' `_draws` and torch's generators do not move.
 """
 import math
 from dataclasses import dataclass
@@ -69,8 +69,8 @@ INIT_STD, TIME_LIMIT, LANE_STEPS = 0.05, 1000, 2000
 CONTROLLERS = {"medium": (0.5, 0.3), "expert": (1.0, 0.1)}        # name -> (push, eps_a)
 SHIFT_GAINS = {"easy": 0.75, "medium": 0.5, "hard": 0.25}
 KINDS = ("random", "medium", "expert", "medium-expert")
-SEED_TASK_EVAL, SEED_TASK_COLLECT = 113, 114                      # seed ids (the algorithm classes use 101-110, FQE 111 and 112)
-STREAM_NOISE, STREAM_ACTION, STREAM_START = 4, 5, 6
+SEED_TASK_EVAL, SEED_TASK_COLLECT, SEED_TASK_ONLINE = 113, 114, 115    # seed ids (the algorithm classes use 101-110, FQE 111 and 112)
+STREAM_NOISE, STREAM_ACTION, STREAM_START, STREAM_POLICY, STREAM_EXPLORE = 4, 5, 6, 11, 12
 CTRL_RANDOM, CTRL_FEEDBACK = 0, 1
 
 
@@ -182,6 +182,10 @@ class Task(object):
         ds["terminals"] = ds["terminals"].astype(bool)
         return ds
 
+    def online(self, buffer, lanes=1, time_limit=TIME_LIMIT, expl=0.0, seed=None, rng="device"):
+        """An OnlineTask: `lanes` lanes of this task whose transitions the current policy writes into `buffer`."""
+        return OnlineTask(self, buffer, lanes, time_limit, expl, seed, rng)
+
     def evaluate(self, net, head, episodes, horizon=TIME_LIMIT, discount=1.0, chunk=50, rng="device", seed=None, controller=None,
                  init_obs=None):
         """The TRUE return of a policy over `episodes` episodes of at most `horizon` steps (mobody_task_evaluate): head 0 / 1 read
@@ -264,3 +268,82 @@ class Task(object):
         w = ops.eval_summary(st, 1, out=words).cpu()[:8].tolist()      # the one host read
         out.update(return_mean=w[4], length_mean=w[5], alive_frac=w[7])
         return out
+
+
+class OnlineTask(object):
+    """The interaction of the driver's online modes (train_mobody.py:675-770) with a Task: `lanes` parallel lanes whose current
+    policy acts, whose transitions go straight into `buffer`'s ring, and whose episode statistics stay on the device until they are
+    asked for.  Owns the lanes' state, the counters and the workspace.  interact() is ONE call of mobody_task_interact (3 launches,
+    no host read); under rng == 'device' it is a captured graph replayed, with the bits of the eager call.  The buffer's host cache of
+    ptr / size advances by the kernel's arithmetic without a device read.  Draws come from seed + SEED_TASK_ONLINE through the device
+    generator: torch's and NumPy's generators and the buffers' `_draws` do not move."""
+
+    def __init__(self, task, buffer, lanes=1, time_limit=TIME_LIMIT, expl=0.0, seed=None, rng="device"):
+        from . import ops
+        lanes, time_limit, expl = int(lanes), int(time_limit), float(expl)
+        if buffer.state.shape[0] != buffer.max_size:
+            raise ValueError("online: the buffer's storage was replaced by convert_D4RL; an online buffer keeps its max_size ring")
+        if not 1 <= lanes <= buffer.max_size:
+            raise ValueError(f"online: lanes {lanes} outside [1, max_size {buffer.max_size}]")
+        if time_limit < 1 or not expl >= 0.0:
+            raise ValueError(f"online: time_limit {time_limit} must be >= 1 and expl {expl} >= 0")
+        if (buffer.state_dim, buffer.action_dim) != (task.spec.S, task.spec.A):
+            raise ValueError(f"online: the buffer holds {buffer.state_dim} / {buffer.action_dim} wide rows, the task {task.spec.S} / {task.spec.A}")
+        self.task, self.buffer, self.lanes, self.time_limit, self.expl, self.rng = task, buffer, lanes, time_limit, expl, rng
+        self.seed = task._seed(seed, SEED_TASK_ONLINE)
+        self.state = ops.online_state(lanes, task.spec.S, task.device)
+        self.state["lane_obs"].copy_(task.start_states(lanes, self.seed))
+        self.ws, self._graph = None, None
+        self.captures = self.interactions = 0
+
+    def _call(self, net, head):
+        from . import ops
+        b = self.buffer
+        self.ws = ops.task_interact(self.task.params, net.blob, head, b._fields(), b.max_size, b.ptr_size, self.state, self.time_limit,
+                                    self.expl, INIT_STD, self.seed, call0=1, ws=self.ws, policy_blob_T=net.blob_T, precision=net.precision)
+
+    def interact(self, net, head):
+        """One interaction of `net` (head 0: a one-member S -> A actor; head 1: an S -> 2A Gaussian policy, sampled) on every lane."""
+        import torch
+        head = int(head)
+        S, A = self.task.spec.S, self.task.spec.A
+        if head not in (0, 1) or net.in_dim != S or net.out_dim != (A if head == 0 else 2 * A) or net.members != 1:
+            raise ValueError(f"interact: head {head}: the policy must be a one-member {S} -> {A if head == 0 else 2 * A} net (head 0 or 1)")
+        if self.rng != "device":
+            self._call(net, head)
+        else:
+            # the key names every pointer and scalar the captured launches bake in; the lanes' state, the counters and the workspace
+            # live in self and are never replaced, and the graph holds `held` alive
+            held = [t for t in (net.blob, net.blob_T, self.buffer.store, self.buffer.ptr_size) if t is not None]
+            key = (head, net.precision) + tuple(t.data_ptr() for t in held)
+            if self._graph is None or self._graph[0] != key:
+                self._graph = None
+                self._call(net, head)                     # the first interaction runs eagerly (capturing executes nothing)
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    self._call(net, head)
+                self._graph = (key, g, held)
+                self.captures += 1
+            else:
+                self._graph[1].replay()
+        b = self.buffer                                   # k_task_commit's arithmetic on the host cache: no device read
+        b._ptr = (b._ptr + self.lanes) % b.max_size
+        b._size = min(b._size + self.lanes, b.max_size)
+        self.interactions += 1
+
+    def episode_stats(self):
+        """The one host read: dict(episodes, return_mean, length_mean) over the episodes finished since the last call (the means are
+        None when there are none); the per-lane accumulators are added in lane order and cleared."""
+        import torch
+        st = self.state
+        words = torch.stack([st["done_count"].double(), st["ret_sum"].double(), st["len_sum"].double()]).cpu().numpy()
+        n = int(words[0].sum())
+        for k in ("done_count", "ret_sum", "len_sum"):
+            st[k].zero_()
+        if n == 0:
+            return dict(episodes=0, return_mean=None, length_mean=None)
+        ret = 0.0
+        for x in words[1]:
+            ret += float(x)
+        return dict(episodes=n, return_mean=ret / n, length_mean=float(words[2].sum()) / n)

@@ -1,6 +1,8 @@
 """CLI driver -- mirror of the reference's `train_mobody.py` for mode 3 (offline-offline): `--policy MOBODY` and the model-free
 baselines `--policy TD3_BC` and `--policy IQL` (no ensemble dynamics is built, loaded or trained for them, train_mobody.py:820;
-`--max_step` is also T_max of IQL's cosine schedule).
+`--max_step` is also T_max of IQL's cosine schedule).  With `--synthetic 2` the model-free baselines also run the reference's
+online modes in the analytic task: `--mode 1` (offline source data, one target interaction every
+`tar_env_interact_interval` steps, :675-722) and `--mode 2` (online source with exploration noise, offline target, :723-770).
 
 Accepts the reference's flags with the same names, types and defaults (train_mobody.py:210-307),
 merges configuration in the same precedence (yaml <- --params JSON <- CLI-derived keys, :407-416,
@@ -375,12 +377,48 @@ def build_dynamics(args, dynamics, model, src_rb, tar_rb, writer, task, explicit
     return train_and_save(save_path)
 
 
+ONLINE_POLICIES = ("td3_bc", "iql", "dara", "igdf", "bosa")
+ONLINE_EXPL_NOISE = 0.2                               # mode 2: + np.random.normal(0, max_action * 0.2) (train_mobody.py:733-735)
+
+
+def check_mode(args, environ=None):
+    """Refuse, with a SystemExit that names the reason and before any GPU work, what the online modes (1: offline-online,
+    2: online-offline) are not built for.  Mode 3 passes untouched."""
+    if args.mode == 3:
+        return
+    if args.mode == 0:
+        raise SystemExit("--mode 0 (online-online): its SAC is not in the reference tree (call_tune_algo.py:8); nothing to mirror")
+    if args.mode not in (1, 2):
+        raise SystemExit(f"--mode {args.mode}: 1 (offline-online), 2 (online-offline) or 3 (offline-offline)")
+    if args.synthetic != 2:
+        raise SystemExit(f"--mode {args.mode} needs an environment to interact with: the analytic task, --synthetic 2 (simulators are not part of this build)")
+    if uses_model(args.policy):
+        raise SystemExit(f"--mode {args.mode} --policy {args.policy}: the reference builds the dynamics only in its mode-3 branch "
+                         "(train_mobody.py:771-877), and an online buffer holds no data to pre-train it on")
+    if args.policy.lower() not in ONLINE_POLICIES:
+        raise SystemExit(f"--mode {args.mode} --policy {args.policy}: the online modes are built for TD3_BC, IQL, DARA, IGDF and BOSA")
+    env = os.environ if environ is None else environ
+    if int(env.get("WORLD_SIZE", "1") or 1) > 1:
+        raise SystemExit(f"--mode {args.mode}: the online modes run on one GPU (a process group of more than one rank is not supported)")
+    from mobody_amd import synthetic
+    state_dim, action_dim, _ = synthetic.env_shape(args.env)
+    config = build_config(args, state_dim, action_dim, 1.0)
+    if args.policy.lower() == "bosa" and not config.get("critic_actor"):
+        raise SystemExit(f"--mode {args.mode} --policy BOSA: the actor that interacts exists only with config['critic_actor'] set")
+    if args.mode == 1:
+        bad = sorted(k for k, v in config.items() if k.startswith(("model_eval_", "model_error_", "fqe_")) and v)
+        if bad:
+            raise SystemExit(f"--mode 1: {', '.join(bad)}: these evaluators start from episode starts of target data chosen once at "
+                             "start-up, and the target buffer starts empty")
+    if int(config.get("online_lanes", 1)) < 1:
+        raise SystemExit(f"--mode {args.mode}: online_lanes {config.get('online_lanes')} must be at least 1")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if "_" in args.env:
         args.env = args.env.replace("_", "-")
-    if args.mode != 3:
-        raise NotImplementedError("only mode 3 (offline-offline, MOBODY) is built on the MI355X path")
+    check_mode(args)                                  # the refusals of the online modes come before any GPU work
     from mobody_amd import dp
     rank, world, device = dp.init_from_env()          # one data-parallel rank per process when a launcher set WORLD_SIZE
     try:
@@ -445,15 +483,18 @@ def _run(args, rank, world, device):
     data_returns = None
     if synthetic_mode == 2:
         # lanes of 2000 steps under the data type's controller(s), the first `rows` rows kept; seeds of their own per domain
-        src_ds = task_src.collect(args.srctype, args.src_rows, seed=args.seed + 1)
-        tar_ds = task_tar.collect(args.tartype, args.tar_rows, seed=args.seed + 2)
-        src_rb.convert_D4RL(src_ds)
-        tar_rb.convert_D4RL(tar_ds)
-        data_returns = tuple(float(np.mean(np.add.reduceat(np.asarray(d["rewards"], np.float64).reshape(-1),
-                                                           episode_starts(d["observations"], d["next_observations"], d["terminals"]))))
+        # (online modes: the buffer the policy fills by interacting starts EMPTY at max_size -- the target's in mode 1, the source's
+        # in mode 2 -- and nothing is collected for it)
+        src_ds = task_src.collect(args.srctype, args.src_rows, seed=args.seed + 1) if args.mode != 2 else None
+        tar_ds = task_tar.collect(args.tartype, args.tar_rows, seed=args.seed + 2) if args.mode != 1 else None
+        for rb, d in ((src_rb, src_ds), (tar_rb, tar_ds)):
+            if d is not None:
+                rb.convert_D4RL(d)
+        data_returns = tuple(None if d is None else float(np.mean(np.add.reduceat(
+            np.asarray(d["rewards"], np.float64).reshape(-1), episode_starts(d["observations"], d["next_observations"], d["terminals"]))))
                              for d in (src_ds, tar_ds))
-        say(f"task data: {src_rb.size} source ({args.srctype}, mean episode return {data_returns[0]:.1f}) / {tar_rb.size} target "
-            f"({args.tartype}, {data_returns[1]:.1f}) transitions")
+        told = ["online" if r is None else f"{k}, mean episode return {r:.1f}" for k, r in zip((args.srctype, args.tartype), data_returns)]
+        say(f"task data: {src_rb.size} source ({told[0]}) / {tar_rb.size} target ({told[1]}) transitions")
         src_ds = tar_ds = None
     elif synthetic_mode:
         synthetic.fill_buffer(src_rb, args.src_rows, task, args.seed)
@@ -561,8 +602,9 @@ def _run(args, rank, world, device):
                                  for c in ("random", "expert"))
         say(f"task reference points in the target: random {task_ref_returns[0]:.1f}, expert {task_ref_returns[1]:.1f}")
         if writer is not None:
-            writer.add_scalar("data/source return", data_returns[0], global_step=0)
-            writer.add_scalar("data/target return", data_returns[1], global_step=0)
+            for tag, r in zip(("data/source return", "data/target return"), data_returns):
+                if r is not None:
+                    writer.add_scalar(tag, r, global_step=0)
 
     if args.save_model and rank == 0:
         os.makedirs(f"{outdir}/models", exist_ok=True)
@@ -570,8 +612,23 @@ def _run(args, rank, world, device):
         # IGDF's contrastive encoders: the reference's driver never trains them (they keep their initial values); an optional key
         # of the merged config runs the class's update_info once, info_update_step steps, before the loop
         policy.update_info(src_rb, tar_rb, config["batch_size"], writer)
+    # The online modes (train_mobody.py:675-770) in the analytic task: the policy's own net acts on `online_lanes` lanes (an optional
+    # key of the merged config, default 1: the reference drives one environment) and the transition goes straight into the ring on
+    # the device (mobody_task_interact).  Mode 1: one target interaction at every t % tar_env_interact_interval == 0, no exploration
+    # noise (:683-685); mode 2: one source interaction with noise before every train call (:733-735).
+    online, online_every, online_tag = None, 1, None
+    if args.mode in (1, 2):
+        lanes = int(config.get("online_lanes", 1))
+        if args.mode == 1:
+            online = task_tar.online(tar_rb, lanes, task_eval[1], 0.0, seed=args.seed + 2, rng=args.rng)
+            online_every, online_tag = int(config["tar_env_interact_interval"]), "train/target return"
+        else:
+            online = task_src.online(src_rb, lanes, task_eval[1], ONLINE_EXPL_NOISE, seed=args.seed + 1, rng=args.rng)
+            online_tag = "train/source return"
     start = time.time()
     for t in range(int(config["max_step"])):
+        if online is not None and t % online_every == 0:
+            online.interact(*policy.eval_policy())
         policy.train(src_rb, tar_rb, config["batch_size"], writer, None)
         if (t + 1) % args.log_every == 0:
             if hasattr(policy, "log_line"):           # BOSA: the stage's own losses under their own names
@@ -636,6 +693,14 @@ def _run(args, rank, world, device):
                 # reference points that coincide (a shift in which the expert falls at once, a tiny task_episode_steps): NaN
                 score = 100.0 * (ev_t["return_mean"] - r_rand) / (r_exp - r_rand) if r_exp != r_rand else float("nan")
                 writer.add_scalar("test/target normalized score", score, global_step=t + 1)
+            if writer is not None and online is not None:
+                # the reference logs every finished episode (:700-704, :750-752), which would cost a host read per step; here the
+                # mean over the episodes finished since the previous evaluation, nothing when there are none
+                es = online.episode_stats()
+                if es["episodes"] > 0:
+                    writer.add_scalar(online_tag, es["return_mean"], global_step=t + 1)
+                    writer.add_scalar("train/episodes", es["episodes"], global_step=t + 1)
+                    writer.add_scalar("train/episode length", es["length_mean"], global_step=t + 1)
             if writer is not None and fqe is not None:
                 # the discounted value at config['gamma'] of the policy as it is now, by FQE: an estimate whose bias grows with the
                 # policy's distance from the data; not a return, so no normalized score is derived from it
